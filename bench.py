@@ -1,9 +1,14 @@
 #!/usr/bin/env python3
 """Headline benchmark: Go-ICP branch-and-bound on the bunny-shaped cloud (BASELINE.json configs[1]).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run measures the headline leg alone: set-up, W warm-up steps, K timed steps, the JSON line.  --full adds every other
+leg below, the headline's comparison run with the early exit off and the per-kernel figures ("roofline", which needs HIP events
+around the bounds kernel in the timed steps).  --dump-outputs DIR writes the headline's results of its last timed step (R, t,
+best_sse; float32 .npy) for output-for-output comparisons between builds.
 
 One "step" = one complete FastGoICP::run() (initial ICP, outer SO(3) x inner R^3 branch-and-bound to
 the global optimum, final ICP refine — the span the reference's CLI times, src/main.cpp:50-53) on a
@@ -18,10 +23,10 @@ optimum's residual (3.4), so the first good ICP ends the search and the step mea
 the branch-and-bound.  The reference's own example (test/bunny.toml: ~3k source points, ns*mse ~ 3,
 below the residual of the shipped clouds) is in the opposite regime: the search has to CERTIFY the
 optimum.  The headline step therefore uses mse_threshold = 5e-5 (ns*mse = 2.0 < residual), same
-clouds, same LUT, same optimum — ~100x more branch-and-bound work — and the default-threshold run is
-reported next to it ("default_threshold_*" keys and "reference_default_threshold").
+clouds, same LUT, same optimum — ~100x more branch-and-bound work — and with --full the default-threshold
+run is reported next to it ("default_threshold_*" keys and "reference_default_threshold").
 
-Legs (every one is a full run() on its own workload; --only LEG runs one alone, e.g. under rocprofv3):
+Legs (every one is a full run() on its own workload; all but the headline with --full only; --only LEG runs one alone, e.g. under rocprofv3):
   headline            bunny shape, mse 5e-5, schedule ROUND (adaptive width), K timed steps
   default_threshold   same clouds, mse 1e-3 (BASELINE.md's parameters)
   serial              same clouds, mse 5e-5, the reference's exploration order (SERIAL schedule), one step
@@ -64,10 +69,15 @@ def parse():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="bunny", choices=["bunny", "dragon", "small", "tiny"])
     ap.add_argument("--lut-resolution", type=float, default=0.005)
-    ap.add_argument("--mse-threshold", type=float, default=5e-5, help="headline threshold (see module docstring); the reference default 1e-3 is measured as well")
+    ap.add_argument("--mse-threshold", type=float, default=5e-5, help="headline threshold (see module docstring); with --full the reference default 1e-3 is measured as well")
     ap.add_argument("--schedule", default="round", choices=["round", "serial"])
     ap.add_argument("--round-width", type=int, default=0, help="rotation cubes popped per round (0 = adaptive)")
-    ap.add_argument("--only", default=None, choices=LEGS, help="run ONE leg (profiling); the headline keys then describe that leg")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, run every secondary measurement: the legs after `headline` (module docstring), the headline's comparison run "
+                         "with the early exit off, and the per-kernel figures (roofline, counters) that need HIP events around the bounds kernel")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline's last step returned (R.npy, t.npy, best_sse.npy; float32) into DIR")
+    ap.add_argument("--only", default=None, choices=LEGS, help="run ONE leg of the --full run (profiling; implies --full); the headline keys then describe that leg")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-default-threshold-run", action="store_true")
     ap.add_argument("--no-full-evaluation", action="store_true", help="skip the headline's comparison run with the early exit off")
@@ -78,7 +88,13 @@ def parse():
     ap.add_argument("--cpu-seconds", type=float, default=6.0, help="time budget of the one-core operator sample of cpu_baseline")
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="N > 1 rehearsal on a one-GPU box: every rank uses device 0 and the exchange runs on gloo (timings are meaningless)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if a.dump_outputs and a.only not in (None, "headline"):
+        ap.error("--dump-outputs writes the headline's results: it cannot be combined with --only " + a.only)
+    a.full = a.full or a.only is not None
+    return a
 
 
 def rot_err_deg(R, R_gt):
@@ -167,10 +183,11 @@ class Env:
         return t.tolist(), m.tolist()
 
 
-def run_leg(env, fg, tgt, src, res, mse, sched, K, steps, warmup, trim=0.0, early_exit=True):
+def run_leg(env, fg, tgt, src, res, mse, sched, K, steps, warmup, trim=0.0, early_exit=True, profile=True):
     """W warm-up + exactly `steps` timed run()s bracketed by barrier + synchronize; wall = max over ranks, subcubes = sum.
     early_exit (the library's default): the inner BnBs hand their thresholds to the bounds operator, which stops evaluating a subcube
-    the search drops anyway (fgoicp_bounds_submit_cut; same trajectory, counters and result as evaluating everything in full)."""
+    the search drops anyway (fgoicp_bounds_submit_cut; same trajectory, counters and result as evaluating everything in full).
+    profile: HIP events around every bounds kernel of the timed steps (`prof`, what roofline() reads); off, `prof` is None."""
     t0 = time.perf_counter()
     solver = fg.FastGoICP(tgt, src, res, mse, schedule=sched, round_width=K, device=env.local_rank, trim_fraction=trim)
     env.torch.cuda.synchronize()
@@ -183,9 +200,10 @@ def run_leg(env, fg, tgt, src, res, mse, sched, K, steps, warmup, trim=0.0, earl
         reg.set_coop_split(None, None)  # N > 1: refinements replicated on every rank (see Env)
     for _ in range(warmup):
         solver.run()
-    reg.set_profile(True)  # HIP events around every bounds kernel of the timed region (~2 % of a step)
-    reg.profile(reset=True)
-    reg.cut_stats(reset=True)
+    if profile:
+        reg.set_profile(True)  # HIP events around every bounds kernel of the timed region (~2 % of a step)
+        reg.profile(reset=True)
+        reg.cut_stats(reset=True)
     sub, stats, R, t = 0, None, None, None
     env.barrier()
     t0 = time.perf_counter()
@@ -195,15 +213,17 @@ def run_leg(env, fg, tgt, src, res, mse, sched, K, steps, warmup, trim=0.0, earl
         sub += stats["trans_cubes"]
     env.barrier()
     elapsed = time.perf_counter() - t0
-    prof = reg.profile(reset=True)
-    prof["work_items_offered"], prof["work_items_not_evaluated"] = reg.cut_stats(reset=True)
-    reg.set_profile(False)
+    prof = None
+    if profile:
+        prof = reg.profile(reset=True)
+        prof["work_items_offered"], prof["work_items_not_evaluated"] = reg.cut_stats(reset=True)
+        reg.set_profile(False)
+        info = reg.info()
+        prof["chunks_per_evaluation"] = info["items_per_evaluation"]
+        prof["chunks_per_work_item"] = info["chunks_per_item_with_thresholds"] if (early_exit and not env.no_early_exit and trim == 0.0) else 1
     sums, maxes = env.sum_max([sub, elapsed])
     if stats is not None and steps > 1:  # ICP figures over all timed steps (stats() describes the last run only)
         stats = dict(stats)
-    info = reg.info()
-    prof["chunks_per_evaluation"] = info["items_per_evaluation"]
-    prof["chunks_per_work_item"] = info["chunks_per_item_with_thresholds"] if (early_exit and not env.no_early_exit and trim == 0.0) else 1
     out = dict(solver=solver, reg=reg, R=R, t=t, stats=stats, prof=prof, elapsed=maxes[1], subcubes=sums[0], subcubes_rank=sub, steps=steps, setup_s=setup_s, trim=trim,
                best_sse=float(solver.get_best_error()), ns=reg.ns, nt=reg.nt, lut_dims=list(reg.lut_dims()))
     return out
@@ -385,21 +405,30 @@ def leg_summary(leg, R_gt, t_gt, what):
             "setup_s_upload_plus_lut_build": leg["setup_s"], "lut_dims": leg["lut_dims"]}
 
 
+def dump_outputs(out_dir, leg):
+    """What FastGoICP.run() handed back in the leg's last timed step (the rotation and the translation, in the caller's frame) and the
+    incumbent's error (get_best_error()), as float32 .npy files: the inputs are seeded, so two builds can be compared output for output."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, value in (("R", leg["R"]), ("t", leg["t"]), ("best_sse", leg["best_sse"])):
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(value, dtype=np.float32))
+
+
 def main():
     a = parse()
     import fgoicp_amd as fg
     env = Env(a)
     world, rank = env.world, env.rank
-    want = lambda name: (a.only is None or a.only == name)
+    want = lambda name: (a.only is None or a.only == name) and (a.full or name == "headline")  # a plain run: the headline alone
     pmc_all, pmc_extra = {}, {}
-    try:
-        pmc_all = json.load(open(os.path.join(REPO, "profiles", "bench_pmc.json")))
-    except Exception:
-        pass
-    try:  # SQ / TA / TCP passes of the same legs (tools/pmc_extra.sh -> tools/pmc_extra_summary.py)
-        pmc_extra = json.load(open(os.path.join(REPO, "profiles", "bench_pmc_extra.json")))
-    except Exception:
-        pass
+    if a.full:
+        try:
+            pmc_all = json.load(open(os.path.join(REPO, "profiles", "bench_pmc.json")))
+        except Exception:
+            pass
+        try:  # SQ / TA / TCP passes of the same legs (tools/pmc_extra.sh -> tools/pmc_extra_summary.py)
+            pmc_extra = json.load(open(os.path.join(REPO, "profiles", "bench_pmc_extra.json")))
+        except Exception:
+            pass
 
     K = a.round_width
     sched = fg.SCHEDULE_ROUND if a.schedule == "round" else fg.SCHEDULE_SERIAL
@@ -409,7 +438,7 @@ def main():
             "data": "synthetic"}
     head = None
     if want("headline"):
-        head = run_leg(env, fg, tgt, src, a.lut_resolution, a.mse_threshold, sched, K, a.steps, a.warmup)
+        head = run_leg(env, fg, tgt, src, a.lut_resolution, a.mse_threshold, sched, K, a.steps, a.warmup, profile=a.full)
         line.update({"value": head["subcubes"] / head["elapsed"], "ms_per_step": head["elapsed"] / a.steps * 1e3,
                      "config": {"workload": f"{a.workload}-shape synthetic pair (nt={len(tgt)}, ns={len(src)}), lut_resolution={a.lut_resolution}, "
                                             f"mse_threshold={a.mse_threshold}, full FastGoICP::run() per step",
@@ -420,6 +449,9 @@ def main():
         line.update({k: s[k] for k in ("rot_cubes_rank0", "icp_runs_rank0", "rounds", "seconds_bnb_rank0", "seconds_icp_rank0", "setup_s_upload_plus_lut_build")})
         line["result"] = {"best_sse": head["best_sse"], "rotation_error_deg_vs_ground_truth": s["rotation_error_deg_vs_ground_truth"],
                           "translation_error_vs_ground_truth": s["translation_error_vs_ground_truth"]}
+        if a.dump_outputs and rank == 0:
+            dump_outputs(a.dump_outputs, head)
+    if head is not None and a.full:
         line["roofline"] = roofline(head, pmc_all.get("headline"), {})
         if a.only in (None, "headline") and not a.no_full_evaluation and world == 1:
             # the same steps with every subcube evaluated in full, as the reference evaluates them (fgoicp_solver_set_early_exit(0)): the

@@ -153,7 +153,7 @@ def test_bench_two_rank_path_rehearsal(gpu_required):
         so.bind(("127.0.0.1", 0))
         port = so.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--rehearse-on-one-gpu", "--no-dragon", "--no-trimmed"]
+           os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--rehearse-on-one-gpu", "--full", "--no-dragon", "--no-trimmed"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=REPO)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{"metric"')]

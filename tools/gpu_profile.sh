@@ -9,9 +9,9 @@ OUT=$REPO/gpurun_out/profiles
 mkdir -p $OUT
 export TMPDIR=/tmp
 if [ -z "$3" ]; then
-  (timeout -k 10 700 python bench.py > gpurun_out/${TAG}_bench_default.log 2>&1; echo "exit $?" >> gpurun_out/${TAG}_bench_default.log)
-  grep '^{"metric"' gpurun_out/${TAG}_bench_default.log > $OUT/${TAG}_bench_line.json
-  tail -2 gpurun_out/${TAG}_bench_default.log | cut -c1-300
+  (timeout -k 10 700 python bench.py --full > $OUT/${TAG}_bench_full.log 2>&1; echo "exit $?" >> $OUT/${TAG}_bench_full.log)
+  grep '^{"metric"' $OUT/${TAG}_bench_full.log > $OUT/${TAG}_bench_line.json
+  tail -2 $OUT/${TAG}_bench_full.log | cut -c1-300
 fi
 cd /tmp
 SPECS=""

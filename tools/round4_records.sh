@@ -10,9 +10,10 @@ mkdir -p gpurun_out
 case "$PART" in
   suite)     # the whole GPU suite (shipped build; the dev_knobs tests in one child process on the development build), then smoke()
     bash tools/run_gputests.sh "$TAG" ;;
-  bench)     # the line the driver records
-    timeout -k 10 900 python3 bench.py > "gpurun_out/${TAG}_bench.json" 2> "gpurun_out/${TAG}_bench.err" || { tail -20 "gpurun_out/${TAG}_bench.err"; exit 1; }
-    python3 tools/bench_pick.py < "gpurun_out/${TAG}_bench.json" ;;
+  bench)     # the line the driver records, with every leg (--full); line and stderr kept under build/
+    mkdir -p build
+    timeout -k 10 900 python3 bench.py --full > "build/${TAG}_bench.json" 2> "build/${TAG}_bench.err" || { tail -20 "build/${TAG}_bench.err"; exit 1; }
+    python3 tools/bench_pick.py < "build/${TAG}_bench.json" ;;
   profile)   # bench + rocprofv3 kernel stats + FETCH_SIZE / WRITE_SIZE passes per leg -> profiles/bench_pmc.json
     bash tools/gpu_profile.sh "$TAG" 2 ;;
   counters)  # SQ / TCP / TA passes per leg (TA counters one per pass) -> profiles/bench_pmc_extra.json via tools/pmc_extra_summary.py
