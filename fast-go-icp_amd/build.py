@@ -13,8 +13,8 @@ REPO = os.path.dirname(PKG_DIR)
 CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_DIR = os.path.join(PKG_DIR, "lib")
 DEFAULT_LIB = os.path.join(LIB_DIR, "libfgoicp_amd.so")
-DEV_LIB = os.path.join(LIB_DIR, "libfgoicp_amd_dev.so")  # the same sources with -DFGOICP_DEV_KNOBS (csrc/host/knobs.hpp): reads the A/B environment knobs, instantiates the rejected kernel variants
-LIB_PATH = os.environ.get("FGOICP_LIB") or DEFAULT_LIB  # FGOICP_LIB: another build to load (the development build, tools/ablate.sh)
+DEV_LIB = os.path.join(LIB_DIR, "libfgoicp_amd_dev.so")  # the same sources with -DFGOICP_DEV_KNOBS (csrc/host/knobs.hpp): reads the A/B environment knobs
+LIB_PATH = os.environ.get("FGOICP_LIB") or DEFAULT_LIB  # FGOICP_LIB: another build to load (e.g. the development build)
 CLI_PATH = os.path.join(LIB_DIR, "fast-go-icp")
 
 SOURCES = [

@@ -2,7 +2,8 @@
 //
 // kernComputeBounds + the two reductions (fgoicp/registration.cu:27-60, :126-140): a work item is (evaluation s, chunk c of 256 ... 2048
 // consecutive source points) = ONE wave, four points per lane and pass.  Same per-point fp32 values and the same fp64 sums, in the same
-// order, as round 3's bounds_sorted_kernel<64, 4, ...> (kept in the development build as the A/B and bit reference) — rewritten against
+// order, as round 3's bounds_sorted_kernel<64, 4, ...> (retired; NOTES.md), whose outputs on the submissions of
+// tests/test_gpu_ops.py::test_item_kernel_keeps_every_bit are kept as its bit reference in tests/golden/item_kernel_bits.npz — rewritten against
 // the instruction stream (120 -> 77 VALU instructions per point-evaluation; the launches did not get shorter for it: the texture
 // addresser / L1 path binds both the sparse and the dense leg):
 //   * everything wave-uniform is read once (rotation, sin, kind of the item: round 3 re-read `sin_half` and `fix_rot` through the scalar
@@ -136,7 +137,7 @@ __device__ __forceinline__ void item_pass(const float4* __restrict__ src, int ns
             ga[k] = *reinterpret_cast<const float4u*>(item_address<WIDE, 3>(lutp, idx));
             gb[k] = *reinterpret_cast<const float4u*>(item_address<WIDE, 3>(row1, idx));
         }
-    } else {            // yz-quads (at most 2^30 of them), the two 16-byte halves of a lookup fetched by a pair of neighbouring lanes (quad_pair_issue above)
+    } else {            // yz-quads (at most 2^30 of them), the two 16-byte halves of a lookup fetched by a pair of neighbouring lanes (swap_lane_pair above)
         QuadPairLoads qp[P];
 #pragma unroll
         for (int k = 0; k < P; ++k) {
@@ -304,7 +305,7 @@ __global__ __launch_bounds__(64) void bounds_item_kernel(const float4* __restric
         else if (gr.fix_rot) item_walk<LAYOUT, TRIM, WIDE, QUANT, 0>(src, ns, lutp, G, R, t_xy, sb.tz, gr.sin_half, trans_radius, base, chunk_pts, lane, acc, row0, row1, samp_shift);
         else item_walk<LAYOUT, TRIM, WIDE, QUANT, 1>(src, ns, lutp, G, R, t_xy, sb.tz, gr.sin_half, trans_radius, base, chunk_pts, lane, acc, row0, row1, samp_shift);
         if (TRIM) continue;
-        // the wave tree of block_sum with one wave (bounds_sorted_kernel<64, ...>: same operands, same order), lane 0 writes
+        // the wave tree of block_sum with one wave (same operands, same order), lane 0 writes
         const double r0 = wave_sum(acc[0]), r1 = wave_sum(acc[1]);
         lb_fix += r1;
         if (sb.dual) {

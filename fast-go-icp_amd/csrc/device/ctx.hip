@@ -114,18 +114,11 @@ static int tick_launch_window(fgoicp_ctx* c, fgoicp_ctx::TickSlot& sl) {
     // A small tick (the tail of a round: a few long-running tasks left, or one of many ranks) is pure latency: its bounds
     // kernel reads the descriptors straight from the pinned staging buffers and takes the items in submission order —
     // two copies and four sort launches fewer on the critical path.  Results do not depend on the item order.
-    const int um = sl.win_units > 0 ? c->unit_m : 1;
     // windows with thresholds: an item may span several chunks (fewer workgroups to dispatch for the items that end early)
-    int span = sl.win_cut ? c->cut_span : 1;
-#ifdef FGOICP_DEV_KNOBS
-    if (span > 1 && bounds_dev_variant_selected(c->d_lut_zp, c->lut_layout, c->unit_m)) span = 1;  // round 3's kernels take one chunk per item
-#endif
+    const int span = sl.win_cut ? c->cut_span : 1;
     const int per_eval = (c->nchunk1 + span - 1) / span;  // work items per evaluation
-    bool tiers = sl.win_cut && c->cut_tier_level > 0.0f;   // ... and its items in two tiers, the heavy ones first (launch_tick_sort)
-#ifdef FGOICP_DEV_KNOBS
-    if (tiers && bounds_dev_variant_selected(c->d_lut_zp, c->lut_layout, c->unit_m)) tiers = false;
-#endif
-    const size_t nitems = (size_t)(neval - sl.win_units * (um - 1)) * (size_t)per_eval;
+    const bool tiers = sl.win_cut && c->cut_tier_level > 0.0f;   // ... and its items in two tiers, the heavy ones first (launch_tick_sort)
+    const size_t nitems = (size_t)neval * (size_t)per_eval;
     const bool small = nitems <= (size_t)c->small_tick_items;
     const TickGroup* dev_groups = small ? sl.hd_groups : sl.d_groups;
     const TickSub* dev_subs = small ? sl.hd_subs : sl.d_subs;
@@ -142,12 +135,8 @@ static int tick_launch_window(fgoicp_ctx* c, fgoicp_ctx::TickSlot& sl) {
         }
         ++c->sorted_ticks;
         const int fault = c->sort_fault_tick && c->sorted_ticks == (uint64_t)c->sort_fault_tick;
-        // FGOICP_SEPARATE_CHECK=1 (development build): the permutation check as round 3's launch behind the scatter instead of inside the bounds kernel
-        static const bool separate_check = [] { const char* e = dev_env("FGOICP_SEPARATE_CHECK"); return e && std::atoi(e) != 0; }();
         launch_tick_sort(c->geom, span > 1 ? c->d_span_cen : c->d_chunk_cen, per_eval, sl.d_groups, sl.d_subs, neval, c->cell_shift, sl.d_keys, sl.d_ranks, sl.d_hist, sl.d_hist_xcd, sl.d_xoff, sl.d_block_sums, sl.d_cursor, sl.d_sorted,
-                         c->sort_xcd ? 1 : 0, c->sort_check ? 1 : 0, separate_check && c->sort_check ? sl.hd_sort_err : nullptr, fault, sl.sort_stream, sl.win_units, um,
-                         tiers ? c->d_lut : nullptr, c->cut_tier_level / (float)c->ns);
-        if (separate_check) fused_err = nullptr;
+                         c->sort_xcd ? 1 : 0, c->sort_check ? 1 : 0, fault, sl.sort_stream, tiers ? c->d_lut : nullptr, c->cut_tier_level / (float)c->ns);
         HIPCHK(hipEventRecord(sl.sorted_ev, sl.sort_stream));
         HIPCHK(hipStreamWaitEvent(sl.stream, sl.sorted_ev, 0));
     }
@@ -172,8 +161,8 @@ static int tick_launch_window(fgoicp_ctx* c, fgoicp_ctx::TickSlot& sl) {
     if (tiers && !small) cut.tier_split = sl.d_cursor + kTickTierSplit;
     static const int cut_probe = [] { const char* e = dev_env("FGOICP_CUT_PROBE"); return e ? std::atoi(e) : 0; }();  // measurement of the early exit's own cost (tools/op_bench.py)
     cut.probe = cut_probe;
-    const bool cut_on = launch_bounds_sorted(c->d_src, (int)c->ns, c->d_lut, c->d_lut_zp, c->lut_layout, c->geom, c->nchunk1, c->chunk_pts, dev_groups, dev_subs, neval, small ? nullptr : sl.d_sorted,
-                                             sl.d_partials, c->inliers ? sl.d_evals : nullptr, c->erow, c->trim_samp_shift, fused_err, cut, span, e0, e1, sl.stream, sl.win_units, um);
+    const bool cut_on = launch_bounds_sorted(c->d_src, (int)c->ns, c->d_lut_zp, c->lut_layout, c->geom, c->nchunk1, c->chunk_pts, dev_groups, dev_subs, neval, small ? nullptr : sl.d_sorted,
+                                             sl.d_partials, c->inliers ? sl.d_evals : nullptr, c->erow, c->trim_samp_shift, fused_err, cut, span, e0, e1, sl.stream);
     if (cut_on) c->cut_items_offered += (size_t)neval * c->nchunk1;  // (counted in chunks, like the skipped ones: bounds_finalize_kernel)
     // the per-subcube sums run on the slot's side stream, so the main stream holds nothing but bounds kernels back to back
     hipStream_t fin = c->finalize_on_side ? sl.sort_stream : sl.stream;
@@ -259,56 +248,6 @@ static int tick_enqueue_window(fgoicp_ctx* c, fgoicp_ctx::TickSlot& sl, int G, c
     }
     sl.win_cut = cut_above != nullptr && !c->inliers;
     for (int k = 0; k < ng; ++k) sl.h_groups[k].pad_ = 0;
-    // Sibling units (bounds_units_kernel): the eight children of a translation node carry one queue key (fgoicp.cpp:157-168), so the
-    // inner BnB pops them together and they sit next to each other here.  A run of 8 evaluations of one group, one span and one
-    // kind whose centres are the 8 corners of a cube of side 2 * span is taken as an octet (checked, not assumed) and moved to
-    // the front of the descriptor list, as 8 / unit_m units; everything else follows as one-sibling items.
-    sl.win_units = 0;
-    if (c->unit_m > 1 && neval >= 8) {
-        const int M = c->unit_m;
-        std::vector<TickSub>& tmp = sl.sub_tmp;
-        tmp.assign(sl.h_subs, sl.h_subs + neval);
-        std::vector<int>& mark = sl.unit_of;
-        mark.assign((size_t)neval, 0);
-        int nocts = 0;
-        for (int i = 0; i + 8 <= neval;) {
-            const TickSub& a = tmp[(size_t)i];
-            bool ok = c->inliers || !a.dual;   // the untrimmed kernel keeps its accumulators for single-kind, non-dual units
-            float lo[3] = {a.tx, a.ty, a.tz}, hi[3] = {a.tx, a.ty, a.tz};
-            for (int j = 1; j < 8 && ok; ++j) {
-                const TickSub& b = tmp[(size_t)(i + j)];
-                ok = b.group == a.group && b.span == a.span && b.dual == a.dual;
-                lo[0] = std::min(lo[0], b.tx); lo[1] = std::min(lo[1], b.ty); lo[2] = std::min(lo[2], b.tz);
-                hi[0] = std::max(hi[0], b.tx); hi[1] = std::max(hi[1], b.ty); hi[2] = std::max(hi[2], b.tz);
-            }
-            unsigned corners = 0;
-            for (int j = 0; j < 8 && ok; ++j) {
-                const TickSub& b = tmp[(size_t)(i + j)];
-                const float v[3] = {b.tx, b.ty, b.tz};
-                unsigned bits = 0;
-                for (int ax = 0; ax < 3; ++ax) {
-                    ok = ok && hi[ax] - lo[ax] == 2.0f * a.span && (v[ax] == lo[ax] || v[ax] == hi[ax]);
-                    bits |= (v[ax] == hi[ax] ? 1u : 0u) << ax;
-                }
-                corners |= 1u << bits;
-            }
-            if (ok && corners == 0xFFu) {
-                for (int j = 0; j < 8; ++j) mark[(size_t)(i + j)] = 1;
-                ++nocts;
-                i += 8;
-            } else {
-                ++i;
-            }
-        }
-        if (nocts > 0) {
-            int w = 0;
-            for (int i = 0; i < neval; ++i) if (mark[(size_t)i]) sl.h_subs[w++] = tmp[(size_t)i];
-            for (int i = 0; i < neval; ++i) if (!mark[(size_t)i]) sl.h_subs[w++] = tmp[(size_t)i];
-            sl.win_units = nocts * (8 / M);
-        }
-        c->unit_evals += (uint64_t)nocts * 8;
-    }
-    c->unit_total += (uint64_t)neval;
     const double t1 = g_tt.on ? now_s() : 0;
     sl.win_pos = pos;
     sl.win_rows = rows;
@@ -441,72 +380,15 @@ int ctx_bounds_collect(fgoicp_ctx* c, int slot, float* lb_out, float* ub_out) {
     return FGOICP_OK;
 }
 
-static int ctx_bounds_multi_sorted(fgoicp_ctx* c, int G, const float* R9, const float* rot_span, const int* fix_rot, const int* offsets,
-                                   const float* tn4, float* lb_out, float* ub_out, const float* cut_above) {
-    int rc = ctx_bounds_submit(c, 0, G, R9, rot_span, fix_rot, offsets, tn4, nullptr, cut_above);
-    if (rc) return rc;
-    return ctx_bounds_collect(c, 0, lb_out, ub_out);
-}
-
 // -------------------------------------------------------------------------------------------
-// Registration::compute_sse_error(RotNode&, vector<TransNode>&, bool, StreamPool&) for G groups.
+// Registration::compute_sse_error(RotNode&, vector<TransNode>&, bool, StreamPool&) for G groups: one submission on slot 0, collected at once.
 // -------------------------------------------------------------------------------------------
 int ctx_bounds_multi(fgoicp_ctx* c, int G, const float* R9, const float* rot_span, const int* fix_rot, const int* offsets,
                      const float* tn4, float* lb_out, float* ub_out, const float* cut_above) {
     HIPCHK(hipSetDevice(c->device));
-    if (c->sorted_bounds) return ctx_bounds_multi_sorted(c, G, R9, rot_span, fix_rot, offsets, tn4, lb_out, ub_out, cut_above);  // (the per-node path below ignores cut_above: exact rows)
-    if (c->inliers) { set_error("trimmed bounds need the sorted bounds path (FGOICP_BOUNDS_SORTED=0 is set)"); return FGOICP_ERR_INVALID_ARG; }
-    struct Piece { int g, pos, B; };
-    std::vector<Piece> pieces;
-    for (int g = 0; g < G; ++g)
-        for (int pos = offsets[g]; pos < offsets[g + 1]; pos += kMaxBatch) pieces.push_back({g, pos, std::min(kMaxBatch, offsets[g + 1] - pos)});
-    size_t pi = 0;
-    while (pi < pieces.size()) {
-        // one window = at most max_subcubes rows of `partials`, one finalize, one host sync
-        const int first = pieces[pi].pos;
-        int rows = 0;
-        while (pi < pieces.size() && rows + pieces[pi].B <= c->max_subcubes) {
-            const Piece& pc = pieces[pi];
-            BoundsArgs a;
-            std::memcpy(a.R, R9 + 9 * pc.g, sizeof(a.R));
-            const float half_angle = rot_span[pc.g] * kSqrt3 * kPi / 2.0f;  // registration.cu:42
-            a.sin_half = std::sin(half_angle);
-            a.fix_rot = fix_rot[pc.g] ? 1 : 0;
-            a.B = pc.B;
-            a.out_base = rows;
-            a.pad_ = 0;
-            std::memcpy(a.tn, tn4 + 4 * (size_t)pc.pos, sizeof(float) * 4 * pc.B);
-            const bool prof = c->profile;
-            if (prof) {
-                if (c->ev_used == (int)c->ev_start.size()) {
-                    HIPCHK(hipStreamSynchronize(c->stream));
-                    int rc = ctx_flush_profile(c);
-                    if (rc) return rc;
-                }
-                HIPCHK(hipEventRecord(c->ev_start[c->ev_used], c->stream));
-            }
-            launch_bounds(c->d_src, (int)c->ns, c->d_lut, c->geom, a, c->d_partials, c->nchunk, c->pts_per_thread, c->stream);
-            if (prof) {
-                HIPCHK(hipEventRecord(c->ev_stop[c->ev_used], c->stream));
-                c->ev_used++;
-                c->prof_launches++;
-                c->prof_subcubes += pc.B;
-                c->prof_evals += pc.B;
-            }
-            rows += pc.B;
-            ++pi;
-        }
-        launch_bounds_finalize(c->d_partials, c->nchunk, rows, c->hd_lb, c->hd_ub, TickCut(), c->stream);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(c->stream));
-        std::memcpy(lb_out + first, c->h_lb, sizeof(float) * rows);
-        std::memcpy(ub_out + first, c->h_ub, sizeof(float) * rows);
-        if (c->profile) {
-            int rc = ctx_flush_profile(c);
-            if (rc) return rc;
-        }
-    }
-    return FGOICP_OK;
+    int rc = ctx_bounds_submit(c, 0, G, R9, rot_span, fix_rot, offsets, tn4, nullptr, cut_above);
+    if (rc) return rc;
+    return ctx_bounds_collect(c, 0, lb_out, ub_out);
 }
 
 // ---- host-side final folds of the fused reductions (small clouds) -----------------------------------------------------------------
@@ -683,26 +565,13 @@ int ctx_procrustes_device(fgoicp_ctx* c, fgoicp_ctx::IcpLane& L, Mat3f* R_out, V
 // iteration k, so they run next to each other — both are latency chains that fill half the device at 40k points.  The pass of
 // iteration k+1 is speculative (the loop may end on the SSE of iteration k); it is drained before returning.  Same kernels,
 // same arithmetic, same order of every sum as the one-stream loop (FGOICP_ICP_OVERLAP=0).
-#ifdef FGOICP_DEV_KNOBS
-static int lane_icp_device(fgoicp_ctx* c, fgoicp_ctx::IcpLane& L, const float* R0, const float* t0, size_t max_iter, float thr, float* sse_out, float* R_out9,
-                           float* t_out3, int* iters_out);
-static int lane_icp_gated(fgoicp_ctx* c, fgoicp_ctx::IcpLane& L, const float* R0, const float* t0, size_t max_iter, float thr, float* sse_out, float* R_out9,
-                          float* t_out3, int* iters_out);
-#endif
 static int lane_icp_dual(fgoicp_ctx* c, fgoicp_ctx::IcpLane& L, const float* R0, const float* t0, size_t max_iter, float thr, float* sse_out, float* R_out9,
                          float* t_out3, int* iters_out);
 static int lane_icp(fgoicp_ctx* c, fgoicp_ctx::IcpLane& L, const float* R0, const float* t0, size_t max_iter, float thr, float* sse_out, float* R_out9, float* t_out3,
                     int* iters_out) {
-#ifdef FGOICP_DEV_KNOBS
-    if (c->icp_device && c->icp_overlap && !c->brute_force_nn && !c->inliers) return lane_icp_device(c, L, R0, t0, max_iter, thr, sse_out, R_out9, t_out3, iters_out);
-#endif
     // one walk for both scans where the device is full anyway (clouds beyond 262 144 points, trimmed runs: -3 ... -5 % of the ICP time); below
     // that the two scans of an iteration overlap on two streams and a wave carrying both query sets only lengthens the chain (40k points:
     // 51-53 -> 55-56 us per iteration) — FGOICP_ICP_DUAL = 1 / 0 forces either
-#ifdef FGOICP_DEV_KNOBS
-    if (c->icp_gated && c->icp_gate_ok && c->icp_dual_env <= 0 && c->icp_overlap && icp_fused(c) && L.sig_b && L.sig_a)
-        return lane_icp_gated(c, L, R0, t0, max_iter, thr, sse_out, R_out9, t_out3, iters_out);
-#endif
     const bool dual = c->icp_dual_env >= 0 ? c->icp_dual_env != 0 : !icp_fused(c);
     if (dual && c->icp_overlap && !c->brute_force_nn) return lane_icp_dual(c, L, R0, t0, max_iter, thr, sse_out, R_out9, t_out3, iters_out);
     HIPCHK(hipSetDevice(c->device));  // per host thread
@@ -789,91 +658,6 @@ static int lane_icp(fgoicp_ctx* c, fgoicp_ctx::IcpLane& L, const float* R0, cons
     if (iters_out) *iters_out = iters;
     return FGOICP_OK;
 }
-
-#ifdef FGOICP_DEV_KNOBS
-// The same loop advanced ON THE DEVICE (kernels.hip, icp_step_kernel): no host round trip inside the loop.  Per iteration j the
-// host enqueues, without waiting for anything,
-//   stream B:  step_j   (waits for the SSE partials of iteration j-1: loop test of :94, then SVD, compose -> state)
-//   stream A:  E_j      exact SSE of the composed (R, t) of the state on the pristine source   (scan + block sums)
-//   stream B:  P_{j+1}  correspondences of the working cloud moved by the state's (R_, t_) (+ write-back), sums, covariance
-// and paces itself by the progress word the step kernel leaves in pinned memory (`icp_ahead` iterations ahead at most).  Once a
-// step kernel has ended the loop everything enqueued behind it returns at once.  Same kernels, same sums in the same order as the
-// host loop: bit-identical (sse, R, t, iterations) (tests/test_gpu_ops.py).  Untrimmed tree path only.
-static int lane_icp_device(fgoicp_ctx* c, fgoicp_ctx::IcpLane& L, const float* R0, const float* t0, size_t max_iter, float thr, float* sse_out, float* R_out9,
-                           float* t_out3, int* iters_out) {
-    HIPCHK(hipSetDevice(c->device));
-    const int ns = (int)c->ns, nt = (int)c->nt;
-    const int nb = reduce_blocks_for(ns);
-    const int mi = (int)std::min<size_t>(max_iter, (size_t)1 << 30);
-    constexpr int kRing = fgoicp_ctx::IcpLane::kRing;
-    hipStream_t A = L.stream, B = L.icp_stream;
-    const bool seeding = c->icp_seeding;
-    uint32_t* idx[2] = {L.d_first_idx, L.d_first_idx2};
-    const float* st_f = reinterpret_cast<const float*>(L.d_icp);
-    const int* done = &L.d_icp->done;
-    volatile IcpHostResult* res = L.h_res;
-    res->done = 0;
-    res->iters_done = 0;
-    launch_icp_init(L.d_icp, R0, t0, mi, thr, L.hd_res, A);
-    HIPCHK(hipEventRecord(L.icp_ev_w, A));
-    HIPCHK(hipStreamWaitEvent(B, L.icp_ev_w, 0));
-    // P_1: the pristine source moved by (R0, t0) becomes the working cloud (icp3d.cu:85) inside the first correspondence scan
-    launch_nn_scan(c->d_src, ns, c->bvh_tgt.view(), c->d_lut, c->geom, R0, t0, 1, 1, c->d_tgt, nt, nullptr, nullptr, nullptr, idx[0], B, L.d_work);
-    launch_icp_sums(L.d_work, c->d_tgt, idx[0], ns, nt, nullptr, L.d_bp, nb, B);
-    launch_icp_cov_cen(L.d_work, c->d_tgt, idx[0], ns, nt, L.d_bp, nb, 0, L.d_cen, L.d_bp2, nb, B);
-    int cur = 0, enq = 0;
-    for (int j = 1; j <= mi; ++j) {
-        // pace: at most icp_ahead iterations ahead of the step kernels that have run.  The progress word is only a pacing hint;
-        // if it does not move for 20 ms (it always has), the host falls back to draining the stream — never a hang.
-        if (!res->done && j - res->iters_done > c->icp_ahead) {
-            const auto t_spin = std::chrono::steady_clock::now();
-            unsigned spins = 0;
-            while (!res->done && j - res->iters_done > c->icp_ahead) {
-#if defined(__x86_64__)
-                __builtin_ia32_pause();
-#endif
-                if ((++spins & 1023u) == 0 && std::chrono::steady_clock::now() - t_spin > std::chrono::milliseconds(20)) {
-                    HIPCHK(hipStreamSynchronize(B));
-                    break;
-                }
-            }
-        }
-        if (res->done) break;
-        if (j > 1) HIPCHK(hipStreamWaitEvent(B, L.ev_sse[(j - 1) % kRing], 0));
-        launch_icp_step(L.d_icp, L.d_bp2, nb, L.d_bp3, nb, L.d_cen, L.hd_res, B);
-        HIPCHK(hipEventRecord(L.ev_step[j % kRing], B));
-        const uint32_t* seed = seeding ? idx[cur] : nullptr;
-        // P_{j+1} first: it is the head of the next iteration's critical chain (scan -> sums -> covariance -> step)
-        if (j < mi) {
-            launch_nn_scan(L.d_work, ns, c->bvh_tgt.view(), c->d_lut, c->geom, nullptr, nullptr, 1, 1, c->d_tgt, nt, seed, nullptr, nullptr, idx[cur ^ 1], B, L.d_work,
-                           st_f + 12, done);
-        }
-        HIPCHK(hipStreamWaitEvent(A, L.ev_step[j % kRing], 0));
-        launch_nn_scan(c->d_src, ns, c->bvh_tgt.view(), c->d_lut, c->geom, nullptr, nullptr, 1, 0, c->d_tgt, nt, seed, nullptr, nullptr, L.d_min_bits, A, nullptr, st_f, done);
-        if (j < mi) {
-            launch_icp_sums(L.d_work, c->d_tgt, idx[cur ^ 1], ns, nt, nullptr, L.d_bp, nb, B, done);
-            launch_icp_cov_cen(L.d_work, c->d_tgt, idx[cur ^ 1], ns, nt, L.d_bp, nb, 0, L.d_cen, L.d_bp2, nb, B, done);
-            cur ^= 1;
-        }
-        launch_sum_f32_as_f64(L.d_min_bits, ns, L.d_bp3, nb, A, done);
-        HIPCHK(hipEventRecord(L.ev_sse[j % kRing], A));
-        enq = j;
-    }
-    // the deciding step: behind the last SSE (returns at once if an earlier step already ended the loop)
-    if (enq > 0) HIPCHK(hipStreamWaitEvent(B, L.ev_sse[enq % kRing], 0));
-    launch_icp_step(L.d_icp, L.d_bp2, nb, L.d_bp3, nb, L.d_cen, L.hd_res, B);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(B));
-    HIPCHK(hipStreamSynchronize(A));  // passes enqueued ahead of the decision: drained (they return at once)
-    if (!res->done) { set_error("device-resident ICP loop ended without a result"); return FGOICP_ERR_HIP; }
-    *sse_out = res->sse;
-    for (int k = 0; k < 9; ++k) R_out9[k] = res->R[k];
-    for (int k = 0; k < 3; ++k) t_out3[k] = res->t[k];
-    if (iters_out) *iters_out = res->iters;
-    return FGOICP_OK;
-}
-
-#endif  // FGOICP_DEV_KNOBS (device-resident loop)
 
 int ctx_icp(fgoicp_ctx* c, const float* R0, const float* t0, size_t max_iter, float thr, float* sse_out, float* R_out9, float* t_out3, int* iters_out) {
     return lane_icp(c, c->lanes[0], R0, t0, max_iter, thr, sse_out, R_out9, t_out3, iters_out);
@@ -1116,119 +900,6 @@ static int lane_icp_dual(fgoicp_ctx* c, fgoicp_ctx::IcpLane& L, const float* R0,
     return FGOICP_OK;
 }
 
-#ifdef FGOICP_DEV_KNOBS
-// (FGOICP_ICP_GATED=1; measured SLOWER than paying the launches — 50-53 -> 53-56 us per iteration at 40k points: the command processor's
-// wait-value poll and the two extra stream operations per iteration cost more than the launch latency they hide — so this is a knob, off by default.)
-// The two-stream loop of small clouds with the launch latency taken off the iteration's chain (round 3).  An iteration's kernels depend on the
-// host only through 24 floats (R_, t_, R, t): they are enqueued one iteration AHEAD, behind a stream wait (hipStreamWaitValue64) on a signal
-// word, and read their motion from pinned memory; when the SVD is done the host writes the motion and raises the signal — the command
-// processor releases kernels that are already queued instead of the host paying three launches (5 us each to submit, 6-8 us until the first
-// one starts) between the SVD and the scan.  Same kernels, same arithmetic as lane_icp's fused path (the scans' `rt_dev` / `done` arguments of the
-// device-resident loop are reused): bit-identical (tests).  The set enqueued behind a gate the loop never opens is released with `done` set.
-static int lane_icp_gated(fgoicp_ctx* c, fgoicp_ctx::IcpLane& L, const float* R0, const float* t0, size_t max_iter, float thr, float* sse_out, float* R_out9,
-                          float* t_out3, int* iters_out) {
-    HIPCHK(hipSetDevice(c->device));
-    const int ns = (int)c->ns, nt = (int)c->nt, nb = reduce_blocks_for(ns), groups = (ns + 63) / 64;
-    constexpr int kRing = fgoicp_ctx::IcpLane::kRing;
-    hipStream_t A = L.stream, B = L.icp_stream;
-    const bool seeding = c->icp_seeding;
-    uint32_t* idx[2] = {L.d_first_idx, L.d_first_idx2};
-    const uint64_t base = L.gate_seq;  // gate j of this run opens at base + j
-    *(volatile int*)L.h_done = 0;
-    L.sse_on_host = true;              // where the gated kernels leave their results (as the fused enqueue functions would record)
-    L.cov_on_host = true;
-    L.cov_blocks = nb;
-    HIPCHK(hipMemcpyAsync(L.d_work, c->d_src, sizeof(float4) * c->ns, hipMemcpyDeviceToDevice, A));
-    launch_transform_inplace(L.d_work, ns, R0, t0, A);  // icp3d.cu:85
-    Mat3f R = Mat3f::from(R0);
-    Vec3f t{t0[0], t0[1], t0[2]};
-    size_t iter = 0;
-    float sse = kInf, last_sse = 2.0f * kInf;
-    Mat3f last_R = Mat3f::identity();
-    Vec3f last_t{0, 0, 0};
-    int iters = 0;
-    uint64_t enq = 0;     // highest gate with kernels queued behind it
-    uint64_t opened = 0;  // highest gate raised
-    // pass j+1 and the SSE of iteration j, queued behind gate j; pass j writes idx[j & 1] and is seeded by idx[(j - 1) & 1]
-    auto enqueue_gated = [&](uint64_t j) -> int {
-        const float* rt = L.hd_rt + 24 * (j & 1);
-        const uint32_t* seed = seeding ? idx[j & 1] : nullptr;
-        enq = j;  // from here on something may be waiting behind gate j: release_all() has to raise it whatever happens below
-        HIPCHK(hipStreamWaitValue64(B, L.sig_b, base + j, hipStreamWaitValueGte, 0xFFFFFFFFFFFFFFFFull));
-        launch_nn_scan(L.d_work, ns, c->bvh_tgt.view(), c->d_lut, c->geom, nullptr, nullptr, 1, 1, c->d_tgt, nt, seed, nullptr, nullptr, idx[(j + 1) & 1], B, L.d_work, rt, L.hd_done, L.d_wsum);
-        launch_icp_cov_cen(L.d_work, c->d_tgt, idx[(j + 1) & 1], ns, nt, L.d_wsum, nb, groups, L.hd_cen, L.hd_covbp, nb, B, L.hd_done);
-        HIPCHK(hipEventRecord(L.ev_step[(j + 1) % kRing], B));
-        HIPCHK(hipStreamWaitValue64(A, L.sig_a, base + j, hipStreamWaitValueGte, 0xFFFFFFFFFFFFFFFFull));
-        launch_nn_scan(c->d_src, ns, c->bvh_tgt.view(), c->d_lut, c->geom, nullptr, nullptr, 1, 0, c->d_tgt, nt, seed, nullptr, nullptr, L.d_min_bits, A, nullptr, rt + 12, L.hd_done, L.hd_wsse);
-        HIPCHK(hipEventRecord(L.ev_sse[j % kRing], A));
-        HIPCHK(hipGetLastError());
-        return FGOICP_OK;
-    };
-    auto open_gate = [&](uint64_t j) {
-        __atomic_store_n(L.sig_b, base + j, __ATOMIC_RELEASE);
-        __atomic_store_n(L.sig_a, base + j, __ATOMIC_RELEASE);
-        opened = j;
-    };
-    int rc = FGOICP_OK;
-    if (max_iter > 0) {
-        HIPCHK(hipEventRecord(L.icp_ev_w, A));
-        HIPCHK(hipStreamWaitEvent(B, L.icp_ev_w, 0));
-        rc = procrustes_enqueue(c, L, nullptr, idx[1], L.d_sel_wide2, B);  // pass 1 (no gate: its motion is (R0, t0), applied above)
-        if (rc == FGOICP_OK) HIPCHK(hipEventRecord(L.ev_step[1 % kRing], B));
-        if (rc == FGOICP_OK && max_iter > 1) rc = enqueue_gated(1);
-    }
-    // every exit below has to leave no kernel waiting behind a closed gate
-    auto release_all = [&]() {
-        if (enq > opened) { *(volatile int*)L.h_done = 1; __atomic_thread_fence(__ATOMIC_SEQ_CST); open_gate(enq); }
-        (void)hipStreamSynchronize(B);
-        (void)hipStreamSynchronize(A);
-        L.gate_seq = base + (enq > opened ? enq : opened) + 1;
-        *(volatile uint64_t*)L.sig_b = L.gate_seq;
-        *(volatile uint64_t*)L.sig_a = L.gate_seq;
-        *(volatile int*)L.h_done = 0;
-    };
-    if (rc) { release_all(); return rc; }
-    while (iter++ < max_iter && (last_sse - sse) > thr * last_sse) {  // icp3d.cu:94
-        last_sse = sse;
-        last_R = R;
-        last_t = t;
-        if (hipEventSynchronize(L.ev_step[iter % kRing]) != hipSuccess) { release_all(); set_error("hipEventSynchronize failed in the ICP loop"); return FGOICP_ERR_HIP; }
-        Mat3f Rn;
-        Vec3f tn;
-        procrustes_finish(L, &Rn, &tn, nullptr, nullptr);
-        const float tn3[3] = {tn.x, tn.y, tn.z};
-        R = Rn * R;                                              // :101
-        t = Rn * t + tn;                                         // :102
-        const float t3[3] = {t.x, t.y, t.z};
-        if (iter < max_iter) {
-            float* slot = L.h_rt + 24 * (iter & 1);
-            std::memcpy(slot, Rn.m, 36); std::memcpy(slot + 9, tn3, 12);
-            std::memcpy(slot + 12, R.m, 36); std::memcpy(slot + 21, t3, 12);
-            open_gate(iter);                                      // pass iter+1 and SSE iter start now: they were queued an iteration ago
-            if (iter + 1 < max_iter) { rc = enqueue_gated(iter + 1); if (rc) { release_all(); return rc; } }
-        } else {  // the last iteration the loop can make: nothing was queued for it
-            launch_transform_inplace(L.d_work, ns, Rn.m, tn3, B);  // :100
-            rc = sse_enqueue(c, L, R.m, t3, seeding ? idx[iter & 1] : nullptr, A);
-            if (rc) { release_all(); return rc; }
-            HIPCHK(hipEventRecord(L.ev_sse[iter % kRing], A));
-        }
-        if (hipEventSynchronize(L.ev_sse[iter % kRing]) != hipSuccess) { release_all(); set_error("hipEventSynchronize failed in the ICP loop"); return FGOICP_ERR_HIP; }
-        sse = sse_result(c, L);
-        ++iters;
-    }
-    release_all();  // the speculative pass (and a set behind a gate the loop never opened): drained, not used
-    const bool cur_best = sse < last_sse;  // :106-107
-    *sse_out = cur_best ? sse : last_sse;
-    const Mat3f& Ro = cur_best ? R : last_R;
-    const Vec3f& to = cur_best ? t : last_t;
-    std::memcpy(R_out9, Ro.m, sizeof(Ro.m));
-    t_out3[0] = to.x; t_out3[1] = to.y; t_out3[2] = to.z;
-    if (iters_out) *iters_out = iters;
-    return FGOICP_OK;
-}
-
-#endif  // FGOICP_DEV_KNOBS (gated loop)
-
 // One ICP run on a lane of its own (lane >= 1: own scratch, own two streams — nothing of it queues on the context's main stream,
 // where the bounds kernels run): the late-joining refinement of the ROUND schedule (driver.hpp) calls this from a background
 // host thread while the main thread keeps submitting bounds ticks.  Same kernels and sums as ctx_icp.
@@ -1269,7 +940,6 @@ int ctx_icp_batch(fgoicp_ctx* c, int n, const float* R0s, const float* t0s, size
 int ctx_set_inliers(fgoicp_ctx* c, size_t k) {
     HIPCHK(hipSetDevice(c->device));
     if (k >= c->ns) k = 0;
-    if (k && !c->sorted_bounds) { set_error("trimming needs the sorted bounds path (FGOICP_BOUNDS_SORTED=0 is set)"); return FGOICP_ERR_INVALID_ARG; }
     if (c->slots[0].inflight || c->slots[1].inflight) { set_error("fgoicp_ctx_set_inliers: a bounds submission is in flight"); return FGOICP_ERR_INVALID_ARG; }
     if (k && !c->trim_ready) {
         // per-point e of one window, per slot: up to 12 GiB (a sixth of what is free): 3000 subcubes of a 1M-point cloud per
@@ -1487,7 +1157,7 @@ static int ctx_create_impl(const float* tgt_xyz, size_t nt, const float* src_xyz
         }
         if (e3 != hipSuccess) { set_error(std::string("LUT build failed: ") + hipGetErrorString(e3)); return fail(e3 == hipErrorOutOfMemory ? FGOICP_ERR_OOM : FGOICP_ERR_HIP); }
         g.idx = c->d_lut_idx;  // from here on the exact scans seed their bounds with it (kernels.hip lut_upper_bound_d2)
-        // Packed copy for the bounds kernel: 0 none, 1 z-pair (2x bytes, two rows per lookup), 2 yz-quad (4x bytes, one
+        // Packed copy for the bounds kernel: 1 z-pair (2x bytes, two rows per lookup), 2 yz-quad (4x bytes, one
         // line per lookup).  Measured: the quad wins on sparse clouds (every lane-gather its own line; +8 % at 40k
         // points), loses on dense ones (lanes share lines and the 4x footprint falls out of cache; -5 % at 437k), so it
         // is chosen by the number of source points per voxel of the LUT's projected faces.
@@ -1497,42 +1167,25 @@ static int ctx_create_impl(const float* tgt_xyz, size_t nt, const float* src_xyz
         // patch of base voxels; 21.3 instead of 16 B per node) — bounds kernel -1.1 % on the bunny shape, three A/B pairs
         const size_t apron_bytes = (size_t)((g.px + 2) / 3) * ((g.py + 1) / 2) * g.pz * 8 * sizeof(float4);
         if (layout == 2 && apron_bytes <= ((size_t)16 << 30)) layout = 4;
-        if (const char* e = dev_env("FGOICP_LUT_ZPAIR")) layout = std::atoi(e);  // tuning knob
-        const char* units_env = dev_env("FGOICP_UNITS");
-        const bool units_on = units_env && (std::atoi(units_env) == 4 || std::atoi(units_env) == 8);
-        if (layout == 3 && (g.px > 1023 || g.py > 1023 || g.pz > 1023 || c->inliers)) layout = 2;  // the bricked copy packs indices in 10 bits
-        if (layout == 4 && (g.px > 1023 || g.py > 1023 || g.pz > 1023 || units_on)) layout = 2;     // the apron copy too; no sibling-unit kernel for it
+        if (const char* e = dev_env("FGOICP_LUT_ZPAIR")) { const int v = std::atoi(e); if (v == 1 || v == 2 || v == 4) layout = v; }  // tuning knob
+        if (layout == 4 && (g.px > 1023 || g.py > 1023 || g.pz > 1023)) layout = 2;  // the apron copy packs indices in 10 bits
         c->lut_layout = layout;
         if (layout == 4) {
             const size_t lines = (size_t)((g.px + 2) / 3) * ((g.py + 1) / 2) * g.pz;
             CHK(hipMalloc(&c->d_lut_zp, lines * 8 * sizeof(float4)));
             launch_lut_quad_apron(c->d_lut, g, reinterpret_cast<float4*>(c->d_lut_zp), c->stream);
-        } else if (layout == 3) {
-            const size_t bricks = (size_t)((g.px + 3) / 4) * ((g.py + 3) / 4) * ((g.pz + 3) / 4);
-            CHK(hipMalloc(&c->d_lut_zp, bricks * 64 * sizeof(float4)));
-            launch_lut_quad_bricked(c->d_lut, g, reinterpret_cast<float4*>(c->d_lut_zp), c->stream);
         } else if (layout == 2) {
             CHK(hipMalloc(&c->d_lut_zp, total * sizeof(float4)));
             launch_lut_quad(c->d_lut, g, reinterpret_cast<float4*>(c->d_lut_zp), c->stream);
-        } else if (layout == 1) {
+        } else {
             CHK(hipMalloc(&c->d_lut_zp, total * sizeof(float2)));
             launch_lut_zpair(c->d_lut, g, c->d_lut_zp, c->stream);
         }
-        if (layout) {
-            CHK(hipGetLastError());
-            CHK(hipStreamSynchronize(c->stream));
-        }
+        CHK(hipGetLastError());
+        CHK(hipStreamSynchronize(c->stream));
     }
-    // bounds scratch: P points per thread so that one 32-subcube launch has >= ~2048 blocks
+    // bounds scratch
     {
-        int P = 8;
-        while (P > 1 && ((ns + (size_t)kBlock * P - 1) / ((size_t)kBlock * P)) * kMaxBatch < 2048) P >>= 1;
-        if (const char* e = dev_env("FGOICP_PTS_PER_THREAD")) {  // tuning knob: 1, 2, 4 or 8
-            const int v = std::atoi(e);
-            if (v == 1 || v == 2 || v == 4 || v == 8) P = v;
-        }
-        c->pts_per_thread = P;
-        c->nchunk = (int)((ns + (size_t)kBlock * P - 1) / ((size_t)kBlock * P));
         // subcubes per window: as many as 4 GiB of per-(subcube, chunk) scratch per slot hold, 4096..131072 (wide rounds submit
         // tens of thousands per tick; bigger launches sort into longer runs of items per LUT cell and re-use the L2 better)
         {
@@ -1547,7 +1200,7 @@ static int ctx_create_impl(const float* tgt_xyz, size_t nt, const float* src_xyz
                 c->chunk_pts = density >= 1.0 ? 2048 : density >= 0.5 ? 1024 : density >= 0.25 ? 512 : 256;
                 if (const char* e = dev_env("FGOICP_CHUNK_PTS")) {  // tuning knob
                     const int v = std::atoi(e);
-                    if (v == 64 || v == 128 || v == 256 || v == 512 || v == 1024 || v == 2048 || v == 4096) c->chunk_pts = v;  // 64 / 128 need FGOICP_BOUNDS_VARIANT 4 / 3
+                    if (v == 256 || v == 512 || v == 1024 || v == 2048 || v == 4096) c->chunk_pts = v;
                 }
             }
             const size_t nchunk1 = (ns + c->chunk_pts - 1) / c->chunk_pts;
@@ -1562,30 +1215,22 @@ static int ctx_create_impl(const float* tgt_xyz, size_t nt, const float* src_xyz
             }
             c->max_subcubes = (int)std::min<size_t>((size_t)c->max_subcubes, launch_fit);
         }
-        CHK(hipMalloc(&c->d_partials, sizeof(double2) * (size_t)c->max_subcubes * c->nchunk));
-        CHK(hipHostMalloc((void**)&c->h_lb, sizeof(float) * c->max_subcubes, hipHostMallocMapped));
-        CHK(hipHostMalloc((void**)&c->h_ub, sizeof(float) * c->max_subcubes, hipHostMallocMapped));
-        CHK(hipHostGetDevicePointer((void**)&c->hd_lb, c->h_lb, 0));
-        CHK(hipHostGetDevicePointer((void**)&c->hd_ub, c->h_ub, 0));
     }
     // locality-sorted whole-tick path
     {
-        if (const char* e = dev_env("FGOICP_BOUNDS_SORTED")) c->sorted_bounds = std::atoi(e) != 0;
         c->nchunk1 = (int)((ns + c->chunk_pts - 1) / c->chunk_pts);
         c->max_groups = std::max(512, c->max_subcubes / 8);
         if (const char* e = dev_env("FGOICP_FINALIZE_SIDE")) c->finalize_on_side = std::atoi(e) != 0;  // tuning knob
         if (const char* e = dev_env("FGOICP_ICP_SEED")) c->icp_seeding = std::atoi(e) != 0;             // tuning knob
         if (const char* e = dev_env("FGOICP_COOP_SPLIT_MIN")) c->coop_split_min = c->coop_split_trim_min = (size_t)std::max(0L, std::atol(e));  // tuning knob (both thresholds)
-        if (const char* e = dev_env("FGOICP_UNITS")) { const int v = std::atoi(e); c->unit_m = (v == 4 || v == 8) ? v : 0; }  // tuning knob: siblings per work item
-        if (c->lut_layout == 4) c->unit_m = 0;  // the apron layout has no sibling-unit kernel
         if (const char* e = dev_env("FGOICP_SMALL_TICK")) c->small_tick_items = std::max(0, std::atoi(e));  // tuning knob: items
         int maxd = std::max(g.dx, std::max(g.dy, g.dz));
         c->cell_shift = 0;
         while ((maxd >> c->cell_shift) > 32) ++c->cell_shift;  // 5 bits per axis
-        // [0, n): centres of the runs of `pts` consecutive points; [n, 2 n): their normals (direction of least variance)
+        // centres of the runs of `pts` consecutive points (the tick sort's keys)
         const auto run_centres = [&](size_t pts) {
             const size_t n = (ns + pts - 1) / pts;
-            std::vector<float4> cen(2 * n);
+            std::vector<float4> cen(n);
             for (size_t k = 0; k < n; ++k) {
                 double sx = 0, sy = 0, sz = 0;
                 const size_t a = k * pts, b = std::min(ns, a + pts);
@@ -1594,16 +1239,7 @@ static int ctx_create_impl(const float* tgt_xyz, size_t nt, const float* src_xyz
                     sx += p[0]; sy += p[1]; sz += p[2];
                 }
                 const double inv = 1.0 / (double)(b - a);
-                const double m[3] = {sx * inv, sy * inv, sz * inv};
-                cen[k] = make_float4((float)m[0], (float)m[1], (float)m[2], 0.f);
-                double H[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, U[3][3], S[3], V[3][3];
-                for (size_t i = a; i < b; ++i) {
-                    const float* p = src_xyz + 3 * (size_t)c->perm[i];
-                    const double d[3] = {p[0] - m[0], p[1] - m[1], p[2] - m[2]};
-                    for (int r = 0; r < 3; ++r) for (int q = 0; q < 3; ++q) H[r][q] += d[r] * d[q];
-                }
-                svd3_jacobi(H, U, S, V);  // symmetric positive semi-definite: the last column belongs to the smallest eigenvalue
-                cen[n + k] = make_float4((float)V[0][2], (float)V[1][2], (float)V[2][2], 0.f);
+                cen[k] = make_float4((float)(sx * inv), (float)(sy * inv), (float)(sz * inv), 0.f);
             }
             return cen;
         };
@@ -1674,13 +1310,10 @@ static int ctx_create_impl(const float* tgt_xyz, size_t nt, const float* src_xyz
                 CHK(hipMalloc(&c->d_cut_stat, sizeof(unsigned long long) * kCutStatSlots));
                 CHK(hipMemset(c->d_cut_stat, 0, sizeof(unsigned long long) * kCutStatSlots));
             }
-            if (k == 0) { sl.h_lb = c->h_lb; sl.h_ub = c->h_ub; sl.hd_lb = c->hd_lb; sl.hd_ub = c->hd_ub; }
-            else {
-                CHK(hipHostMalloc((void**)&sl.h_lb, sizeof(float) * c->max_subcubes, hipHostMallocMapped));
-                CHK(hipHostMalloc((void**)&sl.h_ub, sizeof(float) * c->max_subcubes, hipHostMallocMapped));
-                CHK(hipHostGetDevicePointer((void**)&sl.hd_lb, sl.h_lb, 0));
-                CHK(hipHostGetDevicePointer((void**)&sl.hd_ub, sl.h_ub, 0));
-            }
+            CHK(hipHostMalloc((void**)&sl.h_lb, sizeof(float) * c->max_subcubes, hipHostMallocMapped));
+            CHK(hipHostMalloc((void**)&sl.h_ub, sizeof(float) * c->max_subcubes, hipHostMallocMapped));
+            CHK(hipHostGetDevicePointer((void**)&sl.hd_lb, sl.h_lb, 0));
+            CHK(hipHostGetDevicePointer((void**)&sl.hd_ub, sl.h_ub, 0));
         }
     }
     // exact-NN / ICP scratch
@@ -1688,11 +1321,8 @@ static int ctx_create_impl(const float* tgt_xyz, size_t nt, const float* src_xyz
         int nl = 4;  // concurrent ICP runs (ctx_icp_batch); lane 0 shares the context's main stream
         if (const char* e = dev_env("FGOICP_ICP_LANES")) nl = std::max(1, std::min(16, std::atoi(e)));  // tuning knob
         if (const char* e = dev_env("FGOICP_ICP_OVERLAP")) c->icp_overlap = std::atoi(e) != 0;       // tuning knob
-        if (const char* e = dev_env("FGOICP_ICP_DEVICE")) c->icp_device = std::atoi(e) != 0;         // tuning knob / A-B: 1 = loop advanced on the device (measured slower)
         if (const char* e = dev_env("FGOICP_ICP_DUAL")) c->icp_dual_env = std::atoi(e) != 0 ? 1 : 0; // tuning knob / A-B: 1 = one walk for both scans of an iteration, 0 = two scans on two streams
-        if (const char* e = dev_env("FGOICP_ICP_GATED")) c->icp_gated = std::atoi(e) != 0;           // tuning knob / A-B: 1 = iterations pre-enqueued behind stream gates
         if (const char* e = dev_env("FGOICP_ICP_FUSE")) c->icp_fuse = std::atoi(e) != 0;             // tuning knob / A-B: 0 = separate reduction kernels
-        if (const char* e = dev_env("FGOICP_ICP_AHEAD")) c->icp_ahead = std::max(1, std::min(6, std::atoi(e)));  // tuning knob
         c->lanes.resize((size_t)nl);
         for (int l = 0; l < nl; ++l) {
             fgoicp_ctx::IcpLane& L = c->lanes[(size_t)l];
@@ -1719,33 +1349,6 @@ static int ctx_create_impl(const float* tgt_xyz, size_t nt, const float* src_xyz
             CHK(hipHostGetDevicePointer((void**)&L.hd_wsse, L.h_wsse, 0));
             CHK(hipHostMalloc((void**)&L.h_covbp, sizeof(double) * 1024 * 9, hipHostMallocMapped));
             CHK(hipHostGetDevicePointer((void**)&L.hd_covbp, L.h_covbp, 0));
-            CHK(hipHostMalloc((void**)&L.h_rt, sizeof(float) * 48, hipHostMallocMapped));
-            CHK(hipHostGetDevicePointer((void**)&L.hd_rt, L.h_rt, 0));
-            CHK(hipHostMalloc((void**)&L.h_done, sizeof(int) * 4, hipHostMallocMapped));
-            CHK(hipHostGetDevicePointer((void**)&L.hd_done, L.h_done, 0));
-            *L.h_done = 0;
-            // signal words for hipStreamWaitValue64; without them (or without the stream operation) the gated loop is simply not used
-            if (hipExtMallocWithFlags((void**)&L.sig_b, 8, hipMallocSignalMemory) != hipSuccess) L.sig_b = nullptr;
-            if (hipExtMallocWithFlags((void**)&L.sig_a, 8, hipMallocSignalMemory) != hipSuccess) L.sig_a = nullptr;
-            (void)hipGetLastError();
-            CHK(hipMalloc(&L.d_icp, sizeof(IcpDevState)));
-            CHK(hipHostMalloc((void**)&L.h_res, sizeof(IcpHostResult), hipHostMallocMapped));
-            CHK(hipHostGetDevicePointer((void**)&L.hd_res, L.h_res, 0));
-            for (int k = 0; k < fgoicp_ctx::IcpLane::kRing; ++k) {
-                CHK(hipEventCreateWithFlags(&L.ev_step[k], hipEventDisableTiming));
-                CHK(hipEventCreateWithFlags(&L.ev_sse[k], hipEventDisableTiming));
-            }
-        }
-    }
-    {   // probe the stream wait-value operation once: a wait that is already satisfied, on lane 0's side stream
-        fgoicp_ctx::IcpLane& L0 = c->lanes[0];
-        c->icp_gate_ok = false;
-        if (L0.sig_b && L0.sig_a) {
-            *(volatile uint64_t*)L0.sig_b = 1;
-            if (hipStreamWaitValue64(L0.icp_stream, L0.sig_b, 1, hipStreamWaitValueGte, 0xFFFFFFFFFFFFFFFFull) == hipSuccess && hipStreamSynchronize(L0.icp_stream) == hipSuccess)
-                c->icp_gate_ok = true;
-            (void)hipGetLastError();
-            for (auto& L : c->lanes) { if (L.sig_b) *(volatile uint64_t*)L.sig_b = 1; if (L.sig_a) *(volatile uint64_t*)L.sig_a = 1; L.gate_seq = 1; }
         }
     }
 #undef CHK
@@ -1768,9 +1371,6 @@ void fgoicp_ctx_destroy(fgoicp_ctx* c) {
                      1e6 * g_tt.pack / g_tt.ticks, 1e6 * g_tt.enqueue / g_tt.ticks, 1e6 * g_tt.wait / g_tt.ticks, 1e6 * g_tt.copyout / g_tt.ticks);
         g_tt = TickTiming{};
     }
-    if (c->unit_m > 1 && dev_env("FGOICP_UNITS_STATS"))
-        std::fprintf(stderr, "[fgoicp units] M = %d: %llu of %llu evaluations in sibling units (%.1f %%)\n", c->unit_m, (unsigned long long)c->unit_evals,
-                     (unsigned long long)c->unit_total, c->unit_total ? 100.0 * (double)c->unit_evals / (double)c->unit_total : 0.0);
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     for (auto& e : c->ev_start) if (e) (void)hipEventDestroy(e);
@@ -1778,26 +1378,15 @@ void fgoicp_ctx_destroy(fgoicp_ctx* c) {
     for (auto& e : c->ev_sel_start) if (e) (void)hipEventDestroy(e);
     for (auto& e : c->ev_sel_stop) if (e) (void)hipEventDestroy(e);
     (void)hipFree(c->d_src); (void)hipFree(c->d_tgt); (void)hipFree(c->d_lut); (void)hipFree(c->d_lut_idx); (void)hipFree(c->d_lut_zp);
-    (void)hipFree(c->d_partials);
     (void)hipFree(c->d_cut_stat);
     for (auto& L : c->lanes) {
         if (L.stream && L.stream != c->stream) { (void)hipStreamSynchronize(L.stream); (void)hipStreamDestroy(L.stream); }
         if (L.icp_stream) { (void)hipStreamSynchronize(L.icp_stream); (void)hipStreamDestroy(L.icp_stream); }
         if (L.icp_ev_w) (void)hipEventDestroy(L.icp_ev_w);
         if (L.icp_ev_b) (void)hipEventDestroy(L.icp_ev_b);
-        for (int k = 0; k < fgoicp_ctx::IcpLane::kRing; ++k) {
-            if (L.ev_step[k]) (void)hipEventDestroy(L.ev_step[k]);
-            if (L.ev_sse[k]) (void)hipEventDestroy(L.ev_sse[k]);
-        }
-        (void)hipFree(L.d_icp);
-        if (L.sig_b) (void)hipFree(L.sig_b);
-        if (L.sig_a) (void)hipFree(L.sig_a);
-        if (L.h_rt) (void)hipHostFree(L.h_rt);
-        if (L.h_done) (void)hipHostFree(L.h_done);
         (void)hipFree(L.d_wsum);
         if (L.h_wsse) (void)hipHostFree(L.h_wsse);
         if (L.h_covbp) (void)hipHostFree(L.h_covbp);
-        if (L.h_res) (void)hipHostFree(L.h_res);
         (void)hipFree(L.d_work); (void)hipFree(L.d_min_bits); (void)hipFree(L.d_thr_bits); (void)hipFree(L.d_first_idx); (void)hipFree(L.d_first_idx2);
         (void)hipFree(L.d_bp); (void)hipFree(L.d_bp2); (void)hipFree(L.d_bp3); (void)hipFree(L.d_cen);
         (void)hipFree(L.d_d2); (void)hipFree(L.d_nn_lb); (void)hipFree(L.d_nn_ub); (void)hipFree(L.d_nn_lb2); (void)hipFree(L.d_nn_ub2);
@@ -1825,11 +1414,9 @@ void fgoicp_ctx_destroy(fgoicp_ctx* c) {
         (void)hipFree(sl.d_cursor); (void)hipFree(sl.d_block_sums); (void)hipFree(sl.d_hist_xcd); (void)hipFree(sl.d_xoff); (void)hipFree(sl.d_sorted); (void)hipFree(sl.d_partials); (void)hipFree(sl.d_cut_acc); (void)hipFree(sl.d_row_cut); (void)hipFree(sl.d_cut_done);
         if (sl.h_groups) (void)hipHostFree(sl.h_groups);
         if (sl.h_subs) (void)hipHostFree(sl.h_subs);
-        if (k == 1 && sl.h_lb) (void)hipHostFree(sl.h_lb);
-        if (k == 1 && sl.h_ub) (void)hipHostFree(sl.h_ub);
+        if (sl.h_lb) (void)hipHostFree(sl.h_lb);
+        if (sl.h_ub) (void)hipHostFree(sl.h_ub);
     }
-    if (c->h_lb) (void)hipHostFree(c->h_lb);
-    if (c->h_ub) (void)hipHostFree(c->h_ub);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -1854,10 +1441,9 @@ int fgoicp_ctx_get_info(const fgoicp_ctx* c, fgoicp_ctx_info* out) {
     out->lut_layout = c->d_lut_zp ? c->lut_layout : 0;
     out->lut_nodes = (uint64_t)g.dx * g.dy * g.dz;
     const uint64_t padded = (uint64_t)g.px * g.py * g.pz;
-    size_t packed = 0;  // the bricked yz-quad copy (layout 3) holds whole 4 x 4 x 4 bricks of float4
+    size_t packed = 0;
     if (c->d_lut_zp) {
         if (c->lut_layout == 4) packed = (size_t)((c->geom.px + 2) / 3) * ((c->geom.py + 1) / 2) * c->geom.pz * 8 * sizeof(float4);
-        else if (c->lut_layout == 3) packed = (size_t)((c->geom.px + 3) / 4) * ((c->geom.py + 3) / 4) * ((c->geom.pz + 3) / 4) * 64 * sizeof(float4);
         else packed = padded * (c->lut_layout == 2 ? sizeof(float4) : sizeof(float2));
     }
     out->lut_bytes = padded * sizeof(float) + packed + (c->d_lut_idx ? padded * sizeof(uint32_t) : 0);  // + the index LUT of the exact scans
@@ -1939,7 +1525,6 @@ int fgoicp_bounds_submit_twins(fgoicp_ctx* c, int slot, int G, const float* R9, 
 int fgoicp_bounds_submit_cut(fgoicp_ctx* c, int slot, int G, const float* R9, const float* rot_span, const int* fix_rot, const int* offsets,
                              const float* tn4, const int* twin, const float* cut_above) {
     if (!c || slot < 0 || slot > 1 || G < 0 || (G > 0 && (!R9 || !rot_span || !fix_rot || !offsets || !tn4))) return FGOICP_ERR_INVALID_ARG;
-    if (!c->sorted_bounds) { set_error("fgoicp_bounds_submit needs the sorted bounds path (FGOICP_BOUNDS_SORTED=0 is set)"); return FGOICP_ERR_INVALID_ARG; }
     static const int zero[1] = {0};
     if (G == 0) offsets = zero;
     for (int g = 0; g < G; ++g)
@@ -1970,7 +1555,7 @@ int fgoicp_bounds_batch(fgoicp_ctx* c, const float* R9, float rot_span, const fl
 
 int fgoicp_bounds_point_distances(fgoicp_ctx* c, const float* R9, float rot_span, const float* tnode4, int fix_rot, float* e_out) {
     if (!c || !R9 || !tnode4 || !e_out) return FGOICP_ERR_INVALID_ARG;
-    if (!c->inliers || !c->sorted_bounds) { set_error("fgoicp_bounds_point_distances: trimming is off (fgoicp_ctx_set_inliers)"); return FGOICP_ERR_INVALID_ARG; }
+    if (!c->inliers) { set_error("fgoicp_bounds_point_distances: trimming is off (fgoicp_ctx_set_inliers)"); return FGOICP_ERR_INVALID_ARG; }
     const int offsets[2] = {0, 1};
     float lb = 0.f, ub = 0.f;
     int rc = ctx_bounds_submit(c, 0, 1, R9, &rot_span, &fix_rot, offsets, tnode4, nullptr);

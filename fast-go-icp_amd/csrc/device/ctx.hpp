@@ -25,7 +25,7 @@ struct fgoicp_ctx {
     float4* d_src = nullptr;     // ns  x {x,y,z,|p|^2}, Morton order (pristine source, registration.hpp:63)
     float4* d_tgt = nullptr;     // nt  x {x,y,z,0}, caller order (registration.hpp:61)
     float* d_lut = nullptr;      // (dx+2)(dy+2)(dz+2) floats, x fastest, replicated border
-    int lut_layout = 1;          // 1: d_lut_zp is the z-paired copy (float2), 2: it is the yz-quad copy (float4)
+    int lut_layout = 1;          // 1: d_lut_zp is the z-paired copy (float2), 2: the yz-quad copy (float4), 4: the apron-bricked yz-quads (float4)
     int source_order = 0, tree_order = 0;  // what ctx_create chose (fgoicp_ctx_get_info)
     uint32_t* d_lut_idx = nullptr;  // index LUT (geom.idx): per padded node the caller index of a nearest target point; seeds of the exact scans (FGOICP_LUT_INDEX=0: none)
     float2* d_lut_zp = nullptr;  // z-paired copy {T[o], T[o + z-slice]} for the bounds kernel (2x the bytes, half the gathers)
@@ -35,12 +35,9 @@ struct fgoicp_ctx {
     std::vector<uint32_t> perm;  // device slot i holds caller point perm[i]
 
     // bounds-operator scratch (persistent: the reference mallocs/frees per call, registration.cu:95-149)
-    int pts_per_thread = 1, nchunk = 0, max_subcubes = 0;
-    double2* d_partials = nullptr;           // [max_subcubes][nchunk] {sum_ub, sum_lb}
-    float *h_lb = nullptr, *h_ub = nullptr;  // pinned, device-visible result rows
-    float *hd_lb = nullptr, *hd_ub = nullptr;
+    int max_subcubes = 0;
 
-    // locality-sorted whole-tick path (kernels.hip, bounds_sorted_kernel): 256-point chunks.
+    // locality-sorted whole-tick path (kernels.hip, bounds_item.hpp): chunk_pts-point chunks.
     // Two tick slots: the host prepares / consumes one half of a round's inner BnBs while the device
     // evaluates the other (fgoicp_bounds_submit / _collect).
     struct TickSlot {
@@ -56,7 +53,7 @@ struct fgoicp_ctx {
         unsigned* d_ranks = nullptr;             // place of every item inside its key's bin (returned by the histogram atomic)
         unsigned *d_hist = nullptr, *d_block_sums = nullptr, *d_cursor = nullptr, *d_sorted = nullptr;
         unsigned *d_hist_xcd = nullptr, *d_xoff = nullptr;   // per-XCD histograms of the tick sort and their offsets inside a bin
-        double2* d_partials = nullptr;           // [max_subcubes][nchunk1]
+        double2* d_partials = nullptr;           // [max_subcubes][nchunk1] {sum_ub, sum_lb}
         double* d_cut_acc = nullptr;             // early exit (fgoicp_bounds_submit_cut): 2 running sums per evaluation, zero between windows
         float* d_row_cut = nullptr;              // ... and the threshold of every output row
         unsigned* d_cut_done = nullptr;          // ... and the cached "finished" hint per evaluation
@@ -64,11 +61,8 @@ struct fgoicp_ctx {
         float *h_lb = nullptr, *h_ub = nullptr, *hd_lb = nullptr, *hd_ub = nullptr;  // pinned results of the window in flight
         float* d_evals = nullptr;                // trimmed mode: per-point e = max(d, 0) of every output row, [vals_rows][erow]
         float *h_row_span = nullptr, *hd_row_span = nullptr;   // translation span of every output row of the window (pinned)
-        unsigned *h_sort_err = nullptr, *hd_sort_err = nullptr; // pinned: set by tick_check_kernel when `sorted` is no permutation
+        unsigned *h_sort_err = nullptr, *hd_sort_err = nullptr; // pinned: set by the bounds kernel when `sorted` is no permutation
         int win_groups = 0, win_evals = 0;       // the window in flight: groups and evaluations in the staging buffers
-        int win_units = 0;                       // ... of which the first win_units * unit_m evaluations are sibling units (bounds_units_kernel)
-        std::vector<fgoicp::TickSub> sub_tmp;    // packing scratch of the unit detection
-        std::vector<int> unit_of;
         std::vector<float> lb, ub;
         std::vector<int> row_group;              // window-local group of every output row (packing scratch)               // results of the whole submission
         int total = 0, win_pos = 0, win_rows = 0;
@@ -78,15 +72,12 @@ struct fgoicp_ctx {
     uint64_t cut_items_offered = 0;              // items of the windows submitted with thresholds
     uint64_t cut_verify_windows = 0, cut_verify_rows = 0, cut_verify_above = 0, cut_verify_bad = 0;  // development build, FGOICP_CUT_VERIFY
     uint64_t cut_stat_base = 0;                  // value of *d_cut_stat at the last reset
-    bool sorted_bounds = true;
     bool sort_xcd = true;                    // XCD-private histograms for the tick sort (cleared for good if a permutation check fails)
     bool sort_check = true;                  // verify on the device that every tick's `sorted` is a permutation
     int sort_fault_tick = 0;                 // test hook
     uint64_t sorted_ticks = 0, sort_fallbacks = 0;
     int nchunk1 = 0, max_groups = 0, cell_shift = 4;
     int chunk_pts = 256;                     // points per (subcube, chunk) work item of the sorted path
-    int unit_m = 0;                          // siblings per work item (0 / 1 = off): the children of one translation node share the point loads and the rotation
-    uint64_t unit_evals = 0, unit_total = 0; // evaluations that went into units / all evaluations (statistics)
     bool finalize_on_side = true;
     int small_tick_items = 4096;             // ticks of at most this many items skip the descriptor copies and the locality sort
     size_t coop_split_min = (size_t)-1;      // cooperative ICP: source clouds of at least this many points split the two scans of an iteration over the ranks (FGOICP_COOP_SPLIT_MIN); default: never —
@@ -141,26 +132,11 @@ struct fgoicp_ctx {
         double *h_covbp = nullptr, *hd_covbp = nullptr;   // pinned: [blocks][9] block partials of the covariance
         bool cov_on_host = false, sse_on_host = false;    // where the result of the last enqueued pass lands
         int cov_blocks = 0;
-        // gated loop (ctx.hip lane_icp_gated): the next iteration's kernels are enqueued BEFORE their motion is known, behind a stream
-        // wait on a signal word the host raises once it has written the motion into pinned memory
-        uint64_t *sig_b = nullptr, *sig_a = nullptr;   // hipMallocSignalMemory, 8 bytes each
-        uint64_t gate_seq = 0;                         // last value the gates have been raised to
-        float *h_rt = nullptr, *hd_rt = nullptr;       // pinned: 2 slots x {R_[9], t_[3], R[9], t[3]}
-        int *h_done = nullptr, *hd_done = nullptr;     // pinned: kernels enqueued behind a gate return at once when it is set
-        // device-resident ICP loop (ctx.hip lane_icp_device)
-        fgoicp::IcpDevState* d_icp = nullptr;    // loop state in device memory
-        fgoicp::IcpHostResult *h_res = nullptr, *hd_res = nullptr;   // pinned result + progress words
-        static constexpr int kRing = 8;
-        hipEvent_t ev_step[kRing] = {}, ev_sse[kRing] = {};   // step kernel j done (stream B) / SSE partials of iteration j ready (stream A)
     };
     std::vector<IcpLane> lanes;
     bool icp_overlap = true;
     bool icp_fuse = true;                    // small clouds: reductions started in the scans' epilogues, folded on the host (FGOICP_ICP_FUSE=0: separate kernels)
-    bool icp_gated = false;                  // FGOICP_ICP_GATED=1: small clouds, iterations pre-enqueued behind stream gates (built in round 3; measured slower, off)
-    bool icp_gate_ok = false;                // stream wait-value operations work on this device (probed at context creation)
     int icp_dual_env = -1;                   // FGOICP_ICP_DUAL: one walk serves the two scans of an ICP iteration (nn_scan_dual_kernel); -1 = by cloud size
-    bool icp_device = false;                 // ICP loop advanced on the device (FGOICP_ICP_DEVICE=0: the host loop, for A/B and as the bit reference)
-    int icp_ahead = 2;                       // iterations the host may enqueue ahead of the device's progress
 
     // HIP-event profile of the bounds kernel
     std::vector<hipEvent_t> ev_start, ev_stop, ev_sel_start, ev_sel_stop;   // bounds kernel / trimmed selection kernel of the same window

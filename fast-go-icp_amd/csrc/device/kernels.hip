@@ -14,7 +14,6 @@
 #include <cstdio>
 #include <cstdlib>
 
-#include "../host/math3.hpp"
 #include "../host/knobs.hpp"
 #include "slab.hpp"
 #include "bvh.hpp"
@@ -105,17 +104,11 @@ __device__ __forceinline__ void tex_axis(float u, int d, int quant, int& i, floa
 __device__ __forceinline__ float lerp(float p, float q, float w) { return fma_(w, q - p, p); }
 
 // ---------------------------------------------------------------------------------------------
-// kernComputeBounds (+ the two thrust::reduce calls) — fgoicp/registration.cu:27-60, :126-140.
-// grid = chunks of 256*P points x translation nodes of the batch (XCD-aware order); one block
-// owns one (chunk, subcube) pair and emits one {sum_ub, sum_lb} partial.  The source cloud is float4
-// {x, y, z, x*x+y*y+z*z}: one coalesced 16-byte load per point (TODO.md:14 of the reference).
+// lut_search in two halves: the texel address and weights, then the blend of the 2x2x2 footprint.
 // ---------------------------------------------------------------------------------------------
-// lut_search split in two so that a thread can put the gathers of several points in flight before
-// it consumes any of them (memory-level parallelism is what bounds this kernel, not arithmetic).
 struct TexAddr {
     size_t o;         // element offset of the first texel (x0, y0, z0) in the padded LUT
     float a, b, c;    // interpolation weights
-    unsigned pk;      // the same texel as packed padded indices x | y << 10 | z << 20 (bricked layout; dims <= 1023)
 };
 __device__ __forceinline__ TexAddr lut_address(const LutGeom& g, float qx, float qy, float qz) {
     const float x = (qx + g.off_x) * g.scale;
@@ -129,7 +122,6 @@ __device__ __forceinline__ TexAddr lut_address(const LutGeom& g, float qx, float
     // indices are >= 0 and < 4096: the row number fits 24 + bits, one 32 x 32 -> 64 multiply-add finishes the offset (signed size_t
     // arithmetic cost seven instructions here, a point is ~120)
     t.o = (size_t)((unsigned long long)((unsigned)iz * (unsigned)g.py + (unsigned)iy) * (unsigned)g.px + (unsigned)ix);
-    t.pk = (unsigned)ix | ((unsigned)iy << 10) | ((unsigned)iz << 20);
     return t;
 }
 __device__ __forceinline__ float lut_blend(const TexAddr& t, float2u v00, float2u v10, float2u v01, float2u v11) {
@@ -153,27 +145,10 @@ __device__ __forceinline__ float lut_search(const float* __restrict__ lut, const
 // processing of divergent gathers, not by bytes (measured 1.6x on the sparse 40k cloud).  Same texels,
 // same blend order -> bit-identical values.
 typedef float float4u __attribute__((ext_vector_type(4), aligned(8)));
-__device__ __forceinline__ void zpair_gather(const float2* __restrict__ zp, const LutGeom& g, const TexAddr& t, float2u& v00, float2u& v10,
-                                             float2u& v01, float2u& v11) {
-    const float4u a = *(const float4u*)(zp + t.o);
-    const float4u b = *(const float4u*)(zp + t.o + (size_t)g.px);
-    v00 = float2u{a.x, a.z};  // (x0, x1) at (y0, z0)
-    v01 = float2u{a.y, a.w};  // (x0, x1) at (y0, z1)
-    v10 = float2u{b.x, b.z};  // (x0, x1) at (y1, z0)
-    v11 = float2u{b.y, b.w};  // (x0, x1) at (y1, z1)
-}
 
 // yz-quad copy: q[o] = {T[o], T[o + z-slice], T[o + row], T[o + row + z-slice]} — a lookup is then 32 CONTIGUOUS bytes
 // (q[o], q[o+1]: x0 and x1), i.e. one cache line (two when x0 % 8 == 7) instead of two rows.  4x the bytes of the LUT.
 typedef float float4a __attribute__((ext_vector_type(4), aligned(16)));
-__device__ __forceinline__ void quad_gather(const float4* __restrict__ qd, const TexAddr& t, float2u& v00, float2u& v10, float2u& v01, float2u& v11) {
-    const float4a a = *(const float4a*)(qd + t.o);
-    const float4a b = *(const float4a*)(qd + t.o + 1);
-    v00 = float2u{a.x, b.x};  // (x0, x1) at (y0, z0)
-    v01 = float2u{a.y, b.y};  // (y0, z1)
-    v10 = float2u{a.z, b.z};  // (y1, z0)
-    v11 = float2u{a.w, b.w};  // (y1, z1)
-}
 // The same lookup with the two 16-byte halves fetched by a PAIR of neighbouring lanes in ONE instruction: load 1 brings
 // q[o], q[o+1] of the even lane's point (even lane: q[o], odd lane: q[o+1]), load 2 those of the odd lane's point, and the
 // lanes swap what the other one needs (DPP quad_perm, no LDS).  The texture addresser merges the two lanes' accesses to the
@@ -182,48 +157,6 @@ __device__ __forceinline__ void quad_gather(const float4* __restrict__ qd, const
 __device__ __forceinline__ int swap_lane_pair(int v) { return __builtin_amdgcn_mov_dpp(v, 0xB1 /* quad_perm [1,0,3,2] */, 0xF, 0xF, true); }
 __device__ __forceinline__ float swap_lane_pair(float v) { return __int_as_float(swap_lane_pair(__float_as_int(v))); }
 struct QuadPairLoads { float4a r1, r2; };
-__device__ __forceinline__ QuadPairLoads quad_pair_issue(const float4* __restrict__ qd, const TexAddr& t, int odd) {
-    const int own = (int)t.o, other = swap_lane_pair(own);
-    const int o_even = odd ? other : own, o_odd = odd ? own : other;
-    QuadPairLoads q;
-    q.r1 = *(const float4a*)(qd + (size_t)(o_even + odd));
-    q.r2 = *(const float4a*)(qd + (size_t)(o_odd + odd));
-    return q;
-}
-__device__ __forceinline__ void quad_pair_finish(const QuadPairLoads& q, int odd, float2u& v00, float2u& v10, float2u& v01, float2u& v11) {
-    float4a send = odd ? q.r1 : q.r2, recv;
-    recv.x = swap_lane_pair(send.x); recv.y = swap_lane_pair(send.y); recv.z = swap_lane_pair(send.z); recv.w = swap_lane_pair(send.w);
-    const float4a a = odd ? recv : q.r1, b = odd ? q.r2 : recv;
-    v00 = float2u{a.x, b.x};
-    v01 = float2u{a.y, b.y};
-    v10 = float2u{a.z, b.z};
-    v11 = float2u{a.w, b.w};
-}
-// Bricked yz-quad copy (experimental, FGOICP_LUT_ZPAIR=3): the quads of a 4 x 4 x 4 block of nodes are contiguous (1 KiB) and
-// Morton-ordered inside it, so a 128-byte line holds a 2 x 2 x 2 block of quads instead of a run of 8 along x: a surface patch of
-// any orientation then uses ~4 of the 8 quads of a line it touches, an x-run ~3 on average (1 + ln 8).
-__device__ __forceinline__ unsigned spread2(unsigned v) { return (v & 1u) | ((v & 2u) << 2); }
-__device__ __forceinline__ size_t brick_index(unsigned x, unsigned y, unsigned z, unsigned nbx, unsigned nby) {
-    const size_t b = ((size_t)(z >> 2) * nby + (y >> 2)) * nbx + (x >> 2);
-    return b * 64 + (spread2(x & 3u) | (spread2(y & 3u) << 1) | (spread2(z & 3u) << 2));
-}
-__device__ __forceinline__ QuadPairLoads quad_pair_issue_bricked(const float4* __restrict__ qd, const TexAddr& t, int odd, unsigned nbx, unsigned nby) {
-    const int own = (int)t.pk, other = swap_lane_pair(own);
-    const unsigned p_even = (unsigned)(odd ? other : own), p_odd = (unsigned)(odd ? own : other);
-    QuadPairLoads q;
-    q.r1 = *(const float4a*)(qd + brick_index((p_even & 1023u) + odd, (p_even >> 10) & 1023u, p_even >> 20, nbx, nby));
-    q.r2 = *(const float4a*)(qd + brick_index((p_odd & 1023u) + odd, (p_odd >> 10) & 1023u, p_odd >> 20, nbx, nby));
-    return q;
-}
-__global__ __launch_bounds__(kBlock) void lut_quad_bricked_kernel(const float* __restrict__ lut, LutGeom g, float4* __restrict__ qd) {
-    const unsigned nbx = (unsigned)(g.px + 3) >> 2, nby = (unsigned)(g.py + 3) >> 2;
-    const size_t total = (size_t)g.px * g.py * g.pz, sy = (size_t)g.px, sz = (size_t)g.px * g.py;
-    for (size_t n = (size_t)blockIdx.x * kBlock + threadIdx.x; n < total; n += (size_t)gridDim.x * kBlock) {
-        const unsigned x = (unsigned)(n % g.px), y = (unsigned)((n / g.px) % g.py), z = (unsigned)(n / sz);
-        const size_t nz = n + sz < total ? n + sz : n, ny = n + sy < total ? n + sy : n, nyz = n + sy + sz < total ? n + sy + sz : n;
-        qd[brick_index(x, y, z, nbx, nby)] = make_float4(lut[n], lut[nz], lut[ny], lut[nyz]);
-    }
-}
 
 // Apron-bricked yz-quad copy (round 3, FGOICP_LUT_ZPAIR=4): a 128-byte line holds the quads of 4 consecutive x at 2 consecutive y
 // (one z), and consecutive lines OVERLAP by one x: line (xb, yb, z) = quads x in [3 xb, 3 xb + 3], y in {2 yb, 2 yb + 1}.  A lookup
@@ -236,14 +169,6 @@ __device__ __forceinline__ unsigned apron_index(unsigned pk /* x | y << 10 | z <
     const unsigned x = pk & 1023u, y = (pk >> 10) & 1023u, z = pk >> 20;
     const unsigned q = (x * 43691u) >> 17;  // x / 3 (x < 1024)
     return ((z * nby2 + (y >> 1)) * nbx3 + q) * 8u + ((y & 1u) << 2) + (x - 3u * q);
-}
-__device__ __forceinline__ QuadPairLoads quad_pair_issue_apron(const float4* __restrict__ qd, const TexAddr& t, int odd, unsigned nbx3, unsigned nby2) {
-    const int own = (int)apron_index(t.pk, nbx3, nby2), other = swap_lane_pair(own);
-    const int o_even = odd ? other : own, o_odd = odd ? own : other;
-    QuadPairLoads q;
-    q.r1 = *(const float4a*)(qd + (size_t)(o_even + odd));
-    q.r2 = *(const float4a*)(qd + (size_t)(o_odd + odd));
-    return q;
 }
 __global__ __launch_bounds__(kBlock) void lut_quad_apron_kernel(const float* __restrict__ lut, LutGeom g, float4* __restrict__ qd) {
     const unsigned nbx3 = (unsigned)(g.px + 2) / 3u, nby2 = (unsigned)(g.py + 1) >> 1;
@@ -286,62 +211,6 @@ __device__ __forceinline__ unsigned xcd_remap(unsigned id, unsigned total) {
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
 }
 
-template <int P>
-__global__ __launch_bounds__(kBlock) void bounds_kernel(const float4* __restrict__ src, int ns, const float* __restrict__ lut,
-                                                        LutGeom g, BoundsArgs a, double2* __restrict__ partials, int nchunk) {
-    __shared__ double red[8];
-    const unsigned v = xcd_remap(blockIdx.x, gridDim.x);
-    const int b = (int)(v / (unsigned)nchunk);
-    const int chunk = (int)(v - (unsigned)b * (unsigned)nchunk);
-    const float4 tn = a.tn[b];
-    const float trans_uncertain_radius = kSqrt3 * tn.w;  // :33
-    const int base = chunk * (kBlock * P) + threadIdx.x;
-    const size_t sy = (size_t)g.px, sz = (size_t)g.px * g.py;
-
-    // phase 1: the points (coalesced 16-byte loads; out-of-range lanes re-read the last point)
-    float4 p[P];
-#pragma unroll
-    for (int k = 0; k < P; ++k) {
-        const int i = base + k * kBlock;
-        p[k] = src[i < ns ? i : ns - 1];
-    }
-    // phase 2: all 4*P gathers in flight
-    TexAddr ta[P];
-    float2u v00[P], v10[P], v01[P], v11[P];
-#pragma unroll
-    for (int k = 0; k < P; ++k) {
-        float rx, ry, rz;
-        rotate(a.R, p[k].x, p[k].y, p[k].z, rx, ry, rz);
-        ta[k] = lut_address(g, rx + tn.x, ry + tn.y, rz + tn.z);  // :34, :323-325
-    }
-#pragma unroll
-    for (int k = 0; k < P; ++k) {
-        const float* q = lut + ta[k].o;
-        v00[k] = *(const float2u*)(q);
-        v10[k] = *(const float2u*)(q + sy);
-        v01[k] = *(const float2u*)(q + sz);
-        v11[k] = *(const float2u*)(q + sz + sy);
-    }
-    // phase 3: blend, bounds, fp64 accumulation
-    double acc[2] = {0.0, 0.0};
-#pragma unroll
-    for (int k = 0; k < P; ++k) {
-        const float dsq = lut_blend(ta[k], v00[k], v10[k], v01[k], v11[k]);  // :46
-        float d = sqrtf(dsq);                                                 // :48
-        if (!a.fix_rot) d -= 2.0f * p[k].w * a.sin_half;                      // :39-43, :49-52
-        const float ubv = d > 0.0f ? d * d : 0.0f;                            // :54
-        const float l = d - trans_uncertain_radius;                           // :57
-        const float lbv = l > 0.0f ? l * l : 0.0f;                            // :58
-        const bool valid = base + k * kBlock < ns;
-        acc[0] += valid ? (double)ubv : 0.0;
-        acc[1] += valid ? (double)lbv : 0.0;
-    }
-    const double r = block_sum<2>(acc, red);
-    // threads 0 and 1 hold sum_ub and sum_lb
-    double* out = reinterpret_cast<double*>(partials + ((size_t)(a.out_base + b) * nchunk + chunk));
-    if (threadIdx.x < 2) out[threadIdx.x] = r;
-}
-
 // ---------------------------------------------------------------------------------------------
 // Locality-sorted variant for a whole tick (many rotation nodes, hundreds of subcubes).
 // A work item is (subcube s, chunk c of 256 Morton-consecutive points): a compact surface patch that
@@ -353,7 +222,7 @@ __global__ __launch_bounds__(kBlock) void bounds_kernel(const float4* __restrict
 // consecutive cells), and the XCD-aware remap hands each XCD one contiguous run of that order:
 // blocks resident together on an XCD read the same neighbourhood of the LUT.  Every item writes the
 // same partial it would write in any order, and the finalize sum is ordered by (s, c) — results
-// are bit-identical to the plain kernel.
+// do not depend on the order.
 // ---------------------------------------------------------------------------------------------
 constexpr int kKeyBits = 15;
 constexpr int kNumKeys = 1 << kKeyBits;
@@ -395,34 +264,17 @@ __device__ __forceinline__ unsigned hilbert15(unsigned x, unsigned y, unsigned z
 // ones).  An address is only ever touched from one XCD, so the L2 is a sufficient point of coherence; the dirty lines reach
 // memory at the end of the kernel like any other store.  The rank then carries the XCD in its top bits.
 constexpr int kTickXcds = 16;  // the XCC_ID field is 4 bits wide
-template <int HILBERT, int XCD>
+template <int XCD>
 __global__ __launch_bounds__(64) void tick_keys_kernel(const float4* __restrict__ chunk_cen, int nchunk, const TickGroup* __restrict__ groups,
-                                                           const TickSub* __restrict__ subs, int nsub, LutGeom g, int cell_shift,
-                                                           unsigned short* __restrict__ keys, unsigned* __restrict__ ranks, unsigned* __restrict__ hist,
-                                                           unsigned* __restrict__ prefill /* optional: `sorted`, filled with 0xFFFFFFFF for the permutation check of the bounds kernel */,
-                                                           int nunits, int unit_m /* sibling units: the first nunits * unit_m evaluations, unit_m per item */,
-                                                           int orient /* experimental: 1 = 12-bit cell index + 3 bits of the rotated patch normal (chunk_cen[nchunk + c]) */,
-                                                           const float* __restrict__ tier_lut /* windows with thresholds: the plain LUT; nullptr = one tier */, float tier_level) {
-    const size_t unit_items = (size_t)nunits * nchunk;
-    const size_t nitems = unit_items + (size_t)(nsub - nunits * unit_m) * nchunk;
+                                                       const TickSub* __restrict__ subs, int nsub, LutGeom g, int cell_shift,
+                                                       unsigned short* __restrict__ keys, unsigned* __restrict__ ranks, unsigned* __restrict__ hist,
+                                                       unsigned* __restrict__ prefill /* optional: `sorted`, filled with 0xFFFFFFFF for the permutation check of the bounds kernel */,
+                                                       const float* __restrict__ tier_lut /* windows with thresholds: the plain LUT; nullptr = one tier */, float tier_level) {
+    const size_t nitems = (size_t)nsub * nchunk;
     for (size_t i = (size_t)blockIdx.x * 64 + threadIdx.x; i < nitems; i += (size_t)gridDim.x * 64) {
         if (prefill) prefill[i] = 0xFFFFFFFFu;
-        int s, c;
-        TickSub sb;
-        if (i < unit_items) {  // a sibling unit is keyed by the mean of its translation nodes (the parent's centre for a whole octet)
-            const int u = (int)(i / nchunk);
-            c = (int)(i - (size_t)u * nchunk);
-            s = u * unit_m;
-            sb = subs[s];
-            for (int j = 1; j < unit_m; ++j) { const TickSub o = subs[s + j]; sb.tx += o.tx; sb.ty += o.ty; sb.tz += o.tz; }
-            const float inv = 1.0f / (float)unit_m;
-            sb.tx *= inv; sb.ty *= inv; sb.tz *= inv;
-        } else {
-            const size_t r = i - unit_items;
-            s = nunits * unit_m + (int)(r / nchunk);
-            c = (int)(r - (size_t)(s - nunits * unit_m) * nchunk);
-            sb = subs[s];
-        }
+        const int s = (int)(i / nchunk), c = (int)(i - (size_t)s * nchunk);
+        const TickSub sb = subs[s];
         const TickGroup& gr = groups[sb.group];
         const float4 cc = chunk_cen[c];
         float rx, ry, rz;
@@ -430,18 +282,7 @@ __global__ __launch_bounds__(64) void tick_keys_kernel(const float4* __restrict_
         const int vx = (int)fminf(fmaxf((rx + sb.tx + g.off_x) * g.scale, 0.0f), (float)(g.dx - 1)) >> cell_shift;
         const int vy = (int)fminf(fmaxf((ry + sb.ty + g.off_y) * g.scale, 0.0f), (float)(g.dy - 1)) >> cell_shift;
         const int vz = (int)fminf(fmaxf((rz + sb.tz + g.off_z) * g.scale, 0.0f), (float)(g.dz - 1)) >> cell_shift;
-        unsigned key = HILBERT ? hilbert15((unsigned)vx, (unsigned)vy, (unsigned)vz)
-                               : part1by2_5((unsigned)vx) | (part1by2_5((unsigned)vy) << 1) | (part1by2_5((unsigned)vz) << 2);
-        if (orient) {
-            // two patches around the same LUT cell share lines only if they lie in (nearly) the same plane: cells twice as wide, and
-            // inside a cell the items grouped by the direction of the rotated patch normal (hemisphere: 4 quadrants x {pole cap, rim})
-            const float4 nn = chunk_cen[nchunk + c];
-            float nx, ny, nz;
-            rotate(gr.R, nn.x, nn.y, nn.z, nx, ny, nz);
-            if (nz < 0.0f) { nx = -nx; ny = -ny; }
-            const unsigned oc = (nx >= 0.0f ? 1u : 0u) | (ny >= 0.0f ? 2u : 0u) | (nz * nz > 0.5f ? 4u : 0u);
-            key = (hilbert15((unsigned)vx >> 1, (unsigned)vy >> 1, (unsigned)vz >> 1) << 3) | oc;
-        }
+        unsigned key = hilbert15((unsigned)vx, (unsigned)vy, (unsigned)vz);
         if (tier_lut) {
             // Windows with thresholds (fgoicp_bounds_submit_cut): an evaluation is over as soon as the lower-bound sums of its finished items
             // reach its threshold T, so the items likely to carry much of the sum go FIRST (tier 0: the top key bit clear; inside a tier the
@@ -557,14 +398,6 @@ __global__ __launch_bounds__(64) void tick_scatter_xcd_kernel(const unsigned sho
         sorted[cursor[k] + xoff[(size_t)(r >> 28) * kNumKeys + k] + (r & 0x0FFFFFFFu)] = (unsigned)i;
     }
 }
-#ifdef FGOICP_DEV_KNOBS
-// The permutation check as a launch of its own, for round 3's bounds kernels (bounds_item_kernel carries it itself: see there).
-__global__ __launch_bounds__(64) void tick_check_kernel(const unsigned* __restrict__ sorted, size_t nitems, unsigned* __restrict__ err) {
-    bool bad = false;
-    for (size_t i = (size_t)blockIdx.x * 64 + threadIdx.x; i < nitems; i += (size_t)gridDim.x * 64) bad = bad || sorted[i] >= nitems;
-    if (__any(bad) && threadIdx.x == 0) *err = 1u;
-}
-#endif
 // The tick's descriptors from the pinned staging buffers into device memory: one launch instead of two hipMemcpyAsync calls (each
 // costs the submitting thread ~10 us; the bytes — <= 150 KB — cross PCIe either way).
 __global__ __launch_bounds__(64) void tick_upload_kernel(const uint4* __restrict__ hg, uint4* __restrict__ dg, unsigned ng16, const uint4* __restrict__ hs,
@@ -575,26 +408,12 @@ __global__ __launch_bounds__(64) void tick_upload_kernel(const uint4* __restrict
     }
 }
 __global__ void tick_fault_kernel(unsigned* sorted) { sorted[0] = 0xFFFFFFFFu; }  // test hook (FGOICP_SORT_FAULT_TICK): a slot no item was scattered to
-// A/B only (FGOICP_SORT_RANKS=0): the classic scatter with its own atomic per item
-__global__ __launch_bounds__(64) void tick_scatter_atomic_kernel(const unsigned short* __restrict__ keys, size_t nitems, unsigned* __restrict__ cursor,
-                                                                 unsigned* __restrict__ sorted) {
-    for (size_t i = (size_t)blockIdx.x * 64 + threadIdx.x; i < nitems; i += (size_t)gridDim.x * 64)
-        sorted[atomicAdd(&cursor[keys[i]], 1u)] = (unsigned)i;
-}
 __global__ __launch_bounds__(64) void tick_scatter_kernel(const unsigned short* __restrict__ keys, const unsigned* __restrict__ ranks, size_t nitems,
                                                           const unsigned* __restrict__ cursor, unsigned* __restrict__ sorted) {
     for (size_t i = (size_t)blockIdx.x * 64 + threadIdx.x; i < nitems; i += (size_t)gridDim.x * 64)
         sorted[cursor[keys[i]] + ranks[i]] = (unsigned)i;  // order inside a bin is irrelevant (scheduling only)
 }
 
-// One pass = THREADS x P points.  Measured on MI355X, bunny shape, whole benchmark step, yz-quad layout, wide rounds:
-// 64x4 (default: one wave per item, no block-level reduction) 2.94 M subcubes/s, 128x2 2.81, 256x1 2.54; 128- and 64-point
-// items (64x2, 64x1) 2.77 / 2.26 — smaller items do not buy locality, they only add items.  Dragon shape: 64x4 = 128x2.
-// Fewer resident blocks per CU (LDS padding) only hurts — the kernel wants every wave slot and many gathers in flight.
-// WPG > 1 (THREADS == 64 only): a workgroup is WPG independent one-wave items that are NEIGHBOURS in the sorted order, so they run
-// on one CU at the same time and share its L1 (the XCD remap alone spreads neighbours over the 32 CUs of an XCD: they share
-// the L2 only).  NT = 1: the source points are loaded non-temporally (they stream through once per item; kept out of the L1
-// they leave it to the LUT lines).
 // Trimmed mode: the per-point e of an output row, and — samp_shift > 0 — one point of every run of 2^samp_shift points of the stored cloud
 // once more in a compact SAMPLE behind the row (offset: ns rounded up to 64 floats): a systematic sample of the row that the selection
 // reads first (125 KB instead of 4 MB at 1M points) to bracket the cut, so that it needs ONE pass over the row instead of two
@@ -619,475 +438,6 @@ __device__ __forceinline__ void trim_store(float* __restrict__ evals, size_t row
 #include "bounds_item.hpp"   // round 4: the bounds kernel of the sorted path (bounds_item_kernel)
 
 typedef float v4f __attribute__((ext_vector_type(4)));
-// FGOICP_BOUNDS_WAVES (development builds, tools/ab_waves.sh): ask the register allocator for that many resident waves per SIMD
-#ifdef FGOICP_BOUNDS_WAVES
-#define FGOICP_BOUNDS_OCC __attribute__((amdgpu_waves_per_eu(FGOICP_BOUNDS_WAVES, FGOICP_BOUNDS_WAVES)))
-#else
-#define FGOICP_BOUNDS_OCC
-#endif
-template <int THREADS, int P, int ZPAIR, int TRIM, int WPG = 1, int NT = 0>
-__global__ __launch_bounds__(THREADS * WPG) FGOICP_BOUNDS_OCC void bounds_sorted_kernel(const float4* __restrict__ src, int ns, const float* __restrict__ lut,
-                                                                const float2* __restrict__ zp, LutGeom g,
-                                                                const TickGroup* __restrict__ groups, const TickSub* __restrict__ subs,
-                                                                const unsigned* __restrict__ sorted, int nchunk, int chunk_pts,
-                                                                double2* __restrict__ partials, float* __restrict__ evals, size_t erow, int samp_shift, unsigned nitems) {
-    static_assert(THREADS % 64 == 0 && THREADS * P <= kBlock, "one pass covers THREADS * P points");
-    static_assert(WPG == 1 || THREADS == 64, "several items per workgroup: one wave each");
-    __shared__ double red[4 * (THREADS / 64)];
-    const unsigned slot = xcd_remap(blockIdx.x, gridDim.x) * WPG + (WPG > 1 ? threadIdx.x >> 6 : 0);
-    if (WPG > 1 && slot >= nitems) return;
-    const unsigned item = sorted ? sorted[slot] : slot;  // small ticks come unsorted
-    if (item >= nitems) return;  // never taken when `sorted` is a permutation (tick_check_kernel verifies that on the device)
-    const unsigned tix = WPG > 1 ? (threadIdx.x & 63u) : threadIdx.x;  // thread index inside the item
-    const int s = (int)(item / (unsigned)nchunk);
-    const int chunk = (int)(item - (unsigned)s * (unsigned)nchunk);
-    const TickSub sb = subs[s];
-    const TickGroup& gr = groups[sb.group];
-    const float trans_uncertain_radius = kSqrt3 * sb.span;  // registration.cu:33
-    const size_t sy = (size_t)g.px, sz = (size_t)g.px * g.py;
-    double acc[4] = {0.0, 0.0, 0.0, 0.0};  // {ub, lb} of the item's variant; a dual item: {ub, lb} with fix_rot = 1, then with fix_rot = 0
-    const bool dual = sb.dual != 0;
-    // an item is chunk_pts (256 .. 2048) Morton-consecutive points, walked in passes of THREADS * P: dense clouds take bigger
-    // items (the patch of 256 points is only a few voxels wide there), which divides the items to sort and the partials
-    for (int pass = 0; pass < chunk_pts; pass += THREADS * P) {
-        float4 p[P];
-        TexAddr ta[P];
-        float2u v00[P], v10[P], v01[P], v11[P];
-        const int first = chunk * chunk_pts + pass + (int)tix;
-#pragma unroll
-        for (int k = 0; k < P; ++k) {
-            const int i = first + k * THREADS;
-            if (NT) {
-                const v4f v = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(src + (i < ns ? i : ns - 1)));
-                p[k] = make_float4(v.x, v.y, v.z, v.w);
-            } else {
-                p[k] = src[i < ns ? i : ns - 1];
-            }
-            float rx, ry, rz;
-#if defined(FGOICP_ABLATE) && (FGOICP_ABLATE & 1)   // timing-only build (tools/ablate.sh): what the per-evaluation rotation costs
-            rx = p[k].x; ry = p[k].y; rz = p[k].z;
-#else
-            rotate(gr.R, p[k].x, p[k].y, p[k].z, rx, ry, rz);
-#endif
-            ta[k] = lut_address(g, rx + sb.tx, ry + sb.ty, rz + sb.tz);  // :34, :323-325
-#if defined(FGOICP_ABLATE) && (FGOICP_ABLATE & 4)   // timing-only build: every gather hits a 64 KiB corner of the LUT (address unit + VALU, no misses)
-            ta[k].o &= (size_t)4095;
-#endif
-        }
-        QuadPairLoads qp[(ZPAIR == 3 || ZPAIR == 4 || ZPAIR == 5) ? P : 1];
-        const int odd = (int)tix & 1;
-        if (ZPAIR == 3 || ZPAIR == 4 || ZPAIR == 5) {
-            const unsigned nbx = (unsigned)(g.px + 3) >> 2, nby = (unsigned)(g.py + 3) >> 2;
-            const unsigned nbx3 = (unsigned)(g.px + 2) / 3u, nby2 = (unsigned)(g.py + 1) >> 1;
-#pragma unroll
-            for (int k = 0; k < P; ++k)
-                qp[k] = ZPAIR == 4 ? quad_pair_issue_bricked(reinterpret_cast<const float4*>(zp), ta[k], odd, nbx, nby)
-                      : ZPAIR == 5 ? quad_pair_issue_apron(reinterpret_cast<const float4*>(zp), ta[k], odd, nbx3, nby2)
-                                   : quad_pair_issue(reinterpret_cast<const float4*>(zp), ta[k], odd);
-#pragma unroll
-            for (int k = 0; k < P; ++k) quad_pair_finish(qp[k], odd, v00[k], v10[k], v01[k], v11[k]);
-        }
-#pragma unroll
-        for (int k = 0; k < P; ++k) {
-            if (ZPAIR == 3 || ZPAIR == 4 || ZPAIR == 5) {
-            } else if (ZPAIR == 2) {
-                quad_gather(reinterpret_cast<const float4*>(zp), ta[k], v00[k], v10[k], v01[k], v11[k]);
-            } else if (ZPAIR == 1) {
-                zpair_gather(zp, g, ta[k], v00[k], v10[k], v01[k], v11[k]);
-            } else {
-                const float* q = lut + ta[k].o;
-                v00[k] = *(const float2u*)(q);  // default cache policy: non-temporal loads measured 2x slower here
-                v10[k] = *(const float2u*)(q + sy);
-                v01[k] = *(const float2u*)(q + sz);
-                v11[k] = *(const float2u*)(q + sz + sy);
-            }
-        }
-        float te0[TRIM ? P : 1], te1[TRIM ? P : 1];
-#pragma unroll
-        for (int k = 0; k < P; ++k) {
-            const float dsq = lut_blend(ta[k], v00[k], v10[k], v01[k], v11[k]);  // :46
-            float d = sqrtf(dsq);                                                 // :48
-            const int i = first + k * THREADS;
-            const bool valid = i < ns;
-            if (TRIM) {
-                // trimmed Go-ICP: both bounds are non-decreasing functions of e = max(d, 0) (ub = e*e, lb = max(e - r_t, 0)^2 —
-                // the same fp32 values as :54-58), so ONE row of e per variant carries both selections (trim_rows_kernel)
-                float e0, e1 = 0.0f;
-                if (dual) {
-                    e0 = d > 0.0f ? d : 0.0f;
-                    d -= 2.0f * p[k].w * gr.sin_half;
-                    e1 = d > 0.0f ? d : 0.0f;
-                } else {
-                    if (!gr.fix_rot) d -= 2.0f * p[k].w * gr.sin_half;
-                    e0 = d > 0.0f ? d : 0.0f;
-                }
-                if (valid) {
-                    evals[(size_t)sb.out0 * erow + i] = e0;
-                    if (dual) evals[(size_t)sb.out1 * erow + i] = e1;
-                }
-                te0[k] = e0;
-                te1[k] = e1;
-                continue;
-            }
-            if (dual) {  // wave-uniform
-                const float ub1 = d > 0.0f ? d * d : 0.0f;                        // fix_rot = 1: :54
-                const float l1 = d - trans_uncertain_radius;                      // :57
-                const float lb1 = l1 > 0.0f ? l1 * l1 : 0.0f;                     // :58
-                d -= 2.0f * p[k].w * gr.sin_half;                                 // fix_rot = 0: :39-43, :49-52
-                const float ub0 = d > 0.0f ? d * d : 0.0f;
-                const float l0 = d - trans_uncertain_radius;
-                const float lb0 = l0 > 0.0f ? l0 * l0 : 0.0f;
-                acc[0] += valid ? (double)ub1 : 0.0;
-                acc[1] += valid ? (double)lb1 : 0.0;
-                acc[2] += valid ? (double)ub0 : 0.0;
-                acc[3] += valid ? (double)lb0 : 0.0;
-                continue;
-            }
-            if (!gr.fix_rot) d -= 2.0f * p[k].w * gr.sin_half;                    // :39-43, :49-52
-            const float ubv = d > 0.0f ? d * d : 0.0f;                            // :54
-            const float l = d - trans_uncertain_radius;                           // :57
-            const float lbv = l > 0.0f ? l * l : 0.0f;                            // :58
-            acc[0] += valid ? (double)ubv : 0.0;
-            acc[1] += valid ? (double)lbv : 0.0;
-        }
-        if (TRIM && samp_shift > 0) {
-            // the row's sample (see trim_store / trim_is_sample): one point of every run of 2^samp_shift once more behind the row
-            const size_t off = trim_sample_offset(ns);
-#pragma unroll
-            for (int k = 0; k < P; ++k) {
-                const int i = first + k * THREADS;
-                if (i < ns && trim_is_sample(i, samp_shift, ns)) {
-                    evals[(size_t)sb.out0 * erow + off + (size_t)(i >> samp_shift)] = te0[k];
-                    if (dual) evals[(size_t)sb.out1 * erow + off + (size_t)(i >> samp_shift)] = te1[k];
-                }
-            }
-        }
-    }
-    if (!TRIM && WPG > 1) {  // one wave per item, several items per workgroup: the wave tree only (= block_sum with one wave), no barrier
-        const double r0 = wave_sum(acc[0]), r1 = wave_sum(acc[1]);
-        if (dual) {
-            const double r2 = wave_sum(acc[2]), r3 = wave_sum(acc[3]);
-            if (tix == 0) {
-                partials[(size_t)sb.out0 * nchunk + chunk] = make_double2(r0, r1);
-                partials[(size_t)sb.out1 * nchunk + chunk] = make_double2(r2, r3);
-            }
-        } else if (tix == 0) {
-            partials[(size_t)sb.out0 * nchunk + chunk] = make_double2(r0, r1);
-        }
-    } else if (!TRIM) {
-        // sums 0, 1 land in threads 0, 1 (dual: sums 2, 3 in threads 2, 3); same reduction tree per sum either way
-        if (dual) {
-            const double r = block_sum<4, THREADS / 64>(acc, red);
-            if (threadIdx.x < 4) {
-                double* out = reinterpret_cast<double*>(partials + ((size_t)(threadIdx.x < 2 ? sb.out0 : sb.out1) * nchunk + chunk));
-                out[threadIdx.x & 1] = r;
-            }
-        } else {
-            const double a2[2] = {acc[0], acc[1]};
-            const double r = block_sum<2, THREADS / 64>(a2, red);
-            double* out = reinterpret_cast<double*>(partials + ((size_t)sb.out0 * nchunk + chunk));
-            if (threadIdx.x < 2) out[threadIdx.x] = r;
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// Sibling units (round 3; dense clouds).  The inner BnB (fgoicp.cpp:157-168) pushes the eight children of a translation node with
-// one key, so they are popped together: almost every evaluation of a tick has its seven siblings next to it — the same rotation,
-// the same points, translations 2 * span apart.  bounds_sorted_kernel re-loads and re-rotates the chunk's points for each of them
-// (16 B per point-evaluation against the 0.375 B of SURVEY 8d; at 1M points the cloud is 16 MB and no L2 holds it).  Here an item is
-// (unit of M siblings, chunk): the wave loads and rotates its 4 points per lane ONCE per pass (the reference's TODO.md:11, "avoid
-// repeated rotation computation") and walks the M translations with them — per sibling the same lookups, the same per-point
-// expressions and the same per-lane accumulation order as bounds_sorted_kernel, one partial per (subcube, chunk) as before, so
-// every sum keeps its bits.  Items are keyed by the unit's mean translation (tick_keys_kernel); evaluations that are not in a
-// unit follow as one-sibling items.  M = 8 for the trimmed kernel (no accumulators), 4 or 8 otherwise (2 fp64 sums per sibling in
-// registers).  Dual (twin) evaluations are grouped only in the trimmed kernel.
-// ---------------------------------------------------------------------------------------------
-template <int ZPAIR /* 0 plain, 1 z-pair, 2 yz-quad (lane-paired) */, int TRIM, int M>
-__global__ __launch_bounds__(64) void bounds_units_kernel(const float4* __restrict__ src, int ns, const float* __restrict__ lut, const float2* __restrict__ zp, LutGeom g,
-                                                          const TickGroup* __restrict__ groups, const TickSub* __restrict__ subs, const unsigned* __restrict__ sorted,
-                                                          int nchunk, int chunk_pts, double2* __restrict__ partials, float* __restrict__ evals, size_t erow, int samp_shift,
-                                                          unsigned nitems, int nunits) {
-    constexpr int P = 4;
-    const unsigned slot = xcd_remap(blockIdx.x, gridDim.x);
-    const unsigned item = sorted ? sorted[slot] : slot;
-    if (item >= nitems) return;
-    const unsigned unit_items = (unsigned)nunits * (unsigned)nchunk;
-    int s0, chunk, count;
-    if (item < unit_items) {
-        const int u = (int)(item / (unsigned)nchunk);
-        chunk = (int)(item - (unsigned)u * (unsigned)nchunk);
-        s0 = u * M;
-        count = M;
-    } else {
-        const unsigned r = item - unit_items;
-        const int q = (int)(r / (unsigned)nchunk);
-        chunk = (int)(r - (unsigned)q * (unsigned)nchunk);
-        s0 = nunits * M + q;
-        count = 1;
-    }
-    const int tix = (int)threadIdx.x;
-    const TickSub sb0 = subs[s0];
-    const TickGroup& gr = groups[sb0.group];  // one rotation node per unit
-    const bool dual = sb0.dual != 0;           // ... and one kind (the host groups only evaluations of the same kind)
-    const size_t sy = (size_t)g.px, sz = (size_t)g.px * g.py;
-    double acc[TRIM ? 1 : 2 * M];
-#pragma unroll
-    for (int k = 0; k < (TRIM ? 1 : 2 * M); ++k) acc[k] = 0.0;
-    double accd[4] = {0.0, 0.0, 0.0, 0.0};  // a dual one-sibling item of the untrimmed kernel (as bounds_sorted_kernel)
-    const int odd = tix & 1;
-    for (int pass = 0; pass < chunk_pts; pass += 64 * P) {
-        float4 p[P];
-        float rx[P], ry[P], rz[P];
-        const int first = chunk * chunk_pts + pass + tix;
-#pragma unroll
-        for (int k = 0; k < P; ++k) {
-            const int i = first + k * 64;
-            p[k] = src[i < ns ? i : ns - 1];
-            rotate(gr.R, p[k].x, p[k].y, p[k].z, rx[k], ry[k], rz[k]);
-        }
-#pragma unroll
-        for (int j = 0; j < M; ++j) {
-            if (j >= count) break;  // wave-uniform
-            const TickSub sb = subs[s0 + j];
-            const float trans_uncertain_radius = kSqrt3 * sb.span;  // registration.cu:33
-            TexAddr ta[P];
-            float2u v00[P], v10[P], v01[P], v11[P];
-#pragma unroll
-            for (int k = 0; k < P; ++k) ta[k] = lut_address(g, rx[k] + sb.tx, ry[k] + sb.ty, rz[k] + sb.tz);  // :34, :323-325
-            if (ZPAIR == 2) {
-                QuadPairLoads qp[P];
-#pragma unroll
-                for (int k = 0; k < P; ++k) qp[k] = quad_pair_issue(reinterpret_cast<const float4*>(zp), ta[k], odd);
-#pragma unroll
-                for (int k = 0; k < P; ++k) quad_pair_finish(qp[k], odd, v00[k], v10[k], v01[k], v11[k]);
-            } else {
-#pragma unroll
-                for (int k = 0; k < P; ++k) {
-                    if (ZPAIR == 1) {
-                        zpair_gather(zp, g, ta[k], v00[k], v10[k], v01[k], v11[k]);
-                    } else {
-                        const float* q = lut + ta[k].o;
-                        v00[k] = *(const float2u*)(q);
-                        v10[k] = *(const float2u*)(q + sy);
-                        v01[k] = *(const float2u*)(q + sz);
-                        v11[k] = *(const float2u*)(q + sz + sy);
-                    }
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < P; ++k) {
-                const float dsq = lut_blend(ta[k], v00[k], v10[k], v01[k], v11[k]);  // :46
-                float d = sqrtf(dsq);                                                 // :48
-                const int i = first + k * 64;
-                const bool valid = i < ns;
-                if (TRIM) {
-                    if (valid) {
-                        if (dual) {
-                            trim_store(evals, (size_t)sb.out0 * erow, i, d > 0.0f ? d : 0.0f, samp_shift, ns);
-                            d -= 2.0f * p[k].w * gr.sin_half;
-                            trim_store(evals, (size_t)sb.out1 * erow, i, d > 0.0f ? d : 0.0f, samp_shift, ns);
-                        } else {
-                            if (!gr.fix_rot) d -= 2.0f * p[k].w * gr.sin_half;
-                            trim_store(evals, (size_t)sb.out0 * erow, i, d > 0.0f ? d : 0.0f, samp_shift, ns);
-                        }
-                    }
-                    continue;
-                }
-                if (dual) {  // wave-uniform; one-sibling items only (the host does not group dual evaluations for this kernel)
-                    const float ub1 = d > 0.0f ? d * d : 0.0f;                        // fix_rot = 1: :54
-                    const float l1 = d - trans_uncertain_radius;                      // :57
-                    const float lb1 = l1 > 0.0f ? l1 * l1 : 0.0f;                     // :58
-                    d -= 2.0f * p[k].w * gr.sin_half;                                 // fix_rot = 0: :39-43, :49-52
-                    const float ub0 = d > 0.0f ? d * d : 0.0f;
-                    const float l0 = d - trans_uncertain_radius;
-                    const float lb0 = l0 > 0.0f ? l0 * l0 : 0.0f;
-                    accd[0] += valid ? (double)ub1 : 0.0;
-                    accd[1] += valid ? (double)lb1 : 0.0;
-                    accd[2] += valid ? (double)ub0 : 0.0;
-                    accd[3] += valid ? (double)lb0 : 0.0;
-                    continue;
-                }
-                if (!gr.fix_rot) d -= 2.0f * p[k].w * gr.sin_half;                    // :39-43, :49-52
-                const float ubv = d > 0.0f ? d * d : 0.0f;                            // :54
-                const float l = d - trans_uncertain_radius;                           // :57
-                const float lbv = l > 0.0f ? l * l : 0.0f;                            // :58
-                acc[TRIM ? 0 : 2 * j] += valid ? (double)ubv : 0.0;
-                acc[TRIM ? 0 : 2 * j + 1] += valid ? (double)lbv : 0.0;
-            }
-        }
-    }
-    if (TRIM) return;
-    if (dual) {  // count == 1
-        const double r0 = wave_sum(accd[0]), r1 = wave_sum(accd[1]), r2 = wave_sum(accd[2]), r3 = wave_sum(accd[3]);
-        if (tix == 0) {
-            partials[(size_t)sb0.out0 * nchunk + chunk] = make_double2(r0, r1);
-            partials[(size_t)sb0.out1 * nchunk + chunk] = make_double2(r2, r3);
-        }
-        return;
-    }
-#pragma unroll
-    for (int j = 0; j < M; ++j) {
-        if (j >= count) break;
-        const double r0 = wave_sum(acc[TRIM ? 0 : 2 * j]), r1 = wave_sum(acc[TRIM ? 0 : 2 * j + 1]);
-        if (tix == 0) partials[(size_t)subs[s0 + j].out0 * nchunk + chunk] = make_double2(r0, r1);
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// LDS-staged LUT tiles (round 3; north_star names them, the reference wished for them: TODO.md:12).  One wave per item as in
-// bounds_sorted_kernel (64 x 4).  Per pass of 256 Hilbert-consecutive points the wave
-//   1. computes the points' first texels and takes their bounding brick (wave min / max of the three padded indices),
-//   2. if the brick is at most 16 nodes wide and ROWS rows (y x z) high, copies it from the plain fp32 LUT into LDS — 16 lanes per
-//      row, four rows per load instruction, rows padded to 16 floats, so the staging loads are row-coalesced —
-//   3. and reads the 2 x 2 x 2 footprints of its points from LDS (four 8-byte reads per point) instead of gathering them from
-//      global memory; a pass whose brick does not fit gathers from the plain LUT as before.
-// Same texels, same blend, same per-lane accumulation order: bit-identical sums (tests).  Whether it pays is a question of how
-// many lookups share a staged node: 256 points of a surface patch touch a brick of (patch extent + 2)^2 x depth nodes.
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ int wave_min_i(int v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = min(v, __shfl_xor(v, off, 64));
-    return v;
-}
-__device__ __forceinline__ int wave_max_i(int v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off, 64));
-    return v;
-}
-template <int TRIM, int ROWS>
-__global__ __launch_bounds__(64) void bounds_lds_kernel(const float4* __restrict__ src, int ns, const float* __restrict__ lut, LutGeom g,
-                                                        const TickGroup* __restrict__ groups, const TickSub* __restrict__ subs, const unsigned* __restrict__ sorted,
-                                                        int nchunk, int chunk_pts, double2* __restrict__ partials, float* __restrict__ evals, size_t erow, int samp_shift,
-                                                        unsigned nitems, unsigned* __restrict__ stat /* optional: [0] staged passes, [1] all passes */) {
-    constexpr int P = 4;
-    __shared__ float tile[ROWS * 16];
-    const unsigned slot = xcd_remap(blockIdx.x, gridDim.x);
-    const unsigned item = sorted ? sorted[slot] : slot;
-    if (item >= nitems) return;
-    const int s = (int)(item / (unsigned)nchunk);
-    const int chunk = (int)(item - (unsigned)s * (unsigned)nchunk);
-    const int tix = (int)threadIdx.x;
-    const TickSub sb = subs[s];
-    const TickGroup& gr = groups[sb.group];
-    const float trans_uncertain_radius = kSqrt3 * sb.span;  // registration.cu:33
-    const bool dual = sb.dual != 0;
-    const size_t sy = (size_t)g.px, sz = (size_t)g.px * g.py;
-    double acc[4] = {0.0, 0.0, 0.0, 0.0};
-    unsigned staged_passes = 0, all_passes = 0;
-    for (int pass = 0; pass < chunk_pts; pass += 64 * P) {
-        float4 p[P];
-        TexAddr ta[P];
-        float2u v00[P], v10[P], v01[P], v11[P];
-        const int first = chunk * chunk_pts + pass + tix;
-        int lo[3] = {1 << 20, 1 << 20, 1 << 20}, hi[3] = {0, 0, 0};
-#pragma unroll
-        for (int k = 0; k < P; ++k) {
-            const int i = first + k * 64;
-            p[k] = src[i < ns ? i : ns - 1];
-            float rx, ry, rz;
-            rotate(gr.R, p[k].x, p[k].y, p[k].z, rx, ry, rz);
-            ta[k] = lut_address(g, rx + sb.tx, ry + sb.ty, rz + sb.tz);  // :34, :323-325
-            const int ix = (int)(ta[k].pk & 1023u), iy = (int)((ta[k].pk >> 10) & 1023u), iz = (int)(ta[k].pk >> 20);
-            lo[0] = min(lo[0], ix); lo[1] = min(lo[1], iy); lo[2] = min(lo[2], iz);
-            hi[0] = max(hi[0], ix); hi[1] = max(hi[1], iy); hi[2] = max(hi[2], iz);
-        }
-        // the pass's brick: [lo, hi + 1] per axis (wave-uniform after the reductions)
-        int bx, by, bz;
-        {
-            const int x0 = wave_min_i(lo[0]), y0 = wave_min_i(lo[1]), z0 = wave_min_i(lo[2]);
-            bx = wave_max_i(hi[0]) - x0 + 2; by = wave_max_i(hi[1]) - y0 + 2; bz = wave_max_i(hi[2]) - z0 + 2;
-            lo[0] = x0; lo[1] = y0; lo[2] = z0;
-        }
-        const int rows = by * bz;
-        const bool fits = bx <= 16 && rows <= ROWS && g.px < 1024 && g.py < 1024 && g.pz < 1024;  // `pk` holds 10 bits per index
-        ++all_passes;
-        if (fits) {  // wave-uniform
-            ++staged_passes;
-            const int sub = tix >> 4, xl = tix & 15;
-            int y = sub % by, z = sub / by;  // row r = y + by * z, rows r0 + sub for r0 = 0, 4, 8, ...
-            const int xg = min(lo[0] + xl, g.px - 1);  // lanes beyond the brick's width copy in-range neighbours nobody reads
-            for (int r = sub; r < rows; r += 4) {
-                tile[r * 16 + xl] = lut[((size_t)(lo[2] + z) * g.py + (size_t)(lo[1] + y)) * g.px + (size_t)xg];
-                y += 4;
-                while (y >= by) { y -= by; ++z; }
-            }
-            __syncthreads();
-#pragma unroll
-            for (int k = 0; k < P; ++k) {
-                const int ix = (int)(ta[k].pk & 1023u) - lo[0], iy = (int)((ta[k].pk >> 10) & 1023u) - lo[1], iz = (int)(ta[k].pk >> 20) - lo[2];
-                const float* t0 = tile + ((iz * by + iy) * 16 + ix);
-                v00[k] = float2u{t0[0], t0[1]};                       // (x0, x1) at (y0, z0)
-                v10[k] = float2u{t0[16], t0[17]};                     // (y1, z0)
-                v01[k] = float2u{t0[by * 16], t0[by * 16 + 1]};       // (y0, z1)
-                v11[k] = float2u{t0[by * 16 + 16], t0[by * 16 + 17]}; // (y1, z1)
-            }
-            __syncthreads();  // the next pass overwrites the tile
-        } else {
-#pragma unroll
-            for (int k = 0; k < P; ++k) {
-                const float* q = lut + ta[k].o;
-                v00[k] = *(const float2u*)(q);
-                v10[k] = *(const float2u*)(q + sy);
-                v01[k] = *(const float2u*)(q + sz);
-                v11[k] = *(const float2u*)(q + sz + sy);
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < P; ++k) {
-            const float dsq = lut_blend(ta[k], v00[k], v10[k], v01[k], v11[k]);  // :46
-            float d = sqrtf(dsq);                                                 // :48
-            const int i = first + k * 64;
-            const bool valid = i < ns;
-            if (TRIM) {
-                if (valid) {
-                    if (dual) {
-                        trim_store(evals, (size_t)sb.out0 * erow, i, d > 0.0f ? d : 0.0f, samp_shift, ns);
-                        d -= 2.0f * p[k].w * gr.sin_half;
-                        trim_store(evals, (size_t)sb.out1 * erow, i, d > 0.0f ? d : 0.0f, samp_shift, ns);
-                    } else {
-                        if (!gr.fix_rot) d -= 2.0f * p[k].w * gr.sin_half;
-                        trim_store(evals, (size_t)sb.out0 * erow, i, d > 0.0f ? d : 0.0f, samp_shift, ns);
-                    }
-                }
-                continue;
-            }
-            if (dual) {
-                const float ub1 = d > 0.0f ? d * d : 0.0f;
-                const float l1 = d - trans_uncertain_radius;
-                const float lb1 = l1 > 0.0f ? l1 * l1 : 0.0f;
-                d -= 2.0f * p[k].w * gr.sin_half;
-                const float ub0 = d > 0.0f ? d * d : 0.0f;
-                const float l0 = d - trans_uncertain_radius;
-                const float lb0 = l0 > 0.0f ? l0 * l0 : 0.0f;
-                acc[0] += valid ? (double)ub1 : 0.0;
-                acc[1] += valid ? (double)lb1 : 0.0;
-                acc[2] += valid ? (double)ub0 : 0.0;
-                acc[3] += valid ? (double)lb0 : 0.0;
-                continue;
-            }
-            if (!gr.fix_rot) d -= 2.0f * p[k].w * gr.sin_half;
-            const float ubv = d > 0.0f ? d * d : 0.0f;
-            const float l = d - trans_uncertain_radius;
-            const float lbv = l > 0.0f ? l * l : 0.0f;
-            acc[0] += valid ? (double)ubv : 0.0;
-            acc[1] += valid ? (double)lbv : 0.0;
-        }
-    }
-    if (stat && tix == 0) { atomicAdd(&stat[0], staged_passes); atomicAdd(&stat[1], all_passes); }
-    if (TRIM) return;
-    const double r0 = wave_sum(acc[0]), r1 = wave_sum(acc[1]);
-    if (dual) {
-        const double r2 = wave_sum(acc[2]), r3 = wave_sum(acc[3]);
-        if (tix == 0) {
-            partials[(size_t)sb.out0 * nchunk + chunk] = make_double2(r0, r1);
-            partials[(size_t)sb.out1 * nchunk + chunk] = make_double2(r2, r3);
-        }
-    } else if (tix == 0) {
-        partials[(size_t)sb.out0 * nchunk + chunk] = make_double2(r0, r1);
-    }
-}
-
 // ---------------------------------------------------------------------------------------------
 // EXTENSION — trimmed Go-ICP (no reference behaviour: `params.trim` is parsed and ignored upstream).
 // Per output row (one subcube variant) the bounds kernel leaves n values e_i = max(d_i, 0) >= 0; with r_t = sqrt3 * span
@@ -2297,8 +1647,8 @@ __global__ __launch_bounds__(64 * kMaxParts) void nn_scan_kernel(const float4* p
                                                                  const uint32_t* seed_idx, const float* __restrict__ skip_lb, const uint32_t* __restrict__ skip_u, uint32_t* out,
                                                                  float4* writeback, const float* __restrict__ rt_dev, const int* __restrict__ done,
                                                                  double* __restrict__ wsum, int dynamic_claim, int flat_walk) {
-    if (done && *done) return;  // device-resident ICP loop: the run has ended, this pass was enqueued ahead of the decision
-    if (rt_dev) {               // ... and the motion is the one the step kernel left in device memory (12 floats: R, t)
+    if (done && *done) return;  // optional: the caller has ended the run, this pass was enqueued ahead of the decision
+    if (rt_dev) {               // optional: the motion is read from device memory (12 floats: R, t)
 #pragma unroll
         for (int k = 0; k < 9; ++k) rt.R[k] = rt_dev[k];
 #pragma unroll
@@ -2764,10 +2114,10 @@ __global__ __launch_bounds__(kBlock) void icp_cov_kernel(const float4* __restric
     if (threadIdx.x < 9) bp[(size_t)blockIdx.x * 9 + threadIdx.x] = r;
 }
 
-// The same with icp_centroids_kernel folded in (device-resident ICP loop: one launch less on the iteration's chain): every block
+// The same with icp_centroids_kernel folded in (one launch less on the iteration's chain): every block
 // reduces the block partials of icp_sums_kernel itself — per component one wave, lane-strided partial sums + the shuffle tree,
 // rounded to fp32, divided by float(ns): the arithmetic and order of icp_centroids_kernel, hence the same bits — and block 0
-// leaves the centroids in device memory for the step kernel.
+// leaves the centroids in device memory.
 __global__ __launch_bounds__(kBlock) void icp_cov_cen_kernel(const float4* __restrict__ work, const float4* __restrict__ tgt,
                                                              const uint32_t* __restrict__ idx, int n, int nt, const double* __restrict__ sums_bp,
                                                              int sums_nblocks, int from_waves, float* __restrict__ cen_out, double* __restrict__ bp,
@@ -2812,84 +2162,6 @@ __global__ __launch_bounds__(kBlock) void icp_cov_cen_kernel(const float4* __res
     if (threadIdx.x < 9) bp[(size_t)blockIdx.x * 9 + threadIdx.x] = r;
 }
 
-// ---------------------------------------------------------------------------------------------
-// Device-resident ICP loop (IterativeClosestPoint3D::run, icp3d.cu:88-107).  The host loop needs the covariance on the host for
-// the 3x3 SVD and the SSE for the loop test — two host round trips per iteration, 18 us of a 90-us iteration at 40k points.
-// Here the state of the loop lives in device memory (IcpDevState) and ONE thread advances it:
-//   step j  =  [loop test of icp3d.cu:94 with the SSE of iteration j-1]  +  [Procrustes finish of iteration j: cross-covariance
-//               from the block partials, closest_orthogonal_approximation (math3.hpp, the host's source compiled for the device),
-//               t_ = c_corr - R_ c_src, R = R_ R, t = R_ t + t_]
-// so the passes of iteration j+1 can be enqueued before iteration j has been decided: every kernel of the loop returns at once
-// when `done` is set, and the scans take their motion from the state instead of the kernarg segment.  Sums are folded exactly
-// as sum_partials_kernel folds them (one wave per component, lane-strided, shuffle tree), so (sse, R, t, iterations) are the bits
-// of the host loop (FGOICP_ICP_DEVICE=0; tests/test_gpu_ops.py).
-// ---------------------------------------------------------------------------------------------
-__global__ void icp_init_kernel(IcpDevState* __restrict__ st, Rt rt0, int max_iter, float thr, IcpHostResult* __restrict__ res) {
-    if (threadIdx.x != 0) return;
-    for (int k = 0; k < 9; ++k) { st->R[k] = rt0.R[k]; st->Rn[k] = rt0.R[k]; st->last_R[k] = (k % 4 == 0) ? 1.0f : 0.0f; }
-    for (int k = 0; k < 3; ++k) { st->t[k] = rt0.t[k]; st->tn[k] = rt0.t[k]; st->last_t[k] = 0.0f; }
-    st->sse = kInf;                 // icp3d.cu:89-90
-    st->last_sse = 2.0f * kInf;
-    st->iters = 0;
-    st->done = 0;
-    st->max_iter = max_iter;
-    st->thr = thr;
-    res->iters_done = 0;
-    res->done = 0;
-}
-
-__global__ __launch_bounds__(640) void icp_step_kernel(IcpDevState* __restrict__ st, const double* __restrict__ bp_cov, int nb_cov,
-                                                       const double* __restrict__ bp_sse, int nb_sse, const float* __restrict__ cen,
-                                                       IcpHostResult* __restrict__ res) {
-    if (st->done) return;
-    __shared__ double red[10];
-    {   // sum_partials_kernel's fold: wave k < 9 the covariance component k, wave 9 the SSE of the iteration before
-        const int k = threadIdx.x >> 6, lane = threadIdx.x & 63;
-        const double* bp = k < 9 ? bp_cov : bp_sse;
-        const int nb = k < 9 ? nb_cov : nb_sse, width = k < 9 ? 9 : 1, col = k < 9 ? k : 0;
-        double s = 0.0;
-        for (int b = lane; b < nb; b += 64) s += bp[(size_t)b * width + col];
-        s = wave_sum(s);
-        if (lane == 0) red[k] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    const int it = st->iters;                       // iterations completed = `iter` of icp3d.cu:94 before its post-increment
-    float sse = st->sse, last_sse = st->last_sse;
-    if (it > 0) sse = (float)red[9];                // sse = reg.compute_sse_error(R, t) of iteration `it` (:103)
-    Mat3f R = Mat3f::from(st->R);
-    Vec3f t{st->t[0], st->t[1], st->t[2]};
-    const bool go_on = it < st->max_iter && (last_sse - sse) > st->thr * last_sse;   // :94
-    if (!go_on) {
-        const bool cur_best = sse < last_sse;       // :106-107
-        res->sse = cur_best ? sse : last_sse;
-        for (int k = 0; k < 9; ++k) res->R[k] = cur_best ? R.m[k] : st->last_R[k];
-        for (int k = 0; k < 3; ++k) res->t[k] = cur_best ? st->t[k] : st->last_t[k];
-        res->iters = it;
-        st->sse = sse;
-        st->done = 1;
-        __threadfence_system();
-        *(volatile int*)&res->done = 1;
-        return;
-    }
-    for (int k = 0; k < 9; ++k) st->last_R[k] = R.m[k];   // :96-98
-    for (int k = 0; k < 3; ++k) st->last_t[k] = st->t[k];
-    st->last_sse = sse;
-    st->sse = sse;
-    Mat3f ABt;
-    for (int k = 0; k < 9; ++k) ABt.m[k] = (float)red[k];
-    const Mat3f Rn = closest_orthogonal_approximation(ABt);  // :168
-    const Vec3f sc{cen[0], cen[1], cen[2]}, cc{cen[3], cen[4], cen[5]};
-    const Vec3f tn = cc - Rn * sc;                             // :169
-    R = Rn * R;                                                // :101
-    t = Rn * t + tn;                                           // :102
-    for (int k = 0; k < 9; ++k) { st->R[k] = R.m[k]; st->Rn[k] = Rn.m[k]; }
-    st->t[0] = t.x; st->t[1] = t.y; st->t[2] = t.z;
-    st->tn[0] = tn.x; st->tn[1] = tn.y; st->tn[2] = tn.z;
-    st->iters = it + 1;
-    *(volatile int*)&res->iters_done = it + 1;  // progress hint for the host's look-ahead (no ordering needed: the host only paces itself by it)
-}
-
 // Centroids on the device (icp3d.cu:152-156): ordered fp64 sum of the block partials, rounded to fp32,
 // divided by float(ns) in fp32 (correctly rounded division, as on the host).  Written both to device
 // memory (for icp_cov_kernel) and to pinned host memory (for t_ = c_corr - R_ * c_src).
@@ -2927,177 +2199,28 @@ int nn_slices(int nq, int nt) {
 // ---------------------------------------------------------------------------------------------
 // launch wrappers
 // ---------------------------------------------------------------------------------------------
-void launch_bounds(const float4* src, int ns, const float* lut, const LutGeom& g, const BoundsArgs& a, double2* partials, int nchunk,
-                   int P, hipStream_t s) {
-#ifndef FGOICP_DEV_KNOBS
-    (void)src; (void)ns; (void)lut; (void)g; (void)a; (void)partials; (void)nchunk; (void)P; (void)s;  // the per-rotation-node kernel is the development build's A/B reference (FGOICP_BOUNDS_SORTED=0)
-#else
-    dim3 grid((unsigned)nchunk * (unsigned)a.B), block(kBlock);
-    switch (P) {
-        case 1: hipLaunchKernelGGL(bounds_kernel<1>, grid, block, 0, s, src, ns, lut, g, a, partials, nchunk); break;
-        case 2: hipLaunchKernelGGL(bounds_kernel<2>, grid, block, 0, s, src, ns, lut, g, a, partials, nchunk); break;
-        case 4: hipLaunchKernelGGL(bounds_kernel<4>, grid, block, 0, s, src, ns, lut, g, a, partials, nchunk); break;
-        default: hipLaunchKernelGGL(bounds_kernel<8>, grid, block, 0, s, src, ns, lut, g, a, partials, nchunk); break;
-    }
-#endif
-}
-
-// The locality sort of one tick (descriptors must already be on the device): keys + histogram, scan, scatter.
+// The locality sort of one tick (descriptors must already be on the device): Hilbert keys with ranks from the histogram atomic, scan,
+// scatter (the scatter needs no atomics of its own).
 void launch_tick_sort(const LutGeom& g, const float4* chunk_cen, int nchunk, const TickGroup* groups, const TickSub* subs, int nsub, int cell_shift,
                       unsigned short* keys, unsigned* ranks, unsigned* hist, unsigned* hist_xcd, unsigned* xoff, unsigned* block_sums, unsigned* cursor, unsigned* sorted,
-                      int allow_xcd, int prefill, unsigned* check_err, int inject_fault, hipStream_t s, int nunits, int unit_m, const float* tier_lut, float tier_level) {
-    const size_t nitems = (size_t)(nsub - nunits * (unit_m - 1)) * nchunk;
+                      int allow_xcd, int prefill, int inject_fault, hipStream_t s, const float* tier_lut, float tier_level) {
+    const size_t nitems = (size_t)nsub * nchunk;
     const unsigned kb = (unsigned)std::min<size_t>((nitems + 63) / 64, 8192);  // `hist` / `hist_xcd` are zero here: the scan / fold kernels re-zero them
-#ifdef FGOICP_DEV_KNOBS
-    static const int hilbert = [] { const char* e = dev_env("FGOICP_SORT_CURVE"); return e ? std::atoi(e) : 1; }();  // tuning knob: 1 = Hilbert (default), 0 = Z-order
-    static const int use_ranks = [] { const char* e = dev_env("FGOICP_SORT_RANKS"); return e ? std::atoi(e) : 1; }();  // tuning knob
-    static const int orient = [] { const char* e = dev_env("FGOICP_SORT_ORIENT"); return e ? std::atoi(e) : 0; }();  // tuning knob (experimental): orientation bits in the sort key
-#else
-    constexpr int orient = 0;  // shipped: Hilbert keys, ranks from the histogram atomic (the scatter needs no atomics of its own)
-#endif
-    const bool xcd = allow_xcd != 0 && hist_xcd && xoff
-#ifdef FGOICP_DEV_KNOBS
-                     && use_ranks != 0
-#endif
-        ;  // allow_xcd: per context, cleared by a failed permutation check
+    const bool xcd = allow_xcd != 0 && hist_xcd && xoff;  // allow_xcd: per context, cleared by a failed permutation check
     if (xcd) {
-#ifdef FGOICP_DEV_KNOBS
-        if (!hilbert) hipLaunchKernelGGL((tick_keys_kernel<0, 1>), dim3(kb), dim3(64), 0, s, chunk_cen, nchunk, groups, subs, nsub, g, cell_shift, keys, ranks, hist_xcd, prefill ? sorted : nullptr, nunits, unit_m, orient, tier_lut, tier_level);
-        else
-#endif
-        hipLaunchKernelGGL((tick_keys_kernel<1, 1>), dim3(kb), dim3(64), 0, s, chunk_cen, nchunk, groups, subs, nsub, g, cell_shift, keys, ranks, hist_xcd, prefill ? sorted : nullptr, nunits, unit_m, orient, tier_lut, tier_level);
+        hipLaunchKernelGGL(tick_keys_kernel<1>, dim3(kb), dim3(64), 0, s, chunk_cen, nchunk, groups, subs, nsub, g, cell_shift, keys, ranks, hist_xcd, prefill ? sorted : nullptr, tier_lut, tier_level);
         hipLaunchKernelGGL(tick_fold_sums_kernel, dim3(kScanBlocks), dim3(64), 0, s, hist_xcd, xoff, hist, block_sums);
     } else {
-#ifdef FGOICP_DEV_KNOBS
-        if (!hilbert) hipLaunchKernelGGL((tick_keys_kernel<0, 0>), dim3(kb), dim3(64), 0, s, chunk_cen, nchunk, groups, subs, nsub, g, cell_shift, keys, ranks, hist, prefill ? sorted : nullptr, nunits, unit_m, orient, tier_lut, tier_level);
-        else
-#endif
-        hipLaunchKernelGGL((tick_keys_kernel<1, 0>), dim3(kb), dim3(64), 0, s, chunk_cen, nchunk, groups, subs, nsub, g, cell_shift, keys, ranks, hist, prefill ? sorted : nullptr, nunits, unit_m, orient, tier_lut, tier_level);
+        hipLaunchKernelGGL(tick_keys_kernel<0>, dim3(kb), dim3(64), 0, s, chunk_cen, nchunk, groups, subs, nsub, g, cell_shift, keys, ranks, hist, prefill ? sorted : nullptr, tier_lut, tier_level);
+        hipLaunchKernelGGL(tick_scan_sums_kernel, dim3(kScanBlocks), dim3(64), 0, s, hist, block_sums);
     }
-    if (!xcd) hipLaunchKernelGGL(tick_scan_sums_kernel, dim3(kScanBlocks), dim3(64), 0, s, hist, block_sums);
     hipLaunchKernelGGL(tick_scan_apply_kernel, dim3(kScanBlocks), dim3(64), 0, s, hist, block_sums, cursor);
     if (xcd) hipLaunchKernelGGL(tick_scatter_xcd_kernel, dim3(kb), dim3(64), 0, s, keys, ranks, nitems, cursor, xoff, sorted);
-#ifdef FGOICP_DEV_KNOBS
-    else if (!use_ranks) hipLaunchKernelGGL(tick_scatter_atomic_kernel, dim3(kb), dim3(64), 0, s, keys, nitems, cursor, sorted);
-#endif
     else hipLaunchKernelGGL(tick_scatter_kernel, dim3(kb), dim3(64), 0, s, keys, ranks, nitems, cursor, sorted);
     if (inject_fault) hipLaunchKernelGGL(tick_fault_kernel, dim3(1), dim3(1), 0, s, sorted);
-#ifdef FGOICP_DEV_KNOBS
-    if (check_err) hipLaunchKernelGGL(tick_check_kernel, dim3(kb), dim3(64), 0, s, sorted, nitems, check_err);  // FGOICP_SEPARATE_CHECK=1 (ctx.hip)
-#endif
 }
-
-#ifdef FGOICP_DEV_KNOBS
-// development build: does a knob select one of round 3's kernels (which know neither thresholds nor chunk spans) for this context's windows?
-bool bounds_dev_variant_selected(const float2* zp, int layout, int unit_m) {
-    const int lds_rows = [] { const char* e = dev_env("FGOICP_LDS_TILES"); return e ? std::atoi(e) : 0; }();
-    const int item_kernel = [] { const char* e = dev_env("FGOICP_BOUNDS_ITEM"); return e ? std::atoi(e) : 1; }();
-    return lds_rows == 128 || lds_rows == 192 || unit_m > 1 || !item_kernel || dev_env("FGOICP_BOUNDS_VARIANT") || dev_env("FGOICP_ITEMS_PER_WG") || dev_env("FGOICP_NT_SOURCE") ||
-           dev_env("FGOICP_TRIM_VARIANT") || dev_env("FGOICP_QUAD_PAIRED") || dev_env("FGOICP_LDS_PAD") || !zp || layout == 3;
-}
-// Round 3's launch logic with every variant behind its knob; false = nothing launched (the shipped kernel follows).
-static bool launch_bounds_sorted_dev(const float4* src, int ns, const float* lut, const float2* zp, int layout, const LutGeom& g, int nchunk, int chunk_pts,
-                                     const TickGroup* groups, const TickSub* subs, int nsub, const unsigned* sorted, double2* partials, float* evals, size_t erow, int samp_shift,
-                                     hipStream_t s, int nunits, int unit_m) {
-    const hipEvent_t ev_start = nullptr, ev_stop = nullptr;  // (recorded by the caller)
-    const size_t nitems = (size_t)(nsub - nunits * (unit_m - 1)) * nchunk;
-    const int lds_rows = [] { const char* e = dev_env("FGOICP_LDS_TILES"); return e ? std::atoi(e) : 0; }();  // tuning knob / A-B (read per launch: tests toggle it): 128 or 192 rows of 16 floats per wave
-    if (nunits == 0 && (lds_rows == 128 || lds_rows == 192) && lut) {
-        static unsigned* d_stat = [] { unsigned* p = nullptr; if (dev_env("FGOICP_LDS_STATS")) { (void)hipMalloc(&p, 8); (void)hipMemset(p, 0, 8); } return p; }();
-        if (ev_start) (void)hipEventRecord(ev_start, s);
-        const dim3 lgrid((unsigned)nitems);
-        if (evals) {
-            if (lds_rows == 128) hipLaunchKernelGGL((bounds_lds_kernel<1, 128>), lgrid, dim3(64), 0, s, src, ns, lut, g, groups, subs, sorted, nchunk, chunk_pts, partials, evals, erow, samp_shift, (unsigned)nitems, d_stat);
-            else hipLaunchKernelGGL((bounds_lds_kernel<1, 192>), lgrid, dim3(64), 0, s, src, ns, lut, g, groups, subs, sorted, nchunk, chunk_pts, partials, evals, erow, samp_shift, (unsigned)nitems, d_stat);
-        } else {
-            if (lds_rows == 128) hipLaunchKernelGGL((bounds_lds_kernel<0, 128>), lgrid, dim3(64), 0, s, src, ns, lut, g, groups, subs, sorted, nchunk, chunk_pts, partials, evals, erow, samp_shift, (unsigned)nitems, d_stat);
-            else hipLaunchKernelGGL((bounds_lds_kernel<0, 192>), lgrid, dim3(64), 0, s, src, ns, lut, g, groups, subs, sorted, nchunk, chunk_pts, partials, evals, erow, samp_shift, (unsigned)nitems, d_stat);
-        }
-        if (ev_stop) (void)hipEventRecord(ev_stop, s);
-        if (d_stat) {
-            static int calls = 0;
-            if ((++calls & 63) == 0) {
-                unsigned h[2] = {0, 0};
-                (void)hipStreamSynchronize(s);
-                (void)hipMemcpy(h, d_stat, 8, hipMemcpyDeviceToHost);
-                std::fprintf(stderr, "[fgoicp lds tiles] %u of %u passes staged (%.1f %%)\n", h[0], h[1], h[1] ? 100.0 * h[0] / h[1] : 0.0);
-            }
-        }
-        return true;
-    }
-    if (nunits > 0) {  // sibling units (dense clouds): the z-pair or plain layouts, one wave per item, 4 points per lane
-        if (ev_start) (void)hipEventRecord(ev_start, s);
-        const dim3 ugrid((unsigned)nitems);
-#define FGOICP_LAUNCH_UNITS(Z, TR, M) \
-        hipLaunchKernelGGL((bounds_units_kernel<Z, TR, M>), ugrid, dim3(64), 0, s, src, ns, lut, zp, g, groups, subs, sorted, nchunk, chunk_pts, partials, evals, erow, samp_shift, (unsigned)nitems, nunits)
-        const int z = (zp && layout == 2) ? 2 : zp ? 1 : 0;
-        if (evals) {
-            if (unit_m == 8) { if (z == 2) FGOICP_LAUNCH_UNITS(2, 1, 8); else if (z == 1) FGOICP_LAUNCH_UNITS(1, 1, 8); else FGOICP_LAUNCH_UNITS(0, 1, 8); }
-            else { if (z == 2) FGOICP_LAUNCH_UNITS(2, 1, 4); else if (z == 1) FGOICP_LAUNCH_UNITS(1, 1, 4); else FGOICP_LAUNCH_UNITS(0, 1, 4); }
-        } else {
-            if (unit_m == 8) { if (z == 2) FGOICP_LAUNCH_UNITS(2, 0, 8); else if (z == 1) FGOICP_LAUNCH_UNITS(1, 0, 8); else FGOICP_LAUNCH_UNITS(0, 0, 8); }
-            else { if (z == 2) FGOICP_LAUNCH_UNITS(2, 0, 4); else if (z == 1) FGOICP_LAUNCH_UNITS(1, 0, 4); else FGOICP_LAUNCH_UNITS(0, 0, 4); }
-        }
-#undef FGOICP_LAUNCH_UNITS
-        if (ev_stop) (void)hipEventRecord(ev_stop, s);
-        return true;
-    }
-    // FGOICP_BOUNDS_ITEM (default 1): 0 = round 3's kernel family below instead of bounds_item_kernel; the variants further down imply it
-    const int item_kernel = [] { const char* e = dev_env("FGOICP_BOUNDS_ITEM"); return e ? std::atoi(e) : 1; }();  // (read per launch: tests toggle it)
-    const bool other_variant = dev_env("FGOICP_BOUNDS_VARIANT") || dev_env("FGOICP_ITEMS_PER_WG") || dev_env("FGOICP_NT_SOURCE") || dev_env("FGOICP_TRIM_VARIANT") || dev_env("FGOICP_QUAD_PAIRED") ||
-                               dev_env("FGOICP_LDS_PAD") || !zp || layout == 3;
-    if (item_kernel && !other_variant) return false;
-    const TickGroup* gp = groups;
-    const TickSub* sp = subs;
-    static const int variant = [] { const char* e = dev_env("FGOICP_BOUNDS_VARIANT"); return e ? std::atoi(e) : 2; }();  // tuning knob (2 = default: one wave, 4 points per lane)
-    const dim3 grid((unsigned)nitems);
-    static const int wpg = [] { const char* e = dev_env("FGOICP_ITEMS_PER_WG"); return e ? std::atoi(e) : 1; }();   // tuning knob: 1, 2 or 4 one-wave items per workgroup
-    static const int nt_src = [] { const char* e = dev_env("FGOICP_NT_SOURCE"); return e ? std::atoi(e) : 0; }();   // tuning knob: non-temporal source loads
-    static const unsigned lds_pad = [] { const char* e = dev_env("FGOICP_LDS_PAD"); return e ? (unsigned)std::atoi(e) : 0u; }();  // tuning knob: unused dynamic LDS per workgroup = fewer resident waves per CU
-#define FGOICP_LAUNCH_SORTED(T, PP, Z, TR) \
-    hipLaunchKernelGGL((bounds_sorted_kernel<T, PP, Z, TR>), grid, dim3(T), lds_pad, s, src, ns, lut, zp, g, gp, sp, sorted, nchunk, chunk_pts, partials, evals, erow, samp_shift, (unsigned)nitems)
-#define FGOICP_LAUNCH_WPG(Z, W, N) \
-    hipLaunchKernelGGL((bounds_sorted_kernel<64, 4, Z, 0, W, N>), dim3((unsigned)((nitems + W - 1) / W)), dim3(64 * W), 0, s, src, ns, lut, zp, g, gp, sp, sorted, nchunk, chunk_pts, partials, evals, erow, samp_shift, (unsigned)nitems)
-    if (!evals && variant == 2 && (wpg > 1 || nt_src)) {  // experimental variants of the default 64 x 4 kernel
-        const int z = (zp && layout == 2) ? 3 : zp ? 1 : 0;
-        bool done = true;
-        if (z == 3) { if (wpg == 4 && nt_src) FGOICP_LAUNCH_WPG(3, 4, 1); else if (wpg == 4) FGOICP_LAUNCH_WPG(3, 4, 0); else if (wpg == 2 && nt_src) FGOICP_LAUNCH_WPG(3, 2, 1); else if (wpg == 2) FGOICP_LAUNCH_WPG(3, 2, 0); else if (nt_src) FGOICP_LAUNCH_WPG(3, 1, 1); else done = false; }
-        else if (z == 1) { if (wpg == 4 && nt_src) FGOICP_LAUNCH_WPG(1, 4, 1); else if (wpg == 4) FGOICP_LAUNCH_WPG(1, 4, 0); else if (wpg == 2 && nt_src) FGOICP_LAUNCH_WPG(1, 2, 1); else if (wpg == 2) FGOICP_LAUNCH_WPG(1, 2, 0); else if (nt_src) FGOICP_LAUNCH_WPG(1, 1, 1); else done = false; }
-        else done = false;
-        if (done) return true;
-    }
-    if (evals) {
-        static const int trim_variant = [] { const char* e = dev_env("FGOICP_TRIM_VARIANT"); return e ? std::atoi(e) : 2; }();  // tuning knob (2 = 64x4, default)
-        if (trim_variant == 2) {
-            if (zp && layout == 4) FGOICP_LAUNCH_SORTED(64, 4, 5, 1); else
-            if (zp && layout == 2) FGOICP_LAUNCH_SORTED(64, 4, 3, 1); else if (zp) FGOICP_LAUNCH_SORTED(64, 4, 1, 1); else FGOICP_LAUNCH_SORTED(64, 4, 0, 1);
-        } else if (zp && layout == 2) FGOICP_LAUNCH_SORTED(128, 2, 2, 1); else if (zp) FGOICP_LAUNCH_SORTED(128, 2, 1, 1); else FGOICP_LAUNCH_SORTED(128, 2, 0, 1);
-    } else if (zp && layout == 3) {
-        FGOICP_LAUNCH_SORTED(64, 4, 4, 0);
-    } else if (zp && layout == 4) {
-        FGOICP_LAUNCH_SORTED(64, 4, 5, 0);
-    } else if (zp && layout == 2) {
-        static const int paired = [] { const char* e = dev_env("FGOICP_QUAD_PAIRED"); return e ? std::atoi(e) : 1; }();  // tuning knob (1 = default)
-        if (variant == 2 && paired) FGOICP_LAUNCH_SORTED(64, 4, 3, 0); else
-        if (variant == 0) FGOICP_LAUNCH_SORTED(256, 1, 2, 0); else if (variant == 2) FGOICP_LAUNCH_SORTED(64, 4, 2, 0);
-        else if (variant == 3) FGOICP_LAUNCH_SORTED(64, 2, 2, 0); else if (variant == 4) FGOICP_LAUNCH_SORTED(64, 1, 2, 0); else FGOICP_LAUNCH_SORTED(128, 2, 2, 0);
-    } else if (zp) {
-        if (variant == 0) FGOICP_LAUNCH_SORTED(256, 1, 1, 0); else if (variant == 2) FGOICP_LAUNCH_SORTED(64, 4, 1, 0);
-        else if (variant == 3) FGOICP_LAUNCH_SORTED(64, 2, 1, 0); else if (variant == 4) FGOICP_LAUNCH_SORTED(64, 1, 1, 0); else FGOICP_LAUNCH_SORTED(128, 2, 1, 0);
-    } else {
-        if (variant == 0) FGOICP_LAUNCH_SORTED(256, 1, 0, 0); else if (variant == 2) FGOICP_LAUNCH_SORTED(64, 4, 0, 0); else FGOICP_LAUNCH_SORTED(128, 2, 0, 0);
-    }
-#undef FGOICP_LAUNCH_SORTED
-#undef FGOICP_LAUNCH_WPG
-    return true;
-}
-
-#endif  // FGOICP_DEV_KNOBS
-
-// The bounds kernel of a window.  Shipped: bounds_item_kernel (bounds_item.hpp), one instantiation per packed layout x trimmed x wide
-// addressing x weight quantisation.  Development build: FGOICP_BOUNDS_ITEM=0 runs round 3's bounds_sorted_kernel family instead (the
-// bit reference of tests/test_gpu_ops.py::test_item_kernel_keeps_every_bit), and the variants that were measured and rejected —
-// sibling units, LDS tiles, several items per workgroup, other thread / point shapes — stay selectable by their knobs (NOTES.md).
+// The bounds kernel of a window: bounds_item_kernel (bounds_item.hpp), one instantiation per packed layout x trimmed x wide addressing x
+// weight quantisation x chunk spans.
 template <int LAYOUT, int TRIM>
 static void launch_item(const float4* src, int ns, const char* lutp, const LutGeom& g, bool wide, const TickGroup* groups, const TickSub* subs, const unsigned* sorted, int nchunk,
                         int chunk_pts, double2* partials, float* evals, size_t erow, int samp_shift, unsigned nitems, unsigned* sort_err, const TickCut& cut, int span, hipStream_t s) {
@@ -3111,37 +2234,27 @@ static void launch_item(const float4* src, int ns, const char* lutp, const LutGe
 #undef FGOICP_ITEM
 }
 
-bool launch_bounds_sorted(const float4* src, int ns, const float* lut, const float2* zp, int layout, const LutGeom& g, int nchunk, int chunk_pts,
-                          const TickGroup* groups, const TickSub* subs, int nsub, const unsigned* sorted, double2* partials, float* evals, size_t erow, int samp_shift,
-                          unsigned* sort_err, const TickCut& cut, int span, hipEvent_t ev_start, hipEvent_t ev_stop, hipStream_t s, int nunits, int unit_m) {
-    const size_t nitems = (size_t)(nsub - nunits * (unit_m - 1)) * (size_t)((nchunk + span - 1) / span);
+bool launch_bounds_sorted(const float4* src, int ns, const float2* packed, int layout, const LutGeom& g, int nchunk, int chunk_pts, const TickGroup* groups,
+                          const TickSub* subs, int nsub, const unsigned* sorted, double2* partials, float* evals, size_t erow, int samp_shift, unsigned* sort_err,
+                          const TickCut& cut, int span, hipEvent_t ev_start, hipEvent_t ev_stop, hipStream_t s) {
+    const unsigned nitems = (unsigned)((size_t)nsub * (size_t)((nchunk + span - 1) / span));
+    const size_t nodes = (size_t)g.px * g.py * g.pz;
+    // 32-bit texel addressing: the row number (z * py + y) must fit the signed 24-bit multiply and the byte offsets of the packed copy 32 bits
+    const size_t bytes = layout == 4 ? (size_t)((g.px + 2) / 3) * ((g.py + 1) / 2) * g.pz * 8 * sizeof(float4) : nodes * (layout == 2 ? sizeof(float4) : sizeof(float2));
+    const bool wide = (size_t)g.py * g.pz > ((size_t)1 << 23) || bytes + 64 > ((size_t)1 << 32);
+    const char* lutp = reinterpret_cast<const char*>(packed);
     if (ev_start) (void)hipEventRecord(ev_start, s);
-    bool done = false, item_kernel = false;
-#ifdef FGOICP_DEV_KNOBS
-    done = launch_bounds_sorted_dev(src, ns, lut, zp, layout, g, nchunk, chunk_pts, groups, subs, nsub, sorted, partials, evals, erow, samp_shift, s, nunits, unit_m);
-    // round 3's kernels do not look at the values they read from `sorted`: their check is a launch of its own
-    if (done && sorted && sort_err) hipLaunchKernelGGL(tick_check_kernel, dim3((unsigned)std::min<size_t>((nitems + 63) / 64, 4096)), dim3(64), 0, s, sorted, nitems, sort_err);
-#endif
-    if (!done && zp && (layout == 1 || layout == 2 || layout == 4) && nunits == 0) {
-        const size_t nodes = (size_t)g.px * g.py * g.pz;
-        // 32-bit texel addressing: the row number (z * py + y) must fit the signed 24-bit multiply and the byte offsets of the packed copy 32 bits
-        const size_t bytes = layout == 4 ? (size_t)((g.px + 2) / 3) * ((g.py + 1) / 2) * g.pz * 8 * sizeof(float4) : nodes * (layout == 2 ? sizeof(float4) : sizeof(float2));
-        const bool wide = (size_t)g.py * g.pz > ((size_t)1 << 23) || bytes + 64 > ((size_t)1 << 32);
-        const char* lutp = reinterpret_cast<const char*>(zp);
-        if (evals) {
-            if (layout == 1) launch_item<1, 1>(src, ns, lutp, g, wide, groups, subs, sorted, nchunk, chunk_pts, partials, evals, erow, samp_shift, (unsigned)nitems, sort_err, cut, span, s);
-            else if (layout == 2) launch_item<3, 1>(src, ns, lutp, g, wide, groups, subs, sorted, nchunk, chunk_pts, partials, evals, erow, samp_shift, (unsigned)nitems, sort_err, cut, span, s);
-            else launch_item<5, 1>(src, ns, lutp, g, wide, groups, subs, sorted, nchunk, chunk_pts, partials, evals, erow, samp_shift, (unsigned)nitems, sort_err, cut, span, s);
-        } else {
-            if (layout == 1) launch_item<1, 0>(src, ns, lutp, g, wide, groups, subs, sorted, nchunk, chunk_pts, partials, evals, erow, samp_shift, (unsigned)nitems, sort_err, cut, span, s);
-            else if (layout == 2) launch_item<3, 0>(src, ns, lutp, g, wide, groups, subs, sorted, nchunk, chunk_pts, partials, evals, erow, samp_shift, (unsigned)nitems, sort_err, cut, span, s);
-            else launch_item<5, 0>(src, ns, lutp, g, wide, groups, subs, sorted, nchunk, chunk_pts, partials, evals, erow, samp_shift, (unsigned)nitems, sort_err, cut, span, s);
-        }
-        done = item_kernel = true;
+    if (evals) {
+        if (layout == 1) launch_item<1, 1>(src, ns, lutp, g, wide, groups, subs, sorted, nchunk, chunk_pts, partials, evals, erow, samp_shift, nitems, sort_err, cut, span, s);
+        else if (layout == 2) launch_item<3, 1>(src, ns, lutp, g, wide, groups, subs, sorted, nchunk, chunk_pts, partials, evals, erow, samp_shift, nitems, sort_err, cut, span, s);
+        else launch_item<5, 1>(src, ns, lutp, g, wide, groups, subs, sorted, nchunk, chunk_pts, partials, evals, erow, samp_shift, nitems, sort_err, cut, span, s);
+    } else {
+        if (layout == 1) launch_item<1, 0>(src, ns, lutp, g, wide, groups, subs, sorted, nchunk, chunk_pts, partials, evals, erow, samp_shift, nitems, sort_err, cut, span, s);
+        else if (layout == 2) launch_item<3, 0>(src, ns, lutp, g, wide, groups, subs, sorted, nchunk, chunk_pts, partials, evals, erow, samp_shift, nitems, sort_err, cut, span, s);
+        else launch_item<5, 0>(src, ns, lutp, g, wide, groups, subs, sorted, nchunk, chunk_pts, partials, evals, erow, samp_shift, nitems, sort_err, cut, span, s);
     }
-    if (!done) std::fprintf(stderr, "fgoicp: no bounds kernel for packed layout %d in this build\n", layout);  // (ctx_create only chooses layouts 1, 2, 4 outside the development build)
     if (ev_stop) (void)hipEventRecord(ev_stop, s);
-    return item_kernel && cut.acc && !evals;  // the early exit was in force (round 3's kernels in the development build do not know it: exact rows then)
+    return cut.acc && !evals;  // the early exit was in force (trimmed windows carry no thresholds: exact rows)
 }
 
 void launch_tick_upload(const TickGroup* h_groups, TickGroup* d_groups, int ngroups, const TickSub* h_subs, TickSub* d_subs, int nsubs, hipStream_t s) {
@@ -3160,14 +2273,6 @@ void launch_lut_build(const float4* tgt_shifted, int nt, const LutGeom& g, float
     const size_t per_block = (size_t)kBlock * kLutNodes;
     const unsigned blocks = (unsigned)((total + per_block - 1) / per_block);
     hipLaunchKernelGGL(lut_build_kernel, dim3(blocks), dim3(kBlock), 0, s, tgt_shifted, nt, g, lut_padded);
-}
-
-void launch_lut_quad_bricked(const float* lut_padded, const LutGeom& g, float4* qd, hipStream_t s) {
-#ifdef FGOICP_DEV_KNOBS   // layout 3 (2 x 2 x 2 quad bricks): measured slower, development build only
-    hipLaunchKernelGGL(lut_quad_bricked_kernel, dim3(8192), dim3(kBlock), 0, s, lut_padded, g, qd);
-#else
-    (void)lut_padded; (void)g; (void)qd; (void)s;
-#endif
 }
 
 void launch_lut_quad_apron(const float* lut_padded, const LutGeom& g, float4* qd, hipStream_t s) {
@@ -3323,16 +2428,6 @@ void launch_icp_cov_cen(const float4* work, const float4* tgt, const uint32_t* i
                         float* cen_out, double* bp, int nblocks, hipStream_t s, const int* done) {
     hipLaunchKernelGGL(icp_cov_cen_kernel, dim3(nblocks), dim3(kBlock), 0, s, work, tgt, idx, n, nt, sums_bp, sums_nblocks, from_waves, cen_out, bp, done);
 }
-
-#ifdef FGOICP_DEV_KNOBS   // the device-resident ICP loop (measured slower than the host loop): development build only
-void launch_icp_init(IcpDevState* st, const float* R9, const float* t3, int max_iter, float thr, IcpHostResult* res, hipStream_t s) {
-    hipLaunchKernelGGL(icp_init_kernel, dim3(1), dim3(64), 0, s, st, make_rt(R9, t3), max_iter, thr, res);
-}
-
-void launch_icp_step(IcpDevState* st, const double* bp_cov, int nb_cov, const double* bp_sse, int nb_sse, const float* cen, IcpHostResult* res, hipStream_t s) {
-    hipLaunchKernelGGL(icp_step_kernel, dim3(1), dim3(640), 0, s, st, bp_cov, nb_cov, bp_sse, nb_sse, cen, res);
-}
-#endif
 
 // trimmed bounds of a window: out_ub[row] / out_lb[row] from the row's k smallest e (trim_rows_kernel)
 void launch_trim_rows(const float* evals, size_t erow, int n, int k, int rows, const float* row_span, float* out_ub, float* out_lb, hipStream_t s,

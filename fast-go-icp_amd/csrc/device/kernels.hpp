@@ -10,7 +10,7 @@ namespace fgoicp {
 
 struct BvhView;
 
-constexpr int kMaxBatch = 32;          // translation nodes per bounds launch (kernarg-resident)
+constexpr int kMaxBatch = 32;          // the fewest subcubes a bounds window holds (FGOICP_MAX_SUBCUBES)
 constexpr int kBlock = 256;            // 4 wave64 per workgroup everywhere
 constexpr float kSqrt3 = 1.732050807568877f;   // fgoicp/common.hpp:19
 constexpr float kPi = 3.141592653589793f;      // fgoicp/common.hpp:17
@@ -30,24 +30,9 @@ struct LutGeom {
                                  // pruning bound with the distance to it (round 3, kernels.hip lut_upper_bound_d2); not read by the bounds kernels
 };
 
-// One bounds launch = one rotation node + up to kMaxBatch translation nodes, passed by value in
-// the kernarg segment (the reference passes RotNode/TransNode by value too, registration.cu:111).
-struct BoundsArgs {
-    float R[9];        // glm::mat3 order (column-major)
-    float sin_half;    // sin(rot_span * sqrt3 * pi / 2), registration.cu:42-43, hoisted to the host
-    int fix_rot;
-    int B;
-    int out_base;      // first row of `partials` this launch writes
-    int pad_;
-    float4 tn[kMaxBatch];   // t.x, t.y, t.z, span
-};
-
-// bounds: partials[(out_base + b) * nchunk + chunk] = {sum_ub, sum_lb} over the chunk's points
-void launch_bounds(const float4* src, int ns, const float* lut, const LutGeom& g, const BoundsArgs& a, double2* partials,
-                   int nchunk, int pts_per_thread, hipStream_t s);
-// Whole-tick variant: all subcubes of all rotation nodes in ONE launch, work items ordered by LUT locality
+// The bounds of a whole tick: all subcubes of all rotation nodes in ONE launch, work items ordered by LUT locality
 // (kernels.hip).  groups/subs are device arrays of TickGroup (48 B) / TickSub (48 B); partials is indexed
-// [s * nchunk + chunk] with 256-point chunks; events (optional) bracket the bounds kernel only.
+// [s * nchunk + chunk]; events (optional) bracket the bounds kernel only.
 struct TickGroup {   // one rotation node
     float R[9];
     float sin_half;
@@ -84,26 +69,23 @@ void launch_tick_sort(const LutGeom& g, const float4* chunk_cen, int nchunk, con
                       unsigned* hist_xcd /* 16 x kTickNumKeys, zero on entry and on exit (optional) */, unsigned* xoff /* 16 x kTickNumKeys (optional) */,
                       unsigned* block_sums /* 64 */, unsigned* cursor, unsigned* sorted,
                       int allow_xcd /* 0: device-scope histogram atomics */, int prefill /* 1: `sorted` is filled with 0xFFFFFFFF first, for the permutation check in launch_bounds_sorted */,
-                      unsigned* check_err /* development build, A/B only: the check as a launch of its own behind the scatter */,
                       int inject_fault /* test hook */, hipStream_t s,
-                      int nunits = 0, int unit_m = 1 /* sibling units: the first nunits * unit_m evaluations form nunits items per chunk (bounds_units_kernel) */,
                       const float* tier_lut = nullptr /* windows with thresholds: the plain LUT — items likely to carry much of their evaluation's lower bound are sorted
                                                          in front of the others (two tiers; cursor[kTickTierSplit] = items of the first) */,
                       float tier_level = 0.0f /* ... those whose per-point term at the patch centre reaches tier_level * T */);
 constexpr int kTickTierSplit = 1 << 14;
 // descriptors of a tick: pinned staging (device-visible addresses) -> device arrays, one launch
 void launch_tick_upload(const TickGroup* hd_groups, TickGroup* d_groups, int ngroups, const TickSub* hd_subs, TickSub* d_subs, int nsubs, hipStream_t s);
-#ifdef FGOICP_DEV_KNOBS
-bool bounds_dev_variant_selected(const float2* packed_or_null, int layout, int unit_m);
-#endif
-bool launch_bounds_sorted(const float4* src, int ns, const float* lut, const float2* packed_or_null, int layout /* 1 z-pair, 2 yz-quad */, const LutGeom& g, int nchunk,
-                          int chunk_pts /* 256 .. 2048 points per item */, const TickGroup* groups, const TickSub* subs, int nsub, const unsigned* sorted, double2* partials,
-                          float* evals_or_null /* trimmed mode: row r = the per-point e = max(d, 0) of output row r */, size_t erow /* floats per row, multiple of 4 */,
+// Returns true if the early exit was in force: the window carried thresholds and is untrimmed (trimmed windows carry none, so trimmed
+// contexts are the only case where fgoicp_bounds_submit_cut returns exact rows above the threshold).
+bool launch_bounds_sorted(const float4* src, int ns, const float2* packed, int layout /* 1 z-pair, 2 yz-quad, 4 apron-bricked yz-quad */, const LutGeom& g,
+                          int nchunk, int chunk_pts /* 256 .. 2048 points per item */, const TickGroup* groups, const TickSub* subs, int nsub, const unsigned* sorted,
+                          double2* partials, float* evals_or_null /* trimmed mode: row r = the per-point e = max(d, 0) of output row r */, size_t erow /* floats per row, multiple of 4 */,
                           int samp_shift /* trimmed mode: > 0 = every 2^samp_shift-th point once more in the sample behind the row (offset: ns rounded up to 64 floats) */,
                           unsigned* sort_err /* optional, host-visible: set to 1 unless `sorted` (prefilled, see launch_tick_sort) is a permutation of the items */,
                           const TickCut& cut /* early exit of evaluations whose lower bound has reached its group's cut_above */,
-                          int span /* chunks per work item: `sorted` then orders nsub * ceil(nchunk / span) items (1 unless the item kernel runs: bounds_dev_variant_selected) */,
-                          hipEvent_t ev_start, hipEvent_t ev_stop, hipStream_t s, int nunits = 0, int unit_m = 1);
+                          int span /* chunks per work item: `sorted` then orders nsub * ceil(nchunk / span) items */,
+                          hipEvent_t ev_start, hipEvent_t ev_stop, hipStream_t s);
 // EXTENSION (trimmed Go-ICP): per output row the sums of ub = e*e and lb = max(e - sqrt3*span, 0)^2 over the row's k smallest e
 // (one exact selection per row, kernels.hip trim_rows_kernel); row_span[r] = translation span of row r (device-readable)
 // samp_shift > 0: one pass per row (trim_rows_sampled_kernel) — the bracket of the cut comes from the row's sample, `margin` sample ranks
@@ -119,11 +101,10 @@ void launch_icp_inliers(const float4* work, const float4* tgt, const uint32_t* i
 void launch_bounds_finalize(const double2* partials, int nchunk, int total, float* out_lb, float* out_ub, const TickCut& cut, hipStream_t s);
 
 void launch_lut_build(const float4* tgt_shifted, int nt, const LutGeom& g, float* lut_padded, hipStream_t s);
-// zp[o] = {lut[o], lut[o + one z-slice]}: the z-paired copy the sorted bounds kernel gathers from (kernels.hip)
+// zp[o] = {lut[o], lut[o + one z-slice]}: the z-paired copy the bounds kernel gathers from (kernels.hip)
 void launch_lut_zpair(const float* lut_padded, const LutGeom& g, float2* zp, hipStream_t s);
 void launch_lut_quad(const float* lut_padded, const LutGeom& g, float4* qd, hipStream_t s);
 void launch_lut_quad_apron(const float* lut_padded, const LutGeom& g, float4* qd /* ceil(px/3)*ceil(py/2)*pz*8 quads */, hipStream_t s);
-void launch_lut_quad_bricked(const float* lut_padded, const LutGeom& g, float4* qd /* ceil(px/4)*ceil(py/4)*ceil(pz/4)*64 quads */, hipStream_t s);
 void launch_lut_unpad(const float* lut_padded, const LutGeom& g, float* out, hipStream_t s);
 void launch_lut_search(const float* lut, const LutGeom& g, const float* q_xyz, size_t n, float* out, hipStream_t s);
 void launch_lut_nodes(const float* lut_padded, const LutGeom& g, const int* xyz /* device, n node indices (clamped into the grid) */, size_t n, float* out, hipStream_t s);
@@ -177,24 +158,6 @@ void launch_icp_cov(const float4* work, const float4* tgt, const uint32_t* idx, 
                     double* block_partials, int nblocks, hipStream_t s);  // width 9: glm mat3 order
 
 
-// Device-resident ICP loop (kernels.hip): the loop state of IterativeClosestPoint3D::run (icp3d.cu:88-107) in device memory,
-// advanced by icp_step_kernel; the scans read their motion from it (R/t at float offset 0, Rn/tn at 12).
-struct IcpDevState {
-    float R[9], t[3];            // composed transform of the current iteration (icp3d.cu:101-102)
-    float Rn[9], tn[3];          // (R_, t_) of the last Procrustes step: the move of the working cloud (:100)
-    float last_R[9], last_t[3];  // :97-98
-    float sse, last_sse;
-    int iters, done, max_iter;
-    float thr;
-};
-struct IcpHostResult {           // pinned, written by the step kernel
-    float sse, R[9], t[3];
-    int iters;
-    int iters_done;              // progress: iterations whose Procrustes step has run
-    int done;                    // set after everything above
-};
-void launch_icp_init(IcpDevState* st, const float* R9, const float* t3, int max_iter, float thr, IcpHostResult* res, hipStream_t s);
-void launch_icp_step(IcpDevState* st, const double* bp_cov, int nb_cov, const double* bp_sse, int nb_sse, const float* cen, IcpHostResult* res, hipStream_t s);
 // icp_cov with the centroid kernel folded in (same bits); cen_out receives the six centroid components
 // sums_bp: block partials of icp_sums_kernel (from_waves = 0) or the per-wave sums of the scan's epilogue (from_waves = their count)
 void launch_icp_cov_cen(const float4* work, const float4* tgt, const uint32_t* idx, int n, int nt, const double* sums_bp, int sums_nblocks, int from_waves,

@@ -1,7 +1,7 @@
-// Development knobs.  Rounds 1-3 grew ~70 environment variables that select kernel variants, schedules and thresholds for A/B runs;
+// Development knobs.  Rounds 1-3 grew environment variables that select layouts, schedules, work sizes and thresholds for A/B runs;
 // every default is the measured best (NOTES.md).  A shipped library must not change its code path because a stray variable is set
 // (VERDICT r03 #7), so the DEFAULT build reads none of them: dev_env() is a constant nullptr there — the variable names do not even
-// reach the binary — and the launches of the rejected variants are compiled out (#ifdef FGOICP_DEV_KNOBS).  The development build
+// reach the binary.  The kernel variants that were measured and rejected have been retired from the tree (NOTES.md).  The development build
 // (fgoicp_amd.build.build(dev=True): -DFGOICP_DEV_KNOBS -> libfgoicp_amd_dev.so, loaded with FGOICP_LIB) reads them as before; the
 // A/B scripts under tools/ and the tests marked `dev_knobs` use it.
 // What the default build does read from the environment: FGOICP_HOST_THREADS, FGOICP_HOST_SPIN (host-thread deployment of the driver's

@@ -10,9 +10,8 @@
 #include <limits>
 #include <utility>
 
-// The 3x3 types and the SVD below are also compiled for the device (csrc/device/kernels.hip: the ICP loop's step kernel runs
-// the same source on one GPU thread, so the host loop and the device-resident loop return the same bits); g++-only
-// translation units (tests/host_harness) see plain functions.
+// The 3x3 types and the SVD below are __host__ __device__ under hipcc, so device code can run the same source as the host;
+// g++-only translation units (tests/host_harness) see plain functions.
 #if defined(__HIPCC__)
 #define FGOICP_HD __host__ __device__
 #else

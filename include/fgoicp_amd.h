@@ -147,7 +147,8 @@ int fgoicp_bounds_submit_twins(fgoicp_ctx* ctx, int slot, int G, const float* R9
  * evaluation of a subcube is spread over many work items (chunks of source points), so the kernel stops evaluating a subcube once the
  * sums of its finished items have reached T: on a certify run two thirds of all point evaluations belong to such subcubes
  * (profiles/r04_early_exit_*).  Rows below their threshold are bit-identical to fgoicp_bounds_submit_twins; the answer for a row at or
- * above it is {T, T} whether the kernel got to cut it short or not (deterministic).  Trimmed contexts ignore cut_above.
+ * above it is {T, T} whether the kernel got to cut it short or not (deterministic).  Trimmed contexts ignore cut_above: they are the only
+ * case in which rows at or above their threshold come back exact.
  */
 int fgoicp_bounds_submit_cut(fgoicp_ctx* ctx, int slot, int G, const float* R9, const float* rot_span, const int* fix_rot,
                              const int* offsets, const float* tnodes4, const int* twin, const float* cut_above);

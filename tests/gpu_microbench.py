@@ -11,7 +11,7 @@ tgt, src, R_gt, t_gt = fg.synth.workload(name, angle_deg=120.0, min_angle_deg=90
 t_c, s_c, off_t, off_s, scale, bounds = fg.synth.preprocess(tgt, src)
 t0 = time.time()
 reg = fg.Registration(t_c, s_c, bounds, res, flags=fg.FLAG_PROFILE)
-print(f"[{name} res={res} P={os.environ.get('FGOICP_PTS_PER_THREAD','auto')} mode={mode}] ctx_create (upload + LUT {reg.lut_dims()}): {time.time()-t0:.3f}s", flush=True)
+print(f"[{name} res={res} mode={mode}] ctx_create (upload + LUT {reg.lut_dims()}): {time.time()-t0:.3f}s", flush=True)
 rng = np.random.default_rng(0)
 rn = fg.RotNode(0.25, -0.125, 0.375, 0.125)
 

@@ -155,6 +155,6 @@ def test_abi_revision_and_shipped_build(fg):
         data = open(fg._lib.lib_path(), "rb").read()
         import re
         names = set(re.findall(rb"FGOICP_[A-Z][A-Z_0-9]+", data))
-        assert names <= {b"FGOICP_HOST_THREADS", b"FGOICP_HOST_SPIN", b"FGOICP_TRANSPORT_IN_PROCESS", b"FGOICP_BOUNDS_SORTED"}, names
+        assert names <= {b"FGOICP_HOST_THREADS", b"FGOICP_HOST_SPIN", b"FGOICP_TRANSPORT_IN_PROCESS"}, names
         dev = open(fg.build.DEV_LIB, "rb").read()
         assert len(set(re.findall(rb"FGOICP_[A-Z][A-Z_0-9]+", dev))) > 40

@@ -1,6 +1,5 @@
 """GPU: the tests that set FGOICP_* A/B knobs (marked `dev_knobs` by tests/conftest.py) need the development build of the library
-(-DFGOICP_DEV_KNOBS: csrc/host/knobs.hpp) — the shipped build reads none of those variables and does not instantiate the rejected
-kernel variants.  They run here, in ONE child process that loads libfgoicp_amd_dev.so (FGOICP_LIB), so that `pytest -m gpu` covers
+(-DFGOICP_DEV_KNOBS: csrc/host/knobs.hpp) — the shipped build reads none of those variables.  They run here, in ONE child process that loads libfgoicp_amd_dev.so (FGOICP_LIB), so that `pytest -m gpu` covers
 both builds: every other GPU test runs against the shipped library in this process."""
 import os
 import subprocess

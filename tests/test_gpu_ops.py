@@ -218,26 +218,25 @@ def test_brute_force_flag_matches_oracle(fg, oracle, tiny_case, gpu_required):
     hip.close()
 
 
-def test_sorted_and_plain_bounds_paths_agree(fg, tiny_case, gpu_required, monkeypatch):
-    """The locality-sorted whole-tick kernel and the plain per-rotation-node kernel compute the same
-    per-point values; only the fp64 chunking differs (256- vs 256*P-point chunks)."""
+def test_sorted_and_plain_bounds_paths_agree(fg, oracle, tiny_case, gpu_required):
+    """The locality-sorted whole-tick path is run-to-run bit-reproducible and computes the per-point values of the plain
+    per-rotation-node evaluation (the oracle's compute_bounds); only the fp64 summation order differs."""
     c = tiny_case
     rng = np.random.default_rng(8)
     nodes = [fg.RotNode(0.5, 0.5, -0.5, 0.5), fg.RotNode(0.0, 0.125, 0.0, 0.25), fg.RotNode(-0.25, 0.25, 0.25, 0.0625)]
     groups = [_tnodes(rng, 32, 0.5), _tnodes(rng, 5, 0.25), _tnodes(rng, 70, 0.125)]
     fixes = [True, False, False]
-    out = {}
-    for mode in ("1", "0"):
-        monkeypatch.setenv("FGOICP_BOUNDS_SORTED", mode)
-        reg = fg.Registration(c["pct"], c["pcs"], c["bounds"], c["res"])
-        out[mode] = reg.compute_bounds_multi([n.q.R for n in nodes], [n.span for n in nodes], fixes, groups)
-        again = reg.compute_bounds_multi([n.q.R for n in nodes], [n.span for n in nodes], fixes, groups)
-        for (a, b), (a2, b2) in zip(out[mode], again):
-            assert np.array_equal(a, a2) and np.array_equal(b, b2)  # run-to-run bit-reproducible in either mode
-        reg.close()
-    for (lb1, ub1), (lb0, ub0) in zip(out["1"], out["0"]):
-        assert rel(ub1, ub0) <= REL
-        assert np.max(np.abs(lb1.astype(np.float64) - lb0)) <= REL * max(float(np.max(ub0)), 1e-30)
+    reg = fg.Registration(c["pct"], c["pcs"], c["bounds"], c["res"])
+    out = reg.compute_bounds_multi([n.q.R for n in nodes], [n.span for n in nodes], fixes, groups)
+    again = reg.compute_bounds_multi([n.q.R for n in nodes], [n.span for n in nodes], fixes, groups)
+    for (a, b), (a2, b2) in zip(out, again):
+        assert np.array_equal(a, a2) and np.array_equal(b, b2)  # run-to-run bit-reproducible
+    reg.close()
+    orc = oracle.Registration(c["pct"], c["pcs"], c["bounds"], c["res"])
+    for n, tn, fix, (lb1, ub1) in zip(nodes, groups, fixes, out):
+        lbo, ubo = orc.compute_bounds(n.q.R, n.span, tn, fix)
+        assert rel(ub1, ubo) <= REL
+        assert np.max(np.abs(lb1.astype(np.float64) - lbo)) <= REL * max(float(np.max(ubo)), 1e-30)
 
 
 @pytest.mark.parametrize("window", [300, 4096, 0])
@@ -321,22 +320,16 @@ def test_icp_loop_variants_are_bit_identical(fg, gpu_required, monkeypatch, work
       dual_unfused  the same with separate reduction kernels;
       two_scans  two scans on two streams (FGOICP_ICP_DUAL=0), fused reductions, every iteration enqueued after its SVD — the default up to
                  262 144 points;
-      gated      the same kernels enqueued one iteration AHEAD behind stream gates (hipStreamWaitValue64) the host opens once it has written the
-                 motion into pinned memory (FGOICP_ICP_GATED=1; measured slower, a knob);
       unfused    two scans, separate reduction kernels (FGOICP_ICP_FUSE=0);
-      sequential one stream, separate kernels (FGOICP_ICP_OVERLAP=0);
-      device     the loop advanced ON THE DEVICE (FGOICP_ICP_DEVICE=1: SVD, compose and loop test in a one-thread kernel — the host's
-                 SVD source compiled for the device —, passes enqueued ahead; measured slower, kept as a knob).
+      sequential one stream, separate kernels (FGOICP_ICP_OVERLAP=0).
     Every output bit equal, including the iteration count."""
     tgt, src, R_gt, t_gt = fg.synth.workload(workload, angle_deg=30.0)
     pct, pcs, off_t, off_s, scale, bounds = fg.synth.preprocess(tgt, src)
     rng = np.random.default_rng(3)
     out = {}
-    for mode in ("1", "dual_unfused", "two_scans", "gated", "unfused", "device", "0"):
-        monkeypatch.setenv("FGOICP_ICP_GATED", "1" if mode == "gated" else "0")
+    for mode in ("1", "dual_unfused", "two_scans", "unfused", "0"):
         monkeypatch.setenv("FGOICP_ICP_OVERLAP", "0" if mode == "0" else "1")
-        monkeypatch.setenv("FGOICP_ICP_DEVICE", "1" if mode == "device" else "0")
-        monkeypatch.setenv("FGOICP_ICP_DUAL", "1" if mode in ("1", "dual_unfused") else "0")  # "gated": two scans, fused, pre-enqueued behind stream gates
+        monkeypatch.setenv("FGOICP_ICP_DUAL", "1" if mode in ("1", "dual_unfused") else "0")
         monkeypatch.setenv("FGOICP_ICP_FUSE", "0" if mode in ("unfused", "dual_unfused", "0") else "1")
         reg = fg.Registration(pct, pcs, bounds, res)
         runs = []
@@ -352,7 +345,7 @@ def test_icp_loop_variants_are_bit_identical(fg, gpu_required, monkeypatch, work
         runs.append(np.float32(reg.compute_sse_error(R, t)).view(np.uint32))
         out[mode] = runs
         reg.close()
-    for other in ("dual_unfused", "two_scans", "gated", "unfused", "device", "0"):
+    for other in ("dual_unfused", "two_scans", "unfused", "0"):
         for a, b in zip(out["1"][:6], out[other][:6]):
             assert a[0] == b[0] and np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2]) and a[3] == b[3], (other, a, b)
         assert np.array_equal(out["1"][6], out[other][6]) and out["1"][7] == out[other][7]
@@ -605,52 +598,20 @@ def _lattice_tick(fg, rng, n_groups):
 
 
 @pytest.mark.parametrize("trim", [False, True])
-@pytest.mark.parametrize("workload,res,chunk", [("tiny", 0.05, None), ("small", 0.02, "1024")])
-def test_sibling_units_keep_every_bit(fg, gpu_required, monkeypatch, workload, res, chunk, trim):
-    """FGOICP_UNITS = 4 / 8: the children of one translation node share the point loads and the rotation (bounds_units_kernel);
-    FGOICP_LDS_TILES = 128 / 192: the LUT brick under a pass of 256 points is staged in LDS and the footprints are read from there
-    (bounds_lds_kernel).  Lookups, per-point expressions and the order of every sum are those of the one-evaluation kernel — all bounds
-    bit-identical, trimmed or not."""
-    tgt, src, R_gt, t_gt = fg.synth.workload(workload, angle_deg=30.0)
-    pct, pcs, off_t, off_s, scale, bounds = fg.synth.preprocess(tgt, src)
-    if chunk:
-        monkeypatch.setenv("FGOICP_CHUNK_PTS", chunk)
-    monkeypatch.setenv("FGOICP_SMALL_TICK", "0")  # through the sort even for this small tick
-    out = {}
-    for units in ("0", "4", "8", "lds128", "lds192"):
-        monkeypatch.setenv("FGOICP_UNITS", units if units.isdigit() else "0")
-        monkeypatch.setenv("FGOICP_LDS_TILES", units[3:] if units.startswith("lds") else "0")  # LUT tiles staged in LDS (bounds_lds_kernel)
-        reg = fg.Registration(pct, pcs, bounds, res)
-        if trim:
-            reg.set_inliers(int(0.8 * len(pcs)))
-        args = _lattice_tick(fg, np.random.default_rng(5), 24)
-        out[units] = reg.compute_bounds_multi(*args)
-        reg.close()
-    for units in ("4", "8", "lds128", "lds192"):
-        for (lb0, ub0), (lb1, ub1) in zip(out["0"], out[units]):
-            assert np.array_equal(lb0.view(np.uint32), lb1.view(np.uint32)) and np.array_equal(ub0.view(np.uint32), ub1.view(np.uint32)), units
-
-
-@pytest.mark.parametrize("trim", [False, True])
 @pytest.mark.parametrize("workload,res", [("tiny", 0.05), ("small", 0.02), ("small", 0.013)])
 def test_packed_lut_layouts_keep_every_bit(fg, gpu_required, monkeypatch, workload, res, trim):
-    """FGOICP_LUT_ZPAIR = 0 plain / 1 z-pair / 2 yz-quad runs / 3 2x2x2 quad bricks / 4 apron-bricked quads (4 x 2 quads per line,
-    lines overlapping by one x): the same texels in the same blend order under every layout — all bounds bit-identical, trimmed or
-    not (the bricked layouts have no trimmed kernel and fall back to the runs there; the apron layout has one).  LUT dims that are
-    and are not multiples of the brick sizes."""
+    """FGOICP_LUT_ZPAIR = 1 z-pair / 2 yz-quad runs / 4 apron-bricked quads (4 x 2 quads per line, lines overlapping by one x): the
+    same texels in the same blend order under every layout — all bounds bit-identical, trimmed or not.  LUT dims that are and are
+    not multiples of the brick sizes."""
     tgt, src, R_gt, t_gt = fg.synth.workload(workload, angle_deg=30.0)
     pct, pcs, off_t, off_s, scale, bounds = fg.synth.preprocess(tgt, src)
     monkeypatch.setenv("FGOICP_SMALL_TICK", "0")  # through the sort even for this small tick
     out = {}
-    for layout in ("2", "0", "1", "3", "4"):
+    for layout in ("2", "1", "4"):
         monkeypatch.setenv("FGOICP_LUT_ZPAIR", layout)
         reg = fg.Registration(pct, pcs, bounds, res)
-        if layout == "4":
-            assert reg.info()["lut_layout"] == 4
+        assert reg.info()["lut_layout"] == int(layout)
         if trim:
-            if layout == "3":
-                reg.close()
-                continue
             reg.set_inliers(int(0.8 * len(pcs)))
         args = _lattice_tick(fg, np.random.default_rng(5), 24)
         out[layout] = reg.compute_bounds_multi(*args)
@@ -664,69 +625,41 @@ def test_packed_lut_layouts_keep_every_bit(fg, gpu_required, monkeypatch, worklo
 @pytest.mark.parametrize("workload,res,chunk", [("tiny", 0.05, "256"), ("small", 0.02, "256"), ("small", 0.013, "1024")])
 def test_item_kernel_keeps_every_bit(fg, gpu_required, monkeypatch, workload, res, chunk, flags):
     """bounds_item_kernel (round 4: the shipped bounds kernel — packed fp32, 32-bit texel addressing, per-pass item kinds; csrc/device/bounds_item.hpp)
-    against round 3's bounds_sorted_kernel family (development build, FGOICP_BOUNDS_ITEM=0) on the same submission: every bound bit for bit —
-    under the z-pair, yz-quad and apron layouts, trimmed or not, twins (dual items) included, multi-pass items, a cloud whose size is not a multiple
-    of a pass (the tail pass with missing points), CUDA's 1.8 fixed-point weights on and off (FGOICP_FLAG_NO_WEIGHT_QUANT)."""
+    against round 3's bounds_sorted_kernel family on the same submission, kept as data (tests/golden/item_kernel_bits.npz, recorded by
+    tests/golden/make_item_kernel_bits.py with both kernels bit-identical): every bound bit for bit — under the z-pair, yz-quad and apron layouts,
+    trimmed or not, twins (dual items) included, multi-pass items, a cloud whose size is not a multiple of a pass (the tail pass with missing points),
+    CUDA's 1.8 fixed-point weights on and off (FGOICP_FLAG_NO_WEIGHT_QUANT)."""
     import ctypes as C
-    tgt, src, R_gt, t_gt = fg.synth.workload(workload, angle_deg=30.0)
-    pct, pcs, off_t, off_s, scale, bounds = fg.synth.preprocess(tgt, src)
-    pcs = pcs[:len(pcs) - 3]  # never a whole number of passes
+    import os
+    ref = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "item_kernel_bits.npz"))
+    pct, pcs, bounds = ref[workload + "_pct"], ref[workload + "_pcs"], ref[workload + "_bounds"]
+    assert len(pcs) % 256 != 0  # never a whole number of passes
     monkeypatch.setenv("FGOICP_SMALL_TICK", "0")
     monkeypatch.setenv("FGOICP_CHUNK_PTS", chunk)
     lib = fg._lib.load()
-    rng = np.random.default_rng(21)
-    rn = [fg.RotNode(0.125, -0.25, 0.375, 0.25), fg.RotNode(-0.375, 0.125, 0.25, 0.125)]
-    ta, tb, tc, td = _tnodes(rng, 20, 0.25), _tnodes(rng, 24, 0.25), _tnodes(rng, 9, 0.125), _tnodes(rng, 7, 0.125)
-    tb[3:15] = ta[5:17]  # twelve twins between group 0 (fix_rot) and group 1
-    R9 = np.concatenate([fg.nodes.to_glm(n.q.R) for n in (rn[0], rn[0], rn[1], rn[1])]).astype(np.float32)
-    spans = np.array([rn[0].span, rn[0].span, rn[1].span, rn[1].span], np.float32)
-    fix = np.array([1, 0, 1, 0], np.int32)
-    offs = np.array([0, 20, 44, 53, 60], np.int32)
-    tn4 = np.ascontiguousarray(np.concatenate([ta, tb, tc, td]), np.float32)
-    twin = np.full(60, -1, np.int32)
-    for k in range(12):
-        twin[5 + k], twin[20 + 3 + k] = 20 + 3 + k, 5 + k
+    R9, spans, fix, offs, tn4, twin = (np.ascontiguousarray(ref[k]) for k in ("R9", "spans", "fix", "offs", "tn", "twin"))
+    assert int(np.sum(twin >= 0)) == 24  # twelve twins between group 0 (fix_rot) and group 1
     fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int)
     out = {}
     for layout in ("1", "2", "4"):
         monkeypatch.setenv("FGOICP_LUT_ZPAIR", layout)
         for trim in (False, True):
-            for item in ("1", "0"):
-                monkeypatch.setenv("FGOICP_BOUNDS_ITEM", item)
-                reg = fg.Registration(pct, pcs, bounds, res, flags=fg.FLAG_NO_WEIGHT_QUANT if flags else 0)
-                if trim:
-                    reg.set_inliers(int(0.8 * len(pcs)))
-                lb, ub = np.zeros(60, np.float32), np.zeros(60, np.float32)
-                assert lib.fgoicp_bounds_submit_twins(reg._h, 0, 4, R9.ctypes.data_as(fp), spans.ctypes.data_as(fp), fix.ctypes.data_as(ip), offs.ctypes.data_as(ip),
-                                                      tn4.ctypes.data_as(fp), twin.ctypes.data_as(ip)) == 0
-                assert lib.fgoicp_bounds_collect(reg._h, 0, lb.ctypes.data_as(fp), ub.ctypes.data_as(fp)) == 0
-                out[(layout, trim, item)] = (lb, ub)
-                reg.close()
-            a, b = out[(layout, trim, "1")], out[(layout, trim, "0")]
-            assert np.array_equal(a[0].view(np.uint32), b[0].view(np.uint32)) and np.array_equal(a[1].view(np.uint32), b[1].view(np.uint32)), (layout, trim)
-            assert float(a[1].max()) > 0
+            reg = fg.Registration(pct, pcs, bounds, res, flags=fg.FLAG_NO_WEIGHT_QUANT if flags else 0)
+            assert reg.info()["lut_layout"] == int(layout)
+            if trim:
+                reg.set_inliers(int(0.8 * len(pcs)))
+            lb, ub = np.zeros(60, np.float32), np.zeros(60, np.float32)
+            assert lib.fgoicp_bounds_submit_twins(reg._h, 0, 4, R9.ctypes.data_as(fp), spans.ctypes.data_as(fp), fix.ctypes.data_as(ip), offs.ctypes.data_as(ip),
+                                                  tn4.ctypes.data_as(fp), twin.ctypes.data_as(ip)) == 0
+            assert lib.fgoicp_bounds_collect(reg._h, 0, lb.ctypes.data_as(fp), ub.ctypes.data_as(fp)) == 0
+            reg.close()
+            key = f"{workload}_{res}_{chunk}_{'noquant' if flags else 'quant'}_z{layout}_{'trim' if trim else 'full'}"
+            assert np.array_equal(lb.view(np.uint32), ref[key + "_lb"].view(np.uint32)) and np.array_equal(ub.view(np.uint32), ref[key + "_ub"].view(np.uint32)), (layout, trim)
+            assert float(ub.max()) > 0
+            out[(layout, trim)] = (lb, ub)
     for trim in (False, True):  # and the layouts among each other
         for layout in ("2", "4"):
-            assert np.array_equal(out[("1", trim, "1")][1].view(np.uint32), out[(layout, trim, "1")][1].view(np.uint32))
-
-
-def test_sibling_units_whole_run(fg, gpu_required, monkeypatch):
-    """A whole FastGoICP::run() with and without sibling units: same counters, same result bits (twins and the memo included)."""
-    tgt, src, R_gt, t_gt = fg.synth.workload("small", angle_deg=150.0, min_angle_deg=110.0)
-    monkeypatch.setenv("FGOICP_CHUNK_PTS", "1024")
-    res = {}
-    for units in ("0", "4", "8"):
-        monkeypatch.setenv("FGOICP_UNITS", units)
-        for trim in (0.0, 0.2):
-            s = fg.FastGoICP(tgt, src, 0.02, 1e-4, schedule=fg.SCHEDULE_ROUND, round_width=0, trim_fraction=trim)
-            R, t = s.run()
-            st = s.stats()
-            res[(units, trim)] = (np.float32(s.get_best_error()).view(np.uint32), R.copy(), t.copy(), int(st["trans_cubes"]), int(st["rot_cubes"]))
-            s.close()
-    for units in ("4", "8"):
-        for trim in (0.0, 0.2):
-            a, b = res[("0", trim)], res[(units, trim)]
-            assert a[0] == b[0] and np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2]) and a[3:] == b[3:], (units, trim, a, b)
+            assert np.array_equal(out[("1", trim)][1].view(np.uint32), out[(layout, trim)][1].view(np.uint32))
 
 
 @pytest.mark.gpu

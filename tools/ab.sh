@@ -1,6 +1,5 @@
 #!/bin/bash
 # A/B of a development-build knob on bench legs, alternating arms, stderr kept:   tools/ab.sh TAG KNOB "VAL_A VAL_B ..." "LEG ..." [REPEATS]
-# e.g.  tools/ab.sh r04_item FGOICP_BOUNDS_ITEM "0 1" "dragon trimmed" 2
 # Replaces round 3's one-off ab_*.sh scripts (their records are under profiles/r03_ab_*.txt; the knobs they flip exist in the development
 # build only: libfgoicp_amd_dev.so, csrc/host/knobs.hpp).
 set -u -o pipefail

@@ -1,6 +1,6 @@
 """Not a test: microseconds per ICP iteration (IterativeClosestPoint3D::run, icp3d.cu:88-107) for the loop variants.
     python tools/icp_bench.py [workload=bunny] [repeats=5]
-Prints JSON lines per variant (csrc/device/ctx.hip): fused reductions (default), separate reduction kernels, the device-resident loop, one stream."""
+Prints JSON lines per variant (csrc/device/ctx.hip): fused reductions (default), one walk for both scans, separate reduction kernels, one stream."""
 import json
 import os
 import subprocess
@@ -10,7 +10,7 @@ import time
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
-VARIANTS = {"default": {}, "gated_two_scans_fused": {"FGOICP_ICP_GATED": "1"}, "dual_walk_fused": {"FGOICP_ICP_DUAL": "1"}, "two_scans_unfused": {"FGOICP_ICP_GATED": "0", "FGOICP_ICP_DUAL": "0", "FGOICP_ICP_FUSE": "0"}, "device_loop": {"FGOICP_ICP_DEVICE": "1"},
+VARIANTS = {"default": {}, "dual_walk_fused": {"FGOICP_ICP_DUAL": "1"}, "two_scans_unfused": {"FGOICP_ICP_DUAL": "0", "FGOICP_ICP_FUSE": "0"},
             "one_stream_unfused": {"FGOICP_ICP_DUAL": "0", "FGOICP_ICP_FUSE": "0", "FGOICP_ICP_OVERLAP": "0"}}
 
 

@@ -1,5 +1,5 @@
 """Operator-level timing of the bounds kernel on a FIXED tick (results do not feed back into a search, so builds that change the
-arithmetic — tools/ablate.sh — stay comparable):  python tools/op_bench.py [workload] [groups] [reps]
+arithmetic stay comparable):  python tools/op_bench.py [workload] [groups] [reps]
 G random rotation nodes (span 0.125) x 32 translation nodes (span 0.0625) scattered within +-0.15 of the ground-truth translation in
 the scaled frame; fix_rot alternates.  Prints ns per evaluation and the algorithmic GB/s of the kernel.
 OP_BENCH_CUT=q: the tick goes through fgoicp_bounds_submit_cut with every group's threshold at the q-quantile of its exact lower bounds
