@@ -14,5 +14,6 @@ from .nodes import Rotation, RotNode, TransNode, from_glm, to_glm  # noqa: F401
 try:  # the driver mirror needs nothing beyond the C ABI, but keep import errors local to it
     from .fgoicp import FastGoICP  # noqa: F401
     from .multi import MultiGoICP, RcclExchange, rccl_unique_id  # noqa: F401
+    from .batch import FastGoICPBatch  # noqa: F401
 except ImportError:  # pragma: no cover
     pass

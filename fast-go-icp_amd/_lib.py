@@ -58,6 +58,15 @@ FLAG_NO_MORTON = 1 << 1
 FLAG_PROFILE = 1 << 2
 FLAG_BRUTE_FORCE_NN = 1 << 3
 FLAG_CURVE_ORDER = 1 << 4
+class BatchPair(C.Structure):
+    _fields_ = [("tgt_xyz", c_float_p), ("nt", C.c_size_t), ("src_xyz", c_float_p), ("ns", C.c_size_t), ("lut_resolution", C.c_float),
+                ("mse_threshold", C.c_float)]
+
+
+class BatchOpts(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("solver", SolverOpts), ("max_live", C.c_int)]
+
+
 SCHEDULE_SERIAL = 0
 SCHEDULE_ROUND = 1
 
@@ -134,6 +143,12 @@ _SIGS = {
     "fgoicp_multi_recorded": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "fgoicp_multi_test_fault": (C.c_int, [C.c_void_p, C.c_int, C.c_long]),
     "fgoicp_multi_replay_rank": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double)]),
+    "fgoicp_batch_create": (C.c_int, [C.POINTER(BatchPair), C.c_int, C.POINTER(BatchOpts), C.POINTER(C.c_void_p)]),
+    "fgoicp_batch_run": (C.c_int, [C.c_void_p, c_float_p, c_float_p, c_int_p]),
+    "fgoicp_batch_best_error": (C.c_int, [C.c_void_p, C.c_int, c_float_p]),
+    "fgoicp_batch_stats": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RunStats)]),
+    "fgoicp_batch_launches": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "fgoicp_batch_destroy": (None, [C.c_void_p]),
 }
 TRANSPORT_RCCL = 0
 TRANSPORT_IN_PROCESS = 1

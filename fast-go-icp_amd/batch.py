@@ -1,0 +1,68 @@
+"""Many registrations on one device in one run (fgoicp_batch, include/fgoicp_amd.h).  Each pair returns exactly what FastGoICP.run()
+returns for it alone with the same options; the bounds and ICP work of all live pairs is evaluated in shared launches."""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from .nodes import from_glm
+from .registration import _cloud, _fp
+
+
+class FastGoICPBatch:
+    """pairs: iterable of (pct, pcs) or (pct, pcs, lut_resolution, mse_threshold); the defaults below apply to the short form."""
+
+    def __init__(self, pairs, lut_resolution=0.005, mse_threshold=1e-3, schedule=_lib.SCHEDULE_SERIAL, round_width=1, device=0, flags=0,
+                 max_live=0):
+        self._lib = _lib.load()
+        self._clouds = []
+        arr = (_lib.BatchPair * max(1, len(pairs)))()
+        for i, p in enumerate(pairs):
+            pct, pcs = _cloud(p[0]), _cloud(p[1])
+            lr, mt = (p[2], p[3]) if len(p) > 2 else (lut_resolution, mse_threshold)
+            self._clouds.append((pct, pcs))  # the library copies them at create; kept until then
+            arr[i] = _lib.BatchPair(_fp(pct), len(pct), _fp(pcs), len(pcs), float(lr), float(mt))
+        self.n = len(pairs)
+        opts = _lib.BatchOpts(C.sizeof(_lib.BatchOpts), _lib.SolverOpts(int(schedule), int(round_width), int(flags), int(device), 0.0), int(max_live))
+        self._h = C.c_void_p()
+        _lib.check(self._lib.fgoicp_batch_create(arr, self.n, C.byref(opts), C.byref(self._h)), "fgoicp_batch_create")
+        self._clouds = None
+        self._status = [None] * self.n
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.fgoicp_batch_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def run(self):
+        """-> list of (R (3,3), t (3,)) per pair, t restored to the callers' frame; None for a pair that could not be served (see status(i))."""
+        R = np.zeros(9 * self.n, np.float32); t = np.zeros(3 * self.n, np.float32); st = np.zeros(self.n, np.int32)
+        _lib.check(self._lib.fgoicp_batch_run(self._h, _fp(R), _fp(t), st.ctypes.data_as(_lib.c_int_p)), "fgoicp_batch_run")
+        self._status = [int(s) for s in st]
+        return [None if st[i] else (from_glm(R[9 * i:9 * i + 9]), t[3 * i:3 * i + 3].copy()) for i in range(self.n)]
+
+    def status(self, i):
+        """fgoicp_status of pair i in the last run (0 = OK)."""
+        return self._status[i]
+
+    def get_best_error(self, i):
+        v = C.c_float()
+        _lib.check(self._lib.fgoicp_batch_best_error(self._h, int(i), C.byref(v)), "fgoicp_batch_best_error")
+        return np.float32(v.value)
+
+    def stats(self, i):
+        st = _lib.RunStats()
+        _lib.check(self._lib.fgoicp_batch_stats(self._h, int(i), C.byref(st)), "fgoicp_batch_stats")
+        return st.as_dict()
+
+    def launches(self):
+        """-> (fused bounds launches, lock-step ICP iterations) of the last run."""
+        b = C.c_uint64(); c = C.c_uint64()
+        _lib.check(self._lib.fgoicp_batch_launches(self._h, C.byref(b), C.byref(c)), "fgoicp_batch_launches")
+        return int(b.value), int(c.value)

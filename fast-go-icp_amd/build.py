@@ -23,6 +23,7 @@ SOURCES = [
     os.path.join(CSRC, "device", "bvh.hip"),
     os.path.join(CSRC, "host", "solver.cpp"),
     os.path.join(CSRC, "host", "multi.cpp"),
+    os.path.join(CSRC, "host", "batch.cpp"),
 ]
 CLI_SOURCES = [os.path.join(CSRC, "cli", "main.cpp")]
 

@@ -1,10 +1,14 @@
 // fast-go-icp — the reference's CLI (src/main.cpp:8-58) over libfgoicp_amd.so:
 //     fast-go-icp -c config.toml [-v]
+//     fast-go-icp --batch LIST [-v]      (EXTENSION: every config of LIST as one batch on one GPU, fgoicp_batch_*)
 // Same flags, same TOML keys / defaults / clamps, same log lines; the search runs on the MI355X.
 #include <chrono>
 #include <cstdlib>
+#include <cstring>
 #include <filesystem>
+#include <fstream>
 #include <string>
+#include <vector>
 
 #include "../../../include/fgoicp/fgoicp.hpp"
 #include "config.hpp"
@@ -14,11 +18,76 @@ static std::string usage(const std::string& exe) {
            "  -h,--help                   Print this help message and exit\n"
            "  -c,--config TEXT REQUIRED   Path to the TOML configuration file\n"
            "  -v,--verbose                Enable verbose logging\n"
-           "  -g,--gpus N                 Shard the search over N GPUs of this node (default: params.gpus, 1)\n\nExample Usage:\n  " + exe + " -c config.toml --verbose\n  " + exe + " --config=config.toml\n";
+           "  -g,--gpus N                 Shard the search over N GPUs of this node (default: params.gpus, 1)\n"
+           "  -b,--batch LIST             Run every config listed in LIST (one path per line, relative to LIST) as one batch on one GPU\n\nExample Usage:\n  " + exe + " -c config.toml --verbose\n  " + exe + " --config=config.toml\n";
+}
+
+// --batch LIST: every config of the list registered in one fgoicp_batch run; each config's io.output / io.visualization as a lone -c run
+// of it writes them (the seconds written are the batch's).  The configs must agree on the schedule and round width; trimming is refused.
+static int run_batch(const std::string& list_file) {
+    std::ifstream lf(list_file);
+    if (!lf) { icp::Logger(icp::LogLevel::Error) << "Unable to read " << list_file; return 1; }
+    const std::filesystem::path dir = std::filesystem::path(list_file).parent_path();
+    std::vector<cli::Config> configs;
+    for (std::string line; std::getline(lf, line);) {
+        line = cli::trim(line);
+        if (line.empty() || line[0] == '#') continue;
+        const std::filesystem::path p(line);
+        configs.emplace_back((p.is_absolute() ? p : dir / p).string());
+    }
+    if (configs.empty()) { icp::Logger(icp::LogLevel::Error) << "--batch: " << list_file << " lists no config"; return 1; }
+    const cli::Config& c0 = configs[0];
+    for (const cli::Config& c : configs) {
+        if (c.params.trim_fraction > 0.0f) { icp::Logger(icp::LogLevel::Error) << "--batch: trimmed configs cannot run in a batch"; return 1; }
+        if (c.params.gpus > 1) { icp::Logger(icp::LogLevel::Error) << "--batch: a batch runs on one GPU (params.gpus > 1)"; return 1; }
+        if (c.params.schedule != c0.params.schedule || c.params.round_width != c0.params.round_width) {
+            icp::Logger(icp::LogLevel::Error) << "--batch: every config of a batch must have the same params.schedule and params.round_width";
+            return 1;
+        }
+    }
+    const size_t n = configs.size();
+    std::vector<std::vector<icp::vec3>> pct(n), pcs(n);
+    std::vector<fgoicp_batch_pair> pairs(n);
+    for (size_t i = 0; i < n; ++i) {
+        const cli::Config& c = configs[i];
+        cli::load_cloud(c.io.target, c.params.target_subsample, pct[i], c.params.seed);
+        cli::load_cloud(c.io.source, c.params.source_subsample, pcs[i], c.params.seed < 0 ? -1 : c.params.seed + 1);
+        icp::Logger(icp::LogLevel::Info) << "Pair " << i << ": target (" << pct[i].size() << ") " << c.io.target << ", source (" << pcs[i].size() << ") " << c.io.source;
+        pairs[i] = fgoicp_batch_pair{&pct[i].data()->x, pct[i].size(), &pcs[i].data()->x, pcs[i].size(), c.params.lut_resolution, c.params.mse_threshold};
+    }
+    const int schedule = c0.params.schedule == "round" ? FGOICP_SCHEDULE_ROUND : FGOICP_SCHEDULE_SERIAL;
+    fgoicp_batch_opts o{};
+    o.struct_size = sizeof(o);
+    o.solver = fgoicp_solver_opts{schedule, c0.params.round_width, 0u, 0, 0.0f};
+    fgoicp_batch* b = nullptr;
+    icp::check_status(fgoicp_batch_create(pairs.data(), (int)n, &o, &b), "fgoicp_batch_create");
+    std::vector<float> R9(9 * n), t3(3 * n);
+    std::vector<int> status(n, 0);
+    const auto start = std::chrono::high_resolution_clock::now();
+    icp::check_status(fgoicp_batch_run(b, R9.data(), t3.data(), status.data()), "fgoicp_batch_run");
+    const std::chrono::duration<double> elapsed = std::chrono::high_resolution_clock::now() - start;
+    icp::Logger(icp::LogLevel::Info) << "Fast Go-ICP batch of " << n << " finished, time elapsed: " << std::fixed << std::setprecision(3) << elapsed.count() << " seconds";
+    int rc = 0;
+    for (size_t i = 0; i < n; ++i) {
+        if (status[i]) { icp::Logger(icp::LogLevel::Error) << "Pair " << i << " failed (status " << status[i] << ")"; rc = 1; continue; }
+        icp::mat3 R;
+        std::memcpy(R.data(), &R9[9 * i], 9 * sizeof(float));
+        const icp::vec3 t{t3[3 * i], t3[3 * i + 1], t3[3 * i + 2]};
+        float best_error = 0.f;
+        fgoicp_run_stats st{};
+        icp::check_status(fgoicp_batch_best_error(b, (int)i, &best_error), "fgoicp_batch_best_error");
+        icp::check_status(fgoicp_batch_stats(b, (int)i, &st), "fgoicp_batch_stats");
+        icp::Logger(icp::LogLevel::Info) << "Pair " << i << ": Best Error: " << best_error << "\n\tRotation:\n" << R << "\n\tTranslation: " << t;
+        const cli::Config& c = configs[i];
+        if (!c.io.output.empty()) cli::write_result_toml(c.io.output, R, t, best_error, pcs[i].size(), elapsed.count(), st);
+        if (!c.io.visualization.empty()) cli::write_visualization_ply(c.io.visualization, pct[i], pcs[i], R, t);
+    }
+    fgoicp_batch_destroy(b);
+    return rc;
 }
 
 int main(int argc, char* argv[]) {
-    std::string config_file;
+    std::string config_file, batch_file;
     bool verbose = false;
     int gpus_flag = 0;
     const std::string exe = std::filesystem::path(argv[0]).filename().string();
@@ -33,10 +102,18 @@ int main(int argc, char* argv[]) {
         else if (a == "-v" || a == "--verbose") verbose = true;
         else if (a == "-g" || a == "--gpus") { if (i + 1 >= argc) fail("--gpus: 1 required INT missing", 114); gpus_flag = std::atoi(argv[++i]); }
         else if (a.rfind("--gpus=", 0) == 0) gpus_flag = std::atoi(a.substr(7).c_str());
+        else if (a == "-b" || a == "--batch") { if (i + 1 >= argc) fail("--batch: 1 required TEXT missing", 114); batch_file = argv[++i]; }
+        else if (a.rfind("--batch=", 0) == 0) batch_file = a.substr(8);
         else if (a == "-c" || a == "--config") { if (i + 1 >= argc) fail("--config: 1 required TEXT missing", 114); config_file = argv[++i]; }
         else if (a.rfind("--config=", 0) == 0) config_file = a.substr(9);
         else if (a.rfind("-c", 0) == 0 && a.size() > 2) config_file = a.substr(2);
         else fail("The following argument was not expected: " + a, 109);
+    }
+    if (!batch_file.empty()) {
+        if (!config_file.empty()) fail("--batch excludes --config", 109);
+        if (gpus_flag > 1) fail("--batch runs on one GPU: --gpus > 1 is not allowed with it", 109);
+        icp::Logger::set_verbose(verbose);
+        return run_batch(batch_file);
     }
     if (config_file.empty()) fail("--config is required", 106);
     icp::Logger::set_verbose(verbose);

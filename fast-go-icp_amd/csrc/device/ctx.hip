@@ -663,6 +663,68 @@ int ctx_icp(fgoicp_ctx* c, const float* R0, const float* t0, size_t max_iter, fl
     return lane_icp(c, c->lanes[0], R0, t0, max_iter, thr, sse_out, R_out9, t_out3, iters_out);
 }
 
+// lane_icp's overlapped loop on ONE stream, cut at its host turn-arounds (fgoicp_batch: many contexts share every turn-around).  Each
+// step enqueues what the loop enqueues between two waits — the correspondence pass of the next iteration (which moves the working cloud
+// first) and this iteration's SSE — so the kernels, their inputs and the order of every sum are lane_icp's: the same (sse, R, t, iterations).
+bool ctx_icp_steppable(const fgoicp_ctx* c) { return icp_fused(c) && c->icp_overlap && c->icp_dual_env <= 0; }
+int ctx_icp_step_begin(fgoicp_ctx* c, IcpStepState& s, const float* R0, const float* t0, size_t max_iter, float thr) {
+    HIPCHK(hipSetDevice(c->device));
+    fgoicp_ctx::IcpLane& L = c->lanes[0];
+    s = IcpStepState();
+    s.R = Mat3f::from(R0);
+    s.t = Vec3f{t0[0], t0[1], t0[2]};
+    s.max_iter = max_iter;
+    s.thr = thr;
+    HIPCHK(hipMemcpyAsync(L.d_work, c->d_src, sizeof(float4) * c->ns, hipMemcpyDeviceToDevice, L.stream));
+    launch_transform_inplace(L.d_work, (int)c->ns, R0, t0, L.stream);  // icp3d.cu:85
+    if (max_iter > 0) {
+        int rc = procrustes_enqueue(c, L, nullptr, L.d_first_idx, L.d_sel_wide2, L.stream);
+        if (rc) return rc;
+    }
+    HIPCHK(hipGetLastError());
+    return FGOICP_OK;
+}
+// Call once the context's stream has drained.  Sets s.done when the loop has ended (the outputs are then in s.sse_out, s.R_out, s.t_out).
+int ctx_icp_step(fgoicp_ctx* c, IcpStepState& s) {
+    fgoicp_ctx::IcpLane& L = c->lanes[0];
+    if (s.have_sse) {
+        s.sse = sse_result(c, L);
+        ++s.iters;
+    }
+    if (!(s.iter++ < s.max_iter && (s.last_sse - s.sse) > s.thr * s.last_sse)) {  // icp3d.cu:94
+        const bool cur_best = s.sse < s.last_sse;  // :106-107
+        s.sse_out = cur_best ? s.sse : s.last_sse;
+        s.R_out = cur_best ? s.R : s.last_R;
+        s.t_out = cur_best ? s.t : s.last_t;
+        s.done = true;
+        return FGOICP_OK;
+    }
+    HIPCHK(hipSetDevice(c->device));
+    s.last_sse = s.sse;
+    s.last_R = s.R;
+    s.last_t = s.t;
+    Mat3f Rn;
+    Vec3f tn;
+    procrustes_finish(L, &Rn, &tn, nullptr, nullptr);
+    const float tn3[3] = {tn.x, tn.y, tn.z};
+    s.R = Rn * s.R;          // :101
+    s.t = Rn * s.t + tn;     // :102
+    const float t3[3] = {s.t.x, s.t.y, s.t.z};
+    uint32_t* idx[2] = {L.d_first_idx, L.d_first_idx2};
+    const uint32_t* seed = c->icp_seeding ? idx[s.cur] : nullptr;
+    const bool next = s.iter < s.max_iter;
+    if (next) {
+        int rc = procrustes_enqueue(c, L, seed, idx[s.cur ^ 1], L.d_sel_wide2, L.stream, Rn.m, tn3);
+        if (rc) return rc;
+    }
+    int rc = sse_enqueue(c, L, s.R.m, t3, seed, L.stream);  // :103
+    if (rc) return rc;
+    if (next) s.cur ^= 1;
+    s.have_sse = true;
+    HIPCHK(hipGetLastError());
+    return FGOICP_OK;
+}
+
 // COOPERATIVE ICP (round 3): `world` ranks that hold the same clouds run ONE IterativeClosestPoint3D::run() (icp3d.cu:80-108)
 // together.  The two exact scans of an iteration — what an ICP run consists of (600-1900 us per iteration at 437k points) — are
 // split by query range: rank r scans the Hilbert-consecutive queries [r * per, (r + 1) * per), `gather` all-gathers the results

@@ -436,6 +436,7 @@ __device__ __forceinline__ void trim_store(float* __restrict__ evals, size_t row
 }
 
 #include "bounds_item.hpp"   // round 4: the bounds kernel of the sorted path (bounds_item_kernel)
+#include "bounds_fused.hpp"  // the same per-point code over the pairs of a batch (fgoicp_batch)
 
 typedef float v4f __attribute__((ext_vector_type(4)));
 // ---------------------------------------------------------------------------------------------
@@ -2238,10 +2239,7 @@ bool launch_bounds_sorted(const float4* src, int ns, const float2* packed, int l
                           const TickSub* subs, int nsub, const unsigned* sorted, double2* partials, float* evals, size_t erow, int samp_shift, unsigned* sort_err,
                           const TickCut& cut, int span, hipEvent_t ev_start, hipEvent_t ev_stop, hipStream_t s) {
     const unsigned nitems = (unsigned)((size_t)nsub * (size_t)((nchunk + span - 1) / span));
-    const size_t nodes = (size_t)g.px * g.py * g.pz;
-    // 32-bit texel addressing: the row number (z * py + y) must fit the signed 24-bit multiply and the byte offsets of the packed copy 32 bits
-    const size_t bytes = layout == 4 ? (size_t)((g.px + 2) / 3) * ((g.py + 1) / 2) * g.pz * 8 * sizeof(float4) : nodes * (layout == 2 ? sizeof(float4) : sizeof(float2));
-    const bool wide = (size_t)g.py * g.pz > ((size_t)1 << 23) || bytes + 64 > ((size_t)1 << 32);
+    const bool wide = bounds_lut_wide(g, layout);
     const char* lutp = reinterpret_cast<const char*>(packed);
     if (ev_start) (void)hipEventRecord(ev_start, s);
     if (evals) {
@@ -2255,6 +2253,33 @@ bool launch_bounds_sorted(const float4* src, int ns, const float2* packed, int l
     }
     if (ev_stop) (void)hipEventRecord(ev_stop, s);
     return cut.acc && !evals;  // the early exit was in force (trimmed windows carry no thresholds: exact rows)
+}
+
+// 32-bit texel addressing unless the row number (z * py + y) does not fit the signed 24-bit multiply or the byte offsets of the packed
+// copy do not fit 32 bits (launch_bounds_sorted and the fused kernel of fgoicp_batch)
+bool bounds_lut_wide(const LutGeom& g, int layout) {
+    const size_t nodes = (size_t)g.px * g.py * g.pz;
+    const size_t bytes = layout == 4 ? (size_t)((g.px + 2) / 3) * ((g.py + 1) / 2) * g.pz * 8 * sizeof(float4) : nodes * (layout == 2 ? sizeof(float4) : sizeof(float2));
+    return (size_t)g.py * g.pz > ((size_t)1 << 23) || bytes + 64 > ((size_t)1 << 32);
+}
+
+void launch_fused_bounds(int layout, bool wide, bool quant, const FusedPairView* pairs, const FusedEval* evals, const uint2* items, unsigned nitems, double2* partials,
+                         hipStream_t s) {
+    if (nitems == 0) return;
+    const dim3 grid(nitems), block(64);
+#define FGOICP_FUSED(L, W, Q) hipLaunchKernelGGL((fused_bounds_item_kernel<L, W, Q>), grid, block, 0, s, pairs, evals, items, nitems, partials)
+#define FGOICP_FUSED_WQ(L) do { if (wide) { if (quant) FGOICP_FUSED(L, true, true); else FGOICP_FUSED(L, true, false); } \
+                                else { if (quant) FGOICP_FUSED(L, false, true); else FGOICP_FUSED(L, false, false); } } while (0)
+    if (layout == 1) FGOICP_FUSED_WQ(1);
+    else if (layout == 2) FGOICP_FUSED_WQ(3);
+    else FGOICP_FUSED_WQ(5);
+#undef FGOICP_FUSED_WQ
+#undef FGOICP_FUSED
+}
+
+void launch_fused_finalize(const FusedEval* evals, int nevals, const double2* partials, float* out_lb, float* out_ub, hipStream_t s) {
+    if (nevals <= 0) return;
+    hipLaunchKernelGGL(fused_bounds_finalize_kernel, dim3(nevals), dim3(64), 0, s, evals, nevals, partials, out_lb, out_ub);
 }
 
 void launch_tick_upload(const TickGroup* h_groups, TickGroup* d_groups, int ngroups, const TickSub* h_subs, TickSub* d_subs, int nsubs, hipStream_t s) {

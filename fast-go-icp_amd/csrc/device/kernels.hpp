@@ -97,6 +97,31 @@ void launch_trim_select(const float* vals, int n, int k, float* out, uint32_t* s
                         uint32_t* wide_scratch /* 64 KiB, optional: rows of n >= 32768 are then selected by the whole device */, hipStream_t s);
 void launch_icp_inliers(const float4* work, const float4* tgt, const uint32_t* idx, int n, int nt, int k, float* d2, uint32_t* sel_info,
                         uint32_t* equal_count, const uint32_t* orig_of_slot, unsigned char* use, uint32_t* wide_scratch, hipStream_t s);
+// The bounds of many registrations in one launch (fgoicp_batch, bounds_fused.hpp): a view per pair of the batch, an evaluation per output
+// row, work items {evaluation, chunk}.  Every row is the bits its pair's own context computes with thresholds off.
+struct FusedPairView {
+    const float4* src;           // the context's d_src (its device order)
+    const char* lutp;            // its packed LUT (d_lut_zp)
+    LutGeom g;
+    int ns;
+    int chunk_pts;               // its points per work item
+};
+struct FusedEval {
+    float R[9];
+    float sin_half;              // sin(rot_span * sqrt3 * pi / 2), computed as the context's window packing does (registration.cu:42)
+    float tx, ty, tz, span;
+    int fix_rot;
+    int pair;                    // index into the views
+    int nchunk;                  // the pair's chunks per evaluation
+    int pad_;
+    unsigned long long partial_base;  // its nchunk partials start here
+};
+bool bounds_lut_wide(const LutGeom& g, int layout);
+// layout: fgoicp_ctx::lut_layout (1, 2, 4) of EVERY pair the items belong to; wide = bounds_lut_wide, quant = g.quantize, alike for all of them
+void launch_fused_bounds(int layout, bool wide, bool quant, const FusedPairView* pairs, const FusedEval* evals, const uint2* items, unsigned nitems, double2* partials,
+                         hipStream_t s);
+void launch_fused_finalize(const FusedEval* evals, int nevals, const double2* partials, float* out_lb, float* out_ub, hipStream_t s);
+
 // out_lb[i], out_ub[i] = float(sum over chunks), fixed order → bit-reproducible
 void launch_bounds_finalize(const double2* partials, int nchunk, int total, float* out_lb, float* out_ub, const TickCut& cut, hipStream_t s);
 

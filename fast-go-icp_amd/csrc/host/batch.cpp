@@ -1,0 +1,378 @@
+// fgoicp_batch (include/fgoicp_amd.h): many registrations on one device.  The scheduler (batch.hpp) runs every live pair's unchanged
+// driver on a host thread of its own; this file is its device backend — one fgoicp_ctx per live pair, the bounds of all pending requests
+// in fused launches (kernels.hip, bounds_fused.hpp), the ICP runs advanced in lock-step so that they share each host turn-around.
+// The launcher (the thread that calls fgoicp_batch_run) is the only thread that touches the device.
+#include <cmath>
+#include <cstddef>
+#include <cstring>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "../../../include/fgoicp_amd.h"
+#include "../device/ctx.hpp"
+#include "batch.hpp"
+
+namespace fgoicp {
+namespace {
+
+#define BCHK(expr)                                                                          \
+    do {                                                                                    \
+        hipError_t e_ = (expr);                                                             \
+        if (e_ != hipSuccess) {                                                             \
+            set_error(std::string("fgoicp_batch: " #expr ": ") + hipGetErrorString(e_));    \
+            return e_ == hipErrorOutOfMemory ? FGOICP_ERR_OOM : FGOICP_ERR_HIP;             \
+        }                                                                                   \
+    } while (0)
+
+// pre-processing of one pair (fgoicp_solver_create, fgoicp.cpp:176-287)
+struct PairHost {
+    std::vector<Vec3f> pcs, pct;
+    size_t ns = 0, nt = 0;
+    Vec3f offset_pcs{0, 0, 0}, offset_pct{0, 0, 0};
+    float scaling_factor = 1.f;
+    float bounds6[6] = {0, 0, 0, 0, 0, 0};
+    float lut_resolution = 0.f, mse_threshold = 0.f;
+};
+
+// device staging of one class of work items (same LUT layout, addressing and quantisation)
+struct ItemClass {
+    int layout = 0;
+    bool wide = false, quant = false;
+    std::vector<uint2> items;
+};
+
+// Grow-only device buffer
+template <class T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t cap = 0;
+    int ensure(size_t n) {
+        if (n <= cap) return FGOICP_OK;
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+        const size_t want = n + n / 2 + 64;
+        BCHK(hipMalloc(&p, sizeof(T) * want));
+        cap = want;
+        return FGOICP_OK;
+    }
+    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+};
+template <class T>
+struct PinBuf {
+    T* p = nullptr;
+    size_t cap = 0;
+    int ensure(size_t n) {
+        if (n <= cap) return FGOICP_OK;
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        cap = 0;
+        const size_t want = n + n / 2 + 64;
+        BCHK(hipHostMalloc((void**)&p, sizeof(T) * want, hipHostMallocDefault));
+        cap = want;
+        return FGOICP_OK;
+    }
+    void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
+};
+
+struct HipBatchBackend {
+    std::vector<PairHost>* pairs = nullptr;
+    int device = 0;
+    unsigned ctx_flags = 0;
+    std::vector<fgoicp_ctx*> ctx;
+    std::vector<IcpStepState> icp_state;
+    hipStream_t stream = nullptr;
+    uint64_t bounds_launches = 0, icp_launches = 0;
+    size_t last_lut_bytes = 0;
+    // tick staging
+    PinBuf<FusedPairView> h_views;
+    PinBuf<FusedEval> h_evals;
+    PinBuf<uint2> h_items;
+    PinBuf<float> h_out;
+    DevBuf<FusedPairView> d_views;
+    DevBuf<FusedEval> d_evals;
+    DevBuf<uint2> d_items;
+    DevBuf<double2> d_partials;
+    DevBuf<float> d_out;
+
+    ~HipBatchBackend() {
+        for (fgoicp_ctx*& c : ctx) { fgoicp_ctx_destroy(c); c = nullptr; }
+        h_views.release(); h_evals.release(); h_items.release(); h_out.release();
+        d_views.release(); d_evals.release(); d_items.release(); d_partials.release(); d_out.release();
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+    int init() {
+        if (hipSetDevice(device) != hipSuccess) { set_error("fgoicp_batch_run: no usable HIP device (there is no CPU path)"); return FGOICP_ERR_NO_DEVICE; }
+        BCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        ctx.assign(pairs->size(), nullptr);
+        icp_state.assign(pairs->size(), IcpStepState());
+        return FGOICP_OK;
+    }
+
+    int admit(int i) {
+        PairHost& p = (*pairs)[(size_t)i];
+        fgoicp_ctx* c = nullptr;
+        const int rc = fgoicp_ctx_create(reinterpret_cast<const float*>(p.pct.data()), p.nt, reinterpret_cast<const float*>(p.pcs.data()), p.ns, p.bounds6,
+                                         p.lut_resolution, device, ctx_flags, &c);
+        if (rc == FGOICP_ERR_OOM) return kBatchNoRoom;  // the scheduler reports OOM itself when no other pair is live
+        if (rc) return rc;
+        if (!c->d_lut_zp) {  // the fused kernel reads the packed LUT copy
+            fgoicp_ctx_destroy(c);
+            set_error("fgoicp_batch_run: pair " + std::to_string(i) + " has no packed LUT");
+            return FGOICP_ERR_INVALID_ARG;
+        }
+        ctx[(size_t)i] = c;
+        fgoicp_ctx_info info{};
+        info.struct_size = sizeof(info);
+        if (fgoicp_ctx_get_info(c, &info) == FGOICP_OK) last_lut_bytes = info.lut_bytes;
+        return FGOICP_OK;
+    }
+    // max_live = 0: another pair enters while the device has room for one more LUT the size of the last one created (and a quarter on top)
+    bool room_for_more(int /*live*/) {
+        size_t free_b = 0, total_b = 0;
+        if (hipSetDevice(device) != hipSuccess || hipMemGetInfo(&free_b, &total_b) != hipSuccess) return false;
+        return free_b > last_lut_bytes + last_lut_bytes / 4 + ((size_t)256 << 20);
+    }
+    void release(int i) {
+        (void)hipSetDevice(device);
+        fgoicp_ctx_destroy(ctx[(size_t)i]);
+        ctx[(size_t)i] = nullptr;
+    }
+
+    // One tick: every row of every request, one launch per item class, one finalize.
+    int bounds(std::vector<BatchBoundsReq*>& reqs) {
+        BCHK(hipSetDevice(device));
+        // views: one per pair that has a request
+        std::vector<int> view_of(pairs->size(), -1);
+        std::vector<int> view_pair;
+        size_t nevals = 0;
+        for (BatchBoundsReq* r : reqs) {
+            if (view_of[(size_t)r->pair] < 0) { view_of[(size_t)r->pair] = (int)view_pair.size(); view_pair.push_back(r->pair); }
+            nevals += (size_t)r->offsets[(size_t)r->G];
+        }
+        if (nevals == 0) return FGOICP_OK;
+        int rc;
+        if ((rc = h_views.ensure(view_pair.size())) || (rc = h_evals.ensure(nevals)) || (rc = h_out.ensure(2 * nevals)) || (rc = d_views.ensure(view_pair.size())) ||
+            (rc = d_evals.ensure(nevals)) || (rc = d_out.ensure(2 * nevals)))
+            return rc;
+        std::vector<ItemClass> classes;
+        std::vector<int> class_of_view(view_pair.size());
+        for (size_t v = 0; v < view_pair.size(); ++v) {
+            const fgoicp_ctx* c = ctx[(size_t)view_pair[v]];
+            FusedPairView& pv = h_views.p[v];
+            pv.src = c->d_src;
+            pv.lutp = reinterpret_cast<const char*>(c->d_lut_zp);
+            pv.g = c->geom;
+            pv.ns = (int)c->ns;
+            pv.chunk_pts = c->chunk_pts;
+            const bool wide = bounds_lut_wide(c->geom, c->lut_layout), quant = c->geom.quantize != 0;
+            int k = 0;
+            while (k < (int)classes.size() && !(classes[(size_t)k].layout == c->lut_layout && classes[(size_t)k].wide == wide && classes[(size_t)k].quant == quant)) ++k;
+            if (k == (int)classes.size()) { classes.emplace_back(); classes.back().layout = c->lut_layout; classes.back().wide = wide; classes.back().quant = quant; }
+            class_of_view[v] = k;
+        }
+        // evaluations in request order; their chunks as work items of their pair's class
+        size_t e = 0, partials = 0;
+        for (BatchBoundsReq* r : reqs) {
+            const int v = view_of[(size_t)r->pair];
+            const fgoicp_ctx* c = ctx[(size_t)r->pair];
+            ItemClass& cl = classes[(size_t)class_of_view[(size_t)v]];
+            for (int g = 0; g < r->G; ++g) {
+                const float half_angle = r->spans[(size_t)g] * kSqrt3 * kPi / 2.0f;  // registration.cu:42, as the context's window packing computes it
+                const float sin_half = std::sin(half_angle);
+                for (int i = r->offsets[(size_t)g]; i < r->offsets[(size_t)g + 1]; ++i, ++e) {
+                    FusedEval& fe = h_evals.p[e];
+                    std::memcpy(fe.R, &r->R9[9 * (size_t)g], sizeof(fe.R));
+                    fe.sin_half = sin_half;
+                    fe.tx = r->tn4[4 * (size_t)i]; fe.ty = r->tn4[4 * (size_t)i + 1]; fe.tz = r->tn4[4 * (size_t)i + 2]; fe.span = r->tn4[4 * (size_t)i + 3];
+                    fe.fix_rot = r->fix[(size_t)g] ? 1 : 0;
+                    fe.pair = v;
+                    fe.nchunk = c->nchunk1;
+                    fe.pad_ = 0;
+                    fe.partial_base = partials;
+                    for (int ch = 0; ch < c->nchunk1; ++ch) cl.items.push_back(make_uint2((unsigned)e, (unsigned)ch));
+                    partials += (size_t)c->nchunk1;
+                }
+            }
+        }
+        size_t nitems = 0;
+        for (const ItemClass& cl : classes) nitems += cl.items.size();
+        if ((rc = h_items.ensure(nitems)) || (rc = d_items.ensure(nitems)) || (rc = d_partials.ensure(partials))) return rc;
+        size_t pos = 0;
+        for (const ItemClass& cl : classes) { std::memcpy(h_items.p + pos, cl.items.data(), sizeof(uint2) * cl.items.size()); pos += cl.items.size(); }
+        BCHK(hipMemcpyAsync(d_views.p, h_views.p, sizeof(FusedPairView) * view_pair.size(), hipMemcpyHostToDevice, stream));
+        BCHK(hipMemcpyAsync(d_evals.p, h_evals.p, sizeof(FusedEval) * nevals, hipMemcpyHostToDevice, stream));
+        BCHK(hipMemcpyAsync(d_items.p, h_items.p, sizeof(uint2) * nitems, hipMemcpyHostToDevice, stream));
+        pos = 0;
+        for (const ItemClass& cl : classes) {
+            launch_fused_bounds(cl.layout, cl.wide, cl.quant, d_views.p, d_evals.p, d_items.p + pos, (unsigned)cl.items.size(), d_partials.p, stream);
+            pos += cl.items.size();
+            ++bounds_launches;
+        }
+        launch_fused_finalize(d_evals.p, (int)nevals, d_partials.p, d_out.p, d_out.p + nevals, stream);
+        BCHK(hipGetLastError());
+        BCHK(hipMemcpyAsync(h_out.p, d_out.p, sizeof(float) * 2 * nevals, hipMemcpyDeviceToHost, stream));
+        BCHK(hipStreamSynchronize(stream));
+        e = 0;
+        for (BatchBoundsReq* r : reqs) {
+            const size_t n = (size_t)r->offsets[(size_t)r->G];
+            std::memcpy(r->lb.data(), h_out.p + e, sizeof(float) * n);
+            std::memcpy(r->ub.data(), h_out.p + nevals + e, sizeof(float) * n);
+            e += n;
+        }
+        return FGOICP_OK;
+    }
+
+    int icp_start(BatchIcpReq& r) {
+        fgoicp_ctx* c = ctx[(size_t)r.pair];
+        if (!ctx_icp_steppable(c)) {  // large clouds, brute-force contexts: the context's own loop, at once
+            const int rc = ctx_icp(c, r.R0, r.t0, r.max_iter, r.thr, &r.sse, r.R, r.t, &r.iters);
+            r.done = true;
+            return rc;
+        }
+        return ctx_icp_step_begin(c, icp_state[(size_t)r.pair], r.R0, r.t0, r.max_iter, r.thr);
+    }
+    int icp_step(std::vector<BatchIcpReq*>& runs) {
+        for (BatchIcpReq* r : runs) BCHK(hipStreamSynchronize(ctx[(size_t)r->pair]->stream));
+        for (BatchIcpReq* r : runs) {
+            IcpStepState& s = icp_state[(size_t)r->pair];
+            const int rc = ctx_icp_step(ctx[(size_t)r->pair], s);
+            if (rc) return rc;
+            if (s.done) {
+                r->sse = s.sse_out;
+                std::memcpy(r->R, s.R_out.m, sizeof(r->R));
+                r->t[0] = s.t_out.x; r->t[1] = s.t_out.y; r->t[2] = s.t_out.z;
+                r->iters = s.iters;
+                r->done = true;
+            }
+        }
+        ++icp_launches;
+        return FGOICP_OK;
+    }
+};
+
+}  // namespace
+}  // namespace fgoicp
+
+using namespace fgoicp;
+
+struct fgoicp_batch {
+    std::vector<PairHost> pairs;
+    fgoicp_batch_opts opts{};
+    std::vector<BatchPairResult> results;
+    std::vector<int> status;
+    uint64_t bounds_launches = 0, icp_launches = 0;
+    bool ran = false;
+};
+
+extern "C" {
+
+static int batch_create_impl(const fgoicp_batch_pair* pairs, int n, const fgoicp_batch_opts* opts, fgoicp_batch** out) {
+    if (!pairs || n <= 0 || !opts) { set_error("fgoicp_batch_create: invalid argument"); return FGOICP_ERR_INVALID_ARG; }
+    const size_t sz = opts->struct_size;
+    if (sz < offsetof(fgoicp_batch_opts, solver) + sizeof(fgoicp_solver_opts) || sz > 4096) {
+        set_error("fgoicp_batch_create: set struct_size = sizeof(fgoicp_batch_opts)");
+        return FGOICP_ERR_INVALID_ARG;
+    }
+    auto b = std::make_unique<fgoicp_batch>();
+    std::memcpy(&b->opts, opts, sz < sizeof(b->opts) ? sz : sizeof(b->opts));  // members beyond the caller's struct stay 0
+    b->opts.struct_size = sizeof(b->opts);
+    if (b->opts.solver.trim_fraction != 0.0f) { set_error("fgoicp_batch_create: trimmed pairs are not supported in a batch"); return FGOICP_ERR_INVALID_ARG; }
+    if (b->opts.max_live < 0) { set_error("fgoicp_batch_create: max_live < 0"); return FGOICP_ERR_INVALID_ARG; }
+    b->pairs.resize((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        const fgoicp_batch_pair& q = pairs[i];
+        if (!q.tgt_xyz || !q.src_xyz || q.nt == 0 || q.ns == 0 || !(q.lut_resolution > 0) || !(q.mse_threshold >= 0)) {
+            set_error("fgoicp_batch_create: invalid pair " + std::to_string(i));
+            return FGOICP_ERR_INVALID_ARG;
+        }
+        PairHost& p = b->pairs[(size_t)i];
+        p.ns = q.ns;
+        p.nt = q.nt;
+        p.pcs.resize(q.ns);
+        p.pct.resize(q.nt);
+        std::memcpy(p.pcs.data(), q.src_xyz, sizeof(Vec3f) * q.ns);
+        std::memcpy(p.pct.data(), q.tgt_xyz, sizeof(Vec3f) * q.nt);
+        // member-initialiser order of the reference ctor (fgoicp.hpp:13-19), as fgoicp_solver_create
+        p.offset_pcs = center_point_cloud(p.pcs);
+        p.offset_pct = center_point_cloud(p.pct);
+        p.scaling_factor = scale_point_clouds(p.pct, p.pcs);
+        point_cloud_ranges(p.pct, p.bounds6);
+        p.lut_resolution = q.lut_resolution;
+        p.mse_threshold = q.mse_threshold;
+    }
+    b->results.assign((size_t)n, BatchPairResult());
+    b->status.assign((size_t)n, FGOICP_OK);
+    *out = b.release();
+    return FGOICP_OK;
+}
+int fgoicp_batch_create(const fgoicp_batch_pair* pairs, int n, const fgoicp_batch_opts* opts, fgoicp_batch** out) {
+    if (!out) return FGOICP_ERR_INVALID_ARG;
+    *out = nullptr;
+    return fgoicp::abi_guard("fgoicp_batch_create", [&] { return batch_create_impl(pairs, n, opts, out); });
+}
+
+void fgoicp_batch_destroy(fgoicp_batch* b) { delete b; }
+
+static int batch_run_impl(fgoicp_batch* b, float* R_out9n, float* t_out3n, int* status_n) {
+    const int n = (int)b->pairs.size();
+    HipBatchBackend be;
+    be.pairs = &b->pairs;
+    be.device = b->opts.solver.device;
+    be.ctx_flags = b->opts.solver.ctx_flags;
+    int rc = be.init();
+    if (rc) return rc;
+    std::vector<BatchPairSpec> specs((size_t)n);
+    for (int i = 0; i < n; ++i) { specs[(size_t)i].n_thr = b->pairs[(size_t)i].ns; specs[(size_t)i].mse_threshold = b->pairs[(size_t)i].mse_threshold; }
+    {
+        BatchScheduler<HipBatchBackend> sched(be, specs, b->opts.solver.schedule, b->opts.solver.round_width, b->opts.max_live);
+        rc = sched.run();
+        if (rc) return rc;
+        for (int i = 0; i < n; ++i) {
+            b->results[(size_t)i] = sched.result(i);
+            b->status[(size_t)i] = sched.result(i).status;
+        }
+    }
+    b->bounds_launches = be.bounds_launches;
+    b->icp_launches = be.icp_launches;
+    b->ran = true;
+    for (int i = 0; i < n; ++i) {
+        const BatchPairResult& r = b->results[(size_t)i];
+        const PairHost& p = b->pairs[(size_t)i];
+        if (status_n) status_n[i] = b->status[(size_t)i];
+        if (b->status[(size_t)i]) continue;
+        const Vec3f tr = r.t / p.scaling_factor + r.R * p.offset_pcs - p.offset_pct;  // restore_translation, fgoicp.hpp:87-90
+        if (R_out9n) std::memcpy(R_out9n + 9 * (size_t)i, r.R.m, sizeof(r.R.m));
+        if (t_out3n) { t_out3n[3 * (size_t)i] = tr.x; t_out3n[3 * (size_t)i + 1] = tr.y; t_out3n[3 * (size_t)i + 2] = tr.z; }
+    }
+    return FGOICP_OK;
+}
+int fgoicp_batch_run(fgoicp_batch* b, float* R_out9n, float* t_out3n, int* status_n) {
+    if (!b) return FGOICP_ERR_INVALID_ARG;
+    return fgoicp::abi_guard("fgoicp_batch_run", [&] { return batch_run_impl(b, R_out9n, t_out3n, status_n); });
+}
+
+int fgoicp_batch_best_error(const fgoicp_batch* b, int i, float* sse_out) {
+    if (!b || !sse_out || i < 0 || i >= (int)b->pairs.size() || !b->ran || b->status[(size_t)i]) return FGOICP_ERR_INVALID_ARG;
+    *sse_out = b->results[(size_t)i].best_sse;
+    return FGOICP_OK;
+}
+
+int fgoicp_batch_stats(const fgoicp_batch* b, int i, fgoicp_run_stats* out) {
+    if (!b || !out || i < 0 || i >= (int)b->pairs.size() || !b->ran || b->status[(size_t)i]) return FGOICP_ERR_INVALID_ARG;
+    const DriverStats& d = b->results[(size_t)i].stats;
+    out->trans_cubes = d.trans_cubes; out->bounds_calls = d.bounds_calls; out->rot_cubes = d.rot_cubes;
+    out->icp_runs = d.icp_runs; out->icp_iters = d.icp_iters; out->inner_bnb = d.inner_bnb; out->rounds = d.rounds;
+    out->seconds_total = d.seconds_total; out->seconds_bnb = d.seconds_bnb; out->seconds_icp = d.seconds_icp; out->initial_icp_sse = d.initial_icp_sse;
+    return FGOICP_OK;
+}
+
+int fgoicp_batch_launches(const fgoicp_batch* b, uint64_t* bounds_launches, uint64_t* icp_launches) {
+    if (!b) return FGOICP_ERR_INVALID_ARG;
+    if (bounds_launches) *bounds_launches = b->bounds_launches;
+    if (icp_launches) *icp_launches = b->icp_launches;
+    return FGOICP_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,352 @@
+// Host side of fgoicp_batch: many registrations on one device, every link of their latency chains paid once for all of them.
+//
+// Each live pair runs its own, unchanged GoIcpDriver (driver.hpp) on a host thread of its own, over BatchOps: bounds_submit queues
+// the request, bounds_collect and icp block.  ONE launcher thread (the caller of run()) loops:
+//   1. wait until every live driver is blocked or has finished;
+//   2. hand every pending bounds request to the backend at once (one fused evaluation per tick);
+//   3. start the ICP runs that were asked for and advance every active one by one iteration (one shared host turn-around);
+//   4. wake the drivers whose requests are complete.
+// Pairs enter a window of at most max_live live pairs in index order; the backend creates a pair's device state when it enters and
+// frees it when it finishes.  Written against an abstract backend, without HIP (like multi_link.hpp), so that the CPU tests run it over
+// the oracle's operators and under ThreadSanitizer:
+//
+//     int  Backend::admit(int pair)                     device state of the pair (0, or a status; kBatchNoRoom = retry when a slot frees)
+//     bool Backend::room_for_more(int live)             max_live = 0: may another pair enter next to `live` live ones?
+//     void Backend::release(int pair)
+//     int  Backend::bounds(std::vector<BatchBoundsReq*>&)   every request's lb / ub
+//     int  Backend::icp_start(BatchIcpReq&)             a run of fgoicp_icp; may complete it at once (req.done)
+//     int  Backend::icp_step(std::vector<BatchIcpReq*>&)    one iteration of every active run; completes those whose loop ended
+//
+// A request's results depend on its pair and its inputs only, never on which other requests share the launch, so every pair gets the
+// bits of its own solo run whatever the grouping (tests/test_batch_host.py varies it at random).
+#pragma once
+#include <condition_variable>
+#include <cstdint>
+#include <cstring>
+#include <functional>
+#include <memory>
+#include <mutex>
+#include <random>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "../../../include/fgoicp_amd.h"
+#include "driver.hpp"
+
+namespace fgoicp {
+
+void set_error(const std::string& s);  // the thread's fgoicp_last_error
+
+// max_live = 0: at most this many live pairs (each holds a host thread and a context with its streams), fewer if device memory says so
+constexpr int kBatchAutoLive = 16;
+constexpr int kBatchNoRoom = -1;  // Backend::admit: out of device memory while other pairs are live — wait for one of them to finish
+
+struct BatchBoundsReq {
+    int pair = 0;
+    int G = 0;
+    std::vector<float> R9, spans, tn4, lb, ub;
+    std::vector<int> fix, offsets;
+    bool pending = false, done = false;
+    int rc = 0;
+};
+struct BatchIcpReq {
+    int pair = 0;
+    float R0[9], t0[3];
+    size_t max_iter = 0;
+    float thr = 0.f;
+    float sse = 0.f, R[9], t[3];
+    int iters = 0;
+    bool pending = false, started = false, done = false;
+    int rc = 0;
+};
+
+// what one pair of the batch is run with
+struct BatchPairSpec {
+    size_t n_thr = 0;        // points behind sse_threshold (ns)
+    float mse_threshold = 0.f;
+};
+struct BatchPairResult {
+    int status = 0;
+    Mat3f R = Mat3f::identity();
+    Vec3f t{0.f, 0.f, 0.f};  // in the solver's scaled frame (the caller restores it)
+    float best_sse = 0.f;
+    DriverStats stats;
+};
+
+template <class Backend> class BatchScheduler;
+
+// The operator interface of driver.hpp as seen by one driver of a batch.
+template <class Backend>
+struct BatchOps {
+    BatchScheduler<Backend>* s = nullptr;
+    int pair = 0;
+    int bounds_submit(int slot, int G, const float* R9, const float* rot_span, const int* fix_rot, const int* offsets, const float* tn4, const int* /*twin: rows apart*/,
+                      const float* /*cut_above: full evaluation*/) {
+        return s->submit(pair, slot, G, R9, rot_span, fix_rot, offsets, tn4);
+    }
+    int bounds_collect(int slot, float* lb, float* ub) { return s->collect(pair, slot, lb, ub); }
+    int bounds_multi(int G, const float* R9, const float* rot_span, const int* fix_rot, const int* offsets, const float* tn4, float* lb, float* ub, const float* cut_above) {
+        const int rc = bounds_submit(0, G, R9, rot_span, fix_rot, offsets, tn4, nullptr, cut_above);
+        return rc ? rc : bounds_collect(0, lb, ub);
+    }
+    bool async() const { return true; }
+    // as the solo context answers: its LB tasks then keep the memo of their twins' rows, and under ROUND the memo decides how many
+    // batches a task consumes per tick — hence which tasks share a half, hence the tail batch sizes and the counters.  The fused kernel
+    // evaluates a twin pair as two rows: same bits (fgoicp_bounds_submit_twins).
+    bool twins() const { return true; }
+    int icp(const float* R0, const float* t0, size_t max_iter, float thr, float* sse, float* R9, float* t3, int* iters) {
+        return s->icp(pair, R0, t0, max_iter, thr, sse, R9, t3, iters);
+    }
+    int icp_background(const float* R0, const float* t0, size_t max_iter, float thr, float* sse, float* R9, float* t3, int* iters) {
+        return icp(R0, t0, max_iter, thr, sse, R9, t3, iters);
+    }
+    int icp_coop(int, int, int (*)(void*, size_t, void*), void*, const float* R0, const float* t0, size_t max_iter, float thr, float* sse, float* R9, float* t3, int* iters) {
+        return icp(R0, t0, max_iter, thr, sse, R9, t3, iters);  // a batch has one rank
+    }
+};
+
+template <class Backend>
+class BatchScheduler {
+public:
+    BatchScheduler(Backend& be, std::vector<BatchPairSpec> specs, int schedule, int round_width, int max_live)
+        : be_(be), specs_(std::move(specs)), schedule_(schedule), round_width_(round_width), max_live_(max_live < 0 ? 0 : max_live), pairs_(specs_.size()) {}
+    ~BatchScheduler() { join_all(); }
+
+    // Test hook: with seed != 0 every launcher pass serves a random non-empty subset of the pending requests, after a random pause of up to
+    // max_pause_us, so that the grouping of requests into launches varies from run to run.
+    void set_jitter(uint64_t seed, int max_pause_us) { jitter_seed_ = seed; jitter_pause_us_ = max_pause_us; }
+
+    // Runs every pair; returns 0 when the batch ran (per-pair outcomes in result(i)), or the status of a launcher failure.
+    int run() {
+        std::mt19937_64 rng(jitter_seed_);
+        const int n = (int)pairs_.size();
+        for (auto& p : pairs_) p = std::make_unique<PairState>();
+        int next = 0, live = 0, rc_all = 0;
+        bool no_room = false;  // the last admission ran out of device memory: retried once a live pair has finished
+        std::unique_lock<std::mutex> lk(mu_);
+        for (;;) {
+            // admission, in index order
+            while (next < n && !no_room && (max_live_ == 0 ? (live == 0 || (live < kBatchAutoLive && be_.room_for_more(live))) : live < max_live_)) {
+                lk.unlock();
+                const int rc = be_.admit(next);
+                lk.lock();
+                if (rc == kBatchNoRoom && live > 0) { no_room = true; break; }  // wait for a live pair to finish before the next attempt
+                if (rc) { pairs_[(size_t)next]->result.status = rc == kBatchNoRoom ? FGOICP_ERR_OOM : rc; ++next; continue; }
+                start_pair(next);
+                ++live;
+                ++next;
+            }
+            if (live == 0 && next >= n) break;
+            cv_launcher_.wait(lk, [&] { return running_ == 0; });
+            // finished drivers: join, free their device state
+            bool reaped = false;
+            for (int i = 0; i < n; ++i) {
+                PairState& p = *pairs_[(size_t)i];
+                if (p.thread.joinable() && p.finished) {
+                    lk.unlock();
+                    p.thread.join();
+                    be_.release(i);
+                    lk.lock();
+                    p.released = true;
+                    --live;
+                    no_room = false;
+                    reaped = true;
+                }
+            }
+            std::vector<BatchBoundsReq*> breqs;
+            std::vector<BatchIcpReq*> starts;
+            for (auto& pp : pairs_) {
+                PairState& p = *pp;
+                for (auto& r : p.slot) if (r.pending) breqs.push_back(&r);
+                if (p.icp.pending && !p.icp.started) starts.push_back(&p.icp);
+            }
+            if (jitter_seed_) {
+                auto thin = [&](auto& v) {
+                    if (v.size() < 2) return;
+                    std::vector<typename std::decay_t<decltype(v)>::value_type> keep;
+                    for (auto* r : v) if (rng() & 1) keep.push_back(r);
+                    if (keep.empty()) keep.push_back(v[rng() % v.size()]);
+                    v.swap(keep);
+                };
+                thin(breqs);
+                thin(starts);
+            }
+            if (breqs.empty() && starts.empty() && active_icp_.empty()) {
+                if (reaped) continue;
+                // nothing to serve and nobody running: every live driver would wait for ever (cannot happen: a blocked driver has a request)
+                fgoicp::set_error("fgoicp_batch_run: the launcher found no request while drivers waited");
+                return abort_all(lk, FGOICP_ERR_HIP);
+            }
+            lk.unlock();
+            if (jitter_pause_us_ > 0) std::this_thread::sleep_for(std::chrono::microseconds((int)(rng() % (uint64_t)jitter_pause_us_)));
+            int rc = breqs.empty() ? 0 : be_.bounds(breqs);
+            for (BatchIcpReq* r : starts) {
+                if (rc) break;
+                r->started = true;
+                rc = be_.icp_start(*r);
+                if (!rc && !r->done) active_icp_.push_back(r);
+            }
+            if (!rc && !active_icp_.empty()) {
+                std::vector<BatchIcpReq*> step = active_icp_;
+                rc = be_.icp_step(step);
+            }
+            lk.lock();
+            if (rc) {
+                rc_all = rc;
+                for (BatchBoundsReq* r : breqs) { r->rc = rc; r->done = true; }
+                for (BatchIcpReq* r : active_icp_) { r->rc = rc; r->done = true; }
+                for (BatchIcpReq* r : starts) { r->rc = rc; r->done = true; }
+            }
+            for (BatchBoundsReq* r : breqs) { r->pending = false; r->done = true; }
+            std::vector<BatchIcpReq*> still;
+            for (BatchIcpReq* r : active_icp_) if (!r->done) still.push_back(r);
+            active_icp_.swap(still);
+            for (BatchIcpReq* r : starts) if (r->done) r->pending = false;
+            for (auto& pp : pairs_) {
+                PairState& p = *pp;
+                if (p.icp.done) p.icp.pending = false;
+                if (p.waiting && (p.wait_slot == 2 ? p.icp.done : p.slot[p.wait_slot].done)) wake(p);
+            }
+            cv_drivers_.notify_all();
+            if (rc) return abort_all(lk, rc_all);  // the device failed: every driver gets the status, the launcher drains them and stops
+        }
+        lk.unlock();
+        join_all();
+        return rc_all;
+    }
+    const BatchPairResult& result(int i) const { return pairs_[(size_t)i]->result; }
+    int size() const { return (int)pairs_.size(); }
+
+    // ---- driver side (BatchOps) ----
+    int submit(int pair, int slot, int G, const float* R9, const float* rot_span, const int* fix_rot, const int* offsets, const float* tn4) {
+        PairState& p = *pairs_[(size_t)pair];
+        std::lock_guard<std::mutex> g(mu_);
+        BatchBoundsReq& r = p.slot[slot];
+        if (r.pending) return FGOICP_ERR_INVALID_ARG;
+        r.pair = pair;
+        r.G = G;
+        const int total = offsets[G];
+        r.R9.assign(R9, R9 + 9 * G);
+        r.spans.assign(rot_span, rot_span + G);
+        r.fix.assign(fix_rot, fix_rot + G);
+        r.offsets.assign(offsets, offsets + G + 1);
+        r.tn4.assign(tn4, tn4 + 4 * (size_t)total);
+        r.lb.assign((size_t)total, 0.f);
+        r.ub.assign((size_t)total, 0.f);
+        r.rc = 0;
+        r.done = false;
+        r.pending = true;
+        return 0;
+    }
+    int collect(int pair, int slot, float* lb, float* ub) {
+        PairState& p = *pairs_[(size_t)pair];
+        std::unique_lock<std::mutex> lk(mu_);
+        BatchBoundsReq& r = p.slot[slot];
+        block(lk, p, slot, [&] { return r.done || abort_; });
+        if (!r.done) return FGOICP_ERR_HIP;  // the launcher stopped (its status is the run's)
+        r.done = false;
+        if (r.rc) return r.rc;
+        std::memcpy(lb, r.lb.data(), sizeof(float) * r.lb.size());
+        std::memcpy(ub, r.ub.data(), sizeof(float) * r.ub.size());
+        return 0;
+    }
+    int icp(int pair, const float* R0, const float* t0, size_t max_iter, float thr, float* sse, float* R9, float* t3, int* iters) {
+        PairState& p = *pairs_[(size_t)pair];
+        std::unique_lock<std::mutex> lk(mu_);
+        BatchIcpReq& r = p.icp;
+        r.pair = pair;
+        std::memcpy(r.R0, R0, sizeof(r.R0));
+        std::memcpy(r.t0, t0, sizeof(r.t0));
+        r.max_iter = max_iter;
+        r.thr = thr;
+        r.rc = 0;
+        r.done = r.started = false;
+        r.pending = true;
+        block(lk, p, 2, [&] { return r.done || abort_; });
+        if (!r.done) return FGOICP_ERR_HIP;  // the launcher stopped (its status is the run's)
+        r.done = false;
+        if (r.rc) return r.rc;
+        *sse = r.sse;
+        std::memcpy(R9, r.R, sizeof(r.R));
+        std::memcpy(t3, r.t, sizeof(r.t));
+        *iters = r.iters;
+        return 0;
+    }
+
+private:
+    // mu_ held: every driver is released with an error status, joined, and every live pair's device state freed
+    int abort_all(std::unique_lock<std::mutex>& lk, int rc) {
+        abort_ = true;
+        for (auto& pp : pairs_) if (pp->waiting) wake(*pp);
+        cv_drivers_.notify_all();
+        lk.unlock();
+        join_all();
+        for (size_t i = 0; i < pairs_.size(); ++i)
+            if (pairs_[i]->admitted && !pairs_[i]->released) { be_.release((int)i); pairs_[i]->released = true; }
+        return rc;
+    }
+    struct PairState {
+        std::thread thread;
+        BatchBoundsReq slot[2];
+        BatchIcpReq icp;
+        bool waiting = false, finished = false, admitted = false, released = false;
+        int wait_slot = 0;          // 0, 1: a bounds slot, 2: the ICP run
+        BatchPairResult result;
+    };
+    // called with mu_ held: the driver waits until `ready`; while it waits it does not count as running
+    template <class Pred>
+    void block(std::unique_lock<std::mutex>& lk, PairState& p, int what, Pred ready) {
+        if (ready()) return;
+        p.waiting = true;
+        p.wait_slot = what;
+        if (--running_ == 0) cv_launcher_.notify_one();
+        cv_drivers_.wait(lk, [&] { return !p.waiting; });
+    }
+    void wake(PairState& p) {  // mu_ held
+        p.waiting = false;
+        ++running_;
+    }
+    void start_pair(int i) {  // mu_ held
+        PairState& p = *pairs_[(size_t)i];
+        p.admitted = true;
+        ++running_;
+        p.thread = std::thread([this, i] { drive(i); });
+    }
+    void drive(int i) {
+        PairState& p = *pairs_[(size_t)i];
+        BatchOps<Backend> ops;
+        ops.s = this;
+        ops.pair = i;
+        BatchPairResult res;
+        {
+            GoIcpDriver<BatchOps<Backend>> drv(ops, specs_[(size_t)i].n_thr, specs_[(size_t)i].mse_threshold, schedule_, round_width_, 1);
+            res.status = drv.run();
+            drv.best_transform(res.R, res.t);
+            res.best_sse = drv.best_sse();
+            res.stats = drv.stats();
+        }
+        std::lock_guard<std::mutex> g(mu_);
+        p.result = res;
+        p.finished = true;
+        if (--running_ == 0) cv_launcher_.notify_one();
+    }
+    void join_all() {
+        for (auto& p : pairs_)
+            if (p && p->thread.joinable()) p->thread.join();
+    }
+
+    Backend& be_;
+    std::vector<BatchPairSpec> specs_;
+    int schedule_, round_width_, max_live_;
+    std::vector<std::unique_ptr<PairState>> pairs_;
+    std::vector<BatchIcpReq*> active_icp_;   // launcher only
+    std::mutex mu_;
+    std::condition_variable cv_launcher_, cv_drivers_;
+    int running_ = 0;                        // live drivers that are neither blocked nor finished
+    bool abort_ = false;
+    uint64_t jitter_seed_ = 0;
+    int jitter_pause_us_ = 0;
+};
+
+}  // namespace fgoicp

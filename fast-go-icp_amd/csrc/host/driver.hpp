@@ -364,10 +364,12 @@ private:
 template <class Ops>
 class GoIcpDriver {
 public:
-    GoIcpDriver(Ops& ops, size_t ns, float mse_threshold, int schedule, int round_width)
+    // host_threads > 0: that many pool threads (1 = none besides the caller; the drivers of a batch), 0 = FGOICP_HOST_THREADS or 4
+    GoIcpDriver(Ops& ops, size_t ns, float mse_threshold, int schedule, int round_width, int host_threads = 0)
         : ops_(ops), sse_threshold_(ns * mse_threshold), ns_(ns), schedule_(schedule), round_width_(round_width < 0 ? 0 : round_width) {
         int nthreads = 4;
         if (const char* e = std::getenv("FGOICP_HOST_THREADS")) nthreads = std::atoi(e);
+        if (host_threads > 0) nthreads = host_threads;
         const int hw = (int)std::thread::hardware_concurrency();
         if (hw > 0 && nthreads > hw) nthreads = hw;
         if (nthreads < 1) nthreads = 1;

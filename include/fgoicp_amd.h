@@ -394,6 +394,39 @@ int fgoicp_multi_recorded(const fgoicp_multi* m, int rank, uint64_t* host_exchan
 int fgoicp_multi_test_fault(fgoicp_multi* m, int rank, long call);
 int fgoicp_multi_replay_rank(fgoicp_multi* m, int rank, double* seconds_out);
 
+/* ------------------------------------------------------------------------------------------
+ * Batches: many registrations on one device (no reference counterpart).  Each pair of a batch returns exactly what
+ * fgoicp_solver_run returns for it alone with the same options — R, the restored t, the best error and the counters trans_cubes,
+ * rot_cubes, inner_bnb, icp_runs, icp_iters, rounds, initial_icp_sse, bit for bit, under both schedules — whatever the other pairs,
+ * their order or the grouping of requests into launches.  bounds_calls and the timings are not part of that.  Every live pair runs
+ * its own search; the bounds requests of all of them are evaluated in fused launches (one per LUT layout present in a tick) and their
+ * ICP runs are advanced in lock-step, so the host turn-arounds are paid once for all live pairs.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct fgoicp_batch fgoicp_batch;
+typedef struct fgoicp_batch_pair {
+    const float* tgt_xyz; size_t nt; const float* src_xyz; size_t ns;
+    float lut_resolution; float mse_threshold;           /* per pair, as fgoicp_solver_create takes them */
+} fgoicp_batch_pair;
+typedef struct fgoicp_batch_opts {
+    size_t struct_size;          /* sizeof(fgoicp_batch_opts) as the caller was compiled (ABI 2): members beyond it are taken as 0 */
+    fgoicp_solver_opts solver;   /* schedule, round_width, ctx_flags, device; trim_fraction must be 0 */
+    int max_live;                /* pairs whose device state (context: LUT, tree, source order) exists at once; 0 = as many as device memory allows, at most 16 */
+} fgoicp_batch_opts;
+/* Copies the clouds and pre-processes every pair on the host (centre, scale, bounds, as fgoicp_solver_create); creates no device
+ * state.  Refuses n <= 0, a null or empty cloud, trim_fraction != 0 and a struct_size shorter than the solver options. */
+int fgoicp_batch_create(const fgoicp_batch_pair* pairs, int n, const fgoicp_batch_opts* opts, fgoicp_batch** out);
+/* Runs every pair: pairs enter a window of at most max_live live pairs in index order; a pair's context is created when it enters
+ * and destroyed when it finishes.  Returns FGOICP_OK when the batch ran; status_n[i] is pair i's own status (a pair that cannot be
+ * served — LUT dims above 4094: FGOICP_ERR_INVALID_ARG; FGOICP_ERR_OOM only if it does not fit with no other pair live — leaves
+ * the others untouched).  R_out9n / t_out3n: 9 / 3 floats per pair, as fgoicp_solver_run; untouched for a failed pair. */
+int fgoicp_batch_run(fgoicp_batch* b, float* R_out9n, float* t_out3n, int* status_n);
+int fgoicp_batch_best_error(const fgoicp_batch* b, int i, float* sse_out);
+int fgoicp_batch_stats(const fgoicp_batch* b, int i, fgoicp_run_stats* out);
+/* Launches of the last run: fused bounds launches (one per LUT layout class per tick, the finalize not counted) and lock-step ICP
+ * iterations (one host turn-around each, shared by every active ICP run). */
+int fgoicp_batch_launches(const fgoicp_batch* b, uint64_t* bounds_launches, uint64_t* icp_launches);
+void fgoicp_batch_destroy(fgoicp_batch* b);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,94 @@
+"""Batched Go-ICP against a loop of solo runs (fgoicp_batch vs FastGoICP), same pairs, same process, one GPU.
+
+    python tools/batch_bench.py --workload a      # 64 pairs of ~1k source / 2k target points, lut_resolution 0.01, mse_threshold 1e-3
+    python tools/batch_bench.py --workload b      # 16 pairs of the size of the reference's test/bunny.toml (~3k / 18k points)
+
+Prints one JSON line: wall time of the batch and of the loop (the loop split into context creation = LUT builds, and runs), the
+ratio, whether every pair of the batch is bit-equal to its solo run (R, t, best error, counters), and the fused bounds launches of
+the batch against the bounds launches of the solo runs summed (a profiled second loop: FGOICP_FLAG_PROFILE)."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import fgoicp_amd as fg  # noqa: E402
+
+CONTRACT = ("trans_cubes", "rot_cubes", "inner_bnb", "icp_runs", "icp_iters", "rounds", "initial_icp_sse")
+WORKLOADS = {"a": dict(n=64, ns=1000, nt=2000, lut=0.01, mse=1e-3), "b": dict(n=16, ns=3000, nt=18000, lut=0.005, mse=1e-3)}
+
+
+def make_pairs(w, seed):
+    rng = np.random.default_rng(seed)
+    pairs = []
+    for i in range(w["n"]):
+        tgt, src, _, _ = fg.synth.make_pair(w["nt"], w["ns"], (1.0, 0.8, 0.6), seed=seed * 1000 + i, angle_deg=float(rng.uniform(10, 90)))
+        pairs.append((tgt, src, w["lut"], w["mse"]))
+    return pairs
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--workload", choices=sorted(WORKLOADS), default="a")
+    ap.add_argument("--schedule", choices=["serial", "round"], default="serial")
+    ap.add_argument("--max-live", type=int, default=0)
+    ap.add_argument("--seed", type=int, default=1)
+    a = ap.parse_args()
+    w = WORKLOADS[a.workload]
+    sched = fg.SCHEDULE_ROUND if a.schedule == "round" else fg.SCHEDULE_SERIAL
+    rw = 0 if sched == fg.SCHEDULE_ROUND else 1
+    pairs = make_pairs(w, a.seed)
+    import torch
+    torch.cuda.init()
+
+    # warm-up: one solo run (module load, first allocations)
+    s = fg.FastGoICP(*pairs[0], schedule=sched, round_width=rw)
+    s.run()
+    s.close()
+
+    solo, t_create, t_run = [], 0.0, 0.0
+    for p in pairs:
+        t0 = time.perf_counter()
+        s = fg.FastGoICP(*p, schedule=sched, round_width=rw)
+        t1 = time.perf_counter()
+        R, t = s.run()
+        t2 = time.perf_counter()
+        t_create += t1 - t0
+        t_run += t2 - t1
+        solo.append((R, t, s.get_best_error(), s.stats()))
+        s.close()
+
+    b = fg.FastGoICPBatch(pairs, schedule=sched, round_width=rw, max_live=a.max_live)
+    t0 = time.perf_counter()
+    out = b.run()
+    t_batch = time.perf_counter() - t0
+    equal = []
+    for i, (R, t, e, st) in enumerate(solo):
+        ok = out[i] is not None and np.array_equal(out[i][0].view(np.uint32), R.view(np.uint32)) and np.array_equal(out[i][1].view(np.uint32), t.view(np.uint32))
+        ok = ok and np.float32(b.get_best_error(i)).view(np.uint32) == np.float32(e).view(np.uint32)
+        ok = ok and all(b.stats(i)[k] == st[k] for k in CONTRACT)
+        equal.append(bool(ok))
+    bounds_launches, icp_steps = b.launches()
+    b.close()
+
+    solo_launches = 0
+    for p in pairs:
+        s = fg.FastGoICP(*p, schedule=sched, round_width=rw, flags=fg.FLAG_PROFILE)
+        s.run()
+        solo_launches += s.registration.profile()["launches"]
+        s.close()
+
+    loop = t_create + t_run
+    print(json.dumps({
+        "workload": a.workload, "pairs": w["n"], "ns": w["ns"], "nt": w["nt"], "lut_resolution": w["lut"], "mse_threshold": w["mse"], "schedule": a.schedule,
+        "batch_s": round(t_batch, 4), "loop_s": round(loop, 4), "loop_lut_build_s": round(t_create, 4), "loop_run_s": round(t_run, 4),
+        "speedup_vs_loop": round(loop / t_batch, 3), "speedup_vs_loop_runs_only": round(t_run / t_batch, 3),
+        "bit_equal": equal, "all_bit_equal": all(equal),
+        "fused_bounds_launches": bounds_launches, "solo_bounds_launches_summed": solo_launches, "icp_lockstep_iterations": icp_steps}))
+
+
+if __name__ == "__main__":
+    main()
