@@ -149,6 +149,10 @@ _SIGS = {
     "fgoicp_batch_stats": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RunStats)]),
     "fgoicp_batch_launches": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "fgoicp_batch_destroy": (None, [C.c_void_p]),
+    "fgoicp_batch_test_bounds": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, c_int_p, c_int_p, c_float_p, c_float_p, c_int_p, c_int_p, c_float_p,
+                                           c_float_p, c_float_p, C.POINTER(C.c_uint64)]),
+    "fgoicp_batch_test_icp": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, c_int_p, c_float_p, c_float_p, C.POINTER(C.c_size_t), c_float_p, c_float_p,
+                                        c_float_p, c_float_p, c_int_p]),
 }
 TRANSPORT_RCCL = 0
 TRANSPORT_IN_PROCESS = 1

@@ -6,7 +6,8 @@
 // chunk's sums are folded by the same wave tree into the same partial, so an evaluation's partials — and the row that
 // fused_bounds_finalize_kernel sums from them in bounds_finalize_kernel's order — are the bits the pair's own context computes.  Full
 // evaluation only: no thresholds, no twin pairs, no trimming.  The layout of the packed LUT, 32/64-bit texel addressing and the weight
-// quantisation are template parameters: one launch per combination present in a tick.
+// quantisation are template parameters: one launch per combination present in a tick, split by the host into launches of at most 2^24
+// items (HipBatchBackend::bounds).
 #pragma once
 
 template <int LAYOUT, bool WIDE, bool QUANT>

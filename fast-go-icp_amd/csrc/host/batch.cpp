@@ -2,6 +2,7 @@
 // driver on a host thread of its own; this file is its device backend — one fgoicp_ctx per live pair, the bounds of all pending requests
 // in fused launches (kernels.hip, bounds_fused.hpp), the ICP runs advanced in lock-step so that they share each host turn-around.
 // The launcher (the thread that calls fgoicp_batch_run) is the only thread that touches the device.
+#include <algorithm>
 #include <cmath>
 #include <cstddef>
 #include <cstring>
@@ -34,6 +35,10 @@ struct PairHost {
     float bounds6[6] = {0, 0, 0, 0, 0, 0};
     float lut_resolution = 0.f, mse_threshold = 0.f;
 };
+
+// work items per fused launch (one 64-thread block each): a class with more is split, so that blocks x threads stay inside the 32-bit
+// grid size of a dispatch, with the margin the solo path keeps (ctx.hip, launch_fit)
+constexpr size_t kFusedLaunchItems = (size_t)1 << 24;
 
 // device staging of one class of work items (same LUT layout, addressing and quantisation)
 struct ItemClass {
@@ -81,6 +86,7 @@ struct HipBatchBackend {
     int device = 0;
     unsigned ctx_flags = 0;
     std::vector<fgoicp_ctx*> ctx;
+    bool borrowed = false;  // the test hooks: the contexts are the caller's (not destroyed here)
     std::vector<IcpStepState> icp_state;
     hipStream_t stream = nullptr;
     uint64_t bounds_launches = 0, icp_launches = 0;
@@ -97,7 +103,8 @@ struct HipBatchBackend {
     DevBuf<float> d_out;
 
     ~HipBatchBackend() {
-        for (fgoicp_ctx*& c : ctx) { fgoicp_ctx_destroy(c); c = nullptr; }
+        if (!borrowed)
+            for (fgoicp_ctx*& c : ctx) { fgoicp_ctx_destroy(c); c = nullptr; }
         h_views.release(); h_evals.release(); h_items.release(); h_out.release();
         d_views.release(); d_evals.release(); d_items.release(); d_partials.release(); d_out.release();
         if (stream) (void)hipStreamDestroy(stream);
@@ -107,6 +114,16 @@ struct HipBatchBackend {
         BCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
         ctx.assign(pairs->size(), nullptr);
         icp_state.assign(pairs->size(), IcpStepState());
+        return FGOICP_OK;
+    }
+    // the test hooks: the caller's contexts as the live pairs (checked by the caller: one device, the packed LUT)
+    int init_borrowed(fgoicp_ctx* const* cs, int n) {
+        borrowed = true;
+        ctx.assign(cs, cs + n);
+        icp_state.assign((size_t)n, IcpStepState());
+        device = n > 0 ? cs[0]->device : 0;
+        BCHK(hipSetDevice(device));
+        BCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
         return FGOICP_OK;
     }
 
@@ -140,11 +157,11 @@ struct HipBatchBackend {
         ctx[(size_t)i] = nullptr;
     }
 
-    // One tick: every row of every request, one launch per item class, one finalize.
+    // One tick: every row of every request, one launch per item class (more for a class above kFusedLaunchItems), one finalize.
     int bounds(std::vector<BatchBoundsReq*>& reqs) {
         BCHK(hipSetDevice(device));
         // views: one per pair that has a request
-        std::vector<int> view_of(pairs->size(), -1);
+        std::vector<int> view_of(ctx.size(), -1);
         std::vector<int> view_pair;
         size_t nevals = 0;
         for (BatchBoundsReq* r : reqs) {
@@ -205,10 +222,13 @@ struct HipBatchBackend {
         BCHK(hipMemcpyAsync(d_evals.p, h_evals.p, sizeof(FusedEval) * nevals, hipMemcpyHostToDevice, stream));
         BCHK(hipMemcpyAsync(d_items.p, h_items.p, sizeof(uint2) * nitems, hipMemcpyHostToDevice, stream));
         pos = 0;
-        for (const ItemClass& cl : classes) {
-            launch_fused_bounds(cl.layout, cl.wide, cl.quant, d_views.p, d_evals.p, d_items.p + pos, (unsigned)cl.items.size(), d_partials.p, stream);
+        for (const ItemClass& cl : classes) {  // one launch per class, split where it would not fit the 32-bit grid
+            for (size_t first = 0; first < cl.items.size(); first += kFusedLaunchItems) {
+                const size_t n = std::min(kFusedLaunchItems, cl.items.size() - first);
+                launch_fused_bounds(cl.layout, cl.wide, cl.quant, d_views.p, d_evals.p, d_items.p + pos + first, (unsigned)n, d_partials.p, stream);
+                ++bounds_launches;
+            }
             pos += cl.items.size();
-            ++bounds_launches;
         }
         launch_fused_finalize(d_evals.p, (int)nevals, d_partials.p, d_out.p, d_out.p + nevals, stream);
         BCHK(hipGetLastError());
@@ -373,6 +393,148 @@ int fgoicp_batch_launches(const fgoicp_batch* b, uint64_t* bounds_launches, uint
     if (bounds_launches) *bounds_launches = b->bounds_launches;
     if (icp_launches) *icp_launches = b->icp_launches;
     return FGOICP_OK;
+}
+
+// ---- test hooks: the backend's own bounds() / icp_start() + icp_step() over the caller's contexts ----
+
+// what HipBatchBackend::admit asks of a context, and one device for all of them
+static int borrowed_ctx_check(fgoicp_ctx* const* ctxs, int nctx, const char* where) {
+    for (int i = 0; i < nctx; ++i) {
+        const fgoicp_ctx* c = ctxs[i];
+        if (!c) { set_error(std::string(where) + ": context " + std::to_string(i) + " is null"); return FGOICP_ERR_INVALID_ARG; }
+        if (c->device != ctxs[0]->device) { set_error(std::string(where) + ": the contexts are on different devices"); return FGOICP_ERR_INVALID_ARG; }
+    }
+    return FGOICP_OK;
+}
+
+static int batch_test_bounds_impl(fgoicp_ctx* const* ctxs, int nctx, int nreq, const int* req_ctx, const int* req_G, const float* R9, const float* rot_span,
+                                  const int* fix_rot, const int* offsets, const float* tn4, float* lb_out, float* ub_out, uint64_t* launches_out) {
+    const char* where = "fgoicp_batch_test_bounds";
+    if (!ctxs || nctx <= 0 || nreq < 0 || (nreq > 0 && (!req_ctx || !req_G || !offsets))) { set_error(std::string(where) + ": invalid argument"); return FGOICP_ERR_INVALID_ARG; }
+    int rc = borrowed_ctx_check(ctxs, nctx, where);
+    if (rc) return rc;
+    size_t groups = 0, rows = 0, offs = 0;
+    for (int q = 0; q < nreq; ++q) {
+        const int k = req_ctx[q], G = req_G[q];
+        if (k < 0 || k >= nctx || G < 0) { set_error(std::string(where) + ": request " + std::to_string(q) + ": context index or group count out of range"); return FGOICP_ERR_INVALID_ARG; }
+        const fgoicp_ctx* c = ctxs[k];
+        if (c->inliers) { set_error(std::string(where) + ": context " + std::to_string(k) + " is trimmed (a batch has no trimmed pairs)"); return FGOICP_ERR_INVALID_ARG; }
+        if (!c->d_lut_zp) { set_error(std::string(where) + ": context " + std::to_string(k) + " has no packed LUT"); return FGOICP_ERR_INVALID_ARG; }
+        const int* o = offsets + offs;
+        for (int g = 0; g < G; ++g)
+            if (o[0] != 0 || o[g + 1] < o[g]) { set_error(std::string(where) + ": request " + std::to_string(q) + ": offsets must start at 0 and be non-decreasing"); return FGOICP_ERR_INVALID_ARG; }
+        groups += (size_t)G;
+        rows += (size_t)o[G];
+        offs += (size_t)G + 1;
+    }
+    if ((groups > 0 && (!R9 || !rot_span || !fix_rot)) || (rows > 0 && (!tn4 || !lb_out || !ub_out))) { set_error(std::string(where) + ": invalid argument"); return FGOICP_ERR_INVALID_ARG; }
+    // the requests as the scheduler hands them over (BatchScheduler::submit)
+    std::vector<BatchBoundsReq> reqs((size_t)nreq);
+    std::vector<BatchBoundsReq*> tick;
+    groups = rows = offs = 0;
+    for (int q = 0; q < nreq; ++q) {
+        BatchBoundsReq& r = reqs[(size_t)q];
+        const int G = req_G[q], n = offsets[offs + (size_t)G];
+        r.pair = req_ctx[q];
+        r.G = G;
+        r.R9.assign(R9 + 9 * groups, R9 + 9 * (groups + G));
+        r.spans.assign(rot_span + groups, rot_span + groups + G);
+        r.fix.assign(fix_rot + groups, fix_rot + groups + G);
+        r.offsets.assign(offsets + offs, offsets + offs + G + 1);
+        r.tn4.assign(tn4 + 4 * rows, tn4 + 4 * (rows + n));
+        r.lb.assign((size_t)n, 0.f);
+        r.ub.assign((size_t)n, 0.f);
+        tick.push_back(&r);
+        groups += (size_t)G;
+        rows += (size_t)n;
+        offs += (size_t)G + 1;
+    }
+    HipBatchBackend be;
+    if ((rc = be.init_borrowed(ctxs, nctx))) return rc;
+    if (!tick.empty() && (rc = be.bounds(tick))) return rc;
+    rows = 0;
+    for (const BatchBoundsReq& r : reqs) {
+        std::memcpy(lb_out + rows, r.lb.data(), sizeof(float) * r.lb.size());
+        std::memcpy(ub_out + rows, r.ub.data(), sizeof(float) * r.ub.size());
+        rows += r.lb.size();
+    }
+    if (launches_out) *launches_out = be.bounds_launches;
+    return FGOICP_OK;
+}
+int fgoicp_batch_test_bounds(fgoicp_ctx* const* ctxs, int nctx, int nreq, const int* req_ctx, const int* req_G, const float* R9, const float* rot_span,
+                             const int* fix_rot, const int* offsets, const float* tn4, float* lb_out, float* ub_out, uint64_t* launches_out) {
+    return fgoicp::abi_guard("fgoicp_batch_test_bounds", [&] {
+        return batch_test_bounds_impl(ctxs, nctx, nreq, req_ctx, req_G, R9, rot_span, fix_rot, offsets, tn4, lb_out, ub_out, launches_out);
+    });
+}
+
+static int batch_test_icp_impl(fgoicp_ctx* const* ctxs, int n, const int* start_pass, const float* R0s_9, const float* t0s_3, const size_t* max_iter,
+                               const float* thr, float* sse_out, float* R_out9, float* t_out3, int* iters_out) {
+    const char* where = "fgoicp_batch_test_icp";
+    if (n < 0 || (n > 0 && (!ctxs || !start_pass || !R0s_9 || !t0s_3 || !max_iter || !thr || !sse_out || !R_out9 || !t_out3 || !iters_out))) {
+        set_error(std::string(where) + ": invalid argument");
+        return FGOICP_ERR_INVALID_ARG;
+    }
+    if (n == 0) return FGOICP_OK;
+    int rc = borrowed_ctx_check(ctxs, n, where);
+    if (rc) return rc;
+    for (int i = 0; i < n; ++i) {
+        if (start_pass[i] < 0) { set_error(std::string(where) + ": start_pass < 0"); return FGOICP_ERR_INVALID_ARG; }
+        for (int j = 0; j < i; ++j)
+            if (ctxs[j] == ctxs[i]) { set_error(std::string(where) + ": a context may run one ICP at a time"); return FGOICP_ERR_INVALID_ARG; }
+    }
+    std::vector<BatchIcpReq> reqs((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        BatchIcpReq& r = reqs[(size_t)i];
+        r.pair = i;
+        std::memcpy(r.R0, R0s_9 + 9 * (size_t)i, sizeof(r.R0));
+        std::memcpy(r.t0, t0s_3 + 3 * (size_t)i, sizeof(r.t0));
+        r.max_iter = max_iter[i];
+        r.thr = thr[i];
+    }
+    HipBatchBackend be;
+    if ((rc = be.init_borrowed(ctxs, n))) return rc;
+    // the launcher's passes (BatchScheduler::run): the runs that start now, then one step of every active run
+    std::vector<BatchIcpReq*> active;
+    int left = n;
+    for (int pass = 0; left > 0; ++pass) {
+        if (active.empty()) {  // nothing to step: on to the next pass that starts a run
+            int next = -1;
+            for (int i = 0; i < n; ++i)
+                if (!reqs[(size_t)i].started && (next < 0 || start_pass[i] < next)) next = start_pass[i];
+            if (next > pass) pass = next;
+        }
+        for (int i = 0; i < n; ++i) {
+            BatchIcpReq& r = reqs[(size_t)i];
+            if (r.started || start_pass[i] != pass) continue;
+            r.started = true;
+            if ((rc = be.icp_start(r))) return rc;
+            if (!r.done) active.push_back(&r);
+        }
+        if (!active.empty()) {
+            std::vector<BatchIcpReq*> step = active;
+            if ((rc = be.icp_step(step))) return rc;
+        }
+        std::vector<BatchIcpReq*> still;
+        for (BatchIcpReq* r : active) if (!r->done) still.push_back(r);
+        active.swap(still);
+        left = 0;
+        for (const BatchIcpReq& r : reqs) left += r.done ? 0 : 1;
+    }
+    for (int i = 0; i < n; ++i) {
+        const BatchIcpReq& r = reqs[(size_t)i];
+        sse_out[i] = r.sse;
+        std::memcpy(R_out9 + 9 * (size_t)i, r.R, sizeof(r.R));
+        std::memcpy(t_out3 + 3 * (size_t)i, r.t, sizeof(r.t));
+        iters_out[i] = r.iters;
+    }
+    return FGOICP_OK;
+}
+int fgoicp_batch_test_icp(fgoicp_ctx* const* ctxs, int n, const int* start_pass, const float* R0s_9, const float* t0s_3, const size_t* max_iter,
+                          const float* thr, float* sse_out, float* R_out9, float* t_out3, int* iters_out) {
+    return fgoicp::abi_guard("fgoicp_batch_test_icp", [&] {
+        return batch_test_icp_impl(ctxs, n, start_pass, R0s_9, t0s_3, max_iter, thr, sse_out, R_out9, t_out3, iters_out);
+    });
 }
 
 }  // extern "C"

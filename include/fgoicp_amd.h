@@ -399,7 +399,7 @@ int fgoicp_multi_replay_rank(fgoicp_multi* m, int rank, double* seconds_out);
  * fgoicp_solver_run returns for it alone with the same options — R, the restored t, the best error and the counters trans_cubes,
  * rot_cubes, inner_bnb, icp_runs, icp_iters, rounds, initial_icp_sse, bit for bit, under both schedules — whatever the other pairs,
  * their order or the grouping of requests into launches.  bounds_calls and the timings are not part of that.  Every live pair runs
- * its own search; the bounds requests of all of them are evaluated in fused launches (one per LUT layout present in a tick) and their
+ * its own search; the bounds requests of all of them are evaluated in fused launches (one per LUT class present in a tick; a class of more than 2^24 work items is split) and their
  * ICP runs are advanced in lock-step, so the host turn-arounds are paid once for all live pairs.
  * ------------------------------------------------------------------------------------------ */
 typedef struct fgoicp_batch fgoicp_batch;
@@ -422,10 +422,25 @@ int fgoicp_batch_create(const fgoicp_batch_pair* pairs, int n, const fgoicp_batc
 int fgoicp_batch_run(fgoicp_batch* b, float* R_out9n, float* t_out3n, int* status_n);
 int fgoicp_batch_best_error(const fgoicp_batch* b, int i, float* sse_out);
 int fgoicp_batch_stats(const fgoicp_batch* b, int i, fgoicp_run_stats* out);
-/* Launches of the last run: fused bounds launches (one per LUT layout class per tick, the finalize not counted) and lock-step ICP
+/* Launches of the last run: fused bounds launches (one per LUT class per tick, more for a class of more than 2^24 work items; the finalize not counted) and lock-step ICP
  * iterations (one host turn-around each, shared by every active ICP run). */
 int fgoicp_batch_launches(const fgoicp_batch* b, uint64_t* bounds_launches, uint64_t* icp_launches);
 void fgoicp_batch_destroy(fgoicp_batch* b);
+/* TEST HOOK, not part of the drop-in surface: one tick of the batch's bounds path over contexts the caller made (fgoicp_ctx_create;
+ * borrowed, not destroyed).  Request q goes to ctxs[req_ctx[q]] (a context may be named by several requests) with req_G[q] groups; R9,
+ * rot_span, fix_rot, offsets (req_G[q] + 1 entries per request, each run starting at 0), tn4, lb_out and ub_out are laid out as
+ * fgoicp_bounds_multi takes them, the requests' arrays concatenated.  All requests share the fused launches of one tick;
+ * launches_out (optional) = fused bounds launches the tick made.  Refuses (FGOICP_ERR_INVALID_ARG, before any device work) null
+ * arguments, nreq < 0, an index out of range, bad offsets, a trimmed context (fgoicp_ctx_set_inliers), a context without the packed
+ * LUT and contexts on different devices. */
+int fgoicp_batch_test_bounds(fgoicp_ctx* const* ctxs, int nctx, int nreq, const int* req_ctx, const int* req_G, const float* R9, const float* rot_span,
+                             const int* fix_rot, const int* offsets, const float* tn4, float* lb_out, float* ub_out, uint64_t* launches_out);
+/* TEST HOOK, not part of the drop-in surface: n ICP runs stepped as a batch steps them, run i on ctxs[i] (borrowed; each context once,
+ * all on one device).  Pass p starts the runs whose start_pass is p, then advances every active run by one iteration; contexts that
+ * cannot be stepped (more than 262144 source points, brute force) run their whole loop when they start.  Outputs as fgoicp_icp, one
+ * run after the other (9 / 3 floats per run). */
+int fgoicp_batch_test_icp(fgoicp_ctx* const* ctxs, int n, const int* start_pass, const float* R0s_9, const float* t0s_3, const size_t* max_iter,
+                          const float* thr, float* sse_out, float* R_out9, float* t_out3, int* iters_out);
 
 #ifdef __cplusplus
 }

@@ -117,6 +117,28 @@ def test_invalid_arguments_are_refused_before_any_device_work(fg):
     assert lib.fgoicp_multi_run(None, None, None) == 1 and lib.fgoicp_multi_world(None) == 0 and not lib.fgoicp_multi_solver(None, 0)
     assert lib.fgoicp_multi_recorded(None, 0, None, None) == 1 and lib.fgoicp_multi_set_record(None, 1) == 1 and lib.fgoicp_multi_replay_rank(None, 0, None) == 1 and lib.fgoicp_multi_seconds(None, 0, None) == 1
     assert lib.fgoicp_rccl_comm_count(None, None) == 1 and lib.fgoicp_multi_test_fault(None, 0, 0) == 1 and lib.fgoicp_ctx_test_sort_fault(None, 0) == 1
+    # the batch test hooks: null arguments, counts and indices out of range, a null context, bad offsets — all before any device work
+    one, zero, minus = (C.c_int * 2)(1, 1), (C.c_int * 2)(0, 0), (C.c_int * 2)(-1, -1)
+    offs = (C.c_int * 2)(0, 1)
+    fake = (C.c_void_p * 2)(None, None)
+    buf = np.zeros(18, np.float32)
+    b = buf.ctypes.data_as(fg._lib.c_float_p)
+    n_out = C.c_uint64(7)
+    tb = lib.fgoicp_batch_test_bounds
+    assert tb(None, 1, 1, zero, one, b, b, zero, offs, b, b, b, C.byref(n_out)) == 1
+    assert tb(fake, 0, 0, None, None, None, None, None, None, None, None, None, None) == 1  # no contexts
+    assert tb(fake, 1, -1, None, None, None, None, None, None, None, None, None, None) == 1  # nreq < 0
+    assert tb(fake, 1, 1, None, one, b, b, zero, offs, b, b, b, None) == 1 and tb(fake, 1, 1, zero, None, b, b, zero, offs, b, b, b, None) == 1
+    assert tb(fake, 1, 1, zero, one, b, b, zero, None, b, b, b, None) == 1
+    assert tb(fake, 1, 1, zero, one, b, b, zero, offs, b, b, b, None) == 1  # a null context
+    assert n_out.value == 7  # nothing written on refusal
+    tc = lib.fgoicp_batch_test_icp
+    sz = (C.c_size_t * 2)(5, 5)
+    assert tc(None, 1, zero, b, b, sz, b, b, b, b, zero) == 1 and tc(fake, -1, zero, b, b, sz, b, b, b, b, zero) == 1
+    assert tc(fake, 1, None, b, b, sz, b, b, b, b, zero) == 1 and tc(fake, 1, zero, b, b, None, b, b, b, b, zero) == 1
+    assert tc(fake, 1, zero, b, b, sz, b, b, b, b, None) == 1
+    assert tc(fake, 1, zero, b, b, sz, b, b, b, b, zero) == 1 and tc(fake, 1, minus, b, b, sz, b, b, b, b, zero) == 1  # a null context
+    assert tc(fake, 0, None, None, None, None, None, None, None, None, None) == 0  # nothing to run
     lib.fgoicp_multi_destroy(None); lib.fgoicp_rccl_destroy(None)  # no-ops
     assert b"invalid" in lib.fgoicp_last_error() or b"" == lib.fgoicp_last_error()[:0]
 
