@@ -64,7 +64,7 @@ class BatchPair(C.Structure):
 
 
 class BatchOpts(C.Structure):
-    _fields_ = [("struct_size", C.c_size_t), ("solver", SolverOpts), ("max_live", C.c_int)]
+    _fields_ = [("struct_size", C.c_size_t), ("solver", SolverOpts), ("max_live", C.c_int), ("trim_fractions", c_float_p)]  # n entries or NULL
 
 
 SCHEDULE_SERIAL = 0
@@ -151,6 +151,8 @@ _SIGS = {
     "fgoicp_batch_destroy": (None, [C.c_void_p]),
     "fgoicp_batch_test_bounds": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, c_int_p, c_int_p, c_float_p, c_float_p, c_int_p, c_int_p, c_float_p,
                                            c_float_p, c_float_p, C.POINTER(C.c_uint64)]),
+    "fgoicp_batch_test_trim_bounds": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, c_int_p, c_int_p, c_float_p, c_float_p, c_int_p, c_int_p, c_float_p,
+                                                c_float_p, c_float_p, C.POINTER(C.c_uint64), C.c_size_t, C.POINTER(C.c_uint64)]),
     "fgoicp_batch_test_icp": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, c_int_p, c_float_p, c_float_p, C.POINTER(C.c_size_t), c_float_p, c_float_p,
                                         c_float_p, c_float_p, c_int_p]),
 }

@@ -10,20 +10,24 @@ from .registration import _cloud, _fp
 
 
 class FastGoICPBatch:
-    """pairs: iterable of (pct, pcs) or (pct, pcs, lut_resolution, mse_threshold); the defaults below apply to the short form."""
+    """pairs: iterable of (pct, pcs), (pct, pcs, lut_resolution, mse_threshold) or (pct, pcs, lut_resolution, mse_threshold, trim_fraction);
+    the defaults below apply to what a pair leaves out.  trim_fraction: as FastGoICP's, per pair (0 = untrimmed)."""
 
     def __init__(self, pairs, lut_resolution=0.005, mse_threshold=1e-3, schedule=_lib.SCHEDULE_SERIAL, round_width=1, device=0, flags=0,
-                 max_live=0):
+                 max_live=0, trim_fraction=0.0):
         self._lib = _lib.load()
         self._clouds = []
         arr = (_lib.BatchPair * max(1, len(pairs)))()
+        trim = np.zeros(max(1, len(pairs)), np.float32)
         for i, p in enumerate(pairs):
             pct, pcs = _cloud(p[0]), _cloud(p[1])
             lr, mt = (p[2], p[3]) if len(p) > 2 else (lut_resolution, mse_threshold)
+            trim[i] = p[4] if len(p) > 4 else trim_fraction
             self._clouds.append((pct, pcs))  # the library copies them at create; kept until then
             arr[i] = _lib.BatchPair(_fp(pct), len(pct), _fp(pcs), len(pcs), float(lr), float(mt))
         self.n = len(pairs)
-        opts = _lib.BatchOpts(C.sizeof(_lib.BatchOpts), _lib.SolverOpts(int(schedule), int(round_width), int(flags), int(device), 0.0), int(max_live))
+        opts = _lib.BatchOpts(C.sizeof(_lib.BatchOpts), _lib.SolverOpts(int(schedule), int(round_width), int(flags), int(device), 0.0), int(max_live),
+                              _fp(trim))
         self._h = C.c_void_p()
         _lib.check(self._lib.fgoicp_batch_create(arr, self.n, C.byref(opts), C.byref(self._h)), "fgoicp_batch_create")
         self._clouds = None

@@ -23,7 +23,8 @@ static std::string usage(const std::string& exe) {
 }
 
 // --batch LIST: every config of the list registered in one fgoicp_batch run; each config's io.output / io.visualization as a lone -c run
-// of it writes them (the seconds written are the batch's).  The configs must agree on the schedule and round width; trimming is refused.
+// of it writes them (the seconds written are the batch's).  The configs must agree on the schedule and round width; each is trimmed with
+// its own params.trim_fraction.
 static int run_batch(const std::string& list_file) {
     std::ifstream lf(list_file);
     if (!lf) { icp::Logger(icp::LogLevel::Error) << "Unable to read " << list_file; return 1; }
@@ -38,7 +39,6 @@ static int run_batch(const std::string& list_file) {
     if (configs.empty()) { icp::Logger(icp::LogLevel::Error) << "--batch: " << list_file << " lists no config"; return 1; }
     const cli::Config& c0 = configs[0];
     for (const cli::Config& c : configs) {
-        if (c.params.trim_fraction > 0.0f) { icp::Logger(icp::LogLevel::Error) << "--batch: trimmed configs cannot run in a batch"; return 1; }
         if (c.params.gpus > 1) { icp::Logger(icp::LogLevel::Error) << "--batch: a batch runs on one GPU (params.gpus > 1)"; return 1; }
         if (c.params.schedule != c0.params.schedule || c.params.round_width != c0.params.round_width) {
             icp::Logger(icp::LogLevel::Error) << "--batch: every config of a batch must have the same params.schedule and params.round_width";
@@ -48,17 +48,20 @@ static int run_batch(const std::string& list_file) {
     const size_t n = configs.size();
     std::vector<std::vector<icp::vec3>> pct(n), pcs(n);
     std::vector<fgoicp_batch_pair> pairs(n);
+    std::vector<float> trim(n);
     for (size_t i = 0; i < n; ++i) {
         const cli::Config& c = configs[i];
         cli::load_cloud(c.io.target, c.params.target_subsample, pct[i], c.params.seed);
         cli::load_cloud(c.io.source, c.params.source_subsample, pcs[i], c.params.seed < 0 ? -1 : c.params.seed + 1);
         icp::Logger(icp::LogLevel::Info) << "Pair " << i << ": target (" << pct[i].size() << ") " << c.io.target << ", source (" << pcs[i].size() << ") " << c.io.source;
         pairs[i] = fgoicp_batch_pair{&pct[i].data()->x, pct[i].size(), &pcs[i].data()->x, pcs[i].size(), c.params.lut_resolution, c.params.mse_threshold};
+        trim[i] = c.params.trim_fraction;
     }
     const int schedule = c0.params.schedule == "round" ? FGOICP_SCHEDULE_ROUND : FGOICP_SCHEDULE_SERIAL;
     fgoicp_batch_opts o{};
     o.struct_size = sizeof(o);
     o.solver = fgoicp_solver_opts{schedule, c0.params.round_width, 0u, 0, 0.0f};
+    o.trim_fractions = trim.data();
     fgoicp_batch* b = nullptr;
     icp::check_status(fgoicp_batch_create(pairs.data(), (int)n, &o, &b), "fgoicp_batch_create");
     std::vector<float> R9(9 * n), t3(3 * n);

@@ -998,28 +998,36 @@ int ctx_icp_batch(fgoicp_ctx* c, int n, const float* R0s, const float* t0s, size
     return FGOICP_OK;
 }
 
-// EXTENSION: trimmed Go-ICP.  k = 0 (or k >= ns) switches trimming off.
-int ctx_set_inliers(fgoicp_ctx* c, size_t k) {
+// per-point e of one window, per slot: up to 12 GiB (a sixth of what is free): 3000 subcubes of a 1M-point cloud per window — the
+// selection launches one workgroup per row and wants several hundred of them.  A batch's e-row arena has the same budget.
+size_t trim_rows_budget(size_t free_b) { return std::max<size_t>((size_t)3 << 29, std::min<size_t>((size_t)12 << 30, free_b / 6)); }
+
+// device bytes of what trimmed ICP adds to a context of ns points and `lanes` ICP lanes (trim_setup below)
+size_t trim_icp_bytes(size_t ns, size_t lanes) { return lanes * (5 * sizeof(float) * ns + ns + 2 * (size_t)65536 + 17 * sizeof(uint32_t)) + sizeof(uint32_t) * ns; }
+
+// EXTENSION: trimmed Go-ICP.  k = 0 (or k >= ns) switches trimming off.  slot_rows = false (fgoicp_batch): everything trimmed ICP and a
+// batch's fused bounds need, but not the windows' e-rows in the two slots (nor the selection statistics) — the batch keeps one arena.
+static int trim_setup(fgoicp_ctx* c, size_t k, bool slot_rows) {
     HIPCHK(hipSetDevice(c->device));
     if (k >= c->ns) k = 0;
     if (c->slots[0].inflight || c->slots[1].inflight) { set_error("fgoicp_ctx_set_inliers: a bounds submission is in flight"); return FGOICP_ERR_INVALID_ARG; }
     if (k && !c->trim_ready) {
-        // per-point e of one window, per slot: up to 12 GiB (a sixth of what is free): 3000 subcubes of a 1M-point cloud per
-        // window — the selection launches one workgroup per row and wants several hundred of them
-        size_t free_b = 0, total_b = 0;
-        HIPCHK(hipMemGetInfo(&free_b, &total_b));
-        const size_t budget = std::max<size_t>((size_t)3 << 29, std::min<size_t>((size_t)12 << 30, free_b / 6));
         if (const char* e = dev_env("FGOICP_TRIM_SAMPLE")) c->trim_samp_shift = std::max(0, std::min(10, std::atoi(e)));  // tuning knob: 0 = two-pass selection, no sample
         if (const char* e = dev_env("FGOICP_TRIM_MARGIN")) c->trim_margin_sd = (float)std::atof(e);                          // tuning knob: bracket half-width (standard deviations)
         c->erow = (c->ns + 3) & ~(size_t)3;  // rows start 16-byte aligned
         if (c->trim_samp_shift > 0)  // + the row's sample (trim_store); rows and samples then start on 256-byte boundaries
             c->erow = ((c->ns + 63) & ~(size_t)63) + (((((c->ns + ((size_t)1 << c->trim_samp_shift) - 1) >> c->trim_samp_shift)) + 63) & ~(size_t)63);
-        if (!c->d_trim_stat) { HIPCHK(hipMalloc(&c->d_trim_stat, sizeof(unsigned long long) * 4)); HIPCHK(hipMemset(c->d_trim_stat, 0, sizeof(unsigned long long) * 4)); }
-        size_t rows = budget / (sizeof(float) * c->erow);
-        rows = std::max<size_t>(1, std::min<size_t>(rows, (size_t)c->max_subcubes));
-        c->vals_rows = (int)rows;
         // every pointer is guarded on its own: a call that failed half-way (out of memory) can be repeated without leaking
-        for (auto& sl : c->slots) if (!sl.d_evals) HIPCHK(hipMalloc(&sl.d_evals, sizeof(float) * c->erow * rows));
+        if (slot_rows) {
+            size_t free_b = 0, total_b = 0;
+            HIPCHK(hipMemGetInfo(&free_b, &total_b));
+            const size_t budget = trim_rows_budget(free_b);
+            if (!c->d_trim_stat) { HIPCHK(hipMalloc(&c->d_trim_stat, sizeof(unsigned long long) * 4)); HIPCHK(hipMemset(c->d_trim_stat, 0, sizeof(unsigned long long) * 4)); }
+            size_t rows = budget / (sizeof(float) * c->erow);
+            rows = std::max<size_t>(1, std::min<size_t>(rows, (size_t)c->max_subcubes));
+            c->vals_rows = (int)rows;
+            for (auto& sl : c->slots) if (!sl.d_evals) HIPCHK(hipMalloc(&sl.d_evals, sizeof(float) * c->erow * rows));
+        }
         for (auto& L : c->lanes) {
             if (!L.d_d2) HIPCHK(hipMalloc(&L.d_d2, sizeof(float) * c->ns));
             if (!L.d_nn_lb) HIPCHK(hipMalloc(&L.d_nn_lb, sizeof(float) * c->ns));
@@ -1043,7 +1051,7 @@ int ctx_set_inliers(fgoicp_ctx* c, size_t k) {
             HIPCHK(hipMalloc(&c->d_orig_of_slot, sizeof(uint32_t) * c->ns));
             HIPCHK(hipMemcpy(c->d_orig_of_slot, c->perm.data(), sizeof(uint32_t) * c->ns, hipMemcpyHostToDevice));
         }
-        c->trim_ready = true;
+        c->trim_ready = slot_rows;  // (a batch context never gets its slot rows: a later call with them allocates only what is missing)
     }
     c->inliers = k;
     if (k && c->trim_samp_shift > 0) {
@@ -1054,6 +1062,8 @@ int ctx_set_inliers(fgoicp_ctx* c, size_t k) {
     }
     return FGOICP_OK;
 }
+int ctx_set_inliers(fgoicp_ctx* c, size_t k) { return trim_setup(c, k, true); }
+int ctx_set_inliers_batch(fgoicp_ctx* c, size_t k) { return trim_setup(c, k, false); }
 
 }  // namespace fgoicp
 

@@ -158,6 +158,19 @@ int ctx_bounds_submit(fgoicp_ctx* c, int slot, int G, const float* R9, const flo
                       const int* twin = nullptr, const float* cut_above = nullptr);
 int ctx_bounds_collect(fgoicp_ctx* c, int slot, float* lb_out, float* ub_out);
 int ctx_set_inliers(fgoicp_ctx* c, size_t k);
+// Trimmed Go-ICP as fgoicp_solver_create and fgoicp_batch set a context up for trim fraction f: the context flags (curve order) and the
+// inlier count — inlierNum = (int)(Nd * (1 - trimFraction)), as in Go-ICP, at least 1; 0 = untrimmed (f <= 0, or no point trimmed).
+inline unsigned trim_ctx_flags(unsigned flags, float f) { return flags | (f > 0.0f ? (unsigned)FGOICP_FLAG_CURVE_ORDER : 0u); }
+inline size_t trim_inliers(size_t ns, float f) {
+    if (!(f > 0.0f)) return 0;
+    size_t k = (size_t)((double)ns * (1.0 - (double)f));
+    if (k < 1) k = 1;
+    return k < ns ? k : 0;
+}
+// fgoicp_batch: ctx_set_inliers without the slots' e-rows (the batch evaluates trimmed bounds into an arena of its own)
+int ctx_set_inliers_batch(fgoicp_ctx* c, size_t k);
+size_t trim_rows_budget(size_t free_bytes);        // bytes of e-rows per slot (solo) / per batch arena
+size_t trim_icp_bytes(size_t ns, size_t lanes);    // device bytes trimmed ICP adds to a context
 int ctx_sse(fgoicp_ctx* c, const float* R9, const float* t3, float* sse_out, const uint32_t* seed_idx = nullptr);
 int ctx_icp(fgoicp_ctx* c, const float* R0, const float* t0, size_t max_iter, float thr, float* sse_out, float* R_out9, float* t_out3,
             int* iters_out);

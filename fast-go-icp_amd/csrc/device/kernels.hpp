@@ -113,14 +113,30 @@ struct FusedEval {
     int fix_rot;
     int pair;                    // index into the views
     int nchunk;                  // the pair's chunks per evaluation
-    int pad_;
-    unsigned long long partial_base;  // its nchunk partials start here
+    int samp_shift;              // trimmed rows: the pair's sample shift (trim_store; 0 = no sample); 0 otherwise
+    union {
+        unsigned long long partial_base;  // untrimmed rows: its nchunk partials start here
+        unsigned long long row_off;       // trimmed rows: its e-row starts here in the arena (floats; 16-byte aligned)
+    };
+};
+static_assert(sizeof(FusedEval) == 80, "FusedEval: one layout for both kinds of row");
+// one trimmed row of a batch tick for fused_trim_select_kernel: the row's n values of e (its sample behind them), its pair's k, sample
+// shift and margin (fgoicp_ctx::inliers, trim_samp_shift, trim_margin), its translation span and where its {ub, lb} go
+struct FusedTrimRow {
+    const float* row;
+    int n, k, samp_shift, margin;
+    float span;
+    int out;
 };
 bool bounds_lut_wide(const LutGeom& g, int layout);
 // layout: fgoicp_ctx::lut_layout (1, 2, 4) of EVERY pair the items belong to; wide = bounds_lut_wide, quant = g.quantize, alike for all of them
 void launch_fused_bounds(int layout, bool wide, bool quant, const FusedPairView* pairs, const FusedEval* evals, const uint2* items, unsigned nitems, double2* partials,
                          hipStream_t s);
 void launch_fused_finalize(const FusedEval* evals, int nevals, const double2* partials, float* out_lb, float* out_ub, hipStream_t s);
+// trimmed pairs: the items' per-point e (and samples) into their rows of the arena; then one selection workgroup per row
+void launch_fused_trim_bounds(int layout, bool wide, bool quant, const FusedPairView* pairs, const FusedEval* evals, const uint2* items, unsigned nitems, float* arena,
+                              hipStream_t s);
+void launch_fused_trim_select(const FusedTrimRow* rows, int nrows, float* out_ub, float* out_lb, hipStream_t s);
 
 // out_lb[i], out_ub[i] = float(sum over chunks), fixed order → bit-reproducible
 void launch_bounds_finalize(const double2* partials, int nchunk, int total, float* out_lb, float* out_ub, const TickCut& cut, hipStream_t s);

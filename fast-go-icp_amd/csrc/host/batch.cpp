@@ -1,6 +1,7 @@
 // fgoicp_batch (include/fgoicp_amd.h): many registrations on one device.  The scheduler (batch.hpp) runs every live pair's unchanged
 // driver on a host thread of its own; this file is its device backend — one fgoicp_ctx per live pair, the bounds of all pending requests
 // in fused launches (kernels.hip, bounds_fused.hpp), the ICP runs advanced in lock-step so that they share each host turn-around.
+// Trimmed pairs evaluate their rows into one e-row arena for the whole batch and select them there; their ICP runs are not stepped.
 // The launcher (the thread that calls fgoicp_batch_run) is the only thread that touches the device.
 #include <algorithm>
 #include <cmath>
@@ -34,17 +35,24 @@ struct PairHost {
     float scaling_factor = 1.f;
     float bounds6[6] = {0, 0, 0, 0, 0, 0};
     float lut_resolution = 0.f, mse_threshold = 0.f;
+    float trim_fraction = 0.f;
+    size_t inliers = 0;  // trim_inliers(ns, trim_fraction): 0 = untrimmed
 };
 
 // work items per fused launch (one 64-thread block each): a class with more is split, so that blocks x threads stay inside the 32-bit
 // grid size of a dispatch, with the margin the solo path keeps (ctx.hip, launch_fit)
 constexpr size_t kFusedLaunchItems = (size_t)1 << 24;
 
-// device staging of one class of work items (same LUT layout, addressing and quantisation)
+// device staging of one class of work items (same LUT layout, addressing and quantisation; trimmed or not)
 struct ItemClass {
     int layout = 0;
-    bool wide = false, quant = false;
+    bool wide = false, quant = false, trim = false;
     std::vector<uint2> items;
+};
+// the trimmed rows of a tick that share one fill of the arena: their items per class (indexed as the tick's classes), their rows
+struct TrimSubTick {
+    std::vector<std::vector<uint2>> items;
+    size_t first_row = 0, rows = 0, floats = 0;
 };
 
 // Grow-only device buffer
@@ -52,12 +60,12 @@ template <class T>
 struct DevBuf {
     T* p = nullptr;
     size_t cap = 0;
-    int ensure(size_t n) {
+    int ensure(size_t n, bool exact = false) {
         if (n <= cap) return FGOICP_OK;
         if (p) (void)hipFree(p);
         p = nullptr;
         cap = 0;
-        const size_t want = n + n / 2 + 64;
+        const size_t want = exact ? n : n + n / 2 + 64;
         BCHK(hipMalloc(&p, sizeof(T) * want));
         cap = want;
         return FGOICP_OK;
@@ -89,8 +97,15 @@ struct HipBatchBackend {
     bool borrowed = false;  // the test hooks: the contexts are the caller's (not destroyed here)
     std::vector<IcpStepState> icp_state;
     hipStream_t stream = nullptr;
-    uint64_t bounds_launches = 0, icp_launches = 0;
-    size_t last_lut_bytes = 0;
+    uint64_t bounds_launches = 0, icp_launches = 0, selection_launches = 0;
+    size_t last_lut_bytes = 0, last_lanes = 4;
+    int next_pair = 0;            // the pair the scheduler admits next (room_for_more)
+    // trimmed pairs: one grow-only arena of e-rows for the whole run (one fill per sub-tick), the solo formula's budget (trim_rows_budget)
+    size_t arena_budget = 0;      // bytes; 0 = not set yet
+    size_t arena_rows_max = 0;    // test hook: at most this many rows per fill (0: the budget decides)
+    DevBuf<float> d_arena;
+    PinBuf<FusedTrimRow> h_trows;
+    DevBuf<FusedTrimRow> d_trows;
     // tick staging
     PinBuf<FusedPairView> h_views;
     PinBuf<FusedEval> h_evals;
@@ -105,8 +120,8 @@ struct HipBatchBackend {
     ~HipBatchBackend() {
         if (!borrowed)
             for (fgoicp_ctx*& c : ctx) { fgoicp_ctx_destroy(c); c = nullptr; }
-        h_views.release(); h_evals.release(); h_items.release(); h_out.release();
-        d_views.release(); d_evals.release(); d_items.release(); d_partials.release(); d_out.release();
+        h_views.release(); h_evals.release(); h_items.release(); h_out.release(); h_trows.release();
+        d_views.release(); d_evals.release(); d_items.release(); d_partials.release(); d_out.release(); d_arena.release(); d_trows.release();
         if (stream) (void)hipStreamDestroy(stream);
     }
     int init() {
@@ -114,6 +129,13 @@ struct HipBatchBackend {
         BCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
         ctx.assign(pairs->size(), nullptr);
         icp_state.assign(pairs->size(), IcpStepState());
+        for (const PairHost& p : *pairs)
+            if (p.inliers) {  // the arena's budget is set aside before any pair enters (room_for_more)
+                size_t free_b = 0, total_b = 0;
+                BCHK(hipMemGetInfo(&free_b, &total_b));
+                arena_budget = trim_rows_budget(free_b);
+                break;
+            }
         return FGOICP_OK;
     }
     // the test hooks: the caller's contexts as the live pairs (checked by the caller: one device, the packed LUT)
@@ -130,26 +152,40 @@ struct HipBatchBackend {
     int admit(int i) {
         PairHost& p = (*pairs)[(size_t)i];
         fgoicp_ctx* c = nullptr;
-        const int rc = fgoicp_ctx_create(reinterpret_cast<const float*>(p.pct.data()), p.nt, reinterpret_cast<const float*>(p.pcs.data()), p.ns, p.bounds6,
-                                         p.lut_resolution, device, ctx_flags, &c);
+        next_pair = i;
+        int rc = fgoicp_ctx_create(reinterpret_cast<const float*>(p.pct.data()), p.nt, reinterpret_cast<const float*>(p.pcs.data()), p.ns, p.bounds6,
+                                   p.lut_resolution, device, trim_ctx_flags(ctx_flags, p.trim_fraction), &c);
         if (rc == FGOICP_ERR_OOM) return kBatchNoRoom;  // the scheduler reports OOM itself when no other pair is live
-        if (rc) return rc;
+        if (rc) { next_pair = i + 1; return rc; }
+        if (p.inliers && (rc = ctx_set_inliers_batch(c, p.inliers))) {  // trimmed ICP's buffers; no slot e-rows (the arena)
+            fgoicp_ctx_destroy(c);
+            if (rc == FGOICP_ERR_OOM) return kBatchNoRoom;
+            next_pair = i + 1;
+            return rc;
+        }
+        next_pair = i + 1;
         if (!c->d_lut_zp) {  // the fused kernel reads the packed LUT copy
             fgoicp_ctx_destroy(c);
             set_error("fgoicp_batch_run: pair " + std::to_string(i) + " has no packed LUT");
             return FGOICP_ERR_INVALID_ARG;
         }
         ctx[(size_t)i] = c;
+        last_lanes = c->lanes.size();
         fgoicp_ctx_info info{};
         info.struct_size = sizeof(info);
         if (fgoicp_ctx_get_info(c, &info) == FGOICP_OK) last_lut_bytes = info.lut_bytes;
         return FGOICP_OK;
     }
-    // max_live = 0: another pair enters while the device has room for one more LUT the size of the last one created (and a quarter on top)
+    // max_live = 0: another pair enters while the device has room for one more LUT the size of the last one created (and a quarter on top),
+    // the trimmed ICP buffers of the next pair if it is trimmed, and what the arena may still grow by
     bool room_for_more(int /*live*/) {
         size_t free_b = 0, total_b = 0;
         if (hipSetDevice(device) != hipSuccess || hipMemGetInfo(&free_b, &total_b) != hipSuccess) return false;
-        return free_b > last_lut_bytes + last_lut_bytes / 4 + ((size_t)256 << 20);
+        size_t need = last_lut_bytes + last_lut_bytes / 4 + ((size_t)256 << 20);
+        if (next_pair < (int)pairs->size() && (*pairs)[(size_t)next_pair].inliers) need += trim_icp_bytes((*pairs)[(size_t)next_pair].ns, last_lanes);
+        const size_t arena_b = sizeof(float) * d_arena.cap;
+        if (arena_budget > arena_b) need += arena_budget - arena_b;
+        return free_b > need;
     }
     void release(int i) {
         (void)hipSetDevice(device);
@@ -157,21 +193,24 @@ struct HipBatchBackend {
         ctx[(size_t)i] = nullptr;
     }
 
-    // One tick: every row of every request, one launch per item class (more for a class above kFusedLaunchItems), one finalize.
+    // One tick: every row of every request.  Untrimmed rows: one launch per item class (more for a class above kFusedLaunchItems), one
+    // finalize.  Trimmed rows: laid out in the arena in request order, in sub-ticks of what one fill holds; per sub-tick one launch per
+    // class (split alike) writes the rows' e, then one selection launch reduces them.
     int bounds(std::vector<BatchBoundsReq*>& reqs) {
         BCHK(hipSetDevice(device));
         // views: one per pair that has a request
         std::vector<int> view_of(ctx.size(), -1);
         std::vector<int> view_pair;
-        size_t nevals = 0;
+        size_t nu = 0, nt = 0;  // untrimmed / trimmed rows
         for (BatchBoundsReq* r : reqs) {
             if (view_of[(size_t)r->pair] < 0) { view_of[(size_t)r->pair] = (int)view_pair.size(); view_pair.push_back(r->pair); }
-            nevals += (size_t)r->offsets[(size_t)r->G];
+            (ctx[(size_t)r->pair]->inliers ? nt : nu) += (size_t)r->offsets[(size_t)r->G];
         }
+        const size_t nevals = nu + nt;
         if (nevals == 0) return FGOICP_OK;
         int rc;
         if ((rc = h_views.ensure(view_pair.size())) || (rc = h_evals.ensure(nevals)) || (rc = h_out.ensure(2 * nevals)) || (rc = d_views.ensure(view_pair.size())) ||
-            (rc = d_evals.ensure(nevals)) || (rc = d_out.ensure(2 * nevals)))
+            (rc = d_evals.ensure(nevals)) || (rc = d_out.ensure(2 * nevals)) || (nt && ((rc = h_trows.ensure(nt)) || (rc = d_trows.ensure(nt)))))
             return rc;
         std::vector<ItemClass> classes;
         std::vector<int> class_of_view(view_pair.size());
@@ -183,22 +222,37 @@ struct HipBatchBackend {
             pv.g = c->geom;
             pv.ns = (int)c->ns;
             pv.chunk_pts = c->chunk_pts;
-            const bool wide = bounds_lut_wide(c->geom, c->lut_layout), quant = c->geom.quantize != 0;
+            const bool wide = bounds_lut_wide(c->geom, c->lut_layout), quant = c->geom.quantize != 0, trim = c->inliers != 0;
             int k = 0;
-            while (k < (int)classes.size() && !(classes[(size_t)k].layout == c->lut_layout && classes[(size_t)k].wide == wide && classes[(size_t)k].quant == quant)) ++k;
-            if (k == (int)classes.size()) { classes.emplace_back(); classes.back().layout = c->lut_layout; classes.back().wide = wide; classes.back().quant = quant; }
+            while (k < (int)classes.size() && !(classes[(size_t)k].layout == c->lut_layout && classes[(size_t)k].wide == wide && classes[(size_t)k].quant == quant &&
+                                                 classes[(size_t)k].trim == trim))
+                ++k;
+            if (k == (int)classes.size()) {
+                classes.emplace_back();
+                classes.back().layout = c->lut_layout; classes.back().wide = wide; classes.back().quant = quant; classes.back().trim = trim;
+            }
             class_of_view[v] = k;
         }
-        // evaluations in request order; their chunks as work items of their pair's class
-        size_t e = 0, partials = 0;
+        if (nt && !arena_budget) {  // (the test hooks: set at the first trimmed tick)
+            size_t free_b = 0, total_b = 0;
+            BCHK(hipMemGetInfo(&free_b, &total_b));
+            arena_budget = trim_rows_budget(free_b);
+        }
+        const size_t arena_floats = arena_budget / sizeof(float);
+        // evaluations in request order, the untrimmed ones [0, nu), the trimmed ones [nu, nevals); their chunks as work items of their
+        // pair's class, the trimmed ones per sub-tick
+        std::vector<TrimSubTick> subs;
+        size_t eu = 0, et = nu, partials = 0;
         for (BatchBoundsReq* r : reqs) {
             const int v = view_of[(size_t)r->pair];
             const fgoicp_ctx* c = ctx[(size_t)r->pair];
-            ItemClass& cl = classes[(size_t)class_of_view[(size_t)v]];
+            const bool trim = c->inliers != 0;
+            const int cls = class_of_view[(size_t)v];
             for (int g = 0; g < r->G; ++g) {
                 const float half_angle = r->spans[(size_t)g] * kSqrt3 * kPi / 2.0f;  // registration.cu:42, as the context's window packing computes it
                 const float sin_half = std::sin(half_angle);
-                for (int i = r->offsets[(size_t)g]; i < r->offsets[(size_t)g + 1]; ++i, ++e) {
+                for (int i = r->offsets[(size_t)g]; i < r->offsets[(size_t)g + 1]; ++i) {
+                    const size_t e = trim ? et++ : eu++;
                     FusedEval& fe = h_evals.p[e];
                     std::memcpy(fe.R, &r->R9[9 * (size_t)g], sizeof(fe.R));
                     fe.sin_half = sin_half;
@@ -206,21 +260,54 @@ struct HipBatchBackend {
                     fe.fix_rot = r->fix[(size_t)g] ? 1 : 0;
                     fe.pair = v;
                     fe.nchunk = c->nchunk1;
-                    fe.pad_ = 0;
-                    fe.partial_base = partials;
-                    for (int ch = 0; ch < c->nchunk1; ++ch) cl.items.push_back(make_uint2((unsigned)e, (unsigned)ch));
-                    partials += (size_t)c->nchunk1;
+                    if (!trim) {
+                        fe.samp_shift = 0;
+                        fe.partial_base = partials;
+                        std::vector<uint2>& items = classes[(size_t)cls].items;
+                        for (int ch = 0; ch < c->nchunk1; ++ch) items.push_back(make_uint2((unsigned)e, (unsigned)ch));
+                        partials += (size_t)c->nchunk1;
+                        continue;
+                    }
+                    // a new fill of the arena when this row would not fit (a row larger than the whole budget gets a fill of its own)
+                    if (subs.empty() || (subs.back().rows > 0 && ((arena_rows_max && subs.back().rows >= arena_rows_max) || subs.back().floats + c->erow > arena_floats))) {
+                        subs.emplace_back();
+                        subs.back().items.resize(classes.size());
+                        subs.back().first_row = e - nu;
+                    }
+                    TrimSubTick& st = subs.back();
+                    fe.samp_shift = c->trim_samp_shift;
+                    fe.row_off = st.floats;
+                    FusedTrimRow& tr = h_trows.p[e - nu];
+                    tr.row = nullptr;  // (the arena's address is known once it has grown: below)
+                    tr.n = (int)c->ns;
+                    tr.k = (int)c->inliers;
+                    tr.samp_shift = c->trim_samp_shift;
+                    tr.margin = c->trim_margin;
+                    tr.span = fe.span;
+                    tr.out = (int)e;
+                    for (int ch = 0; ch < c->nchunk1; ++ch) st.items[(size_t)cls].push_back(make_uint2((unsigned)e, (unsigned)ch));
+                    st.floats += c->erow;
+                    st.rows++;
                 }
             }
         }
-        size_t nitems = 0;
+        size_t fill = 0, nitems = 0;
+        for (const TrimSubTick& st : subs) {
+            fill = std::max(fill, st.floats);
+            for (const std::vector<uint2>& it : st.items) nitems += it.size();
+        }
         for (const ItemClass& cl : classes) nitems += cl.items.size();
-        if ((rc = h_items.ensure(nitems)) || (rc = d_items.ensure(nitems)) || (rc = d_partials.ensure(partials))) return rc;
+        if ((rc = h_items.ensure(nitems)) || (rc = d_items.ensure(nitems)) || (rc = d_partials.ensure(partials)) || (fill && (rc = d_arena.ensure(fill, true)))) return rc;
+        for (const TrimSubTick& st : subs)
+            for (size_t q = st.first_row; q < st.first_row + st.rows; ++q) h_trows.p[q].row = d_arena.p + h_evals.p[nu + q].row_off;
         size_t pos = 0;
         for (const ItemClass& cl : classes) { std::memcpy(h_items.p + pos, cl.items.data(), sizeof(uint2) * cl.items.size()); pos += cl.items.size(); }
+        for (const TrimSubTick& st : subs)
+            for (const std::vector<uint2>& it : st.items) { std::memcpy(h_items.p + pos, it.data(), sizeof(uint2) * it.size()); pos += it.size(); }
         BCHK(hipMemcpyAsync(d_views.p, h_views.p, sizeof(FusedPairView) * view_pair.size(), hipMemcpyHostToDevice, stream));
         BCHK(hipMemcpyAsync(d_evals.p, h_evals.p, sizeof(FusedEval) * nevals, hipMemcpyHostToDevice, stream));
         BCHK(hipMemcpyAsync(d_items.p, h_items.p, sizeof(uint2) * nitems, hipMemcpyHostToDevice, stream));
+        if (nt) BCHK(hipMemcpyAsync(d_trows.p, h_trows.p, sizeof(FusedTrimRow) * nt, hipMemcpyHostToDevice, stream));
         pos = 0;
         for (const ItemClass& cl : classes) {  // one launch per class, split where it would not fit the 32-bit grid
             for (size_t first = 0; first < cl.items.size(); first += kFusedLaunchItems) {
@@ -230,13 +317,29 @@ struct HipBatchBackend {
             }
             pos += cl.items.size();
         }
-        launch_fused_finalize(d_evals.p, (int)nevals, d_partials.p, d_out.p, d_out.p + nevals, stream);
+        if (nu) launch_fused_finalize(d_evals.p, (int)nu, d_partials.p, d_out.p, d_out.p + nevals, stream);
+        for (const TrimSubTick& st : subs) {  // one fill of the arena after the other, on the one stream
+            for (size_t k = 0; k < classes.size(); ++k) {
+                const ItemClass& cl = classes[k];
+                const std::vector<uint2>& it = st.items[k];
+                for (size_t first = 0; first < it.size(); first += kFusedLaunchItems) {
+                    const size_t n = std::min(kFusedLaunchItems, it.size() - first);
+                    launch_fused_trim_bounds(cl.layout, cl.wide, cl.quant, d_views.p, d_evals.p, d_items.p + pos + first, (unsigned)n, d_arena.p, stream);
+                    ++bounds_launches;
+                }
+                pos += it.size();
+            }
+            launch_fused_trim_select(d_trows.p + st.first_row, (int)st.rows, d_out.p + nevals, d_out.p, stream);
+            ++selection_launches;
+        }
         BCHK(hipGetLastError());
         BCHK(hipMemcpyAsync(h_out.p, d_out.p, sizeof(float) * 2 * nevals, hipMemcpyDeviceToHost, stream));
         BCHK(hipStreamSynchronize(stream));
-        e = 0;
+        eu = 0;
+        et = nu;
         for (BatchBoundsReq* r : reqs) {
             const size_t n = (size_t)r->offsets[(size_t)r->G];
+            size_t& e = ctx[(size_t)r->pair]->inliers ? et : eu;
             std::memcpy(r->lb.data(), h_out.p + e, sizeof(float) * n);
             std::memcpy(r->ub.data(), h_out.p + nevals + e, sizeof(float) * n);
             e += n;
@@ -298,8 +401,15 @@ static int batch_create_impl(const fgoicp_batch_pair* pairs, int n, const fgoicp
     auto b = std::make_unique<fgoicp_batch>();
     std::memcpy(&b->opts, opts, sz < sizeof(b->opts) ? sz : sizeof(b->opts));  // members beyond the caller's struct stay 0
     b->opts.struct_size = sizeof(b->opts);
-    if (b->opts.solver.trim_fraction != 0.0f) { set_error("fgoicp_batch_create: trimmed pairs are not supported in a batch"); return FGOICP_ERR_INVALID_ARG; }
+    if (b->opts.solver.trim_fraction != 0.0f) {
+        set_error("fgoicp_batch_create: solver.trim_fraction must be 0 (trimming is per pair: fgoicp_batch_opts.trim_fractions)");
+        return FGOICP_ERR_INVALID_ARG;
+    }
     if (b->opts.max_live < 0) { set_error("fgoicp_batch_create: max_live < 0"); return FGOICP_ERR_INVALID_ARG; }
+    const float* trim = b->opts.trim_fractions;
+    b->opts.trim_fractions = nullptr;  // read here only
+    for (int i = 0; trim && i < n; ++i)
+        if (!(trim[i] >= 0.0f && trim[i] < 1.0f)) { set_error("fgoicp_batch_create: trim_fractions[" + std::to_string(i) + "] is not in [0, 1)"); return FGOICP_ERR_INVALID_ARG; }
     b->pairs.resize((size_t)n);
     for (int i = 0; i < n; ++i) {
         const fgoicp_batch_pair& q = pairs[i];
@@ -321,6 +431,8 @@ static int batch_create_impl(const fgoicp_batch_pair* pairs, int n, const fgoicp
         point_cloud_ranges(p.pct, p.bounds6);
         p.lut_resolution = q.lut_resolution;
         p.mse_threshold = q.mse_threshold;
+        p.trim_fraction = trim ? trim[i] : 0.0f;
+        p.inliers = trim_inliers(p.ns, p.trim_fraction);  // as fgoicp_solver_create
     }
     b->results.assign((size_t)n, BatchPairResult());
     b->status.assign((size_t)n, FGOICP_OK);
@@ -344,7 +456,11 @@ static int batch_run_impl(fgoicp_batch* b, float* R_out9n, float* t_out3n, int* 
     int rc = be.init();
     if (rc) return rc;
     std::vector<BatchPairSpec> specs((size_t)n);
-    for (int i = 0; i < n; ++i) { specs[(size_t)i].n_thr = b->pairs[(size_t)i].ns; specs[(size_t)i].mse_threshold = b->pairs[(size_t)i].mse_threshold; }
+    for (int i = 0; i < n; ++i) {  // sse_threshold over the inliers when trimming, as fgoicp_solver_create
+        const PairHost& p = b->pairs[(size_t)i];
+        specs[(size_t)i].n_thr = p.inliers ? p.inliers : p.ns;
+        specs[(size_t)i].mse_threshold = p.mse_threshold;
+    }
     {
         BatchScheduler<HipBatchBackend> sched(be, specs, b->opts.solver.schedule, b->opts.solver.round_width, b->opts.max_live);
         rc = sched.run();
@@ -407,9 +523,9 @@ static int borrowed_ctx_check(fgoicp_ctx* const* ctxs, int nctx, const char* whe
     return FGOICP_OK;
 }
 
-static int batch_test_bounds_impl(fgoicp_ctx* const* ctxs, int nctx, int nreq, const int* req_ctx, const int* req_G, const float* R9, const float* rot_span,
-                                  const int* fix_rot, const int* offsets, const float* tn4, float* lb_out, float* ub_out, uint64_t* launches_out) {
-    const char* where = "fgoicp_batch_test_bounds";
+static int batch_test_bounds_impl(const char* where, bool allow_trim, fgoicp_ctx* const* ctxs, int nctx, int nreq, const int* req_ctx, const int* req_G,
+                                  const float* R9, const float* rot_span, const int* fix_rot, const int* offsets, const float* tn4, float* lb_out, float* ub_out,
+                                  uint64_t* launches_out, size_t arena_rows, uint64_t* selection_launches_out) {
     if (!ctxs || nctx <= 0 || nreq < 0 || (nreq > 0 && (!req_ctx || !req_G || !offsets))) { set_error(std::string(where) + ": invalid argument"); return FGOICP_ERR_INVALID_ARG; }
     int rc = borrowed_ctx_check(ctxs, nctx, where);
     if (rc) return rc;
@@ -418,7 +534,7 @@ static int batch_test_bounds_impl(fgoicp_ctx* const* ctxs, int nctx, int nreq, c
         const int k = req_ctx[q], G = req_G[q];
         if (k < 0 || k >= nctx || G < 0) { set_error(std::string(where) + ": request " + std::to_string(q) + ": context index or group count out of range"); return FGOICP_ERR_INVALID_ARG; }
         const fgoicp_ctx* c = ctxs[k];
-        if (c->inliers) { set_error(std::string(where) + ": context " + std::to_string(k) + " is trimmed (a batch has no trimmed pairs)"); return FGOICP_ERR_INVALID_ARG; }
+        if (c->inliers && !allow_trim) { set_error(std::string(where) + ": context " + std::to_string(k) + " is trimmed (fgoicp_batch_test_trim_bounds takes trimmed contexts)"); return FGOICP_ERR_INVALID_ARG; }
         if (!c->d_lut_zp) { set_error(std::string(where) + ": context " + std::to_string(k) + " has no packed LUT"); return FGOICP_ERR_INVALID_ARG; }
         const int* o = offsets + offs;
         for (int g = 0; g < G; ++g)
@@ -450,6 +566,7 @@ static int batch_test_bounds_impl(fgoicp_ctx* const* ctxs, int nctx, int nreq, c
         offs += (size_t)G + 1;
     }
     HipBatchBackend be;
+    be.arena_rows_max = arena_rows;
     if ((rc = be.init_borrowed(ctxs, nctx))) return rc;
     if (!tick.empty() && (rc = be.bounds(tick))) return rc;
     rows = 0;
@@ -459,12 +576,22 @@ static int batch_test_bounds_impl(fgoicp_ctx* const* ctxs, int nctx, int nreq, c
         rows += r.lb.size();
     }
     if (launches_out) *launches_out = be.bounds_launches;
+    if (selection_launches_out) *selection_launches_out = be.selection_launches;
     return FGOICP_OK;
 }
 int fgoicp_batch_test_bounds(fgoicp_ctx* const* ctxs, int nctx, int nreq, const int* req_ctx, const int* req_G, const float* R9, const float* rot_span,
                              const int* fix_rot, const int* offsets, const float* tn4, float* lb_out, float* ub_out, uint64_t* launches_out) {
     return fgoicp::abi_guard("fgoicp_batch_test_bounds", [&] {
-        return batch_test_bounds_impl(ctxs, nctx, nreq, req_ctx, req_G, R9, rot_span, fix_rot, offsets, tn4, lb_out, ub_out, launches_out);
+        return batch_test_bounds_impl("fgoicp_batch_test_bounds", false, ctxs, nctx, nreq, req_ctx, req_G, R9, rot_span, fix_rot, offsets, tn4, lb_out, ub_out,
+                                      launches_out, 0, nullptr);
+    });
+}
+int fgoicp_batch_test_trim_bounds(fgoicp_ctx* const* ctxs, int nctx, int nreq, const int* req_ctx, const int* req_G, const float* R9, const float* rot_span,
+                                  const int* fix_rot, const int* offsets, const float* tn4, float* lb_out, float* ub_out, uint64_t* launches_out,
+                                  size_t arena_rows, uint64_t* selection_launches_out) {
+    return fgoicp::abi_guard("fgoicp_batch_test_trim_bounds", [&] {
+        return batch_test_bounds_impl("fgoicp_batch_test_trim_bounds", true, ctxs, nctx, nreq, req_ctx, req_G, R9, rot_span, fix_rot, offsets, tn4, lb_out,
+                                      ub_out, launches_out, arena_rows, selection_launches_out);
     });
 }
 

@@ -97,18 +97,14 @@ static int solver_create_impl(const float* tgt_xyz, size_t nt, const float* src_
     s->scaling_factor = scale_point_clouds(s->pct, s->pcs);
     point_cloud_ranges(s->pct, s->bounds6);
     int rc = fgoicp_ctx_create(reinterpret_cast<const float*>(s->pct.data()), nt, reinterpret_cast<const float*>(s->pcs.data()), ns,
-                               s->bounds6, lut_resolution, o.device, o.ctx_flags | (o.trim_fraction > 0.0f ? (unsigned)FGOICP_FLAG_CURVE_ORDER : 0u), &s->ctx);
+                               s->bounds6, lut_resolution, o.device, trim_ctx_flags(o.ctx_flags, o.trim_fraction), &s->ctx);
     if (rc) return rc;
     s->ops.ctx = s->ctx;
     size_t n_thr = ns;  // sse_threshold = n * mse_threshold (fgoicp.hpp:23); over the inliers when trimming
-    if (o.trim_fraction > 0.0f) {  // inlierNum = (int)(Nd * (1 - trimFraction)), as in Go-ICP
-        size_t k = (size_t)((double)ns * (1.0 - (double)o.trim_fraction));
-        if (k < 1) k = 1;
-        if (k < ns) {
-            rc = ctx_set_inliers(s->ctx, k);
-            if (rc) return rc;
-            n_thr = k;
-        }
+    if (const size_t k = trim_inliers(ns, o.trim_fraction)) {
+        rc = ctx_set_inliers(s->ctx, k);
+        if (rc) return rc;
+        n_thr = k;
     }
     s->driver.reset(new GoIcpDriver<HipOps>(s->ops, n_thr, mse_threshold, o.schedule, o.round_width));
     *out = s.release();

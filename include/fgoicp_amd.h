@@ -400,7 +400,10 @@ int fgoicp_multi_replay_rank(fgoicp_multi* m, int rank, double* seconds_out);
  * rot_cubes, inner_bnb, icp_runs, icp_iters, rounds, initial_icp_sse, bit for bit, under both schedules — whatever the other pairs,
  * their order or the grouping of requests into launches.  bounds_calls and the timings are not part of that.  Every live pair runs
  * its own search; the bounds requests of all of them are evaluated in fused launches (one per LUT class present in a tick; a class of more than 2^24 work items is split) and their
- * ICP runs are advanced in lock-step, so the host turn-arounds are paid once for all live pairs.
+ * ICP runs are advanced in lock-step, so the host turn-arounds are paid once for all live pairs.  Trimming is per
+ * pair (fgoicp_batch_opts.trim_fractions): a trimmed pair returns what fgoicp_solver_run returns for it alone with that trim_fraction.
+ * Its bounds rows go through the batch's e-row arena (fused trimmed launches per LUT class, then one selection launch per arena fill)
+ * and its ICP runs are not stepped: each runs its whole loop while the other pairs wait.
  * ------------------------------------------------------------------------------------------ */
 typedef struct fgoicp_batch fgoicp_batch;
 typedef struct fgoicp_batch_pair {
@@ -409,11 +412,14 @@ typedef struct fgoicp_batch_pair {
 } fgoicp_batch_pair;
 typedef struct fgoicp_batch_opts {
     size_t struct_size;          /* sizeof(fgoicp_batch_opts) as the caller was compiled (ABI 2): members beyond it are taken as 0 */
-    fgoicp_solver_opts solver;   /* schedule, round_width, ctx_flags, device; trim_fraction must be 0 */
+    fgoicp_solver_opts solver;   /* schedule, round_width, ctx_flags, device; trim_fraction must be 0 (trimming is per pair: trim_fractions) */
     int max_live;                /* pairs whose device state (context: LUT, tree, source order) exists at once; 0 = as many as device memory allows, at most 16 */
+    const float* trim_fractions; /* n entries, pair i trimmed as fgoicp_solver_create trims with solver.trim_fraction = trim_fractions[i] (0 = untrimmed);
+                                    NULL, or a struct_size that ends before this member: no pair is trimmed.  Read by fgoicp_batch_create only */
 } fgoicp_batch_opts;
-/* Copies the clouds and pre-processes every pair on the host (centre, scale, bounds, as fgoicp_solver_create); creates no device
- * state.  Refuses n <= 0, a null or empty cloud, trim_fraction != 0 and a struct_size shorter than the solver options. */
+/* Copies the clouds and pre-processes every pair on the host (centre, scale, bounds, inlier count, as fgoicp_solver_create); creates no
+ * device state.  Refuses n <= 0, a null or empty cloud, solver.trim_fraction != 0, a trim_fractions entry that is NaN, negative or >= 1,
+ * and a struct_size shorter than the solver options. */
 int fgoicp_batch_create(const fgoicp_batch_pair* pairs, int n, const fgoicp_batch_opts* opts, fgoicp_batch** out);
 /* Runs every pair: pairs enter a window of at most max_live live pairs in index order; a pair's context is created when it enters
  * and destroyed when it finishes.  Returns FGOICP_OK when the batch ran; status_n[i] is pair i's own status (a pair that cannot be
@@ -422,8 +428,9 @@ int fgoicp_batch_create(const fgoicp_batch_pair* pairs, int n, const fgoicp_batc
 int fgoicp_batch_run(fgoicp_batch* b, float* R_out9n, float* t_out3n, int* status_n);
 int fgoicp_batch_best_error(const fgoicp_batch* b, int i, float* sse_out);
 int fgoicp_batch_stats(const fgoicp_batch* b, int i, fgoicp_run_stats* out);
-/* Launches of the last run: fused bounds launches (one per LUT class per tick, more for a class of more than 2^24 work items; the finalize not counted) and lock-step ICP
- * iterations (one host turn-around each, shared by every active ICP run). */
+/* Launches of the last run: fused bounds launches (one per LUT class per tick, more for a class of more than 2^24 work items, and per
+ * arena fill for trimmed pairs; neither the finalize nor the trimmed selection counted) and lock-step ICP iterations (one host
+ * turn-around each, shared by every active ICP run). */
 int fgoicp_batch_launches(const fgoicp_batch* b, uint64_t* bounds_launches, uint64_t* icp_launches);
 void fgoicp_batch_destroy(fgoicp_batch* b);
 /* TEST HOOK, not part of the drop-in surface: one tick of the batch's bounds path over contexts the caller made (fgoicp_ctx_create;
@@ -435,6 +442,14 @@ void fgoicp_batch_destroy(fgoicp_batch* b);
  * LUT and contexts on different devices. */
 int fgoicp_batch_test_bounds(fgoicp_ctx* const* ctxs, int nctx, int nreq, const int* req_ctx, const int* req_G, const float* R9, const float* rot_span,
                              const int* fix_rot, const int* offsets, const float* tn4, float* lb_out, float* ub_out, uint64_t* launches_out);
+/* TEST HOOK, not part of the drop-in surface: fgoicp_batch_test_bounds for trimmed contexts (fgoicp_ctx_set_inliers) and untrimmed ones
+ * mixed in one tick.  A trimmed row is evaluated into the batch's e-row arena and selected there; the trimmed rows of the tick run in
+ * sub-ticks of at most arena_rows rows (0 = as many as the batch's own arena budget holds), each one fused trimmed bounds launch per LUT
+ * class and one selection launch.  launches_out (optional) = fused bounds launches, selection_launches_out (optional) = selection
+ * launches.  Refuses what fgoicp_batch_test_bounds refuses, trimmed contexts excepted, before any device work. */
+int fgoicp_batch_test_trim_bounds(fgoicp_ctx* const* ctxs, int nctx, int nreq, const int* req_ctx, const int* req_G, const float* R9, const float* rot_span,
+                                  const int* fix_rot, const int* offsets, const float* tn4, float* lb_out, float* ub_out, uint64_t* launches_out,
+                                  size_t arena_rows, uint64_t* selection_launches_out);
 /* TEST HOOK, not part of the drop-in surface: n ICP runs stepped as a batch steps them, run i on ctxs[i] (borrowed; each context once,
  * all on one device).  Pass p starts the runs whose start_pass is p, then advances every active run by one iteration; contexts that
  * cannot be stepped (more than 262144 source points, brute force) run their whole loop when they start.  Outputs as fgoicp_icp, one

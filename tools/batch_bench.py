@@ -2,6 +2,7 @@
 
     python tools/batch_bench.py --workload a      # 64 pairs of ~1k source / 2k target points, lut_resolution 0.01, mse_threshold 1e-3
     python tools/batch_bench.py --workload b      # 16 pairs of the size of the reference's test/bunny.toml (~3k / 18k points)
+    python tools/batch_bench.py --trim 0.2        # every pair trimmed (trim_fraction 0.2; a tenth of each source replaced by outliers)
 
 Prints one JSON line: wall time of the batch and of the loop (the loop split into context creation = LUT builds, and runs), the
 ratio, whether every pair of the batch is bit-equal to its solo run (R, t, best error, counters), and the fused bounds launches of
@@ -21,11 +22,11 @@ CONTRACT = ("trans_cubes", "rot_cubes", "inner_bnb", "icp_runs", "icp_iters", "r
 WORKLOADS = {"a": dict(n=64, ns=1000, nt=2000, lut=0.01, mse=1e-3), "b": dict(n=16, ns=3000, nt=18000, lut=0.005, mse=1e-3)}
 
 
-def make_pairs(w, seed):
+def make_pairs(w, seed, trim=0.0):
     rng = np.random.default_rng(seed)
     pairs = []
     for i in range(w["n"]):
-        tgt, src, _, _ = fg.synth.make_pair(w["nt"], w["ns"], (1.0, 0.8, 0.6), seed=seed * 1000 + i, angle_deg=float(rng.uniform(10, 90)))
+        tgt, src, _, _ = fg.synth.make_pair(w["nt"], w["ns"], (1.0, 0.8, 0.6), seed=seed * 1000 + i, angle_deg=float(rng.uniform(10, 90)), outlier_frac=trim / 2)
         pairs.append((tgt, src, w["lut"], w["mse"]))
     return pairs
 
@@ -36,23 +37,25 @@ def main():
     ap.add_argument("--schedule", choices=["serial", "round"], default="serial")
     ap.add_argument("--max-live", type=int, default=0)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--trim", type=float, default=0.0, help="trim_fraction of every pair (0: untrimmed)")
     a = ap.parse_args()
     w = WORKLOADS[a.workload]
     sched = fg.SCHEDULE_ROUND if a.schedule == "round" else fg.SCHEDULE_SERIAL
     rw = 0 if sched == fg.SCHEDULE_ROUND else 1
-    pairs = make_pairs(w, a.seed)
+    pairs = make_pairs(w, a.seed, a.trim)
+    kw = dict(schedule=sched, round_width=rw, trim_fraction=a.trim)
     import torch
     torch.cuda.init()
 
     # warm-up: one solo run (module load, first allocations)
-    s = fg.FastGoICP(*pairs[0], schedule=sched, round_width=rw)
+    s = fg.FastGoICP(*pairs[0], **kw)
     s.run()
     s.close()
 
     solo, t_create, t_run = [], 0.0, 0.0
     for p in pairs:
         t0 = time.perf_counter()
-        s = fg.FastGoICP(*p, schedule=sched, round_width=rw)
+        s = fg.FastGoICP(*p, **kw)
         t1 = time.perf_counter()
         R, t = s.run()
         t2 = time.perf_counter()
@@ -61,7 +64,7 @@ def main():
         solo.append((R, t, s.get_best_error(), s.stats()))
         s.close()
 
-    b = fg.FastGoICPBatch(pairs, schedule=sched, round_width=rw, max_live=a.max_live)
+    b = fg.FastGoICPBatch(pairs, max_live=a.max_live, **kw)
     t0 = time.perf_counter()
     out = b.run()
     t_batch = time.perf_counter() - t0
@@ -76,14 +79,14 @@ def main():
 
     solo_launches = 0
     for p in pairs:
-        s = fg.FastGoICP(*p, schedule=sched, round_width=rw, flags=fg.FLAG_PROFILE)
+        s = fg.FastGoICP(*p, **kw, flags=fg.FLAG_PROFILE)
         s.run()
         solo_launches += s.registration.profile()["launches"]
         s.close()
 
     loop = t_create + t_run
     print(json.dumps({
-        "workload": a.workload, "pairs": w["n"], "ns": w["ns"], "nt": w["nt"], "lut_resolution": w["lut"], "mse_threshold": w["mse"], "schedule": a.schedule,
+        "workload": a.workload, "pairs": w["n"], "ns": w["ns"], "nt": w["nt"], "lut_resolution": w["lut"], "mse_threshold": w["mse"], "schedule": a.schedule, "trim_fraction": a.trim,
         "batch_s": round(t_batch, 4), "loop_s": round(loop, 4), "loop_lut_build_s": round(t_create, 4), "loop_run_s": round(t_run, 4),
         "speedup_vs_loop": round(loop / t_batch, 3), "speedup_vs_loop_runs_only": round(t_run / t_batch, 3),
         "bit_equal": equal, "all_bit_equal": all(equal),
