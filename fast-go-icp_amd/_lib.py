@@ -7,6 +7,8 @@ from . import build as _build
 
 c_float_p = C.POINTER(C.c_float)
 c_int_p = C.POINTER(C.c_int)
+c_uint32_p = C.POINTER(C.c_uint32)
+c_uint8_p = C.POINTER(C.c_uint8)
 
 
 class CtxInfo(C.Structure):
@@ -64,7 +66,17 @@ class BatchPair(C.Structure):
 
 
 class BatchOpts(C.Structure):
-    _fields_ = [("struct_size", C.c_size_t), ("solver", SolverOpts), ("max_live", C.c_int), ("trim_fractions", c_float_p)]  # n entries or NULL
+    _fields_ = [("struct_size", C.c_size_t), ("solver", SolverOpts), ("max_live", C.c_int), ("trim_fractions", c_float_p),  # n entries or NULL
+                ("alignment", C.c_int)]  # != 0: the run keeps every pair's alignment report (fgoicp_batch_alignment)
+
+
+class AlignmentSummary(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("points", C.c_uint64), ("inliers", C.c_uint64), ("targets_hit", C.c_uint64), ("sse", C.c_float),
+                ("max_inlier_dist2", C.c_float), ("scaling_factor", C.c_float)]
+
+    def __init__(self):
+        super().__init__()
+        self.struct_size = C.sizeof(AlignmentSummary)  # the library writes no byte beyond it
 
 
 SCHEDULE_SERIAL = 0
@@ -97,6 +109,9 @@ _SIGS = {
     "fgoicp_solver_set_early_exit": (C.c_int, [C.c_void_p, C.c_int]),
     "fgoicp_bounds_collect": (C.c_int, [C.c_void_p, C.c_int, c_float_p, c_float_p]),
     "fgoicp_sse": (C.c_int, [C.c_void_p, c_float_p, c_float_p, c_float_p]),
+    "fgoicp_alignment": (C.c_int, [C.c_void_p, c_float_p, c_float_p, c_uint32_p, c_float_p, c_uint8_p, c_uint8_p, C.POINTER(AlignmentSummary)]),
+    "fgoicp_solver_alignment": (C.c_int, [C.c_void_p, c_uint32_p, c_float_p, c_uint8_p, c_uint8_p, C.POINTER(AlignmentSummary)]),
+    "fgoicp_batch_alignment": (C.c_int, [C.c_void_p, C.c_int, c_uint32_p, c_float_p, c_uint8_p, c_uint8_p, C.POINTER(AlignmentSummary)]),
     "fgoicp_icp": (C.c_int, [C.c_void_p, c_float_p, c_float_p, C.c_size_t, C.c_float, c_float_p, c_float_p, c_float_p, c_int_p]),
     "fgoicp_icp_batch": (C.c_int, [C.c_void_p, C.c_int, c_float_p, c_float_p, C.c_size_t, C.c_float, c_float_p, c_float_p, c_float_p, c_int_p]),
     "fgoicp_procrustes": (C.c_int, [C.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p, c_int_p]),

@@ -6,7 +6,7 @@ import numpy as np
 
 from . import _lib
 from .nodes import from_glm
-from .registration import _cloud, _fp
+from .registration import _alignment, _cloud, _fp
 
 
 class FastGoICPBatch:
@@ -14,9 +14,10 @@ class FastGoICPBatch:
     the defaults below apply to what a pair leaves out.  trim_fraction: as FastGoICP's, per pair (0 = untrimmed)."""
 
     def __init__(self, pairs, lut_resolution=0.005, mse_threshold=1e-3, schedule=_lib.SCHEDULE_SERIAL, round_width=1, device=0, flags=0,
-                 max_live=0, trim_fraction=0.0):
+                 max_live=0, trim_fraction=0.0, alignment=False):
         self._lib = _lib.load()
         self._clouds = []
+        self._sizes = []
         arr = (_lib.BatchPair * max(1, len(pairs)))()
         trim = np.zeros(max(1, len(pairs)), np.float32)
         for i, p in enumerate(pairs):
@@ -24,10 +25,11 @@ class FastGoICPBatch:
             lr, mt = (p[2], p[3]) if len(p) > 2 else (lut_resolution, mse_threshold)
             trim[i] = p[4] if len(p) > 4 else trim_fraction
             self._clouds.append((pct, pcs))  # the library copies them at create; kept until then
+            self._sizes.append((len(pcs), len(pct)))
             arr[i] = _lib.BatchPair(_fp(pct), len(pct), _fp(pcs), len(pcs), float(lr), float(mt))
         self.n = len(pairs)
         opts = _lib.BatchOpts(C.sizeof(_lib.BatchOpts), _lib.SolverOpts(int(schedule), int(round_width), int(flags), int(device), 0.0), int(max_live),
-                              _fp(trim))
+                              _fp(trim), int(bool(alignment)))
         self._h = C.c_void_p()
         _lib.check(self._lib.fgoicp_batch_create(arr, self.n, C.byref(opts), C.byref(self._h)), "fgoicp_batch_create")
         self._clouds = None
@@ -64,6 +66,12 @@ class FastGoICPBatch:
         st = _lib.RunStats()
         _lib.check(self._lib.fgoicp_batch_stats(self._h, int(i), C.byref(st)), "fgoicp_batch_stats")
         return st.as_dict()
+
+    def alignment(self, i):
+        """EXTENSION (fgoicp_batch_alignment; needs alignment=True): pair i's Alignment at its best transform, what FastGoICP.alignment()
+        returns for that pair alone."""
+        ns, nt = self._sizes[i]
+        return _alignment(lambda *a: self._lib.fgoicp_batch_alignment(self._h, int(i), *a), "fgoicp_batch_alignment", ns, nt)
 
     def launches(self):
         """-> (fused bounds launches, lock-step ICP iterations) of the last run."""

@@ -110,7 +110,7 @@ inline TomlTable parse_toml(const std::string& path) {
 // Config — src/utilities.hpp:18-107 (same keys, defaults and clamps; `seed` is an addition)
 // ------------------------------------------------------------------------------------------
 struct Config {
-    struct IO { std::string target, source, output, visualization; } io;
+    struct IO { std::string target, source, output, visualization, alignment; } io;  // alignment: EXTENSION, optional (write_alignment_txt)
     struct Params {
         bool trim = false;
         float target_subsample = 1.0f, source_subsample = 1.0f, lut_resolution = 0.005f, mse_threshold = 1e-3f;
@@ -153,6 +153,7 @@ struct Config {
         io.source = str("io", "source", "");
         io.output = str("io", "output", "");                // declared in test/bunny.toml:10, unparsed upstream
         io.visualization = str("io", "visualization", "");  // declared in test/bunny.toml:11, unparsed upstream
+        io.alignment = str("io", "alignment", "");          // EXTENSION: where the alignment report goes ("" = none; not part of the printed summary)
         auto clampf0 = [](float x) { return x < 0.0f ? 0.0f : (x > 0.9f ? 0.9f : x); };
         if (tbl.count("params")) {
             params.trim = boolean("params", "trim", false);
@@ -348,6 +349,25 @@ inline void write_result_toml(const std::string& path, const icp::mat3& R, const
     f << "sse = " << sse << "\nmse = " << sse / (float)ns << "\nseconds = " << seconds << "\n";
     f << "\n[stats]\nsubcubes = " << st.trans_cubes << "\nrotation_cubes = " << st.rot_cubes << "\nicp_runs = " << st.icp_runs
       << "\nicp_iterations = " << st.icp_iters << "\nrounds = " << st.rounds << "\n";
+}
+
+// io.alignment (EXTENSION): the alignment report of the run (fgoicp_solver_alignment / fgoicp_batch_alignment).  Two '#' lines — the summary,
+// the column names — then one line per registered source point, in the order the cloud was loaded (after source_subsample): its coordinates
+// as loaded, the index of its nearest target point (into the target as loaded), its distance to it in the files' units
+// (sqrt(dist2) / scaling_factor) and 1 if the optimum counts it as an inlier.
+inline void write_alignment_txt(const std::string& path, const std::vector<icp::vec3>& src, const uint32_t* idx, const float* dist2, const uint8_t* inlier,
+                                const fgoicp_alignment_summary& s) {
+    std::ofstream f(path);
+    if (!f) throw std::runtime_error("Unable to write " + path);
+    f.precision(9);
+    const double scale = (double)s.scaling_factor;
+    f << "# alignment: points = " << s.points << ", inliers = " << s.inliers << ", targets_hit = " << s.targets_hit << ", sse = " << s.sse
+      << ", max_inlier_dist2 = " << s.max_inlier_dist2 << ", scaling_factor = " << s.scaling_factor
+      << ", fitness = " << (s.points ? (double)s.inliers / (double)s.points : 0.0)
+      << ", inlier_rmse = " << (s.inliers ? std::sqrt((double)s.sse / (double)s.inliers) / scale : 0.0) << "\n";
+    f << "# x y z target_index distance inlier\n";
+    for (size_t i = 0; i < src.size(); ++i)
+        f << src[i].x << " " << src[i].y << " " << src[i].z << " " << idx[i] << " " << std::sqrt((double)dist2[i]) / scale << " " << (int)inlier[i] << "\n";
 }
 
 inline void write_visualization_ply(const std::string& path, const std::vector<icp::vec3>& tgt, const std::vector<icp::vec3>& src,

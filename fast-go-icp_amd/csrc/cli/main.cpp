@@ -62,6 +62,7 @@ static int run_batch(const std::string& list_file) {
     o.struct_size = sizeof(o);
     o.solver = fgoicp_solver_opts{schedule, c0.params.round_width, 0u, 0, 0.0f};
     o.trim_fractions = trim.data();
+    for (const cli::Config& c : configs) o.alignment |= c.io.alignment.empty() ? 0 : 1;  // the reports are kept only if a config asks for one
     fgoicp_batch* b = nullptr;
     icp::check_status(fgoicp_batch_create(pairs.data(), (int)n, &o, &b), "fgoicp_batch_create");
     std::vector<float> R9(9 * n), t3(3 * n);
@@ -84,6 +85,15 @@ static int run_batch(const std::string& list_file) {
         const cli::Config& c = configs[i];
         if (!c.io.output.empty()) cli::write_result_toml(c.io.output, R, t, best_error, pcs[i].size(), elapsed.count(), st);
         if (!c.io.visualization.empty()) cli::write_visualization_ply(c.io.visualization, pct[i], pcs[i], R, t);
+        if (!c.io.alignment.empty()) {
+            std::vector<uint32_t> idx(pcs[i].size());
+            std::vector<float> d2(pcs[i].size());
+            std::vector<uint8_t> inl(pcs[i].size());
+            fgoicp_alignment_summary sm{};
+            sm.struct_size = sizeof(sm);
+            icp::check_status(fgoicp_batch_alignment(b, (int)i, idx.data(), d2.data(), inl.data(), nullptr, &sm), "fgoicp_batch_alignment");
+            cli::write_alignment_txt(c.io.alignment, pcs[i], idx.data(), d2.data(), inl.data(), sm);
+        }
     }
     fgoicp_batch_destroy(b);
     return rc;
@@ -143,6 +153,17 @@ int main(int argc, char* argv[]) {
     fgoicp_run_stats st{};
     float best_error = 0.f;
     std::chrono::duration<double> elapsed_seconds{};
+    // io.alignment: the report at the best transform, from the solver that ran (rank 0's on several GPUs: every rank holds the same answer)
+    auto write_alignment = [&](fgoicp_solver* s) {
+        if (config.io.alignment.empty()) return;
+        std::vector<uint32_t> idx(pcs_in.size());
+        std::vector<float> d2(pcs_in.size());
+        std::vector<uint8_t> inl(pcs_in.size());
+        fgoicp_alignment_summary sm{};
+        sm.struct_size = sizeof(sm);
+        icp::check_status(fgoicp_solver_alignment(s, idx.data(), d2.data(), inl.data(), nullptr, &sm), "fgoicp_solver_alignment");
+        cli::write_alignment_txt(config.io.alignment, pcs_in, idx.data(), d2.data(), inl.data(), sm);
+    };
     if (gpus > 1) {
         // EXTENSION: one host thread + one solver per GPU (include/fgoicp_amd.h, fgoicp_multi_*).  params.schedule = "serial" (the
         // default) keeps the reference's exact trajectory and deals the inner BnBs of every speculative evaluation over the GPUs;
@@ -176,6 +197,7 @@ int main(int argc, char* argv[]) {
             if (r == 0) { st.rounds = s1.rounds; st.initial_icp_sse = s1.initial_icp_sse; }
         }
         icp::check_status(fgoicp_solver_best_error(fgoicp_multi_solver(m, 0), &best_error), "fgoicp_solver_best_error");
+        write_alignment(fgoicp_multi_solver(m, 0));
         fgoicp_multi_destroy(m);
         icp::Logger(icp::LogLevel::Info) << "Searching over! Best Error: " << best_error << "\n\tRotation:\n" << R << "\n\tTranslation: " << t;  // fgoicp.cpp:25-27
     } else {
@@ -186,6 +208,7 @@ int main(int argc, char* argv[]) {
         elapsed_seconds = std::chrono::high_resolution_clock::now() - start;
         st = fgoicp.stats();
         best_error = fgoicp.get_best_error();
+        write_alignment(fgoicp.handle());
     }
     icp::Logger(icp::LogLevel::Debug) << "Subcubes: " << st.trans_cubes << ", rotation cubes: " << st.rot_cubes << ", ICP runs: " << st.icp_runs;
     icp::Logger(icp::LogLevel::Info) << "Fast Go-ICP finished, time elapsed: " << std::fixed << std::setprecision(3) << elapsed_seconds.count() << " seconds";

@@ -475,6 +475,84 @@ int ctx_sse(fgoicp_ctx* c, const float* R9, const float* t3, float* sse_out, con
     return lane_sse(c, c->lanes[0], R9, t3, sse_out, seed_idx);
 }
 
+// EXTENSION: the alignment report (fgoicp_alignment) for the pristine source under (R, t), on lane 0.
+//   1. the minima by the path fgoicp_sse takes for this context (sse_enqueue: fused scan, tree scan or brute force; its sum is the
+//      summary's sse, so the bits are fgoicp_sse's by construction) — with the trimmed skip off, so that every query is searched; the k
+//      smallest minima and the fixed order of their sum do not change, the skipped queries' stand-ins lay above the cut like the true
+//      minima they replace;
+//   2. the correspondences by a second walk in index mode (nn_scan_kernel<1> returns the index, not the minimum), or the brute-force
+//      tie-set kernels on the moved cloud;
+//   3. trimmed: the inlier mask from those exact minima (selection + mask + ties, launch_inlier_mask);
+//   4. device order -> caller order, target marks and the integer summary (launch_align_scatter).
+// Everything written is scratch that every other path fills before it reads (d_min_bits, d_work, d_thr_bits, d_sel, d_eq, d_use, the
+// pinned sums) or the report's own allocation; d_first_idx / d_first_idx2, the seeds of a later ICP pass, are not touched.
+int ctx_alignment(fgoicp_ctx* c, const float* R9, const float* t3, uint32_t* corr_idx, float* dist2, uint8_t* inlier, uint8_t* target_hit,
+                  fgoicp_alignment_summary* out) {
+    HIPCHK(hipSetDevice(c->device));
+    fgoicp_ctx::IcpLane& L = c->lanes[0];
+    fgoicp_ctx::AlignScratch& A = c->align;
+    const int ns = (int)c->ns, nt = (int)c->nt;
+    if (!c->d_orig_of_slot) {  // untrimmed contexts have had no use for it so far
+        HIPCHK(hipMalloc(&c->d_orig_of_slot, sizeof(uint32_t) * c->ns));
+        HIPCHK(hipMemcpy(c->d_orig_of_slot, c->perm.data(), sizeof(uint32_t) * c->ns, hipMemcpyHostToDevice));
+    }
+    if (!A.base) {
+        auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+        A.nt16 = (c->nt + 15) & ~(size_t)15;
+        const size_t nblk = (c->ns + kBlock - 1) / kBlock;
+        const size_t o_idx = 0, o_corr = o_idx + up(4 * c->ns), o_d2 = o_corr + up(4 * c->ns), o_inl = o_d2 + up(4 * c->ns), o_hit = o_inl + up(c->ns),
+                     o_part = o_hit + up(A.nt16), o_sum = o_part + up(sizeof(uint2) * nblk), total = o_sum + 256;
+        HIPCHK(hipMalloc(&A.base, total));
+        char* b = static_cast<char*>(A.base);
+        A.d_idx = reinterpret_cast<uint32_t*>(b + o_idx);
+        A.d_corr = reinterpret_cast<uint32_t*>(b + o_corr);
+        A.d_d2 = reinterpret_cast<float*>(b + o_d2);
+        A.d_inl = reinterpret_cast<unsigned char*>(b + o_inl);
+        A.d_hit = reinterpret_cast<unsigned char*>(b + o_hit);
+        A.d_partials = reinterpret_cast<uint2*>(b + o_part);
+        A.d_sum = reinterpret_cast<uint32_t*>(b + o_sum);
+    }
+    hipStream_t st = L.stream;
+    const bool skip = c->trim_skip;
+    c->trim_skip = false;
+    const int rc = sse_enqueue(c, L, R9, t3, nullptr, st);
+    c->trim_skip = skip;
+    if (rc) return rc;
+    if (c->brute_force_nn) {  // kernFindNearestNeighbor (icp3d.cu:11-28) as procrustes_enqueue runs it, on the source moved as the scan's queries are
+        HIPCHK(hipMemcpyAsync(L.d_work, c->d_src, sizeof(float4) * c->ns, hipMemcpyDeviceToDevice, st));
+        launch_transform_inplace(L.d_work, ns, R9, t3, st);
+        launch_fill_u32(A.d_idx, 0x7fffffffu, c->ns, st);
+        launch_nn_tie_threshold(L.d_min_bits, ns, L.d_thr_bits, st);
+        launch_nn_first_index(L.d_work, ns, c->d_tgt, nt, L.d_thr_bits, A.d_idx, st);
+    } else {
+        launch_nn_scan(c->d_src, ns, c->bvh_tgt.view(), c->d_lut, c->geom, R9, t3, 1, 1, c->d_tgt, nt, nullptr, nullptr, nullptr, A.d_idx, st);
+    }
+    const unsigned char* use = nullptr;
+    if (c->inliers) {
+        launch_inlier_mask(reinterpret_cast<const float*>(L.d_min_bits), ns, (int)c->inliers, L.d_sel, L.d_eq, c->d_orig_of_slot, L.d_use, L.d_sel_wide, st);
+        use = L.d_use;
+    }
+    HIPCHK(hipMemsetAsync(A.d_hit, 0, A.nt16, st));
+    launch_align_scatter(A.d_idx, L.d_min_bits, use, c->d_orig_of_slot, ns, nt, A.d_corr, A.d_d2, A.d_inl, A.d_hit, A.nt16, A.d_partials, A.d_sum, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    uint32_t sum3[3] = {0, 0, 0};
+    HIPCHK(hipMemcpy(sum3, A.d_sum, sizeof(sum3), hipMemcpyDeviceToHost));
+    if (corr_idx) HIPCHK(hipMemcpy(corr_idx, A.d_corr, sizeof(uint32_t) * c->ns, hipMemcpyDeviceToHost));
+    if (dist2) HIPCHK(hipMemcpy(dist2, A.d_d2, sizeof(float) * c->ns, hipMemcpyDeviceToHost));
+    if (inlier) HIPCHK(hipMemcpy(inlier, A.d_inl, c->ns, hipMemcpyDeviceToHost));
+    if (target_hit) HIPCHK(hipMemcpy(target_hit, A.d_hit, c->nt, hipMemcpyDeviceToHost));
+    if (out) {
+        out->points = c->ns;
+        out->inliers = sum3[0];
+        out->targets_hit = sum3[1];
+        out->sse = sse_result(c, L);
+        std::memcpy(&out->max_inlier_dist2, &sum3[2], sizeof(float));
+        out->scaling_factor = 1.0f;
+    }
+    return FGOICP_OK;
+}
+
 // IterativeClosestPoint3D::procrustes() on L.d_work — icp3d.cu:140-172.  The device half (enqueue only): correspondences
 // into `idx`, centroids and covariance into pinned memory; `wide` is the selection scratch of the trimmed variant.
 // move9 / move3 (optional): the working cloud is first moved by this (R_, t_) — icp3d.cu:100 of the iteration before — inside the
@@ -1471,6 +1549,7 @@ void fgoicp_ctx_destroy(fgoicp_ctx* c) {
     (void)hipFree(c->d_chunk_cen);
     (void)hipFree(c->d_span_cen);
     (void)hipFree(c->d_orig_of_slot);
+    (void)hipFree(c->align.base);
     for (int k = 0; k < 2; ++k) {
         fgoicp_ctx::TickSlot& sl = c->slots[k];
         if (sl.done) (void)hipEventDestroy(sl.done);
@@ -1658,6 +1737,15 @@ int fgoicp_ctx_sort_fallbacks(const fgoicp_ctx* c, uint64_t* sorted_ticks, uint6
 int fgoicp_sse(fgoicp_ctx* c, const float* R9, const float* t3, float* sse_out) {
     if (!c || !R9 || !t3 || !sse_out) return FGOICP_ERR_INVALID_ARG;
     return ctx_sse(c, R9, t3, sse_out, nullptr);
+}
+
+int fgoicp_alignment(fgoicp_ctx* c, const float* R9, const float* t3, uint32_t* corr_idx_ns, float* dist2_ns, uint8_t* inlier_ns, uint8_t* target_hit_nt,
+                     fgoicp_alignment_summary* out) {
+    if (!c || !R9 || !t3) { set_error("fgoicp_alignment: the context, R and t must not be null"); return FGOICP_ERR_INVALID_ARG; }
+    if (out && (out->struct_size < sizeof(uint32_t) || out->struct_size > 4096)) { set_error("fgoicp_alignment: set out->struct_size = sizeof(fgoicp_alignment_summary)"); return FGOICP_ERR_INVALID_ARG; }
+    fgoicp_alignment_summary full{};
+    const int rc = ctx_alignment(c, R9, t3, corr_idx_ns, dist2_ns, inlier_ns, target_hit_nt, &full);
+    return rc ? rc : alignment_summary_out(full, out, "fgoicp_alignment");
 }
 
 int fgoicp_icp(fgoicp_ctx* c, const float* R0, const float* t0, size_t max_iter, float thr, float* sse_out, float* R_out9, float* t_out3,

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -106,7 +107,19 @@ struct fgoicp_ctx {
     bool trim_skip = true;                   // exact NN only for queries that can be among the k smallest (nn_prep_kernel)
     float bounds6[6] = {0, 0, 0, 0, 0, 0};   // target_bounds as passed to fgoicp_ctx_create (they place the LUT)
     float tgt_box6[6] = {0, 0, 0, 0, 0, 0};  // the target's bounding box computed from the points (trimmed search: nn_prep_kernel)
-    uint32_t* d_orig_of_slot = nullptr;      // caller index of every device slot (ties at the inlier cut)
+    uint32_t* d_orig_of_slot = nullptr;      // caller index of every device slot (ties at the inlier cut; the alignment report)
+
+    // the alignment report (ctx_alignment): one allocation on the first call, 13 bytes per source point and one per target point
+    struct AlignScratch {
+        void* base = nullptr;
+        uint32_t* d_idx = nullptr;               // correspondences, device order
+        uint32_t* d_corr = nullptr;              // ... and the report in caller order: correspondences, squared distances, inlier flags
+        float* d_d2 = nullptr;
+        unsigned char *d_inl = nullptr, *d_hit = nullptr;   // d_hit: nt16 bytes
+        uint2* d_partials = nullptr;
+        uint32_t* d_sum = nullptr;               // {inliers, targets hit, bits of the largest inlier squared distance}
+        size_t nt16 = 0;
+    } align;
 
     // exact-NN / ICP scratch, one set per lane: ICP runs on different lanes may be in flight together (ctx_icp_batch).  Lane 0 is
     // the lane of fgoicp_sse / fgoicp_icp / fgoicp_procrustes and queues on the context's main stream.
@@ -172,6 +185,18 @@ int ctx_set_inliers_batch(fgoicp_ctx* c, size_t k);
 size_t trim_rows_budget(size_t free_bytes);        // bytes of e-rows per slot (solo) / per batch arena
 size_t trim_icp_bytes(size_t ns, size_t lanes);    // device bytes trimmed ICP adds to a context
 int ctx_sse(fgoicp_ctx* c, const float* R9, const float* t3, float* sse_out, const uint32_t* seed_idx = nullptr);
+// fgoicp_alignment on lane 0; every output may be null.  `out` is filled whole (scaling_factor = 1), whatever its struct_size says.
+int ctx_alignment(fgoicp_ctx* c, const float* R9, const float* t3, uint32_t* corr_idx, float* dist2, uint8_t* inlier, uint8_t* target_hit,
+                  fgoicp_alignment_summary* out);
+// a summary handed to a caller: no byte beyond the struct_size the caller set is written (0, or less than the size field itself: refused)
+inline int alignment_summary_out(const fgoicp_alignment_summary& full, fgoicp_alignment_summary* out, const char* where) {
+    if (!out) return FGOICP_OK;
+    const uint32_t n = out->struct_size;
+    if (n < sizeof(uint32_t) || n > 4096) { set_error(std::string(where) + ": set out->struct_size = sizeof(fgoicp_alignment_summary)"); return FGOICP_ERR_INVALID_ARG; }
+    std::memcpy(out, &full, n < sizeof(full) ? n : sizeof(full));
+    out->struct_size = n;
+    return FGOICP_OK;
+}
 int ctx_icp(fgoicp_ctx* c, const float* R0, const float* t0, size_t max_iter, float thr, float* sse_out, float* R_out9, float* t_out3,
             int* iters_out);
 int ctx_icp_coop(fgoicp_ctx* c, int rank, int world, int (*gather)(void* dev_buf, size_t bytes_per_rank, void* user), void* user, const float* R0,

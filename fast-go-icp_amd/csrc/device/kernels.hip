@@ -2374,4 +2374,99 @@ void launch_icp_inliers(const float4* work, const float4* tgt, const uint32_t* i
     hipLaunchKernelGGL(icp_inlier_ties_kernel, dim3(std::max(1, std::min(256, (n + 1023) / 1024))), dim3(1024), 0, s, n, sel_info, equal_count, orig_of_slot, use);
 }
 
+// launch_icp_inliers without its first kernel: the squared distances are given (the exact minima of a scan)
+void launch_inlier_mask(const float* d2, int n, int k, uint32_t* sel_info, uint32_t* equal_count, const uint32_t* orig_of_slot, unsigned char* use,
+                        uint32_t* wide_scratch, hipStream_t s) {
+    const int nb = (n + kBlock - 1) / kBlock;
+    launch_fill_u32(equal_count, 0u, 1, s);  // counted by icp_inlier_mask_kernel (icp_corr_d2_kernel zeroes it in launch_icp_inliers)
+    launch_trim_select(d2, n, k, nullptr, sel_info, wide_scratch, s);
+    hipLaunchKernelGGL(icp_inlier_mask_kernel, dim3(nb), dim3(kBlock), 0, s, d2, n, sel_info, use, equal_count);
+    hipLaunchKernelGGL(icp_inlier_ties_kernel, dim3(std::max(1, std::min(256, (n + 1023) / 1024))), dim3(1024), 0, s, n, sel_info, equal_count, orig_of_slot, use);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The alignment report (fgoicp_alignment): what the exact scans left per device slot, in the caller's point order.
+// Slot i holds caller point orig_of_slot[i]: every thread reads its slot's correspondence, minimum and inlier flag (coalesced) and stores
+// them at the caller index (4 + 4 + 1 bytes scattered; the three arrays of the largest cloud served are 9 MB and stay in L2, and the call
+// runs once per registration, so no inverse permutation is built).  An inlier marks its neighbour in target_hit with a plain byte store of
+// 1 — every writer of a byte stores the same value, so the array does not depend on timing.  Each block leaves {inliers, bits of the
+// largest inlier minimum} (non-negative floats order like their bit patterns); align_fold_kernel folds them and counts target_hit.
+// Integer sums and a max: independent of order, hence reproducible.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void align_scatter_kernel(const uint32_t* __restrict__ idx, const uint32_t* __restrict__ min_bits,
+                                                               const unsigned char* __restrict__ use /* nullptr: every point is an inlier */,
+                                                               const uint32_t* __restrict__ orig_of_slot, int n, int nt, uint32_t* __restrict__ corr_out,
+                                                               uint32_t* __restrict__ d2_out, unsigned char* __restrict__ inlier_out,
+                                                               unsigned char* __restrict__ target_hit, uint2* __restrict__ partials) {
+    __shared__ unsigned s_cnt[kBlock / 64], s_max[kBlock / 64];
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    unsigned cnt = 0u, mx = 0u;
+    if (i < n) {
+        const uint32_t o = orig_of_slot[i], j = idx[i], b = min_bits[i];
+        const bool in = use ? use[i] != 0 : true;
+        if (o < (uint32_t)n) {
+            corr_out[o] = j;
+            d2_out[o] = b;
+            inlier_out[o] = in ? 1 : 0;
+        }
+        if (in) {
+            if (j < (uint32_t)nt) target_hit[j] = 1;
+            cnt = 1u;
+            mx = b;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        cnt += __shfl_xor(cnt, off, 64);
+        mx = max(mx, (unsigned)__shfl_xor(mx, off, 64));
+    }
+    if ((threadIdx.x & 63) == 0) { s_cnt[threadIdx.x >> 6] = cnt; s_max[threadIdx.x >> 6] = mx; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int w = 1; w < kBlock / 64; ++w) { cnt += s_cnt[w]; mx = max(mx, s_max[w]); }
+        partials[blockIdx.x] = make_uint2(cnt, mx);
+    }
+}
+// One block: out = {inliers, distinct targets hit, bits of the largest inlier minimum}.  target_hit holds nt16 bytes (nt rounded up to 16,
+// the padding zero), every byte 0 or 1: the ones of a 16-byte word are its set bits.
+__global__ __launch_bounds__(1024) void align_fold_kernel(const unsigned char* __restrict__ target_hit, size_t nt16, const uint2* __restrict__ partials, int nblocks,
+                                                          uint32_t* __restrict__ out) {
+    __shared__ unsigned s_acc[3];
+    if (threadIdx.x < 3) s_acc[threadIdx.x] = 0u;
+    __syncthreads();
+    unsigned hits = 0u, cnt = 0u, mx = 0u;
+    const uint4* h4 = reinterpret_cast<const uint4*>(target_hit);
+    for (size_t q = threadIdx.x; q < nt16 / 16; q += 1024) {
+        const uint4 v = h4[q];
+        hits += __popc(v.x) + __popc(v.y) + __popc(v.z) + __popc(v.w);
+    }
+    for (int b = threadIdx.x; b < nblocks; b += 1024) {
+        const uint2 p = partials[b];
+        cnt += p.x;
+        mx = max(mx, p.y);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        hits += __shfl_xor(hits, off, 64);
+        cnt += __shfl_xor(cnt, off, 64);
+        mx = max(mx, (unsigned)__shfl_xor(mx, off, 64));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        atomicAdd(&s_acc[0], cnt);
+        atomicAdd(&s_acc[1], hits);
+        atomicMax(&s_acc[2], mx);
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) out[threadIdx.x] = s_acc[threadIdx.x];
+}
+
+void launch_align_scatter(const uint32_t* idx, const uint32_t* min_bits, const unsigned char* use, const uint32_t* orig_of_slot, int n, int nt, uint32_t* corr_out,
+                          float* d2_out, unsigned char* inlier_out, unsigned char* target_hit, size_t nt16, uint2* partials, uint32_t* summary3, hipStream_t s) {
+    const int nb = (n + kBlock - 1) / kBlock;
+    hipLaunchKernelGGL(align_scatter_kernel, dim3(nb), dim3(kBlock), 0, s, idx, min_bits, use, orig_of_slot, n, nt, corr_out, reinterpret_cast<uint32_t*>(d2_out), inlier_out,
+                       target_hit, partials);
+    hipLaunchKernelGGL(align_fold_kernel, dim3(1), dim3(1024), 0, s, target_hit, nt16, partials, nb, summary3);
+}
+
 }  // namespace fgoicp

@@ -97,6 +97,16 @@ void launch_trim_select(const float* vals, int n, int k, float* out, uint32_t* s
                         uint32_t* wide_scratch /* 64 KiB, optional: rows of n >= 32768 are then selected by the whole device */, hipStream_t s);
 void launch_icp_inliers(const float4* work, const float4* tgt, const uint32_t* idx, int n, int nt, int k, float* d2, uint32_t* sel_info,
                         uint32_t* equal_count, const uint32_t* orig_of_slot, unsigned char* use, uint32_t* wide_scratch, hipStream_t s);
+// launch_icp_inliers on given squared distances (fgoicp_alignment: the exact minima of a scan): use[i] = 1 for the k smallest of d2[0..n), ties at
+// the cut to the lowest caller indices (orig_of_slot)
+void launch_inlier_mask(const float* d2, int n, int k, uint32_t* sel_info, uint32_t* equal_count, const uint32_t* orig_of_slot, unsigned char* use,
+                        uint32_t* wide_scratch, hipStream_t s);
+// The alignment report (fgoicp_alignment; kernels.hip align_scatter_kernel, align_fold_kernel): idx / min_bits / use (nullptr: every point is an
+// inlier) per device slot -> corr_out / d2_out / inlier_out per caller index (n entries each); target_hit[j] = 1 for every neighbour of an inlier
+// (nt16 = nt rounded up to 16 bytes, zero on entry); partials: ceil(n / kBlock) entries; summary3 = {inliers, distinct targets hit, bits of the
+// largest inlier squared distance}
+void launch_align_scatter(const uint32_t* idx, const uint32_t* min_bits, const unsigned char* use, const uint32_t* orig_of_slot, int n, int nt, uint32_t* corr_out,
+                          float* d2_out, unsigned char* inlier_out, unsigned char* target_hit, size_t nt16, uint2* partials, uint32_t* summary3, hipStream_t s);
 // The bounds of many registrations in one launch (fgoicp_batch, bounds_fused.hpp): a view per pair of the batch, an evaluation per output
 // row, work items {evaluation, chunk}.  Every row is the bits its pair's own context computes with thresholds off.
 struct FusedPairView {

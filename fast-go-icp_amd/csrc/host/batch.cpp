@@ -39,6 +39,17 @@ struct PairHost {
     size_t inliers = 0;  // trim_inliers(ns, trim_fraction): 0 = untrimmed
 };
 
+// a finished pair's alignment report, kept on the host (fgoicp_batch_opts.alignment): 9 bytes per source point, 1 per target point
+struct PairAlign {
+    std::vector<uint32_t> corr;
+    std::vector<float> d2;
+    std::vector<uint8_t> inlier, hit;
+    fgoicp_alignment_summary sum{};
+    int rc = FGOICP_OK;
+    std::string err;
+    bool have = false;
+};
+
 // work items per fused launch (one 64-thread block each): a class with more is split, so that blocks x threads stay inside the 32-bit
 // grid size of a dispatch, with the margin the solo path keeps (ctx.hip, launch_fit)
 constexpr size_t kFusedLaunchItems = (size_t)1 << 24;
@@ -100,6 +111,7 @@ struct HipBatchBackend {
     uint64_t bounds_launches = 0, icp_launches = 0, selection_launches = 0;
     size_t last_lut_bytes = 0, last_lanes = 4;
     int next_pair = 0;            // the pair the scheduler admits next (room_for_more)
+    std::vector<PairAlign>* align = nullptr;   // fgoicp_batch_opts.alignment: where finished() leaves every pair's report (nullptr: off)
     // trimmed pairs: one grow-only arena of e-rows for the whole run (one fill per sub-tick), the solo formula's budget (trim_rows_budget)
     size_t arena_budget = 0;      // bytes; 0 = not set yet
     size_t arena_rows_max = 0;    // test hook: at most this many rows per fill (0: the budget decides)
@@ -186,6 +198,19 @@ struct HipBatchBackend {
         const size_t arena_b = sizeof(float) * d_arena.cap;
         if (arena_budget > arena_b) need += arena_budget - arena_b;
         return free_b > need;
+    }
+    // BatchScheduler's optional hook: the pair's driver has ended, its context is still there.  The report at the pair's best transform, as
+    // fgoicp_solver_alignment takes it from a solver of that pair alone (ctx_alignment on the pair's own context: nothing is shared).
+    void finished(int i, const BatchPairResult& r) {
+        if (!align || r.status || !ctx[(size_t)i]) return;
+        const PairHost& p = (*pairs)[(size_t)i];
+        PairAlign& a = (*align)[(size_t)i];
+        a.corr.resize(p.ns); a.d2.resize(p.ns); a.inlier.resize(p.ns); a.hit.resize(p.nt);
+        const float t3[3] = {r.t.x, r.t.y, r.t.z};
+        a.rc = ctx_alignment(ctx[(size_t)i], r.R.m, t3, a.corr.data(), a.d2.data(), a.inlier.data(), a.hit.data(), &a.sum);
+        a.sum.scaling_factor = p.scaling_factor;
+        a.have = a.rc == FGOICP_OK;
+        if (a.rc) a.err = fgoicp_last_error();
     }
     void release(int i) {
         (void)hipSetDevice(device);
@@ -387,6 +412,7 @@ struct fgoicp_batch {
     std::vector<int> status;
     uint64_t bounds_launches = 0, icp_launches = 0;
     bool ran = false;
+    std::vector<PairAlign> align;  // opts.alignment: one per pair
 };
 
 extern "C" {
@@ -453,6 +479,10 @@ static int batch_run_impl(fgoicp_batch* b, float* R_out9n, float* t_out3n, int* 
     be.pairs = &b->pairs;
     be.device = b->opts.solver.device;
     be.ctx_flags = b->opts.solver.ctx_flags;
+    if (b->opts.alignment) {
+        b->align.assign((size_t)n, PairAlign());
+        be.align = &b->align;
+    }
     int rc = be.init();
     if (rc) return rc;
     std::vector<BatchPairSpec> specs((size_t)n);
@@ -502,6 +532,24 @@ int fgoicp_batch_stats(const fgoicp_batch* b, int i, fgoicp_run_stats* out) {
     out->icp_runs = d.icp_runs; out->icp_iters = d.icp_iters; out->inner_bnb = d.inner_bnb; out->rounds = d.rounds;
     out->seconds_total = d.seconds_total; out->seconds_bnb = d.seconds_bnb; out->seconds_icp = d.seconds_icp; out->initial_icp_sse = d.initial_icp_sse;
     return FGOICP_OK;
+}
+
+int fgoicp_batch_alignment(const fgoicp_batch* b, int i, uint32_t* corr_idx_ns, float* dist2_ns, uint8_t* inlier_ns, uint8_t* target_hit_nt,
+                           fgoicp_alignment_summary* out) {
+    const char* where = "fgoicp_batch_alignment";
+    if (!b) { set_error(std::string(where) + ": the batch must not be null"); return FGOICP_ERR_INVALID_ARG; }
+    if (!b->opts.alignment) { set_error(std::string(where) + ": the batch was created with fgoicp_batch_opts.alignment = 0"); return FGOICP_ERR_INVALID_ARG; }
+    if (!b->ran) { set_error(std::string(where) + ": fgoicp_batch_run has not run yet"); return FGOICP_ERR_INVALID_ARG; }
+    if (i < 0 || i >= (int)b->pairs.size()) { set_error(std::string(where) + ": pair index out of range"); return FGOICP_ERR_INVALID_ARG; }
+    if (b->status[(size_t)i]) { set_error(std::string(where) + ": pair " + std::to_string(i) + " failed (status " + std::to_string(b->status[(size_t)i]) + ")"); return FGOICP_ERR_INVALID_ARG; }
+    if (out && (out->struct_size < sizeof(uint32_t) || out->struct_size > 4096)) { set_error(std::string(where) + ": set out->struct_size = sizeof(fgoicp_alignment_summary)"); return FGOICP_ERR_INVALID_ARG; }
+    const PairAlign& a = b->align[(size_t)i];
+    if (!a.have) { set_error(std::string(where) + ": pair " + std::to_string(i) + ": " + (a.err.empty() ? "no report was taken" : a.err)); return a.rc ? a.rc : FGOICP_ERR_INVALID_ARG; }
+    if (corr_idx_ns) std::memcpy(corr_idx_ns, a.corr.data(), sizeof(uint32_t) * a.corr.size());
+    if (dist2_ns) std::memcpy(dist2_ns, a.d2.data(), sizeof(float) * a.d2.size());
+    if (inlier_ns) std::memcpy(inlier_ns, a.inlier.data(), a.inlier.size());
+    if (target_hit_nt) std::memcpy(target_hit_nt, a.hit.data(), a.hit.size());
+    return alignment_summary_out(a.sum, out, where);
 }
 
 int fgoicp_batch_launches(const fgoicp_batch* b, uint64_t* bounds_launches, uint64_t* icp_launches) {

@@ -16,6 +16,7 @@
 //     int  Backend::bounds(std::vector<BatchBoundsReq*>&)   every request's lb / ub
 //     int  Backend::icp_start(BatchIcpReq&)             a run of fgoicp_icp; may complete it at once (req.done)
 //     int  Backend::icp_step(std::vector<BatchIcpReq*>&)    one iteration of every active run; completes those whose loop ended
+//     void Backend::finished(int pair, const BatchPairResult&)   optional (BackendHasFinished): before release, the driver has ended
 //
 // A request's results depend on its pair and its inputs only, never on which other requests share the launch, so every pair gets the
 // bits of its own solo run whatever the grouping (tests/test_batch_host.py varies it at random).
@@ -29,6 +30,8 @@
 #include <random>
 #include <string>
 #include <thread>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../../include/fgoicp_amd.h"
@@ -75,6 +78,13 @@ struct BatchPairResult {
 };
 
 template <class Backend> class BatchScheduler;
+
+// Optional backend hook: void Backend::finished(int pair, const BatchPairResult&), called on the launcher thread once the pair's driver has
+// ended, before release(pair) — the pair's device state still exists (the HIP backend takes the alignment report there).
+template <class Backend, class = void>
+struct BackendHasFinished : std::false_type {};
+template <class Backend>
+struct BackendHasFinished<Backend, std::void_t<decltype(std::declval<Backend&>().finished(0, std::declval<const BatchPairResult&>()))>> : std::true_type {};
 
 // The operator interface of driver.hpp as seen by one driver of a batch.
 template <class Backend>
@@ -146,6 +156,7 @@ public:
                 if (p.thread.joinable() && p.finished) {
                     lk.unlock();
                     p.thread.join();
+                    if constexpr (BackendHasFinished<Backend>::value) be_.finished(i, p.result);  // the driver thread has ended: its result is final
                     be_.release(i);
                     lk.lock();
                     p.released = true;

@@ -59,6 +59,7 @@ struct fgoicp_solver {
     std::unique_ptr<GoIcpDriver<HipOps>> driver;
     fgoicp_exchange ex{};
     bool has_ex = false;
+    bool ran = false;  // a run() has succeeded: the driver holds a best transform (fgoicp_solver_alignment)
     ~fgoicp_solver() {  // the context goes with the solver however the solver goes (fgoicp_solver_destroy, a failed or throwing create)
         driver.reset();
         fgoicp_ctx_destroy(ctx);
@@ -172,6 +173,7 @@ static int solver_run_impl(fgoicp_solver* s, float* R_out9, float* t_out3) {
     int rc = s->driver->run();
     if (rc == kDriverExchangeFailed) set_error("fgoicp_solver_run: exchange callback failed");
     if (rc) return rc;
+    s->ran = true;
     Mat3f R;
     Vec3f t;
     s->driver->best_transform(R, t);
@@ -213,6 +215,21 @@ int fgoicp_solver_stats(const fgoicp_solver* s, fgoicp_run_stats* out) {
     out->icp_runs = d.icp_runs; out->icp_iters = d.icp_iters; out->inner_bnb = d.inner_bnb; out->rounds = d.rounds;
     out->seconds_total = d.seconds_total; out->seconds_bnb = d.seconds_bnb; out->seconds_icp = d.seconds_icp; out->initial_icp_sse = d.initial_icp_sse;
     return FGOICP_OK;
+}
+
+int fgoicp_solver_alignment(fgoicp_solver* s, uint32_t* corr_idx_ns, float* dist2_ns, uint8_t* inlier_ns, uint8_t* target_hit_nt, fgoicp_alignment_summary* out) {
+    if (!s) { set_error("fgoicp_solver_alignment: the solver must not be null"); return FGOICP_ERR_INVALID_ARG; }
+    if (!s->ran) { set_error("fgoicp_solver_alignment: fgoicp_solver_run has not succeeded yet: there is no best transform"); return FGOICP_ERR_INVALID_ARG; }
+    if (out && (out->struct_size < sizeof(uint32_t) || out->struct_size > 4096)) { set_error("fgoicp_solver_alignment: set out->struct_size = sizeof(fgoicp_alignment_summary)"); return FGOICP_ERR_INVALID_ARG; }
+    Mat3f R;
+    Vec3f t;
+    s->driver->best_transform(R, t);  // the normalised frame the search ran in (no restore_translation)
+    const float t3[3] = {t.x, t.y, t.z};
+    fgoicp_alignment_summary full{};
+    const int rc = ctx_alignment(s->ctx, R.m, t3, corr_idx_ns, dist2_ns, inlier_ns, target_hit_nt, &full);
+    if (rc) return rc;
+    full.scaling_factor = s->scaling_factor;
+    return alignment_summary_out(full, out, "fgoicp_solver_alignment");
 }
 
 int fgoicp_solver_preproc(const fgoicp_solver* s, float* offs6, float* scale, float* bounds6) {

@@ -6,7 +6,7 @@ import numpy as np
 
 from . import _lib
 from .nodes import from_glm
-from .registration import Registration, _cloud, _fp
+from .registration import Registration, _alignment, _cloud, _fp
 
 
 class FastGoICP:
@@ -52,6 +52,11 @@ class FastGoICP:
         v = C.c_float()
         _lib.check(self._lib.fgoicp_solver_best_error(self._h, C.byref(v)), "fgoicp_solver_best_error")
         return np.float32(v.value)
+
+    def alignment(self):
+        """EXTENSION (fgoicp_solver_alignment): the Alignment at the best transform, after run().  Indices and masks refer to the clouds as
+        passed in; dist2 is in the solver's centred and scaled frame, .distances and .inlier_rmse are in the callers' units."""
+        return _alignment(lambda *a: self._lib.fgoicp_solver_alignment(self._h, *a), "fgoicp_solver_alignment", self.ns, self.nt)
 
     def _transform(self, fn, name):
         R = np.empty(9, np.float32); t = np.empty(3, np.float32)

@@ -37,6 +37,42 @@ def cloud_stats(points):
                 max_abs_centred=float(st.max_abs_centred), rms_radius=float(st.rms_radius))
 
 
+class Alignment:
+    """EXTENSION: the alignment report of fgoicp_alignment / fgoicp_solver_alignment / fgoicp_batch_alignment.  Arrays in the caller's point
+    order: indices (ns,) uint32 — nearest target point of every source point; dist2 (ns,) float32 — its squared distance in the frame the
+    search ran in; inlier (ns,) bool; target_hit (nt,) bool — neighbour of an inlier.  Summary: points, inliers, targets_hit, sse (the bits
+    of compute_sse_error(R, t)), max_inlier_dist2, scaling_factor (1 for a bare Registration, the solver's scale otherwise)."""
+
+    def __init__(self, indices, dist2, inlier, target_hit, summary):
+        self.indices, self.dist2, self.inlier, self.target_hit = indices, dist2, inlier.view(np.bool_), target_hit.view(np.bool_)
+        self.points, self.inliers, self.targets_hit = int(summary.points), int(summary.inliers), int(summary.targets_hit)
+        self.sse, self.max_inlier_dist2 = np.float32(summary.sse), np.float32(summary.max_inlier_dist2)
+        self.scaling_factor = np.float32(summary.scaling_factor)
+
+    @property
+    def fitness(self):
+        """inliers / points (Open3D's evaluate_registration names it so; without a distance threshold every untrimmed point is an inlier)"""
+        return self.inliers / self.points
+
+    @property
+    def inlier_rmse(self):
+        """root mean squared inlier distance in the callers' units"""
+        return float(np.sqrt(np.float64(self.sse) / self.inliers) / np.float64(self.scaling_factor))
+
+    @property
+    def distances(self):
+        """(ns,) float64: distance of every source point to its neighbour in the callers' units, sqrt(dist2) / scaling_factor"""
+        return np.sqrt(self.dist2.astype(np.float64)) / np.float64(self.scaling_factor)
+
+
+def _alignment(call, where, ns, nt):
+    """call(corr, d2, inlier, hit, summary) -> status; the marshalling shared by the three entry points"""
+    idx = np.empty(ns, np.uint32); d2 = np.empty(ns, np.float32); inl = np.empty(ns, np.uint8); hit = np.empty(nt, np.uint8)
+    sm = _lib.AlignmentSummary()
+    _lib.check(call(idx.ctypes.data_as(_lib.c_uint32_p), _fp(d2), inl.ctypes.data_as(_lib.c_uint8_p), hit.ctypes.data_as(_lib.c_uint8_p), C.byref(sm)), where)
+    return Alignment(idx, d2, inl, hit, sm)
+
+
 class Registration:
     """icp::Registration (fgoicp/registration.hpp:49-98) + its NearestNeighborLUT member."""
 
@@ -126,6 +162,13 @@ class Registration:
         out = C.c_float()
         _lib.check(self._lib.fgoicp_sse(self._h, _fp(Rg), _fp(tt), C.byref(out)), "fgoicp_sse")
         return np.float32(out.value)
+
+    def alignment(self, R, t):
+        """EXTENSION (fgoicp_alignment): the Alignment of R*pcs + t against the target — exact correspondences, squared distances, the
+        inlier mask (trimmed contexts: the set_inliers(k) smallest, ties to the lowest index) and the targets the inliers land on."""
+        Rg = to_glm(R)
+        tt = np.ascontiguousarray(t, dtype=np.float32).reshape(3)
+        return _alignment(lambda *a: self._lib.fgoicp_alignment(self._h, _fp(Rg), _fp(tt), *a), "fgoicp_alignment", self.ns, self.nt)
 
     def compute_bounds(self, R, rot_span, tnodes, fix_rot):
         Rg = to_glm(R)

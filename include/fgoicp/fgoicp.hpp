@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "registration.hpp"
 
 namespace icp {
 
@@ -12,7 +13,8 @@ class FastGoICP {
 public:
     // fgoicp.hpp:13 (+ optional schedule: FGOICP_SCHEDULE_SERIAL reproduces the reference's order)
     FastGoICP(std::vector<vec3> pct, std::vector<vec3> pcs, float lut_resolution, float mse_threshold,
-              int schedule = FGOICP_SCHEDULE_SERIAL, int round_width = 1, int device = 0, float trim_fraction = 0.0f) {
+              int schedule = FGOICP_SCHEDULE_SERIAL, int round_width = 1, int device = 0, float trim_fraction = 0.0f)
+        : nt_(pct.size()), ns_(pcs.size()) {
         fgoicp_solver_opts o{schedule, round_width, 0u, device, trim_fraction};
         check_status(fgoicp_solver_create(&pct.data()->x, pct.size(), &pcs.data()->x, pcs.size(), lut_resolution, mse_threshold, &o, &s_),
                      "fgoicp_solver_create");
@@ -38,6 +40,16 @@ public:
     // not in the reference: false = every subcube is evaluated in full, as kernComputeBounds does (default: the inner BnBs tell the bounds
     // operator what they do not need to know, fgoicp_bounds_submit_cut — same trajectory, counters and result)
     void set_early_exit(bool on) { check_status(fgoicp_solver_set_early_exit(s_, on ? 1 : 0), "fgoicp_solver_set_early_exit"); }
+    // not in the reference (EXTENSION): correspondences, residuals and the inlier set at the best transform, after run()
+    // (fgoicp_solver_alignment).  Indices and masks refer to the clouds as passed in; dist2 is in the solver's centred and scaled
+    // frame, Alignment::distance / inlier_rmse are in the callers' units.
+    Alignment alignment() const {
+        Alignment a;
+        a.indices.resize(ns_); a.dist2.resize(ns_); a.inlier.resize(ns_); a.target_hit.resize(nt_);
+        a.summary.struct_size = sizeof(a.summary);
+        check_status(fgoicp_solver_alignment(s_, a.indices.data(), a.dist2.data(), a.inlier.data(), a.target_hit.data(), &a.summary), "fgoicp_solver_alignment");
+        return a;
+    }
     fgoicp_run_stats stats() const { fgoicp_run_stats st{}; check_status(fgoicp_solver_stats(s_, &st), "fgoicp_solver_stats"); return st; }
     fgoicp_solver* handle() const { return s_; }
     // the reference's own lines while the search runs (fgoicp.cpp:15-17 Info, :85-87 Debug), from the driver's log events
@@ -49,6 +61,7 @@ public:
         else Logger(LogLevel::Debug) << "New best error: " << sse << "\n\tRotation:\n" << R << "\n\tTranslation: " << t;
     }
 private:
+    size_t nt_ = 0, ns_ = 0;
     fgoicp_solver* s_ = nullptr;
 };
 

@@ -3,6 +3,8 @@
 // HIP context behind include/fgoicp_amd.h.  Non-copyable (the reference's versions double-free on copy).
 #pragma once
 #include <array>
+#include <cmath>
+#include <cstdint>
 #include <tuple>
 #include <utility>
 
@@ -38,6 +40,19 @@ private:
     fgoicp_ctx* ctx_ = nullptr;
 };
 
+// EXTENSION (ours; the reference ends in (R, t) and the best error): the alignment report of fgoicp_alignment /
+// fgoicp_solver_alignment.  Arrays in the caller's point order; dist2 in the frame the search ran in.
+struct Alignment {
+    std::vector<uint32_t> indices;     // ns: nearest target point of every source point (lowest index among sqrt-ties, icp3d.cu:20-25)
+    std::vector<float> dist2;          // ns: its squared distance
+    std::vector<uint8_t> inlier;       // ns: 1 = counted by the optimum (all ones unless trimmed)
+    std::vector<uint8_t> target_hit;   // nt: 1 = neighbour of an inlier
+    fgoicp_alignment_summary summary{};
+    double fitness() const { return summary.points ? (double)summary.inliers / (double)summary.points : 0.0; }
+    double inlier_rmse() const { return summary.inliers ? std::sqrt((double)summary.sse / (double)summary.inliers) / (double)summary.scaling_factor : 0.0; }
+    double distance(size_t i) const { return std::sqrt((double)dist2[i]) / (double)summary.scaling_factor; }  // in the callers' units
+};
+
 class Registration {
 public:
     // registration.hpp:68
@@ -69,6 +84,15 @@ public:
         check_status(fgoicp_bounds_batch(ctx_, rnode.q.R.data(), rnode.span, tn4.data(), (int)B, fix_rot ? 1 : 0, lb.data(), ub.data()),
                      "fgoicp_bounds_batch");
         return {lb, ub};
+    }
+
+    // EXTENSION: correspondences, residuals and the inlier set of R*pcs + t (fgoicp_alignment)
+    Alignment alignment(mat3 R, vec3 t) const {
+        Alignment a;
+        a.indices.resize(ns); a.dist2.resize(ns); a.inlier.resize(ns); a.target_hit.resize(nt);
+        a.summary.struct_size = sizeof(a.summary);
+        check_status(fgoicp_alignment(ctx_, R.data(), &t.x, a.indices.data(), a.dist2.data(), a.inlier.data(), a.target_hit.data(), &a.summary), "fgoicp_alignment");
+        return a;
     }
 
     fgoicp_ctx* handle() const { return ctx_; }

@@ -162,6 +162,26 @@ int fgoicp_ctx_cut_stats(fgoicp_ctx* ctx, uint64_t* items_offered, uint64_t* ite
  * neighbour SSE of R*src + t against the target. */
 int fgoicp_sse(fgoicp_ctx* ctx, const float* R9, const float* t3, float* sse_out);
 
+/*
+ * EXTENSION — the alignment report (no reference counterpart: the reference ends in (R, t) and the best error).  For R*src + t: per
+ * source point the exact nearest target point (index into the target as handed to the create call; the tie rule of icp3d.cu:20-25 —
+ * square roots compared, lowest index) and its squared distance, the inlier mask (all ones; on a trimmed context the `inliers` smallest
+ * squared distances, ties at the cut to the lowest source indices), and per target point whether it is the neighbour of an inlier.
+ * Every output pointer may be NULL; arrays are in the caller's point order (corr_idx_ns, dist2_ns, inlier_ns: ns entries;
+ * target_hit_nt: nt).  On a trimmed context the outliers get their true neighbour too.  Distances are in the frame of the clouds the
+ * context holds (a solver's are centred and scaled: scaling_factor).  The call leaves the context as it found it.
+ */
+typedef struct fgoicp_alignment_summary {
+    uint32_t struct_size;      /* IN: sizeof(fgoicp_alignment_summary) as the CALLER was compiled; no byte beyond it is written, 0 is refused */
+    uint64_t points, inliers;  /* ns; ns or the trimmed k */
+    uint64_t targets_hit;      /* distinct target points that are the neighbour of an inlier */
+    float sse;                 /* == fgoicp_sse(ctx, R, t), bit for bit */
+    float max_inlier_dist2;
+    float scaling_factor;      /* 1 for a bare context; the solver's (fgoicp_solver_preproc) otherwise: sqrt(dist2) / scaling_factor is in the callers' units */
+} fgoicp_alignment_summary;
+int fgoicp_alignment(fgoicp_ctx* ctx, const float* R9, const float* t3, uint32_t* corr_idx_ns, float* dist2_ns, uint8_t* inlier_ns,
+                     uint8_t* target_hit_nt, fgoicp_alignment_summary* out);
+
 /* Replaces IterativeClosestPoint3D(reg, pct, pcs, max_iter, thr, R, t) + run()
  * (fgoicp/icp3d.hpp:30-35, icp3d.cu:55-108).  Returns the reference's Result_t {sse, R, t}
  * plus the number of loop iterations executed. */
@@ -311,6 +331,12 @@ int fgoicp_solver_best_error(const fgoicp_solver* s, float* sse_out);
 int fgoicp_solver_best_transform(const fgoicp_solver* s, float* R9, float* t3);
 int fgoicp_solver_last_transform(const fgoicp_solver* s, float* R9, float* t3);
 int fgoicp_solver_stats(const fgoicp_solver* s, fgoicp_run_stats* out);
+/* EXTENSION: fgoicp_alignment at the best transform the solver holds (the normalised one, before restore_translation), after a
+ * successful fgoicp_solver_run — before that the call is refused (FGOICP_ERR_INVALID_ARG).  Indices and masks refer to the clouds as
+ * handed to fgoicp_solver_create; distances are in the solver's centred and scaled frame, out->scaling_factor is its scale.  A later
+ * fgoicp_solver_run returns what it returned before.  On a multi-GPU run every rank answers from its own context. */
+int fgoicp_solver_alignment(fgoicp_solver* s, uint32_t* corr_idx_ns, float* dist2_ns, uint8_t* inlier_ns, uint8_t* target_hit_nt,
+                            fgoicp_alignment_summary* out);
 /* Pre-processing results (tests): offs6 = {offset_pcs, offset_pct}, bounds6 as in ctx_create. */
 int fgoicp_solver_preproc(const fgoicp_solver* s, float* offs6, float* scale, float* bounds6);
 /* Statistics of a raw cloud, host side, no device needed (TODO.md:7 of the reference: "compute point clouds' stats"): what the
@@ -416,6 +442,8 @@ typedef struct fgoicp_batch_opts {
     int max_live;                /* pairs whose device state (context: LUT, tree, source order) exists at once; 0 = as many as device memory allows, at most 16 */
     const float* trim_fractions; /* n entries, pair i trimmed as fgoicp_solver_create trims with solver.trim_fraction = trim_fractions[i] (0 = untrimmed);
                                     NULL, or a struct_size that ends before this member: no pair is trimmed.  Read by fgoicp_batch_create only */
+    int alignment;               /* != 0: the run keeps every pair's alignment report (fgoicp_batch_alignment) on the host: 9 bytes per source point, 1 per target
+                                    point.  Appended within revision 2: 0 for a caller built with the shorter struct (struct_size) */
 } fgoicp_batch_opts;
 /* Copies the clouds and pre-processes every pair on the host (centre, scale, bounds, inlier count, as fgoicp_solver_create); creates no
  * device state.  Refuses n <= 0, a null or empty cloud, solver.trim_fraction != 0, a trim_fractions entry that is NaN, negative or >= 1,
@@ -428,6 +456,11 @@ int fgoicp_batch_create(const fgoicp_batch_pair* pairs, int n, const fgoicp_batc
 int fgoicp_batch_run(fgoicp_batch* b, float* R_out9n, float* t_out3n, int* status_n);
 int fgoicp_batch_best_error(const fgoicp_batch* b, int i, float* sse_out);
 int fgoicp_batch_stats(const fgoicp_batch* b, int i, fgoicp_run_stats* out);
+/* Pair i's alignment report as fgoicp_solver_alignment gives it for that pair alone, bit for bit, whatever the window, the order or the
+ * other pairs: computed when the pair finished, before its context was released, and kept on the host.  Refused (FGOICP_ERR_INVALID_ARG)
+ * when fgoicp_batch_opts.alignment was 0, before fgoicp_batch_run, and for a pair whose status is not FGOICP_OK. */
+int fgoicp_batch_alignment(const fgoicp_batch* b, int i, uint32_t* corr_idx_ns, float* dist2_ns, uint8_t* inlier_ns, uint8_t* target_hit_nt,
+                           fgoicp_alignment_summary* out);
 /* Launches of the last run: fused bounds launches (one per LUT class per tick, more for a class of more than 2^24 work items, and per
  * arena fill for trimmed pairs; neither the finalize nor the trimmed selection counted) and lock-step ICP iterations (one host
  * turn-around each, shared by every active ICP run). */
