@@ -70,6 +70,13 @@ class BatchOpts(C.Structure):
                 ("alignment", C.c_int)]  # != 0: the run keeps every pair's alignment report (fgoicp_batch_alignment)
 
 
+class BatchOptsInformation(BatchOpts):
+    """fgoicp_batch_opts whole: BatchOpts is the struct as first published with `alignment` (48 bytes, still accepted: struct_size); the members
+    appended since start behind its tail padding (reserved0 in the header)."""
+    _fields_ = [("information", C.c_int),  # != 0: the run keeps every pair's information matrix (fgoicp_batch_information)
+                ("information_max_distance", C.c_float)]  # callers' units; <= 0: no threshold
+
+
 class AlignmentSummary(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("points", C.c_uint64), ("inliers", C.c_uint64), ("targets_hit", C.c_uint64), ("sse", C.c_float),
                 ("max_inlier_dist2", C.c_float), ("scaling_factor", C.c_float)]
@@ -77,6 +84,15 @@ class AlignmentSummary(C.Structure):
     def __init__(self):
         super().__init__()
         self.struct_size = C.sizeof(AlignmentSummary)  # the library writes no byte beyond it
+
+
+class Information(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("points", C.c_uint64), ("correspondences", C.c_uint64), ("sum_dist2", C.c_double), ("sum_q", C.c_double * 3),
+                ("sum_qq", C.c_double * 6), ("info", C.c_double * 36), ("max_dist2", C.c_float), ("scaling_factor", C.c_float)]
+
+    def __init__(self):
+        super().__init__()
+        self.struct_size = C.sizeof(Information)  # the library writes no byte beyond it
 
 
 SCHEDULE_SERIAL = 0
@@ -112,6 +128,11 @@ _SIGS = {
     "fgoicp_alignment": (C.c_int, [C.c_void_p, c_float_p, c_float_p, c_uint32_p, c_float_p, c_uint8_p, c_uint8_p, C.POINTER(AlignmentSummary)]),
     "fgoicp_solver_alignment": (C.c_int, [C.c_void_p, c_uint32_p, c_float_p, c_uint8_p, c_uint8_p, C.POINTER(AlignmentSummary)]),
     "fgoicp_batch_alignment": (C.c_int, [C.c_void_p, C.c_int, c_uint32_p, c_float_p, c_uint8_p, c_uint8_p, C.POINTER(AlignmentSummary)]),
+    "fgoicp_information": (C.c_int, [C.c_void_p, c_float_p, c_float_p, C.c_float, C.POINTER(Information)]),
+    "fgoicp_solver_information": (C.c_int, [C.c_void_p, C.c_float, C.POINTER(Information)]),
+    "fgoicp_batch_information": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Information)]),
+    "fgoicp_information_from_moments": (C.c_int, [C.c_uint64, C.POINTER(C.c_double), C.POINTER(C.c_double), c_float_p, C.c_float, C.POINTER(C.c_double),
+                                                  C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "fgoicp_icp": (C.c_int, [C.c_void_p, c_float_p, c_float_p, C.c_size_t, C.c_float, c_float_p, c_float_p, c_float_p, c_int_p]),
     "fgoicp_icp_batch": (C.c_int, [C.c_void_p, C.c_int, c_float_p, c_float_p, C.c_size_t, C.c_float, c_float_p, c_float_p, c_float_p, c_int_p]),
     "fgoicp_procrustes": (C.c_int, [C.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p, c_int_p]),

@@ -6,15 +6,16 @@ import numpy as np
 
 from . import _lib
 from .nodes import from_glm
-from .registration import _alignment, _cloud, _fp
+from .registration import _alignment, _cloud, _fp, _information
 
 
 class FastGoICPBatch:
     """pairs: iterable of (pct, pcs), (pct, pcs, lut_resolution, mse_threshold) or (pct, pcs, lut_resolution, mse_threshold, trim_fraction);
-    the defaults below apply to what a pair leaves out.  trim_fraction: as FastGoICP's, per pair (0 = untrimmed)."""
+    the defaults below apply to what a pair leaves out.  trim_fraction: as FastGoICP's, per pair (0 = untrimmed).  information: False, True
+    (every pair's Information without a distance threshold) or a distance in the callers' units."""
 
     def __init__(self, pairs, lut_resolution=0.005, mse_threshold=1e-3, schedule=_lib.SCHEDULE_SERIAL, round_width=1, device=0, flags=0,
-                 max_live=0, trim_fraction=0.0, alignment=False):
+                 max_live=0, trim_fraction=0.0, alignment=False, information=False):
         self._lib = _lib.load()
         self._clouds = []
         self._sizes = []
@@ -28,8 +29,9 @@ class FastGoICPBatch:
             self._sizes.append((len(pcs), len(pct)))
             arr[i] = _lib.BatchPair(_fp(pct), len(pct), _fp(pcs), len(pcs), float(lr), float(mt))
         self.n = len(pairs)
-        opts = _lib.BatchOpts(C.sizeof(_lib.BatchOpts), _lib.SolverOpts(int(schedule), int(round_width), int(flags), int(device), 0.0), int(max_live),
-                              _fp(trim), int(bool(alignment)))
+        opts = _lib.BatchOptsInformation(C.sizeof(_lib.BatchOptsInformation), _lib.SolverOpts(int(schedule), int(round_width), int(flags), int(device), 0.0), int(max_live),
+                              _fp(trim), int(bool(alignment)), int(information is not False and information is not None),
+                              0.0 if isinstance(information, bool) or information is None else float(information))
         self._h = C.c_void_p()
         _lib.check(self._lib.fgoicp_batch_create(arr, self.n, C.byref(opts), C.byref(self._h)), "fgoicp_batch_create")
         self._clouds = None
@@ -72,6 +74,11 @@ class FastGoICPBatch:
         returns for that pair alone."""
         ns, nt = self._sizes[i]
         return _alignment(lambda *a: self._lib.fgoicp_batch_alignment(self._h, int(i), *a), "fgoicp_batch_alignment", ns, nt)
+
+    def information(self, i):
+        """EXTENSION (fgoicp_batch_information; needs information=True or a distance): pair i's Information at its best transform, what
+        FastGoICP.information(distance) returns for that pair alone."""
+        return _information(lambda out: self._lib.fgoicp_batch_information(self._h, int(i), out), "fgoicp_batch_information")
 
     def launches(self):
         """-> (fused bounds launches, lock-step ICP iterations) of the last run."""

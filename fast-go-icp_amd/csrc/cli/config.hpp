@@ -110,7 +110,7 @@ inline TomlTable parse_toml(const std::string& path) {
 // Config — src/utilities.hpp:18-107 (same keys, defaults and clamps; `seed` is an addition)
 // ------------------------------------------------------------------------------------------
 struct Config {
-    struct IO { std::string target, source, output, visualization, alignment; } io;  // alignment: EXTENSION, optional (write_alignment_txt)
+    struct IO { std::string target, source, output, visualization, alignment, information; } io;  // alignment, information: EXTENSION, optional (write_alignment_txt, write_information_txt)
     struct Params {
         bool trim = false;
         float target_subsample = 1.0f, source_subsample = 1.0f, lut_resolution = 0.005f, mse_threshold = 1e-3f;
@@ -119,6 +119,7 @@ struct Config {
         int round_width = 1;
         float trim_fraction = 0.0f;  // EXTENSION: > 0 enables trimmed Go-ICP; `trim` itself stays parsed-and-ignored as upstream
         int gpus = 1;                // EXTENSION: > 1 shards the outer BnB over that many GPUs of this node (one host thread each, RCCL)
+        float information_distance = 0.0f;  // EXTENSION: distance threshold of io.information in the files' units (absent or 0: none)
     } params;
 
     explicit Config(const std::string& toml_filepath) {
@@ -154,6 +155,7 @@ struct Config {
         io.output = str("io", "output", "");                // declared in test/bunny.toml:10, unparsed upstream
         io.visualization = str("io", "visualization", "");  // declared in test/bunny.toml:11, unparsed upstream
         io.alignment = str("io", "alignment", "");          // EXTENSION: where the alignment report goes ("" = none; not part of the printed summary)
+        io.information = str("io", "information", "");      // EXTENSION: where the information matrix goes ("" = none; not part of the printed summary)
         auto clampf0 = [](float x) { return x < 0.0f ? 0.0f : (x > 0.9f ? 0.9f : x); };
         if (tbl.count("params")) {
             params.trim = boolean("params", "trim", false);
@@ -166,6 +168,8 @@ struct Config {
             params.round_width = (int)num("params", "round_width", 1);
             params.trim_fraction = clampf0((float)num("params", "trim_fraction", 0.0));
             params.gpus = std::max(1, (int)num("params", "gpus", 1));
+            params.information_distance = (float)num("params", "information_distance", 0.0);
+            if (!(params.information_distance > 0.0f)) params.information_distance = 0.0f;
             auto clampf = [](float x, float lo, float hi) { return x < hi ? (x > lo ? x : lo) : hi; };
             params.target_subsample = clampf(params.target_subsample, 1e-5f, 1.0f);  // utilities.hpp:101-104
             params.source_subsample = clampf(params.source_subsample, 1e-5f, 1.0f);
@@ -368,6 +372,21 @@ inline void write_alignment_txt(const std::string& path, const std::vector<icp::
     f << "# x y z target_index distance inlier\n";
     for (size_t i = 0; i < src.size(); ++i)
         f << src[i].x << " " << src[i].y << " " << src[i].z << " " << idx[i] << " " << std::sqrt((double)dist2[i]) / scale << " " << (int)inlier[i] << "\n";
+}
+
+// io.information (EXTENSION): the information matrix of the run (fgoicp_solver_information / fgoicp_batch_information) in the files' frame.
+// One '#' line — correspondences, fitness, inlier_rmse and the distance used (inf: none) — then the six rows of the matrix, six numbers each
+// at precision 17 (a double read back from it is the double written), twist order (wx, wy, wz, vx, vy, vz).
+inline void write_information_txt(const std::string& path, const fgoicp_information_t& s, float distance) {
+    std::ofstream f(path);
+    if (!f) throw std::runtime_error("Unable to write " + path);
+    f.precision(9);
+    f << "# information: correspondences = " << s.correspondences << ", fitness = " << (s.points ? (double)s.correspondences / (double)s.points : 0.0)
+      << ", inlier_rmse = " << (s.correspondences ? std::sqrt(s.sum_dist2 / (double)s.correspondences) / (double)s.scaling_factor : 0.0)
+      << ", distance = " << (distance > 0.0f ? distance : INFINITY) << "\n";
+    f.precision(17);
+    for (int r = 0; r < 6; ++r)
+        for (int k = 0; k < 6; ++k) f << s.info[6 * r + k] << (k == 5 ? "\n" : " ");
 }
 
 inline void write_visualization_ply(const std::string& path, const std::vector<icp::vec3>& tgt, const std::vector<icp::vec3>& src,

@@ -63,6 +63,15 @@ static int run_batch(const std::string& list_file) {
     o.solver = fgoicp_solver_opts{schedule, c0.params.round_width, 0u, 0, 0.0f};
     o.trim_fractions = trim.data();
     for (const cli::Config& c : configs) o.alignment |= c.io.alignment.empty() ? 0 : 1;  // the reports are kept only if a config asks for one
+    for (const cli::Config& c : configs) {  // ... and the information matrices; a batch has one distance threshold
+        if (c.io.information.empty()) continue;
+        if (o.information && c.params.information_distance != o.information_max_distance) {
+            icp::Logger(icp::LogLevel::Error) << "--batch: every config of a batch that names io.information must have the same params.information_distance";
+            return 1;
+        }
+        o.information = 1;
+        o.information_max_distance = c.params.information_distance;
+    }
     fgoicp_batch* b = nullptr;
     icp::check_status(fgoicp_batch_create(pairs.data(), (int)n, &o, &b), "fgoicp_batch_create");
     std::vector<float> R9(9 * n), t3(3 * n);
@@ -93,6 +102,12 @@ static int run_batch(const std::string& list_file) {
             sm.struct_size = sizeof(sm);
             icp::check_status(fgoicp_batch_alignment(b, (int)i, idx.data(), d2.data(), inl.data(), nullptr, &sm), "fgoicp_batch_alignment");
             cli::write_alignment_txt(c.io.alignment, pcs[i], idx.data(), d2.data(), inl.data(), sm);
+        }
+        if (!c.io.information.empty()) {
+            fgoicp_information_t inf{};
+            inf.struct_size = sizeof(inf);
+            icp::check_status(fgoicp_batch_information(b, (int)i, &inf), "fgoicp_batch_information");
+            cli::write_information_txt(c.io.information, inf, c.params.information_distance);
         }
     }
     fgoicp_batch_destroy(b);
@@ -164,6 +179,15 @@ int main(int argc, char* argv[]) {
         icp::check_status(fgoicp_solver_alignment(s, idx.data(), d2.data(), inl.data(), nullptr, &sm), "fgoicp_solver_alignment");
         cli::write_alignment_txt(config.io.alignment, pcs_in, idx.data(), d2.data(), inl.data(), sm);
     };
+    // io.information: the information matrix at the best transform, in the files' frame
+    auto write_information = [&](fgoicp_solver* s) {
+        if (config.io.information.empty()) return;
+        fgoicp_information_t inf{};
+        inf.struct_size = sizeof(inf);
+        const float d = config.params.information_distance;
+        icp::check_status(fgoicp_solver_information(s, d > 0.0f ? d : INFINITY, &inf), "fgoicp_solver_information");
+        cli::write_information_txt(config.io.information, inf, d);
+    };
     if (gpus > 1) {
         // EXTENSION: one host thread + one solver per GPU (include/fgoicp_amd.h, fgoicp_multi_*).  params.schedule = "serial" (the
         // default) keeps the reference's exact trajectory and deals the inner BnBs of every speculative evaluation over the GPUs;
@@ -198,6 +222,7 @@ int main(int argc, char* argv[]) {
         }
         icp::check_status(fgoicp_solver_best_error(fgoicp_multi_solver(m, 0), &best_error), "fgoicp_solver_best_error");
         write_alignment(fgoicp_multi_solver(m, 0));
+        write_information(fgoicp_multi_solver(m, 0));
         fgoicp_multi_destroy(m);
         icp::Logger(icp::LogLevel::Info) << "Searching over! Best Error: " << best_error << "\n\tRotation:\n" << R << "\n\tTranslation: " << t;  // fgoicp.cpp:25-27
     } else {
@@ -209,6 +234,7 @@ int main(int argc, char* argv[]) {
         st = fgoicp.stats();
         best_error = fgoicp.get_best_error();
         write_alignment(fgoicp.handle());
+        write_information(fgoicp.handle());
     }
     icp::Logger(icp::LogLevel::Debug) << "Subcubes: " << st.trans_cubes << ", rotation cubes: " << st.rot_cubes << ", ICP runs: " << st.icp_runs;
     icp::Logger(icp::LogLevel::Info) << "Fast Go-ICP finished, time elapsed: " << std::fixed << std::setprecision(3) << elapsed_seconds.count() << " seconds";

@@ -486,8 +486,8 @@ int ctx_sse(fgoicp_ctx* c, const float* R9, const float* t3, float* sse_out, con
 //   4. device order -> caller order, target marks and the integer summary (launch_align_scatter).
 // Everything written is scratch that every other path fills before it reads (d_min_bits, d_work, d_thr_bits, d_sel, d_eq, d_use, the
 // pinned sums) or the report's own allocation; d_first_idx / d_first_idx2, the seeds of a later ICP pass, are not touched.
-int ctx_alignment(fgoicp_ctx* c, const float* R9, const float* t3, uint32_t* corr_idx, float* dist2, uint8_t* inlier, uint8_t* target_hit,
-                  fgoicp_alignment_summary* out) {
+// The device half: everything above is enqueued on lane 0's stream, nothing is waited for.
+static int alignment_enqueue(fgoicp_ctx* c, const float* R9, const float* t3) {
     HIPCHK(hipSetDevice(c->device));
     fgoicp_ctx::IcpLane& L = c->lanes[0];
     fgoicp_ctx::AlignScratch& A = c->align;
@@ -501,7 +501,8 @@ int ctx_alignment(fgoicp_ctx* c, const float* R9, const float* t3, uint32_t* cor
         A.nt16 = (c->nt + 15) & ~(size_t)15;
         const size_t nblk = (c->ns + kBlock - 1) / kBlock;
         const size_t o_idx = 0, o_corr = o_idx + up(4 * c->ns), o_d2 = o_corr + up(4 * c->ns), o_inl = o_d2 + up(4 * c->ns), o_hit = o_inl + up(c->ns),
-                     o_part = o_hit + up(A.nt16), o_sum = o_part + up(sizeof(uint2) * nblk), total = o_sum + 256;
+                     o_part = o_hit + up(A.nt16), o_sum = o_part + up(sizeof(uint2) * nblk), o_rows = o_sum + 256, o_info = o_rows + up(sizeof(AlignInfoRow) * nblk),
+                     total = o_info + 256;
         HIPCHK(hipMalloc(&A.base, total));
         char* b = static_cast<char*>(A.base);
         A.d_idx = reinterpret_cast<uint32_t*>(b + o_idx);
@@ -511,6 +512,8 @@ int ctx_alignment(fgoicp_ctx* c, const float* R9, const float* t3, uint32_t* cor
         A.d_hit = reinterpret_cast<unsigned char*>(b + o_hit);
         A.d_partials = reinterpret_cast<uint2*>(b + o_part);
         A.d_sum = reinterpret_cast<uint32_t*>(b + o_sum);
+        A.d_info_rows = reinterpret_cast<AlignInfoRow*>(b + o_rows);
+        A.d_info = reinterpret_cast<unsigned long long*>(b + o_info);
     }
     hipStream_t st = L.stream;
     const bool skip = c->trim_skip;
@@ -535,7 +538,13 @@ int ctx_alignment(fgoicp_ctx* c, const float* R9, const float* t3, uint32_t* cor
     HIPCHK(hipMemsetAsync(A.d_hit, 0, A.nt16, st));
     launch_align_scatter(A.d_idx, L.d_min_bits, use, c->d_orig_of_slot, ns, nt, A.d_corr, A.d_d2, A.d_inl, A.d_hit, A.nt16, A.d_partials, A.d_sum, st);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(st));
+    return FGOICP_OK;
+}
+// The copy-out half: waits for lane 0's stream and hands the report over; every output may be null.
+static int alignment_copy_out(fgoicp_ctx* c, uint32_t* corr_idx, float* dist2, uint8_t* inlier, uint8_t* target_hit, fgoicp_alignment_summary* out) {
+    fgoicp_ctx::IcpLane& L = c->lanes[0];
+    fgoicp_ctx::AlignScratch& A = c->align;
+    HIPCHK(hipStreamSynchronize(L.stream));
     uint32_t sum3[3] = {0, 0, 0};
     HIPCHK(hipMemcpy(sum3, A.d_sum, sizeof(sum3), hipMemcpyDeviceToHost));
     if (corr_idx) HIPCHK(hipMemcpy(corr_idx, A.d_corr, sizeof(uint32_t) * c->ns, hipMemcpyDeviceToHost));
@@ -551,6 +560,45 @@ int ctx_alignment(fgoicp_ctx* c, const float* R9, const float* t3, uint32_t* cor
         out->scaling_factor = 1.0f;
     }
     return FGOICP_OK;
+}
+int ctx_alignment(fgoicp_ctx* c, const float* R9, const float* t3, uint32_t* corr_idx, float* dist2, uint8_t* inlier, uint8_t* target_hit,
+                  fgoicp_alignment_summary* out) {
+    const int rc = alignment_enqueue(c, R9, t3);
+    return rc ? rc : alignment_copy_out(c, corr_idx, dist2, inlier, target_hit, out);
+}
+
+// EXTENSION: the moments behind the information matrix (fgoicp_information), enqueued behind the report's device half on the same stream:
+// one scan of the report's caller-order arrays (the report has just written them), one gather of the target per counted point.  Writes
+// the report's own allocation only.
+static int information_enqueue(fgoicp_ctx* c, float max_dist2) {
+    fgoicp_ctx::AlignScratch& A = c->align;
+    launch_align_info(A.d_inl, A.d_d2, A.d_corr, c->d_tgt, (int)c->ns, (int)c->nt, max_dist2, A.d_info_rows, A.d_info, c->lanes[0].stream);
+    HIPCHK(hipGetLastError());
+    return FGOICP_OK;
+}
+static int information_copy_out(fgoicp_ctx* c, InfoMoments* m) {
+    HIPCHK(hipStreamSynchronize(c->lanes[0].stream));
+    unsigned long long h[1 + kAlignInfoTerms];
+    HIPCHK(hipMemcpy(h, c->align.d_info, sizeof(h), hipMemcpyDeviceToHost));
+    double v[kAlignInfoTerms];
+    std::memcpy(v, h + 1, sizeof(v));
+    m->n = h[0];
+    for (int k = 0; k < 3; ++k) m->sum_q[k] = v[k];
+    for (int k = 0; k < 6; ++k) m->sum_qq[k] = v[3 + k];
+    m->sum_d2 = v[9];
+    return FGOICP_OK;
+}
+int ctx_information(fgoicp_ctx* c, const float* R9, const float* t3, float max_dist2, InfoMoments* m) {
+    int rc = alignment_enqueue(c, R9, t3);
+    if (!rc) rc = information_enqueue(c, max_dist2);
+    return rc ? rc : information_copy_out(c, m);
+}
+int ctx_alignment_information(fgoicp_ctx* c, const float* R9, const float* t3, uint32_t* corr_idx, float* dist2, uint8_t* inlier, uint8_t* target_hit,
+                              fgoicp_alignment_summary* out, float max_dist2, InfoMoments* m) {
+    int rc = alignment_enqueue(c, R9, t3);
+    if (!rc) rc = information_enqueue(c, max_dist2);
+    if (!rc) rc = alignment_copy_out(c, corr_idx, dist2, inlier, target_hit, out);
+    return rc ? rc : information_copy_out(c, m);
 }
 
 // IterativeClosestPoint3D::procrustes() on L.d_work — icp3d.cu:140-172.  The device half (enqueue only): correspondences
@@ -1746,6 +1794,18 @@ int fgoicp_alignment(fgoicp_ctx* c, const float* R9, const float* t3, uint32_t* 
     fgoicp_alignment_summary full{};
     const int rc = ctx_alignment(c, R9, t3, corr_idx_ns, dist2_ns, inlier_ns, target_hit_nt, &full);
     return rc ? rc : alignment_summary_out(full, out, "fgoicp_alignment");
+}
+
+int fgoicp_information(fgoicp_ctx* c, const float* R9, const float* t3, float max_dist2, fgoicp_information_t* out) {
+    if (!c || !R9 || !t3) { set_error("fgoicp_information: the context, R and t must not be null"); return FGOICP_ERR_INVALID_ARG; }
+    if (!information_size_ok(out)) { set_error("fgoicp_information: out must not be null and out->struct_size = sizeof(fgoicp_information_t)"); return FGOICP_ERR_INVALID_ARG; }
+    if (!(max_dist2 >= 0.0f)) { set_error("fgoicp_information: max_dist2 must be >= 0 (+inf: no threshold)"); return FGOICP_ERR_INVALID_ARG; }
+    InfoMoments m;
+    const int rc = ctx_information(c, R9, t3, max_dist2, &m);
+    if (rc) return rc;
+    fgoicp_information_t full;
+    information_fill(full, c->ns, m, nullptr, 1.0f, max_dist2);
+    return information_out(full, out, "fgoicp_information");
 }
 
 int fgoicp_icp(fgoicp_ctx* c, const float* R0, const float* t0, size_t max_iter, float thr, float* sse_out, float* R_out9, float* t_out3,

@@ -13,6 +13,7 @@
 
 #include "../host/math3.hpp"
 #include "../host/abi_guard.hpp"
+#include "../host/information.hpp"
 #include "bvh.hpp"
 #include "kernels.hpp"
 
@@ -109,7 +110,8 @@ struct fgoicp_ctx {
     float tgt_box6[6] = {0, 0, 0, 0, 0, 0};  // the target's bounding box computed from the points (trimmed search: nn_prep_kernel)
     uint32_t* d_orig_of_slot = nullptr;      // caller index of every device slot (ties at the inlier cut; the alignment report)
 
-    // the alignment report (ctx_alignment): one allocation on the first call, 13 bytes per source point and one per target point
+    // the alignment report (ctx_alignment) and the information moments (ctx_information): one allocation on the first call, 13 bytes per source
+    // point, one per target point and 88 per block of kBlock source points
     struct AlignScratch {
         void* base = nullptr;
         uint32_t* d_idx = nullptr;               // correspondences, device order
@@ -119,6 +121,8 @@ struct fgoicp_ctx {
         uint2* d_partials = nullptr;
         uint32_t* d_sum = nullptr;               // {inliers, targets hit, bits of the largest inlier squared distance}
         size_t nt16 = 0;
+        fgoicp::AlignInfoRow* d_info_rows = nullptr;   // the moments: one row of partial sums per block of the report
+        unsigned long long* d_info = nullptr;    // {count, the bits of ten sums} (launch_align_info)
     } align;
 
     // exact-NN / ICP scratch, one set per lane: ICP runs on different lanes may be in flight together (ctx_icp_batch).  Lane 0 is
@@ -188,6 +192,12 @@ int ctx_sse(fgoicp_ctx* c, const float* R9, const float* t3, float* sse_out, con
 // fgoicp_alignment on lane 0; every output may be null.  `out` is filled whole (scaling_factor = 1), whatever its struct_size says.
 int ctx_alignment(fgoicp_ctx* c, const float* R9, const float* t3, uint32_t* corr_idx, float* dist2, uint8_t* inlier, uint8_t* target_hit,
                   fgoicp_alignment_summary* out);
+// fgoicp_information on lane 0: the report's device half (shared with ctx_alignment), then the moments of the counted correspondences
+// (launch_align_info).  max_dist2 must have been checked (not NaN, >= 0).  Context frame.
+int ctx_information(fgoicp_ctx* c, const float* R9, const float* t3, float max_dist2, InfoMoments* m);
+// both from one pass of the report's device half (fgoicp_batch with both options on): ctx_alignment's outputs and ctx_information's
+int ctx_alignment_information(fgoicp_ctx* c, const float* R9, const float* t3, uint32_t* corr_idx, float* dist2, uint8_t* inlier, uint8_t* target_hit,
+                              fgoicp_alignment_summary* out, float max_dist2, InfoMoments* m);
 // a summary handed to a caller: no byte beyond the struct_size the caller set is written (0, or less than the size field itself: refused)
 inline int alignment_summary_out(const fgoicp_alignment_summary& full, fgoicp_alignment_summary* out, const char* where) {
     if (!out) return FGOICP_OK;

@@ -2469,4 +2469,114 @@ void launch_align_scatter(const uint32_t* idx, const uint32_t* min_bits, const u
     hipLaunchKernelGGL(align_fold_kernel, dim3(1), dim3(1024), 0, s, target_hit, nt16, partials, nb, summary3);
 }
 
+// ---------------------------------------------------------------------------------------------
+// The information matrix of a registration (fgoicp_information): the moments of the COUNTED correspondences of the report above — the
+// caller indices i with inlier[i] != 0, d2[i] <= max_d2 and corr[i] < nt.  One thread per caller index: three coalesced reads of the
+// report's arrays (9 bytes), one 16-byte gather of the target point q the correspondence names, the ten terms {q (3), q q^T (6, in the
+// order xx xy xz yy yz zz), d2} in fp64 — a product of two floats is exact in a double, so the only roundings are those of the sums,
+// and their order is fixed: a butterfly over the wave (both operands of every addition are the same pair whichever lane adds them, so
+// all lanes end with the same bits), waves 0..3 of the block in that order, one row per block; align_info_fold_kernel adds the rows
+// t, t + 1024, ... in thread t, then the same tree.  No atomics: the result does not depend on the order in which blocks arrive.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ double wave_xor_sum(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const int lo = __shfl_xor(__double2loint(v), off, 64), hi = __shfl_xor(__double2hiint(v), off, 64);
+        v += __hiloint2double(hi, lo);
+    }
+    return v;
+}
+__global__ __launch_bounds__(kBlock) void align_info_kernel(const unsigned char* __restrict__ inlier, const float* __restrict__ d2,
+                                                            const uint32_t* __restrict__ corr, const float4* __restrict__ tgt, int n, int nt, float max_d2,
+                                                            AlignInfoRow* __restrict__ rows) {
+    __shared__ double s_v[kBlock / 64][kAlignInfoTerms];
+    __shared__ unsigned s_cnt[kBlock / 64];
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    double v[kAlignInfoTerms];
+#pragma unroll
+    for (int k = 0; k < kAlignInfoTerms; ++k) v[k] = 0.0;
+    unsigned cnt = 0u;
+    if (i < n) {
+        const uint32_t j = corr[i];
+        const float d = d2[i];
+        if (inlier[i] != 0 && d <= max_d2 && j < (uint32_t)nt) {
+            const float4 q = tgt[j];
+            const double x = (double)q.x, y = (double)q.y, z = (double)q.z;
+            v[0] = x; v[1] = y; v[2] = z;
+            v[3] = x * x; v[4] = x * y; v[5] = x * z; v[6] = y * y; v[7] = y * z; v[8] = z * z;
+            v[9] = (double)d;
+            cnt = 1u;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
+#pragma unroll
+    for (int k = 0; k < kAlignInfoTerms; ++k) v[k] = wave_xor_sum(v[k]);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+        s_cnt[wave] = cnt;
+#pragma unroll
+        for (int k = 0; k < kAlignInfoTerms; ++k) s_v[wave][k] = v[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < kAlignInfoTerms) {
+        double r = s_v[0][threadIdx.x];
+#pragma unroll
+        for (int w = 1; w < kBlock / 64; ++w) r += s_v[w][threadIdx.x];
+        rows[blockIdx.x].v[threadIdx.x] = r;
+    }
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int w = 1; w < kBlock / 64; ++w) cnt += s_cnt[w];
+        rows[blockIdx.x].count = cnt;
+        rows[blockIdx.x].pad = 0u;
+    }
+}
+// One block of 1024 threads: out = {counted correspondences (one 64-bit integer), the ten sums}.
+__global__ __launch_bounds__(1024) void align_info_fold_kernel(const AlignInfoRow* __restrict__ rows, int nrows, unsigned long long* __restrict__ out) {
+    __shared__ double s_v[16][kAlignInfoTerms];
+    __shared__ unsigned long long s_cnt[16];
+    double v[kAlignInfoTerms];
+#pragma unroll
+    for (int k = 0; k < kAlignInfoTerms; ++k) v[k] = 0.0;
+    unsigned long long cnt = 0ull;
+    for (int b = threadIdx.x; b < nrows; b += 1024) {
+        cnt += rows[b].count;
+#pragma unroll
+        for (int k = 0; k < kAlignInfoTerms; ++k) v[k] += rows[b].v[k];
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned lo = __shfl_xor((unsigned)cnt, off, 64), hi = __shfl_xor((unsigned)(cnt >> 32), off, 64);
+        cnt += ((unsigned long long)hi << 32) | lo;
+    }
+#pragma unroll
+    for (int k = 0; k < kAlignInfoTerms; ++k) v[k] = wave_xor_sum(v[k]);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+        s_cnt[wave] = cnt;
+#pragma unroll
+        for (int k = 0; k < kAlignInfoTerms; ++k) s_v[wave][k] = v[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < kAlignInfoTerms) {
+        double r = s_v[0][threadIdx.x];
+#pragma unroll
+        for (int w = 1; w < 16; ++w) r += s_v[w][threadIdx.x];
+        out[1 + threadIdx.x] = (unsigned long long)__double_as_longlong(r);
+    }
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int w = 1; w < 16; ++w) cnt += s_cnt[w];
+        out[0] = cnt;
+    }
+}
+
+void launch_align_info(const unsigned char* inlier, const float* d2, const uint32_t* corr, const float4* tgt, int n, int nt, float max_d2, AlignInfoRow* rows,
+                       unsigned long long* out11, hipStream_t s) {
+    const int nb = (n + kBlock - 1) / kBlock;
+    hipLaunchKernelGGL(align_info_kernel, dim3(nb), dim3(kBlock), 0, s, inlier, d2, corr, tgt, n, nt, max_d2, rows);
+    hipLaunchKernelGGL(align_info_fold_kernel, dim3(1), dim3(1024), 0, s, rows, nb, out11);
+}
+
 }  // namespace fgoicp

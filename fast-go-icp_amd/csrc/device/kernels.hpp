@@ -107,6 +107,17 @@ void launch_inlier_mask(const float* d2, int n, int k, uint32_t* sel_info, uint3
 // largest inlier squared distance}
 void launch_align_scatter(const uint32_t* idx, const uint32_t* min_bits, const unsigned char* use, const uint32_t* orig_of_slot, int n, int nt, uint32_t* corr_out,
                           float* d2_out, unsigned char* inlier_out, unsigned char* target_hit, size_t nt16, uint2* partials, uint32_t* summary3, hipStream_t s);
+// The information matrix's moments (fgoicp_information; kernels.hip align_info_kernel, align_info_fold_kernel) over the report's arrays in caller
+// order: the counted correspondences are the i with inlier[i] != 0, d2[i] <= max_d2 and corr[i] < nt.  rows: ceil(n / kBlock) entries;
+// out11 = {count, sum q (3), sum q q^T (xx xy xz yy yz zz), sum d2} — the count a 64-bit integer, the rest the bits of doubles.  Fixed
+// order of every addition: the same arrays give the same bits.
+constexpr int kAlignInfoTerms = 10;
+struct AlignInfoRow {
+    uint32_t count, pad;
+    double v[kAlignInfoTerms];
+};
+void launch_align_info(const unsigned char* inlier, const float* d2, const uint32_t* corr, const float4* tgt, int n, int nt, float max_d2, AlignInfoRow* rows,
+                       unsigned long long* out11, hipStream_t s);
 // The bounds of many registrations in one launch (fgoicp_batch, bounds_fused.hpp): a view per pair of the batch, an evaluation per output
 // row, work items {evaluation, chunk}.  Every row is the bits its pair's own context computes with thresholds off.
 struct FusedPairView {

@@ -9,6 +9,7 @@
 #include <cstring>
 #include <memory>
 #include <string>
+#include <limits>
 #include <vector>
 
 #include "../../../include/fgoicp_amd.h"
@@ -45,6 +46,15 @@ struct PairAlign {
     std::vector<float> d2;
     std::vector<uint8_t> inlier, hit;
     fgoicp_alignment_summary sum{};
+    int rc = FGOICP_OK;
+    std::string err;
+    bool have = false;
+};
+
+// a finished pair's information moments, kept on the host (fgoicp_batch_opts.information): context frame, as the device left them
+struct PairInfo {
+    InfoMoments m;
+    float max_dist2 = 0.f;
     int rc = FGOICP_OK;
     std::string err;
     bool have = false;
@@ -112,6 +122,8 @@ struct HipBatchBackend {
     size_t last_lut_bytes = 0, last_lanes = 4;
     int next_pair = 0;            // the pair the scheduler admits next (room_for_more)
     std::vector<PairAlign>* align = nullptr;   // fgoicp_batch_opts.alignment: where finished() leaves every pair's report (nullptr: off)
+    std::vector<PairInfo>* info = nullptr;     // fgoicp_batch_opts.information: ... and every pair's information moments (nullptr: off)
+    float info_max_distance = 0.f;             // callers' units, > 0 (+inf: no threshold)
     // trimmed pairs: one grow-only arena of e-rows for the whole run (one fill per sub-tick), the solo formula's budget (trim_rows_budget)
     size_t arena_budget = 0;      // bytes; 0 = not set yet
     size_t arena_rows_max = 0;    // test hook: at most this many rows per fill (0: the budget decides)
@@ -202,15 +214,30 @@ struct HipBatchBackend {
     // BatchScheduler's optional hook: the pair's driver has ended, its context is still there.  The report at the pair's best transform, as
     // fgoicp_solver_alignment takes it from a solver of that pair alone (ctx_alignment on the pair's own context: nothing is shared).
     void finished(int i, const BatchPairResult& r) {
-        if (!align || r.status || !ctx[(size_t)i]) return;
+        if ((!align && !info) || r.status || !ctx[(size_t)i]) return;
         const PairHost& p = (*pairs)[(size_t)i];
-        PairAlign& a = (*align)[(size_t)i];
-        a.corr.resize(p.ns); a.d2.resize(p.ns); a.inlier.resize(p.ns); a.hit.resize(p.nt);
         const float t3[3] = {r.t.x, r.t.y, r.t.z};
-        a.rc = ctx_alignment(ctx[(size_t)i], r.R.m, t3, a.corr.data(), a.d2.data(), a.inlier.data(), a.hit.data(), &a.sum);
-        a.sum.scaling_factor = p.scaling_factor;
-        a.have = a.rc == FGOICP_OK;
-        if (a.rc) a.err = fgoicp_last_error();
+        PairInfo* f = info ? &(*info)[(size_t)i] : nullptr;
+        if (f) f->max_dist2 = information_max_dist2(info_max_distance, p.scaling_factor);  // as fgoicp_solver_information
+        int rc;
+        if (align) {
+            PairAlign& a = (*align)[(size_t)i];
+            a.corr.resize(p.ns); a.d2.resize(p.ns); a.inlier.resize(p.ns); a.hit.resize(p.nt);
+            // both options on: one pass of the report's device half serves both
+            rc = f ? ctx_alignment_information(ctx[(size_t)i], r.R.m, t3, a.corr.data(), a.d2.data(), a.inlier.data(), a.hit.data(), &a.sum, f->max_dist2, &f->m)
+                   : ctx_alignment(ctx[(size_t)i], r.R.m, t3, a.corr.data(), a.d2.data(), a.inlier.data(), a.hit.data(), &a.sum);
+            a.rc = rc;
+            a.sum.scaling_factor = p.scaling_factor;
+            a.have = a.rc == FGOICP_OK;
+            if (a.rc) a.err = fgoicp_last_error();
+        } else {
+            rc = ctx_information(ctx[(size_t)i], r.R.m, t3, f->max_dist2, &f->m);
+        }
+        if (f) {
+            f->rc = rc;
+            f->have = rc == FGOICP_OK;
+            if (rc) f->err = fgoicp_last_error();
+        }
     }
     void release(int i) {
         (void)hipSetDevice(device);
@@ -413,6 +440,7 @@ struct fgoicp_batch {
     uint64_t bounds_launches = 0, icp_launches = 0;
     bool ran = false;
     std::vector<PairAlign> align;  // opts.alignment: one per pair
+    std::vector<PairInfo> info;    // opts.information: one per pair
 };
 
 extern "C" {
@@ -432,6 +460,10 @@ static int batch_create_impl(const fgoicp_batch_pair* pairs, int n, const fgoicp
         return FGOICP_ERR_INVALID_ARG;
     }
     if (b->opts.max_live < 0) { set_error("fgoicp_batch_create: max_live < 0"); return FGOICP_ERR_INVALID_ARG; }
+    if (b->opts.information && b->opts.information_max_distance != b->opts.information_max_distance) {
+        set_error("fgoicp_batch_create: information_max_distance is NaN");
+        return FGOICP_ERR_INVALID_ARG;
+    }
     const float* trim = b->opts.trim_fractions;
     b->opts.trim_fractions = nullptr;  // read here only
     for (int i = 0; trim && i < n; ++i)
@@ -482,6 +514,11 @@ static int batch_run_impl(fgoicp_batch* b, float* R_out9n, float* t_out3n, int* 
     if (b->opts.alignment) {
         b->align.assign((size_t)n, PairAlign());
         be.align = &b->align;
+    }
+    if (b->opts.information) {
+        b->info.assign((size_t)n, PairInfo());
+        be.info = &b->info;
+        be.info_max_distance = b->opts.information_max_distance > 0.0f ? b->opts.information_max_distance : std::numeric_limits<float>::infinity();
     }
     int rc = be.init();
     if (rc) return rc;
@@ -550,6 +587,23 @@ int fgoicp_batch_alignment(const fgoicp_batch* b, int i, uint32_t* corr_idx_ns, 
     if (inlier_ns) std::memcpy(inlier_ns, a.inlier.data(), a.inlier.size());
     if (target_hit_nt) std::memcpy(target_hit_nt, a.hit.data(), a.hit.size());
     return alignment_summary_out(a.sum, out, where);
+}
+
+int fgoicp_batch_information(const fgoicp_batch* b, int i, fgoicp_information_t* out) {
+    const char* where = "fgoicp_batch_information";
+    if (!b) { set_error(std::string(where) + ": the batch must not be null"); return FGOICP_ERR_INVALID_ARG; }
+    if (!b->opts.information) { set_error(std::string(where) + ": the batch was created with fgoicp_batch_opts.information = 0"); return FGOICP_ERR_INVALID_ARG; }
+    if (!b->ran) { set_error(std::string(where) + ": fgoicp_batch_run has not run yet"); return FGOICP_ERR_INVALID_ARG; }
+    if (i < 0 || i >= (int)b->pairs.size()) { set_error(std::string(where) + ": pair index out of range"); return FGOICP_ERR_INVALID_ARG; }
+    if (b->status[(size_t)i]) { set_error(std::string(where) + ": pair " + std::to_string(i) + " failed (status " + std::to_string(b->status[(size_t)i]) + ")"); return FGOICP_ERR_INVALID_ARG; }
+    if (!information_size_ok(out)) { set_error(std::string(where) + ": out must not be null and out->struct_size = sizeof(fgoicp_information_t)"); return FGOICP_ERR_INVALID_ARG; }
+    const PairInfo& f = b->info[(size_t)i];
+    if (!f.have) { set_error(std::string(where) + ": pair " + std::to_string(i) + ": " + (f.err.empty() ? "no moments were taken" : f.err)); return f.rc ? f.rc : FGOICP_ERR_INVALID_ARG; }
+    const PairHost& p = b->pairs[(size_t)i];
+    const float c3[3] = {-p.offset_pct.x, -p.offset_pct.y, -p.offset_pct.z};  // the centroid that was subtracted: center_point_cloud returns minus it
+    fgoicp_information_t full;
+    information_fill(full, p.ns, f.m, c3, p.scaling_factor, f.max_dist2);
+    return information_out(full, out, where);
 }
 
 int fgoicp_batch_launches(const fgoicp_batch* b, uint64_t* bounds_launches, uint64_t* icp_launches) {

@@ -43,6 +43,37 @@ struct HipOps {
     bool pipeline = [] { const char* e = dev_env("FGOICP_PIPELINE"); return e ? std::atoi(e) != 0 : true; }();  // tuning knob
 };
 
+// the host half of the information matrix (information.hpp)
+void information_from_moments(uint64_t n, const double* sq_s, const double* sqq_s, const float* offset3, float scale, double* info36, double* sum_q3_out,
+                                     double* sum_qq6_out) {
+    const double N = (double)n, s = (double)scale;
+    const double c[3] = {offset3 ? (double)offset3[0] : 0.0, offset3 ? (double)offset3[1] : 0.0, offset3 ? (double)offset3[2] : 0.0};
+    double q[3], qq[6];
+    static const int A[6] = {0, 0, 0, 1, 1, 2}, B[6] = {0, 1, 2, 1, 2, 2};
+    if (!offset3 && scale == 1.0f) {
+        for (int k = 0; k < 3; ++k) q[k] = sq_s[k];
+        for (int k = 0; k < 6; ++k) qq[k] = sqq_s[k];
+    } else {
+        for (int k = 0; k < 3; ++k) q[k] = sq_s[k] / s + N * c[k];
+        for (int k = 0; k < 6; ++k) {
+            const int a = A[k], b = B[k];
+            qq[k] = sqq_s[k] / (s * s) + (c[a] * sq_s[b] + sq_s[a] * c[b]) / s + N * c[a] * c[b];
+        }
+    }
+    if (sum_q3_out) std::memcpy(sum_q3_out, q, sizeof(q));
+    if (sum_qq6_out) std::memcpy(sum_qq6_out, qq, sizeof(qq));
+    if (!info36) return;
+    const double xx = qq[0], xy = qq[1], xz = qq[2], yy = qq[3], yz = qq[4], zz = qq[5];
+    const double M[6][6] = {{yy + zz, -xy, -xz, 0.0, -q[2], q[1]},
+                            {-xy, xx + zz, -yz, q[2], 0.0, -q[0]},
+                            {-xz, -yz, xx + yy, -q[1], q[0], 0.0},
+                            {0.0, q[2], -q[1], N, 0.0, 0.0},
+                            {-q[2], 0.0, q[0], 0.0, N, 0.0},
+                            {q[1], -q[0], 0.0, 0.0, 0.0, N}};
+    for (int r = 0; r < 6; ++r)
+        for (int k = 0; k < 6; ++k) info36[6 * r + k] = M[r][k] + 0.0;  // + 0.0: no negative zeros in the matrix
+}
+
 }  // namespace fgoicp
 
 using namespace fgoicp;
@@ -230,6 +261,33 @@ int fgoicp_solver_alignment(fgoicp_solver* s, uint32_t* corr_idx_ns, float* dist
     if (rc) return rc;
     full.scaling_factor = s->scaling_factor;
     return alignment_summary_out(full, out, "fgoicp_solver_alignment");
+}
+
+int fgoicp_solver_information(fgoicp_solver* s, float max_distance, fgoicp_information_t* out) {
+    if (!s) { set_error("fgoicp_solver_information: the solver must not be null"); return FGOICP_ERR_INVALID_ARG; }
+    if (!s->ran) { set_error("fgoicp_solver_information: fgoicp_solver_run has not succeeded yet: there is no best transform"); return FGOICP_ERR_INVALID_ARG; }
+    if (!information_size_ok(out)) { set_error("fgoicp_solver_information: out must not be null and out->struct_size = sizeof(fgoicp_information_t)"); return FGOICP_ERR_INVALID_ARG; }
+    if (!(max_distance >= 0.0f)) { set_error("fgoicp_solver_information: max_distance must be >= 0 (+inf: no threshold)"); return FGOICP_ERR_INVALID_ARG; }
+    Mat3f R;
+    Vec3f t;
+    s->driver->best_transform(R, t);  // the normalised frame the search ran in, as fgoicp_solver_alignment
+    const float t3[3] = {t.x, t.y, t.z};
+    const float max_dist2 = information_max_dist2(max_distance, s->scaling_factor);
+    InfoMoments m;
+    const int rc = ctx_information(s->ctx, R.m, t3, max_dist2, &m);
+    if (rc) return rc;
+    const float c3[3] = {-s->offset_pct.x, -s->offset_pct.y, -s->offset_pct.z};  // the centroid that was subtracted: center_point_cloud returns minus it
+    fgoicp_information_t full;
+    information_fill(full, s->ns, m, c3, s->scaling_factor, max_dist2);
+    return information_out(full, out, "fgoicp_solver_information");
+}
+
+int fgoicp_information_from_moments(uint64_t n, const double* sum_q3, const double* sum_qq6, const float* offset3, float scale, double* info36, double* sum_q3_out,
+                                    double* sum_qq6_out) {
+    if (!sum_q3 || !sum_qq6) { set_error("fgoicp_information_from_moments: sum_q3 and sum_qq6 must not be null"); return FGOICP_ERR_INVALID_ARG; }
+    if (!(scale > 0.0f) || !std::isfinite(scale)) { set_error("fgoicp_information_from_moments: scale must be a positive finite number"); return FGOICP_ERR_INVALID_ARG; }
+    information_from_moments(n, sum_q3, sum_qq6, offset3, scale, info36, sum_q3_out, sum_qq6_out);
+    return FGOICP_OK;
 }
 
 int fgoicp_solver_preproc(const fgoicp_solver* s, float* offs6, float* scale, float* bounds6) {

@@ -6,7 +6,7 @@ import numpy as np
 
 from . import _lib
 from .nodes import from_glm
-from .registration import Registration, _alignment, _cloud, _fp
+from .registration import Registration, _alignment, _cloud, _fp, _information
 
 
 class FastGoICP:
@@ -57,6 +57,13 @@ class FastGoICP:
         """EXTENSION (fgoicp_solver_alignment): the Alignment at the best transform, after run().  Indices and masks refer to the clouds as
         passed in; dist2 is in the solver's centred and scaled frame, .distances and .inlier_rmse are in the callers' units."""
         return _alignment(lambda *a: self._lib.fgoicp_solver_alignment(self._h, *a), "fgoicp_solver_alignment", self.ns, self.nt)
+
+    def information(self, max_distance=None):
+        """EXTENSION (fgoicp_solver_information): the Information at the best transform, after run(), in the callers' frame — the target
+        points as passed in.  max_distance: callers' units (None: no threshold); counted are the Alignment's inliers with
+        dist2 <= (float32(max_distance) * scale)^2, evaluated in float32."""
+        d = float("inf") if max_distance is None else float(max_distance)
+        return _information(lambda out: self._lib.fgoicp_solver_information(self._h, d, out), "fgoicp_solver_information")
 
     def _transform(self, fn, name):
         R = np.empty(9, np.float32); t = np.empty(3, np.float32)

@@ -73,6 +73,52 @@ def _alignment(call, where, ns, nt):
     return Alignment(idx, d2, inl, hit, sm)
 
 
+class Information:
+    """EXTENSION: the information matrix of fgoicp_information / fgoicp_solver_information / fgoicp_batch_information — matrix (6, 6) float64,
+    sum G^T G over the counted correspondences with G = [-[q]x | I], twist order (wx, wy, wz, vx, vy, vz), q the target points (a bare
+    Registration: as it holds them; a solver or a batch: as the caller passed them in).  correspondences: the inliers of the Alignment
+    within the distance threshold; sum_q (3,), sum_qq (6,: xx xy xz yy yz zz) the moments the matrix is made of; sum_dist2 and max_dist2 in
+    the frame the search ran in (scaling_factor converts)."""
+
+    def __init__(self, raw):
+        self.matrix = np.array(raw.info, np.float64).reshape(6, 6)
+        self.points, self.correspondences = int(raw.points), int(raw.correspondences)
+        self.sum_q, self.sum_qq = np.array(raw.sum_q, np.float64), np.array(raw.sum_qq, np.float64)
+        self.sum_dist2 = float(raw.sum_dist2)
+        self.max_dist2, self.scaling_factor = np.float32(raw.max_dist2), np.float32(raw.scaling_factor)
+        self.raw = bytes(raw)  # the struct as the library filled it (two results of the same inputs are the same bytes)
+
+    @property
+    def fitness(self):
+        """correspondences / points (Open3D's evaluate_registration at this distance threshold)"""
+        return self.correspondences / self.points
+
+    @property
+    def inlier_rmse(self):
+        """root mean squared distance of the counted correspondences in the callers' units (0 when nothing is counted)"""
+        if not self.correspondences:
+            return 0.0
+        return float(np.sqrt(self.sum_dist2 / self.correspondences) / np.float64(self.scaling_factor))
+
+
+def _information(call, where):
+    """call(out) -> status; the marshalling shared by the three entry points"""
+    raw = _lib.Information()
+    _lib.check(call(C.byref(raw)), where)
+    return Information(raw)
+
+
+def information_from_moments(n, sum_q, sum_qq, offset=None, scale=1.0):
+    """fgoicp_information_from_moments (host only): moments of n points q_s -> (matrix (6, 6), sum_q, sum_qq) of q = q_s / scale + offset."""
+    q = np.ascontiguousarray(sum_q, np.float64).reshape(3); qq = np.ascontiguousarray(sum_qq, np.float64).reshape(6)
+    off = None if offset is None else np.ascontiguousarray(offset, np.float32).reshape(3)
+    info = np.empty(36, np.float64); qo = np.empty(3, np.float64); qqo = np.empty(6, np.float64)
+    dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+    _lib.check(_lib.load().fgoicp_information_from_moments(int(n), dp(q), dp(qq), None if off is None else _fp(off), float(scale), dp(info), dp(qo), dp(qqo)),
+               "fgoicp_information_from_moments")
+    return info.reshape(6, 6), qo, qqo
+
+
 class Registration:
     """icp::Registration (fgoicp/registration.hpp:49-98) + its NearestNeighborLUT member."""
 
@@ -169,6 +215,13 @@ class Registration:
         Rg = to_glm(R)
         tt = np.ascontiguousarray(t, dtype=np.float32).reshape(3)
         return _alignment(lambda *a: self._lib.fgoicp_alignment(self._h, _fp(Rg), _fp(tt), *a), "fgoicp_alignment", self.ns, self.nt)
+
+    def information(self, R, t, max_dist2=np.inf):
+        """EXTENSION (fgoicp_information): the Information of R*pcs + t against the target over the Alignment's inliers with
+        dist2 <= max_dist2 (inf: all of them), in the frame of the clouds this object holds."""
+        Rg = to_glm(R)
+        tt = np.ascontiguousarray(t, dtype=np.float32).reshape(3)
+        return _information(lambda out: self._lib.fgoicp_information(self._h, _fp(Rg), _fp(tt), float(max_dist2), out), "fgoicp_information")
 
     def compute_bounds(self, R, rot_span, tnodes, fix_rot):
         Rg = to_glm(R)

@@ -50,6 +50,14 @@ public:
         check_status(fgoicp_solver_alignment(s_, a.indices.data(), a.dist2.data(), a.inlier.data(), a.target_hit.data(), &a.summary), "fgoicp_solver_alignment");
         return a;
     }
+    // EXTENSION: the information matrix at the best transform, after run(), in the callers' frame (fgoicp_solver_information);
+    // max_distance in the callers' units, INFINITY: no threshold
+    Information information(float max_distance = INFINITY) const {
+        Information f;
+        f.result.struct_size = sizeof(f.result);
+        check_status(fgoicp_solver_information(s_, max_distance, &f.result), "fgoicp_solver_information");
+        return f;
+    }
     fgoicp_run_stats stats() const { fgoicp_run_stats st{}; check_status(fgoicp_solver_stats(s_, &st), "fgoicp_solver_stats"); return st; }
     fgoicp_solver* handle() const { return s_; }
     // the reference's own lines while the search runs (fgoicp.cpp:15-17 Info, :85-87 Debug), from the driver's log events

@@ -53,6 +53,16 @@ struct Alignment {
     double distance(size_t i) const { return std::sqrt((double)dist2[i]) / (double)summary.scaling_factor; }  // in the callers' units
 };
 
+// EXTENSION (ours; Open3D: get_information_matrix_from_point_clouds): the information matrix of fgoicp_information /
+// fgoicp_solver_information — result.info, 6 x 6 row-major, twist order (wx, wy, wz, vx, vy, vz), over the report's inliers within the
+// distance threshold.
+struct Information {
+    fgoicp_information_t result{};
+    double operator()(int r, int c) const { return result.info[6 * r + c]; }
+    double fitness() const { return result.points ? (double)result.correspondences / (double)result.points : 0.0; }
+    double inlier_rmse() const { return result.correspondences ? std::sqrt(result.sum_dist2 / (double)result.correspondences) / (double)result.scaling_factor : 0.0; }  // callers' units
+};
+
 class Registration {
 public:
     // registration.hpp:68
@@ -93,6 +103,14 @@ public:
         a.summary.struct_size = sizeof(a.summary);
         check_status(fgoicp_alignment(ctx_, R.data(), &t.x, a.indices.data(), a.dist2.data(), a.inlier.data(), a.target_hit.data(), &a.summary), "fgoicp_alignment");
         return a;
+    }
+
+    // EXTENSION: the information matrix of R*pcs + t over the report's inliers with dist2 <= max_dist2, in the frame of the clouds as passed in (fgoicp_information)
+    Information information(mat3 R, vec3 t, float max_dist2 = INFINITY) const {
+        Information f;
+        f.result.struct_size = sizeof(f.result);
+        check_status(fgoicp_information(ctx_, R.data(), &t.x, max_dist2, &f.result), "fgoicp_information");
+        return f;
     }
 
     fgoicp_ctx* handle() const { return ctx_; }

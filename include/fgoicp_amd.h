@@ -182,6 +182,43 @@ typedef struct fgoicp_alignment_summary {
 int fgoicp_alignment(fgoicp_ctx* ctx, const float* R9, const float* t3, uint32_t* corr_idx_ns, float* dist2_ns, uint8_t* inlier_ns,
                      uint8_t* target_hit_nt, fgoicp_alignment_summary* out);
 
+/*
+ * EXTENSION — the information matrix of a registration (no reference counterpart; Open3D: get_information_matrix_from_point_clouds), the
+ * weight of a pose-graph edge.  For a transform (R, t) the COUNTED correspondences are the source points i that
+ *   - the alignment report marks an inlier (every point; on a trimmed context the k smallest),
+ *   - have dist2[i] <= max_dist2 (+inf: no threshold; NaN and negative values are refused before any device work), and
+ *   - have corr_idx[i] < nt.
+ * With q_i the target point corr_idx[i] names and G_i = [ -[q_i]x | I3 ]:
+ *   info = sum G_i^T G_i = [ (sum |q|^2) I - sum q q^T   [sum q]x ]
+ *                          [ -[sum q]x                   N I      ]
+ * 6 x 6, row-major, twist order rotation first (wx, wy, wz, vx, vy, vz).  The device computes N, sum q, sum q q^T (xx xy xz yy yz zz) and
+ * sum dist2 over the counted set behind the report's device half, with every addition in a fixed order (two calls return the same bytes);
+ * the host forms the matrix in fp64.  fitness = correspondences / points, inlier_rmse = sqrt(sum_dist2 / correspondences) / scaling_factor.
+ * The call leaves the context as it found it, as fgoicp_alignment does.
+ * Frame: fgoicp_information answers in the frame of the clouds the context holds.  fgoicp_solver_information and fgoicp_batch_information
+ * answer in the CALLERS' frame, q as handed to the create call: the context holds q_s = (q - c) * s (c = the target's centroid, MINUS the target offset of
+ * fgoicp_solver_preproc, which follows the reference's sign; s = its scale) and the host converts, sum q = sum q_s / s + N c and sum q q^T = sum q_s q_s^T / s^2 + (c sum q_s^T + sum q_s c^T) / s
+ * + N c c^T (fgoicp_information_from_moments).  Their threshold is a DISTANCE in the callers' units; the library forms, in fp32,
+ *   ds = (float)max_distance * scale;  max_dist2 = ds * ds;
+ * and counts dist2[i] <= max_dist2 against the report's dist2 (fgoicp_solver_alignment), so a caller can reproduce the set.  sum_dist2 and
+ * max_dist2 stay in the context's frame whichever call filled them (scaling_factor converts, as for fgoicp_alignment_summary).
+ * (The struct is fgoicp_information_t, as fgoicp_cloud_stats_t: C has one name space for a typedef and a function.)
+ */
+typedef struct fgoicp_information_t {
+    uint32_t struct_size;            /* IN: sizeof(fgoicp_information_t) as the CALLER was compiled; no byte beyond it is written, 0 is refused */
+    uint64_t points, correspondences; /* ns; the counted correspondences N */
+    double   sum_dist2;              /* over the counted set, context frame */
+    double   sum_q[3], sum_qq[6];    /* frame as defined above; sum_qq in the order xx xy xz yy yz zz */
+    double   info[36];
+    float    max_dist2, scaling_factor; /* the threshold the device compared with (context frame); 1 for a bare context, the solver's scale otherwise */
+} fgoicp_information_t;
+int fgoicp_information(fgoicp_ctx* ctx, const float* R9, const float* t3, float max_dist2, fgoicp_information_t* out);
+/* The host half of the three calls, no device needed: moments of n points in one frame -> the moments in the frame q = q_s / scale + offset
+ * and the matrix.  offset3 = NULL, scale = 1: no change of frame.  info36, sum_q3_out and sum_qq6_out may each be NULL; the outputs may
+ * alias the inputs.  Refuses null inputs and a scale that is not a positive finite number. */
+int fgoicp_information_from_moments(uint64_t n, const double* sum_q3, const double* sum_qq6, const float* offset3, float scale, double* info36,
+                                    double* sum_q3_out, double* sum_qq6_out);
+
 /* Replaces IterativeClosestPoint3D(reg, pct, pcs, max_iter, thr, R, t) + run()
  * (fgoicp/icp3d.hpp:30-35, icp3d.cu:55-108).  Returns the reference's Result_t {sse, R, t}
  * plus the number of loop iterations executed. */
@@ -337,6 +374,10 @@ int fgoicp_solver_stats(const fgoicp_solver* s, fgoicp_run_stats* out);
  * fgoicp_solver_run returns what it returned before.  On a multi-GPU run every rank answers from its own context. */
 int fgoicp_solver_alignment(fgoicp_solver* s, uint32_t* corr_idx_ns, float* dist2_ns, uint8_t* inlier_ns, uint8_t* target_hit_nt,
                             fgoicp_alignment_summary* out);
+/* EXTENSION: fgoicp_information at the best transform the solver holds, in the callers' frame, after a successful fgoicp_solver_run —
+ * before that the call is refused (FGOICP_ERR_INVALID_ARG).  max_distance: callers' units, +inf = no threshold, NaN and negative values
+ * refused.  A later fgoicp_solver_run returns what it returned before. */
+int fgoicp_solver_information(fgoicp_solver* s, float max_distance, fgoicp_information_t* out);
 /* Pre-processing results (tests): offs6 = {offset_pcs, offset_pct}, bounds6 as in ctx_create. */
 int fgoicp_solver_preproc(const fgoicp_solver* s, float* offs6, float* scale, float* bounds6);
 /* Statistics of a raw cloud, host side, no device needed (TODO.md:7 of the reference: "compute point clouds' stats"): what the
@@ -444,6 +485,11 @@ typedef struct fgoicp_batch_opts {
                                     NULL, or a struct_size that ends before this member: no pair is trimmed.  Read by fgoicp_batch_create only */
     int alignment;               /* != 0: the run keeps every pair's alignment report (fgoicp_batch_alignment) on the host: 9 bytes per source point, 1 per target
                                     point.  Appended within revision 2: 0 for a caller built with the shorter struct (struct_size) */
+    int reserved0;               /* the tail padding of the struct as first published with `alignment` (48 bytes): a caller built against it may leave anything
+                                    here, so it is never read and the members below start behind it */
+    int information;             /* != 0: the run keeps every pair's information matrix (fgoicp_batch_information): under 200 bytes per pair.  Appended within
+                                    revision 2: 0 for a caller built with a shorter struct (struct_size) */
+    float information_max_distance; /* its distance threshold in the callers' units, as fgoicp_solver_information takes it; <= 0: none.  NaN is refused */
 } fgoicp_batch_opts;
 /* Copies the clouds and pre-processes every pair on the host (centre, scale, bounds, inlier count, as fgoicp_solver_create); creates no
  * device state.  Refuses n <= 0, a null or empty cloud, solver.trim_fraction != 0, a trim_fractions entry that is NaN, negative or >= 1,
@@ -461,6 +507,10 @@ int fgoicp_batch_stats(const fgoicp_batch* b, int i, fgoicp_run_stats* out);
  * when fgoicp_batch_opts.alignment was 0, before fgoicp_batch_run, and for a pair whose status is not FGOICP_OK. */
 int fgoicp_batch_alignment(const fgoicp_batch* b, int i, uint32_t* corr_idx_ns, float* dist2_ns, uint8_t* inlier_ns, uint8_t* target_hit_nt,
                            fgoicp_alignment_summary* out);
+/* Pair i's information matrix as fgoicp_solver_information(s, information_max_distance) gives it for that pair alone, byte for byte: taken
+ * when the pair finished, next to the report (one pass of the report's device half serves both when both options are on).  Refused
+ * (FGOICP_ERR_INVALID_ARG) when fgoicp_batch_opts.information was 0, before fgoicp_batch_run, and for a pair whose status is not FGOICP_OK. */
+int fgoicp_batch_information(const fgoicp_batch* b, int i, fgoicp_information_t* out);
 /* Launches of the last run: fused bounds launches (one per LUT class per tick, more for a class of more than 2^24 work items, and per
  * arena fill for trimmed pairs; neither the finalize nor the trimmed selection counted) and lock-step ICP iterations (one host
  * turn-around each, shared by every active ICP run). */

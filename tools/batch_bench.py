@@ -39,6 +39,7 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--trim", type=float, default=0.0, help="trim_fraction of every pair (0: untrimmed)")
     ap.add_argument("--alignment", action="store_true", help="the batch keeps every pair's alignment report (fgoicp_batch_opts.alignment)")
+    ap.add_argument("--information", action="store_true", help="the batch keeps every pair's information matrix (fgoicp_batch_opts.information)")
     a = ap.parse_args()
     w = WORKLOADS[a.workload]
     sched = fg.SCHEDULE_ROUND if a.schedule == "round" else fg.SCHEDULE_SERIAL
@@ -65,7 +66,7 @@ def main():
         solo.append((R, t, s.get_best_error(), s.stats()))
         s.close()
 
-    b = fg.FastGoICPBatch(pairs, max_live=a.max_live, alignment=a.alignment, **kw)
+    b = fg.FastGoICPBatch(pairs, max_live=a.max_live, alignment=a.alignment, information=a.information, **kw)
     t0 = time.perf_counter()
     out = b.run()
     t_batch = time.perf_counter() - t0
@@ -87,7 +88,7 @@ def main():
 
     loop = t_create + t_run
     print(json.dumps({
-        "workload": a.workload, "pairs": w["n"], "ns": w["ns"], "nt": w["nt"], "lut_resolution": w["lut"], "mse_threshold": w["mse"], "schedule": a.schedule, "trim_fraction": a.trim, "alignment": bool(a.alignment),
+        "workload": a.workload, "pairs": w["n"], "ns": w["ns"], "nt": w["nt"], "lut_resolution": w["lut"], "mse_threshold": w["mse"], "schedule": a.schedule, "trim_fraction": a.trim, "alignment": bool(a.alignment), "information": bool(a.information),
         "batch_s": round(t_batch, 4), "loop_s": round(loop, 4), "loop_lut_build_s": round(t_create, 4), "loop_run_s": round(t_run, 4),
         "speedup_vs_loop": round(loop / t_batch, 3), "speedup_vs_loop_runs_only": round(t_run / t_batch, 3),
         "bit_equal": equal, "all_bit_equal": all(equal),
