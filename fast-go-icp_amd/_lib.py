@@ -95,6 +95,23 @@ class Information(C.Structure):
         self.struct_size = C.sizeof(Information)  # the library writes no byte beyond it
 
 
+class PlaneMoments(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("points", C.c_uint64), ("correspondences", C.c_uint64), ("m", C.c_double * 28), ("max_dist2", C.c_float)]
+
+    def __init__(self):
+        super().__init__()
+        self.struct_size = C.sizeof(PlaneMoments)  # the library writes no byte beyond it
+
+
+class PlaneResult(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("R", C.c_float * 9), ("t", C.c_float * 3), ("iterations", C.c_int), ("rank", C.c_int), ("correspondences", C.c_uint64),
+                ("plane_rmse", C.c_double), ("sse", C.c_float), ("scaling_factor", C.c_float)]
+
+    def __init__(self):
+        super().__init__()
+        self.struct_size = C.sizeof(PlaneResult)  # the library writes no byte beyond it
+
+
 SCHEDULE_SERIAL = 0
 SCHEDULE_ROUND = 1
 
@@ -133,6 +150,14 @@ _SIGS = {
     "fgoicp_batch_information": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Information)]),
     "fgoicp_information_from_moments": (C.c_int, [C.c_uint64, C.POINTER(C.c_double), C.POINTER(C.c_double), c_float_p, C.c_float, C.POINTER(C.c_double),
                                                   C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "fgoicp_ctx_set_target_normals": (C.c_int, [C.c_void_p, c_float_p, C.c_int]),
+    "fgoicp_target_normals": (C.c_int, [C.c_void_p, c_float_p]),
+    "fgoicp_target_knn": (C.c_int, [C.c_void_p, C.c_int, c_uint32_p, c_float_p]),
+    "fgoicp_plane_moments": (C.c_int, [C.c_void_p, c_float_p, c_float_p, C.c_float, C.POINTER(PlaneMoments)]),
+    "fgoicp_plane_step_from_moments": (C.c_int, [C.c_uint64, C.POINTER(C.c_double), C.POINTER(C.c_double), c_int_p]),
+    "fgoicp_plane_apply_step": (C.c_int, [c_float_p, c_float_p, C.POINTER(C.c_double), c_float_p, c_float_p]),
+    "fgoicp_icp_plane": (C.c_int, [C.c_void_p, c_float_p, c_float_p, C.c_size_t, C.c_float, C.c_float, C.POINTER(PlaneResult)]),
+    "fgoicp_solver_refine_plane": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.c_float, C.c_float, C.POINTER(PlaneResult)]),
     "fgoicp_icp": (C.c_int, [C.c_void_p, c_float_p, c_float_p, C.c_size_t, C.c_float, c_float_p, c_float_p, c_float_p, c_int_p]),
     "fgoicp_icp_batch": (C.c_int, [C.c_void_p, C.c_int, c_float_p, c_float_p, C.c_size_t, C.c_float, c_float_p, c_float_p, c_float_p, c_int_p]),
     "fgoicp_procrustes": (C.c_int, [C.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p, c_int_p]),

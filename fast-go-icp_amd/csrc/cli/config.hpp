@@ -120,6 +120,10 @@ struct Config {
         float trim_fraction = 0.0f;  // EXTENSION: > 0 enables trimmed Go-ICP; `trim` itself stays parsed-and-ignored as upstream
         int gpus = 1;                // EXTENSION: > 1 shards the outer BnB over that many GPUs of this node (one host thread each, RCCL)
         float information_distance = 0.0f;  // EXTENSION: distance threshold of io.information in the files' units (absent or 0: none)
+        std::string refine;          // EXTENSION: "plane" = point-to-plane refinement after the search (fgoicp_solver_refine_plane); absent or "": none; anything else is refused
+        int refine_knn = 16;         // ... neighbours per target point for its normal (4 .. 32)
+        int refine_max_iter = 30;
+        float refine_distance = 0.0f;  // ... distance threshold in the files' units (absent or 0: none)
     } params;
 
     explicit Config(const std::string& toml_filepath) {
@@ -170,6 +174,14 @@ struct Config {
             params.gpus = std::max(1, (int)num("params", "gpus", 1));
             params.information_distance = (float)num("params", "information_distance", 0.0);
             if (!(params.information_distance > 0.0f)) params.information_distance = 0.0f;
+            params.refine = str("params", "refine", "");
+            params.refine_knn = (int)num("params", "refine_knn", 16);
+            params.refine_max_iter = std::max(0, (int)num("params", "refine_max_iter", 30));
+            params.refine_distance = (float)num("params", "refine_distance", 0.0);
+            if (!(params.refine_distance > 0.0f)) params.refine_distance = 0.0f;
+            if (!params.refine.empty() && params.refine != "plane")  // (thrown, not exit(1): the callers report it; a typo must not silently skip the refinement)
+                throw std::invalid_argument("params.refine = \"" + params.refine + "\" is not supported: the only refinement is \"plane\"");
+            if (params.refine == "plane" && (params.refine_knn < 4 || params.refine_knn > 32)) throw std::invalid_argument("params.refine_knn must lie in [4, 32]");
             auto clampf = [](float x, float lo, float hi) { return x < hi ? (x > lo ? x : lo) : hi; };
             params.target_subsample = clampf(params.target_subsample, 1e-5f, 1.0f);  // utilities.hpp:101-104
             params.source_subsample = clampf(params.source_subsample, 1e-5f, 1.0f);
@@ -341,8 +353,9 @@ inline size_t load_cloud(const std::string& filepath, float subsample, std::vect
 }
 
 // io.output / io.visualization (declared by test/bunny.toml:10-11, unimplemented upstream)
+// refined (optional, EXTENSION: params.refine = "plane"): a [refined] table behind the existing keys, which stay as they are
 inline void write_result_toml(const std::string& path, const icp::mat3& R, const icp::vec3& t, float sse, size_t ns, double seconds,
-                              const fgoicp_run_stats& st) {
+                              const fgoicp_run_stats& st, const fgoicp_plane_result_t* refined = nullptr) {
     std::ofstream f(path);
     if (!f) throw std::runtime_error("Unable to write " + path);
     f.precision(9);
@@ -353,6 +366,13 @@ inline void write_result_toml(const std::string& path, const icp::mat3& R, const
     f << "sse = " << sse << "\nmse = " << sse / (float)ns << "\nseconds = " << seconds << "\n";
     f << "\n[stats]\nsubcubes = " << st.trans_cubes << "\nrotation_cubes = " << st.rot_cubes << "\nicp_runs = " << st.icp_runs
       << "\nicp_iterations = " << st.icp_iters << "\nrounds = " << st.rounds << "\n";
+    if (!refined) return;
+    const float* Q = refined->R;  // glm order: Q[col * 3 + row]
+    f << "\n[refined]\nrotation = [\n";
+    for (int r = 0; r < 3; ++r) f << "  [" << Q[r] << ", " << Q[3 + r] << ", " << Q[6 + r] << "],\n";
+    f << "]\ntranslation = [" << refined->t[0] << ", " << refined->t[1] << ", " << refined->t[2] << "]\n";
+    f << "plane_rmse = " << refined->plane_rmse / (double)refined->scaling_factor << "\niterations = " << refined->iterations << "\nrank = " << refined->rank
+      << "\ncorrespondences = " << refined->correspondences << "\n";
 }
 
 // io.alignment (EXTENSION): the alignment report of the run (fgoicp_solver_alignment / fgoicp_batch_alignment).  Two '#' lines — the summary,

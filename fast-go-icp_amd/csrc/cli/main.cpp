@@ -34,7 +34,13 @@ static int run_batch(const std::string& list_file) {
         line = cli::trim(line);
         if (line.empty() || line[0] == '#') continue;
         const std::filesystem::path p(line);
-        configs.emplace_back((p.is_absolute() ? p : dir / p).string());
+        try {
+            configs.emplace_back((p.is_absolute() ? p : dir / p).string());
+        } catch (const std::invalid_argument& e) {
+            icp::Logger(icp::LogLevel::Error) << e.what();
+            return 1;
+        }
+        if (!configs.back().params.refine.empty()) { icp::Logger(icp::LogLevel::Error) << "--batch: params.refine is not supported in a batch"; return 1; }
     }
     if (configs.empty()) { icp::Logger(icp::LogLevel::Error) << "--batch: " << list_file << " lists no config"; return 1; }
     const cli::Config& c0 = configs[0];
@@ -146,7 +152,14 @@ int main(int argc, char* argv[]) {
     if (config_file.empty()) fail("--config is required", 106);
     icp::Logger::set_verbose(verbose);
 
-    cli::Config config(config_file);
+    cli::Config config = [&] {
+        try {
+            return cli::Config(config_file);
+        } catch (const std::invalid_argument& e) {
+            icp::Logger(icp::LogLevel::Error) << e.what();
+            std::exit(1);
+        }
+    }();
     std::vector<icp::vec3> pct, pcs;
     cli::load_cloud(config.io.target, config.params.target_subsample, pct, config.params.seed);
     icp::Logger(icp::LogLevel::Info) << "Target point cloud (" << pct.size() << ") loaded from " << config.io.target;
@@ -179,13 +192,44 @@ int main(int argc, char* argv[]) {
         icp::check_status(fgoicp_solver_alignment(s, idx.data(), d2.data(), inl.data(), nullptr, &sm), "fgoicp_solver_alignment");
         cli::write_alignment_txt(config.io.alignment, pcs_in, idx.data(), d2.data(), inl.data(), sm);
     };
-    // io.information: the information matrix at the best transform, in the files' frame
+    // params.refine = "plane": point-to-plane refinement from the best transform, after the search (the search's own result stays as it is)
+    fgoicp_plane_result_t refined{};
+    bool have_refined = false;
+    auto refine = [&](fgoicp_solver* s) {
+        if (config.params.refine != "plane") return;
+        refined.struct_size = sizeof(refined);
+        const float d = config.params.refine_distance;
+        icp::check_status(fgoicp_solver_refine_plane(s, config.params.refine_knn, (size_t)config.params.refine_max_iter, 1e-6f, d > 0.0f ? d : INFINITY, &refined),
+                          "fgoicp_solver_refine_plane");
+        have_refined = true;
+        icp::mat3 Rr;
+        std::memcpy(Rr.data(), refined.R, sizeof(refined.R));
+        icp::Logger(icp::LogLevel::Info) << "Point-to-plane refinement: " << refined.iterations << " iterations, rank " << refined.rank << ", " << refined.correspondences
+                                         << " correspondences, plane RMSE " << refined.plane_rmse / (double)refined.scaling_factor << "\n\tRotation:\n" << Rr
+                                         << "\n\tTranslation: " << icp::vec3{refined.t[0], refined.t[1], refined.t[2]};
+    };
+    // io.information: the information matrix in the files' frame — at the best transform, or at the refined pose when there is one: then
+    // from the context at that pose in the solver's frame (the restored translation taken back, t_s = (t - R offset_pcs + offset_pct) * scale)
+    // and converted as fgoicp_solver_information converts (fgoicp_information_from_moments)
     auto write_information = [&](fgoicp_solver* s) {
         if (config.io.information.empty()) return;
         fgoicp_information_t inf{};
         inf.struct_size = sizeof(inf);
         const float d = config.params.information_distance;
-        icp::check_status(fgoicp_solver_information(s, d > 0.0f ? d : INFINITY, &inf), "fgoicp_solver_information");
+        if (!have_refined) {
+            icp::check_status(fgoicp_solver_information(s, d > 0.0f ? d : INFINITY, &inf), "fgoicp_solver_information");
+        } else {
+            float offs[6], scale = 1.0f;
+            icp::check_status(fgoicp_solver_preproc(s, offs, &scale, nullptr), "fgoicp_solver_preproc");
+            const float* Q = refined.R;
+            float ts[3];
+            for (int r = 0; r < 3; ++r) ts[r] = (refined.t[r] - (Q[r] * offs[0] + Q[3 + r] * offs[1] + Q[6 + r] * offs[2]) + offs[3 + r]) * scale;
+            const float ds = d * scale;
+            icp::check_status(fgoicp_information(fgoicp_solver_ctx(s), refined.R, ts, d > 0.0f ? ds * ds : INFINITY, &inf), "fgoicp_information");
+            const float c3[3] = {-offs[3], -offs[4], -offs[5]};
+            icp::check_status(fgoicp_information_from_moments(inf.correspondences, inf.sum_q, inf.sum_qq, c3, scale, inf.info, inf.sum_q, inf.sum_qq), "fgoicp_information_from_moments");
+            inf.scaling_factor = scale;
+        }
         cli::write_information_txt(config.io.information, inf, d);
     };
     if (gpus > 1) {
@@ -222,6 +266,7 @@ int main(int argc, char* argv[]) {
         }
         icp::check_status(fgoicp_solver_best_error(fgoicp_multi_solver(m, 0), &best_error), "fgoicp_solver_best_error");
         write_alignment(fgoicp_multi_solver(m, 0));
+        refine(fgoicp_multi_solver(m, 0));
         write_information(fgoicp_multi_solver(m, 0));
         fgoicp_multi_destroy(m);
         icp::Logger(icp::LogLevel::Info) << "Searching over! Best Error: " << best_error << "\n\tRotation:\n" << R << "\n\tTranslation: " << t;  // fgoicp.cpp:25-27
@@ -234,11 +279,12 @@ int main(int argc, char* argv[]) {
         st = fgoicp.stats();
         best_error = fgoicp.get_best_error();
         write_alignment(fgoicp.handle());
+        refine(fgoicp.handle());
         write_information(fgoicp.handle());
     }
     icp::Logger(icp::LogLevel::Debug) << "Subcubes: " << st.trans_cubes << ", rotation cubes: " << st.rot_cubes << ", ICP runs: " << st.icp_runs;
     icp::Logger(icp::LogLevel::Info) << "Fast Go-ICP finished, time elapsed: " << std::fixed << std::setprecision(3) << elapsed_seconds.count() << " seconds";
-    if (!config.io.output.empty()) cli::write_result_toml(config.io.output, R, t, best_error, pcs_in.size(), elapsed_seconds.count(), st);
+    if (!config.io.output.empty()) cli::write_result_toml(config.io.output, R, t, best_error, pcs_in.size(), elapsed_seconds.count(), st, have_refined ? &refined : nullptr);
     if (!config.io.visualization.empty()) cli::write_visualization_ply(config.io.visualization, pct_in, pcs_in, R, t);
     return 0;
 }

@@ -487,7 +487,9 @@ int ctx_sse(fgoicp_ctx* c, const float* R9, const float* t3, float* sse_out, con
 // Everything written is scratch that every other path fills before it reads (d_min_bits, d_work, d_thr_bits, d_sel, d_eq, d_use, the
 // pinned sums) or the report's own allocation; d_first_idx / d_first_idx2, the seeds of a later ICP pass, are not touched.
 // The device half: everything above is enqueued on lane 0's stream, nothing is waited for.
-static int alignment_enqueue(fgoicp_ctx* c, const float* R9, const float* t3) {
+// keep_moved: the index scan also stores its moved queries R p + t in L.d_work, device order (ctx_plane_moments reads them; the brute-force
+// path has them there anyway).
+static int alignment_enqueue(fgoicp_ctx* c, const float* R9, const float* t3, bool keep_moved = false) {
     HIPCHK(hipSetDevice(c->device));
     fgoicp_ctx::IcpLane& L = c->lanes[0];
     fgoicp_ctx::AlignScratch& A = c->align;
@@ -528,7 +530,7 @@ static int alignment_enqueue(fgoicp_ctx* c, const float* R9, const float* t3) {
         launch_nn_tie_threshold(L.d_min_bits, ns, L.d_thr_bits, st);
         launch_nn_first_index(L.d_work, ns, c->d_tgt, nt, L.d_thr_bits, A.d_idx, st);
     } else {
-        launch_nn_scan(c->d_src, ns, c->bvh_tgt.view(), c->d_lut, c->geom, R9, t3, 1, 1, c->d_tgt, nt, nullptr, nullptr, nullptr, A.d_idx, st);
+        launch_nn_scan(c->d_src, ns, c->bvh_tgt.view(), c->d_lut, c->geom, R9, t3, 1, 1, c->d_tgt, nt, nullptr, nullptr, nullptr, A.d_idx, st, keep_moved ? L.d_work : nullptr);
     }
     const unsigned char* use = nullptr;
     if (c->inliers) {
@@ -599,6 +601,139 @@ int ctx_alignment_information(fgoicp_ctx* c, const float* R9, const float* t3, u
     if (!rc) rc = information_enqueue(c, max_dist2);
     if (!rc) rc = alignment_copy_out(c, corr_idx, dist2, inlier, target_hit, out);
     return rc ? rc : information_copy_out(c, m);
+}
+
+// EXTENSION: target normals (fgoicp_ctx_set_target_normals).  Given: checked and normalised on the host (fp64), uploaded.  Estimated:
+// target_knn_kernel over the target's own tree, one launch.
+int ctx_set_target_normals(fgoicp_ctx* c, const float* normals, int k) {
+    const size_t nt = c->nt;
+    std::vector<float4> h;
+    if (normals) {
+        h.resize(nt);
+        for (size_t i = 0; i < nt; ++i) {
+            const double x = normals[3 * i], y = normals[3 * i + 1], z = normals[3 * i + 2];
+            const double len = std::sqrt(x * x + y * y + z * z);
+            if (!std::isfinite(len) || !(len > 0.0)) {
+                set_error("fgoicp_ctx_set_target_normals: normal " + std::to_string(i) + " is zero or not finite");
+                return FGOICP_ERR_INVALID_ARG;
+            }
+            h[i] = make_float4((float)(x / len), (float)(y / len), (float)(z / len), 0.f);
+        }
+    } else {
+        if (k < kKnnMin || k > kKnnMax || (size_t)k > nt) {
+            set_error("fgoicp_ctx_set_target_normals: k must lie in [4, 32] and be at most the number of target points");
+            return FGOICP_ERR_INVALID_ARG;
+        }
+        if (c->brute_force_nn) { set_error("fgoicp_ctx_set_target_normals: estimating normals needs the search tree, which a brute-force context does not build: pass normals"); return FGOICP_ERR_INVALID_ARG; }
+    }
+    HIPCHK(hipSetDevice(c->device));
+    if (!c->d_normals) HIPCHK(hipMalloc(&c->d_normals, sizeof(float4) * nt));
+    hipStream_t st = c->lanes[0].stream;
+    c->normals_set = false;
+    if (normals) {
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipMemcpy(c->d_normals, h.data(), sizeof(float4) * nt, hipMemcpyHostToDevice));
+    } else {
+        launch_target_knn(c->bvh_tgt.view(), c->d_tgt, (int)nt, k, nullptr, nullptr, c->d_normals, st);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    c->normals_set = true;
+    return FGOICP_OK;
+}
+int ctx_target_normals(fgoicp_ctx* c, float* out) {
+    if (!c->normals_set) { set_error("fgoicp_target_normals: the target normals are not set (fgoicp_ctx_set_target_normals)"); return FGOICP_ERR_INVALID_ARG; }
+    HIPCHK(hipSetDevice(c->device));
+    std::vector<float4> h(c->nt);
+    HIPCHK(hipStreamSynchronize(c->lanes[0].stream));
+    HIPCHK(hipMemcpy(h.data(), c->d_normals, sizeof(float4) * c->nt, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < c->nt; ++i) { out[3 * i] = h[i].x; out[3 * i + 1] = h[i].y; out[3 * i + 2] = h[i].z; }
+    return FGOICP_OK;
+}
+int ctx_target_knn(fgoicp_ctx* c, int k, uint32_t* idx, float* d2) {
+    if (k < kKnnMin || k > kKnnMax || (size_t)k > c->nt) { set_error("fgoicp_target_knn: k must lie in [4, 32] and be at most the number of target points"); return FGOICP_ERR_INVALID_ARG; }
+    if (c->brute_force_nn) { set_error("fgoicp_target_knn: needs the search tree, which a brute-force context does not build"); return FGOICP_ERR_INVALID_ARG; }
+    HIPCHK(hipSetDevice(c->device));
+    const size_t n = c->nt * (size_t)k;
+    uint32_t* d_idx = nullptr;
+    float* d_d2 = nullptr;
+    auto done = [&](int rc) { (void)hipFree(d_idx); (void)hipFree(d_d2); return rc; };
+    hipError_t e = hipSuccess;
+    if (idx) e = hipMalloc(&d_idx, sizeof(uint32_t) * n);
+    if (e == hipSuccess && d2) e = hipMalloc(&d_d2, sizeof(float) * n);
+    hipStream_t st = c->lanes[0].stream;
+    if (e == hipSuccess) {
+        launch_target_knn(c->bvh_tgt.view(), c->d_tgt, (int)c->nt, k, d_idx, d_d2, nullptr, st);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess && idx) e = hipMemcpy(idx, d_idx, sizeof(uint32_t) * n, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && d2) e = hipMemcpy(d2, d_d2, sizeof(float) * n, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) { set_error(std::string("fgoicp_target_knn: ") + hipGetErrorString(e)); return done(e == hipErrorOutOfMemory ? FGOICP_ERR_OOM : FGOICP_ERR_HIP); }
+    return done(FGOICP_OK);
+}
+
+// EXTENSION: the point-to-plane normal equations at (R, t) (fgoicp_plane_moments), enqueued behind the report's device half on lane 0's
+// stream like the information moments: reads the report's arrays, the moved queries the index scan left in d_work, the target and its
+// normals; writes its own rows only.
+int ctx_plane_moments(fgoicp_ctx* c, const float* R9, const float* t3, float max_dist2, PlaneMoments* m, float* sse_out) {
+    if (!c->normals_set) { set_error("the target normals are not set: call fgoicp_ctx_set_target_normals first"); return FGOICP_ERR_INVALID_ARG; }
+    HIPCHK(hipSetDevice(c->device));
+    if (!c->d_plane_rows) {
+        const size_t nblk = (c->ns + kBlock - 1) / kBlock;
+        HIPCHK(hipMalloc(&c->d_plane_rows, sizeof(PlaneRow) * nblk));
+        HIPCHK(hipMalloc(&c->d_plane_out, sizeof(unsigned long long) * (1 + kPlaneTerms)));
+    }
+    const int rc = alignment_enqueue(c, R9, t3, true);
+    if (rc) return rc;
+    fgoicp_ctx::IcpLane& L = c->lanes[0];
+    fgoicp_ctx::AlignScratch& A = c->align;
+    launch_plane_moments(L.d_work, c->d_orig_of_slot, A.d_inl, A.d_d2, A.d_corr, c->d_tgt, c->d_normals, (int)c->ns, (int)c->nt, max_dist2, c->d_plane_rows, c->d_plane_out,
+                         L.stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(L.stream));
+    unsigned long long h[1 + kPlaneTerms];
+    HIPCHK(hipMemcpy(h, c->d_plane_out, sizeof(h), hipMemcpyDeviceToHost));
+    static_assert(kPlaneTerms == kPlaneMoments, "the device's row and the host's moments are the same 28 terms");
+    m->n = h[0];
+    std::memcpy(m->m, h + 1, sizeof(m->m));
+    if (sse_out) *sse_out = sse_result(c, L);
+    return FGOICP_OK;
+}
+
+// fgoicp_icp_plane: evaluate, solve, update (plane.hpp), until the step is short, the first solve is rank-deficient, nothing is counted or
+// max_iter steps are done; the result's count, rmse and sse are those of one more evaluation at the pose returned.
+int ctx_icp_plane(fgoicp_ctx* c, const float* R0, const float* t0, size_t max_iter, float thr, float max_dist2, fgoicp_plane_result_t* full) {
+    Mat3f R = Mat3f::from(R0);
+    Vec3f t{t0[0], t0[1], t0[2]};
+    PlaneMoments m;
+    float sse = 0.f;
+    int iters = 0, rank = 0;
+    bool stop = false;
+    for (;;) {
+        const float t3[3] = {t.x, t.y, t.z};
+        const int rc = ctx_plane_moments(c, R.m, t3, max_dist2, &m, &sse);
+        if (rc) return rc;
+        if (stop || (size_t)iters >= max_iter || m.n == 0) break;
+        if (!plane_moments_finite(m.m)) { set_error("fgoicp_icp_plane: the normal equations are not finite"); return FGOICP_ERR_INVALID_ARG; }
+        double xi[6];
+        plane_step(m.m, xi, &rank);
+        plane_apply_step(R, t, xi, R, t);
+        ++iters;
+        const double step = std::sqrt(xi[0] * xi[0] + xi[1] * xi[1] + xi[2] * xi[2]) + std::sqrt(xi[3] * xi[3] + xi[4] * xi[4] + xi[5] * xi[5]);
+        stop = step < (double)thr || (iters == 1 && rank < 6);  // one more evaluation, at the pose returned, then out
+    }
+    std::memset(full, 0, sizeof(*full));  // the padding too: two results of the same inputs are the same bytes
+    full->struct_size = (uint32_t)sizeof(*full);
+    std::memcpy(full->R, R.m, sizeof(R.m));
+    full->t[0] = t.x; full->t[1] = t.y; full->t[2] = t.z;
+    full->iterations = iters;
+    full->rank = rank;
+    full->correspondences = m.n;
+    full->plane_rmse = m.n ? std::sqrt(m.m[27] / (double)m.n) : 0.0;
+    full->sse = sse;
+    full->scaling_factor = 1.0f;
+    return FGOICP_OK;
 }
 
 // IterativeClosestPoint3D::procrustes() on L.d_work — icp3d.cu:140-172.  The device half (enqueue only): correspondences
@@ -1598,6 +1733,7 @@ void fgoicp_ctx_destroy(fgoicp_ctx* c) {
     (void)hipFree(c->d_span_cen);
     (void)hipFree(c->d_orig_of_slot);
     (void)hipFree(c->align.base);
+    (void)hipFree(c->d_normals); (void)hipFree(c->d_plane_rows); (void)hipFree(c->d_plane_out);
     for (int k = 0; k < 2; ++k) {
         fgoicp_ctx::TickSlot& sl = c->slots[k];
         if (sl.done) (void)hipEventDestroy(sl.done);
@@ -1843,6 +1979,45 @@ int fgoicp_procrustes(fgoicp_ctx* c, const float* working_xyz, float* R_out9, fl
         for (size_t i = 0; i < c->ns; ++i) corr_idx[c->perm[i]] = (int)idx[i];
     }
     return FGOICP_OK;
+}
+
+int fgoicp_ctx_set_target_normals(fgoicp_ctx* c, const float* normals_nt3_or_NULL, int k) {
+    if (!c) { set_error("fgoicp_ctx_set_target_normals: the context must not be null"); return FGOICP_ERR_INVALID_ARG; }
+    return fgoicp::abi_guard("fgoicp_ctx_set_target_normals", [&] { return ctx_set_target_normals(c, normals_nt3_or_NULL, k); });
+}
+int fgoicp_target_normals(fgoicp_ctx* c, float* out_nt3) {
+    if (!c || !out_nt3) { set_error("fgoicp_target_normals: the context and the output must not be null"); return FGOICP_ERR_INVALID_ARG; }
+    return fgoicp::abi_guard("fgoicp_target_normals", [&] { return ctx_target_normals(c, out_nt3); });
+}
+int fgoicp_target_knn(fgoicp_ctx* c, int k, uint32_t* idx_ntk, float* d2_ntk) {
+    if (!c) { set_error("fgoicp_target_knn: the context must not be null"); return FGOICP_ERR_INVALID_ARG; }
+    return ctx_target_knn(c, k, idx_ntk, d2_ntk);
+}
+int fgoicp_plane_moments(fgoicp_ctx* c, const float* R9, const float* t3, float max_dist2, fgoicp_plane_moments_t* out) {
+    if (!c || !R9 || !t3) { set_error("fgoicp_plane_moments: the context, R and t must not be null"); return FGOICP_ERR_INVALID_ARG; }
+    if (!plane_size_ok(out)) { set_error("fgoicp_plane_moments: out must not be null and out->struct_size = sizeof(fgoicp_plane_moments_t)"); return FGOICP_ERR_INVALID_ARG; }
+    if (!(max_dist2 >= 0.0f)) { set_error("fgoicp_plane_moments: max_dist2 must be >= 0 (+inf: no threshold)"); return FGOICP_ERR_INVALID_ARG; }
+    if (!c->normals_set) { set_error("fgoicp_plane_moments: the target normals are not set: call fgoicp_ctx_set_target_normals first"); return FGOICP_ERR_INVALID_ARG; }
+    PlaneMoments m;
+    const int rc = ctx_plane_moments(c, R9, t3, max_dist2, &m);
+    if (rc) return rc;
+    fgoicp_plane_moments_t full;
+    std::memset(&full, 0, sizeof(full));
+    full.struct_size = (uint32_t)sizeof(full);
+    full.points = c->ns;
+    full.correspondences = m.n;
+    std::memcpy(full.m, m.m, sizeof(full.m));
+    full.max_dist2 = max_dist2;
+    return plane_out(full, out, "fgoicp_plane_moments", "fgoicp_plane_moments_t");
+}
+int fgoicp_icp_plane(fgoicp_ctx* c, const float* R0_9, const float* t0_3, size_t max_iter, float conv_thr, float max_dist2, fgoicp_plane_result_t* out) {
+    if (!c || !R0_9 || !t0_3) { set_error("fgoicp_icp_plane: the context, R0 and t0 must not be null"); return FGOICP_ERR_INVALID_ARG; }
+    if (!plane_size_ok(out)) { set_error("fgoicp_icp_plane: out must not be null and out->struct_size = sizeof(fgoicp_plane_result_t)"); return FGOICP_ERR_INVALID_ARG; }
+    if (!(max_dist2 >= 0.0f)) { set_error("fgoicp_icp_plane: max_dist2 must be >= 0 (+inf: no threshold)"); return FGOICP_ERR_INVALID_ARG; }
+    if (!c->normals_set) { set_error("fgoicp_icp_plane: the target normals are not set: call fgoicp_ctx_set_target_normals first"); return FGOICP_ERR_INVALID_ARG; }
+    fgoicp_plane_result_t full;
+    const int rc = ctx_icp_plane(c, R0_9, t0_3, max_iter, conv_thr, max_dist2, &full);
+    return rc ? rc : plane_out(full, out, "fgoicp_icp_plane", "fgoicp_plane_result_t");
 }
 
 int fgoicp_ctx_set_inliers(fgoicp_ctx* c, size_t k) {

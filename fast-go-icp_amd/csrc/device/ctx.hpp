@@ -14,6 +14,7 @@
 #include "../host/math3.hpp"
 #include "../host/abi_guard.hpp"
 #include "../host/information.hpp"
+#include "../host/plane.hpp"
 #include "bvh.hpp"
 #include "kernels.hpp"
 
@@ -125,6 +126,13 @@ struct fgoicp_ctx {
         unsigned long long* d_info = nullptr;    // {count, the bits of ten sums} (launch_align_info)
     } align;
 
+    // target normals and the point-to-plane normal equations (ctx_set_target_normals, ctx_plane_moments): each allocated by the first call
+    // that needs it — 16 bytes per target point, 232 per block of kBlock source points
+    float4* d_normals = nullptr;             // nt x {n.x, n.y, n.z, 0}, caller order; the zero vector: no normal
+    bool normals_set = false;
+    fgoicp::PlaneRow* d_plane_rows = nullptr;
+    unsigned long long* d_plane_out = nullptr;   // {count, the bits of 28 sums} (launch_plane_moments)
+
     // exact-NN / ICP scratch, one set per lane: ICP runs on different lanes may be in flight together (ctx_icp_batch).  Lane 0 is
     // the lane of fgoicp_sse / fgoicp_icp / fgoicp_procrustes and queues on the context's main stream.
     struct IcpLane {
@@ -198,6 +206,15 @@ int ctx_information(fgoicp_ctx* c, const float* R9, const float* t3, float max_d
 // both from one pass of the report's device half (fgoicp_batch with both options on): ctx_alignment's outputs and ctx_information's
 int ctx_alignment_information(fgoicp_ctx* c, const float* R9, const float* t3, uint32_t* corr_idx, float* dist2, uint8_t* inlier, uint8_t* target_hit,
                               fgoicp_alignment_summary* out, float max_dist2, InfoMoments* m);
+// EXTENSION: target normals and the point-to-plane refinement (include/fgoicp_amd.h).  normals = nullptr: estimated from k neighbours.
+int ctx_set_target_normals(fgoicp_ctx* c, const float* normals, int k);
+int ctx_target_normals(fgoicp_ctx* c, float* out_nt3);
+int ctx_target_knn(fgoicp_ctx* c, int k, uint32_t* idx, float* d2);
+// one evaluation on lane 0: the report's device half (its index scan keeps the moved queries), then launch_plane_moments.  max_dist2 must
+// have been checked (not NaN, >= 0) and the normals set.  sse_out (optional): the report's sse, the bits of fgoicp_sse.
+int ctx_plane_moments(fgoicp_ctx* c, const float* R9, const float* t3, float max_dist2, PlaneMoments* m, float* sse_out = nullptr);
+// fgoicp_icp_plane; `full` is filled whole (scaling_factor = 1)
+int ctx_icp_plane(fgoicp_ctx* c, const float* R0, const float* t0, size_t max_iter, float thr, float max_dist2, fgoicp_plane_result_t* full);
 // a summary handed to a caller: no byte beyond the struct_size the caller set is written (0, or less than the size field itself: refused)
 inline int alignment_summary_out(const fgoicp_alignment_summary& full, fgoicp_alignment_summary* out, const char* where) {
     if (!out) return FGOICP_OK;

@@ -17,6 +17,7 @@
 #include "../host/knobs.hpp"
 #include "slab.hpp"
 #include "bvh.hpp"
+#include "../host/math3.hpp"
 
 namespace fgoicp {
 namespace {
@@ -2577,6 +2578,224 @@ void launch_align_info(const unsigned char* inlier, const float* d2, const uint3
     const int nb = (n + kBlock - 1) / kBlock;
     hipLaunchKernelGGL(align_info_kernel, dim3(nb), dim3(kBlock), 0, s, inlier, d2, corr, tgt, n, nt, max_d2, rows);
     hipLaunchKernelGGL(align_info_fold_kernel, dim3(1), dim3(1024), 0, s, rows, nb, out11);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Target normals (fgoicp_ctx_set_target_normals, fgoicp_target_knn): the exact k nearest target points of every target point, the point
+// itself included, and the direction of least variance of those k points.
+// The queries are the tree's own points in leaf order: one wave = 64 consecutive slots = two neighbouring leaves, so the wave's query
+// region is two leaf boxes wide and its queries want the same leaves.  The walk is box_scan's (super-leaves, then leaves; a box is skipped
+// when its fp32 distance shrunk by 1e-6 relative exceeds the query's current k-th distance — strictly, so a box that may hold a tie at the
+// cut is visited).  Candidates are ordered by the key (bits(d2) << 32) | caller index, d2 the scans' fp32 dist_sq: squared distances are
+// >= 0, so the keys order like (distance, index) — a TOTAL order, hence the k smallest keys and their order do not depend on the order in
+// which the walk meets them, and a tie at the cut goes to the lowest caller index.
+// The list: k keys per thread in LDS, key j of lane l at [j * 64 + l] (a wave's access to one rank is 64 consecutive 8-byte words: no
+// bank conflict), kept sorted by insertion — a candidate that does not beat the k-th key costs one compare against a register.  One wave
+// per workgroup and k * 512 bytes of LDS: 16 KiB at k = 32 (10 waves per CU of the 160 KiB), 8 KiB at k = 16 (20 waves).  In registers the
+// list would be 2 k VGPRs indexed by a run-time rank, i.e. a fully unrolled compare-and-move chain per candidate.
+// The walk starts with the wave's own two leaves: they fill the list at once, and its k-th distance SEEDS the pruning bound of the real
+// walk, for which the list is emptied again (so no point is met twice and none needs to be recognised): every one of the true k nearest
+// lies within the seed.
+// Epilogue (normals != nullptr): centroid, then the covariance about it, of the k points in list order, in fp64 from the fp32 coordinates;
+// the normal is the eigenvector of the smallest eigenvalue by the two-sided Jacobi of math3.hpp (for a symmetric positive semi-definite
+// matrix its singular triplets are the eigenpairs, descending), normalised in fp64, stored as fp32.  Its SIGN is left as it falls.  A
+// neighbourhood whose largest eigenvalue is zero or not finite gets the zero vector.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void target_knn_kernel(BvhView t, const float4* __restrict__ tgt, int nt, int k, uint32_t* __restrict__ knn_idx,
+                                                        float* __restrict__ knn_d2, float4* __restrict__ normals) {
+    extern __shared__ unsigned long long s_knn[];  // [k][64]
+    const int lane = threadIdx.x;
+    const int slot = blockIdx.x * 64 + lane;
+    const bool active = slot < nt;
+    const float4 p = t.pts[active ? slot : nt - 1];
+    const float qx = p.x, qy = p.y, qz = p.z;
+    const unsigned long long kEmpty = ~0ull;
+    unsigned long long worst = kEmpty;  // the list's last key
+    auto clear = [&]() {
+        for (int j = 0; j < k; ++j) s_knn[j * 64 + lane] = kEmpty;
+        worst = kEmpty;
+    };
+    auto offer = [&](const float4 c, bool on) {
+        const uint32_t j = __float_as_uint(c.w);
+        if (!on || j >= (uint32_t)nt) return;  // padding points carry no caller index
+        const unsigned long long key = ((unsigned long long)__float_as_uint(dist_sq(qx, qy, qz, c.x, c.y, c.z)) << 32) | j;
+        if (!(key < worst)) return;
+        int pos = k - 1;
+        while (pos > 0) {
+            const unsigned long long v = s_knn[(pos - 1) * 64 + lane];
+            if (v < key) break;
+            s_knn[pos * 64 + lane] = v;
+            --pos;
+        }
+        s_knn[pos * 64 + lane] = key;
+        worst = s_knn[(k - 1) * 64 + lane];
+    };
+    auto kth = [&]() { return worst == kEmpty ? kMasked : __uint_as_float((uint32_t)(worst >> 32)); };
+    // the wave's own leaves
+    clear();
+    const int npts = (1 << t.depth) * kBvhLeaf;
+    for (int j = 0; j < 64; ++j) {
+        const int s = blockIdx.x * 64 + j;
+        if (s >= npts) break;
+        offer(t.pts[s], active);
+    }
+    const float seed = kth();
+    clear();
+    box_scan(t, qx, qy, qz, active, 0, 1, offer, [&]() { return fminf(seed, kth()); });
+    if (!active) return;
+    const uint32_t me = __float_as_uint(p.w);
+    if (knn_idx || knn_d2) {
+        for (int j = 0; j < k; ++j) {
+            const unsigned long long key = s_knn[j * 64 + lane];
+            if (knn_idx) knn_idx[(size_t)me * k + j] = (uint32_t)key;
+            if (knn_d2) knn_d2[(size_t)me * k + j] = __uint_as_float((uint32_t)(key >> 32));
+        }
+    }
+    if (!normals) return;
+    if (worst == kEmpty) {  // fewer than k points met: cannot happen with k <= nt; no index of the list is followed then
+        normals[me] = make_float4(0.f, 0.f, 0.f, 0.f);
+        return;
+    }
+    double cen[3] = {0.0, 0.0, 0.0};
+    for (int j = 0; j < k; ++j) {
+        const float4 c = tgt[(uint32_t)s_knn[j * 64 + lane]];
+        cen[0] += (double)c.x; cen[1] += (double)c.y; cen[2] += (double)c.z;
+    }
+    for (int a = 0; a < 3; ++a) cen[a] /= (double)k;
+    double C[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+    for (int j = 0; j < k; ++j) {
+        const float4 c = tgt[(uint32_t)s_knn[j * 64 + lane]];
+        const double d[3] = {(double)c.x - cen[0], (double)c.y - cen[1], (double)c.z - cen[2]};
+        for (int a = 0; a < 3; ++a)
+            for (int b = a; b < 3; ++b) C[a][b] += d[a] * d[b];
+    }
+    C[1][0] = C[0][1]; C[2][0] = C[0][2]; C[2][1] = C[1][2];
+    double U[3][3], S[3], V[3][3];
+    svd3_jacobi(C, U, S, V);
+    float4 out = make_float4(0.f, 0.f, 0.f, 0.f);
+    const double len = sqrt(V[0][2] * V[0][2] + V[1][2] * V[1][2] + V[2][2] * V[2][2]);
+    if (S[0] > 0.0 && S[0] <= 1.7976931348623157e308 && len > 0.5 && len < 2.0)
+        out = make_float4((float)(V[0][2] / len), (float)(V[1][2] / len), (float)(V[2][2] / len), 0.f);
+    normals[me] = out;
+}
+
+void launch_target_knn(const BvhView& t, const float4* tgt, int nt, int k, uint32_t* knn_idx, float* knn_d2, float4* normals, hipStream_t s) {
+    hipLaunchKernelGGL(target_knn_kernel, dim3((nt + 63) / 64), dim3(64), (size_t)k * 64 * sizeof(unsigned long long), s, t, tgt, nt, k, knn_idx, knn_d2, normals);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The point-to-plane normal equations (fgoicp_plane_moments) over the report's arrays.  One thread per device slot i: the moved query
+// x = R p + t as the report's index scan wrote it back (fp32, the scans' fma convention), the slot's caller index o, and the report's
+// entries of o.  COUNTED are the o with inlier[o] != 0, d2[o] <= max_d2, corr[o] < nt and a non-zero normal at corr[o].  With q the target
+// point corr[o], n its normal: r = n.(x - q), J = [ (x cross n)^T, n^T ] (twist order wx wy wz vx vy vz); every term is formed in fp64
+// from the fp32 inputs.  Reduced: the upper triangle of sum J^T J row by row (21), sum J^T r (6), sum r^2 (1), and the count — in
+// align_info_kernel's fixed order (wave butterfly, waves 0..3, one row per block; the fold adds rows t, t + 1024, ... in thread t, then
+// the same tree).  No atomics: the same arrays give the same bytes.  Every term is even in n: the sign of a normal does not matter.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void plane_moments_kernel(const float4* __restrict__ moved, const uint32_t* __restrict__ orig_of_slot,
+                                                               const unsigned char* __restrict__ inlier, const float* __restrict__ d2,
+                                                               const uint32_t* __restrict__ corr, const float4* __restrict__ tgt,
+                                                               const float4* __restrict__ normals, int n, int nt, float max_d2, PlaneRow* __restrict__ rows) {
+    __shared__ double s_v[kBlock / 64][kPlaneTerms];
+    __shared__ unsigned s_cnt[kBlock / 64];
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    double v[kPlaneTerms];
+#pragma unroll
+    for (int k = 0; k < kPlaneTerms; ++k) v[k] = 0.0;
+    unsigned cnt = 0u;
+    if (i < n) {
+        const uint32_t o = orig_of_slot[i];
+        if (o < (uint32_t)n) {
+            const uint32_t j = corr[o];
+            if (inlier[o] != 0 && d2[o] <= max_d2 && j < (uint32_t)nt) {
+                const float4 nn = normals[j];
+                if (nn.x != 0.0f || nn.y != 0.0f || nn.z != 0.0f) {
+                    const float4 x = moved[i], q = tgt[j];
+                    const double X[3] = {(double)x.x, (double)x.y, (double)x.z}, N[3] = {(double)nn.x, (double)nn.y, (double)nn.z};
+                    const double r = N[0] * (X[0] - (double)q.x) + N[1] * (X[1] - (double)q.y) + N[2] * (X[2] - (double)q.z);
+                    const double J[6] = {X[1] * N[2] - X[2] * N[1], X[2] * N[0] - X[0] * N[2], X[0] * N[1] - X[1] * N[0], N[0], N[1], N[2]};
+                    int m = 0;
+#pragma unroll
+                    for (int a = 0; a < 6; ++a)
+#pragma unroll
+                        for (int b = a; b < 6; ++b) v[m++] = J[a] * J[b];
+#pragma unroll
+                    for (int a = 0; a < 6; ++a) v[21 + a] = J[a] * r;
+                    v[27] = r * r;
+                    cnt = 1u;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
+#pragma unroll
+    for (int k = 0; k < kPlaneTerms; ++k) v[k] = wave_xor_sum(v[k]);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+        s_cnt[wave] = cnt;
+#pragma unroll
+        for (int k = 0; k < kPlaneTerms; ++k) s_v[wave][k] = v[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < kPlaneTerms) {
+        double r = s_v[0][threadIdx.x];
+#pragma unroll
+        for (int w = 1; w < kBlock / 64; ++w) r += s_v[w][threadIdx.x];
+        rows[blockIdx.x].v[threadIdx.x] = r;
+    }
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int w = 1; w < kBlock / 64; ++w) cnt += s_cnt[w];
+        rows[blockIdx.x].count = cnt;
+        rows[blockIdx.x].pad = 0u;
+    }
+}
+// One block of 1024 threads: out = {counted correspondences (one 64-bit integer), the bits of the 28 sums}.
+__global__ __launch_bounds__(1024) void plane_moments_fold_kernel(const PlaneRow* __restrict__ rows, int nrows, unsigned long long* __restrict__ out) {
+    __shared__ double s_v[16][kPlaneTerms];
+    __shared__ unsigned long long s_cnt[16];
+    double v[kPlaneTerms];
+#pragma unroll
+    for (int k = 0; k < kPlaneTerms; ++k) v[k] = 0.0;
+    unsigned long long cnt = 0ull;
+    for (int b = threadIdx.x; b < nrows; b += 1024) {
+        cnt += rows[b].count;
+#pragma unroll
+        for (int k = 0; k < kPlaneTerms; ++k) v[k] += rows[b].v[k];
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned lo = __shfl_xor((unsigned)cnt, off, 64), hi = __shfl_xor((unsigned)(cnt >> 32), off, 64);
+        cnt += ((unsigned long long)hi << 32) | lo;
+    }
+#pragma unroll
+    for (int k = 0; k < kPlaneTerms; ++k) v[k] = wave_xor_sum(v[k]);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+        s_cnt[wave] = cnt;
+#pragma unroll
+        for (int k = 0; k < kPlaneTerms; ++k) s_v[wave][k] = v[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < kPlaneTerms) {
+        double r = s_v[0][threadIdx.x];
+#pragma unroll
+        for (int w = 1; w < 16; ++w) r += s_v[w][threadIdx.x];
+        out[1 + threadIdx.x] = (unsigned long long)__double_as_longlong(r);
+    }
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int w = 1; w < 16; ++w) cnt += s_cnt[w];
+        out[0] = cnt;
+    }
+}
+
+void launch_plane_moments(const float4* moved, const uint32_t* orig_of_slot, const unsigned char* inlier, const float* d2, const uint32_t* corr, const float4* tgt,
+                          const float4* normals, int n, int nt, float max_d2, PlaneRow* rows, unsigned long long* out29, hipStream_t s) {
+    const int nb = (n + kBlock - 1) / kBlock;
+    hipLaunchKernelGGL(plane_moments_kernel, dim3(nb), dim3(kBlock), 0, s, moved, orig_of_slot, inlier, d2, corr, tgt, normals, n, nt, max_d2, rows);
+    hipLaunchKernelGGL(plane_moments_fold_kernel, dim3(1), dim3(1024), 0, s, rows, nb, out29);
 }
 
 }  // namespace fgoicp

@@ -118,6 +118,23 @@ struct AlignInfoRow {
 };
 void launch_align_info(const unsigned char* inlier, const float* d2, const uint32_t* corr, const float4* tgt, int n, int nt, float max_d2, AlignInfoRow* rows,
                        unsigned long long* out11, hipStream_t s);
+// Target normals (fgoicp_ctx_set_target_normals, fgoicp_target_knn; kernels.hip target_knn_kernel): per target point its k nearest target points
+// (itself included) by the total order (bits of the fp32 squared distance, caller index), and the unit direction of least variance of
+// those k points.  4 <= k <= 32, k <= nt.  knn_idx / knn_d2 (optional): nt rows of k entries, rows and indices in caller order;
+// normals (optional): nt x {n.x, n.y, n.z, 0} in caller order, the zero vector for a degenerate neighbourhood.
+constexpr int kKnnMin = 4, kKnnMax = 32;
+void launch_target_knn(const BvhView& t, const float4* tgt, int nt, int k, uint32_t* knn_idx, float* knn_d2, float4* normals, hipStream_t s);
+// The point-to-plane normal equations (fgoicp_plane_moments; kernels.hip plane_moments_kernel, plane_moments_fold_kernel) over the report's
+// arrays (caller order) and the moved queries of its index scan (device order, `moved`): counted are the caller indices with inlier != 0,
+// d2 <= max_d2, corr < nt and a non-zero normal at corr.  rows: ceil(n / kBlock) entries; out29 = {count, the bits of 28 doubles: the
+// upper triangle of sum J^T J row by row (21), sum J^T r (6), sum r^2}.  Fixed order of every addition.
+constexpr int kPlaneTerms = 28;
+struct PlaneRow {
+    uint32_t count, pad;
+    double v[kPlaneTerms];
+};
+void launch_plane_moments(const float4* moved, const uint32_t* orig_of_slot, const unsigned char* inlier, const float* d2, const uint32_t* corr, const float4* tgt,
+                          const float4* normals, int n, int nt, float max_d2, PlaneRow* rows, unsigned long long* out29, hipStream_t s);
 // The bounds of many registrations in one launch (fgoicp_batch, bounds_fused.hpp): a view per pair of the batch, an evaluation per output
 // row, work items {evaluation, chunk}.  Every row is the bits its pair's own context computes with thresholds off.
 struct FusedPairView {

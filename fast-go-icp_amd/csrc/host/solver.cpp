@@ -282,6 +282,52 @@ int fgoicp_solver_information(fgoicp_solver* s, float max_distance, fgoicp_infor
     return information_out(full, out, "fgoicp_solver_information");
 }
 
+int fgoicp_solver_refine_plane(fgoicp_solver* s, int k, size_t max_iter, float conv_thr, float max_distance, fgoicp_plane_result_t* out) {
+    if (!s) { set_error("fgoicp_solver_refine_plane: the solver must not be null"); return FGOICP_ERR_INVALID_ARG; }
+    if (!s->ran) { set_error("fgoicp_solver_refine_plane: fgoicp_solver_run has not succeeded yet: there is no best transform"); return FGOICP_ERR_INVALID_ARG; }
+    if (!plane_size_ok(out)) { set_error("fgoicp_solver_refine_plane: out must not be null and out->struct_size = sizeof(fgoicp_plane_result_t)"); return FGOICP_ERR_INVALID_ARG; }
+    if (!(max_distance >= 0.0f)) { set_error("fgoicp_solver_refine_plane: max_distance must be >= 0 (+inf: no threshold)"); return FGOICP_ERR_INVALID_ARG; }
+    return fgoicp::abi_guard("fgoicp_solver_refine_plane", [&] {
+        if (!s->ctx->normals_set) {  // normals are invariant under the solver's centring and uniform scale
+            const int rc = ctx_set_target_normals(s->ctx, nullptr, k);
+            if (rc) return rc;
+        }
+        Mat3f R;
+        Vec3f t;
+        s->driver->best_transform(R, t);  // the normalised frame the search ran in, as fgoicp_solver_information
+        const float t3[3] = {t.x, t.y, t.z};
+        fgoicp_plane_result_t full;
+        const int rc = ctx_icp_plane(s->ctx, R.m, t3, max_iter, conv_thr, information_max_dist2(max_distance, s->scaling_factor), &full);
+        if (rc) return rc;
+        const Mat3f Rr = Mat3f::from(full.R);
+        const Vec3f ts{full.t[0], full.t[1], full.t[2]};
+        const Vec3f tr = ts / s->scaling_factor + Rr * s->offset_pcs - s->offset_pct;  // restore_translation, fgoicp.hpp:87-90
+        full.t[0] = tr.x; full.t[1] = tr.y; full.t[2] = tr.z;
+        full.scaling_factor = s->scaling_factor;
+        return plane_out(full, out, "fgoicp_solver_refine_plane", "fgoicp_plane_result_t");
+    });
+}
+
+int fgoicp_plane_step_from_moments(uint64_t n, const double* m28, double* xi6, int* rank) {
+    if (!m28 || !xi6 || !rank) { set_error("fgoicp_plane_step_from_moments: m28, xi6 and rank must not be null"); return FGOICP_ERR_INVALID_ARG; }
+    if (n == 0) { set_error("fgoicp_plane_step_from_moments: n = 0: nothing was counted, there is no step"); return FGOICP_ERR_INVALID_ARG; }
+    if (!plane_moments_finite(m28)) { set_error("fgoicp_plane_step_from_moments: a moment is not finite"); return FGOICP_ERR_INVALID_ARG; }
+    plane_step(m28, xi6, rank);
+    return FGOICP_OK;
+}
+
+int fgoicp_plane_apply_step(const float* R9, const float* t3, const double* xi6, float* R_out9, float* t_out3) {
+    if (!R9 || !t3 || !xi6 || !R_out9 || !t_out3) { set_error("fgoicp_plane_apply_step: no argument may be null"); return FGOICP_ERR_INVALID_ARG; }
+    for (int k = 0; k < 6; ++k)
+        if (!std::isfinite(xi6[k])) { set_error("fgoicp_plane_apply_step: the step is not finite"); return FGOICP_ERR_INVALID_ARG; }
+    Mat3f R;
+    Vec3f t;
+    plane_apply_step(Mat3f::from(R9), Vec3f{t3[0], t3[1], t3[2]}, xi6, R, t);
+    std::memcpy(R_out9, R.m, sizeof(R.m));
+    t_out3[0] = t.x; t_out3[1] = t.y; t_out3[2] = t.z;
+    return FGOICP_OK;
+}
+
 int fgoicp_information_from_moments(uint64_t n, const double* sum_q3, const double* sum_qq6, const float* offset3, float scale, double* info36, double* sum_q3_out,
                                     double* sum_qq6_out) {
     if (!sum_q3 || !sum_qq6) { set_error("fgoicp_information_from_moments: sum_q3 and sum_qq6 must not be null"); return FGOICP_ERR_INVALID_ARG; }

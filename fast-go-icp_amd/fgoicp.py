@@ -6,7 +6,7 @@ import numpy as np
 
 from . import _lib
 from .nodes import from_glm
-from .registration import Registration, _alignment, _cloud, _fp, _information
+from .registration import PlaneRefinement, Registration, _alignment, _cloud, _fp, _information
 
 
 class FastGoICP:
@@ -64,6 +64,15 @@ class FastGoICP:
         dist2 <= (float32(max_distance) * scale)^2, evaluated in float32."""
         d = float("inf") if max_distance is None else float(max_distance)
         return _information(lambda out: self._lib.fgoicp_solver_information(self._h, d, out), "fgoicp_solver_information")
+
+    def refine_plane(self, k=16, max_iter=30, conv_thr=1e-6, max_distance=None):
+        """EXTENSION (fgoicp_solver_refine_plane): point-to-plane ICP from the best transform, after run() -> PlaneRefinement with R and t
+        in the callers' frame.  The target's normals are estimated from k neighbours unless the registration already has some;
+        max_distance: callers' units (None: no threshold), as information() takes it.  run() and the best transform are untouched."""
+        d = float("inf") if max_distance is None else float(max_distance)
+        raw = _lib.PlaneResult()
+        _lib.check(self._lib.fgoicp_solver_refine_plane(self._h, int(k), int(max_iter), float(conv_thr), d, C.byref(raw)), "fgoicp_solver_refine_plane")
+        return PlaneRefinement(raw)
 
     def _transform(self, fn, name):
         R = np.empty(9, np.float32); t = np.empty(3, np.float32)

@@ -119,6 +119,54 @@ def information_from_moments(n, sum_q, sum_qq, offset=None, scale=1.0):
     return info.reshape(6, 6), qo, qqo
 
 
+class PlaneMomentsResult:
+    """EXTENSION (fgoicp_plane_moments): the point-to-plane normal equations at one pose — JtJ (6, 6) float64 = sum J^T J, Jtr (6,) = sum
+    J^T r, sum_r2, over `correspondences` counted points, with J = [(x cross n)^T, n^T], r = n.(x - q), twist order (wx, wy, wz, vx, vy, vz);
+    m (28,): the sums as the library returned them (upper triangle row by row, J^T r, r^2)."""
+
+    def __init__(self, raw):
+        self.m = np.array(raw.m, np.float64)
+        self.points, self.correspondences = int(raw.points), int(raw.correspondences)
+        self.JtJ = np.zeros((6, 6))
+        self.JtJ[np.triu_indices(6)] = self.m[:21]
+        self.JtJ = self.JtJ + np.triu(self.JtJ, 1).T
+        self.Jtr, self.sum_r2 = self.m[21:27].copy(), float(self.m[27])
+        self.max_dist2 = np.float32(raw.max_dist2)
+        self.raw = bytes(raw)  # the struct as the library filled it (two results of the same inputs are the same bytes)
+
+
+class PlaneRefinement:
+    """EXTENSION (fgoicp_icp_plane / fgoicp_solver_refine_plane): R (3, 3), t (3,) — the refined pose (a solver's: t in the callers' frame);
+    iterations; rank of the last solve (6: well posed); correspondences counted at the returned pose; plane_rmse — root mean squared
+    point-to-plane residual there, in the callers' units; sse — compute_sse_error(R, t) there, bit for bit, in the frame the search ran in."""
+
+    def __init__(self, raw):
+        self.R, self.t = from_glm(np.array(raw.R, np.float32)), np.array(raw.t, np.float32)
+        self.iterations, self.rank, self.correspondences = int(raw.iterations), int(raw.rank), int(raw.correspondences)
+        self.scaling_factor = np.float32(raw.scaling_factor)
+        self.plane_rmse_scaled = float(raw.plane_rmse)
+        self.plane_rmse = float(raw.plane_rmse / np.float64(raw.scaling_factor))
+        self.sse = np.float32(raw.sse)
+        self.raw = bytes(raw)
+
+
+def plane_step_from_moments(n, m28):
+    """fgoicp_plane_step_from_moments (host only): -> (xi (6,) float64 = (w, v), rank) of (sum J^T J) xi = -sum J^T r."""
+    m = np.ascontiguousarray(m28, np.float64).reshape(28)
+    xi = np.empty(6, np.float64); rank = C.c_int()
+    dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+    _lib.check(_lib.load().fgoicp_plane_step_from_moments(int(n), dp(m), dp(xi), C.byref(rank)), "fgoicp_plane_step_from_moments")
+    return xi, rank.value
+
+
+def plane_apply_step(R, t, xi):
+    """fgoicp_plane_apply_step (host only): -> (R', t') = (Rod(w) R, Rod(w) t + v), R' the rotation nearest to the float32 product."""
+    Rg = to_glm(R); tt = np.ascontiguousarray(t, np.float32).reshape(3); x = np.ascontiguousarray(xi, np.float64).reshape(6)
+    Ro = np.empty(9, np.float32); to = np.empty(3, np.float32)
+    _lib.check(_lib.load().fgoicp_plane_apply_step(_fp(Rg), _fp(tt), x.ctypes.data_as(C.POINTER(C.c_double)), _fp(Ro), _fp(to)), "fgoicp_plane_apply_step")
+    return from_glm(Ro), to
+
+
 class Registration:
     """icp::Registration (fgoicp/registration.hpp:49-98) + its NearestNeighborLUT member."""
 
@@ -222,6 +270,46 @@ class Registration:
         Rg = to_glm(R)
         tt = np.ascontiguousarray(t, dtype=np.float32).reshape(3)
         return _information(lambda out: self._lib.fgoicp_information(self._h, _fp(Rg), _fp(tt), float(max_dist2), out), "fgoicp_information")
+
+    def set_target_normals(self, normals=None, k=16):
+        """EXTENSION (fgoicp_ctx_set_target_normals): normals (nt, 3) are normalised and uploaded; None: estimated on the device from
+        every target point's k nearest target points (4 <= k <= 32).  The sign of an estimated normal is arbitrary (nothing depends on it)."""
+        if normals is None:
+            _lib.check(self._lib.fgoicp_ctx_set_target_normals(self._h, None, int(k)), "fgoicp_ctx_set_target_normals")
+            return
+        n = _cloud(normals)
+        if len(n) != self.nt:
+            raise ValueError("normals must be (nt, 3)")
+        _lib.check(self._lib.fgoicp_ctx_set_target_normals(self._h, _fp(n), int(k)), "fgoicp_ctx_set_target_normals")
+
+    def target_normals(self):
+        """fgoicp_target_normals: (nt, 3) float32 unit normals in the caller's order (zero rows: degenerate neighbourhoods)."""
+        out = np.empty((self.nt, 3), np.float32)
+        _lib.check(self._lib.fgoicp_target_normals(self._h, _fp(out)), "fgoicp_target_normals")
+        return out
+
+    def target_knn(self, k):
+        """fgoicp_target_knn: (indices (nt, k) uint32, dist2 (nt, k) float32) — every target point's k nearest target points, itself
+        included, sorted by (squared distance, index)."""
+        idx = np.empty((self.nt, int(k)), np.uint32); d2 = np.empty((self.nt, int(k)), np.float32)
+        _lib.check(self._lib.fgoicp_target_knn(self._h, int(k), idx.ctypes.data_as(_lib.c_uint32_p), _fp(d2)), "fgoicp_target_knn")
+        return idx, d2
+
+    def plane_moments(self, R, t, max_dist2=np.inf):
+        """EXTENSION (fgoicp_plane_moments): the PlaneMomentsResult of R*pcs + t against the target and its normals."""
+        Rg = to_glm(R)
+        tt = np.ascontiguousarray(t, dtype=np.float32).reshape(3)
+        raw = _lib.PlaneMoments()
+        _lib.check(self._lib.fgoicp_plane_moments(self._h, _fp(Rg), _fp(tt), float(max_dist2), C.byref(raw)), "fgoicp_plane_moments")
+        return PlaneMomentsResult(raw)
+
+    def icp_plane(self, R, t, max_iter=30, conv_thr=1e-6, max_dist2=np.inf):
+        """EXTENSION (fgoicp_icp_plane): point-to-plane ICP from (R, t) -> PlaneRefinement.  max_iter = 0 evaluates the start."""
+        Rg = to_glm(R)
+        tt = np.ascontiguousarray(t, dtype=np.float32).reshape(3)
+        raw = _lib.PlaneResult()
+        _lib.check(self._lib.fgoicp_icp_plane(self._h, _fp(Rg), _fp(tt), int(max_iter), float(conv_thr), float(max_dist2), C.byref(raw)), "fgoicp_icp_plane")
+        return PlaneRefinement(raw)
 
     def compute_bounds(self, R, rot_span, tnodes, fix_rot):
         Rg = to_glm(R)

@@ -58,6 +58,15 @@ public:
         check_status(fgoicp_solver_information(s_, max_distance, &f.result), "fgoicp_solver_information");
         return f;
     }
+    // EXTENSION: point-to-plane refinement from the best transform, after run() (fgoicp_solver_refine_plane): R and t in the callers'
+    // frame; normals estimated from k neighbours unless the context has some; max_distance in the callers' units, INFINITY: no threshold.
+    // run() and the best transform are untouched.
+    PlaneRefinement refine_plane(int k = 16, size_t max_iter = 30, float conv_thr = 1e-6f, float max_distance = INFINITY) const {
+        PlaneRefinement p;
+        p.result.struct_size = sizeof(p.result);
+        check_status(fgoicp_solver_refine_plane(s_, k, max_iter, conv_thr, max_distance, &p.result), "fgoicp_solver_refine_plane");
+        return p;
+    }
     fgoicp_run_stats stats() const { fgoicp_run_stats st{}; check_status(fgoicp_solver_stats(s_, &st), "fgoicp_solver_stats"); return st; }
     fgoicp_solver* handle() const { return s_; }
     // the reference's own lines while the search runs (fgoicp.cpp:15-17 Info, :85-87 Debug), from the driver's log events

@@ -63,6 +63,21 @@ struct Information {
     double inlier_rmse() const { return result.correspondences ? std::sqrt(result.sum_dist2 / (double)result.correspondences) / (double)result.scaling_factor : 0.0; }  // callers' units
 };
 
+// EXTENSION (ours): point-to-plane refinement with target normals (fgoicp_ctx_set_target_normals, fgoicp_plane_moments, fgoicp_icp_plane,
+// fgoicp_solver_refine_plane).  PlaneRefinement::result holds the refined pose (glm order), the iterations, the rank of the last solve,
+// the counted correspondences, and plane_rmse / sse in the frame the search ran in.
+struct PlaneRefinement {
+    fgoicp_plane_result_t result{};
+    mat3 R() const { mat3 m; for (int k = 0; k < 9; ++k) m.data()[k] = result.R[k]; return m; }
+    vec3 t() const { return vec3{result.t[0], result.t[1], result.t[2]}; }
+    double plane_rmse() const { return result.plane_rmse / (double)result.scaling_factor; }  // callers' units
+};
+struct TargetKnn {
+    std::vector<uint32_t> indices;  // nt rows of k: every target point's k nearest target points, itself included, sorted by (distance, index)
+    std::vector<float> dist2;
+    int k = 0;
+};
+
 class Registration {
 public:
     // registration.hpp:68
@@ -111,6 +126,36 @@ public:
         f.result.struct_size = sizeof(f.result);
         check_status(fgoicp_information(ctx_, R.data(), &t.x, max_dist2, &f.result), "fgoicp_information");
         return f;
+    }
+
+    // EXTENSION: target normals — given (nt unit or non-unit vectors, normalised on upload), or estimated on the device from every target
+    // point's k nearest target points (4 <= k <= 32); the sign of an estimated normal is arbitrary and nothing depends on it
+    void set_target_normals(const PointCloud& normals) { check_status(fgoicp_ctx_set_target_normals(ctx_, &normals.data()->x, 0), "fgoicp_ctx_set_target_normals"); }
+    void set_target_normals(int k = 16) { check_status(fgoicp_ctx_set_target_normals(ctx_, nullptr, k), "fgoicp_ctx_set_target_normals"); }
+    PointCloud target_normals() const {
+        PointCloud n(nt);
+        check_status(fgoicp_target_normals(ctx_, &n.data()->x), "fgoicp_target_normals");
+        return n;
+    }
+    TargetKnn target_knn(int k) const {
+        TargetKnn r;
+        r.k = k;
+        r.indices.resize(nt * (size_t)(k > 0 ? k : 0)); r.dist2.resize(r.indices.size());
+        check_status(fgoicp_target_knn(ctx_, k, r.indices.data(), r.dist2.data()), "fgoicp_target_knn");
+        return r;
+    }
+    // EXTENSION: the point-to-plane normal equations of R*pcs + t (fgoicp_plane_moments) and the loop from (R, t) (fgoicp_icp_plane)
+    fgoicp_plane_moments_t plane_moments(mat3 R, vec3 t, float max_dist2 = INFINITY) const {
+        fgoicp_plane_moments_t m{};
+        m.struct_size = sizeof(m);
+        check_status(fgoicp_plane_moments(ctx_, R.data(), &t.x, max_dist2, &m), "fgoicp_plane_moments");
+        return m;
+    }
+    PlaneRefinement icp_plane(mat3 R, vec3 t, size_t max_iter = 30, float conv_thr = 1e-6f, float max_dist2 = INFINITY) const {
+        PlaneRefinement p;
+        p.result.struct_size = sizeof(p.result);
+        check_status(fgoicp_icp_plane(ctx_, R.data(), &t.x, max_iter, conv_thr, max_dist2, &p.result), "fgoicp_icp_plane");
+        return p;
     }
 
     fgoicp_ctx* handle() const { return ctx_; }

@@ -219,6 +219,63 @@ int fgoicp_information(fgoicp_ctx* ctx, const float* R9, const float* t3, float 
 int fgoicp_information_from_moments(uint64_t n, const double* sum_q3, const double* sum_qq6, const float* offset3, float scale, double* info36,
                                     double* sum_q3_out, double* sum_qq6_out);
 
+/*
+ * EXTENSION — point-to-plane refinement with target normals (no reference counterpart; what a multiway-registration pipeline runs from the
+ * global result before it takes the pose-graph edge).
+ *
+ * Target normals.  fgoicp_ctx_set_target_normals with a pointer takes the caller's normals (nt triples, caller order), normalised on upload;
+ * a non-finite or zero vector is refused (FGOICP_ERR_INVALID_ARG) before any device work; k is ignored.  With NULL the normals are ESTIMATED
+ * on the device: per target point the unit direction of least variance of its k nearest target points, the point itself included
+ * (4 <= k <= 32, k <= nt; needs the search tree, so a FGOICP_FLAG_BRUTE_FORCE_NN context is refused).  The neighbours are exact: the k
+ * smallest of the fp32 squared distances the scans compute, ordered by (distance, caller index) — ties at the cut go to the lowest index.
+ * The SIGN of an estimated normal is left as it falls: everything below is even in n (r n = (-r)(-n), J^T J and J^T r likewise), so
+ * normals need not be oriented.  A degenerate neighbourhood (all k points equal) gets the zero vector, which takes its point out of the
+ * counted set below.  The array is 16 bytes per target point, allocated by the first call; a context that never asks allocates nothing.
+ * fgoicp_target_normals reads them back (nt triples, caller order; refused before they are set).  fgoicp_target_knn returns the
+ * neighbour sets themselves: nt rows of k, rows and indices in caller order, each row sorted by (distance, index); either output may be NULL.
+ *
+ * The normal equations.  For (R, t) the COUNTED correspondences are the source points i that the alignment report marks an inlier, with
+ * dist2[i] <= max_dist2 (+inf: no threshold; NaN and negative values refused), corr_idx[i] < nt and a non-zero normal at corr_idx[i].  With
+ * x = R p_i + t (fp32, as the report's scan forms it), q the target point, n its normal: r = n.(x - q), J = [ (x cross n)^T, n^T ], twist
+ * order (wx, wy, wz, vx, vy, vz).  m[28] = the upper triangle of sum J^T J row by row (21), sum J^T r (6), sum r^2 (1), every term formed in
+ * fp64 and added in a fixed order (two calls return the same bytes).  Context frame.
+ */
+typedef struct fgoicp_plane_moments_t {
+    uint32_t struct_size;             /* IN: sizeof(fgoicp_plane_moments_t) as the CALLER was compiled; no byte beyond it is written, 0 is refused */
+    uint64_t points, correspondences; /* ns; the counted correspondences N */
+    double   m[28];
+    float    max_dist2;               /* the threshold the device compared with */
+} fgoicp_plane_moments_t;
+typedef struct fgoicp_plane_result_t {
+    uint32_t struct_size;             /* IN: sizeof(fgoicp_plane_result_t) as the CALLER was compiled; no byte beyond it is written, 0 is refused */
+    float    R[9], t[3];              /* the refined pose (fgoicp_solver_refine_plane: t restored to the callers' frame) */
+    int      iterations;              /* steps taken */
+    int      rank;                    /* of the last solve (6: well posed; 0 when max_iter = 0 or nothing was counted) */
+    uint64_t correspondences;         /* counted at the returned pose */
+    double   plane_rmse;              /* sqrt(sum r^2 / N) at the returned pose, context frame (0 when N = 0); / scaling_factor: callers' units */
+    float    sse;                     /* == fgoicp_sse(ctx, R, t) at the returned pose, bit for bit (context frame) */
+    float    scaling_factor;          /* 1 for a bare context; the solver's scale otherwise */
+} fgoicp_plane_result_t;
+int fgoicp_ctx_set_target_normals(fgoicp_ctx* ctx, const float* normals_nt3_or_NULL, int k);
+int fgoicp_target_normals(fgoicp_ctx* ctx, float* out_nt3);
+int fgoicp_target_knn(fgoicp_ctx* ctx, int k, uint32_t* idx_ntk, float* d2_ntk);
+/* One evaluation at a fixed pose: the report's device half, then the reduction.  Refused when the normals are not set.  Leaves the
+ * context as it found it, as fgoicp_alignment does. */
+int fgoicp_plane_moments(fgoicp_ctx* ctx, const float* R9, const float* t3, float max_dist2, fgoicp_plane_moments_t* out);
+/* Host only, no device needed: solves (sum J^T J) xi = -sum J^T r in fp64 by a symmetric eigen-decomposition (6 x 6 Jacobi).  rank = the
+ * number of eigenvalues above 1e-9 x the largest; with rank < 6 the solution lies in the span of the kept eigenvectors (a planar target:
+ * rank 3, the in-plane motions stay zero).  Refuses null arguments, n = 0 and a non-finite moment. */
+int fgoicp_plane_step_from_moments(uint64_t n, const double* m28, double* xi6, int* rank);
+/* Host only: the pose update of a step, R' = Rod(w) R, t' = Rod(w) t + v with Rod = Rodrigues' formula in fp64; R' is rounded to fp32
+ * once and then replaced by the rotation nearest to it (closest_orthogonal_approximation).  The outputs may alias the inputs. */
+int fgoicp_plane_apply_step(const float* R9, const float* t3, const double* xi6, float* R_out9, float* t_out3);
+/* The loop from (R0, t0): moments at (R, t), the step, the update; it ends after the step with |w| + |v| < conv_thr, after the first
+ * step when that solve had rank < 6 (the unconstrained motions would drift), when nothing is counted, or after max_iter steps.
+ * max_iter = 0 evaluates and returns the start.  On a trimmed context the inliers are the report's, selected anew in every iteration.
+ * Refused when the normals are not set.  Leaves the context as it found it: a later fgoicp_icp, fgoicp_sse or solver run returns the
+ * bits it returns without this call. */
+int fgoicp_icp_plane(fgoicp_ctx* ctx, const float* R0_9, const float* t0_3, size_t max_iter, float conv_thr, float max_dist2, fgoicp_plane_result_t* out);
+
 /* Replaces IterativeClosestPoint3D(reg, pct, pcs, max_iter, thr, R, t) + run()
  * (fgoicp/icp3d.hpp:30-35, icp3d.cu:55-108).  Returns the reference's Result_t {sse, R, t}
  * plus the number of loop iterations executed. */
@@ -378,6 +435,14 @@ int fgoicp_solver_alignment(fgoicp_solver* s, uint32_t* corr_idx_ns, float* dist
  * before that the call is refused (FGOICP_ERR_INVALID_ARG).  max_distance: callers' units, +inf = no threshold, NaN and negative values
  * refused.  A later fgoicp_solver_run returns what it returned before. */
 int fgoicp_solver_information(fgoicp_solver* s, float max_distance, fgoicp_information_t* out);
+/* EXTENSION: fgoicp_icp_plane from the best transform the solver holds, after a successful fgoicp_solver_run — before that the call is
+ * refused (FGOICP_ERR_INVALID_ARG).  If the context has no normals yet they are estimated with k neighbours (normals are invariant under
+ * the solver's centring and uniform scale).  max_distance: callers' units, converted as fgoicp_solver_information converts it
+ * (ds = (float)max_distance * scale; max_dist2 = ds * ds); +inf = no threshold.  out->R and out->t: the refined pose in the CALLERS' frame
+ * (the translation restored as fgoicp_solver_run restores it); plane_rmse and sse stay in the solver's frame (scaling_factor converts).
+ * The solver's own best transform, best error and a later fgoicp_solver_run are untouched.  On a multi-GPU run every rank answers from
+ * its own context. */
+int fgoicp_solver_refine_plane(fgoicp_solver* s, int k, size_t max_iter, float conv_thr, float max_distance, fgoicp_plane_result_t* out);
 /* Pre-processing results (tests): offs6 = {offset_pcs, offset_pct}, bounds6 as in ctx_create. */
 int fgoicp_solver_preproc(const fgoicp_solver* s, float* offs6, float* scale, float* bounds6);
 /* Statistics of a raw cloud, host side, no device needed (TODO.md:7 of the reference: "compute point clouds' stats"): what the
