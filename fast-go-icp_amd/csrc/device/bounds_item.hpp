@@ -21,11 +21,11 @@
 // What did shorten the runs is not evaluating what the search drops anyway: the early exit further down (fgoicp_bounds_submit_cut).
 #pragma once
 
-constexpr float kCutNone = 3.0e38f;       // thresholds at or above this (fgoicp_bounds_submit_cut: +inf) switch the early exit off
 constexpr double kCutMargin = 1.000001;   // see bounds_item_kernel
 
 typedef float f2v __attribute__((ext_vector_type(2)));
 typedef float f4v __attribute__((ext_vector_type(4)));
+typedef unsigned u4v __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ f2v pk_fma(f2v a, f2v b, f2v c) { return __builtin_elementwise_fma(a, b, c); }
 __device__ __forceinline__ f2v splat2(float v) { return f2v{v, v}; }
@@ -249,40 +249,39 @@ __global__ __launch_bounds__(64) void bounds_item_kernel(const float4* __restric
     const int s = (int)(item / per_eval);
     const int chunk0 = (int)(item - (unsigned)s * per_eval) * (SPAN ? span : 1);
     const int nsub = SPAN ? min(span, nchunk - chunk0) : 1;
-    // (read next to the descriptor, not behind it: an item that ends early is three dependent L2 round trips — slot, descriptor + hint, partial)
-    const unsigned done_hint = (!TRIM && cut.acc && !(cut.probe & 4)) ? __builtin_nontemporal_load(&cut.done[s]) : 0u;
-    const TickSub sb = subs[s];
     const int lane = (int)threadIdx.x;
     // Early exit (fgoicp_bounds_submit_cut).  Every term of the lower-bound sum is >= 0, so once the partial sums of the evaluation's
     // FINISHED items have reached the caller's threshold the whole sum has, and the caller has said that it only needs to know that
-    // much (the inner BnB drops such a node whatever its exact bounds are: fgoicp.cpp:151): the remaining items leave a partial that
-    // keeps the row at or above the threshold and end.  Which items get here early depends on timing; what is reported does not —
-    // bounds_finalize_kernel returns {T, T} for EVERY row whose lower bound is >= T, cut short or not.  The margin keeps the decision
-    // on the safe side of the two summation orders (this running sum: finished items in any order; the reported one: the fixed tree).
+    // much (the inner BnB drops such a node whatever its exact bounds are: fgoicp.cpp:151): the remaining items end.  Their chunks'
+    // partials already say "not evaluated, at the threshold" — the kernel that wrote the gate left that marker in every chunk of every
+    // cutting evaluation, and only an item that is evaluated overwrites its own — so an item that ends early stores nothing.  Which
+    // items get here early depends on timing; what is reported does not: bounds_finalize_kernel returns {T, T} for EVERY row whose lower
+    // bound is >= T, cut short or not.  The margin keeps the decision on the safe side of the two summation orders (this running
+    // sum: finished items in any order; the reported one: the fixed tree).
+    // (the descriptor: a scalar load issued NEXT TO the gate's, not behind it — an item that ends early does not wait for it, and one that
+    // goes on would pay a round trip more: +0.4 % on a tick in which no item is skipped, profiles/ab_early_exit_gate.txt)
+    const TickSub sb = subs[s];
     bool cutting = false;
     if (!TRIM && cut.acc) {
-        if (chunk0 == 0 && lane == 0) {
-            cut.row_cut[sb.out0] = sb.cut0;
-            if (sb.dual) cut.row_cut[sb.out1] = sb.cut1;
-        }
-        cutting = sb.cut0 < kCutNone && (!sb.dual || sb.cut1 < kCutNone);
-        if (cutting) {
+        // The gate is the only load an item that ends early waits for behind its slot of `sorted`: `done` and the kind of
+        // the evaluation (the same address in every lane; an atomic load of workgroup scope, so that it goes through the vector path to
+        // this XCD's L2 — the scalar cache would keep a 0 for as long as the line stays in it; a load of agent scope, which would also
+        // see another XCD's `done` at once, skipped no more items and was no faster).  The rotation node is read by the items that go on.
+        TickGate* const gate = cut.gate + s;
+        const unsigned long long gw = __hip_atomic_load(reinterpret_cast<unsigned long long*>(gate), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (__builtin_amdgcn_readfirstlane((int)(unsigned)gw) && !(cut.probe & 4)) return;
+        const unsigned flags = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(gw >> 32));
+        cutting = (flags & kGateCutting) != 0u;
+        if (cutting && !(cut.probe & 1)) {
             // The running sums live at the device's point of coherence (the eight XCDs' L2s are not coherent with each other): reading
-            // them costs a trip to memory, ~2 us.  Once an item has found its evaluation finished it says so in `done`, an ordinary
-            // cached word: the later items of that evaluation ON THE SAME XCD (whose L2 holds that store) end after an L2 hit instead.
-            // A stale 0 — another XCD's L2, a line not refreshed yet — only sends the item down the slow path.
-            bool reached = done_hint != 0u;
-            if (!__builtin_amdgcn_readfirstlane((int)reached) && !(cut.probe & 1)) {
-                const double a0 = __hip_atomic_load(&cut.acc[2 * (size_t)s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const double a1 = sb.dual ? __hip_atomic_load(&cut.acc[2 * (size_t)s + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
-                reached = a0 >= (double)sb.cut0 * kCutMargin && (!sb.dual || a1 >= (double)sb.cut1 * kCutMargin);
-                if (reached && lane == 0) cut.done[s] = 1u;
-            }
+            // them costs a trip to memory, ~2 us.  An item that finds its evaluation finished says so in the gate, with a store that
+            // goes to the same place: the later items of the evaluation end at the gate, on this XCD after an L2 hit, on another one
+            // as soon as its L2 fetches the line.  A stale 0 only sends the item down this path.
+            const double a0 = __hip_atomic_load(&cut.acc[2 * (size_t)s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const double a1 = sb.dual ? __hip_atomic_load(&cut.acc[2 * (size_t)s + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
+            const bool reached = a0 >= (double)sb.cut0 * kCutMargin && (!sb.dual || a1 >= (double)sb.cut1 * kCutMargin);
             if (__builtin_amdgcn_readfirstlane((int)reached)) {
-                if (lane < nsub) {  // (the negative upper-bound partial marks a chunk as not evaluated: bounds_finalize_kernel counts them)
-                    partials[(size_t)sb.out0 * nchunk + chunk0 + lane] = make_double2(-1.0, (double)sb.cut0);
-                    if (sb.dual) partials[(size_t)sb.out1 * nchunk + chunk0 + lane] = make_double2(0.0, (double)sb.cut1);
-                }
+                if (lane == 0) __hip_atomic_store(&gate->done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 return;
             }
         }
@@ -320,6 +319,8 @@ __global__ __launch_bounds__(64) void bounds_item_kernel(const float4* __restric
         }
     }
     if (!TRIM && cutting && lane == 0 && !(cut.probe & 2)) {
+        // (no-return atomics: an item that waited for the sums to come back, to publish `done` itself when its own share carried the
+        // evaluation over the thresholds, held its slot longer than the items it spared the slow path gained: profiles/ab_early_exit_gate.txt)
         unsafeAtomicAdd(&cut.acc[2 * (size_t)s], lb_fix);
         if (sb.dual) unsafeAtomicAdd(&cut.acc[2 * (size_t)s + 1], lb_rot);
     }

@@ -122,6 +122,11 @@ static int tick_launch_window(fgoicp_ctx* c, fgoicp_ctx::TickSlot& sl) {
     const bool small = nitems <= (size_t)c->small_tick_items;
     const TickGroup* dev_groups = small ? sl.hd_groups : sl.d_groups;
     const TickSub* dev_subs = small ? sl.hd_subs : sl.d_subs;
+    TickCut cut;  // early exit of evaluations that have reached their group's threshold (fgoicp_bounds_submit_cut)
+    if (sl.win_cut) { cut.acc = sl.d_cut_acc; cut.gate = sl.d_cut_gate; cut.row_cut = sl.d_row_cut; cut.stat = c->d_cut_stat; }
+    if (tiers && !small) cut.tier_split = sl.d_cursor + kTickTierSplit;
+    static const int cut_probe = [] { const char* e = dev_env("FGOICP_CUT_PROBE"); return e ? std::atoi(e) : 0; }();  // measurement of the early exit's own cost (tools/op_bench.py)
+    cut.probe = cut_probe;
     *sl.h_sort_err = 0u;
     unsigned* fused_err = !small && c->sort_check ? sl.hd_sort_err : nullptr;  // the bounds kernel checks the permutation it walks
     if (!small) {
@@ -136,9 +141,13 @@ static int tick_launch_window(fgoicp_ctx* c, fgoicp_ctx::TickSlot& sl) {
         ++c->sorted_ticks;
         const int fault = c->sort_fault_tick && c->sorted_ticks == (uint64_t)c->sort_fault_tick;
         launch_tick_sort(c->geom, span > 1 ? c->d_span_cen : c->d_chunk_cen, per_eval, sl.d_groups, sl.d_subs, neval, c->cell_shift, sl.d_keys, sl.d_ranks, sl.d_hist, sl.d_hist_xcd, sl.d_xoff, sl.d_block_sums, sl.d_cursor, sl.d_sorted,
-                         c->sort_xcd ? 1 : 0, c->sort_check ? 1 : 0, fault, sl.sort_stream, tiers ? c->d_lut : nullptr, c->cut_tier_level / (float)c->ns);
+                         c->sort_xcd ? 1 : 0, c->sort_check ? 1 : 0, fault, sl.sort_stream, tiers ? c->d_lut : nullptr, c->cut_tier_level / (float)c->ns,
+                         sl.win_cut ? &cut : nullptr, sl.d_partials, c->nchunk1, span);
         HIPCHK(hipEventRecord(sl.sorted_ev, sl.sort_stream));
         HIPCHK(hipStreamWaitEvent(sl.stream, sl.sorted_ev, 0));
+    } else if (sl.win_cut) {
+        // (the sorted path's key kernel does this on its way: the gates of the window's evaluations and the partials of the chunks nobody evaluates)
+        launch_tick_prefill(dev_subs, neval, c->nchunk1, cut, sl.d_partials, sl.stream);
     }
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (c->profile) {
@@ -156,11 +165,6 @@ static int tick_launch_window(fgoicp_ctx* c, fgoicp_ctx::TickSlot& sl) {
         c->prof_subcubes += rows;
         c->prof_evals += neval;  // a twin pair is two subcubes and one evaluation
     }
-    TickCut cut;  // early exit of evaluations that have reached their group's threshold (fgoicp_bounds_submit_cut)
-    if (sl.win_cut) { cut.acc = sl.d_cut_acc; cut.done = sl.d_cut_done; cut.row_cut = sl.d_row_cut; cut.stat = c->d_cut_stat; }
-    if (tiers && !small) cut.tier_split = sl.d_cursor + kTickTierSplit;
-    static const int cut_probe = [] { const char* e = dev_env("FGOICP_CUT_PROBE"); return e ? std::atoi(e) : 0; }();  // measurement of the early exit's own cost (tools/op_bench.py)
-    cut.probe = cut_probe;
     const bool cut_on = launch_bounds_sorted(c->d_src, (int)c->ns, c->d_lut_zp, c->lut_layout, c->geom, c->nchunk1, c->chunk_pts, dev_groups, dev_subs, neval, small ? nullptr : sl.d_sorted,
                                              sl.d_partials, c->inliers ? sl.d_evals : nullptr, c->erow, c->trim_samp_shift, fused_err, cut, span, e0, e1, sl.stream);
     if (cut_on) c->cut_items_offered += (size_t)neval * c->nchunk1;  // (counted in chunks, like the skipped ones: bounds_finalize_kernel)
@@ -1637,8 +1641,7 @@ static int ctx_create_impl(const float* tgt_xyz, size_t nt, const float* src_xyz
             CHK(hipMalloc(&sl.d_cut_acc, sizeof(double) * 2 * (size_t)c->max_subcubes));
             CHK(hipMemset(sl.d_cut_acc, 0, sizeof(double) * 2 * (size_t)c->max_subcubes));  // bounds_finalize_kernel re-zeroes what a window used
             CHK(hipMalloc(&sl.d_row_cut, sizeof(float) * (size_t)c->max_subcubes));
-            CHK(hipMalloc(&sl.d_cut_done, sizeof(unsigned) * (size_t)c->max_subcubes));
-            CHK(hipMemset(sl.d_cut_done, 0, sizeof(unsigned) * (size_t)c->max_subcubes));
+            CHK(hipMalloc(&sl.d_cut_gate, sizeof(TickGate) * (size_t)c->max_subcubes));  // written per window, ahead of its bounds kernel
             if (k == 0 && !c->d_cut_stat) {
                 CHK(hipMalloc(&c->d_cut_stat, sizeof(unsigned long long) * kCutStatSlots));
                 CHK(hipMemset(c->d_cut_stat, 0, sizeof(unsigned long long) * kCutStatSlots));
@@ -1746,7 +1749,7 @@ void fgoicp_ctx_destroy(fgoicp_ctx* c) {
         if (sl.h_row_span) (void)hipHostFree(sl.h_row_span);
         if (sl.h_sort_err) (void)hipHostFree(sl.h_sort_err);
         (void)hipFree(sl.d_groups); (void)hipFree(sl.d_subs); (void)hipFree(sl.d_keys); (void)hipFree(sl.d_ranks); (void)hipFree(sl.d_hist);
-        (void)hipFree(sl.d_cursor); (void)hipFree(sl.d_block_sums); (void)hipFree(sl.d_hist_xcd); (void)hipFree(sl.d_xoff); (void)hipFree(sl.d_sorted); (void)hipFree(sl.d_partials); (void)hipFree(sl.d_cut_acc); (void)hipFree(sl.d_row_cut); (void)hipFree(sl.d_cut_done);
+        (void)hipFree(sl.d_cursor); (void)hipFree(sl.d_block_sums); (void)hipFree(sl.d_hist_xcd); (void)hipFree(sl.d_xoff); (void)hipFree(sl.d_sorted); (void)hipFree(sl.d_partials); (void)hipFree(sl.d_cut_acc); (void)hipFree(sl.d_row_cut); (void)hipFree(sl.d_cut_gate);
         if (sl.h_groups) (void)hipHostFree(sl.h_groups);
         if (sl.h_subs) (void)hipHostFree(sl.h_subs);
         if (sl.h_lb) (void)hipHostFree(sl.h_lb);

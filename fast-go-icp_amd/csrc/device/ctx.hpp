@@ -59,7 +59,7 @@ struct fgoicp_ctx {
         double2* d_partials = nullptr;           // [max_subcubes][nchunk1] {sum_ub, sum_lb}
         double* d_cut_acc = nullptr;             // early exit (fgoicp_bounds_submit_cut): 2 running sums per evaluation, zero between windows
         float* d_row_cut = nullptr;              // ... and the threshold of every output row
-        unsigned* d_cut_done = nullptr;          // ... and the cached "finished" hint per evaluation
+        fgoicp::TickGate* d_cut_gate = nullptr;  // ... and what an item waits for first: "finished" and "cutting" per evaluation
         bool win_cut = false;                    // the window in flight carries thresholds
         float *h_lb = nullptr, *h_ub = nullptr, *hd_lb = nullptr, *hd_ub = nullptr;  // pinned results of the window in flight
         float* d_evals = nullptr;                // trimmed mode: per-point e = max(d, 0) of every output row, [vals_rows][erow]

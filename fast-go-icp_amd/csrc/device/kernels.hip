@@ -265,17 +265,48 @@ __device__ __forceinline__ unsigned hilbert15(unsigned x, unsigned y, unsigned z
 // ones).  An address is only ever touched from one XCD, so the L2 is a sufficient point of coherence; the dirty lines reach
 // memory at the end of the kernel like any other store.  The rank then carries the XCD in its top bits.
 constexpr int kTickXcds = 16;  // the XCC_ID field is 4 bits wide
+
+// Windows with thresholds (fgoicp_bounds_submit_cut), ahead of their bounds kernel: what the chunks [chunk_first, chunk_end) of evaluation s
+// look like while no item has evaluated them — the partial {-1, T} that bounds_finalize_kernel counts as "not evaluated" and that keeps the
+// row at its threshold T (the second row of a dual evaluation: {0, T}) — and, from the evaluation's first chunk, its gate (TickGate) and the
+// thresholds of its rows.  The bounds kernel then stores nothing for an item that ends early; an item that is evaluated overwrites its chunks.
+// Evaluations that are not cutting (a threshold of +inf) evaluate every item, so their chunks need no marker.
+__device__ __forceinline__ void cut_prefill(const TickSub& sb, int s, int chunk_first, int chunk_end, int row_chunks, const TickCut& cut, double2* __restrict__ partials) {
+    const bool cutting = sb.cut0 < kCutNone && (!sb.dual || sb.cut1 < kCutNone);
+    if (chunk_first == 0) {
+        *reinterpret_cast<uint2*>(cut.gate + s) = make_uint2(0u, cutting ? kGateCutting : 0u);
+        cut.row_cut[sb.out0] = sb.cut0;
+        if (sb.dual) cut.row_cut[sb.out1] = sb.cut1;
+    }
+    if (!cutting) return;
+    for (int chunk = chunk_first; chunk < chunk_end; ++chunk) {
+        partials[(size_t)sb.out0 * row_chunks + chunk] = make_double2(-1.0, (double)sb.cut0);
+        if (sb.dual) partials[(size_t)sb.out1 * row_chunks + chunk] = make_double2(0.0, (double)sb.cut1);
+    }
+}
+// ... of a window that skips the sort: one thread per (evaluation, chunk)
+__global__ __launch_bounds__(64) void tick_prefill_kernel(const TickSub* __restrict__ subs, int nsub, int nchunk, TickCut cut, double2* __restrict__ partials) {
+    const size_t nitems = (size_t)nsub * nchunk;
+    for (size_t i = (size_t)blockIdx.x * 64 + threadIdx.x; i < nitems; i += (size_t)gridDim.x * 64) {
+        const int s = (int)(i / nchunk), c = (int)(i - (size_t)s * nchunk);
+        cut_prefill(subs[s], s, c, c + 1, nchunk, cut, partials);
+    }
+}
+
 template <int XCD>
 __global__ __launch_bounds__(64) void tick_keys_kernel(const float4* __restrict__ chunk_cen, int nchunk, const TickGroup* __restrict__ groups,
                                                        const TickSub* __restrict__ subs, int nsub, LutGeom g, int cell_shift,
                                                        unsigned short* __restrict__ keys, unsigned* __restrict__ ranks, unsigned* __restrict__ hist,
                                                        unsigned* __restrict__ prefill /* optional: `sorted`, filled with 0xFFFFFFFF for the permutation check of the bounds kernel */,
-                                                       const float* __restrict__ tier_lut /* windows with thresholds: the plain LUT; nullptr = one tier */, float tier_level) {
+                                                       const float* __restrict__ tier_lut /* windows with thresholds: the plain LUT; nullptr = one tier */, float tier_level,
+                                                       TickCut cut, double2* __restrict__ partials /* windows with thresholds (nullptr: none): cut_prefill of every item's chunks */,
+                                                       int row_chunks, int span) {
     const size_t nitems = (size_t)nsub * nchunk;
     for (size_t i = (size_t)blockIdx.x * 64 + threadIdx.x; i < nitems; i += (size_t)gridDim.x * 64) {
         if (prefill) prefill[i] = 0xFFFFFFFFu;
         const int s = (int)(i / nchunk), c = (int)(i - (size_t)s * nchunk);
         const TickSub sb = subs[s];
+        if (partials) cut_prefill(sb, s, c * span, min(c * span + span, row_chunks), row_chunks, cut, partials);
         const TickGroup& gr = groups[sb.group];
         const float4 cc = chunk_cen[c];
         float rx, ry, rz;
@@ -957,7 +988,6 @@ __global__ __launch_bounds__(64) void bounds_finalize_kernel(const double2* __re
         out_ub[s] = ubf;
         out_lb[s] = lbf;
     }
-    if (cut.acc && threadIdx.x == 2) cut.done[s] = 0u;
     if (cut.acc && threadIdx.x < 2) cut.acc[2 * (size_t)s + threadIdx.x] = 0.0;  // evaluations <= rows: the running sums are zero again for the slot's next window
 }
 
@@ -2072,15 +2102,18 @@ int nn_slices(int nq, int nt) {
 // scatter (the scatter needs no atomics of its own).
 void launch_tick_sort(const LutGeom& g, const float4* chunk_cen, int nchunk, const TickGroup* groups, const TickSub* subs, int nsub, int cell_shift,
                       unsigned short* keys, unsigned* ranks, unsigned* hist, unsigned* hist_xcd, unsigned* xoff, unsigned* block_sums, unsigned* cursor, unsigned* sorted,
-                      int allow_xcd, int prefill, int inject_fault, hipStream_t s, const float* tier_lut, float tier_level) {
+                      int allow_xcd, int prefill, int inject_fault, hipStream_t s, const float* tier_lut, float tier_level, const TickCut* prefill_cut, double2* partials,
+                      int row_chunks, int span) {
+    const TickCut pcut = prefill_cut ? *prefill_cut : TickCut();
+    if (!prefill_cut) partials = nullptr;
     const size_t nitems = (size_t)nsub * nchunk;
     const unsigned kb = (unsigned)std::min<size_t>((nitems + 63) / 64, 8192);  // `hist` / `hist_xcd` are zero here: the scan / fold kernels re-zero them
     const bool xcd = allow_xcd != 0 && hist_xcd && xoff;  // allow_xcd: per context, cleared by a failed permutation check
     if (xcd) {
-        hipLaunchKernelGGL(tick_keys_kernel<1>, dim3(kb), dim3(64), 0, s, chunk_cen, nchunk, groups, subs, nsub, g, cell_shift, keys, ranks, hist_xcd, prefill ? sorted : nullptr, tier_lut, tier_level);
+        hipLaunchKernelGGL(tick_keys_kernel<1>, dim3(kb), dim3(64), 0, s, chunk_cen, nchunk, groups, subs, nsub, g, cell_shift, keys, ranks, hist_xcd, prefill ? sorted : nullptr, tier_lut, tier_level, pcut, partials, row_chunks, span);
         hipLaunchKernelGGL(tick_fold_sums_kernel, dim3(kScanBlocks), dim3(64), 0, s, hist_xcd, xoff, hist, block_sums);
     } else {
-        hipLaunchKernelGGL(tick_keys_kernel<0>, dim3(kb), dim3(64), 0, s, chunk_cen, nchunk, groups, subs, nsub, g, cell_shift, keys, ranks, hist, prefill ? sorted : nullptr, tier_lut, tier_level);
+        hipLaunchKernelGGL(tick_keys_kernel<0>, dim3(kb), dim3(64), 0, s, chunk_cen, nchunk, groups, subs, nsub, g, cell_shift, keys, ranks, hist, prefill ? sorted : nullptr, tier_lut, tier_level, pcut, partials, row_chunks, span);
         hipLaunchKernelGGL(tick_scan_sums_kernel, dim3(kScanBlocks), dim3(64), 0, s, hist, block_sums);
     }
     hipLaunchKernelGGL(tick_scan_apply_kernel, dim3(kScanBlocks), dim3(64), 0, s, hist, block_sums, cursor);
@@ -2174,6 +2207,12 @@ void launch_tick_upload(const TickGroup* h_groups, TickGroup* d_groups, int ngro
     const unsigned ng16 = (unsigned)ngroups * (sizeof(TickGroup) / 16), ns16 = (unsigned)nsubs * (sizeof(TickSub) / 16);
     hipLaunchKernelGGL(tick_upload_kernel, dim3(std::min(1024u, (ng16 + ns16 + 63) / 64)), dim3(64), 0, s, reinterpret_cast<const uint4*>(h_groups),
                        reinterpret_cast<uint4*>(d_groups), ng16, reinterpret_cast<const uint4*>(h_subs), reinterpret_cast<uint4*>(d_subs), ns16);
+}
+
+void launch_tick_prefill(const TickSub* subs, int nsub, int nchunk, const TickCut& cut, double2* partials, hipStream_t s) {
+    const size_t nitems = (size_t)nsub * nchunk;
+    if (nitems == 0) return;
+    hipLaunchKernelGGL(tick_prefill_kernel, dim3((unsigned)std::min<size_t>((nitems + 63) / 64, 8192)), dim3(64), 0, s, subs, nsub, nchunk, cut, partials);
 }
 
 void launch_bounds_finalize(const double2* partials, int nchunk, int total, float* out_lb, float* out_ub, const TickCut& cut, hipStream_t s) {

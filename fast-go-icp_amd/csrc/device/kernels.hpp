@@ -52,16 +52,26 @@ struct TickSub {     // one EVALUATION: a translation node + its rotation node, 
 };
 static_assert(sizeof(TickSub) == 48, "TickSub is copied in 16-byte units");
 // Early exit (fgoicp_bounds_submit_cut): acc = 2 doubles per evaluation (sum of the lower-bound partials of its finished items, per
-// variant; zero on entry, re-zeroed by bounds_finalize_kernel), row_cut = the threshold of every output row (written by the
+// variant; zero on entry, re-zeroed by bounds_finalize_kernel), row_cut = the threshold of every output row (written ahead of the
 // bounds kernel, applied by bounds_finalize_kernel), stat = {items not evaluated} (optional).  acc == nullptr: off.
 constexpr int kCutStatSlots = 64;  // the counter is spread over this many words (one atomic per output row with skipped items)
+constexpr float kCutNone = 3.0e38f;  // thresholds at or above this (fgoicp_bounds_submit_cut: +inf) switch the early exit off
+// What a work item of a window with thresholds waits for before anything else: an item whose evaluation is over ends after two
+// dependent loads (its slot of `sorted`, then this) and no store.  Written per window, before its bounds kernel, by the kernel that
+// also leaves the "not evaluated" partials of every chunk (tick_keys_kernel / tick_prefill_kernel).
+struct TickGate {
+    unsigned done;      // 1 = the running sums have been seen at their thresholds (set by the bounds kernel; a stale 0 only costs time)
+    unsigned flags;     // kGateCutting
+};
+static_assert(sizeof(TickGate) == 8, "TickGate is read and written as one 8-byte word");
+constexpr unsigned kGateCutting = 1u;  // every variant of the evaluation has a threshold below kCutNone
 struct TickCut {
     double* acc = nullptr;
-    unsigned* done = nullptr;             // per evaluation: 1 = an item has seen the running sums at their thresholds (a cached hint, zero between windows)
+    TickGate* gate = nullptr;             // per evaluation (see TickGate)
     float* row_cut = nullptr;
     unsigned long long* stat = nullptr;   // [kCutStatSlots]
     const unsigned* tier_split = nullptr; // items of the first tier of `sorted` (launch_tick_sort with tier_lut): the grid walks them before the others
-    int probe = 0;                        // development build, FGOICP_CUT_PROBE: 1 = the running sums are not read (nothing is ever cut), 2 = not added to, 4 = no `done` hint
+    int probe = 0;                        // development build, FGOICP_CUT_PROBE: 1 = the running sums are not read (nothing is ever cut), 2 = not added to, 4 = the gate's `done` is not honoured
 };
 constexpr int kTickNumKeys = 1 << 15;
 void launch_tick_sort(const LutGeom& g, const float4* chunk_cen, int nchunk, const TickGroup* groups, const TickSub* subs, int nsub, int cell_shift,
@@ -72,8 +82,12 @@ void launch_tick_sort(const LutGeom& g, const float4* chunk_cen, int nchunk, con
                       int inject_fault /* test hook */, hipStream_t s,
                       const float* tier_lut = nullptr /* windows with thresholds: the plain LUT — items likely to carry much of their evaluation's lower bound are sorted
                                                          in front of the others (two tiers; cursor[kTickTierSplit] = items of the first) */,
-                      float tier_level = 0.0f /* ... those whose per-point term at the patch centre reaches tier_level * T */);
+                      float tier_level = 0.0f /* ... those whose per-point term at the patch centre reaches tier_level * T */,
+                      const TickCut* prefill_cut = nullptr /* windows with thresholds: the key kernel also writes gate, row_cut and the "not evaluated" partials */,
+                      double2* partials = nullptr, int row_chunks = 0 /* chunks per row of `partials` */, int span = 1 /* chunks per item: nchunk = ceil(row_chunks / span) */);
 constexpr int kTickTierSplit = 1 << 14;
+// The same for a window that skips the sort (small ticks): gate, row_cut and the "not evaluated" partials of its evaluations, one launch on `s`.
+void launch_tick_prefill(const TickSub* subs, int nsub, int nchunk, const TickCut& cut, double2* partials, hipStream_t s);
 // descriptors of a tick: pinned staging (device-visible addresses) -> device arrays, one launch
 void launch_tick_upload(const TickGroup* hd_groups, TickGroup* d_groups, int ngroups, const TickSub* hd_subs, TickSub* d_subs, int nsubs, hipStream_t s);
 // Returns true if the early exit was in force: the window carried thresholds and is untrimmed (trimmed windows carry none, so trimmed
