@@ -112,6 +112,15 @@ class PlaneResult(C.Structure):
         self.struct_size = C.sizeof(PlaneResult)  # the library writes no byte beyond it
 
 
+class VoxelInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("points", C.c_uint64), ("voxels", C.c_uint64), ("max_points_per_voxel", C.c_uint64), ("origin", C.c_float * 3),
+                ("voxel_size", C.c_float)]
+
+    def __init__(self):
+        super().__init__()
+        self.struct_size = C.sizeof(VoxelInfo)  # the library writes no byte beyond it
+
+
 SCHEDULE_SERIAL = 0
 SCHEDULE_ROUND = 1
 
@@ -126,6 +135,7 @@ _SIGS = {
     "fgoicp_lut_dims": (C.c_int, [C.c_void_p, c_int_p]),
     "fgoicp_ctx_get_info": (C.c_int, [C.c_void_p, C.POINTER(CtxInfo)]),
     "fgoicp_cloud_stats": (C.c_int, [c_float_p, C.c_size_t, C.POINTER(CloudStats)]),
+    "fgoicp_voxel_downsample": (C.c_int, [c_float_p, C.c_size_t, C.c_float, c_float_p, C.c_int, c_float_p, C.c_size_t, c_uint32_p, c_uint32_p, C.POINTER(VoxelInfo)]),
     "fgoicp_lut_read": (C.c_int, [C.c_void_p, c_float_p, C.c_size_t]),
     "fgoicp_lut_search": (C.c_int, [C.c_void_p, c_float_p, C.c_size_t, c_float_p]),
     "fgoicp_lut_nodes": (C.c_int, [C.c_void_p, c_int_p, C.c_size_t, c_float_p]),

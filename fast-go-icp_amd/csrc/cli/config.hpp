@@ -124,6 +124,7 @@ struct Config {
         int refine_knn = 16;         // ... neighbours per target point for its normal (4 .. 32)
         int refine_max_iter = 30;
         float refine_distance = 0.0f;  // ... distance threshold in the files' units (absent or 0: none)
+        float target_voxel = 0.0f, source_voxel = 0.0f;  // EXTENSION: voxel size in the files' units; the cloud is replaced by its voxel grid's centroids (fgoicp_voxel_downsample) after loading; absent or <= 0: off, NaN is refused
     } params;
 
     explicit Config(const std::string& toml_filepath) {
@@ -182,6 +183,9 @@ struct Config {
             if (!params.refine.empty() && params.refine != "plane")  // (thrown, not exit(1): the callers report it; a typo must not silently skip the refinement)
                 throw std::invalid_argument("params.refine = \"" + params.refine + "\" is not supported: the only refinement is \"plane\"");
             if (params.refine == "plane" && (params.refine_knn < 4 || params.refine_knn > 32)) throw std::invalid_argument("params.refine_knn must lie in [4, 32]");
+            params.target_voxel = (float)num("params", "target_voxel", 0.0);
+            params.source_voxel = (float)num("params", "source_voxel", 0.0);
+            if (std::isnan(params.target_voxel) || std::isnan(params.source_voxel)) throw std::invalid_argument("params.target_voxel and params.source_voxel must not be NaN");
             auto clampf = [](float x, float lo, float hi) { return x < hi ? (x > lo ? x : lo) : hi; };
             params.target_subsample = clampf(params.target_subsample, 1e-5f, 1.0f);  // utilities.hpp:101-104
             params.source_subsample = clampf(params.source_subsample, 1e-5f, 1.0f);
@@ -378,7 +382,8 @@ inline void write_result_toml(const std::string& path, const icp::mat3& R, const
 // io.alignment (EXTENSION): the alignment report of the run (fgoicp_solver_alignment / fgoicp_batch_alignment).  Two '#' lines — the summary,
 // the column names — then one line per registered source point, in the order the cloud was loaded (after source_subsample): its coordinates
 // as loaded, the index of its nearest target point (into the target as loaded), its distance to it in the files' units
-// (sqrt(dist2) / scaling_factor) and 1 if the optimum counts it as an inlier.
+// (sqrt(dist2) / scaling_factor) and 1 if the optimum counts it as an inlier.  Points and indices refer to the clouds AS REGISTERED: with
+// params.source_voxel / params.target_voxel those are the voxel grids' centroids in their row order, not the points of the files.
 inline void write_alignment_txt(const std::string& path, const std::vector<icp::vec3>& src, const uint32_t* idx, const float* dist2, const uint8_t* inlier,
                                 const fgoicp_alignment_summary& s) {
     std::ofstream f(path);

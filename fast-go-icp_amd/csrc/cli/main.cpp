@@ -22,6 +22,24 @@ static std::string usage(const std::string& exe) {
            "  -b,--batch LIST             Run every config listed in LIST (one path per line, relative to LIST) as one batch on one GPU\n\nExample Usage:\n  " + exe + " -c config.toml --verbose\n  " + exe + " --config=config.toml\n";
 }
 
+// params.target_voxel / params.source_voxel: the loaded cloud replaced by the centroids of its voxel grid (fgoicp_voxel_downsample on device 0,
+// the origin is the cloud's own minimum), once, before any solver exists: everything downstream sees the thinned cloud.  A refused size
+// (too small for the cloud's extent, not finite) is an error of the configuration: reported, exit code 1.
+static void voxel_thin(std::vector<icp::vec3>& pc, float voxel, const char* which) {
+    if (!(voxel > 0.0f)) return;
+    std::vector<icp::vec3> out(pc.size());
+    fgoicp_voxel_info_t vi{};
+    vi.struct_size = sizeof(vi);
+    const int rc = fgoicp_voxel_downsample(&pc.data()->x, pc.size(), voxel, nullptr, 0, &out.data()->x, out.size(), nullptr, nullptr, &vi);
+    if (rc != FGOICP_OK) {
+        icp::Logger(icp::LogLevel::Error) << "params." << which << "_voxel = " << voxel << ": status " << rc << ": " << fgoicp_last_error();
+        std::exit(1);
+    }
+    out.resize((size_t)vi.voxels);
+    icp::Logger(icp::LogLevel::Info) << "Voxel grid (" << which << "): " << pc.size() << " -> " << out.size() << " points, voxel " << voxel;
+    pc.swap(out);
+}
+
 // --batch LIST: every config of the list registered in one fgoicp_batch run; each config's io.output / io.visualization as a lone -c run
 // of it writes them (the seconds written are the batch's).  The configs must agree on the schedule and round width; each is trimmed with
 // its own params.trim_fraction.
@@ -59,6 +77,8 @@ static int run_batch(const std::string& list_file) {
         const cli::Config& c = configs[i];
         cli::load_cloud(c.io.target, c.params.target_subsample, pct[i], c.params.seed);
         cli::load_cloud(c.io.source, c.params.source_subsample, pcs[i], c.params.seed < 0 ? -1 : c.params.seed + 1);
+        voxel_thin(pct[i], c.params.target_voxel, "target");
+        voxel_thin(pcs[i], c.params.source_voxel, "source");
         icp::Logger(icp::LogLevel::Info) << "Pair " << i << ": target (" << pct[i].size() << ") " << c.io.target << ", source (" << pcs[i].size() << ") " << c.io.source;
         pairs[i] = fgoicp_batch_pair{&pct[i].data()->x, pct[i].size(), &pcs[i].data()->x, pcs[i].size(), c.params.lut_resolution, c.params.mse_threshold};
         trim[i] = c.params.trim_fraction;
@@ -165,6 +185,8 @@ int main(int argc, char* argv[]) {
     icp::Logger(icp::LogLevel::Info) << "Target point cloud (" << pct.size() << ") loaded from " << config.io.target;
     cli::load_cloud(config.io.source, config.params.source_subsample, pcs, config.params.seed < 0 ? -1 : config.params.seed + 1);
     icp::Logger(icp::LogLevel::Info) << "Source point cloud (" << pcs.size() << ") loaded from " << config.io.source;
+    voxel_thin(pct, config.params.target_voxel, "target");
+    voxel_thin(pcs, config.params.source_voxel, "source");
     const std::vector<icp::vec3> pct_in = pct, pcs_in = pcs;
     for (const auto* pc : {&pct, &pcs}) {  // verbose: the statistics the pre-processing normalises by (TODO.md:7 of the reference)
         fgoicp_cloud_stats_t cs{};

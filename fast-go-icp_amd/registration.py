@@ -37,6 +37,28 @@ def cloud_stats(points):
                 max_abs_centred=float(st.max_abs_centred), rms_radius=float(st.rms_radius))
 
 
+def voxel_downsample(points, voxel_size, origin=None, device=0, return_map=False):
+    """fgoicp_voxel_downsample: one point per occupied cell of a grid of `voxel_size` — the centroid of the cell's members, rows in ascending
+    (z, y, x) cell order — as an (m, 3) float32 array.  origin: 3 floats, None = the cloud's per-axis minimum.  return_map=True returns
+    (points, voxel_of_point (n,) uint32, counts (m,) uint32, info) with info = dict(points, voxels, max_points_per_voxel, origin, voxel_size)."""
+    p = _cloud(points)
+    o = None if origin is None else np.ascontiguousarray(origin, dtype=np.float32).reshape(3)
+    n = len(p)
+    out = np.empty((n, 3), np.float32)
+    vop = np.empty(n, np.uint32) if return_map else None
+    cnt = np.empty(n, np.uint32) if return_map else None
+    u32 = lambda a: None if a is None else a.ctypes.data_as(_lib.c_uint32_p)
+    info = _lib.VoxelInfo()
+    _lib.check(_lib.load().fgoicp_voxel_downsample(_fp(p) if n else None, n, float(voxel_size), None if o is None else _fp(o), int(device), _fp(out), n, u32(vop), u32(cnt),
+                                                   C.byref(info)), "fgoicp_voxel_downsample")
+    m = int(info.voxels)
+    out = out[:m].copy()
+    if not return_map:
+        return out
+    return out, vop, cnt[:m].copy(), dict(points=int(info.points), voxels=m, max_points_per_voxel=int(info.max_points_per_voxel),
+                                          origin=np.array(info.origin, np.float32), voxel_size=float(info.voxel_size))
+
+
 class Alignment:
     """EXTENSION: the alignment report of fgoicp_alignment / fgoicp_solver_alignment / fgoicp_batch_alignment.  Arrays in the caller's point
     order: indices (ns,) uint32 — nearest target point of every source point; dist2 (ns,) float32 — its squared distance in the frame the

@@ -455,6 +455,40 @@ typedef struct fgoicp_cloud_stats_t {
     float rms_radius;            /* sqrt(mean |p_i - c|^2) */
 } fgoicp_cloud_stats_t;
 int fgoicp_cloud_stats(const float* xyz, size_t n, fgoicp_cloud_stats_t* out);
+/*
+ * EXTENSION — voxel-grid downsampling on the device (no reference counterpart: the reference thins a cloud only in its loaders, keeping each
+ * point with probability p; Open3D: voxel_down_sample, PCL: VoxelGrid).  The first step of a registration pipeline: one point per occupied
+ * cell of a regular grid, so the cloud comes to an even density, reproducibly.
+ *
+ * Inputs: n points (fp32 xyz triples), voxel_size v > 0, optionally an origin o of 3 floats; with NULL, o is the per-axis minimum of the cloud.
+ *   cell of a point   per axis c = floor(((double)p - (double)o) / (double)v), the subtraction and the division in IEEE fp64 (no reciprocal,
+ *                     no fp32, no fast-math: numpy's float64 arithmetic names the same cell for every point, those on a cell face included)
+ *   key               (cz << 42) | (cy << 21) | cx
+ *   output rows       one per occupied cell in ascending key order (z-major, then y, then x): count_per_voxel = the members, out_xyz = the
+ *                     centroid — fp64 sums of the member coordinates (fp32 -> fp64 is exact) divided by the count in fp64 and rounded to
+ *                     fp32 once.  The sums are a function of the input array alone (a fixed order, no floating-point atomics, no dependence
+ *                     on timing): two calls on the same input return the same bytes
+ *   voxel_of_point_n  per input point, the output row it fell into
+ * Refused with FGOICP_ERR_INVALID_ARG before any device work (a host pass over the cloud, as fgoicp_cloud_stats): a null xyz or n == 0,
+ * n >= 2^31, a v that is not a positive finite number, a non-finite coordinate or origin, a null `out` or a struct_size that ends before
+ * max_points_per_voxel, and any c outside [0, 2^21) — a point below a given origin, or an extent of more than 2^21 cells: the voxel size is
+ * too small for the extent.  No usable device: FGOICP_ERR_NO_DEVICE (no CPU fallback); allocation failure: FGOICP_ERR_OOM.
+ * out_xyz (3 floats per row) and count_per_voxel hold capacity_points rows; each of the three arrays may be NULL (all NULL: count only).  If
+ * out_xyz or count_per_voxel is given and capacity_points < voxels the call returns FGOICP_ERR_TOO_LARGE with `out` filled, so a second call
+ * can be sized, and writes nothing to the arrays; a capacity of n always suffices.
+ * The call owns its stream and its device memory (about 70 bytes per point) and frees both before it returns; it touches no fgoicp_ctx and
+ * no global state and may be called from several threads.
+ */
+typedef struct fgoicp_voxel_info_t {
+    uint32_t struct_size;          /* IN: sizeof(fgoicp_voxel_info_t) as the CALLER was compiled; no byte beyond it is written, 0 is refused */
+    uint64_t points, voxels;       /* n; occupied cells */
+    uint64_t max_points_per_voxel;
+    float    origin[3], voxel_size;/* the origin actually used */
+} fgoicp_voxel_info_t;
+int fgoicp_voxel_downsample(const float* xyz, size_t n, float voxel_size, const float* origin3_or_NULL, int device,
+                            float* out_xyz, size_t capacity_points,
+                            uint32_t* voxel_of_point_n, uint32_t* count_per_voxel,
+                            fgoicp_voxel_info_t* out);
 /* The operator context the solver drives (borrowed; valid until solver_destroy). */
 fgoicp_ctx* fgoicp_solver_ctx(fgoicp_solver* s);
 
