@@ -9,6 +9,7 @@ c_float_p = C.POINTER(C.c_float)
 c_int_p = C.POINTER(C.c_int)
 c_uint32_p = C.POINTER(C.c_uint32)
 c_uint8_p = C.POINTER(C.c_uint8)
+c_double_p = C.POINTER(C.c_double)
 
 
 class CtxInfo(C.Structure):
@@ -121,6 +122,18 @@ class VoxelInfo(C.Structure):
         self.struct_size = C.sizeof(VoxelInfo)  # the library writes no byte beyond it
 
 
+class OutlierInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("points", C.c_uint64), ("kept", C.c_uint64), ("mode", C.c_int), ("k", C.c_int), ("mean", C.c_double),
+                ("stddev", C.c_double), ("threshold", C.c_double), ("radius2", C.c_float)]
+
+    def __init__(self):
+        super().__init__()
+        self.struct_size = C.sizeof(OutlierInfo)  # the library writes no byte beyond it
+
+
+OUTLIER_STATISTICAL = 0
+OUTLIER_RADIUS = 1
+
 SCHEDULE_SERIAL = 0
 SCHEDULE_ROUND = 1
 
@@ -136,6 +149,8 @@ _SIGS = {
     "fgoicp_ctx_get_info": (C.c_int, [C.c_void_p, C.POINTER(CtxInfo)]),
     "fgoicp_cloud_stats": (C.c_int, [c_float_p, C.c_size_t, C.POINTER(CloudStats)]),
     "fgoicp_voxel_downsample": (C.c_int, [c_float_p, C.c_size_t, C.c_float, c_float_p, C.c_int, c_float_p, C.c_size_t, c_uint32_p, c_uint32_p, C.POINTER(VoxelInfo)]),
+    "fgoicp_remove_outliers": (C.c_int, [c_float_p, C.c_size_t, C.c_int, C.c_int, C.c_float, C.c_int, c_float_p, C.c_size_t, c_uint32_p, c_uint8_p, c_double_p, c_float_p,
+                                         C.POINTER(OutlierInfo)]),
     "fgoicp_lut_read": (C.c_int, [C.c_void_p, c_float_p, C.c_size_t]),
     "fgoicp_lut_search": (C.c_int, [C.c_void_p, c_float_p, C.c_size_t, c_float_p]),
     "fgoicp_lut_nodes": (C.c_int, [C.c_void_p, c_int_p, C.c_size_t, c_float_p]),

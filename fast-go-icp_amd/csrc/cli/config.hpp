@@ -125,6 +125,11 @@ struct Config {
         int refine_max_iter = 30;
         float refine_distance = 0.0f;  // ... distance threshold in the files' units (absent or 0: none)
         float target_voxel = 0.0f, source_voxel = 0.0f;  // EXTENSION: voxel size in the files' units; the cloud is replaced by its voxel grid's centroids (fgoicp_voxel_downsample) after loading; absent or <= 0: off, NaN is refused
+        // EXTENSION: outlier removal per cloud after the voxel grid (fgoicp_remove_outliers).  *_outlier_knn: the neighbours, absent or <= 0: off;
+        // *_outlier_std: the statistical filter's std ratio; *_outlier_radius (the files' units) > 0: the radius filter in place of the statistical one.
+        // A value that is not a number is refused.
+        int target_outlier_knn = 0, source_outlier_knn = 0;
+        float target_outlier_std = 2.0f, source_outlier_std = 2.0f, target_outlier_radius = 0.0f, source_outlier_radius = 0.0f;
     } params;
 
     explicit Config(const std::string& toml_filepath) {
@@ -186,6 +191,20 @@ struct Config {
             params.target_voxel = (float)num("params", "target_voxel", 0.0);
             params.source_voxel = (float)num("params", "source_voxel", 0.0);
             if (std::isnan(params.target_voxel) || std::isnan(params.source_voxel)) throw std::invalid_argument("params.target_voxel and params.source_voxel must not be NaN");
+            auto strict = [&](const char* key, double def) {  // as num, but a key that is present and not a number is an error of the configuration
+                auto k = tbl["params"].find(key);
+                if (k != tbl["params"].end() && k->second.kind != TomlValue::Number) throw std::invalid_argument(std::string("params.") + key + " must be a number");
+                const double v = num("params", key, def);
+                if (std::isnan(v)) throw std::invalid_argument(std::string("params.") + key + " must not be NaN");
+                return v;
+            };
+            auto knn = [](double v) { return v >= 1.0 ? (v > 1e6 ? 1000000 : (int)v) : 0; };
+            params.target_outlier_knn = knn(strict("target_outlier_knn", 0.0));
+            params.source_outlier_knn = knn(strict("source_outlier_knn", 0.0));
+            params.target_outlier_std = (float)strict("target_outlier_std", 2.0);
+            params.source_outlier_std = (float)strict("source_outlier_std", 2.0);
+            params.target_outlier_radius = (float)strict("target_outlier_radius", 0.0);
+            params.source_outlier_radius = (float)strict("source_outlier_radius", 0.0);
             auto clampf = [](float x, float lo, float hi) { return x < hi ? (x > lo ? x : lo) : hi; };
             params.target_subsample = clampf(params.target_subsample, 1e-5f, 1.0f);  // utilities.hpp:101-104
             params.source_subsample = clampf(params.source_subsample, 1e-5f, 1.0f);
@@ -383,7 +402,7 @@ inline void write_result_toml(const std::string& path, const icp::mat3& R, const
 // the column names — then one line per registered source point, in the order the cloud was loaded (after source_subsample): its coordinates
 // as loaded, the index of its nearest target point (into the target as loaded), its distance to it in the files' units
 // (sqrt(dist2) / scaling_factor) and 1 if the optimum counts it as an inlier.  Points and indices refer to the clouds AS REGISTERED: with
-// params.source_voxel / params.target_voxel those are the voxel grids' centroids in their row order, not the points of the files.
+// params.source_voxel / params.target_voxel those are the voxel grids' centroids in their row order, not the points of the files, and with params.*_outlier_knn the rows the filter kept, in their order.
 inline void write_alignment_txt(const std::string& path, const std::vector<icp::vec3>& src, const uint32_t* idx, const float* dist2, const uint8_t* inlier,
                                 const fgoicp_alignment_summary& s) {
     std::ofstream f(path);

@@ -40,6 +40,30 @@ static void voxel_thin(std::vector<icp::vec3>& pc, float voxel, const char* whic
     pc.swap(out);
 }
 
+// params.*_outlier_knn: the cloud replaced by the points fgoicp_remove_outliers keeps (device 0), after the voxel grid and before any solver
+// exists: everything downstream sees the filtered cloud, and the indices of io.alignment are those of its rows.  A radius > 0 selects the
+// radius filter, otherwise the statistical one runs with the std ratio.  A refused call is an error of the configuration: exit code 1.
+static void outlier_filter(std::vector<icp::vec3>& pc, int knn, float std_ratio, float radius, const char* which) {
+    if (knn <= 0) return;
+    const bool by_radius = radius > 0.0f;
+    std::vector<icp::vec3> out(pc.size());
+    fgoicp_outlier_info_t oi{};
+    oi.struct_size = sizeof(oi);
+    const int rc = fgoicp_remove_outliers(&pc.data()->x, pc.size(), by_radius ? FGOICP_OUTLIER_RADIUS : FGOICP_OUTLIER_STATISTICAL, knn, by_radius ? radius : std_ratio, 0,
+                                          &out.data()->x, out.size(), nullptr, nullptr, nullptr, nullptr, &oi);
+    if (rc != FGOICP_OK) {
+        icp::Logger(icp::LogLevel::Error) << "params." << which << "_outlier_knn = " << knn << ": status " << rc << ": " << fgoicp_last_error();
+        std::exit(1);
+    }
+    out.resize((size_t)oi.kept);
+    if (by_radius)
+        icp::Logger(icp::LogLevel::Info) << "Outlier filter (" << which << "): " << pc.size() << " -> " << out.size() << " points, " << knn << " neighbours, radius " << radius;
+    else
+        icp::Logger(icp::LogLevel::Info) << "Outlier filter (" << which << "): " << pc.size() << " -> " << out.size() << " points, " << knn << " neighbours, std ratio "
+                                         << std_ratio << ", threshold " << oi.threshold;
+    pc.swap(out);
+}
+
 // --batch LIST: every config of the list registered in one fgoicp_batch run; each config's io.output / io.visualization as a lone -c run
 // of it writes them (the seconds written are the batch's).  The configs must agree on the schedule and round width; each is trimmed with
 // its own params.trim_fraction.
@@ -79,6 +103,8 @@ static int run_batch(const std::string& list_file) {
         cli::load_cloud(c.io.source, c.params.source_subsample, pcs[i], c.params.seed < 0 ? -1 : c.params.seed + 1);
         voxel_thin(pct[i], c.params.target_voxel, "target");
         voxel_thin(pcs[i], c.params.source_voxel, "source");
+        outlier_filter(pct[i], c.params.target_outlier_knn, c.params.target_outlier_std, c.params.target_outlier_radius, "target");
+        outlier_filter(pcs[i], c.params.source_outlier_knn, c.params.source_outlier_std, c.params.source_outlier_radius, "source");
         icp::Logger(icp::LogLevel::Info) << "Pair " << i << ": target (" << pct[i].size() << ") " << c.io.target << ", source (" << pcs[i].size() << ") " << c.io.source;
         pairs[i] = fgoicp_batch_pair{&pct[i].data()->x, pct[i].size(), &pcs[i].data()->x, pcs[i].size(), c.params.lut_resolution, c.params.mse_threshold};
         trim[i] = c.params.trim_fraction;
@@ -187,6 +213,8 @@ int main(int argc, char* argv[]) {
     icp::Logger(icp::LogLevel::Info) << "Source point cloud (" << pcs.size() << ") loaded from " << config.io.source;
     voxel_thin(pct, config.params.target_voxel, "target");
     voxel_thin(pcs, config.params.source_voxel, "source");
+    outlier_filter(pct, config.params.target_outlier_knn, config.params.target_outlier_std, config.params.target_outlier_radius, "target");
+    outlier_filter(pcs, config.params.source_outlier_knn, config.params.source_outlier_std, config.params.source_outlier_radius, "source");
     const std::vector<icp::vec3> pct_in = pct, pcs_in = pcs;
     for (const auto* pc : {&pct, &pcs}) {  // verbose: the statistics the pre-processing normalises by (TODO.md:7 of the reference)
         fgoicp_cloud_stats_t cs{};

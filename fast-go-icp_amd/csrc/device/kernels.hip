@@ -2640,9 +2640,14 @@ void launch_align_info(const unsigned char* inlier, const float* d2, const uint3
 // matrix its singular triplets are the eigenpairs, descending), normalised in fp64, stored as fp32.  Its SIGN is left as it falls.  A
 // neighbourhood whose largest eigenvalue is zero or not finite gets the zero vector.
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void target_knn_kernel(BvhView t, const float4* __restrict__ tgt, int nt, int k, uint32_t* __restrict__ knn_idx,
-                                                        float* __restrict__ knn_d2, float4* __restrict__ normals) {
-    extern __shared__ unsigned long long s_knn[];  // [k][64]
+// The walk and the list, shared by target_knn_kernel and outlier_knn_kernel (inlined into both): on return the lane's list is
+// s_knn[j * 64 + lane], j < k, ascending, and `worst` its last key.
+struct KnnQuery {
+    float4 p;                  // the lane's query: a point of the tree, w = its caller index
+    bool active;               // slot < nt
+    unsigned long long worst;  // the list's last key
+};
+__device__ __forceinline__ KnnQuery knn_walk(const BvhView& t, int nt, int k, unsigned long long* s_knn /* [k][64] */) {
     const int lane = threadIdx.x;
     const int slot = blockIdx.x * 64 + lane;
     const bool active = slot < nt;
@@ -2681,8 +2686,17 @@ __global__ __launch_bounds__(64) void target_knn_kernel(BvhView t, const float4*
     const float seed = kth();
     clear();
     box_scan(t, qx, qy, qz, active, 0, 1, offer, [&]() { return fminf(seed, kth()); });
-    if (!active) return;
-    const uint32_t me = __float_as_uint(p.w);
+    return KnnQuery{p, active, worst};
+}
+
+__global__ __launch_bounds__(64) void target_knn_kernel(BvhView t, const float4* __restrict__ tgt, int nt, int k, uint32_t* __restrict__ knn_idx,
+                                                        float* __restrict__ knn_d2, float4* __restrict__ normals) {
+    extern __shared__ unsigned long long s_knn[];  // [k][64]
+    const KnnQuery q = knn_walk(t, nt, k, s_knn);
+    if (!q.active) return;
+    const int lane = threadIdx.x;
+    const unsigned long long kEmpty = ~0ull, worst = q.worst;
+    const uint32_t me = __float_as_uint(q.p.w);
     if (knn_idx || knn_d2) {
         for (int j = 0; j < k; ++j) {
             const unsigned long long key = s_knn[j * 64 + lane];
@@ -2720,6 +2734,25 @@ __global__ __launch_bounds__(64) void target_knn_kernel(BvhView t, const float4*
 
 void launch_target_knn(const BvhView& t, const float4* tgt, int nt, int k, uint32_t* knn_idx, float* knn_d2, float4* normals, hipStream_t s) {
     hipLaunchKernelGGL(target_knn_kernel, dim3((nt + 63) / 64), dim3(64), (size_t)k * 64 * sizeof(unsigned long long), s, t, tgt, nt, k, knn_idx, knn_d2, normals);
+}
+
+// Outlier removal (fgoicp_remove_outliers; outlier.hip): the same walk and list over the cloud's own tree, 2 <= k <= 32.
+// Epilogue: mean_dist[me] = (the sum over the list, in list order, of sqrt((double)d2)) / (double)k — IEEE fp64 square roots, additions
+// and one division — and kth_dist2[me] = the d2 of the list's last entry, both at the caller index (12 bytes per point).
+__global__ __launch_bounds__(64) void outlier_knn_kernel(BvhView t, int nt, int k, double* __restrict__ mean_dist, float* __restrict__ kth_dist2) {
+    extern __shared__ unsigned long long s_knn[];  // [k][64]
+    const KnnQuery q = knn_walk(t, nt, k, s_knn);
+    if (!q.active) return;
+    const int lane = threadIdx.x;
+    const uint32_t me = __float_as_uint(q.p.w);
+    double sum = 0.0;
+    for (int j = 0; j < k; ++j) sum += sqrt((double)__uint_as_float((uint32_t)(s_knn[j * 64 + lane] >> 32)));
+    mean_dist[me] = sum / (double)k;
+    kth_dist2[me] = __uint_as_float((uint32_t)(q.worst >> 32));
+}
+
+void launch_outlier_knn(const BvhView& t, int nt, int k, double* mean_dist, float* kth_dist2, hipStream_t s) {
+    hipLaunchKernelGGL(outlier_knn_kernel, dim3((nt + 63) / 64), dim3(64), (size_t)k * 64 * sizeof(unsigned long long), s, t, nt, k, mean_dist, kth_dist2);
 }
 
 // ---------------------------------------------------------------------------------------------

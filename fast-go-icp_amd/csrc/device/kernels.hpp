@@ -138,6 +138,11 @@ void launch_align_info(const unsigned char* inlier, const float* d2, const uint3
 // normals (optional): nt x {n.x, n.y, n.z, 0} in caller order, the zero vector for a degenerate neighbourhood.
 constexpr int kKnnMin = 4, kKnnMax = 32;
 void launch_target_knn(const BvhView& t, const float4* tgt, int nt, int k, uint32_t* knn_idx, float* knn_d2, float4* normals, hipStream_t s);
+// Outlier removal (fgoicp_remove_outliers; kernels.hip outlier_knn_kernel, the walk and the list of target_knn_kernel): per point of the tree,
+// at its caller index, the mean of the fp64 square roots of its k smallest squared distances (itself included) and the k-th of them.
+// 2 <= k <= 32, k <= nt.
+constexpr int kOutlierKnnMin = 2;
+void launch_outlier_knn(const BvhView& t, int nt, int k, double* mean_dist, float* kth_dist2, hipStream_t s);
 // The point-to-plane normal equations (fgoicp_plane_moments; kernels.hip plane_moments_kernel, plane_moments_fold_kernel) over the report's
 // arrays (caller order) and the moved queries of its index scan (device order, `moved`): counted are the caller indices with inlier != 0,
 // d2 <= max_d2, corr < nt and a non-zero normal at corr.  rows: ceil(n / kBlock) entries; out29 = {count, the bits of 28 doubles: the

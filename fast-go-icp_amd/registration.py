@@ -59,6 +59,43 @@ def voxel_downsample(points, voxel_size, origin=None, device=0, return_map=False
                                           origin=np.array(info.origin, np.float32), voxel_size=float(info.voxel_size))
 
 
+def _remove_outliers(points, mode, k, param, device, return_map):
+    p = _cloud(points)
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+        raise TypeError("k must be an integer")
+    n = len(p)
+    out = np.empty((n, 3), np.float32)
+    idx = np.empty(n, np.uint32) if return_map else None
+    keep = np.empty(n, np.uint8) if return_map else None
+    mean_dist = np.empty(n, np.float64) if return_map else None
+    kth = np.empty(n, np.float32) if return_map else None
+    ptr = lambda a, t: None if a is None else a.ctypes.data_as(t)
+    info = _lib.OutlierInfo()
+    _lib.check(_lib.load().fgoicp_remove_outliers(_fp(p) if n else None, n, mode, int(k), float(param), int(device), _fp(out), n, ptr(idx, _lib.c_uint32_p),
+                                                  ptr(keep, _lib.c_uint8_p), ptr(mean_dist, _lib.c_double_p), ptr(kth, _lib.c_float_p), C.byref(info)),
+               "fgoicp_remove_outliers")
+    m = int(info.kept)
+    out = out[:m].copy()
+    if not return_map:
+        return out
+    return out, keep.astype(bool), idx[:m].copy(), mean_dist, kth, dict(points=int(info.points), kept=m, mode=int(info.mode), k=int(info.k), mean=float(info.mean),
+                                                                        stddev=float(info.stddev), threshold=float(info.threshold), radius2=float(info.radius2))
+
+
+def remove_statistical_outliers(points, k=20, std_ratio=2.0, device=0, return_map=False):
+    """fgoicp_remove_outliers, FGOICP_OUTLIER_STATISTICAL: keeps the points whose mean distance to their k nearest points (themselves included)
+    is at most mean + std_ratio * stddev of that statistic over the cloud — the kept points in caller order as an (m, 3) float32 array.
+    return_map=True returns (kept, keep_mask (n,) bool, kept_index (m,) uint32, mean_dist (n,) float64, kth_dist2 (n,) float32, info) with
+    info = dict(points, kept, mode, k, mean, stddev, threshold, radius2)."""
+    return _remove_outliers(points, _lib.OUTLIER_STATISTICAL, k, std_ratio, device, return_map)
+
+
+def remove_radius_outliers(points, k, radius, device=0, return_map=False):
+    """fgoicp_remove_outliers, FGOICP_OUTLIER_RADIUS: keeps the points with at least k points of the cloud (themselves included) within `radius`;
+    the returns are those of remove_statistical_outliers."""
+    return _remove_outliers(points, _lib.OUTLIER_RADIUS, k, radius, device, return_map)
+
+
 class Alignment:
     """EXTENSION: the alignment report of fgoicp_alignment / fgoicp_solver_alignment / fgoicp_batch_alignment.  Arrays in the caller's point
     order: indices (ns,) uint32 — nearest target point of every source point; dist2 (ns,) float32 — its squared distance in the frame the

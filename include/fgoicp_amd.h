@@ -489,6 +489,45 @@ int fgoicp_voxel_downsample(const float* xyz, size_t n, float voxel_size, const 
                             float* out_xyz, size_t capacity_points,
                             uint32_t* voxel_of_point_n, uint32_t* count_per_voxel,
                             fgoicp_voxel_info_t* out);
+/*
+ * EXTENSION — outlier removal on the device (no reference counterpart; Open3D: remove_statistical_outlier(nb_neighbors, std_ratio) and
+ * remove_radius_outlier(nb_points, radius), PCL: StatisticalOutlierRemoval and RadiusOutlierRemoval).  The step of a registration pipeline
+ * between downsampling and normals / registration: stray points of a TARGET cannot be trimmed away later.
+ *
+ * The list L_i of point i (caller order): the k smallest keys (bits(d2_ij) << 32) | j over ALL j, i itself included (the convention of
+ * fgoicp_target_knn and of Open3D's search_knn), d2_ij the scans' fp32 dist_sq(p_i, p_j) = fma(dz, dz, fma(dy, dy, dx * dx)); a tie at the
+ * cut goes to the lowest caller index.  2 <= k <= 32, k <= n.
+ *   kth_dist2[i]  the fp32 d2 of the last entry of L_i
+ *   mean_dist[i]  (the sum over L_i, in list order, of sqrt((double)d2)) / (double)k: IEEE fp64 square roots, additions and one division
+ * FGOICP_OUTLIER_STATISTICAL (param = std_ratio, finite and >= 0): mean = (sum_i mean_dist[i]) / n, stddev = sqrt(sum_i (mean_dist[i] - mean)^2
+ *   / (n - 1)) (the sample form, as Open3D; 0 for n == 1), both fp64 with every addition in an order that is a function of n alone (no
+ *   floating-point atomics); threshold = mean + (double)param * stddev, formed on the host, unfused; keep[i] = mean_dist[i] <= threshold,
+ *   compared with the very value `out` reports.
+ * FGOICP_OUTLIER_RADIUS (param = the radius, finite and > 0): radius2 = param * param in fp32; keep[i] = kth_dist2[i] <= radius2 — a point
+ *   stays when at least k points of the cloud, itself included, lie within the radius.
+ * Output rows: the kept points in caller order, bits verbatim; kept_index[r] = the caller index of row r.  keep_n (n bytes, 0 / 1),
+ * mean_dist_n (n doubles) and kth_dist2_n (n floats) are per input point.  Every array pointer may be NULL (all NULL: count only).
+ * out_xyz (3 floats per row) and kept_index hold capacity_points rows; if either is given and capacity_points < kept the call returns
+ * FGOICP_ERR_TOO_LARGE with `out` filled, so a second call can be sized, and writes nothing to the arrays; a capacity of n always suffices.
+ * Refused with FGOICP_ERR_INVALID_ARG before any device work (a host pass over the cloud): a null xyz or n == 0, n >= 2^31, an unknown mode,
+ * k outside [2, 32] or above n, a bad param, a non-finite coordinate, a null `out` or a struct_size that ends before radius2.  No usable
+ * device: FGOICP_ERR_NO_DEVICE (no CPU fallback); allocation failure: FGOICP_ERR_OOM.
+ * Two calls on the same input return the same bytes in every output.  The call owns its stream and its device memory (about 70 bytes per
+ * point) and frees both before it returns; it touches no fgoicp_ctx and no global state and may be called from several threads.
+ */
+enum { FGOICP_OUTLIER_STATISTICAL = 0, FGOICP_OUTLIER_RADIUS = 1 };
+typedef struct fgoicp_outlier_info_t {
+    uint32_t struct_size;        /* IN: sizeof(fgoicp_outlier_info_t) as the CALLER was compiled; no byte beyond it is written, 0 is refused */
+    uint64_t points, kept;       /* n; rows of the output */
+    int      mode, k;
+    double   mean, stddev;       /* STATISTICAL: of mean_dist over the cloud; RADIUS: 0 */
+    double   threshold;          /* STATISTICAL: the value mean_dist was compared with; RADIUS: 0 */
+    float    radius2;            /* RADIUS: the fp32 value kth_dist2 was compared with; STATISTICAL: 0 */
+} fgoicp_outlier_info_t;
+int fgoicp_remove_outliers(const float* xyz, size_t n, int mode, int k, float param, int device,
+                           float* out_xyz, size_t capacity_points, uint32_t* kept_index,
+                           uint8_t* keep_n, double* mean_dist_n, float* kth_dist2_n,
+                           fgoicp_outlier_info_t* out);
 /* The operator context the solver drives (borrowed; valid until solver_destroy). */
 fgoicp_ctx* fgoicp_solver_ctx(fgoicp_solver* s);
 
