@@ -183,6 +183,12 @@ _SIGS = {
     "fgoicp_plane_apply_step": (C.c_int, [c_float_p, c_float_p, C.POINTER(C.c_double), c_float_p, c_float_p]),
     "fgoicp_icp_plane": (C.c_int, [C.c_void_p, c_float_p, c_float_p, C.c_size_t, C.c_float, C.c_float, C.POINTER(PlaneResult)]),
     "fgoicp_solver_refine_plane": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.c_float, C.c_float, C.POINTER(PlaneResult)]),
+    "fgoicp_ctx_set_source_normals": (C.c_int, [C.c_void_p, c_float_p, C.c_int]),
+    "fgoicp_source_normals": (C.c_int, [C.c_void_p, c_float_p]),
+    "fgoicp_gicp_moments": (C.c_int, [C.c_void_p, c_float_p, c_float_p, C.c_float, C.c_double, C.POINTER(PlaneMoments)]),
+    "fgoicp_icp_gicp": (C.c_int, [C.c_void_p, c_float_p, c_float_p, C.c_size_t, C.c_float, C.c_float, C.c_double, C.POINTER(PlaneResult)]),
+    "fgoicp_solver_refine_gicp": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.c_float, C.c_float, C.c_double, C.POINTER(PlaneResult)]),
+    "fgoicp_gicp_terms": (C.c_int, [c_float_p, c_float_p, c_float_p, c_float_p, c_float_p, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "fgoicp_icp": (C.c_int, [C.c_void_p, c_float_p, c_float_p, C.c_size_t, C.c_float, c_float_p, c_float_p, c_float_p, c_int_p]),
     "fgoicp_icp_batch": (C.c_int, [C.c_void_p, C.c_int, c_float_p, c_float_p, C.c_size_t, C.c_float, c_float_p, c_float_p, c_float_p, c_int_p]),
     "fgoicp_procrustes": (C.c_int, [C.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p, c_int_p]),

@@ -120,10 +120,11 @@ struct Config {
         float trim_fraction = 0.0f;  // EXTENSION: > 0 enables trimmed Go-ICP; `trim` itself stays parsed-and-ignored as upstream
         int gpus = 1;                // EXTENSION: > 1 shards the outer BnB over that many GPUs of this node (one host thread each, RCCL)
         float information_distance = 0.0f;  // EXTENSION: distance threshold of io.information in the files' units (absent or 0: none)
-        std::string refine;          // EXTENSION: "plane" = point-to-plane refinement after the search (fgoicp_solver_refine_plane); absent or "": none; anything else is refused
+        std::string refine;          // EXTENSION: "plane" = point-to-plane refinement after the search (fgoicp_solver_refine_plane), "gicp" = Generalized ICP (fgoicp_solver_refine_gicp); absent or "": none; anything else is refused
         int refine_knn = 16;         // ... neighbours per target point for its normal (4 .. 32)
         int refine_max_iter = 30;
         float refine_distance = 0.0f;  // ... distance threshold in the files' units (absent or 0: none)
+        double refine_epsilon = 1e-3;  // ... "gicp" only: the smallest eigenvalue of the regularised covariances, in (0, 1]
         float target_voxel = 0.0f, source_voxel = 0.0f;  // EXTENSION: voxel size in the files' units; the cloud is replaced by its voxel grid's centroids (fgoicp_voxel_downsample) after loading; absent or <= 0: off, NaN is refused
         // EXTENSION: outlier removal per cloud after the voxel grid (fgoicp_remove_outliers).  *_outlier_knn: the neighbours, absent or <= 0: off;
         // *_outlier_std: the statistical filter's std ratio; *_outlier_radius (the files' units) > 0: the radius filter in place of the statistical one.
@@ -185,9 +186,11 @@ struct Config {
             params.refine_max_iter = std::max(0, (int)num("params", "refine_max_iter", 30));
             params.refine_distance = (float)num("params", "refine_distance", 0.0);
             if (!(params.refine_distance > 0.0f)) params.refine_distance = 0.0f;
-            if (!params.refine.empty() && params.refine != "plane")  // (thrown, not exit(1): the callers report it; a typo must not silently skip the refinement)
-                throw std::invalid_argument("params.refine = \"" + params.refine + "\" is not supported: the only refinement is \"plane\"");
-            if (params.refine == "plane" && (params.refine_knn < 4 || params.refine_knn > 32)) throw std::invalid_argument("params.refine_knn must lie in [4, 32]");
+            params.refine_epsilon = num("params", "refine_epsilon", 1e-3);
+            if (!params.refine.empty() && params.refine != "plane" && params.refine != "gicp")  // (thrown, not exit(1): the callers report it; a typo must not silently skip the refinement)
+                throw std::invalid_argument("params.refine = \"" + params.refine + "\" is not supported: the refinements are \"plane\" and \"gicp\"");
+            if (!params.refine.empty() && (params.refine_knn < 4 || params.refine_knn > 32)) throw std::invalid_argument("params.refine_knn must lie in [4, 32]");
+            if (params.refine == "gicp" && !(params.refine_epsilon > 0.0 && params.refine_epsilon <= 1.0)) throw std::invalid_argument("params.refine_epsilon must lie in (0, 1]");
             params.target_voxel = (float)num("params", "target_voxel", 0.0);
             params.source_voxel = (float)num("params", "source_voxel", 0.0);
             if (std::isnan(params.target_voxel) || std::isnan(params.source_voxel)) throw std::invalid_argument("params.target_voxel and params.source_voxel must not be NaN");
@@ -376,9 +379,10 @@ inline size_t load_cloud(const std::string& filepath, float subsample, std::vect
 }
 
 // io.output / io.visualization (declared by test/bunny.toml:10-11, unimplemented upstream)
-// refined (optional, EXTENSION: params.refine = "plane"): a [refined] table behind the existing keys, which stay as they are
+// refined (optional, EXTENSION: params.refine): a [refined] table behind the existing keys, which stay as they are; rmse_key names its
+// residual — plane_rmse for "plane", gicp_rmse for "gicp"
 inline void write_result_toml(const std::string& path, const icp::mat3& R, const icp::vec3& t, float sse, size_t ns, double seconds,
-                              const fgoicp_run_stats& st, const fgoicp_plane_result_t* refined = nullptr) {
+                              const fgoicp_run_stats& st, const fgoicp_plane_result_t* refined = nullptr, const char* rmse_key = "plane_rmse") {
     std::ofstream f(path);
     if (!f) throw std::runtime_error("Unable to write " + path);
     f.precision(9);
@@ -394,7 +398,7 @@ inline void write_result_toml(const std::string& path, const icp::mat3& R, const
     f << "\n[refined]\nrotation = [\n";
     for (int r = 0; r < 3; ++r) f << "  [" << Q[r] << ", " << Q[3 + r] << ", " << Q[6 + r] << "],\n";
     f << "]\ntranslation = [" << refined->t[0] << ", " << refined->t[1] << ", " << refined->t[2] << "]\n";
-    f << "plane_rmse = " << refined->plane_rmse / (double)refined->scaling_factor << "\niterations = " << refined->iterations << "\nrank = " << refined->rank
+    f << rmse_key << " = " << refined->plane_rmse / (double)refined->scaling_factor << "\niterations = " << refined->iterations << "\nrank = " << refined->rank
       << "\ncorrespondences = " << refined->correspondences << "\n";
 }
 

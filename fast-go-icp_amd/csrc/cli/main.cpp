@@ -242,13 +242,26 @@ int main(int argc, char* argv[]) {
         icp::check_status(fgoicp_solver_alignment(s, idx.data(), d2.data(), inl.data(), nullptr, &sm), "fgoicp_solver_alignment");
         cli::write_alignment_txt(config.io.alignment, pcs_in, idx.data(), d2.data(), inl.data(), sm);
     };
-    // params.refine = "plane": point-to-plane refinement from the best transform, after the search (the search's own result stays as it is)
+    // params.refine = "plane" / "gicp": point-to-plane / Generalized-ICP refinement from the best transform, after the search (the search's own result stays as it is)
     fgoicp_plane_result_t refined{};
     bool have_refined = false;
+    const bool gicp = config.params.refine == "gicp";
     auto refine = [&](fgoicp_solver* s) {
-        if (config.params.refine != "plane") return;
+        if (config.params.refine != "plane" && !gicp) return;
         refined.struct_size = sizeof(refined);
         const float d = config.params.refine_distance;
+        if (gicp) {
+            icp::check_status(fgoicp_solver_refine_gicp(s, config.params.refine_knn, (size_t)config.params.refine_max_iter, 1e-6f, d > 0.0f ? d : INFINITY,
+                                                        config.params.refine_epsilon, &refined), "fgoicp_solver_refine_gicp");
+            have_refined = true;
+            icp::mat3 Rr;
+            std::memcpy(Rr.data(), refined.R, sizeof(refined.R));
+            icp::Logger(icp::LogLevel::Info) << "Generalized-ICP refinement: " << refined.iterations << " iterations, rank " << refined.rank << ", " << refined.correspondences
+                                             << " correspondences, epsilon " << config.params.refine_epsilon << ", plane-to-plane RMSE "
+                                             << refined.plane_rmse / (double)refined.scaling_factor << "\n\tRotation:\n" << Rr
+                                             << "\n\tTranslation: " << icp::vec3{refined.t[0], refined.t[1], refined.t[2]};
+            return;
+        }
         icp::check_status(fgoicp_solver_refine_plane(s, config.params.refine_knn, (size_t)config.params.refine_max_iter, 1e-6f, d > 0.0f ? d : INFINITY, &refined),
                           "fgoicp_solver_refine_plane");
         have_refined = true;
@@ -334,7 +347,7 @@ int main(int argc, char* argv[]) {
     }
     icp::Logger(icp::LogLevel::Debug) << "Subcubes: " << st.trans_cubes << ", rotation cubes: " << st.rot_cubes << ", ICP runs: " << st.icp_runs;
     icp::Logger(icp::LogLevel::Info) << "Fast Go-ICP finished, time elapsed: " << std::fixed << std::setprecision(3) << elapsed_seconds.count() << " seconds";
-    if (!config.io.output.empty()) cli::write_result_toml(config.io.output, R, t, best_error, pcs_in.size(), elapsed_seconds.count(), st, have_refined ? &refined : nullptr);
+    if (!config.io.output.empty()) cli::write_result_toml(config.io.output, R, t, best_error, pcs_in.size(), elapsed_seconds.count(), st, have_refined ? &refined : nullptr, gicp ? "gicp_rmse" : "plane_rmse");
     if (!config.io.visualization.empty()) cli::write_visualization_ply(config.io.visualization, pct_in, pcs_in, R, t);
     return 0;
 }

@@ -680,8 +680,8 @@ int ctx_target_knn(fgoicp_ctx* c, int k, uint32_t* idx, float* d2) {
 // EXTENSION: the point-to-plane normal equations at (R, t) (fgoicp_plane_moments), enqueued behind the report's device half on lane 0's
 // stream like the information moments: reads the report's arrays, the moved queries the index scan left in d_work, the target and its
 // normals; writes its own rows only.
-int ctx_plane_moments(fgoicp_ctx* c, const float* R9, const float* t3, float max_dist2, PlaneMoments* m, float* sse_out) {
-    if (!c->normals_set) { set_error("the target normals are not set: call fgoicp_ctx_set_target_normals first"); return FGOICP_ERR_INVALID_ARG; }
+// gicp: the Generalized-ICP normal equations (launch_gicp_moments) in place of the point-to-plane ones; everything else is shared
+static int moments_at(fgoicp_ctx* c, const float* R9, const float* t3, float max_dist2, bool gicp, double epsilon, PlaneMoments* m, float* sse_out) {
     HIPCHK(hipSetDevice(c->device));
     if (!c->d_plane_rows) {
         const size_t nblk = (c->ns + kBlock - 1) / kBlock;
@@ -692,8 +692,12 @@ int ctx_plane_moments(fgoicp_ctx* c, const float* R9, const float* t3, float max
     if (rc) return rc;
     fgoicp_ctx::IcpLane& L = c->lanes[0];
     fgoicp_ctx::AlignScratch& A = c->align;
-    launch_plane_moments(L.d_work, c->d_orig_of_slot, A.d_inl, A.d_d2, A.d_corr, c->d_tgt, c->d_normals, (int)c->ns, (int)c->nt, max_dist2, c->d_plane_rows, c->d_plane_out,
-                         L.stream);
+    if (gicp)
+        launch_gicp_moments(L.d_work, c->d_orig_of_slot, A.d_inl, A.d_d2, A.d_corr, c->d_tgt, c->d_normals, c->d_src_normals, R9, epsilon, (int)c->ns, (int)c->nt, max_dist2,
+                            c->d_plane_rows, c->d_plane_out, L.stream);
+    else
+        launch_plane_moments(L.d_work, c->d_orig_of_slot, A.d_inl, A.d_d2, A.d_corr, c->d_tgt, c->d_normals, (int)c->ns, (int)c->nt, max_dist2, c->d_plane_rows, c->d_plane_out,
+                             L.stream);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(L.stream));
     unsigned long long h[1 + kPlaneTerms];
@@ -704,10 +708,21 @@ int ctx_plane_moments(fgoicp_ctx* c, const float* R9, const float* t3, float max
     if (sse_out) *sse_out = sse_result(c, L);
     return FGOICP_OK;
 }
+int ctx_plane_moments(fgoicp_ctx* c, const float* R9, const float* t3, float max_dist2, PlaneMoments* m, float* sse_out) {
+    if (!c->normals_set) { set_error("the target normals are not set: call fgoicp_ctx_set_target_normals first"); return FGOICP_ERR_INVALID_ARG; }
+    return moments_at(c, R9, t3, max_dist2, false, 0.0, m, sse_out);
+}
+int ctx_gicp_moments(fgoicp_ctx* c, const float* R9, const float* t3, float max_dist2, double epsilon, PlaneMoments* m, float* sse_out) {
+    if (!c->normals_set) { set_error("the target normals are not set: call fgoicp_ctx_set_target_normals first"); return FGOICP_ERR_INVALID_ARG; }
+    if (!c->src_normals_set) { set_error("the source normals are not set: call fgoicp_ctx_set_source_normals first"); return FGOICP_ERR_INVALID_ARG; }
+    if (!gicp_epsilon_ok(epsilon)) { set_error("epsilon must be finite and lie in (0, 1]"); return FGOICP_ERR_INVALID_ARG; }
+    return moments_at(c, R9, t3, max_dist2, true, epsilon, m, sse_out);
+}
 
-// fgoicp_icp_plane: evaluate, solve, update (plane.hpp), until the step is short, the first solve is rank-deficient, nothing is counted or
-// max_iter steps are done; the result's count, rmse and sse are those of one more evaluation at the pose returned.
-int ctx_icp_plane(fgoicp_ctx* c, const float* R0, const float* t0, size_t max_iter, float thr, float max_dist2, fgoicp_plane_result_t* full) {
+// fgoicp_icp_plane, fgoicp_icp_gicp: evaluate, solve, update (plane.hpp), until the step is short, the first solve is rank-deficient,
+// nothing is counted or max_iter steps are done; the result's count, rmse and sse are those of one more evaluation at the pose returned.
+template <class Eval>
+static int moments_loop(const char* where, Eval eval, const float* R0, const float* t0, size_t max_iter, float thr, fgoicp_plane_result_t* full) {
     Mat3f R = Mat3f::from(R0);
     Vec3f t{t0[0], t0[1], t0[2]};
     PlaneMoments m;
@@ -716,10 +731,10 @@ int ctx_icp_plane(fgoicp_ctx* c, const float* R0, const float* t0, size_t max_it
     bool stop = false;
     for (;;) {
         const float t3[3] = {t.x, t.y, t.z};
-        const int rc = ctx_plane_moments(c, R.m, t3, max_dist2, &m, &sse);
+        const int rc = eval(R.m, t3, &m, &sse);
         if (rc) return rc;
         if (stop || (size_t)iters >= max_iter || m.n == 0) break;
-        if (!plane_moments_finite(m.m)) { set_error("fgoicp_icp_plane: the normal equations are not finite"); return FGOICP_ERR_INVALID_ARG; }
+        if (!plane_moments_finite(m.m)) { set_error(std::string(where) + ": the normal equations are not finite"); return FGOICP_ERR_INVALID_ARG; }
         double xi[6];
         plane_step(m.m, xi, &rank);
         plane_apply_step(R, t, xi, R, t);
@@ -737,6 +752,89 @@ int ctx_icp_plane(fgoicp_ctx* c, const float* R0, const float* t0, size_t max_it
     full->plane_rmse = m.n ? std::sqrt(m.m[27] / (double)m.n) : 0.0;
     full->sse = sse;
     full->scaling_factor = 1.0f;
+    return FGOICP_OK;
+}
+int ctx_icp_plane(fgoicp_ctx* c, const float* R0, const float* t0, size_t max_iter, float thr, float max_dist2, fgoicp_plane_result_t* full) {
+    return moments_loop("fgoicp_icp_plane", [&](const float* R9, const float* t3, PlaneMoments* m, float* sse) { return ctx_plane_moments(c, R9, t3, max_dist2, m, sse); }, R0, t0,
+                        max_iter, thr, full);
+}
+int ctx_icp_gicp(fgoicp_ctx* c, const float* R0, const float* t0, size_t max_iter, float thr, float max_dist2, double epsilon, fgoicp_plane_result_t* full) {
+    return moments_loop("fgoicp_icp_gicp", [&](const float* R9, const float* t3, PlaneMoments* m, float* sse) { return ctx_gicp_moments(c, R9, t3, max_dist2, epsilon, m, sse); },
+                        R0, t0, max_iter, thr, full);
+}
+
+// EXTENSION: source normals (fgoicp_ctx_set_source_normals), kept in device slot order for gicp_moments_kernel.  Given: checked and
+// normalised on the host (fp64) as the target's, permuted, uploaded.  Estimated: the rule of the target's normals over the source itself —
+// a caller-order float4 copy of the source as the context holds it, a throw-away tree over it (bvh_build_host), one launch of
+// target_knn_kernel, the result moved from caller order into slot order; tree, copy and caller-order normals are freed before the call returns.
+int ctx_set_source_normals(fgoicp_ctx* c, const float* normals, int k) {
+    const size_t ns = c->ns;
+    std::vector<float4> h;
+    if (normals) {
+        h.resize(ns);
+        std::vector<float4> caller(ns);
+        for (size_t i = 0; i < ns; ++i) {
+            const double x = normals[3 * i], y = normals[3 * i + 1], z = normals[3 * i + 2];
+            const double len = std::sqrt(x * x + y * y + z * z);
+            if (!std::isfinite(len) || !(len > 0.0)) {
+                set_error("fgoicp_ctx_set_source_normals: normal " + std::to_string(i) + " is zero or not finite");
+                return FGOICP_ERR_INVALID_ARG;
+            }
+            caller[i] = make_float4((float)(x / len), (float)(y / len), (float)(z / len), 0.f);
+        }
+        for (size_t i = 0; i < ns; ++i) h[i] = caller[c->perm[i]];
+    } else {
+        if (k < kKnnMin || k > kKnnMax || (size_t)k > ns) {
+            set_error("fgoicp_ctx_set_source_normals: k must lie in [4, 32] and be at most the number of source points");
+            return FGOICP_ERR_INVALID_ARG;
+        }
+        if (c->brute_force_nn) { set_error("fgoicp_ctx_set_source_normals: estimating normals needs the search tree, which a brute-force context does not build: pass normals"); return FGOICP_ERR_INVALID_ARG; }
+    }
+    HIPCHK(hipSetDevice(c->device));
+    if (!c->d_src_normals) HIPCHK(hipMalloc(&c->d_src_normals, sizeof(float4) * ns));
+    hipStream_t st = c->lanes[0].stream;
+    HIPCHK(hipStreamSynchronize(st));
+    if (normals) {
+        c->src_normals_set = false;
+        HIPCHK(hipMemcpy(c->d_src_normals, h.data(), sizeof(float4) * ns, hipMemcpyHostToDevice));
+        c->src_normals_set = true;
+        return FGOICP_OK;
+    }
+    if (!c->d_orig_of_slot) {
+        HIPCHK(hipMalloc(&c->d_orig_of_slot, sizeof(uint32_t) * ns));
+        HIPCHK(hipMemcpy(c->d_orig_of_slot, c->perm.data(), sizeof(uint32_t) * ns, hipMemcpyHostToDevice));
+    }
+    h.resize(ns);
+    HIPCHK(hipMemcpy(h.data(), c->d_src, sizeof(float4) * ns, hipMemcpyDeviceToHost));
+    std::vector<float4> caller(ns);
+    for (size_t i = 0; i < ns; ++i) caller[c->perm[i]] = make_float4(h[i].x, h[i].y, h[i].z, 0.f);
+    BvhDevice tree;
+    float4* d_caller = nullptr;  // the source in caller order, then its normals in caller order behind it
+    auto done = [&](int rc) { bvh_free(&tree); (void)hipFree(d_caller); return rc; };
+    hipError_t e = bvh_upload(bvh_build_host(caller.data(), ns), &tree);
+    if (e == hipSuccess) e = hipMalloc(&d_caller, sizeof(float4) * 2 * ns);
+    if (e == hipSuccess) e = hipMemcpy(d_caller, caller.data(), sizeof(float4) * ns, hipMemcpyHostToDevice);
+    c->src_normals_set = false;
+    if (e == hipSuccess) {
+        launch_target_knn(tree.view(), d_caller, (int)ns, k, nullptr, nullptr, d_caller + ns, st);
+        launch_slot_order(d_caller + ns, c->d_orig_of_slot, (int)ns, c->d_src_normals, st);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) { set_error(std::string("fgoicp_ctx_set_source_normals: ") + hipGetErrorString(e)); return done(e == hipErrorOutOfMemory ? FGOICP_ERR_OOM : FGOICP_ERR_HIP); }
+    c->src_normals_set = true;
+    return done(FGOICP_OK);
+}
+int ctx_source_normals(fgoicp_ctx* c, float* out) {
+    if (!c->src_normals_set) { set_error("fgoicp_source_normals: the source normals are not set (fgoicp_ctx_set_source_normals)"); return FGOICP_ERR_INVALID_ARG; }
+    HIPCHK(hipSetDevice(c->device));
+    std::vector<float4> h(c->ns);
+    HIPCHK(hipStreamSynchronize(c->lanes[0].stream));
+    HIPCHK(hipMemcpy(h.data(), c->d_src_normals, sizeof(float4) * c->ns, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < c->ns; ++i) {
+        float* o = out + 3 * (size_t)c->perm[i];
+        o[0] = h[i].x; o[1] = h[i].y; o[2] = h[i].z;
+    }
     return FGOICP_OK;
 }
 
@@ -1736,7 +1834,7 @@ void fgoicp_ctx_destroy(fgoicp_ctx* c) {
     (void)hipFree(c->d_span_cen);
     (void)hipFree(c->d_orig_of_slot);
     (void)hipFree(c->align.base);
-    (void)hipFree(c->d_normals); (void)hipFree(c->d_plane_rows); (void)hipFree(c->d_plane_out);
+    (void)hipFree(c->d_normals); (void)hipFree(c->d_plane_rows); (void)hipFree(c->d_plane_out); (void)hipFree(c->d_src_normals);
     for (int k = 0; k < 2; ++k) {
         fgoicp_ctx::TickSlot& sl = c->slots[k];
         if (sl.done) (void)hipEventDestroy(sl.done);
@@ -2021,6 +2119,53 @@ int fgoicp_icp_plane(fgoicp_ctx* c, const float* R0_9, const float* t0_3, size_t
     fgoicp_plane_result_t full;
     const int rc = ctx_icp_plane(c, R0_9, t0_3, max_iter, conv_thr, max_dist2, &full);
     return rc ? rc : plane_out(full, out, "fgoicp_icp_plane", "fgoicp_plane_result_t");
+}
+int fgoicp_ctx_set_source_normals(fgoicp_ctx* c, const float* normals_ns3_or_NULL, int k) {
+    if (!c) { set_error("fgoicp_ctx_set_source_normals: the context must not be null"); return FGOICP_ERR_INVALID_ARG; }
+    return fgoicp::abi_guard("fgoicp_ctx_set_source_normals", [&] { return ctx_set_source_normals(c, normals_ns3_or_NULL, k); });
+}
+int fgoicp_source_normals(fgoicp_ctx* c, float* out_ns3) {
+    if (!c || !out_ns3) { set_error("fgoicp_source_normals: the context and the output must not be null"); return FGOICP_ERR_INVALID_ARG; }
+    return fgoicp::abi_guard("fgoicp_source_normals", [&] { return ctx_source_normals(c, out_ns3); });
+}
+// what fgoicp_gicp_moments and fgoicp_icp_gicp refuse before any device work, behind the null and struct_size checks
+static int gicp_refusals(const fgoicp_ctx* c, float max_dist2, double epsilon, const char* where) {
+    const std::string w(where);
+    if (!(max_dist2 >= 0.0f)) { set_error(w + ": max_dist2 must be >= 0 (+inf: no threshold)"); return FGOICP_ERR_INVALID_ARG; }
+    if (!gicp_epsilon_ok(epsilon)) { set_error(w + ": epsilon must be finite and lie in (0, 1]"); return FGOICP_ERR_INVALID_ARG; }
+    if (!c->normals_set) { set_error(w + ": the target normals are not set: call fgoicp_ctx_set_target_normals first"); return FGOICP_ERR_INVALID_ARG; }
+    if (!c->src_normals_set) { set_error(w + ": the source normals are not set: call fgoicp_ctx_set_source_normals first"); return FGOICP_ERR_INVALID_ARG; }
+    return FGOICP_OK;
+}
+int fgoicp_gicp_moments(fgoicp_ctx* c, const float* R9, const float* t3, float max_dist2, double epsilon, fgoicp_plane_moments_t* out) {
+    if (!c || !R9 || !t3) { set_error("fgoicp_gicp_moments: the context, R and t must not be null"); return FGOICP_ERR_INVALID_ARG; }
+    if (!plane_size_ok(out)) { set_error("fgoicp_gicp_moments: out must not be null and out->struct_size = sizeof(fgoicp_plane_moments_t)"); return FGOICP_ERR_INVALID_ARG; }
+    return fgoicp::abi_guard("fgoicp_gicp_moments", [&] {
+        int rc = gicp_refusals(c, max_dist2, epsilon, "fgoicp_gicp_moments");
+        if (rc) return rc;
+        PlaneMoments m;
+        rc = ctx_gicp_moments(c, R9, t3, max_dist2, epsilon, &m);
+        if (rc) return rc;
+        fgoicp_plane_moments_t full;
+        std::memset(&full, 0, sizeof(full));  // the padding too: two results of the same inputs are the same bytes
+        full.struct_size = (uint32_t)sizeof(full);
+        full.points = c->ns;
+        full.correspondences = m.n;
+        std::memcpy(full.m, m.m, sizeof(full.m));
+        full.max_dist2 = max_dist2;
+        return plane_out(full, out, "fgoicp_gicp_moments", "fgoicp_plane_moments_t");
+    });
+}
+int fgoicp_icp_gicp(fgoicp_ctx* c, const float* R0_9, const float* t0_3, size_t max_iter, float conv_thr, float max_dist2, double epsilon, fgoicp_plane_result_t* out) {
+    if (!c || !R0_9 || !t0_3) { set_error("fgoicp_icp_gicp: the context, R0 and t0 must not be null"); return FGOICP_ERR_INVALID_ARG; }
+    if (!plane_size_ok(out)) { set_error("fgoicp_icp_gicp: out must not be null and out->struct_size = sizeof(fgoicp_plane_result_t)"); return FGOICP_ERR_INVALID_ARG; }
+    return fgoicp::abi_guard("fgoicp_icp_gicp", [&] {
+        int rc = gicp_refusals(c, max_dist2, epsilon, "fgoicp_icp_gicp");
+        if (rc) return rc;
+        fgoicp_plane_result_t full;
+        rc = ctx_icp_gicp(c, R0_9, t0_3, max_iter, conv_thr, max_dist2, epsilon, &full);
+        return rc ? rc : plane_out(full, out, "fgoicp_icp_gicp", "fgoicp_plane_result_t");
+    });
 }
 
 int fgoicp_ctx_set_inliers(fgoicp_ctx* c, size_t k) {

@@ -15,6 +15,7 @@
 #include "../host/abi_guard.hpp"
 #include "../host/information.hpp"
 #include "../host/plane.hpp"
+#include "../host/gicp.hpp"
 #include "bvh.hpp"
 #include "kernels.hpp"
 
@@ -132,6 +133,9 @@ struct fgoicp_ctx {
     bool normals_set = false;
     fgoicp::PlaneRow* d_plane_rows = nullptr;
     unsigned long long* d_plane_out = nullptr;   // {count, the bits of 28 sums} (launch_plane_moments)
+    // source normals of the Generalized-ICP refinement (ctx_set_source_normals): allocated by the first call, 16 bytes per source point
+    float4* d_src_normals = nullptr;         // ns x {n.x, n.y, n.z, 0}, DEVICE SLOT order (perm); the zero vector: no normal
+    bool src_normals_set = false;
 
     // exact-NN / ICP scratch, one set per lane: ICP runs on different lanes may be in flight together (ctx_icp_batch).  Lane 0 is
     // the lane of fgoicp_sse / fgoicp_icp / fgoicp_procrustes and queues on the context's main stream.
@@ -215,6 +219,14 @@ int ctx_target_knn(fgoicp_ctx* c, int k, uint32_t* idx, float* d2);
 int ctx_plane_moments(fgoicp_ctx* c, const float* R9, const float* t3, float max_dist2, PlaneMoments* m, float* sse_out = nullptr);
 // fgoicp_icp_plane; `full` is filled whole (scaling_factor = 1)
 int ctx_icp_plane(fgoicp_ctx* c, const float* R0, const float* t0, size_t max_iter, float thr, float max_dist2, fgoicp_plane_result_t* full);
+// EXTENSION: source normals and the Generalized-ICP refinement (include/fgoicp_amd.h).  normals = nullptr: estimated from the k nearest
+// SOURCE points through a throw-away tree over the source.
+int ctx_set_source_normals(fgoicp_ctx* c, const float* normals, int k);
+int ctx_source_normals(fgoicp_ctx* c, float* out_ns3);
+// ctx_plane_moments with launch_gicp_moments in place of launch_plane_moments; epsilon checked (gicp_epsilon_ok), both normal sets set
+int ctx_gicp_moments(fgoicp_ctx* c, const float* R9, const float* t3, float max_dist2, double epsilon, PlaneMoments* m, float* sse_out = nullptr);
+// fgoicp_icp_gicp: ctx_icp_plane's loop over ctx_gicp_moments; full->plane_rmse = sqrt(sum d^T M d / N)
+int ctx_icp_gicp(fgoicp_ctx* c, const float* R0, const float* t0, size_t max_iter, float thr, float max_dist2, double epsilon, fgoicp_plane_result_t* full);
 // a summary handed to a caller: no byte beyond the struct_size the caller set is written (0, or less than the size field itself: refused)
 inline int alignment_summary_out(const fgoicp_alignment_summary& full, fgoicp_alignment_summary* out, const char* where) {
     if (!out) return FGOICP_OK;

@@ -18,6 +18,7 @@
 #include "slab.hpp"
 #include "bvh.hpp"
 #include "../host/math3.hpp"
+#include "../host/gicp.hpp"
 
 namespace fgoicp {
 namespace {
@@ -2868,6 +2869,90 @@ void launch_plane_moments(const float4* moved, const uint32_t* orig_of_slot, con
     const int nb = (n + kBlock - 1) / kBlock;
     hipLaunchKernelGGL(plane_moments_kernel, dim3(nb), dim3(kBlock), 0, s, moved, orig_of_slot, inlier, d2, corr, tgt, normals, n, nt, max_d2, rows);
     hipLaunchKernelGGL(plane_moments_fold_kernel, dim3(1), dim3(1024), 0, s, rows, nb, out29);
+}
+
+
+// ---------------------------------------------------------------------------------------------
+// The Generalized-ICP normal equations (fgoicp_gicp_moments) over the same arrays as plane_moments_kernel, plus the
+// SOURCE normals in device slot order (a coalesced read like `moved`).  One thread per device slot i; COUNTED are plane_moments_kernel's
+// caller indices whose own source normal is non-zero too.  The per-pair arithmetic — m = R n_p, S = 2 I - (1 - eps)(n_q n_q^T + m m^T),
+// M = adj(S) / det(S), the 28 terms of J^T M J, J^T M d, d^T M d with J = [ -[x]x | I ] — is gicp_pair_terms (host/gicp.hpp), the text
+// fgoicp_gicp_terms runs on the host.  The reduction is plane_moments_kernel's, addition for addition, and the fold is
+// plane_moments_fold_kernel itself.  No atomics.  Every term is even in n_q and in n_p.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void gicp_moments_kernel(const float4* __restrict__ moved, const uint32_t* __restrict__ orig_of_slot,
+                                                              const unsigned char* __restrict__ inlier, const float* __restrict__ d2,
+                                                              const uint32_t* __restrict__ corr, const float4* __restrict__ tgt,
+                                                              const float4* __restrict__ normals, const float4* __restrict__ src_normals, Rt rt, double eps, int n,
+                                                              int nt, float max_d2, PlaneRow* __restrict__ rows) {
+    __shared__ double s_v[kBlock / 64][kPlaneTerms];
+    __shared__ unsigned s_cnt[kBlock / 64];
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    double v[kPlaneTerms];
+#pragma unroll
+    for (int k = 0; k < kPlaneTerms; ++k) v[k] = 0.0;
+    unsigned cnt = 0u;
+    if (i < n) {
+        const uint32_t o = orig_of_slot[i];
+        const float4 x = moved[i], np = src_normals[i];
+        if (o < (uint32_t)n && (np.x != 0.0f || np.y != 0.0f || np.z != 0.0f)) {
+            const uint32_t j = corr[o];
+            if (inlier[o] != 0 && d2[o] <= max_d2 && j < (uint32_t)nt) {
+                const float4 nn = normals[j];
+                if (nn.x != 0.0f || nn.y != 0.0f || nn.z != 0.0f) {
+                    const float4 q = tgt[j];
+                    const double X[3] = {(double)x.x, (double)x.y, (double)x.z}, Q[3] = {(double)q.x, (double)q.y, (double)q.z};
+                    const double NQ[3] = {(double)nn.x, (double)nn.y, (double)nn.z}, NP[3] = {(double)np.x, (double)np.y, (double)np.z};
+                    gicp_pair_terms(X, Q, NQ, NP, rt.R, eps, nullptr, v);
+                    cnt = 1u;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
+#pragma unroll
+    for (int k = 0; k < kPlaneTerms; ++k) v[k] = wave_xor_sum(v[k]);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+        s_cnt[wave] = cnt;
+#pragma unroll
+        for (int k = 0; k < kPlaneTerms; ++k) s_v[wave][k] = v[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < kPlaneTerms) {
+        double r = s_v[0][threadIdx.x];
+#pragma unroll
+        for (int w = 1; w < kBlock / 64; ++w) r += s_v[w][threadIdx.x];
+        rows[blockIdx.x].v[threadIdx.x] = r;
+    }
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int w = 1; w < kBlock / 64; ++w) cnt += s_cnt[w];
+        rows[blockIdx.x].count = cnt;
+        rows[blockIdx.x].pad = 0u;
+    }
+}
+
+void launch_gicp_moments(const float4* moved, const uint32_t* orig_of_slot, const unsigned char* inlier, const float* d2, const uint32_t* corr, const float4* tgt,
+                         const float4* normals, const float4* src_normals, const float* R9, double eps, int n, int nt, float max_d2, PlaneRow* rows,
+                         unsigned long long* out29, hipStream_t s) {
+    const int nb = (n + kBlock - 1) / kBlock;
+    hipLaunchKernelGGL(gicp_moments_kernel, dim3(nb), dim3(kBlock), 0, s, moved, orig_of_slot, inlier, d2, corr, tgt, normals, src_normals, make_rt(R9, nullptr), eps, n, nt,
+                       max_d2, rows);
+    hipLaunchKernelGGL(plane_moments_fold_kernel, dim3(1), dim3(1024), 0, s, rows, nb, out29);
+}
+
+// out[i] = in[orig_of_slot[i]]: per-point data from caller order into device slot order (the source normals: target_knn_kernel writes them
+// at the caller index)
+__global__ __launch_bounds__(kBlock) void slot_order_kernel(const float4* __restrict__ in, const uint32_t* __restrict__ orig_of_slot, int n, float4* __restrict__ out) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t o = orig_of_slot[i];
+    out[i] = o < (uint32_t)n ? in[o] : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+void launch_slot_order(const float4* in, const uint32_t* orig_of_slot, int n, float4* out, hipStream_t s) {
+    hipLaunchKernelGGL(slot_order_kernel, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, in, orig_of_slot, n, out);
 }
 
 }  // namespace fgoicp

@@ -154,6 +154,15 @@ struct PlaneRow {
 };
 void launch_plane_moments(const float4* moved, const uint32_t* orig_of_slot, const unsigned char* inlier, const float* d2, const uint32_t* corr, const float4* tgt,
                           const float4* normals, int n, int nt, float max_d2, PlaneRow* rows, unsigned long long* out29, hipStream_t s);
+// The Generalized-ICP normal equations (fgoicp_gicp_moments; kernels.hip gicp_moments_kernel, then plane_moments_fold_kernel): as
+// launch_plane_moments, with src_normals = the source normals in DEVICE SLOT order (n x {n.x, n.y, n.z, 0}; a zero vector takes its point
+// out of the counted set), R9 the rotation of the pose `moved` was formed with (glm order) and eps in (0, 1].  out29 = {count, the bits of
+// 28 doubles: the upper triangle of sum J^T M J row by row (21), sum J^T M d (6), sum d^T M d} (host/gicp.hpp).  Fixed order of every addition.
+void launch_gicp_moments(const float4* moved, const uint32_t* orig_of_slot, const unsigned char* inlier, const float* d2, const uint32_t* corr, const float4* tgt,
+                         const float4* normals, const float4* src_normals, const float* R9, double eps, int n, int nt, float max_d2, PlaneRow* rows,
+                         unsigned long long* out29, hipStream_t s);
+// out[i] = in[orig_of_slot[i]], i < n: caller order -> device slot order
+void launch_slot_order(const float4* in, const uint32_t* orig_of_slot, int n, float4* out, hipStream_t s);
 // The bounds of many registrations in one launch (fgoicp_batch, bounds_fused.hpp): a view per pair of the batch, an evaluation per output
 // row, work items {evaluation, chunk}.  Every row is the bits its pair's own context computes with thresholds off.
 struct FusedPairView {

@@ -308,6 +308,41 @@ int fgoicp_solver_refine_plane(fgoicp_solver* s, int k, size_t max_iter, float c
     });
 }
 
+int fgoicp_solver_refine_gicp(fgoicp_solver* s, int k, size_t max_iter, float conv_thr, float max_distance, double epsilon, fgoicp_plane_result_t* out) {
+    if (!s) { set_error("fgoicp_solver_refine_gicp: the solver must not be null"); return FGOICP_ERR_INVALID_ARG; }
+    if (!s->ran) { set_error("fgoicp_solver_refine_gicp: fgoicp_solver_run has not succeeded yet: there is no best transform"); return FGOICP_ERR_INVALID_ARG; }
+    if (!plane_size_ok(out)) { set_error("fgoicp_solver_refine_gicp: out must not be null and out->struct_size = sizeof(fgoicp_plane_result_t)"); return FGOICP_ERR_INVALID_ARG; }
+    if (!(max_distance >= 0.0f)) { set_error("fgoicp_solver_refine_gicp: max_distance must be >= 0 (+inf: no threshold)"); return FGOICP_ERR_INVALID_ARG; }
+    if (!gicp_epsilon_ok(epsilon)) { set_error("fgoicp_solver_refine_gicp: epsilon must be finite and lie in (0, 1]"); return FGOICP_ERR_INVALID_ARG; }
+    return fgoicp::abi_guard("fgoicp_solver_refine_gicp", [&] {
+        if (!s->ctx->normals_set) {  // normals are invariant under the solver's centring and uniform scale
+            const int rc = ctx_set_target_normals(s->ctx, nullptr, k);
+            if (rc) return rc;
+        }
+        if (!s->ctx->src_normals_set) {
+            const int rc = ctx_set_source_normals(s->ctx, nullptr, k);
+            if (rc) return rc;
+        }
+        Mat3f R;
+        Vec3f t;
+        s->driver->best_transform(R, t);  // the normalised frame the search ran in, as fgoicp_solver_refine_plane
+        const float t3[3] = {t.x, t.y, t.z};
+        fgoicp_plane_result_t full;
+        const int rc = ctx_icp_gicp(s->ctx, R.m, t3, max_iter, conv_thr, information_max_dist2(max_distance, s->scaling_factor), epsilon, &full);
+        if (rc) return rc;
+        const Mat3f Rr = Mat3f::from(full.R);
+        const Vec3f ts{full.t[0], full.t[1], full.t[2]};
+        const Vec3f tr = ts / s->scaling_factor + Rr * s->offset_pcs - s->offset_pct;  // restore_translation, fgoicp.hpp:87-90
+        full.t[0] = tr.x; full.t[1] = tr.y; full.t[2] = tr.z;
+        full.scaling_factor = s->scaling_factor;
+        return plane_out(full, out, "fgoicp_solver_refine_gicp", "fgoicp_plane_result_t");
+    });
+}
+
+int fgoicp_gicp_terms(const float* x3, const float* q3, const float* nq3, const float* np3, const float* R9, double epsilon, double* M6_or_NULL, double* v28_or_NULL) {
+    return gicp_terms_entry(x3, q3, nq3, np3, R9, epsilon, M6_or_NULL, v28_or_NULL);
+}
+
 int fgoicp_plane_step_from_moments(uint64_t n, const double* m28, double* xi6, int* rank) {
     if (!m28 || !xi6 || !rank) { set_error("fgoicp_plane_step_from_moments: m28, xi6 and rank must not be null"); return FGOICP_ERR_INVALID_ARG; }
     if (n == 0) { set_error("fgoicp_plane_step_from_moments: n = 0: nothing was counted, there is no step"); return FGOICP_ERR_INVALID_ARG; }

@@ -6,7 +6,7 @@ import numpy as np
 
 from . import _lib
 from .nodes import from_glm
-from .registration import PlaneRefinement, Registration, _alignment, _cloud, _fp, _information
+from .registration import GicpRefinement, PlaneRefinement, Registration, _alignment, _cloud, _fp, _information
 
 
 class FastGoICP:
@@ -73,6 +73,15 @@ class FastGoICP:
         raw = _lib.PlaneResult()
         _lib.check(self._lib.fgoicp_solver_refine_plane(self._h, int(k), int(max_iter), float(conv_thr), d, C.byref(raw)), "fgoicp_solver_refine_plane")
         return PlaneRefinement(raw)
+
+    def refine_gicp(self, k=16, max_iter=30, conv_thr=1e-6, max_distance=None, epsilon=1e-3):
+        """EXTENSION (fgoicp_solver_refine_gicp): Generalized ICP from the best transform, after run() -> GicpRefinement (a
+        PlaneRefinement) with R and t in the callers' frame.  Whichever normal set the registration lacks is estimated from k neighbours;
+        max_distance as refine_plane takes it.  run() and the best transform are untouched."""
+        d = float("inf") if max_distance is None else float(max_distance)
+        raw = _lib.PlaneResult()
+        _lib.check(self._lib.fgoicp_solver_refine_gicp(self._h, int(k), int(max_iter), float(conv_thr), d, float(epsilon), C.byref(raw)), "fgoicp_solver_refine_gicp")
+        return GicpRefinement(raw)
 
     def _transform(self, fn, name):
         R = np.empty(9, np.float32); t = np.empty(3, np.float32)

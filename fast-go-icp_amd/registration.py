@@ -226,6 +226,28 @@ def plane_apply_step(R, t, xi):
     return from_glm(Ro), to
 
 
+class GicpRefinement(PlaneRefinement):
+    """EXTENSION (fgoicp_icp_gicp / fgoicp_solver_refine_gicp): a PlaneRefinement whose residual is the plane-to-plane one — gicp_rmse =
+    sqrt(sum d^T M d / N) at the returned pose in the callers' units (the value the library leaves in plane_rmse)."""
+
+    def __init__(self, raw):
+        super().__init__(raw)
+        self.gicp_rmse_scaled, self.gicp_rmse = self.plane_rmse_scaled, self.plane_rmse
+
+
+def gicp_terms(x, q, nq, np_, R, epsilon=1e-3):
+    """fgoicp_gicp_terms (host only): one pair -> (M (3, 3) float64, v (28,) float64) — M = (C_q + R C_p R^T)^-1 of the regularised
+    covariances, v the pair's terms of J^T M J (upper triangle row by row), J^T M d and d^T M d."""
+    a = [np.ascontiguousarray(v, np.float32).reshape(3) for v in (x, q, nq, np_)]
+    Rg = to_glm(R)
+    M6 = np.empty(6, np.float64); v = np.empty(28, np.float64)
+    dp = lambda z: z.ctypes.data_as(C.POINTER(C.c_double))
+    _lib.check(_lib.load().fgoicp_gicp_terms(_fp(a[0]), _fp(a[1]), _fp(a[2]), _fp(a[3]), _fp(Rg), float(epsilon), dp(M6), dp(v)), "fgoicp_gicp_terms")
+    M = np.empty((3, 3), np.float64)
+    M[np.triu_indices(3)] = M6
+    return np.triu(M) + np.triu(M, 1).T, v
+
+
 class Registration:
     """icp::Registration (fgoicp/registration.hpp:49-98) + its NearestNeighborLUT member."""
 
@@ -369,6 +391,40 @@ class Registration:
         raw = _lib.PlaneResult()
         _lib.check(self._lib.fgoicp_icp_plane(self._h, _fp(Rg), _fp(tt), int(max_iter), float(conv_thr), float(max_dist2), C.byref(raw)), "fgoicp_icp_plane")
         return PlaneRefinement(raw)
+
+    def set_source_normals(self, normals=None, k=16):
+        """EXTENSION (fgoicp_ctx_set_source_normals): normals (ns, 3) are normalised and uploaded; None: estimated on the device from
+        every source point's k nearest source points (4 <= k <= 32).  The sign of an estimated normal is arbitrary (nothing depends on it)."""
+        if normals is None:
+            _lib.check(self._lib.fgoicp_ctx_set_source_normals(self._h, None, int(k)), "fgoicp_ctx_set_source_normals")
+            return
+        n = _cloud(normals)
+        if len(n) != self.ns:
+            raise ValueError("normals must be (ns, 3)")
+        _lib.check(self._lib.fgoicp_ctx_set_source_normals(self._h, _fp(n), int(k)), "fgoicp_ctx_set_source_normals")
+
+    def source_normals(self):
+        """fgoicp_source_normals: (ns, 3) float32 unit normals in the caller's order (zero rows: degenerate neighbourhoods)."""
+        out = np.empty((self.ns, 3), np.float32)
+        _lib.check(self._lib.fgoicp_source_normals(self._h, _fp(out)), "fgoicp_source_normals")
+        return out
+
+    def gicp_moments(self, R, t, max_dist2=np.inf, epsilon=1e-3):
+        """EXTENSION (fgoicp_gicp_moments): the Generalized-ICP normal equations of R*pcs + t as a PlaneMomentsResult — JtJ = sum J^T M J,
+        Jtr = sum J^T M d, sum_r2 = sum d^T M d, with J = [-[x]x | I] and M the inverse of the summed regularised covariances."""
+        Rg = to_glm(R)
+        tt = np.ascontiguousarray(t, dtype=np.float32).reshape(3)
+        raw = _lib.PlaneMoments()
+        _lib.check(self._lib.fgoicp_gicp_moments(self._h, _fp(Rg), _fp(tt), float(max_dist2), float(epsilon), C.byref(raw)), "fgoicp_gicp_moments")
+        return PlaneMomentsResult(raw)
+
+    def icp_gicp(self, R, t, max_iter=30, conv_thr=1e-6, max_dist2=np.inf, epsilon=1e-3):
+        """EXTENSION (fgoicp_icp_gicp): Generalized ICP from (R, t) -> GicpRefinement.  max_iter = 0 evaluates the start."""
+        Rg = to_glm(R)
+        tt = np.ascontiguousarray(t, dtype=np.float32).reshape(3)
+        raw = _lib.PlaneResult()
+        _lib.check(self._lib.fgoicp_icp_gicp(self._h, _fp(Rg), _fp(tt), int(max_iter), float(conv_thr), float(max_dist2), float(epsilon), C.byref(raw)), "fgoicp_icp_gicp")
+        return GicpRefinement(raw)
 
     def compute_bounds(self, R, rot_span, tnodes, fix_rot):
         Rg = to_glm(R)

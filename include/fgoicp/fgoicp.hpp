@@ -67,6 +67,14 @@ public:
         check_status(fgoicp_solver_refine_plane(s_, k, max_iter, conv_thr, max_distance, &p.result), "fgoicp_solver_refine_plane");
         return p;
     }
+    // EXTENSION: Generalized-ICP refinement from the best transform, after run() (fgoicp_solver_refine_gicp): as refine_plane, with the
+    // normals of both clouds (whichever set the context lacks is estimated from k neighbours); plane_rmse() is the plane-to-plane residual.
+    PlaneRefinement refine_gicp(int k = 16, size_t max_iter = 30, float conv_thr = 1e-6f, float max_distance = INFINITY, double epsilon = 1e-3) const {
+        PlaneRefinement p;
+        p.result.struct_size = sizeof(p.result);
+        check_status(fgoicp_solver_refine_gicp(s_, k, max_iter, conv_thr, max_distance, epsilon, &p.result), "fgoicp_solver_refine_gicp");
+        return p;
+    }
     fgoicp_run_stats stats() const { fgoicp_run_stats st{}; check_status(fgoicp_solver_stats(s_, &st), "fgoicp_solver_stats"); return st; }
     fgoicp_solver* handle() const { return s_; }
     // the reference's own lines while the search runs (fgoicp.cpp:15-17 Info, :85-87 Debug), from the driver's log events

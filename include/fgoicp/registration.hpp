@@ -157,6 +157,28 @@ public:
         check_status(fgoicp_icp_plane(ctx_, R.data(), &t.x, max_iter, conv_thr, max_dist2, &p.result), "fgoicp_icp_plane");
         return p;
     }
+    // EXTENSION: source normals for the Generalized-ICP refinement — given, or estimated from every source point's k nearest source points
+    void set_source_normals(const PointCloud& normals) { check_status(fgoicp_ctx_set_source_normals(ctx_, &normals.data()->x, 0), "fgoicp_ctx_set_source_normals"); }
+    void set_source_normals(int k = 16) { check_status(fgoicp_ctx_set_source_normals(ctx_, nullptr, k), "fgoicp_ctx_set_source_normals"); }
+    PointCloud source_normals() const {
+        PointCloud n(ns);
+        check_status(fgoicp_source_normals(ctx_, &n.data()->x), "fgoicp_source_normals");
+        return n;
+    }
+    // EXTENSION: the Generalized-ICP normal equations of R*pcs + t (fgoicp_gicp_moments) and the loop from (R, t) (fgoicp_icp_gicp); the
+    // result's plane_rmse() is the root mean squared plane-to-plane residual sqrt(sum d^T M d / N)
+    fgoicp_plane_moments_t gicp_moments(mat3 R, vec3 t, float max_dist2 = INFINITY, double epsilon = 1e-3) const {
+        fgoicp_plane_moments_t m{};
+        m.struct_size = sizeof(m);
+        check_status(fgoicp_gicp_moments(ctx_, R.data(), &t.x, max_dist2, epsilon, &m), "fgoicp_gicp_moments");
+        return m;
+    }
+    PlaneRefinement icp_gicp(mat3 R, vec3 t, size_t max_iter = 30, float conv_thr = 1e-6f, float max_dist2 = INFINITY, double epsilon = 1e-3) const {
+        PlaneRefinement p;
+        p.result.struct_size = sizeof(p.result);
+        check_status(fgoicp_icp_gicp(ctx_, R.data(), &t.x, max_iter, conv_thr, max_dist2, epsilon, &p.result), "fgoicp_icp_gicp");
+        return p;
+    }
 
     fgoicp_ctx* handle() const { return ctx_; }
     const size_t nt, ns;

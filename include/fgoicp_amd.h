@@ -252,7 +252,8 @@ typedef struct fgoicp_plane_result_t {
     int      iterations;              /* steps taken */
     int      rank;                    /* of the last solve (6: well posed; 0 when max_iter = 0 or nothing was counted) */
     uint64_t correspondences;         /* counted at the returned pose */
-    double   plane_rmse;              /* sqrt(sum r^2 / N) at the returned pose, context frame (0 when N = 0); / scaling_factor: callers' units */
+    double   plane_rmse;              /* sqrt(sum r^2 / N) at the returned pose, context frame (0 when N = 0); / scaling_factor: callers' units
+                                       * (fgoicp_icp_gicp, fgoicp_solver_refine_gicp: sqrt(sum d^T M d / N)) */
     float    sse;                     /* == fgoicp_sse(ctx, R, t) at the returned pose, bit for bit (context frame) */
     float    scaling_factor;          /* 1 for a bare context; the solver's scale otherwise */
 } fgoicp_plane_result_t;
@@ -275,6 +276,46 @@ int fgoicp_plane_apply_step(const float* R9, const float* t3, const double* xi6,
  * Refused when the normals are not set.  Leaves the context as it found it: a later fgoicp_icp, fgoicp_sse or solver run returns the
  * bits it returns without this call. */
 int fgoicp_icp_plane(fgoicp_ctx* ctx, const float* R0_9, const float* t0_3, size_t max_iter, float conv_thr, float max_dist2, fgoicp_plane_result_t* out);
+
+/*
+ * EXTENSION — Generalized-ICP refinement with source normals (no reference counterpart; Segal et al., "Generalized-ICP": the plane-to-plane
+ * error, for two clouds that are both noisy samples of one surface).
+ *
+ * Regularised covariances.  GICP replaces the eigenvalues of a neighbourhood covariance by (1, 1, epsilon); with n the unit direction of
+ * least variance that is C = I - (1 - epsilon) n n^T, so a normal per point of BOTH clouds is all the state.  epsilon must be finite and lie
+ * in (0, 1] (1e-3 is the usual choice); anything else is refused.
+ *
+ * Source normals follow the rule of the target's: fgoicp_ctx_set_source_normals with a pointer takes ns triples in caller order, normalised
+ * on upload, a zero or non-finite one refused with its index before any device work (the stored normals stay), k ignored.  With NULL they
+ * are estimated from every source point's k nearest SOURCE points, itself included (4 <= k <= 32, k <= ns; neighbours by (bits of the fp32
+ * squared distance, caller index); covariance and eigenvector in fp64; sign as it falls; a neighbourhood without extent gets the zero
+ * vector), in the frame of the source as the context holds it, through a search tree over the source that the call builds and frees.  A
+ * FGOICP_FLAG_BRUTE_FORCE_NN context is refused for estimation, as for the target.  16 bytes per source point, allocated by the first
+ * call; a context that never asks allocates nothing.  fgoicp_source_normals reads them back (ns triples, caller order; refused before
+ * they are set).
+ *
+ * The normal equations.  COUNTED at (R, t) are the correspondences fgoicp_plane_moments counts whose own source normal is non-zero too.
+ * Per counted point, in fp64 from the fp32 values: x = R p + t (as the report's scan forms it), q the target point and n_q its normal,
+ * m = R n_p with n_p the source normal, S = 2 I - (1 - epsilon)(n_q n_q^T + m m^T), M = adj(S) / det(S) (S >= 2 epsilon I), d = x - q,
+ * J = [ -[x]x | I ] (3 x 6, twist order wx wy wz vx vy vz).  m[28] = the upper triangle of sum J^T M J row by row (21), sum J^T M d (6),
+ * sum d^T M d (1): the layout of fgoicp_plane_moments_t, so fgoicp_plane_step_from_moments and fgoicp_plane_apply_step serve unchanged
+ * (with M = n n^T the terms are the point-to-plane ones).  Every term is even in n_q and in n_p; the sums are added in
+ * fgoicp_plane_moments' fixed order (two calls return the same bytes).  Context frame.
+ */
+int fgoicp_ctx_set_source_normals(fgoicp_ctx* ctx, const float* normals_ns3_or_NULL, int k);
+int fgoicp_source_normals(fgoicp_ctx* ctx, float* out_ns3);
+/* One evaluation at a fixed pose, as fgoicp_plane_moments.  Refused unless both normal sets are set (the message names the missing
+ * setter), for a NaN or negative max_dist2 and for an epsilon outside (0, 1] — all before any device work. */
+int fgoicp_gicp_moments(fgoicp_ctx* ctx, const float* R9, const float* t3, float max_dist2, double epsilon, fgoicp_plane_moments_t* out);
+/* fgoicp_icp_plane's loop, term for term, over fgoicp_gicp_moments.  HERE out->plane_rmse HOLDS sqrt(sum d^T M d / N) at the returned
+ * pose — the root mean squared plane-to-plane (Mahalanobis) residual, context frame — not the point-to-plane one.  Leaves the context
+ * as it found it. */
+int fgoicp_icp_gicp(fgoicp_ctx* ctx, const float* R0_9, const float* t0_3, size_t max_iter, float conv_thr, float max_dist2, double epsilon,
+                    fgoicp_plane_result_t* out);
+/* Host only, no device needed: the arithmetic of ONE pair, the text the device kernel runs.  x3, q3, nq3, np3: the moved source point, the
+ * target point, its normal, the source point's normal (source frame); R9 in glm order.  M6 (optional): M as xx xy xz yy yz zz; v28
+ * (optional): the pair's 28 terms.  Refuses null inputs and an epsilon outside (0, 1]. */
+int fgoicp_gicp_terms(const float* x3, const float* q3, const float* nq3, const float* np3, const float* R9, double epsilon, double* M6_or_NULL, double* v28_or_NULL);
 
 /* Replaces IterativeClosestPoint3D(reg, pct, pcs, max_iter, thr, R, t) + run()
  * (fgoicp/icp3d.hpp:30-35, icp3d.cu:55-108).  Returns the reference's Result_t {sse, R, t}
@@ -443,6 +484,11 @@ int fgoicp_solver_information(fgoicp_solver* s, float max_distance, fgoicp_infor
  * The solver's own best transform, best error and a later fgoicp_solver_run are untouched.  On a multi-GPU run every rank answers from
  * its own context. */
 int fgoicp_solver_refine_plane(fgoicp_solver* s, int k, size_t max_iter, float conv_thr, float max_distance, fgoicp_plane_result_t* out);
+/* EXTENSION: fgoicp_icp_gicp from the best transform the solver holds, after a successful fgoicp_solver_run — before that the call is
+ * refused (FGOICP_ERR_INVALID_ARG).  Whichever normal set the context lacks is estimated with k neighbours (normals are invariant under
+ * the solver's centring and uniform scale).  max_distance, R, t and scaling_factor as fgoicp_solver_refine_plane; plane_rmse holds
+ * sqrt(sum d^T M d / N) in the solver's frame.  The solver's own result is untouched. */
+int fgoicp_solver_refine_gicp(fgoicp_solver* s, int k, size_t max_iter, float conv_thr, float max_distance, double epsilon, fgoicp_plane_result_t* out);
 /* Pre-processing results (tests): offs6 = {offset_pcs, offset_pct}, bounds6 as in ctx_create. */
 int fgoicp_solver_preproc(const fgoicp_solver* s, float* offs6, float* scale, float* bounds6);
 /* Statistics of a raw cloud, host side, no device needed (TODO.md:7 of the reference: "compute point clouds' stats"): what the
