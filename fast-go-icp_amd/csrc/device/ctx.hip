@@ -422,45 +422,81 @@ static double fold_wave_sums(const double* w, int nwaves) {  // block_sum<1> of 
 }
 static bool icp_fused(const fgoicp_ctx* c) { return c->icp_fuse && !c->brute_force_nn && !c->inliers && c->ns <= 262144; }
 
+static bool trim_skips(const fgoicp_ctx* c) { return c->inliers && c->trim_skip; }
+
+// the caller index of every device slot, on the device: allocated by the first call that needs it (trimmed ICP, the alignment report, source normals)
+static int ensure_orig_of_slot(fgoicp_ctx* c) {
+    if (c->d_orig_of_slot) return FGOICP_OK;
+    HIPCHK(hipMalloc(&c->d_orig_of_slot, sizeof(uint32_t) * c->ns));
+    HIPCHK(hipMemcpy(c->d_orig_of_slot, c->perm.data(), sizeof(uint32_t) * c->ns, hipMemcpyHostToDevice));
+    return FGOICP_OK;
+}
+// the working cloud: a copy of the source moved by (R0, t0) — icp3d.cu:85
+static int work_begin_enqueue(fgoicp_ctx* c, fgoicp_ctx::IcpLane& L, const float* R0, const float* t0, hipStream_t st) {
+    HIPCHK(hipMemcpyAsync(L.d_work, c->d_src, sizeof(float4) * c->ns, hipMemcpyDeviceToDevice, st));
+    launch_transform_inplace(L.d_work, (int)c->ns, R0, t0, st);
+    return FGOICP_OK;
+}
+
+// Trimmed search: the LUT brackets of one query set's nearest distances (launch_nn_prep) and the cut among their upper ends
+// (launch_trim_select).  The exact scan that follows leaves out the queries whose lower end `lb` lies above the cut `sel`.
+struct TrimQueries {
+    const float4* pts;
+    const float *R9, *t3;  // the motion the scan applies to pts (null: none)
+    float *ub, *lb;
+    uint32_t *sel, *wide;
+};
+static TrimQueries trim_working(const fgoicp_ctx::IcpLane& L, uint32_t* wide) { return {L.d_work, nullptr, nullptr, L.d_nn_ub2, L.d_nn_lb2, L.d_sel + 4, wide}; }
+static TrimQueries trim_pristine(const fgoicp_ctx* c, const fgoicp_ctx::IcpLane& L, const float* R9, const float* t3) {  // the source under (R, t)
+    return {c->d_src, R9, t3, L.d_nn_ub, L.d_nn_lb, L.d_sel + 8, L.d_sel_wide};
+}
+static void trim_prep(const fgoicp_ctx* c, const TrimQueries& q, const uint32_t* seed_idx, hipStream_t st) {
+    launch_nn_prep(q.pts, (int)c->ns, c->d_lut, c->geom, q.R9, q.t3, q.R9 ? 1 : 0, c->d_tgt, (int)c->nt, seed_idx, c->tgt_box6, q.ub, q.lb, st);
+}
+static void trim_cut(const fgoicp_ctx* c, const TrimQueries& q, hipStream_t st) { launch_trim_select(q.ub, (int)c->ns, (int)c->inliers, nullptr, q.sel, q.wide, st); }
+static void trim_brackets(const fgoicp_ctx* c, const TrimQueries& q, const uint32_t* seed_idx, hipStream_t st) {
+    trim_prep(c, q, seed_idx, st);
+    trim_cut(c, q, st);
+}
+
 // float Registration::compute_sse_error(glm::mat3, glm::vec3) — registration.cu:62-86.  Enqueue only: the result lands in
-// pinned memory (sse_result) once `st` has drained.
-// `part`: 0 = everything, 1 = the search only, 2 = the sum only (the ICP loop interleaves the launches of its two streams: both long
-// scans first — a launch costs the submitting thread ~5 us, and whatever is enqueued last starts that much later).
-static int sse_enqueue(fgoicp_ctx* c, fgoicp_ctx::IcpLane& L, const float* R9, const float* t3, const uint32_t* seed_idx, hipStream_t st, int part = 0) {
+// pinned memory (sse_result) once `st` has drained.  Two halves, the search and the sum (the ICP loop interleaves the launches of its
+// two streams: both long scans first — a launch costs the submitting thread ~5 us, and whatever is enqueued last starts that much later).
+static int sse_search_enqueue(fgoicp_ctx* c, fgoicp_ctx::IcpLane& L, const float* R9, const float* t3, const uint32_t* seed_idx, bool fused, bool skip, hipStream_t st) {
     const int ns = (int)c->ns;
-    if (icp_fused(c)) {  // one launch: the scan leaves the wave-level sums of its minima in pinned memory, sse_result() folds them
-        if (part != 2) launch_nn_scan(c->d_src, ns, c->bvh_tgt.view(), c->d_lut, c->geom, R9, t3, 1, 0, c->d_tgt, (int)c->nt, seed_idx, nullptr, nullptr, L.d_min_bits, st,
-                                      nullptr, nullptr, nullptr, L.hd_wsse);
-        L.sse_on_host = true;
-        HIPCHK(hipGetLastError());
-        return FGOICP_OK;
-    }
-    L.sse_on_host = false;
-    if (part == 2) {
+    if (fused) {  // one launch: the scan leaves the wave-level sums of its minima in pinned memory, sse_result() folds them
+        launch_nn_scan(c->d_src, ns, c->bvh_tgt.view(), c->d_lut, c->geom, R9, t3, 1, 0, c->d_tgt, (int)c->nt, seed_idx, nullptr, nullptr, L.d_min_bits, st, nullptr, nullptr, nullptr,
+                       L.hd_wsse);
     } else if (c->brute_force_nn) {
         launch_fill_u32(L.d_min_bits, 0x501502F9u /* bits(1e10f) */, c->ns, st);
         launch_nn_min(c->d_src, ns, c->d_tgt, (int)c->nt, R9, t3, 1, L.d_min_bits, st);
     } else {
-        const float* skip_lb = nullptr;
-        const uint32_t* skip_u = nullptr;
-        if (c->inliers && c->trim_skip) {  // trimmed: queries provably beyond the k-th smallest distance are left out of the exact search
-            launch_nn_prep(c->d_src, ns, c->d_lut, c->geom, R9, t3, 1, c->d_tgt, (int)c->nt, seed_idx, c->tgt_box6, L.d_nn_ub, L.d_nn_lb, st);
-            launch_trim_select(L.d_nn_ub, ns, (int)c->inliers, nullptr, L.d_sel + 8, L.d_sel_wide, st);
-            skip_lb = L.d_nn_lb;
-            skip_u = L.d_sel + 8;
-        }
-        launch_nn_scan(c->d_src, ns, c->bvh_tgt.view(), c->d_lut, c->geom, R9, t3, 1, 0, c->d_tgt, (int)c->nt, seed_idx, skip_lb, skip_u, L.d_min_bits, st);
+        const TrimQueries q = trim_pristine(c, L, R9, t3);
+        if (skip) trim_brackets(c, q, seed_idx, st);  // trimmed: queries provably beyond the k-th smallest distance are left out of the exact search
+        launch_nn_scan(c->d_src, ns, c->bvh_tgt.view(), c->d_lut, c->geom, R9, t3, 1, 0, c->d_tgt, (int)c->nt, seed_idx, skip ? q.lb : nullptr, skip ? q.sel : nullptr, L.d_min_bits, st);
     }
-    if (part == 1) {
-    } else if (c->inliers) {  // trimmed SSE: the k smallest nearest-neighbour terms
-        launch_trim_select(reinterpret_cast<const float*>(L.d_min_bits), ns, (int)c->inliers, L.hd_trim, nullptr, L.d_sel_wide, st);
+    HIPCHK(hipGetLastError());
+    return FGOICP_OK;
+}
+// ... and the sum over the minima in `mins` (trimmed: the k smallest nearest-neighbour terms); fused: the search has left it in pinned memory
+static int sse_sum_enqueue(fgoicp_ctx* c, fgoicp_ctx::IcpLane& L, const uint32_t* mins, bool fused, hipStream_t st) {
+    const int ns = (int)c->ns;
+    L.sse_on_host = fused;
+    if (fused) {
+    } else if (c->inliers) {
+        launch_trim_select(reinterpret_cast<const float*>(mins), ns, (int)c->inliers, L.hd_trim, nullptr, L.d_sel_wide, st);
     } else {
         const int nb = reduce_blocks_for(ns);
-        launch_sum_f32_as_f64(L.d_min_bits, ns, L.d_bp3, nb, st);
+        launch_sum_f32_as_f64(mins, ns, L.d_bp3, nb, st);
         launch_sum_partials(L.d_bp3, nb, 1, L.hd_sums + 12, st);
     }
     HIPCHK(hipGetLastError());
     return FGOICP_OK;
+}
+static int sse_enqueue(fgoicp_ctx* c, fgoicp_ctx::IcpLane& L, const float* R9, const float* t3, const uint32_t* seed_idx, hipStream_t st, bool may_skip = true) {
+    const bool fused = icp_fused(c);
+    const int rc = sse_search_enqueue(c, L, R9, t3, seed_idx, fused, may_skip && trim_skips(c), st);
+    return rc ? rc : sse_sum_enqueue(c, L, L.d_min_bits, fused, st);
 }
 static float sse_result(const fgoicp_ctx* c, const fgoicp_ctx::IcpLane& L) {
     if (L.sse_on_host) return (float)fold_wave_sums(L.h_wsse, (int)((c->ns + 63) / 64));
@@ -498,10 +534,8 @@ static int alignment_enqueue(fgoicp_ctx* c, const float* R9, const float* t3, bo
     fgoicp_ctx::IcpLane& L = c->lanes[0];
     fgoicp_ctx::AlignScratch& A = c->align;
     const int ns = (int)c->ns, nt = (int)c->nt;
-    if (!c->d_orig_of_slot) {  // untrimmed contexts have had no use for it so far
-        HIPCHK(hipMalloc(&c->d_orig_of_slot, sizeof(uint32_t) * c->ns));
-        HIPCHK(hipMemcpy(c->d_orig_of_slot, c->perm.data(), sizeof(uint32_t) * c->ns, hipMemcpyHostToDevice));
-    }
+    int rc = ensure_orig_of_slot(c);  // untrimmed contexts have had no use for it so far
+    if (rc) return rc;
     if (!A.base) {
         auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
         A.nt16 = (c->nt + 15) & ~(size_t)15;
@@ -522,14 +556,11 @@ static int alignment_enqueue(fgoicp_ctx* c, const float* R9, const float* t3, bo
         A.d_info = reinterpret_cast<unsigned long long*>(b + o_info);
     }
     hipStream_t st = L.stream;
-    const bool skip = c->trim_skip;
-    c->trim_skip = false;
-    const int rc = sse_enqueue(c, L, R9, t3, nullptr, st);
-    c->trim_skip = skip;
+    rc = sse_enqueue(c, L, R9, t3, nullptr, st, false);
     if (rc) return rc;
     if (c->brute_force_nn) {  // kernFindNearestNeighbor (icp3d.cu:11-28) as procrustes_enqueue runs it, on the source moved as the scan's queries are
-        HIPCHK(hipMemcpyAsync(L.d_work, c->d_src, sizeof(float4) * c->ns, hipMemcpyDeviceToDevice, st));
-        launch_transform_inplace(L.d_work, ns, R9, t3, st);
+        rc = work_begin_enqueue(c, L, R9, t3, st);
+        if (rc) return rc;
         launch_fill_u32(A.d_idx, 0x7fffffffu, c->ns, st);
         launch_nn_tie_threshold(L.d_min_bits, ns, L.d_thr_bits, st);
         launch_nn_first_index(L.d_work, ns, c->d_tgt, nt, L.d_thr_bits, A.d_idx, st);
@@ -800,10 +831,7 @@ int ctx_set_source_normals(fgoicp_ctx* c, const float* normals, int k) {
         c->src_normals_set = true;
         return FGOICP_OK;
     }
-    if (!c->d_orig_of_slot) {
-        HIPCHK(hipMalloc(&c->d_orig_of_slot, sizeof(uint32_t) * ns));
-        HIPCHK(hipMemcpy(c->d_orig_of_slot, c->perm.data(), sizeof(uint32_t) * ns, hipMemcpyHostToDevice));
-    }
+    if (int rc = ensure_orig_of_slot(c)) return rc;
     h.resize(ns);
     HIPCHK(hipMemcpy(h.data(), c->d_src, sizeof(float4) * ns, hipMemcpyDeviceToHost));
     std::vector<float4> caller(ns);
@@ -838,52 +866,47 @@ int ctx_source_normals(fgoicp_ctx* c, float* out) {
     return FGOICP_OK;
 }
 
-// IterativeClosestPoint3D::procrustes() on L.d_work — icp3d.cu:140-172.  The device half (enqueue only): correspondences
-// into `idx`, centroids and covariance into pinned memory; `wide` is the selection scratch of the trimmed variant.
+// IterativeClosestPoint3D::procrustes() on L.d_work — icp3d.cu:140-172.  The device half (enqueue only), itself in two halves: the correspondences
+// into `idx`; then the inlier cut (trimmed), centroids and covariance into pinned memory.  `wide` is the selection scratch of the trimmed variant.
 // move9 / move3 (optional): the working cloud is first moved by this (R_, t_) — icp3d.cu:100 of the iteration before — inside the
 // correspondence scan where that is possible (one launch less on the iteration's critical chain), by its own kernel otherwise.
-// `part` as for sse_enqueue: 1 = up to and including the correspondence search, 2 = the inlier cut and the sums.
-static int procrustes_enqueue(fgoicp_ctx* c, fgoicp_ctx::IcpLane& L, const uint32_t* seed_idx, uint32_t* idx, uint32_t* wide, hipStream_t st,
-                              const float* move9 = nullptr, const float* move3 = nullptr, int part = 0) {
+static int procrustes_corr_enqueue(fgoicp_ctx* c, fgoicp_ctx::IcpLane& L, const uint32_t* seed_idx, uint32_t* idx, uint32_t* wide, bool fused, hipStream_t st,
+                                   const float* move9 = nullptr, const float* move3 = nullptr) {
     const int ns = (int)c->ns, nt = (int)c->nt;
-    if (icp_fused(c)) {  // two launches: scan (+ move, + wave-level sums of points and correspondences), covariance (+ centroids) into pinned memory
-        const int nb = reduce_blocks_for(ns);
-        if (part != 2)
-            launch_nn_scan(L.d_work, ns, c->bvh_tgt.view(), c->d_lut, c->geom, move9, move3, move9 ? 1 : 0, 1, c->d_tgt, nt, seed_idx, nullptr, nullptr, idx, st,
-                           move9 ? L.d_work : nullptr, nullptr, nullptr, L.d_wsum);
-        if (part != 1) launch_icp_cov_cen(L.d_work, c->d_tgt, idx, ns, nt, L.d_wsum, nb, (ns + 63) / 64, L.hd_cen, L.hd_covbp, nb, st);
-        L.cov_on_host = true;
+    if (fused) {  // two launches: scan (+ move, + wave-level sums of points and correspondences), covariance (+ centroids) into pinned memory
+        launch_nn_scan(L.d_work, ns, c->bvh_tgt.view(), c->d_lut, c->geom, move9, move3, move9 ? 1 : 0, 1, c->d_tgt, nt, seed_idx, nullptr, nullptr, idx, st,
+                       move9 ? L.d_work : nullptr, nullptr, nullptr, L.d_wsum);
+        HIPCHK(hipGetLastError());
+        return FGOICP_OK;
+    }
+    static const bool fold_move = [] { const char* e = dev_env("FGOICP_ICP_FOLD_MOVE"); return !e || std::atoi(e) != 0; }();  // tuning knob / A-B
+    const bool skip = trim_skips(c), fold = move9 && fold_move && !c->brute_force_nn && !skip;
+    if (move9 && !fold) launch_transform_inplace(L.d_work, ns, move9, move3, st);
+    // kernFindNearestNeighbor (icp3d.cu:11-28): min distance, tie set, lowest index
+    if (c->brute_force_nn) {
+        launch_fill_u32(L.d_min_bits, 0x501502F9u, c->ns, st);
+        launch_fill_u32(idx, 0x7fffffffu, c->ns, st);
+        launch_nn_min(L.d_work, ns, c->d_tgt, nt, nullptr, nullptr, 0, L.d_min_bits, st);
+        launch_nn_tie_threshold(L.d_min_bits, ns, L.d_thr_bits, st);
+        launch_nn_first_index(L.d_work, ns, c->d_tgt, nt, L.d_thr_bits, idx, st);
+    } else {
+        const TrimQueries q = trim_working(L, wide);
+        if (skip) trim_brackets(c, q, seed_idx, st);  // trimmed: points provably outside the inlier set get no correspondence
+        launch_nn_scan(L.d_work, ns, c->bvh_tgt.view(), c->d_lut, c->geom, fold ? move9 : nullptr, fold ? move3 : nullptr, fold ? 1 : 0, 1, c->d_tgt, nt, seed_idx,
+                       skip ? q.lb : nullptr, skip ? q.sel : nullptr, idx, st, fold ? L.d_work : nullptr);
+    }
+    HIPCHK(hipGetLastError());
+    return FGOICP_OK;
+}
+static int procrustes_sums_enqueue(fgoicp_ctx* c, fgoicp_ctx::IcpLane& L, const uint32_t* idx, uint32_t* wide, bool fused, hipStream_t st) {
+    const int ns = (int)c->ns, nt = (int)c->nt, nb = reduce_blocks_for(ns);
+    L.cov_on_host = fused;
+    if (fused) {
+        launch_icp_cov_cen(L.d_work, c->d_tgt, idx, ns, nt, L.d_wsum, nb, (ns + 63) / 64, L.hd_cen, L.hd_covbp, nb, st);
         L.cov_blocks = nb;
         HIPCHK(hipGetLastError());
         return FGOICP_OK;
     }
-    L.cov_on_host = false;
-    if (part != 2) {
-        static const bool fold_move = [] { const char* e = dev_env("FGOICP_ICP_FOLD_MOVE"); return !e || std::atoi(e) != 0; }();  // tuning knob / A-B
-        const bool fold = move9 && fold_move && !c->brute_force_nn && !(c->inliers && c->trim_skip);
-        if (move9 && !fold) launch_transform_inplace(L.d_work, ns, move9, move3, st);
-        // kernFindNearestNeighbor (icp3d.cu:11-28): min distance, tie set, lowest index
-        if (c->brute_force_nn) {
-            launch_fill_u32(L.d_min_bits, 0x501502F9u, c->ns, st);
-            launch_fill_u32(idx, 0x7fffffffu, c->ns, st);
-            launch_nn_min(L.d_work, ns, c->d_tgt, nt, nullptr, nullptr, 0, L.d_min_bits, st);
-            launch_nn_tie_threshold(L.d_min_bits, ns, L.d_thr_bits, st);
-            launch_nn_first_index(L.d_work, ns, c->d_tgt, nt, L.d_thr_bits, idx, st);
-        } else {
-            const float* skip_lb = nullptr;
-            const uint32_t* skip_u = nullptr;
-            if (c->inliers && c->trim_skip) {  // trimmed: points provably outside the inlier set get no correspondence
-                launch_nn_prep(L.d_work, ns, c->d_lut, c->geom, nullptr, nullptr, 0, c->d_tgt, nt, seed_idx, c->tgt_box6, L.d_nn_ub2, L.d_nn_lb2, st);
-                launch_trim_select(L.d_nn_ub2, ns, (int)c->inliers, nullptr, L.d_sel + 4, wide, st);
-                skip_lb = L.d_nn_lb2;
-                skip_u = L.d_sel + 4;
-            }
-            launch_nn_scan(L.d_work, ns, c->bvh_tgt.view(), c->d_lut, c->geom, fold ? move9 : nullptr, fold ? move3 : nullptr, fold ? 1 : 0, 1, c->d_tgt, nt, seed_idx, skip_lb,
-                           skip_u, idx, st, fold ? L.d_work : nullptr);
-        }
-    }
-    if (part == 1) { HIPCHK(hipGetLastError()); return FGOICP_OK; }
-    const int nb = reduce_blocks_for(ns);
     const unsigned char* use = nullptr;
     int ncount = ns;
     if (c->inliers) {  // trimmed ICP: only the k closest correspondences enter the Procrustes sums
@@ -899,6 +922,12 @@ static int procrustes_enqueue(fgoicp_ctx* c, fgoicp_ctx::IcpLane& L, const uint3
     launch_sum_partials(L.d_bp2, nb, 9, L.hd_sums, st);
     HIPCHK(hipGetLastError());
     return FGOICP_OK;
+}
+static int procrustes_enqueue(fgoicp_ctx* c, fgoicp_ctx::IcpLane& L, const uint32_t* seed_idx, uint32_t* idx, uint32_t* wide, hipStream_t st,
+                              const float* move9 = nullptr, const float* move3 = nullptr) {
+    const bool fused = icp_fused(c);
+    const int rc = procrustes_corr_enqueue(c, L, seed_idx, idx, wide, fused, st, move9, move3);
+    return rc ? rc : procrustes_sums_enqueue(c, L, idx, wide, fused, st);
 }
 // ... and the host half, once the stream has drained: 3x3 SVD, icp3d.cu:168-169
 static void procrustes_finish(const fgoicp_ctx::IcpLane& L, Mat3f* R_out, Vec3f* t_out, float* centroids6_out, Mat3f* ABt_out) {
@@ -941,31 +970,23 @@ static int lane_icp(fgoicp_ctx* c, fgoicp_ctx::IcpLane& L, const float* R0, cons
     const int ns = (int)c->ns;
     const bool overlap = c->icp_overlap && !c->brute_force_nn;
     const bool seeding = c->icp_seeding && !c->brute_force_nn;
+    const bool fused = icp_fused(c);
     hipStream_t A = L.stream, B = overlap ? L.icp_stream : L.stream;
     uint32_t* idx[2] = {L.d_first_idx, overlap ? L.d_first_idx2 : L.d_first_idx};
-    int cur = 0;
-    HIPCHK(hipMemcpyAsync(L.d_work, c->d_src, sizeof(float4) * c->ns, hipMemcpyDeviceToDevice, A));
-    launch_transform_inplace(L.d_work, ns, R0, t0, A);  // icp3d.cu:85
-    Mat3f R = Mat3f::from(R0);
-    Vec3f t{t0[0], t0[1], t0[2]};
-    size_t iter = 0;
-    float sse = kInf, last_sse = 2.0f * kInf;
-    Mat3f last_R = Mat3f::identity();
-    Vec3f last_t{0, 0, 0};
-    int iters = 0;
+    int rc = work_begin_enqueue(c, L, R0, t0, A);
+    if (rc) return rc;
+    IcpLoop s;
+    s.begin(R0, t0, max_iter, thr);
     bool chain_pending = false;  // a correspondence pass is in flight on B
     if (overlap && max_iter > 0) {
         HIPCHK(hipEventRecord(L.icp_ev_w, A));
         HIPCHK(hipStreamWaitEvent(B, L.icp_ev_w, 0));
-        int rc = procrustes_enqueue(c, L, nullptr, idx[0], L.d_sel_wide2, B);
+        rc = procrustes_enqueue(c, L, nullptr, idx[0], L.d_sel_wide2, B);
         if (rc) return rc;
         HIPCHK(hipEventRecord(L.icp_ev_b, B));
         chain_pending = true;
     }
-    while (iter++ < max_iter && (last_sse - sse) > thr * last_sse) {  // icp3d.cu:94
-        last_sse = sse;
-        last_R = R;
-        last_t = t;
+    while (s.next()) {
         Mat3f Rn;
         Vec3f tn;
         if (overlap) {
@@ -974,51 +995,45 @@ static int lane_icp(fgoicp_ctx* c, fgoicp_ctx::IcpLane& L, const float* R0, cons
             procrustes_finish(L, &Rn, &tn, nullptr, nullptr);
         } else {
             // every pass after the first seeds its exact search with the correspondences of the pass before it
-            int rc = ctx_procrustes_device(c, L, &Rn, &tn, nullptr, nullptr, iters > 0 && seeding);
+            rc = ctx_procrustes_device(c, L, &Rn, &tn, nullptr, nullptr, s.iters > 0 && seeding);
             if (rc) return rc;
         }
         const float tn3[3] = {tn.x, tn.y, tn.z};
-        R = Rn * R;                                              // :101
-        t = Rn * t + tn;                                         // :102
-        const float t3[3] = {t.x, t.y, t.z};
+        s.compose(Rn, tn);
+        const float t3[3] = {s.t.x, s.t.y, s.t.z};
+        float sse = 0.f;
         if (overlap) {
             // The working cloud and the next iteration's pass are the critical path (transform -> correspondences -> sums -> host):
             // they go to the side stream FIRST; this iteration's SSE, which needs nothing but (R, t), is enqueued behind them on the
             // main stream.  (Enqueued after the SSE chain, the correspondence scan started 25 us late: five launches of host time.)
-            const uint32_t* seed = seeding ? idx[cur] : nullptr;  // the pass the host has just consumed
-            const bool next = iter < max_iter;  // the next iteration's pass (it moves the cloud first, :100), next to this iteration's SSE
-            int rc = FGOICP_OK;
-            if (next) rc = procrustes_enqueue(c, L, seed, idx[cur ^ 1], L.d_sel_wide2, B, Rn.m, tn3, 1);
+            const uint32_t* seed = seeding ? idx[s.cur] : nullptr;  // the pass the host has just consumed
+            const bool next = s.rides();  // the next iteration's pass (it moves the cloud first, :100), next to this iteration's SSE
+            uint32_t* idx_out = idx[s.cur ^ 1];
+            if (next) rc = procrustes_corr_enqueue(c, L, seed, idx_out, L.d_sel_wide2, fused, B, Rn.m, tn3);
             else launch_transform_inplace(L.d_work, ns, Rn.m, tn3, B);  // :100 (B is in order behind the pass that read d_work)
             if (rc) return rc;
-            rc = sse_enqueue(c, L, R.m, t3, seed, A, 1);  // :103
+            rc = sse_search_enqueue(c, L, s.R.m, t3, seed, fused, trim_skips(c), A);  // :103
             if (rc) return rc;
             if (next) {
-                rc = procrustes_enqueue(c, L, seed, idx[cur ^ 1], L.d_sel_wide2, B, nullptr, nullptr, 2);
+                rc = procrustes_sums_enqueue(c, L, idx_out, L.d_sel_wide2, fused, B);
                 if (rc) return rc;
-                cur ^= 1;
+                s.flip();
             }
             HIPCHK(hipEventRecord(L.icp_ev_b, B));
             chain_pending = true;
-            rc = sse_enqueue(c, L, R.m, t3, seed, A, 2);
+            rc = sse_sum_enqueue(c, L, L.d_min_bits, fused, A);
             if (rc) return rc;
             HIPCHK(wait_stream(A));
             sse = sse_result(c, L);
         } else {
             launch_transform_inplace(L.d_work, ns, Rn.m, tn3, A);  // :100
-            int rc = lane_sse(c, L, R.m, t3, &sse, seeding ? L.d_first_idx : nullptr);  // :103
+            rc = lane_sse(c, L, s.R.m, t3, &sse, seeding ? L.d_first_idx : nullptr);  // :103
             if (rc) return rc;
         }
-        ++iters;
+        s.took(sse);
     }
     if (chain_pending) HIPCHK(hipEventSynchronize(L.icp_ev_b));  // the speculative pass: drained, not used
-    const bool cur_best = sse < last_sse;  // :106-107
-    *sse_out = cur_best ? sse : last_sse;
-    const Mat3f& Ro = cur_best ? R : last_R;
-    const Vec3f& to = cur_best ? t : last_t;
-    std::memcpy(R_out9, Ro.m, sizeof(Ro.m));
-    t_out3[0] = to.x; t_out3[1] = to.y; t_out3[2] = to.z;
-    if (iters_out) *iters_out = iters;
+    s.result(sse_out, R_out9, t_out3, iters_out);
     return FGOICP_OK;
 }
 
@@ -1030,59 +1045,46 @@ int ctx_icp(fgoicp_ctx* c, const float* R0, const float* t0, size_t max_iter, fl
 // step enqueues what the loop enqueues between two waits — the correspondence pass of the next iteration (which moves the working cloud
 // first) and this iteration's SSE — so the kernels, their inputs and the order of every sum are lane_icp's: the same (sse, R, t, iterations).
 bool ctx_icp_steppable(const fgoicp_ctx* c) { return icp_fused(c) && c->icp_overlap && c->icp_dual_env <= 0; }
-int ctx_icp_step_begin(fgoicp_ctx* c, IcpStepState& s, const float* R0, const float* t0, size_t max_iter, float thr) {
+int ctx_icp_step_begin(fgoicp_ctx* c, IcpStepRun& s, const float* R0, const float* t0, size_t max_iter, float thr) {
     HIPCHK(hipSetDevice(c->device));
     fgoicp_ctx::IcpLane& L = c->lanes[0];
-    s = IcpStepState();
-    s.R = Mat3f::from(R0);
-    s.t = Vec3f{t0[0], t0[1], t0[2]};
-    s.max_iter = max_iter;
-    s.thr = thr;
-    HIPCHK(hipMemcpyAsync(L.d_work, c->d_src, sizeof(float4) * c->ns, hipMemcpyDeviceToDevice, L.stream));
-    launch_transform_inplace(L.d_work, (int)c->ns, R0, t0, L.stream);  // icp3d.cu:85
+    s = IcpStepRun();
+    s.loop.begin(R0, t0, max_iter, thr);
+    int rc = work_begin_enqueue(c, L, R0, t0, L.stream);
+    if (rc) return rc;
     if (max_iter > 0) {
-        int rc = procrustes_enqueue(c, L, nullptr, L.d_first_idx, L.d_sel_wide2, L.stream);
+        rc = procrustes_enqueue(c, L, nullptr, L.d_first_idx, L.d_sel_wide2, L.stream);
         if (rc) return rc;
     }
     HIPCHK(hipGetLastError());
     return FGOICP_OK;
 }
-// Call once the context's stream has drained.  Sets s.done when the loop has ended (the outputs are then in s.sse_out, s.R_out, s.t_out).
-int ctx_icp_step(fgoicp_ctx* c, IcpStepState& s) {
+// Call once the context's stream has drained.  Sets s.done when the loop has ended (s.loop.result() then hands the outputs over).
+int ctx_icp_step(fgoicp_ctx* c, IcpStepRun& s) {
     fgoicp_ctx::IcpLane& L = c->lanes[0];
-    if (s.have_sse) {
-        s.sse = sse_result(c, L);
-        ++s.iters;
-    }
-    if (!(s.iter++ < s.max_iter && (s.last_sse - s.sse) > s.thr * s.last_sse)) {  // icp3d.cu:94
-        const bool cur_best = s.sse < s.last_sse;  // :106-107
-        s.sse_out = cur_best ? s.sse : s.last_sse;
-        s.R_out = cur_best ? s.R : s.last_R;
-        s.t_out = cur_best ? s.t : s.last_t;
+    IcpLoop& lp = s.loop;
+    if (s.have_sse) lp.took(sse_result(c, L));
+    if (!lp.next()) {
         s.done = true;
         return FGOICP_OK;
     }
     HIPCHK(hipSetDevice(c->device));
-    s.last_sse = s.sse;
-    s.last_R = s.R;
-    s.last_t = s.t;
     Mat3f Rn;
     Vec3f tn;
     procrustes_finish(L, &Rn, &tn, nullptr, nullptr);
     const float tn3[3] = {tn.x, tn.y, tn.z};
-    s.R = Rn * s.R;          // :101
-    s.t = Rn * s.t + tn;     // :102
-    const float t3[3] = {s.t.x, s.t.y, s.t.z};
+    lp.compose(Rn, tn);
+    const float t3[3] = {lp.t.x, lp.t.y, lp.t.z};
     uint32_t* idx[2] = {L.d_first_idx, L.d_first_idx2};
-    const uint32_t* seed = c->icp_seeding ? idx[s.cur] : nullptr;
-    const bool next = s.iter < s.max_iter;
+    const uint32_t* seed = c->icp_seeding ? idx[lp.cur] : nullptr;
+    const bool next = lp.rides();
     if (next) {
-        int rc = procrustes_enqueue(c, L, seed, idx[s.cur ^ 1], L.d_sel_wide2, L.stream, Rn.m, tn3);
+        int rc = procrustes_enqueue(c, L, seed, idx[lp.cur ^ 1], L.d_sel_wide2, L.stream, Rn.m, tn3);
         if (rc) return rc;
     }
-    int rc = sse_enqueue(c, L, s.R.m, t3, seed, L.stream);  // :103
+    int rc = sse_enqueue(c, L, lp.R.m, t3, seed, L.stream);  // :103
     if (rc) return rc;
-    if (next) s.cur ^= 1;
+    if (next) lp.flip();
     s.have_sse = true;
     HIPCHK(hipGetLastError());
     return FGOICP_OK;
@@ -1120,69 +1122,37 @@ int ctx_icp_coop(fgoicp_ctx* c, int rank, int world, int (*gather)(void* dev_buf
     // lists the kernel wrote 0x7fffffff to a slot before every wave of the block had read its seed — results stayed exact, a seed only
     // tightens a bound, but the work done varied from run to run)
     uint32_t* idx_buf[2] = {c->d_coop, c->d_coop + c->coop_cap};
-    int cur = 0;
-    uint32_t* idx = idx_buf[cur];
     uint32_t* mins = c->d_coop + 2 * c->coop_cap;
     const int qb = (int)std::min<size_t>((size_t)ns, per * rank), nq = (int)std::min<size_t>((size_t)ns, per * (rank + 1)) - qb;
     const bool seeding = c->icp_seeding;
     hipStream_t S = L.stream;
-    const int nb = reduce_blocks_for(ns);
-    HIPCHK(hipMemcpyAsync(L.d_work, c->d_src, sizeof(float4) * c->ns, hipMemcpyDeviceToDevice, S));
-    launch_transform_inplace(L.d_work, ns, R0, t0, S);  // icp3d.cu:85
-    Mat3f R = Mat3f::from(R0);
-    Vec3f t{t0[0], t0[1], t0[2]};
-    size_t iter = 0;
-    float sse = kInf, last_sse = 2.0f * kInf;
-    Mat3f last_R = Mat3f::identity();
-    Vec3f last_t{0, 0, 0};
-    int iters = 0;
+    int rc = work_begin_enqueue(c, L, R0, t0, S);
+    if (rc) return rc;
+    IcpLoop s;
+    s.begin(R0, t0, max_iter, thr);
     // The loop is lane_icp_dual's (one walk per iteration serves the exact SSE of iteration k and the correspondences of iteration k + 1),
     // with the walk cut down to this rank's queries and two in-place all-gathers behind it: ONE scan, two gathers and two host syncs
     // per iteration (a first version ran the two scans one after the other: two scans, two gathers, four syncs).  Trimmed contexts
     // (c->inliers): the LUT brackets, the cuts and the inlier selection run over the whole cloud on every rank (cheap, replicated), the
-    // walk — 85 % of a trimmed iteration at 1M points — on the share; the reductions are the single-GPU loop's own enqueue functions.
-    const bool trimmed = c->inliers != 0, skip = trimmed && c->trim_skip;
-    struct MinBitsGuard {  // sse_enqueue's trimmed selection reads L.d_min_bits: it is pointed at the gathered buffer for the duration of the run
-        fgoicp_ctx::IcpLane& L; uint32_t* saved;
-        MinBitsGuard(fgoicp_ctx::IcpLane& l, uint32_t* m) : L(l), saved(l.d_min_bits) { L.d_min_bits = m; }
-        ~MinBitsGuard() { L.d_min_bits = saved; }
-    } guard(L, mins);
-    auto reduce_pass = [&]() -> int {  // inlier cut (trimmed), sums, centroids, covariance of the correspondences in idx[] (all ranks' shares)
-        if (trimmed) return procrustes_enqueue(c, L, nullptr, idx, L.d_sel_wide2, S, nullptr, nullptr, 2);
-        launch_icp_sums(L.d_work, c->d_tgt, idx, ns, nt, nullptr, L.d_bp, nb, S);
-        launch_icp_centroids(L.d_bp, nb, ns, L.d_cen, L.hd_cen, S);
-        launch_icp_cov(L.d_work, c->d_tgt, idx, ns, nt, L.d_cen, nullptr, L.d_bp2, nb, S);
-        launch_sum_partials(L.d_bp2, nb, 9, L.hd_sums, S);
-        L.cov_on_host = false;
-        return FGOICP_OK;
-    };
-    auto sse_sum = [&]() -> int {  // compute_sse_error's sum over the gathered minima (trimmed: the k smallest)
-        if (trimmed) return sse_enqueue(c, L, nullptr, nullptr, nullptr, S, 2);
-        launch_sum_f32_as_f64(mins, ns, L.d_bp3, nb, S);
-        launch_sum_partials(L.d_bp3, nb, 1, L.hd_sums + 12, S);
-        L.sse_on_host = false;
-        return FGOICP_OK;
-    };
+    // walk — 85 % of a trimmed iteration at 1M points — on the share; the reductions are the single-GPU loop's own sum halves, unfused
+    // (the share's scan leaves no wave sums) and over the gathered arrays.
+    const bool skip = trim_skips(c);
+    const TrimQueries qA = trim_working(L, L.d_sel_wide2);
     bool pending = false;
     if (max_iter > 0) {  // pass 1 (icp3d.cu:140-172): correspondences of my share, gathered; sums over everything
-        if (skip) {
-            launch_nn_prep(L.d_work, ns, c->d_lut, c->geom, nullptr, nullptr, 0, c->d_tgt, nt, nullptr, c->tgt_box6, L.d_nn_ub2, L.d_nn_lb2, S);
-            launch_trim_select(L.d_nn_ub2, ns, (int)c->inliers, nullptr, L.d_sel + 4, L.d_sel_wide2, S);
-        }
+        uint32_t* idx = idx_buf[0];
+        if (skip) trim_brackets(c, qA, nullptr, S);
         if (nq > 0)
-            launch_nn_scan(L.d_work + qb, nq, c->bvh_tgt.view(), c->d_lut, c->geom, nullptr, nullptr, 0, 1, c->d_tgt, nt, nullptr, skip ? L.d_nn_lb2 + qb : nullptr,
-                           skip ? L.d_sel + 4 : nullptr, idx + qb, S);
+            launch_nn_scan(L.d_work + qb, nq, c->bvh_tgt.view(), c->d_lut, c->geom, nullptr, nullptr, 0, 1, c->d_tgt, nt, nullptr, skip ? qA.lb + qb : nullptr,
+                           skip ? qA.sel : nullptr, idx + qb, S);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(S));
         if (gather(idx, sizeof(uint32_t) * per, user)) return FGOICP_ERR_EXCHANGE;
-        int rc = reduce_pass();
+        rc = procrustes_sums_enqueue(c, L, idx, L.d_sel_wide2, false, S);
         if (rc) return rc;
         pending = true;
     }
-    while (iter++ < max_iter && (last_sse - sse) > thr * last_sse) {  // icp3d.cu:94
-        last_sse = sse;
-        last_R = R;
-        last_t = t;
+    while (s.next()) {
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(S));  // first iteration: pass 1; later: a no-op (the SSE's sync below drained the stream)
         pending = false;
@@ -1190,54 +1160,43 @@ int ctx_icp_coop(fgoicp_ctx* c, int rank, int world, int (*gather)(void* dev_buf
         Vec3f tn;
         procrustes_finish(L, &Rn, &tn, nullptr, nullptr);
         const float tn3[3] = {tn.x, tn.y, tn.z};
-        R = Rn * R;                                              // :101
-        t = Rn * t + tn;                                         // :102
-        const float t3[3] = {t.x, t.y, t.z};
+        s.compose(Rn, tn);
+        const float t3[3] = {s.t.x, s.t.y, s.t.z};
         launch_transform_inplace(L.d_work, ns, Rn.m, tn3, S);    // :100 (the whole cloud: the reductions read all of it)
-        const bool next = iter < max_iter;
-        const uint32_t* seed = seeding ? idx : nullptr;          // the gathered correspondences of the pass the host has just consumed
-        uint32_t* idx_out = idx_buf[cur ^ 1];                    // where the pass riding along writes (never the buffer the seeds come from)
-        const float *lbA = nullptr, *lbB = nullptr;
-        const uint32_t *uA = nullptr, *uB = nullptr;
+        const bool next = s.rides();
+        const uint32_t* seed = seeding ? idx_buf[s.cur] : nullptr;  // the gathered correspondences of the pass the host has just consumed
+        uint32_t* idx_out = idx_buf[s.cur ^ 1];                     // where the pass riding along writes (never the buffer the seeds come from)
+        const TrimQueries qB = trim_pristine(c, L, s.R.m, t3);
         if (skip) {  // trimmed: brackets and cuts of both query sets, whole cloud, as lane_icp_dual
-            if (next) {
-                launch_nn_prep(L.d_work, ns, c->d_lut, c->geom, nullptr, nullptr, 0, c->d_tgt, nt, seed, c->tgt_box6, L.d_nn_ub2, L.d_nn_lb2, S);
-                launch_trim_select(L.d_nn_ub2, ns, (int)c->inliers, nullptr, L.d_sel + 4, L.d_sel_wide2, S);
-                lbA = L.d_nn_lb2 + qb; uA = L.d_sel + 4;
-            }
-            launch_nn_prep(c->d_src, ns, c->d_lut, c->geom, R.m, t3, 1, c->d_tgt, nt, seed, c->tgt_box6, L.d_nn_ub, L.d_nn_lb, S);
-            launch_trim_select(L.d_nn_ub, ns, (int)c->inliers, nullptr, L.d_sel + 8, L.d_sel_wide, S);
-            lbB = L.d_nn_lb + qb; uB = L.d_sel + 8;
+            if (next) trim_brackets(c, qA, seed, S);
+            trim_brackets(c, qB, seed, S);
         }
+        const float* lbB = skip ? qB.lb + qb : nullptr;
+        const uint32_t* uB = skip ? qB.sel : nullptr;
         if (nq > 0) {
             if (next)  // compute_sse_error(R, t) (:103) of this iteration and the correspondences of the next: one walk, my share
-                launch_nn_scan_dual(L.d_work + qb, nullptr, nullptr, 0, c->d_src + qb, R.m, t3, nq, c->bvh_tgt.view(), c->d_lut, c->geom, c->d_tgt, nt, seed ? seed + qb : nullptr,
-                                    lbA, uA, lbB, uB, idx_out + qb, mins + qb, nullptr, nullptr, nullptr, S);
+                launch_nn_scan_dual(L.d_work + qb, nullptr, nullptr, 0, c->d_src + qb, s.R.m, t3, nq, c->bvh_tgt.view(), c->d_lut, c->geom, c->d_tgt, nt, seed ? seed + qb : nullptr,
+                                    skip ? qA.lb + qb : nullptr, skip ? qA.sel : nullptr, lbB, uB, idx_out + qb, mins + qb, nullptr, nullptr, nullptr, S);
             else       // the last iteration the loop can make: no pass rides along
-                launch_nn_scan(c->d_src + qb, nq, c->bvh_tgt.view(), c->d_lut, c->geom, R.m, t3, 1, 0, c->d_tgt, nt, seed ? seed + qb : nullptr, lbB, uB, mins + qb, S);
+                launch_nn_scan(c->d_src + qb, nq, c->bvh_tgt.view(), c->d_lut, c->geom, s.R.m, t3, 1, 0, c->d_tgt, nt, seed ? seed + qb : nullptr, lbB, uB, mins + qb, S);
         }
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(S));
         if (next && gather(idx_out, sizeof(uint32_t) * per, user)) return FGOICP_ERR_EXCHANGE;
         if (gather(mins, sizeof(uint32_t) * per, user)) return FGOICP_ERR_EXCHANGE;
-        int rc = FGOICP_OK;
-        if (next) { cur ^= 1; idx = idx_buf[cur]; rc = reduce_pass(); pending = true; }  // speculative, as on one GPU (the loop may end on this iteration's SSE)
+        if (next) {  // speculative, as on one GPU (the loop may end on this iteration's SSE)
+            rc = procrustes_sums_enqueue(c, L, idx_out, L.d_sel_wide2, false, S);
+            if (rc) return rc;
+            s.flip();
+            pending = true;
+        }
+        rc = sse_sum_enqueue(c, L, mins, false, S);  // compute_sse_error's sum over the gathered minima
         if (rc) return rc;
-        rc = sse_sum();
-        if (rc) return rc;
-        HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(S));
-        sse = sse_result(c, L);
-        ++iters;
+        s.took(sse_result(c, L));
     }
     if (pending) HIPCHK(hipStreamSynchronize(S));  // the speculative pass: drained, not used
-    const bool cur_best = sse < last_sse;  // :106-107
-    *sse_out = cur_best ? sse : last_sse;
-    const Mat3f& Ro = cur_best ? R : last_R;
-    const Vec3f& to = cur_best ? t : last_t;
-    std::memcpy(R_out9, Ro.m, sizeof(Ro.m));
-    t_out3[0] = to.x; t_out3[1] = to.y; t_out3[2] = to.z;
-    if (iters_out) *iters_out = iters;
+    s.result(sse_out, R_out9, t_out3, iters_out);
     return FGOICP_OK;
 }
 
@@ -1250,78 +1209,59 @@ static int lane_icp_dual(fgoicp_ctx* c, fgoicp_ctx::IcpLane& L, const float* R0,
                          float* t_out3, int* iters_out) {
     HIPCHK(hipSetDevice(c->device));
     const int ns = (int)c->ns, nt = (int)c->nt;
-    const bool seeding = c->icp_seeding, fused = icp_fused(c), trimmed = c->inliers != 0, skip = trimmed && c->trim_skip;
+    const bool seeding = c->icp_seeding, fused = icp_fused(c), skip = trim_skips(c);
     hipStream_t S = L.stream;
     uint32_t* idx[2] = {L.d_first_idx, L.d_first_idx2};
-    int cur = 0;
-    HIPCHK(hipMemcpyAsync(L.d_work, c->d_src, sizeof(float4) * c->ns, hipMemcpyDeviceToDevice, S));
-    launch_transform_inplace(L.d_work, ns, R0, t0, S);  // icp3d.cu:85
-    Mat3f R = Mat3f::from(R0);
-    Vec3f t{t0[0], t0[1], t0[2]};
-    size_t iter = 0;
-    float sse = kInf, last_sse = 2.0f * kInf;
-    Mat3f last_R = Mat3f::identity();
-    Vec3f last_t{0, 0, 0};
-    int iters = 0;
+    int rc = work_begin_enqueue(c, L, R0, t0, S);
+    if (rc) return rc;
+    IcpLoop s;
+    s.begin(R0, t0, max_iter, thr);
     bool pending = false;
     if (max_iter > 0) {
-        int rc = procrustes_enqueue(c, L, nullptr, idx[0], L.d_sel_wide2, S);
+        rc = procrustes_enqueue(c, L, nullptr, idx[0], L.d_sel_wide2, S);
         if (rc) return rc;
         pending = true;
     }
-    while (iter++ < max_iter && (last_sse - sse) > thr * last_sse) {  // icp3d.cu:94
-        last_sse = sse;
-        last_R = R;
-        last_t = t;
+    while (s.next()) {
         HIPCHK(wait_stream(S));  // first iteration: pass 1; later: a no-op (the SSE's sync below drained the stream)
         pending = false;
         Mat3f Rn;
         Vec3f tn;
         procrustes_finish(L, &Rn, &tn, nullptr, nullptr);
         const float tn3[3] = {tn.x, tn.y, tn.z};
-        R = Rn * R;                                              // :101
-        t = Rn * t + tn;                                         // :102
-        const float t3[3] = {t.x, t.y, t.z};
-        const uint32_t* seed = seeding ? idx[cur] : nullptr;
-        const bool next = iter < max_iter;
-        int rc = FGOICP_OK;
-        if (next) {
-            const float *lbA = nullptr, *lbB = nullptr;
-            const uint32_t *uA = nullptr, *uB = nullptr;
+        s.compose(Rn, tn);
+        const float t3[3] = {s.t.x, s.t.y, s.t.z};
+        const uint32_t* seed = seeding ? idx[s.cur] : nullptr;
+        if (s.rides()) {
+            uint32_t* idx_out = idx[s.cur ^ 1];
+            const TrimQueries qA = trim_working(L, L.d_sel_wide2), qB = trim_pristine(c, L, s.R.m, t3);
             if (skip) {  // trimmed: the brackets need the moved cloud, so the move is its own kernel here (as in the two-stream loop)
                 launch_transform_inplace(L.d_work, ns, Rn.m, tn3, S);  // :100
-                launch_nn_prep(L.d_work, ns, c->d_lut, c->geom, nullptr, nullptr, 0, c->d_tgt, nt, seed, c->tgt_box6, L.d_nn_ub2, L.d_nn_lb2, S);
-                launch_nn_prep(c->d_src, ns, c->d_lut, c->geom, R.m, t3, 1, c->d_tgt, nt, seed, c->tgt_box6, L.d_nn_ub, L.d_nn_lb, S);
-                launch_trim_select(L.d_nn_ub2, ns, (int)c->inliers, nullptr, L.d_sel + 4, L.d_sel_wide2, S);
-                launch_trim_select(L.d_nn_ub, ns, (int)c->inliers, nullptr, L.d_sel + 8, L.d_sel_wide, S);
-                lbA = L.d_nn_lb2; uA = L.d_sel + 4; lbB = L.d_nn_lb; uB = L.d_sel + 8;
+                trim_prep(c, qA, seed, S);
+                trim_prep(c, qB, seed, S);
+                trim_cut(c, qA, S);
+                trim_cut(c, qB, S);
             }
-            launch_nn_scan_dual(L.d_work, skip ? nullptr : Rn.m, skip ? nullptr : tn3, skip ? 0 : 1, c->d_src, R.m, t3, ns, c->bvh_tgt.view(), c->d_lut, c->geom, c->d_tgt, nt, seed,
-                                lbA, uA, lbB, uB, idx[cur ^ 1], L.d_min_bits, skip ? nullptr : L.d_work, fused ? L.d_wsum : nullptr, fused ? L.hd_wsse : nullptr, S);
-            rc = procrustes_enqueue(c, L, seed, idx[cur ^ 1], L.d_sel_wide2, S, nullptr, nullptr, 2);  // inlier cut, sums, covariance of pass k+1
+            launch_nn_scan_dual(L.d_work, skip ? nullptr : Rn.m, skip ? nullptr : tn3, skip ? 0 : 1, c->d_src, s.R.m, t3, ns, c->bvh_tgt.view(), c->d_lut, c->geom, c->d_tgt, nt, seed,
+                                skip ? qA.lb : nullptr, skip ? qA.sel : nullptr, skip ? qB.lb : nullptr, skip ? qB.sel : nullptr, idx_out, L.d_min_bits, skip ? nullptr : L.d_work,
+                                fused ? L.d_wsum : nullptr, fused ? L.hd_wsse : nullptr, S);
+            rc = procrustes_sums_enqueue(c, L, idx_out, L.d_sel_wide2, fused, S);  // inlier cut, sums, covariance of pass k+1
             if (rc) return rc;
-            rc = sse_enqueue(c, L, R.m, t3, seed, S, 2);                                                // sum / trimmed selection of the SSE
+            rc = sse_sum_enqueue(c, L, L.d_min_bits, fused, S);                    // sum / trimmed selection of the SSE
             if (rc) return rc;
-            cur ^= 1;
+            s.flip();
             pending = true;
         } else {  // the last iteration the loop can make: no pass rides along
             launch_transform_inplace(L.d_work, ns, Rn.m, tn3, S);  // :100
-            rc = sse_enqueue(c, L, R.m, t3, seed, S);              // :103
+            rc = sse_enqueue(c, L, s.R.m, t3, seed, S);            // :103
             if (rc) return rc;
         }
         HIPCHK(hipGetLastError());
         HIPCHK(wait_stream(S));
-        sse = sse_result(c, L);
-        ++iters;
+        s.took(sse_result(c, L));
     }
     if (pending) HIPCHK(hipStreamSynchronize(S));  // the speculative pass: drained, not used
-    const bool cur_best = sse < last_sse;  // :106-107
-    *sse_out = cur_best ? sse : last_sse;
-    const Mat3f& Ro = cur_best ? R : last_R;
-    const Vec3f& to = cur_best ? t : last_t;
-    std::memcpy(R_out9, Ro.m, sizeof(Ro.m));
-    t_out3[0] = to.x; t_out3[1] = to.y; t_out3[2] = to.z;
-    if (iters_out) *iters_out = iters;
+    s.result(sse_out, R_out9, t_out3, iters_out);
     return FGOICP_OK;
 }
 
@@ -1410,10 +1350,7 @@ static int trim_setup(fgoicp_ctx* c, size_t k, bool slot_rows) {
                 HIPCHK(hipHostGetDevicePointer((void**)&L.hd_trim, L.h_trim, 0));
             }
         }
-        if (!c->d_orig_of_slot) {
-            HIPCHK(hipMalloc(&c->d_orig_of_slot, sizeof(uint32_t) * c->ns));
-            HIPCHK(hipMemcpy(c->d_orig_of_slot, c->perm.data(), sizeof(uint32_t) * c->ns, hipMemcpyHostToDevice));
-        }
+        if (int rc = ensure_orig_of_slot(c)) return rc;
         c->trim_ready = slot_rows;  // (a batch context never gets its slot rows: a later call with them allocates only what is missing)
     }
     c->inliers = k;

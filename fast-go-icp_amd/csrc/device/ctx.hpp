@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../host/math3.hpp"
+#include "../host/icp_loop.hpp"
 #include "../host/abi_guard.hpp"
 #include "../host/information.hpp"
 #include "../host/plane.hpp"
@@ -247,15 +248,11 @@ int ctx_icp_batch(fgoicp_ctx* c, int n, const float* R0s, const float* t0s, size
 
 // One ctx_icp run cut at its host turn-arounds (fgoicp_batch): begin enqueues, then ctx_icp_step after every drain of the context's
 // stream until `done`.  Only where ctx_icp_steppable (the small-cloud loop); the result is ctx_icp's, bit for bit.
-struct IcpStepState {
-    Mat3f R = Mat3f::identity(), last_R = Mat3f::identity(), R_out = Mat3f::identity();
-    Vec3f t{0, 0, 0}, last_t{0, 0, 0}, t_out{0, 0, 0};
-    float sse = 1E+10f, last_sse = 2.0f * 1E+10f, sse_out = 0.f, thr = 0.f;
-    size_t iter = 0, max_iter = 0;
-    int iters = 0, cur = 0;
-    bool have_sse = false, done = false;
+struct IcpStepRun {
+    IcpLoop loop;
+    bool have_sse = false, done = false;  // an SSE is in flight / the loop has ended: loop.result() has the outputs
 };
 bool ctx_icp_steppable(const fgoicp_ctx* c);
-int ctx_icp_step_begin(fgoicp_ctx* c, IcpStepState& s, const float* R0, const float* t0, size_t max_iter, float thr);
-int ctx_icp_step(fgoicp_ctx* c, IcpStepState& s);
+int ctx_icp_step_begin(fgoicp_ctx* c, IcpStepRun& s, const float* R0, const float* t0, size_t max_iter, float thr);
+int ctx_icp_step(fgoicp_ctx* c, IcpStepRun& s);
 }  // namespace fgoicp

@@ -116,7 +116,7 @@ struct HipBatchBackend {
     unsigned ctx_flags = 0;
     std::vector<fgoicp_ctx*> ctx;
     bool borrowed = false;  // the test hooks: the contexts are the caller's (not destroyed here)
-    std::vector<IcpStepState> icp_state;
+    std::vector<IcpStepRun> icp_state;
     hipStream_t stream = nullptr;
     uint64_t bounds_launches = 0, icp_launches = 0, selection_launches = 0;
     size_t last_lut_bytes = 0, last_lanes = 4;
@@ -152,7 +152,7 @@ struct HipBatchBackend {
         if (hipSetDevice(device) != hipSuccess) { set_error("fgoicp_batch_run: no usable HIP device (there is no CPU path)"); return FGOICP_ERR_NO_DEVICE; }
         BCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
         ctx.assign(pairs->size(), nullptr);
-        icp_state.assign(pairs->size(), IcpStepState());
+        icp_state.assign(pairs->size(), IcpStepRun());
         for (const PairHost& p : *pairs)
             if (p.inliers) {  // the arena's budget is set aside before any pair enters (room_for_more)
                 size_t free_b = 0, total_b = 0;
@@ -166,7 +166,7 @@ struct HipBatchBackend {
     int init_borrowed(fgoicp_ctx* const* cs, int n) {
         borrowed = true;
         ctx.assign(cs, cs + n);
-        icp_state.assign((size_t)n, IcpStepState());
+        icp_state.assign((size_t)n, IcpStepRun());
         device = n > 0 ? cs[0]->device : 0;
         BCHK(hipSetDevice(device));
         BCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
@@ -411,14 +411,11 @@ struct HipBatchBackend {
     int icp_step(std::vector<BatchIcpReq*>& runs) {
         for (BatchIcpReq* r : runs) BCHK(hipStreamSynchronize(ctx[(size_t)r->pair]->stream));
         for (BatchIcpReq* r : runs) {
-            IcpStepState& s = icp_state[(size_t)r->pair];
+            IcpStepRun& s = icp_state[(size_t)r->pair];
             const int rc = ctx_icp_step(ctx[(size_t)r->pair], s);
             if (rc) return rc;
             if (s.done) {
-                r->sse = s.sse_out;
-                std::memcpy(r->R, s.R_out.m, sizeof(r->R));
-                r->t[0] = s.t_out.x; r->t[1] = s.t_out.y; r->t[2] = s.t_out.z;
-                r->iters = s.iters;
+                s.loop.result(&r->sse, r->R, r->t, &r->iters);
                 r->done = true;
             }
         }

@@ -718,6 +718,8 @@ static void rotate_translate_inplace(PointCloud& pc, const Mat3& R, const Vec3& 
     }
 }
 
+void IterativeClosestPoint3D::move_working(const Mat3& R, const Vec3& t) { rotate_translate_inplace(pcs_buf_, R, t); }
+
 std::tuple<Mat3, Vec3> IterativeClosestPoint3D::procrustes(ProcrustesDebug* dbg) {  // :140-172
     const long ns = (long)pcs_buf_.size();
     const long nt = (long)pct_.size();

@@ -180,6 +180,7 @@ public:
     std::tuple<Mat3, Vec3> procrustes(ProcrustesDebug* dbg = nullptr);
     size_t iterations() const { return iters_; }
     PointCloud& working() { return pcs_buf_; }
+    void move_working(const Mat3& R, const Vec3& t);  // run()'s rotate_translate_inplace on working() (:85, :100)
     std::vector<int>& last_corr_index() { return corr_idx_; }
 private:
     const Registration& reg_;

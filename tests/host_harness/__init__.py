@@ -19,7 +19,8 @@ def build():
     pyoracle.build()
     deps = [os.path.join(_DIR, "harness.cpp"), os.path.join(_REPO, "fast-go-icp_amd/csrc/host/driver.hpp"), os.path.join(_REPO, "fast-go-icp_amd/csrc/device/morton.hpp"),
             os.path.join(_REPO, "fast-go-icp_amd/csrc/host/math3.hpp"), os.path.join(_REPO, "oracle/libgoicp_oracle.so"),
-            os.path.join(_DIR, "oracle_ops.hpp"), os.path.join(_REPO, "fast-go-icp_amd/csrc/device/slab.hpp"), os.path.join(_REPO, "fast-go-icp_amd/csrc/host/knobs.hpp")]
+            os.path.join(_DIR, "oracle_ops.hpp"), os.path.join(_REPO, "fast-go-icp_amd/csrc/device/slab.hpp"), os.path.join(_REPO, "fast-go-icp_amd/csrc/host/knobs.hpp"),
+            os.path.join(_REPO, "fast-go-icp_amd/csrc/host/icp_loop.hpp")]
     if not os.path.exists(_SO) or any(os.path.getmtime(d) > os.path.getmtime(_SO) for d in deps):
         tmp = f"{_SO}.{os.getpid()}.tmp"  # several ranks of a world-size-N test may get here together: build aside, rename atomically
         subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-DFGOICP_DEV_KNOBS", "-fopenmp", "-shared", "-o", tmp,
@@ -126,6 +127,25 @@ def point_order(xyz, leaf=64, mode=2, fine=True):
     L.harness_point_order.restype = None
     L.harness_point_order(_f(xyz), len(xyz), int(leaf), int(mode), int(bool(fine)), perm.ctypes.data_as(C.POINTER(C.c_uint32)))
     return perm
+
+
+def icp_loop(pct, pcs, bounds, lut_res, R0, t0, max_iter, thr, inliers=0, script=None):
+    """csrc/host/icp_loop.hpp over the oracle's procrustes / move_working / compute_sse_error, or over `script` (rows of Rn (3, 3), tn, sse):
+    (sse, R, t, iterations)"""
+    L = lib()
+    L.harness_icp_loop.argtypes = [_fp, C.c_size_t, _fp, C.c_size_t, _fp, C.c_float, C.c_size_t, _fp, C.c_size_t, _fp, _fp, C.c_size_t, C.c_float, _fp, _fp, _fp,
+                                   C.POINTER(C.c_int)]
+    pct = np.ascontiguousarray(pct, np.float32).reshape(-1, 3); pcs = np.ascontiguousarray(pcs, np.float32).reshape(-1, 3)
+    b = np.ascontiguousarray(bounds, np.float32).reshape(6)
+    rows = None if script is None else np.ascontiguousarray([np.concatenate([np.asarray(Rn, np.float32).T.reshape(9), np.asarray(tn, np.float32), [np.float32(e)]])
+                                                             for Rn, tn, e in script], np.float32)
+    R0g = np.ascontiguousarray(np.asarray(R0, np.float32).T).reshape(9); t0 = np.ascontiguousarray(t0, np.float32)
+    sse = C.c_float(); R = np.empty(9, np.float32); t = np.empty(3, np.float32); it = C.c_int()
+    rc = L.harness_icp_loop(_f(pct), len(pct), _f(pcs), len(pcs), _f(b), lut_res, int(inliers), None if rows is None else _f(rows), 0 if rows is None else len(rows),
+                            _f(R0g), _f(t0), int(max_iter), thr, C.byref(sse), _f(R), _f(t), C.byref(it))
+    if rc:
+        raise RuntimeError("the script ran out of steps")
+    return np.float32(sse.value), R.reshape(3, 3).T.copy(), t, int(it.value)
 
 
 def slab_d2(n3, a, b, q):

@@ -4,6 +4,7 @@
 // is never part of libfgoicp_amd.so; the product instantiates the template with HIP only.
 #include "oracle_ops.hpp"
 #include "../../fast-go-icp_amd/csrc/device/slab.hpp"
+#include "../../fast-go-icp_amd/csrc/host/icp_loop.hpp"
 
 using namespace host_harness;
 
@@ -105,6 +106,42 @@ void harness_slab_d2(const float* n3, float a, float b, const float* q_xyz, size
 void harness_point_order(const float* xyz, size_t n, size_t leaf, int mode, int fine, uint32_t* perm_out) {
     const std::vector<uint32_t> p = mode == 3 ? fgoicp::mixed_order(xyz, n, 3, leaf, fine != 0) : mode == 2 ? fgoicp::kd_order(xyz, n, 3, leaf, fine != 0) : fgoicp::morton_order(xyz, n, 3);
     std::memcpy(perm_out, p.data(), sizeof(uint32_t) * n);
+}
+// IcpLoop (csrc/host/icp_loop.hpp) driven with the oracle's own operators in the order IterativeClosestPoint3D::run() applies them: it must
+// return run()'s bits.  script (optional, n_script x 13 floats {Rn[9], tn[3], sse}): the steps come from there instead and no cloud is read.
+int harness_icp_loop(const float* tgt, size_t nt, const float* src, size_t ns, const float* bounds6, float lut_res, size_t inliers, const float* script, size_t n_script,
+                     const float* R0, const float* t0, size_t max_iter, float thr, float* sse, float* R9, float* t3, int* iters) {
+    IcpLoop s;
+    s.begin(R0, t0, max_iter, thr);
+    if (script) {
+        for (size_t k = 0; s.next(); ++k) {
+            if (k >= n_script) return 1;
+            const float* e = script + 13 * k;
+            s.compose(Mat3f::from(e), Vec3f{e[9], e[10], e[11]});
+            s.took(e[12]);
+        }
+    } else {
+        orc::PointCloud pct(nt), pcs(ns);
+        std::memcpy(pct.data(), tgt, sizeof(orc::Vec3) * nt);
+        std::memcpy(pcs.data(), src, sizeof(orc::Vec3) * ns);
+        const orc::Bounds b{std::make_pair(bounds6[0], bounds6[1]), std::make_pair(bounds6[2], bounds6[3]), std::make_pair(bounds6[4], bounds6[5])};
+        orc::Registration reg(pct, pcs, b, lut_res, false);  // neither operator below reads the LUT
+        reg.inliers = inliers;
+        orc::Mat3 Ro;
+        std::memcpy(Ro.c, R0, sizeof(Ro.c));
+        const orc::Vec3 to{t0[0], t0[1], t0[2]};
+        orc::IterativeClosestPoint3D icp(reg, pct, pcs, max_iter, thr, Ro, to);
+        icp.move_working(Ro, to);  // icp3d.cu:85
+        while (s.next()) {
+            auto [Rn, tn] = icp.procrustes();
+            icp.move_working(Rn, tn);  // :100
+            s.compose(Mat3f::from(&Rn.c[0][0]), Vec3f{tn.x, tn.y, tn.z});
+            std::memcpy(Ro.c, s.R.m, sizeof(Ro.c));
+            s.took(reg.compute_sse_error(Ro, orc::Vec3{s.t.x, s.t.y, s.t.z}));  // :103
+        }
+    }
+    s.result(sse, R9, t3, iters);
+    return 0;
 }
 
 }  // extern "C"

@@ -98,6 +98,27 @@ def test_cooperative_trimmed_icp_returns_the_single_gpu_bits(fg, gpu_required, m
         m.close()
 
 
+@pytest.mark.parametrize("max_iter", [0, 1])
+def test_cooperative_icp_without_a_riding_pass_returns_the_single_gpu_bits(fg, gpu_required, max_iter):
+    """The two shortest cooperative runs, scans split over three ranks (fgoicp_ctx_set_coop_split), untrimmed and trimmed: max_iter = 0, the
+    loop's body never runs and nothing is enqueued behind the working cloud; max_iter = 1, pass 1 and one iteration whose scan has no
+    pass of a next iteration riding along.  == fgoicp_icp on one context, bit for bit."""
+    tgt, src, R_gt, t_gt = fg.synth.workload("tiny", angle_deg=25.0, outlier_frac=0.2)
+    R0, t0 = fg.synth.random_rotation(np.random.default_rng(5), 12.0).astype(np.float32), np.array([0.01, -0.02, 0.005], np.float32)
+    for trim in (0.0, 0.2):
+        m = fg.MultiGoICP(tgt, src, 0.05, 1e-3, devices=[0] * 3, transport=fg.TRANSPORT_IN_PROCESS, trim_fraction=trim)
+        for r in range(3):
+            m.registration(r).set_coop_split(0, 0)
+        m.set_record(True)
+        icp = fg.IterativeClosestPoint3D(m.registration(0), None, None, max_iter, 0.005, R0, t0)
+        e1, R1, t1 = icp.run()
+        e, R, t, it = m.icp(R0, t0, max_iter, 0.005)
+        assert it == icp.iterations == max_iter
+        assert m.recorded(0)[1] == 2 * max_iter  # the scans were split: pass 1's correspondences and the iteration's minima were gathered
+        assert np.float32(e).view(np.uint32) == np.float32(e1).view(np.uint32) and np.array_equal(R, R1) and np.array_equal(t, t1), (trim, e, e1)
+        m.close()
+
+
 @pytest.mark.parametrize("world", [2, 3])
 def test_cooperative_rounds_are_the_single_gpu_run(fg, gpu_required, monkeypatch, world):
     """The multi-rank run with cooperative refinements (the default for clouds of at least 131072 source points when the exchange can
