@@ -541,7 +541,7 @@ static int alignment_enqueue(fgoicp_ctx* c, const float* R9, const float* t3, bo
         A.nt16 = (c->nt + 15) & ~(size_t)15;
         const size_t nblk = (c->ns + kBlock - 1) / kBlock;
         const size_t o_idx = 0, o_corr = o_idx + up(4 * c->ns), o_d2 = o_corr + up(4 * c->ns), o_inl = o_d2 + up(4 * c->ns), o_hit = o_inl + up(c->ns),
-                     o_part = o_hit + up(A.nt16), o_sum = o_part + up(sizeof(uint2) * nblk), o_rows = o_sum + 256, o_info = o_rows + up(sizeof(AlignInfoRow) * nblk),
+                     o_part = o_hit + up(A.nt16), o_sum = o_part + up(sizeof(uint2) * nblk), o_rows = o_sum + 256, o_info = o_rows + up(sizeof(MomentRow<kAlignInfoTerms>) * nblk),
                      total = o_info + 256;
         HIPCHK(hipMalloc(&A.base, total));
         char* b = static_cast<char*>(A.base);
@@ -552,7 +552,7 @@ static int alignment_enqueue(fgoicp_ctx* c, const float* R9, const float* t3, bo
         A.d_hit = reinterpret_cast<unsigned char*>(b + o_hit);
         A.d_partials = reinterpret_cast<uint2*>(b + o_part);
         A.d_sum = reinterpret_cast<uint32_t*>(b + o_sum);
-        A.d_info_rows = reinterpret_cast<AlignInfoRow*>(b + o_rows);
+        A.d_info_rows = reinterpret_cast<MomentRow<kAlignInfoTerms>*>(b + o_rows);
         A.d_info = reinterpret_cast<unsigned long long*>(b + o_info);
     }
     hipStream_t st = L.stream;
@@ -638,27 +638,49 @@ int ctx_alignment_information(fgoicp_ctx* c, const float* R9, const float* t3, u
     return rc ? rc : information_copy_out(c, m);
 }
 
+// What the entry points of the target's and the source's normals share.
+// given normals: each checked (finite, not zero) and normalised in fp64 -> {x, y, z, 0}; `where` names the entry point in the message
+static int unit_normals(const char* where, const float* normals, size_t n, std::vector<float4>& out) {
+    out.resize(n);
+    for (size_t i = 0; i < n; ++i) {
+        const double x = normals[3 * i], y = normals[3 * i + 1], z = normals[3 * i + 2];
+        const double len = std::sqrt(x * x + y * y + z * z);
+        if (!std::isfinite(len) || !(len > 0.0)) {
+            set_error(std::string(where) + ": normal " + std::to_string(i) + " is zero or not finite");
+            return FGOICP_ERR_INVALID_ARG;
+        }
+        out[i] = make_float4((float)(x / len), (float)(y / len), (float)(z / len), 0.f);
+    }
+    return FGOICP_OK;
+}
+// the neighbour count of target_knn_kernel over a cloud ("target" / "source") of n points
+static int knn_k_ok(const char* where, int k, size_t n, const char* cloud) {
+    if (k >= kKnnMin && k <= kKnnMax && (size_t)k <= n) return FGOICP_OK;
+    set_error(std::string(where) + ": k must lie in [4, 32] and be at most the number of " + cloud + " points");
+    return FGOICP_ERR_INVALID_ARG;
+}
+// out[3 * (perm ? perm[i] : i) ..] = the three floats of the device's d[i], i < n, behind the work queued on lane 0
+static int read_back_xyz(fgoicp_ctx* c, const float4* d, size_t n, const uint32_t* perm, float* out) {
+    HIPCHK(hipSetDevice(c->device));
+    std::vector<float4> h(n);
+    HIPCHK(hipStreamSynchronize(c->lanes[0].stream));
+    HIPCHK(hipMemcpy(h.data(), d, sizeof(float4) * n, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i) {
+        float* o = out + 3 * (perm ? (size_t)perm[i] : i);
+        o[0] = h[i].x; o[1] = h[i].y; o[2] = h[i].z;
+    }
+    return FGOICP_OK;
+}
+
 // EXTENSION: target normals (fgoicp_ctx_set_target_normals).  Given: checked and normalised on the host (fp64), uploaded.  Estimated:
 // target_knn_kernel over the target's own tree, one launch.
 int ctx_set_target_normals(fgoicp_ctx* c, const float* normals, int k) {
     const size_t nt = c->nt;
     std::vector<float4> h;
     if (normals) {
-        h.resize(nt);
-        for (size_t i = 0; i < nt; ++i) {
-            const double x = normals[3 * i], y = normals[3 * i + 1], z = normals[3 * i + 2];
-            const double len = std::sqrt(x * x + y * y + z * z);
-            if (!std::isfinite(len) || !(len > 0.0)) {
-                set_error("fgoicp_ctx_set_target_normals: normal " + std::to_string(i) + " is zero or not finite");
-                return FGOICP_ERR_INVALID_ARG;
-            }
-            h[i] = make_float4((float)(x / len), (float)(y / len), (float)(z / len), 0.f);
-        }
+        if (int rc = unit_normals("fgoicp_ctx_set_target_normals", normals, nt, h)) return rc;
     } else {
-        if (k < kKnnMin || k > kKnnMax || (size_t)k > nt) {
-            set_error("fgoicp_ctx_set_target_normals: k must lie in [4, 32] and be at most the number of target points");
-            return FGOICP_ERR_INVALID_ARG;
-        }
+        if (int rc = knn_k_ok("fgoicp_ctx_set_target_normals", k, nt, "target")) return rc;
         if (c->brute_force_nn) { set_error("fgoicp_ctx_set_target_normals: estimating normals needs the search tree, which a brute-force context does not build: pass normals"); return FGOICP_ERR_INVALID_ARG; }
     }
     HIPCHK(hipSetDevice(c->device));
@@ -678,15 +700,10 @@ int ctx_set_target_normals(fgoicp_ctx* c, const float* normals, int k) {
 }
 int ctx_target_normals(fgoicp_ctx* c, float* out) {
     if (!c->normals_set) { set_error("fgoicp_target_normals: the target normals are not set (fgoicp_ctx_set_target_normals)"); return FGOICP_ERR_INVALID_ARG; }
-    HIPCHK(hipSetDevice(c->device));
-    std::vector<float4> h(c->nt);
-    HIPCHK(hipStreamSynchronize(c->lanes[0].stream));
-    HIPCHK(hipMemcpy(h.data(), c->d_normals, sizeof(float4) * c->nt, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < c->nt; ++i) { out[3 * i] = h[i].x; out[3 * i + 1] = h[i].y; out[3 * i + 2] = h[i].z; }
-    return FGOICP_OK;
+    return read_back_xyz(c, c->d_normals, c->nt, nullptr, out);
 }
 int ctx_target_knn(fgoicp_ctx* c, int k, uint32_t* idx, float* d2) {
-    if (k < kKnnMin || k > kKnnMax || (size_t)k > c->nt) { set_error("fgoicp_target_knn: k must lie in [4, 32] and be at most the number of target points"); return FGOICP_ERR_INVALID_ARG; }
+    if (int rc = knn_k_ok("fgoicp_target_knn", k, c->nt, "target")) return rc;
     if (c->brute_force_nn) { set_error("fgoicp_target_knn: needs the search tree, which a brute-force context does not build"); return FGOICP_ERR_INVALID_ARG; }
     HIPCHK(hipSetDevice(c->device));
     const size_t n = c->nt * (size_t)k;
@@ -716,7 +733,7 @@ static int moments_at(fgoicp_ctx* c, const float* R9, const float* t3, float max
     HIPCHK(hipSetDevice(c->device));
     if (!c->d_plane_rows) {
         const size_t nblk = (c->ns + kBlock - 1) / kBlock;
-        HIPCHK(hipMalloc(&c->d_plane_rows, sizeof(PlaneRow) * nblk));
+        HIPCHK(hipMalloc(&c->d_plane_rows, sizeof(MomentRow<kPlaneTerms>) * nblk));
         HIPCHK(hipMalloc(&c->d_plane_out, sizeof(unsigned long long) * (1 + kPlaneTerms)));
     }
     const int rc = alignment_enqueue(c, R9, t3, true);
@@ -802,23 +819,12 @@ int ctx_set_source_normals(fgoicp_ctx* c, const float* normals, int k) {
     const size_t ns = c->ns;
     std::vector<float4> h;
     if (normals) {
+        std::vector<float4> caller;
+        if (int rc = unit_normals("fgoicp_ctx_set_source_normals", normals, ns, caller)) return rc;
         h.resize(ns);
-        std::vector<float4> caller(ns);
-        for (size_t i = 0; i < ns; ++i) {
-            const double x = normals[3 * i], y = normals[3 * i + 1], z = normals[3 * i + 2];
-            const double len = std::sqrt(x * x + y * y + z * z);
-            if (!std::isfinite(len) || !(len > 0.0)) {
-                set_error("fgoicp_ctx_set_source_normals: normal " + std::to_string(i) + " is zero or not finite");
-                return FGOICP_ERR_INVALID_ARG;
-            }
-            caller[i] = make_float4((float)(x / len), (float)(y / len), (float)(z / len), 0.f);
-        }
         for (size_t i = 0; i < ns; ++i) h[i] = caller[c->perm[i]];
     } else {
-        if (k < kKnnMin || k > kKnnMax || (size_t)k > ns) {
-            set_error("fgoicp_ctx_set_source_normals: k must lie in [4, 32] and be at most the number of source points");
-            return FGOICP_ERR_INVALID_ARG;
-        }
+        if (int rc = knn_k_ok("fgoicp_ctx_set_source_normals", k, ns, "source")) return rc;
         if (c->brute_force_nn) { set_error("fgoicp_ctx_set_source_normals: estimating normals needs the search tree, which a brute-force context does not build: pass normals"); return FGOICP_ERR_INVALID_ARG; }
     }
     HIPCHK(hipSetDevice(c->device));
@@ -855,15 +861,7 @@ int ctx_set_source_normals(fgoicp_ctx* c, const float* normals, int k) {
 }
 int ctx_source_normals(fgoicp_ctx* c, float* out) {
     if (!c->src_normals_set) { set_error("fgoicp_source_normals: the source normals are not set (fgoicp_ctx_set_source_normals)"); return FGOICP_ERR_INVALID_ARG; }
-    HIPCHK(hipSetDevice(c->device));
-    std::vector<float4> h(c->ns);
-    HIPCHK(hipStreamSynchronize(c->lanes[0].stream));
-    HIPCHK(hipMemcpy(h.data(), c->d_src_normals, sizeof(float4) * c->ns, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < c->ns; ++i) {
-        float* o = out + 3 * (size_t)c->perm[i];
-        o[0] = h[i].x; o[1] = h[i].y; o[2] = h[i].z;
-    }
-    return FGOICP_OK;
+    return read_back_xyz(c, c->d_src_normals, c->ns, c->perm.data(), out);
 }
 
 // IterativeClosestPoint3D::procrustes() on L.d_work — icp3d.cu:140-172.  The device half (enqueue only), itself in two halves: the correspondences

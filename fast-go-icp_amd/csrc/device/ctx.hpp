@@ -124,7 +124,7 @@ struct fgoicp_ctx {
         uint2* d_partials = nullptr;
         uint32_t* d_sum = nullptr;               // {inliers, targets hit, bits of the largest inlier squared distance}
         size_t nt16 = 0;
-        fgoicp::AlignInfoRow* d_info_rows = nullptr;   // the moments: one row of partial sums per block of the report
+        fgoicp::MomentRow<fgoicp::kAlignInfoTerms>* d_info_rows = nullptr;   // the moments: one row of partial sums per block of the report
         unsigned long long* d_info = nullptr;    // {count, the bits of ten sums} (launch_align_info)
     } align;
 
@@ -132,7 +132,7 @@ struct fgoicp_ctx {
     // that needs it — 16 bytes per target point, 232 per block of kBlock source points
     float4* d_normals = nullptr;             // nt x {n.x, n.y, n.z, 0}, caller order; the zero vector: no normal
     bool normals_set = false;
-    fgoicp::PlaneRow* d_plane_rows = nullptr;
+    fgoicp::MomentRow<fgoicp::kPlaneTerms>* d_plane_rows = nullptr;
     unsigned long long* d_plane_out = nullptr;   // {count, the bits of 28 sums} (launch_plane_moments)
     // source normals of the Generalized-ICP refinement (ctx_set_source_normals): allocated by the first call, 16 bytes per source point
     float4* d_src_normals = nullptr;         // ns x {n.x, n.y, n.z, 0}, DEVICE SLOT order (perm); the zero vector: no normal

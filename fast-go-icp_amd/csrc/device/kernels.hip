@@ -2515,23 +2515,12 @@ void launch_align_scatter(const uint32_t* idx, const uint32_t* min_bits, const u
 // caller indices i with inlier[i] != 0, d2[i] <= max_d2 and corr[i] < nt.  One thread per caller index: three coalesced reads of the
 // report's arrays (9 bytes), one 16-byte gather of the target point q the correspondence names, the ten terms {q (3), q q^T (6, in the
 // order xx xy xz yy yz zz), d2} in fp64 — a product of two floats is exact in a double, so the only roundings are those of the sums,
-// and their order is fixed: a butterfly over the wave (both operands of every addition are the same pair whichever lane adds them, so
-// all lanes end with the same bits), waves 0..3 of the block in that order, one row per block; align_info_fold_kernel adds the rows
-// t, t + 1024, ... in thread t, then the same tree.  No atomics: the result does not depend on the order in which blocks arrive.
+// and their order is fixed (fixed_sum.hpp: block_moment_row, then moment_fold_kernel).  No atomics: the result does not depend on the
+// order in which blocks arrive.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ double wave_xor_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const int lo = __shfl_xor(__double2loint(v), off, 64), hi = __shfl_xor(__double2hiint(v), off, 64);
-        v += __hiloint2double(hi, lo);
-    }
-    return v;
-}
 __global__ __launch_bounds__(kBlock) void align_info_kernel(const unsigned char* __restrict__ inlier, const float* __restrict__ d2,
                                                             const uint32_t* __restrict__ corr, const float4* __restrict__ tgt, int n, int nt, float max_d2,
-                                                            AlignInfoRow* __restrict__ rows) {
-    __shared__ double s_v[kBlock / 64][kAlignInfoTerms];
-    __shared__ unsigned s_cnt[kBlock / 64];
+                                                            MomentRow<kAlignInfoTerms>* __restrict__ rows) {
     const int i = blockIdx.x * kBlock + threadIdx.x;
     double v[kAlignInfoTerms];
 #pragma unroll
@@ -2549,75 +2538,14 @@ __global__ __launch_bounds__(kBlock) void align_info_kernel(const unsigned char*
             cnt = 1u;
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
-#pragma unroll
-    for (int k = 0; k < kAlignInfoTerms; ++k) v[k] = wave_xor_sum(v[k]);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-        s_cnt[wave] = cnt;
-#pragma unroll
-        for (int k = 0; k < kAlignInfoTerms; ++k) s_v[wave][k] = v[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < kAlignInfoTerms) {
-        double r = s_v[0][threadIdx.x];
-#pragma unroll
-        for (int w = 1; w < kBlock / 64; ++w) r += s_v[w][threadIdx.x];
-        rows[blockIdx.x].v[threadIdx.x] = r;
-    }
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int w = 1; w < kBlock / 64; ++w) cnt += s_cnt[w];
-        rows[blockIdx.x].count = cnt;
-        rows[blockIdx.x].pad = 0u;
-    }
-}
-// One block of 1024 threads: out = {counted correspondences (one 64-bit integer), the ten sums}.
-__global__ __launch_bounds__(1024) void align_info_fold_kernel(const AlignInfoRow* __restrict__ rows, int nrows, unsigned long long* __restrict__ out) {
-    __shared__ double s_v[16][kAlignInfoTerms];
-    __shared__ unsigned long long s_cnt[16];
-    double v[kAlignInfoTerms];
-#pragma unroll
-    for (int k = 0; k < kAlignInfoTerms; ++k) v[k] = 0.0;
-    unsigned long long cnt = 0ull;
-    for (int b = threadIdx.x; b < nrows; b += 1024) {
-        cnt += rows[b].count;
-#pragma unroll
-        for (int k = 0; k < kAlignInfoTerms; ++k) v[k] += rows[b].v[k];
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned lo = __shfl_xor((unsigned)cnt, off, 64), hi = __shfl_xor((unsigned)(cnt >> 32), off, 64);
-        cnt += ((unsigned long long)hi << 32) | lo;
-    }
-#pragma unroll
-    for (int k = 0; k < kAlignInfoTerms; ++k) v[k] = wave_xor_sum(v[k]);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-        s_cnt[wave] = cnt;
-#pragma unroll
-        for (int k = 0; k < kAlignInfoTerms; ++k) s_v[wave][k] = v[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < kAlignInfoTerms) {
-        double r = s_v[0][threadIdx.x];
-#pragma unroll
-        for (int w = 1; w < 16; ++w) r += s_v[w][threadIdx.x];
-        out[1 + threadIdx.x] = (unsigned long long)__double_as_longlong(r);
-    }
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int w = 1; w < 16; ++w) cnt += s_cnt[w];
-        out[0] = cnt;
-    }
+    block_moment_row<kBlock / 64>(v, cnt, &rows[blockIdx.x]);
 }
 
-void launch_align_info(const unsigned char* inlier, const float* d2, const uint32_t* corr, const float4* tgt, int n, int nt, float max_d2, AlignInfoRow* rows,
+void launch_align_info(const unsigned char* inlier, const float* d2, const uint32_t* corr, const float4* tgt, int n, int nt, float max_d2, MomentRow<kAlignInfoTerms>* rows,
                        unsigned long long* out11, hipStream_t s) {
     const int nb = (n + kBlock - 1) / kBlock;
     hipLaunchKernelGGL(align_info_kernel, dim3(nb), dim3(kBlock), 0, s, inlier, d2, corr, tgt, n, nt, max_d2, rows);
-    hipLaunchKernelGGL(align_info_fold_kernel, dim3(1), dim3(1024), 0, s, rows, nb, out11);
+    hipLaunchKernelGGL(moment_fold_kernel<kAlignInfoTerms>, dim3(1), dim3(1024), 0, s, rows, nb, out11);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2762,113 +2690,56 @@ void launch_outlier_knn(const BvhView& t, int nt, int k, double* mean_dist, floa
 // entries of o.  COUNTED are the o with inlier[o] != 0, d2[o] <= max_d2, corr[o] < nt and a non-zero normal at corr[o].  With q the target
 // point corr[o], n its normal: r = n.(x - q), J = [ (x cross n)^T, n^T ] (twist order wx wy wz vx vy vz); every term is formed in fp64
 // from the fp32 inputs.  Reduced: the upper triangle of sum J^T J row by row (21), sum J^T r (6), sum r^2 (1), and the count — in
-// align_info_kernel's fixed order (wave butterfly, waves 0..3, one row per block; the fold adds rows t, t + 1024, ... in thread t, then
-// the same tree).  No atomics: the same arrays give the same bytes.  Every term is even in n: the sign of a normal does not matter.
+// the fixed order of fixed_sum.hpp (block_moment_row, then moment_fold_kernel).  No atomics: the same arrays give the same bytes.  Every
+// term is even in n: the sign of a normal does not matter.
 // ---------------------------------------------------------------------------------------------
+// The counted-set gate of plane_moments_kernel and gicp_moments_kernel for the caller index o of a device slot, and the gathers behind it:
+// true with nn = the target normal and q = the target point at corr[o]
+__device__ __forceinline__ bool nonzero3(const float4& a) { return a.x != 0.0f || a.y != 0.0f || a.z != 0.0f; }
+__device__ __forceinline__ bool counted_pair(uint32_t o, const unsigned char* __restrict__ inlier, const float* __restrict__ d2, const uint32_t* __restrict__ corr,
+                                             const float4* __restrict__ tgt, const float4* __restrict__ normals, int n, int nt, float max_d2, float4& nn, float4& q) {
+    if (!(o < (uint32_t)n)) return false;
+    const uint32_t j = corr[o];
+    if (!(inlier[o] != 0 && d2[o] <= max_d2 && j < (uint32_t)nt)) return false;
+    nn = normals[j];
+    if (!nonzero3(nn)) return false;
+    q = tgt[j];
+    return true;
+}
 __global__ __launch_bounds__(kBlock) void plane_moments_kernel(const float4* __restrict__ moved, const uint32_t* __restrict__ orig_of_slot,
                                                                const unsigned char* __restrict__ inlier, const float* __restrict__ d2,
                                                                const uint32_t* __restrict__ corr, const float4* __restrict__ tgt,
-                                                               const float4* __restrict__ normals, int n, int nt, float max_d2, PlaneRow* __restrict__ rows) {
-    __shared__ double s_v[kBlock / 64][kPlaneTerms];
-    __shared__ unsigned s_cnt[kBlock / 64];
+                                                               const float4* __restrict__ normals, int n, int nt, float max_d2,
+                                                               MomentRow<kPlaneTerms>* __restrict__ rows) {
     const int i = blockIdx.x * kBlock + threadIdx.x;
     double v[kPlaneTerms];
 #pragma unroll
     for (int k = 0; k < kPlaneTerms; ++k) v[k] = 0.0;
     unsigned cnt = 0u;
-    if (i < n) {
-        const uint32_t o = orig_of_slot[i];
-        if (o < (uint32_t)n) {
-            const uint32_t j = corr[o];
-            if (inlier[o] != 0 && d2[o] <= max_d2 && j < (uint32_t)nt) {
-                const float4 nn = normals[j];
-                if (nn.x != 0.0f || nn.y != 0.0f || nn.z != 0.0f) {
-                    const float4 x = moved[i], q = tgt[j];
-                    const double X[3] = {(double)x.x, (double)x.y, (double)x.z}, N[3] = {(double)nn.x, (double)nn.y, (double)nn.z};
-                    const double r = N[0] * (X[0] - (double)q.x) + N[1] * (X[1] - (double)q.y) + N[2] * (X[2] - (double)q.z);
-                    const double J[6] = {X[1] * N[2] - X[2] * N[1], X[2] * N[0] - X[0] * N[2], X[0] * N[1] - X[1] * N[0], N[0], N[1], N[2]};
-                    int m = 0;
+    float4 nn, q;
+    if (i < n && counted_pair(orig_of_slot[i], inlier, d2, corr, tgt, normals, n, nt, max_d2, nn, q)) {
+        const float4 x = moved[i];
+        const double X[3] = {(double)x.x, (double)x.y, (double)x.z}, N[3] = {(double)nn.x, (double)nn.y, (double)nn.z};
+        const double r = N[0] * (X[0] - (double)q.x) + N[1] * (X[1] - (double)q.y) + N[2] * (X[2] - (double)q.z);
+        const double J[6] = {X[1] * N[2] - X[2] * N[1], X[2] * N[0] - X[0] * N[2], X[0] * N[1] - X[1] * N[0], N[0], N[1], N[2]};
+        int m = 0;
 #pragma unroll
-                    for (int a = 0; a < 6; ++a)
+        for (int a = 0; a < 6; ++a)
 #pragma unroll
-                        for (int b = a; b < 6; ++b) v[m++] = J[a] * J[b];
+            for (int b = a; b < 6; ++b) v[m++] = J[a] * J[b];
 #pragma unroll
-                    for (int a = 0; a < 6; ++a) v[21 + a] = J[a] * r;
-                    v[27] = r * r;
-                    cnt = 1u;
-                }
-            }
-        }
+        for (int a = 0; a < 6; ++a) v[21 + a] = J[a] * r;
+        v[27] = r * r;
+        cnt = 1u;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
-#pragma unroll
-    for (int k = 0; k < kPlaneTerms; ++k) v[k] = wave_xor_sum(v[k]);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-        s_cnt[wave] = cnt;
-#pragma unroll
-        for (int k = 0; k < kPlaneTerms; ++k) s_v[wave][k] = v[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < kPlaneTerms) {
-        double r = s_v[0][threadIdx.x];
-#pragma unroll
-        for (int w = 1; w < kBlock / 64; ++w) r += s_v[w][threadIdx.x];
-        rows[blockIdx.x].v[threadIdx.x] = r;
-    }
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int w = 1; w < kBlock / 64; ++w) cnt += s_cnt[w];
-        rows[blockIdx.x].count = cnt;
-        rows[blockIdx.x].pad = 0u;
-    }
-}
-// One block of 1024 threads: out = {counted correspondences (one 64-bit integer), the bits of the 28 sums}.
-__global__ __launch_bounds__(1024) void plane_moments_fold_kernel(const PlaneRow* __restrict__ rows, int nrows, unsigned long long* __restrict__ out) {
-    __shared__ double s_v[16][kPlaneTerms];
-    __shared__ unsigned long long s_cnt[16];
-    double v[kPlaneTerms];
-#pragma unroll
-    for (int k = 0; k < kPlaneTerms; ++k) v[k] = 0.0;
-    unsigned long long cnt = 0ull;
-    for (int b = threadIdx.x; b < nrows; b += 1024) {
-        cnt += rows[b].count;
-#pragma unroll
-        for (int k = 0; k < kPlaneTerms; ++k) v[k] += rows[b].v[k];
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned lo = __shfl_xor((unsigned)cnt, off, 64), hi = __shfl_xor((unsigned)(cnt >> 32), off, 64);
-        cnt += ((unsigned long long)hi << 32) | lo;
-    }
-#pragma unroll
-    for (int k = 0; k < kPlaneTerms; ++k) v[k] = wave_xor_sum(v[k]);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-        s_cnt[wave] = cnt;
-#pragma unroll
-        for (int k = 0; k < kPlaneTerms; ++k) s_v[wave][k] = v[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < kPlaneTerms) {
-        double r = s_v[0][threadIdx.x];
-#pragma unroll
-        for (int w = 1; w < 16; ++w) r += s_v[w][threadIdx.x];
-        out[1 + threadIdx.x] = (unsigned long long)__double_as_longlong(r);
-    }
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int w = 1; w < 16; ++w) cnt += s_cnt[w];
-        out[0] = cnt;
-    }
+    block_moment_row<kBlock / 64>(v, cnt, &rows[blockIdx.x]);
 }
 
 void launch_plane_moments(const float4* moved, const uint32_t* orig_of_slot, const unsigned char* inlier, const float* d2, const uint32_t* corr, const float4* tgt,
-                          const float4* normals, int n, int nt, float max_d2, PlaneRow* rows, unsigned long long* out29, hipStream_t s) {
+                          const float4* normals, int n, int nt, float max_d2, MomentRow<kPlaneTerms>* rows, unsigned long long* out29, hipStream_t s) {
     const int nb = (n + kBlock - 1) / kBlock;
     hipLaunchKernelGGL(plane_moments_kernel, dim3(nb), dim3(kBlock), 0, s, moved, orig_of_slot, inlier, d2, corr, tgt, normals, n, nt, max_d2, rows);
-    hipLaunchKernelGGL(plane_moments_fold_kernel, dim3(1), dim3(1024), 0, s, rows, nb, out29);
+    hipLaunchKernelGGL(moment_fold_kernel<kPlaneTerms>, dim3(1), dim3(1024), 0, s, rows, nb, out29);
 }
 
 
@@ -2877,16 +2748,14 @@ void launch_plane_moments(const float4* moved, const uint32_t* orig_of_slot, con
 // SOURCE normals in device slot order (a coalesced read like `moved`).  One thread per device slot i; COUNTED are plane_moments_kernel's
 // caller indices whose own source normal is non-zero too.  The per-pair arithmetic — m = R n_p, S = 2 I - (1 - eps)(n_q n_q^T + m m^T),
 // M = adj(S) / det(S), the 28 terms of J^T M J, J^T M d, d^T M d with J = [ -[x]x | I ] — is gicp_pair_terms (host/gicp.hpp), the text
-// fgoicp_gicp_terms runs on the host.  The reduction is plane_moments_kernel's, addition for addition, and the fold is
-// plane_moments_fold_kernel itself.  No atomics.  Every term is even in n_q and in n_p.
+// fgoicp_gicp_terms runs on the host.  The reduction is plane_moments_kernel's: block_moment_row, then
+// moment_fold_kernel.  No atomics.  Every term is even in n_q and in n_p.
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void gicp_moments_kernel(const float4* __restrict__ moved, const uint32_t* __restrict__ orig_of_slot,
                                                               const unsigned char* __restrict__ inlier, const float* __restrict__ d2,
                                                               const uint32_t* __restrict__ corr, const float4* __restrict__ tgt,
                                                               const float4* __restrict__ normals, const float4* __restrict__ src_normals, Rt rt, double eps, int n,
-                                                              int nt, float max_d2, PlaneRow* __restrict__ rows) {
-    __shared__ double s_v[kBlock / 64][kPlaneTerms];
-    __shared__ unsigned s_cnt[kBlock / 64];
+                                                              int nt, float max_d2, MomentRow<kPlaneTerms>* __restrict__ rows) {
     const int i = blockIdx.x * kBlock + threadIdx.x;
     double v[kPlaneTerms];
 #pragma unroll
@@ -2895,52 +2764,25 @@ __global__ __launch_bounds__(kBlock) void gicp_moments_kernel(const float4* __re
     if (i < n) {
         const uint32_t o = orig_of_slot[i];
         const float4 x = moved[i], np = src_normals[i];
-        if (o < (uint32_t)n && (np.x != 0.0f || np.y != 0.0f || np.z != 0.0f)) {
-            const uint32_t j = corr[o];
-            if (inlier[o] != 0 && d2[o] <= max_d2 && j < (uint32_t)nt) {
-                const float4 nn = normals[j];
-                if (nn.x != 0.0f || nn.y != 0.0f || nn.z != 0.0f) {
-                    const float4 q = tgt[j];
-                    const double X[3] = {(double)x.x, (double)x.y, (double)x.z}, Q[3] = {(double)q.x, (double)q.y, (double)q.z};
-                    const double NQ[3] = {(double)nn.x, (double)nn.y, (double)nn.z}, NP[3] = {(double)np.x, (double)np.y, (double)np.z};
-                    gicp_pair_terms(X, Q, NQ, NP, rt.R, eps, nullptr, v);
-                    cnt = 1u;
-                }
-            }
+        float4 nn, q;
+        if (nonzero3(np) && counted_pair(o, inlier, d2, corr, tgt, normals, n, nt, max_d2, nn, q)) {
+            const double X[3] = {(double)x.x, (double)x.y, (double)x.z}, Q[3] = {(double)q.x, (double)q.y, (double)q.z};
+            const double NQ[3] = {(double)nn.x, (double)nn.y, (double)nn.z}, NP[3] = {(double)np.x, (double)np.y, (double)np.z};
+            gicp_pair_terms(X, Q, NQ, NP, rt.R, eps, nullptr, v);
+            cnt = 1u;
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
-#pragma unroll
-    for (int k = 0; k < kPlaneTerms; ++k) v[k] = wave_xor_sum(v[k]);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-        s_cnt[wave] = cnt;
-#pragma unroll
-        for (int k = 0; k < kPlaneTerms; ++k) s_v[wave][k] = v[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < kPlaneTerms) {
-        double r = s_v[0][threadIdx.x];
-#pragma unroll
-        for (int w = 1; w < kBlock / 64; ++w) r += s_v[w][threadIdx.x];
-        rows[blockIdx.x].v[threadIdx.x] = r;
-    }
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int w = 1; w < kBlock / 64; ++w) cnt += s_cnt[w];
-        rows[blockIdx.x].count = cnt;
-        rows[blockIdx.x].pad = 0u;
-    }
+    block_moment_row<kBlock / 64>(v, cnt, &rows[blockIdx.x]);
 }
 
+
 void launch_gicp_moments(const float4* moved, const uint32_t* orig_of_slot, const unsigned char* inlier, const float* d2, const uint32_t* corr, const float4* tgt,
-                         const float4* normals, const float4* src_normals, const float* R9, double eps, int n, int nt, float max_d2, PlaneRow* rows,
+                         const float4* normals, const float4* src_normals, const float* R9, double eps, int n, int nt, float max_d2, MomentRow<kPlaneTerms>* rows,
                          unsigned long long* out29, hipStream_t s) {
     const int nb = (n + kBlock - 1) / kBlock;
     hipLaunchKernelGGL(gicp_moments_kernel, dim3(nb), dim3(kBlock), 0, s, moved, orig_of_slot, inlier, d2, corr, tgt, normals, src_normals, make_rt(R9, nullptr), eps, n, nt,
                        max_d2, rows);
-    hipLaunchKernelGGL(plane_moments_fold_kernel, dim3(1), dim3(1024), 0, s, rows, nb, out29);
+    hipLaunchKernelGGL(moment_fold_kernel<kPlaneTerms>, dim3(1), dim3(1024), 0, s, rows, nb, out29);
 }
 
 // out[i] = in[orig_of_slot[i]]: per-point data from caller order into device slot order (the source normals: target_knn_kernel writes them

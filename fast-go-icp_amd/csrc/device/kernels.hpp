@@ -6,6 +6,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "fixed_sum.hpp"
+
 namespace fgoicp {
 
 struct BvhView;
@@ -121,16 +123,12 @@ void launch_inlier_mask(const float* d2, int n, int k, uint32_t* sel_info, uint3
 // largest inlier squared distance}
 void launch_align_scatter(const uint32_t* idx, const uint32_t* min_bits, const unsigned char* use, const uint32_t* orig_of_slot, int n, int nt, uint32_t* corr_out,
                           float* d2_out, unsigned char* inlier_out, unsigned char* target_hit, size_t nt16, uint2* partials, uint32_t* summary3, hipStream_t s);
-// The information matrix's moments (fgoicp_information; kernels.hip align_info_kernel, align_info_fold_kernel) over the report's arrays in caller
+// The information matrix's moments (fgoicp_information; kernels.hip align_info_kernel, fixed_sum.hpp moment_fold_kernel) over the report's arrays in caller
 // order: the counted correspondences are the i with inlier[i] != 0, d2[i] <= max_d2 and corr[i] < nt.  rows: ceil(n / kBlock) entries;
 // out11 = {count, sum q (3), sum q q^T (xx xy xz yy yz zz), sum d2} — the count a 64-bit integer, the rest the bits of doubles.  Fixed
 // order of every addition: the same arrays give the same bits.
 constexpr int kAlignInfoTerms = 10;
-struct AlignInfoRow {
-    uint32_t count, pad;
-    double v[kAlignInfoTerms];
-};
-void launch_align_info(const unsigned char* inlier, const float* d2, const uint32_t* corr, const float4* tgt, int n, int nt, float max_d2, AlignInfoRow* rows,
+void launch_align_info(const unsigned char* inlier, const float* d2, const uint32_t* corr, const float4* tgt, int n, int nt, float max_d2, MomentRow<kAlignInfoTerms>* rows,
                        unsigned long long* out11, hipStream_t s);
 // Target normals (fgoicp_ctx_set_target_normals, fgoicp_target_knn; kernels.hip target_knn_kernel): per target point its k nearest target points
 // (itself included) by the total order (bits of the fp32 squared distance, caller index), and the unit direction of least variance of
@@ -143,23 +141,19 @@ void launch_target_knn(const BvhView& t, const float4* tgt, int nt, int k, uint3
 // 2 <= k <= 32, k <= nt.
 constexpr int kOutlierKnnMin = 2;
 void launch_outlier_knn(const BvhView& t, int nt, int k, double* mean_dist, float* kth_dist2, hipStream_t s);
-// The point-to-plane normal equations (fgoicp_plane_moments; kernels.hip plane_moments_kernel, plane_moments_fold_kernel) over the report's
+// The point-to-plane normal equations (fgoicp_plane_moments; kernels.hip plane_moments_kernel, fixed_sum.hpp moment_fold_kernel) over the report's
 // arrays (caller order) and the moved queries of its index scan (device order, `moved`): counted are the caller indices with inlier != 0,
 // d2 <= max_d2, corr < nt and a non-zero normal at corr.  rows: ceil(n / kBlock) entries; out29 = {count, the bits of 28 doubles: the
 // upper triangle of sum J^T J row by row (21), sum J^T r (6), sum r^2}.  Fixed order of every addition.
 constexpr int kPlaneTerms = 28;
-struct PlaneRow {
-    uint32_t count, pad;
-    double v[kPlaneTerms];
-};
 void launch_plane_moments(const float4* moved, const uint32_t* orig_of_slot, const unsigned char* inlier, const float* d2, const uint32_t* corr, const float4* tgt,
-                          const float4* normals, int n, int nt, float max_d2, PlaneRow* rows, unsigned long long* out29, hipStream_t s);
-// The Generalized-ICP normal equations (fgoicp_gicp_moments; kernels.hip gicp_moments_kernel, then plane_moments_fold_kernel): as
+                          const float4* normals, int n, int nt, float max_d2, MomentRow<kPlaneTerms>* rows, unsigned long long* out29, hipStream_t s);
+// The Generalized-ICP normal equations (fgoicp_gicp_moments; kernels.hip gicp_moments_kernel, then moment_fold_kernel): as
 // launch_plane_moments, with src_normals = the source normals in DEVICE SLOT order (n x {n.x, n.y, n.z, 0}; a zero vector takes its point
 // out of the counted set), R9 the rotation of the pose `moved` was formed with (glm order) and eps in (0, 1].  out29 = {count, the bits of
 // 28 doubles: the upper triangle of sum J^T M J row by row (21), sum J^T M d (6), sum d^T M d} (host/gicp.hpp).  Fixed order of every addition.
 void launch_gicp_moments(const float4* moved, const uint32_t* orig_of_slot, const unsigned char* inlier, const float* d2, const uint32_t* corr, const float4* tgt,
-                         const float4* normals, const float4* src_normals, const float* R9, double eps, int n, int nt, float max_d2, PlaneRow* rows,
+                         const float4* normals, const float4* src_normals, const float* R9, double eps, int n, int nt, float max_d2, MomentRow<kPlaneTerms>* rows,
                          unsigned long long* out29, hipStream_t s);
 // out[i] = in[orig_of_slot[i]], i < n: caller order -> device slot order
 void launch_slot_order(const float4* in, const uint32_t* orig_of_slot, int n, float4* out, hipStream_t s);

@@ -9,10 +9,9 @@
 //   scan      rocPRIM exclusive scan of the flags: the output row of every kept point
 //   scatter   out_xyz[row] = the point's three floats, kept_index[row] = i: stable, the rows are in caller order
 //
-// Every sum is a function of n alone: a block of 256 consecutive caller indices is joined by the xor butterfly over each wave (both operands
-// of every addition are the same pair whichever lane adds them, as align_info_kernel in kernels.hip), waves 0..3 in that order, one row
-// per block; the fold's thread t adds rows t, t + 1024, ... in that order — any number of rows — then the same tree over its 16 waves.
-// No floating-point atomics.
+// Every sum is a function of n alone, in the fixed order of fixed_sum.hpp with one term and no count: a block of 256 consecutive caller
+// indices is joined by wave_xor_sum over each wave and waves_in_order over its four waves, one row per block; the fold's thread t adds
+// rows t, t + 1024, ... in that order — any number of rows — then the same two steps over its 16 waves.  No floating-point atomics.
 #include <hip/hip_runtime.h>
 
 #include <rocprim/device/device_scan.hpp>
@@ -34,15 +33,6 @@ namespace {
 
 constexpr int kOutBlock = 256;
 
-__device__ __forceinline__ double out_wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const int lo = __shfl_xor(__double2loint(v), off, 64), hi = __shfl_xor(__double2hiint(v), off, 64);
-        v += __hiloint2double(hi, lo);
-    }
-    return v;
-}
-
 // rows[block] = the sum over the block's caller indices of m[i] (squared == 0) or (m[i] - mean)^2 (squared != 0); indices >= n add 0
 __global__ __launch_bounds__(kOutBlock) void outlier_rows_kernel(const double* __restrict__ m, uint32_t n, double mean, int squared, double* __restrict__ rows) {
     __shared__ double s_v[kOutBlock / 64];
@@ -55,30 +45,20 @@ __global__ __launch_bounds__(kOutBlock) void outlier_rows_kernel(const double* _
             v = d * d;
         }
     }
-    v = out_wave_sum(v);
+    v = wave_xor_sum(v);
     if ((threadIdx.x & 63) == 0) s_v[threadIdx.x >> 6] = v;
     __syncthreads();
-    if (threadIdx.x == 0) {
-        double r = s_v[0];
-#pragma unroll
-        for (int w = 1; w < kOutBlock / 64; ++w) r += s_v[w];
-        rows[blockIdx.x] = r;
-    }
+    if (threadIdx.x == 0) rows[blockIdx.x] = waves_in_order<kOutBlock / 64>(s_v);
 }
 // One block of 1024 threads, any number of rows.
 __global__ __launch_bounds__(1024) void outlier_fold_kernel(const double* __restrict__ rows, uint32_t nrows, double* __restrict__ out) {
     __shared__ double s_v[16];
     double v = 0.0;
     for (uint32_t b = threadIdx.x; b < nrows; b += 1024u) v += rows[b];
-    v = out_wave_sum(v);
+    v = wave_xor_sum(v);
     if ((threadIdx.x & 63) == 0) s_v[threadIdx.x >> 6] = v;
     __syncthreads();
-    if (threadIdx.x == 0) {
-        double r = s_v[0];
-#pragma unroll
-        for (int w = 1; w < 16; ++w) r += s_v[w];
-        out[0] = r;
-    }
+    if (threadIdx.x == 0) out[0] = waves_in_order<16>(s_v);
 }
 
 __global__ __launch_bounds__(kOutBlock) void outlier_flag_kernel(const double* __restrict__ mean_dist, const float* __restrict__ kth_dist2, uint32_t n, int radius_mode,

@@ -13,7 +13,7 @@
 // (cz << 42) | (cy << 21) | cx, does (z-major, then y, then x) and the radix sort runs over bx + by + bz bits instead of 63.
 //
 // Every sum is a function of the input array alone: a thread or a lane adds its members in ascending sorted position, lanes are joined
-// by the xor butterfly (both operands of every addition are the same pair whichever lane adds them, as align_info_kernel in kernels.hip),
+// by the xor butterfly (both operands of every addition are the same pair whichever lane adds them: wave_xor_sum in fixed_sum.hpp),
 // tiles are added first to last.  No floating-point atomics; the one atomic is an integer maximum.
 #include <hip/hip_runtime.h>
 
@@ -29,6 +29,7 @@
 
 #include "../../../include/fgoicp_amd.h"
 #include "../host/abi_guard.hpp"
+#include "fixed_sum.hpp"
 
 namespace fgoicp {
 namespace {
@@ -46,15 +47,6 @@ struct VoxPartial {  // one tile of a long row
     double x, y, z;
     uint32_t row, tile;
 };
-
-__device__ __forceinline__ double vox_wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const int lo = __shfl_xor(__double2loint(v), off, 64), hi = __shfl_xor(__double2hiint(v), off, 64);
-        v += __hiloint2double(hi, lo);
-    }
-    return v;
-}
 
 __global__ __launch_bounds__(kVoxBlock) void voxel_key_kernel(const float* __restrict__ xyz, uint32_t n, VoxGrid g, uint64_t* __restrict__ keys,
                                                              uint32_t* __restrict__ idx) {
@@ -133,7 +125,7 @@ __device__ __forceinline__ void vox_wave_run(const float* __restrict__ xyz, cons
         const float* p = xyz + 3 * (size_t)idx[j];
         x += (double)p[0]; y += (double)p[1]; z += (double)p[2];
     }
-    x = vox_wave_sum(x); y = vox_wave_sum(y); z = vox_wave_sum(z);
+    x = wave_xor_sum(x); y = wave_xor_sum(y); z = wave_xor_sum(z);
 }
 
 // rows of kVoxThreadMax + 1 .. kVoxTile points: one wave per row (waves of other rows leave at once)

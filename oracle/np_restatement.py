@@ -204,3 +204,40 @@ def closest_orthogonal(H):
     U, S, V = jacobi_svd3(H)
     d = np.linalg.det(V @ U.T)
     return V @ np.diag([1.0, 1.0, d]) @ U.T
+
+
+def _wave_butterfly(v):
+    """(waves, 64, K) float64: six steps v[l] += v[l ^ off], off = 32 .. 1, each step on a copy — every lane ends with the wave's sum"""
+    lanes = np.arange(64)
+    for off in (32, 16, 8, 4, 2, 1):
+        v = v + v[:, lanes ^ off, :]
+    return v
+
+
+def _block_rows(v, block):
+    """(n, K), n a multiple of block -> (n / block, K): the butterfly over each wave of 64, then the block's waves left to right"""
+    K = v.shape[1]
+    w = _wave_butterfly(v.reshape(-1, 64, K))[:, 0, :].reshape(-1, block // 64, K)
+    rows = w[:, 0, :]
+    for i in range(1, block // 64):
+        rows = rows + w[:, i, :]
+    return rows
+
+
+def fixed_order_sum(terms, block=256):
+    """The K doubles that the device's fixed-order fp64 reduction (csrc/device/fixed_sum.hpp) returns for terms (n, K) float64, one row
+    per thread index in order: one row per block of `block` threads (butterfly per wave, waves left to right); the fold's thread t adds
+    rows t, t + 1024, ... starting from +0.0, then the same butterfly and its 16 waves left to right.  Lanes past n, and the rows the
+    caller leaves zero for uncounted lanes, contribute +0.0: they are added, not skipped (-0.0 + 0.0 is +0.0)."""
+    terms = np.asarray(terms, np.float64)
+    n, K = terms.shape
+    padded = np.zeros((max(1, -(-n // block)) * block, K))
+    padded[:n] = terms
+    rows = _block_rows(padded, block)
+    sweeps = -(-len(rows) // 1024)
+    held = np.zeros((sweeps * 1024, K))
+    held[:len(rows)] = rows
+    acc = np.zeros((1024, K))
+    for s in range(sweeps):
+        acc = acc + held[s * 1024:(s + 1) * 1024]
+    return _block_rows(acc, 1024)[0]

@@ -1,5 +1,5 @@
 """GPU: the information matrix of a registration — the moments of the counted correspondences from the device (align_info_kernel,
-align_info_fold_kernel) against numpy on the alignment report, for a context (fgoicp_information), a solver (fgoicp_solver_information),
+moment_fold_kernel of csrc/device/fixed_sum.hpp) against numpy on the alignment report, for a context (fgoicp_information), a solver (fgoicp_solver_information),
 a batch (fgoicp_batch_information), the CLI (io.information) and the C++ facade."""
 import ctypes as C
 import json
@@ -8,6 +8,8 @@ import subprocess
 
 import numpy as np
 import pytest
+
+from oracle import np_restatement as npr
 
 pytestmark = pytest.mark.gpu
 
@@ -45,6 +47,19 @@ def check_against_report(info, a, tgt, max_dist2=np.inf):
     assert info.fitness == n / len(a.indices)
     assert info.inlier_rmse == pytest.approx(np.sqrt(a.dist2[m].astype(f64).mean()) / float(info.scaling_factor) if n else 0.0, rel=1e-9)
     return n
+
+
+def check_bits_against_report(info, a, tgt, max_dist2=np.inf):
+    """the ten sums restated in the device's fixed order (oracle/np_restatement.py fixed_order_sum) over terms formed in float64 from the
+    report and the target — a product of two floats is exact in a double; an index that is not counted contributes a row of +0.0: every bit"""
+    m = counted(a, len(tgt), max_dist2)
+    q = tgt[np.where(m, a.indices, 0)].astype(f64)
+    terms = np.column_stack([q[:, 0], q[:, 1], q[:, 2]] + [q[:, i] * q[:, j] for i, j in PAIRS] + [a.dist2.astype(f64)])
+    terms[~m] = 0.0
+    want = npr.fixed_order_sum(terms)
+    got = np.array(list(info.sum_q) + list(info.sum_qq) + [info.sum_dist2], f64)
+    assert info.correspondences == int(m.sum())
+    assert np.array_equal(got.view(np.uint64), want.view(np.uint64)), (got - want, int(m.sum()))
 
 
 def _clouds(ns, nt, seed):
@@ -94,6 +109,24 @@ def test_moments_are_the_reports_moments(fg, gpu_required, ns, nt):
     reg.close()
 
 
+@pytest.mark.parametrize("trimmed", [False, True], ids=["untrimmed", "trimmed"])
+@pytest.mark.parametrize("ns", [1, 63, 64, 65, 255, 256, 257, 1000])
+def test_sums_have_the_bits_of_the_fixed_order(fg, gpu_required, ns, trimmed):
+    """ns: a partial wave, a full wave and one lane more, a block less one lane, a block, a block and one lane, four blocks; trimmed at
+    0.8 ns (uncounted lanes among the counted), and with a threshold at the median distance"""
+    tgt, src, bounds = _clouds(ns, 500, 300 + ns)
+    R, t = _transform(fg, ns)
+    reg = fg.Registration(tgt, src, bounds, 0.1, flags=fg.FLAG_CURVE_ORDER if trimmed else 0)
+    if trimmed:
+        reg.set_inliers(max(1, int(0.8 * ns)))
+    a = reg.alignment(R, t)
+    assert a.inliers == (max(1, int(0.8 * ns)) if trimmed else ns)
+    check_bits_against_report(reg.information(R, t), a, tgt)
+    med = np.sort(a.dist2)[ns // 2]
+    check_bits_against_report(reg.information(R, t, med), a, tgt, med)
+    reg.close()
+
+
 # ---- 2. the threshold ---------------------------------------------------------------------------------------------------------------
 def test_threshold_counts_the_entries_at_or_below_it(fg, gpu_required):
     tgt, src, bounds = _clouds(1000, 500, 7)
@@ -129,15 +162,19 @@ def test_threshold_counts_the_entries_at_or_below_it(fg, gpu_required):
 
 # ---- 3. the fold's strided loop -----------------------------------------------------------------------------------------------------
 def test_more_than_1024_partial_rows(fg, gpu_required):
-    """270 000 source points: 1055 blocks, so thread t of the fold adds rows t and t + 1024"""
+    """270 000 source points: 1055 blocks, so thread t of the fold adds rows t and t + 1024; the sums bit for bit in the fixed order"""
     tgt, src, R_gt, _ = fg.synth.make_pair(40000, 270000, (1.0, 0.8, 0.6), seed=77, angle_deg=20.0, outlier_frac=0.0)
     pct, pcs, *_, bounds = fg.synth.preprocess(tgt, src)
     reg = fg.Registration(pct, pcs, bounds, 0.05)
     R, t = R_gt.astype(f32), np.zeros(3, f32)
     a = reg.alignment(R, t)
-    assert check_against_report(reg.information(R, t), a, pct) == 270000
+    info = reg.information(R, t)
+    assert check_against_report(info, a, pct) == 270000
+    check_bits_against_report(info, a, pct)
     thr = np.sort(a.dist2)[100000]
-    check_against_report(reg.information(R, t, thr), a, pct, thr)
+    near = reg.information(R, t, thr)
+    check_against_report(near, a, pct, thr)
+    check_bits_against_report(near, a, pct, thr)
     reg.close()
 
 

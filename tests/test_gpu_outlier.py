@@ -142,6 +142,18 @@ def test_statistical_mode(fg, gpu_required, name):
     assert np.array_equal(fg.remove_statistical_outliers(pts, k=k, std_ratio=1.0), ret[0])
 
 
+@pytest.mark.parametrize("n", [2, 255, 256, 257, 1025])
+def test_statistical_moments_have_the_bits_of_the_fixed_order(fg, gpu_required, n):
+    """mean and stddev from the RETURNED mean_dist in the device's fixed order (oracle/np_restatement.py fixed_order_sum), bit for bit.
+    n: one lane pair, a block less one lane, a block, a block and one lane, five blocks of which the last holds one point."""
+    pts = uniform(n, 40 + n)
+    _, _, _, m, _, info = fg.remove_statistical_outliers(pts, k=2, std_ratio=1.0, return_map=True)
+    mean = npr.fixed_order_sum(m[:, None])[0] / f64(n)
+    stddev = np.sqrt(npr.fixed_order_sum(((m - mean) * (m - mean))[:, None])[0] / f64(n - 1))
+    got = np.array([info["mean"], info["stddev"]], f64)
+    assert np.array_equal(got.view(np.uint64), np.array([mean, stddev], f64).view(np.uint64)), (got, mean, stddev)
+
+
 @pytest.mark.parametrize("name", sorted(CLOUDS))
 def test_radius_mode(fg, gpu_required, name):
     pts, k = _cloud(name)
