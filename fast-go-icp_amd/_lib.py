@@ -131,6 +131,15 @@ class OutlierInfo(C.Structure):
         self.struct_size = C.sizeof(OutlierInfo)  # the library writes no byte beyond it
 
 
+class FpsInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("points", C.c_uint64), ("samples", C.c_uint64), ("start_index", C.c_uint64), ("next_index", C.c_uint64),
+                ("cover_dist2", C.c_float)]
+
+    def __init__(self):
+        super().__init__()
+        self.struct_size = C.sizeof(FpsInfo)  # the library writes no byte beyond it
+
+
 OUTLIER_STATISTICAL = 0
 OUTLIER_RADIUS = 1
 
@@ -151,6 +160,8 @@ _SIGS = {
     "fgoicp_voxel_downsample": (C.c_int, [c_float_p, C.c_size_t, C.c_float, c_float_p, C.c_int, c_float_p, C.c_size_t, c_uint32_p, c_uint32_p, C.POINTER(VoxelInfo)]),
     "fgoicp_remove_outliers": (C.c_int, [c_float_p, C.c_size_t, C.c_int, C.c_int, C.c_float, C.c_int, c_float_p, C.c_size_t, c_uint32_p, c_uint8_p, c_double_p, c_float_p,
                                          C.POINTER(OutlierInfo)]),
+    "fgoicp_farthest_point_sample": (C.c_int, [c_float_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, c_float_p, c_uint32_p, c_float_p, c_float_p, c_uint32_p,
+                                               C.POINTER(FpsInfo)]),
     "fgoicp_lut_read": (C.c_int, [C.c_void_p, c_float_p, C.c_size_t]),
     "fgoicp_lut_search": (C.c_int, [C.c_void_p, c_float_p, C.c_size_t, c_float_p]),
     "fgoicp_lut_nodes": (C.c_int, [C.c_void_p, c_int_p, C.c_size_t, c_float_p]),

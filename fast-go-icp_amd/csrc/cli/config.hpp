@@ -131,6 +131,9 @@ struct Config {
         // A value that is not a number is refused.
         int target_outlier_knn = 0, source_outlier_knn = 0;
         float target_outlier_std = 2.0f, source_outlier_std = 2.0f, target_outlier_radius = 0.0f, source_outlier_radius = 0.0f;
+        // EXTENSION: farthest-point sampling per cloud after the outlier filter (fgoicp_farthest_point_sample, start_index 0): the number of points the
+        // cloud is brought down to; absent or <= 0: off; a cloud that has no more points stays as it is.  A value that is not an integer is refused.
+        int target_points = 0, source_points = 0;
     } params;
 
     explicit Config(const std::string& toml_filepath) {
@@ -208,6 +211,13 @@ struct Config {
             params.source_outlier_std = (float)strict("source_outlier_std", 2.0);
             params.target_outlier_radius = (float)strict("target_outlier_radius", 0.0);
             params.source_outlier_radius = (float)strict("source_outlier_radius", 0.0);
+            auto count = [&](const char* key) {  // as strict, and the number must be an integer; <= 0: off
+                const double v = strict(key, 0.0);
+                if (v != std::floor(v)) throw std::invalid_argument(std::string("params.") + key + " must be an integer");
+                return v >= 1.0 ? (v > 2147483647.0 ? 2147483647 : (int)v) : 0;
+            };
+            params.target_points = count("target_points");
+            params.source_points = count("source_points");
             auto clampf = [](float x, float lo, float hi) { return x < hi ? (x > lo ? x : lo) : hi; };
             params.target_subsample = clampf(params.target_subsample, 1e-5f, 1.0f);  // utilities.hpp:101-104
             params.source_subsample = clampf(params.source_subsample, 1e-5f, 1.0f);
@@ -406,7 +416,8 @@ inline void write_result_toml(const std::string& path, const icp::mat3& R, const
 // the column names — then one line per registered source point, in the order the cloud was loaded (after source_subsample): its coordinates
 // as loaded, the index of its nearest target point (into the target as loaded), its distance to it in the files' units
 // (sqrt(dist2) / scaling_factor) and 1 if the optimum counts it as an inlier.  Points and indices refer to the clouds AS REGISTERED: with
-// params.source_voxel / params.target_voxel those are the voxel grids' centroids in their row order, not the points of the files, and with params.*_outlier_knn the rows the filter kept, in their order.
+// params.source_voxel / params.target_voxel those are the voxel grids' centroids in their row order, not the points of the files, and with params.*_outlier_knn the rows the filter kept, in their order;
+// with params.source_points / params.target_points the sampled points in pick order.
 inline void write_alignment_txt(const std::string& path, const std::vector<icp::vec3>& src, const uint32_t* idx, const float* dist2, const uint8_t* inlier,
                                 const fgoicp_alignment_summary& s) {
     std::ofstream f(path);

@@ -64,6 +64,28 @@ static void outlier_filter(std::vector<icp::vec3>& pc, int knn, float std_ratio,
     pc.swap(out);
 }
 
+// params.*_points: the cloud replaced by fgoicp_farthest_point_sample's picks (device 0, start_index 0) in pick order, after the outlier filter
+// and before any solver exists: everything downstream sees the sampled cloud.  A cloud that has no more points than asked stays as it is,
+// order included.  A refused call is an error of the configuration: exit code 1.
+static void farthest_sample(std::vector<icp::vec3>& pc, int points, const char* which) {
+    if (points <= 0) return;
+    if (pc.size() <= (size_t)points) {
+        icp::Logger(icp::LogLevel::Info) << "Farthest-point sampling (" << which << "): " << pc.size() << " points, at most " << points << " asked: unchanged";
+        return;
+    }
+    std::vector<icp::vec3> out((size_t)points);
+    fgoicp_fps_info_t fi{};
+    fi.struct_size = sizeof(fi);
+    const int rc = fgoicp_farthest_point_sample(&pc.data()->x, pc.size(), out.size(), 0, 0, &out.data()->x, nullptr, nullptr, nullptr, nullptr, &fi);
+    if (rc != FGOICP_OK) {
+        icp::Logger(icp::LogLevel::Error) << "params." << which << "_points = " << points << ": status " << rc << ": " << fgoicp_last_error();
+        std::exit(1);
+    }
+    icp::Logger(icp::LogLevel::Info) << "Farthest-point sampling (" << which << "): " << pc.size() << " -> " << out.size() << " points, cover radius "
+                                     << std::sqrt(fi.cover_dist2);
+    pc.swap(out);
+}
+
 // --batch LIST: every config of the list registered in one fgoicp_batch run; each config's io.output / io.visualization as a lone -c run
 // of it writes them (the seconds written are the batch's).  The configs must agree on the schedule and round width; each is trimmed with
 // its own params.trim_fraction.
@@ -105,6 +127,8 @@ static int run_batch(const std::string& list_file) {
         voxel_thin(pcs[i], c.params.source_voxel, "source");
         outlier_filter(pct[i], c.params.target_outlier_knn, c.params.target_outlier_std, c.params.target_outlier_radius, "target");
         outlier_filter(pcs[i], c.params.source_outlier_knn, c.params.source_outlier_std, c.params.source_outlier_radius, "source");
+        farthest_sample(pct[i], c.params.target_points, "target");
+        farthest_sample(pcs[i], c.params.source_points, "source");
         icp::Logger(icp::LogLevel::Info) << "Pair " << i << ": target (" << pct[i].size() << ") " << c.io.target << ", source (" << pcs[i].size() << ") " << c.io.source;
         pairs[i] = fgoicp_batch_pair{&pct[i].data()->x, pct[i].size(), &pcs[i].data()->x, pcs[i].size(), c.params.lut_resolution, c.params.mse_threshold};
         trim[i] = c.params.trim_fraction;
@@ -215,6 +239,8 @@ int main(int argc, char* argv[]) {
     voxel_thin(pcs, config.params.source_voxel, "source");
     outlier_filter(pct, config.params.target_outlier_knn, config.params.target_outlier_std, config.params.target_outlier_radius, "target");
     outlier_filter(pcs, config.params.source_outlier_knn, config.params.source_outlier_std, config.params.source_outlier_radius, "source");
+    farthest_sample(pct, config.params.target_points, "target");
+    farthest_sample(pcs, config.params.source_points, "source");
     const std::vector<icp::vec3> pct_in = pct, pcs_in = pcs;
     for (const auto* pc : {&pct, &pcs}) {  // verbose: the statistics the pre-processing normalises by (TODO.md:7 of the reference)
         fgoicp_cloud_stats_t cs{};

@@ -15,6 +15,7 @@
 #include <cstdlib>
 
 #include "../host/knobs.hpp"
+#include "dist_sq.hpp"  // fma_, dist_sq
 #include "slab.hpp"
 #include "bvh.hpp"
 #include "../host/math3.hpp"
@@ -24,8 +25,6 @@ namespace fgoicp {
 namespace {
 
 typedef float float2u __attribute__((ext_vector_type(2), aligned(4)));  // dword-aligned 8-byte load
-
-__device__ __forceinline__ float fma_(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 
 struct Rt {  // rigid motion by value in the kernarg segment
     float R[9];
@@ -37,12 +36,6 @@ __device__ __forceinline__ void rotate(const float* R, float x, float y, float z
     ox = fma_(R[6], z, fma_(R[3], y, R[0] * x));
     oy = fma_(R[7], z, fma_(R[4], y, R[1] * x));
     oz = fma_(R[8], z, fma_(R[5], y, R[2] * x));
-}
-
-// distance_squared, fgoicp/registration.cu:154-160 / :250-256
-__device__ __forceinline__ float dist_sq(float ax, float ay, float az, float bx, float by, float bz) {
-    float dx = ax - bx, dy = ay - by, dz = az - bz;
-    return fma_(dz, dz, fma_(dy, dy, dx * dx));
 }
 
 // Sum over the wave, valid in lane 0.  The tree is v[i] += v[i + off] for off = 32, 16, 8, 4, 2, 1; the two far steps go

@@ -96,6 +96,36 @@ def remove_radius_outliers(points, k, radius, device=0, return_map=False):
     return _remove_outliers(points, _lib.OUTLIER_RADIUS, k, radius, device, return_map)
 
 
+def farthest_point_sample(points, m, start_index=0, device=0, return_map=False):
+    """fgoicp_farthest_point_sample: exactly m points of the cloud, each the farthest from those picked before it (ties to the lowest index),
+    from points[start_index] on, in pick order, as an (m, 3) float32 array; every prefix is the sampling of that size.  return_map=True returns
+    (samples, sample_index (m,) uint32, pick_dist2 (m,) float32, min_dist2 (n,) float32, owner (n,) uint32, info) with
+    info = dict(points, samples, start_index, next_index, cover_dist2).  m DEPENDENT steps over the n points."""
+    p = _cloud(points)
+    for name, v in (("m", m), ("start_index", start_index)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise TypeError(f"{name} must be an integer")
+    n = len(p)
+    if not 1 <= m <= n:
+        raise ValueError(f"m must lie in [1, {n}], the number of points")
+    if not 0 <= start_index < n:
+        raise ValueError(f"start_index must lie in [0, {n})")
+    m = int(m)
+    out = np.empty((m, 3), np.float32)
+    idx = np.empty(m, np.uint32) if return_map else None
+    pick = np.empty(m, np.float32) if return_map else None
+    mind = np.empty(n, np.float32) if return_map else None
+    owner = np.empty(n, np.uint32) if return_map else None
+    ptr = lambda a, t: None if a is None else a.ctypes.data_as(t)
+    info = _lib.FpsInfo()
+    _lib.check(_lib.load().fgoicp_farthest_point_sample(_fp(p), n, m, int(start_index), int(device), _fp(out), ptr(idx, _lib.c_uint32_p), ptr(pick, _lib.c_float_p),
+                                                        ptr(mind, _lib.c_float_p), ptr(owner, _lib.c_uint32_p), C.byref(info)), "fgoicp_farthest_point_sample")
+    if not return_map:
+        return out
+    return out, idx, pick, mind, owner, dict(points=int(info.points), samples=int(info.samples), start_index=int(info.start_index), next_index=int(info.next_index),
+                                             cover_dist2=np.float32(info.cover_dist2))
+
+
 class Alignment:
     """EXTENSION: the alignment report of fgoicp_alignment / fgoicp_solver_alignment / fgoicp_batch_alignment.  Arrays in the caller's point
     order: indices (ns,) uint32 — nearest target point of every source point; dist2 (ns,) float32 — its squared distance in the frame the

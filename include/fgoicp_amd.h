@@ -574,6 +574,45 @@ int fgoicp_remove_outliers(const float* xyz, size_t n, int mode, int k, float pa
                            float* out_xyz, size_t capacity_points, uint32_t* kept_index,
                            uint8_t* keep_n, double* mean_dist_n, float* kth_dist2_n,
                            fgoicp_outlier_info_t* out);
+/*
+ * EXTENSION — farthest-point sampling on the device (no reference counterpart: the reference thins a cloud only in its loaders; Open3D:
+ * farthest_point_down_sample(num_samples, start_index), PCL: FarthestPointSampling).  Sets the NUMBER of points of a cloud — what the run time
+ * of a search is proportional to — where the voxel grid sets a density: exactly m points, spread as evenly as m points can be, and every
+ * prefix of the result is the sampling of that size.
+ *
+ * Inputs: n points (fp32 xyz triples, caller order), 1 <= m <= n, 0 <= start_index < n.
+ *   d2(i, j)      the scans' fp32 dist_sq(p_i, p_j) = fma(dz, dz, fma(dy, dy, dx * dx)), the differences formed in fp32
+ *   D_0[i] = +inf, c_0 = start_index; after pick c_t: D_{t+1}[i] = min(D_t[i], d2(i, c_t)), and owner[i] = t whenever that minimum strictly
+ *                 decreased at step t (a tie keeps the earlier sample; owner starts at 0)
+ *   c_{t+1}       the point not picked so far with the largest D_{t+1}, a tie to the lowest caller index — the largest 64-bit key
+ *                 (bits(D) << 32) | (0xFFFFFFFF - i) over the unpicked points.  A picked point never wins, also when every remaining point
+ *                 is a copy of a picked one (D = 0 everywhere): the call returns m distinct indices, and m = n a permutation of the cloud
+ * Outputs, every array pointer may be NULL (all NULL: `out` alone); all m rows are always written, there is no capacity argument:
+ *   sample_index_m  the picks c_0 .. c_{m-1} in pick order         out_xyz_m3    those points, bits verbatim, in pick order
+ *   pick_dist2_m    D_t[c_t] at the moment of the pick, +inf for the first; non-increasing
+ *   min_dist2_n     the final D: squared distance to the nearest sample, +0.0 for a sample itself
+ *   owner_n         the position in sample_index of that nearest sample
+ *   out             cover_dist2 = max_i min_dist2[i], the squared cover radius; next_index = the point that attains it under the tie rule, what
+ *                   pick m + 1 would be.  m == n: next_index = n, cover_dist2 = 0
+ * Nothing is summed: the outputs are a function of the input alone, two calls return the same bytes.
+ * Cost: m DEPENDENT steps over the n points, one kernel launch each (each reads 16 bytes per point); device memory 16 bytes per point, plus
+ * 4 for each of min_dist2_n and owner_n when asked.
+ * Refused with FGOICP_ERR_INVALID_ARG before any device work (one host pass over the cloud): a null xyz or n == 0, n >= 2^31, m == 0 or m > n,
+ * start_index >= n, a non-finite coordinate (the message names its index), a null `out` or a struct_size that ends before cover_dist2 or is
+ * above 4096.  No usable device: FGOICP_ERR_NO_DEVICE (no CPU fallback); allocation failure: FGOICP_ERR_OOM.
+ * The call owns its stream and its one device allocation and frees both before it returns; it touches no fgoicp_ctx, no global state and no
+ * knob and may be called from several threads.
+ */
+typedef struct fgoicp_fps_info_t {
+    uint32_t struct_size;        /* IN: sizeof(fgoicp_fps_info_t) as the CALLER was compiled; no byte beyond it is written, 0 is refused */
+    uint64_t points, samples;    /* n, m */
+    uint64_t start_index;
+    uint64_t next_index;         /* what pick m + 1 would be; n when m == n */
+    float    cover_dist2;        /* max_i min_dist2[i] */
+} fgoicp_fps_info_t;
+int fgoicp_farthest_point_sample(const float* xyz, size_t n, size_t m, size_t start_index, int device,
+                                 float* out_xyz_m3, uint32_t* sample_index_m, float* pick_dist2_m,
+                                 float* min_dist2_n, uint32_t* owner_n, fgoicp_fps_info_t* out);
 /* The operator context the solver drives (borrowed; valid until solver_destroy). */
 fgoicp_ctx* fgoicp_solver_ctx(fgoicp_solver* s);
 
