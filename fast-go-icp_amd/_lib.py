@@ -140,6 +140,16 @@ class FpsInfo(C.Structure):
         self.struct_size = C.sizeof(FpsInfo)  # the library writes no byte beyond it
 
 
+class ClusterInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("points", C.c_uint64), ("core_points", C.c_uint64), ("border_points", C.c_uint64), ("noise_points", C.c_uint64),
+                ("clusters", C.c_uint64), ("largest_label", C.c_int64), ("largest_size", C.c_uint64), ("kept", C.c_uint64), ("keep_min_size", C.c_uint64),
+                ("min_points", C.c_int), ("eps2", C.c_float), ("rounds", C.c_uint32)]
+
+    def __init__(self):
+        super().__init__()
+        self.struct_size = C.sizeof(ClusterInfo)  # the library writes no byte beyond it
+
+
 OUTLIER_STATISTICAL = 0
 OUTLIER_RADIUS = 1
 
@@ -162,6 +172,8 @@ _SIGS = {
                                          C.POINTER(OutlierInfo)]),
     "fgoicp_farthest_point_sample": (C.c_int, [c_float_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, c_float_p, c_uint32_p, c_float_p, c_float_p, c_uint32_p,
                                                C.POINTER(FpsInfo)]),
+    "fgoicp_cluster_dbscan": (C.c_int, [c_float_p, C.c_size_t, C.c_float, C.c_int, C.c_size_t, C.c_int, c_float_p, C.c_size_t, c_uint32_p, C.POINTER(C.c_int32), c_uint32_p,
+                                        C.POINTER(C.c_uint64), C.c_size_t, C.POINTER(ClusterInfo)]),
     "fgoicp_lut_read": (C.c_int, [C.c_void_p, c_float_p, C.c_size_t]),
     "fgoicp_lut_search": (C.c_int, [C.c_void_p, c_float_p, C.c_size_t, c_float_p]),
     "fgoicp_lut_nodes": (C.c_int, [C.c_void_p, c_int_p, C.c_size_t, c_float_p]),

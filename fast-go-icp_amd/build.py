@@ -24,6 +24,7 @@ SOURCES = [
     os.path.join(CSRC, "device", "voxel.hip"),
     os.path.join(CSRC, "device", "outlier.hip"),
     os.path.join(CSRC, "device", "fps.hip"),
+    os.path.join(CSRC, "device", "cluster.hip"),
     os.path.join(CSRC, "host", "solver.cpp"),
     os.path.join(CSRC, "host", "multi.cpp"),
     os.path.join(CSRC, "host", "batch.cpp"),

@@ -134,6 +134,12 @@ struct Config {
         // EXTENSION: farthest-point sampling per cloud after the outlier filter (fgoicp_farthest_point_sample, start_index 0): the number of points the
         // cloud is brought down to; absent or <= 0: off; a cloud that has no more points stays as it is.  A value that is not an integer is refused.
         int target_points = 0, source_points = 0;
+        // EXTENSION: density clustering per cloud after the outlier filter and before the sampling (fgoicp_cluster_dbscan).  *_cluster_eps: the
+        // radius in the files' units, absent or <= 0: off; *_cluster_min_points: the neighbours (the point included) that make a point core;
+        // *_cluster_min_size: 0 keeps the largest cluster, >= 1 every cluster of at least that many points.  A value that is not a number is refused.
+        float target_cluster_eps = 0.0f, source_cluster_eps = 0.0f;
+        int target_cluster_min_points = 10, source_cluster_min_points = 10;
+        int target_cluster_min_size = 0, source_cluster_min_size = 0;
     } params;
 
     explicit Config(const std::string& toml_filepath) {
@@ -218,6 +224,17 @@ struct Config {
             };
             params.target_points = count("target_points");
             params.source_points = count("source_points");
+            params.target_cluster_eps = (float)strict("target_cluster_eps", 0.0);
+            params.source_cluster_eps = (float)strict("source_cluster_eps", 0.0);
+            auto whole = [&](const char* key, double def) {  // as strict, and the number must be an integer; the call judges its range
+                const double v = strict(key, def);
+                if (v != std::floor(v)) throw std::invalid_argument(std::string("params.") + key + " must be an integer");
+                return v > 2147483647.0 ? 2147483647 : (v < -2147483647.0 ? -2147483647 : (int)v);
+            };
+            params.target_cluster_min_points = whole("target_cluster_min_points", 10.0);
+            params.source_cluster_min_points = whole("source_cluster_min_points", 10.0);
+            params.target_cluster_min_size = count("target_cluster_min_size");
+            params.source_cluster_min_size = count("source_cluster_min_size");
             auto clampf = [](float x, float lo, float hi) { return x < hi ? (x > lo ? x : lo) : hi; };
             params.target_subsample = clampf(params.target_subsample, 1e-5f, 1.0f);  // utilities.hpp:101-104
             params.source_subsample = clampf(params.source_subsample, 1e-5f, 1.0f);
@@ -416,7 +433,7 @@ inline void write_result_toml(const std::string& path, const icp::mat3& R, const
 // the column names — then one line per registered source point, in the order the cloud was loaded (after source_subsample): its coordinates
 // as loaded, the index of its nearest target point (into the target as loaded), its distance to it in the files' units
 // (sqrt(dist2) / scaling_factor) and 1 if the optimum counts it as an inlier.  Points and indices refer to the clouds AS REGISTERED: with
-// params.source_voxel / params.target_voxel those are the voxel grids' centroids in their row order, not the points of the files, and with params.*_outlier_knn the rows the filter kept, in their order;
+// params.source_voxel / params.target_voxel those are the voxel grids' centroids in their row order, not the points of the files, and with params.*_outlier_knn or params.*_cluster_eps the rows the filter kept, in their order;
 // with params.source_points / params.target_points the sampled points in pick order.
 inline void write_alignment_txt(const std::string& path, const std::vector<icp::vec3>& src, const uint32_t* idx, const float* dist2, const uint8_t* inlier,
                                 const fgoicp_alignment_summary& s) {

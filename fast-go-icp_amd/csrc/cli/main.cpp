@@ -64,6 +64,37 @@ static void outlier_filter(std::vector<icp::vec3>& pc, int knn, float std_ratio,
     pc.swap(out);
 }
 
+// params.*_cluster_eps: the cloud replaced by the points fgoicp_cluster_dbscan keeps (device 0) — its largest cluster, or with
+// params.*_cluster_min_size >= 1 every cluster of at least that many points — after the outlier filter and before the sampling and any solver:
+// everything downstream sees the filtered cloud.  A refused call, and a filter that keeps no point, is an error of the configuration: exit code 1.
+static void cluster_filter(std::vector<icp::vec3>& pc, float eps, int min_points, int min_size, const char* which) {
+    if (!(eps > 0.0f)) return;
+    std::vector<icp::vec3> out(pc.size());
+    std::vector<uint64_t> sizes(pc.size());
+    fgoicp_cluster_info_t ci{};
+    ci.struct_size = sizeof(ci);
+    const int rc = fgoicp_cluster_dbscan(&pc.data()->x, pc.size(), eps, min_points, (size_t)min_size, 0, &out.data()->x, out.size(), nullptr, nullptr, nullptr, sizes.data(),
+                                         sizes.size(), &ci);
+    if (rc != FGOICP_OK) {
+        icp::Logger(icp::LogLevel::Error) << "params." << which << "_cluster_eps = " << eps << ": status " << rc << ": " << fgoicp_last_error();
+        std::exit(1);
+    }
+    if (ci.kept == 0) {
+        icp::Logger(icp::LogLevel::Error) << "params." << which << "_cluster_eps = " << eps << ": the filter keeps no point (" << ci.clusters << " clusters, "
+                                          << ci.noise_points << " noise points, " << min_points << " neighbours, clusters of at least " << min_size << " points)";
+        std::exit(1);
+    }
+    out.resize((size_t)ci.kept);
+    size_t kept_clusters = 0;
+    for (uint64_t c = 0; c < ci.clusters; ++c) kept_clusters += sizes[(size_t)c] >= (uint64_t)min_size ? 1 : 0;
+    icp::Logger log(icp::LogLevel::Info);
+    log << "Cluster filter (" << which << "): " << pc.size() << " -> " << out.size() << " points, eps " << eps << ", " << min_points << " neighbours: " << ci.clusters
+        << " clusters, " << ci.noise_points << " noise points, ";
+    if (min_size <= 0) log << "kept the largest";
+    else log << "kept " << kept_clusters << " clusters of at least " << min_size << " points";
+    pc.swap(out);
+}
+
 // params.*_points: the cloud replaced by fgoicp_farthest_point_sample's picks (device 0, start_index 0) in pick order, after the outlier filter
 // and before any solver exists: everything downstream sees the sampled cloud.  A cloud that has no more points than asked stays as it is,
 // order included.  A refused call is an error of the configuration: exit code 1.
@@ -127,6 +158,8 @@ static int run_batch(const std::string& list_file) {
         voxel_thin(pcs[i], c.params.source_voxel, "source");
         outlier_filter(pct[i], c.params.target_outlier_knn, c.params.target_outlier_std, c.params.target_outlier_radius, "target");
         outlier_filter(pcs[i], c.params.source_outlier_knn, c.params.source_outlier_std, c.params.source_outlier_radius, "source");
+        cluster_filter(pct[i], c.params.target_cluster_eps, c.params.target_cluster_min_points, c.params.target_cluster_min_size, "target");
+        cluster_filter(pcs[i], c.params.source_cluster_eps, c.params.source_cluster_min_points, c.params.source_cluster_min_size, "source");
         farthest_sample(pct[i], c.params.target_points, "target");
         farthest_sample(pcs[i], c.params.source_points, "source");
         icp::Logger(icp::LogLevel::Info) << "Pair " << i << ": target (" << pct[i].size() << ") " << c.io.target << ", source (" << pcs[i].size() << ") " << c.io.source;
@@ -239,6 +272,8 @@ int main(int argc, char* argv[]) {
     voxel_thin(pcs, config.params.source_voxel, "source");
     outlier_filter(pct, config.params.target_outlier_knn, config.params.target_outlier_std, config.params.target_outlier_radius, "target");
     outlier_filter(pcs, config.params.source_outlier_knn, config.params.source_outlier_std, config.params.source_outlier_radius, "source");
+    cluster_filter(pct, config.params.target_cluster_eps, config.params.target_cluster_min_points, config.params.target_cluster_min_size, "target");
+    cluster_filter(pcs, config.params.source_cluster_eps, config.params.source_cluster_min_points, config.params.source_cluster_min_size, "source");
     farthest_sample(pct, config.params.target_points, "target");
     farthest_sample(pcs, config.params.source_points, "source");
     const std::vector<icp::vec3> pct_in = pct, pcs_in = pcs;

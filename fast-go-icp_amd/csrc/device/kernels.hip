@@ -2678,6 +2678,125 @@ void launch_outlier_knn(const BvhView& t, int nt, int k, double* mean_dist, floa
 }
 
 // ---------------------------------------------------------------------------------------------
+// Density clustering (fgoicp_cluster_dbscan; cluster.hip): the fixed-radius walk over the cloud's own tree and its three
+// consumers.  The queries are the tree's points in leaf order, one wave per workgroup, as in knn_walk; the walk is box_scan under the CONSTANT
+// bound eps2 — a box is skipped only when its shrunk fp32 distance exceeds eps2, so no point with d2 <= eps2 is missed, and every candidate's
+// d2 is the scans' dist_sq(query, candidate).  No list, no LDS.  A candidate is wave-uniform (its leaf is read through the scalar unit), so
+// what the consumers gather per candidate — core[j], parent[j] at its CALLER index j — is one word for the whole wave.
+//   count    neighbours[me] = #{ j : d2 <= eps2 } (the point itself among them), core[me] = neighbours[me] >= min_points
+//   hook     one round of the union-find over the core points (below)
+//   border   a core point takes its root's rank; a non-core point the rank of the root of its core neighbour of smallest key
+//            (bits(d2) << 32) | j, or -1 when it has none
+// Union-find: parent[i] = i to begin with.  hook: every core point i, for every core neighbour j < i (the edge is met from its larger end:
+// d2 is symmetric to the bit), chases both to their roots and, if they differ, atomicMin(parent[larger root], smaller root).  Parents only
+// decrease and parent[x] <= x throughout, so a chase ends after at most n steps and waits on no other thread.  Two hooks onto one root in the
+// same instant keep only the smaller, hence ROUNDS (hook, then compress: parent[i] = root(i)) until a round hooks nothing: then every edge
+// joins two points of one tree, a tree never leaves its component, and a tree's root is its smallest index — the same bytes however the
+// hooks interleaved.  parent is read with relaxed agent-scope atomic loads; nothing spins, no barrier across workgroups.
+// ---------------------------------------------------------------------------------------------
+template <class HitFn>
+__device__ __forceinline__ void radius_walk(const BvhView& t, int nt, const float4 p, bool active, float eps2, HitFn hit /* (caller index, d2) */) {
+    const float qx = p.x, qy = p.y, qz = p.z;
+    box_scan(t, qx, qy, qz, active, 0, 1,
+             [&](const float4 c, bool on) {
+                 const uint32_t j = __float_as_uint(c.w);
+                 if (!on || j >= (uint32_t)nt) return;  // padding points carry no caller index
+                 const float d2 = dist_sq(qx, qy, qz, c.x, c.y, c.z);
+                 if (d2 <= eps2) hit(j, d2);
+             },
+             [&]() { return eps2; });
+}
+
+__device__ __forceinline__ uint32_t cluster_root(const uint32_t* parent, uint32_t x) {
+    uint32_t r = __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    while (r != x) {
+        x = r;
+        r = __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    return x;
+}
+
+// core_count: += the number of core points (one integer atomic per wave)
+__global__ __launch_bounds__(64) void cluster_count_kernel(BvhView t, int nt, float eps2, uint32_t min_points, uint32_t* __restrict__ neighbours, uint32_t* __restrict__ core,
+                                                           unsigned long long* __restrict__ core_count) {
+    const int lane = threadIdx.x;
+    const int slot = blockIdx.x * 64 + lane;
+    const bool active = slot < nt;
+    const float4 p = t.pts[active ? slot : nt - 1];
+    uint32_t cnt = 0;
+    radius_walk(t, nt, p, active, eps2, [&](uint32_t, float) { ++cnt; });
+    const bool is_core = active && cnt >= min_points;
+    if (active) {
+        const uint32_t me = __float_as_uint(p.w);
+        neighbours[me] = cnt;
+        core[me] = is_core ? 1u : 0u;
+    }
+    const unsigned long long m = __ballot(is_core);
+    if (lane == 0 && m) atomicAdd(core_count, (unsigned long long)__popcll(m));
+}
+
+__global__ __launch_bounds__(64) void cluster_hook_kernel(BvhView t, int nt, float eps2, const uint32_t* __restrict__ core, uint32_t* parent, uint32_t* changed) {
+    const int slot = blockIdx.x * 64 + threadIdx.x;
+    const bool active = slot < nt;
+    const float4 p = t.pts[active ? slot : nt - 1];
+    const uint32_t me = __float_as_uint(p.w);
+    const bool walks = active && core[me] != 0u;
+    if (!__any(walks)) return;
+    // Where the next chase of me starts: a point of me's COMPONENT, not necessarily an ancestor still (a hook that loses to a smaller one
+    // moves a subtree).  That is enough: a chase from any point of the component ends at a root of the component, so every hook joins two
+    // trees of one component; and the last round, which hooks nothing, reads a parent array nobody writes.
+    uint32_t mine = me;
+    bool hooked = false;
+    radius_walk(t, nt, p, walks, eps2, [&](uint32_t j, float) {
+        if (j >= me || core[j] == 0u) return;
+        mine = cluster_root(parent, mine);
+        const uint32_t theirs = cluster_root(parent, j);
+        if (mine == theirs) return;
+        atomicMin(parent + (mine > theirs ? mine : theirs), mine > theirs ? theirs : mine);
+        hooked = true;
+    });
+    if (hooked) *changed = 1u;
+}
+
+__global__ __launch_bounds__(kBlock) void cluster_compress_kernel(const uint32_t* __restrict__ core, uint32_t* parent, uint32_t n) {
+    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n || core[i] == 0u) return;
+    __hip_atomic_store(parent + i, cluster_root(parent, (uint32_t)i), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// rank: the exclusive scan over caller index of the root flags (core[i] && parent[i] == i), parent compressed
+__global__ __launch_bounds__(64) void cluster_border_kernel(BvhView t, int nt, float eps2, const uint32_t* __restrict__ core, const uint32_t* __restrict__ parent,
+                                                            const uint32_t* __restrict__ rank, int32_t* __restrict__ label) {
+    const int slot = blockIdx.x * 64 + threadIdx.x;
+    const bool active = slot < nt;
+    const float4 p = t.pts[active ? slot : nt - 1];
+    const uint32_t me = __float_as_uint(p.w);
+    const bool is_core = active && core[me] != 0u;
+    if (is_core) label[me] = (int32_t)rank[parent[me]];
+    const bool walks = active && !is_core;
+    if (!__any(walks)) return;
+    const unsigned long long kNone = ~0ull;
+    unsigned long long best = kNone;
+    radius_walk(t, nt, p, walks, eps2, [&](uint32_t j, float d2) {
+        if (core[j] == 0u) return;
+        const unsigned long long key = ((unsigned long long)__float_as_uint(d2) << 32) | j;
+        best = key < best ? key : best;
+    });
+    if (walks) label[me] = best == kNone ? -1 : (int32_t)rank[parent[(uint32_t)best]];
+}
+
+void launch_cluster_count(const BvhView& t, int nt, float eps2, uint32_t min_points, uint32_t* neighbours, uint32_t* core, unsigned long long* core_count, hipStream_t s) {
+    hipLaunchKernelGGL(cluster_count_kernel, dim3((nt + 63) / 64), dim3(64), 0, s, t, nt, eps2, min_points, neighbours, core, core_count);
+}
+void launch_cluster_round(const BvhView& t, int nt, float eps2, const uint32_t* core, uint32_t* parent, uint32_t* changed, hipStream_t s) {
+    hipLaunchKernelGGL(cluster_hook_kernel, dim3((nt + 63) / 64), dim3(64), 0, s, t, nt, eps2, core, parent, changed);
+    hipLaunchKernelGGL(cluster_compress_kernel, dim3((nt + kBlock - 1) / kBlock), dim3(kBlock), 0, s, core, parent, (uint32_t)nt);
+}
+void launch_cluster_border(const BvhView& t, int nt, float eps2, const uint32_t* core, const uint32_t* parent, const uint32_t* rank, int32_t* label, hipStream_t s) {
+    hipLaunchKernelGGL(cluster_border_kernel, dim3((nt + 63) / 64), dim3(64), 0, s, t, nt, eps2, core, parent, rank, label);
+}
+
+// ---------------------------------------------------------------------------------------------
 // The point-to-plane normal equations (fgoicp_plane_moments) over the report's arrays.  One thread per device slot i: the moved query
 // x = R p + t as the report's index scan wrote it back (fp32, the scans' fma convention), the slot's caller index o, and the report's
 // entries of o.  COUNTED are the o with inlier[o] != 0, d2[o] <= max_d2, corr[o] < nt and a non-zero normal at corr[o].  With q the target

@@ -141,6 +141,17 @@ void launch_target_knn(const BvhView& t, const float4* tgt, int nt, int k, uint3
 // 2 <= k <= 32, k <= nt.
 constexpr int kOutlierKnnMin = 2;
 void launch_outlier_knn(const BvhView& t, int nt, int k, double* mean_dist, float* kth_dist2, hipStream_t s);
+// Density clustering (fgoicp_cluster_dbscan; kernels.hip radius_walk and its consumers): every array is indexed by CALLER index, nt entries.
+// count: neighbours[i] = the points within eps2 of point i (itself included, d2 <= eps2 on the scans' fp32 dist_sq), core[i] = 0 / 1 =
+// neighbours[i] >= min_points, *core_count += the number of core points.
+void launch_cluster_count(const BvhView& t, int nt, float eps2, uint32_t min_points, uint32_t* neighbours, uint32_t* core, unsigned long long* core_count, hipStream_t s);
+// One round of the union-find over the core points: hook (every core point, for each core neighbour of a lower index, atomicMin of the larger
+// root's parent with the smaller root; *changed = 1 if any hook was made), then compress (parent[i] = root(i) for every core i).  parent[i] = i
+// before the first round; the caller repeats the round until one leaves *changed at 0: then parent[i] is the lowest index of i's component.
+void launch_cluster_round(const BvhView& t, int nt, float eps2, const uint32_t* core, uint32_t* parent, uint32_t* changed, hipStream_t s);
+// label[i] = rank[parent[i]] for a core point; for another point the same of its core neighbour with the smallest key (bits(d2) << 32) | index,
+// -1 if it has none.  rank: the dense number of every root (the exclusive scan of the root flags over caller index).
+void launch_cluster_border(const BvhView& t, int nt, float eps2, const uint32_t* core, const uint32_t* parent, const uint32_t* rank, int32_t* label, hipStream_t s);
 // The point-to-plane normal equations (fgoicp_plane_moments; kernels.hip plane_moments_kernel, fixed_sum.hpp moment_fold_kernel) over the report's
 // arrays (caller order) and the moved queries of its index scan (device order, `moved`): counted are the caller indices with inlier != 0,
 // d2 <= max_d2, corr < nt and a non-zero normal at corr.  rows: ceil(n / kBlock) entries; out29 = {count, the bits of 28 doubles: the

@@ -126,6 +126,41 @@ def farthest_point_sample(points, m, start_index=0, device=0, return_map=False):
                                              cover_dist2=np.float32(info.cover_dist2))
 
 
+def cluster_dbscan(points, eps, min_points=10, keep_min_size=0, device=0, return_map=False):
+    """fgoicp_cluster_dbscan: density clustering of the cloud (a point is core when at least min_points points, itself included, lie within
+    eps; clusters are the connected components of the core points, numbered by their lowest index; a border point joins its nearest core
+    neighbour's cluster; the rest is noise) — returns the points of the largest cluster (keep_min_size=0) or of every cluster of at least
+    keep_min_size points, in caller order, as an (m, 3) float32 array.  return_map=True returns (kept, label (n,) int32 with -1 = noise,
+    neighbours (n,) uint32, cluster_size (clusters,) uint64, kept_index (m,) uint32, info) with info = dict(points, core_points, border_points,
+    noise_points, clusters, largest_label, largest_size, kept, keep_min_size, min_points, eps2, rounds)."""
+    p = _cloud(points)
+    for name, v in (("min_points", min_points), ("keep_min_size", keep_min_size)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise TypeError(f"{name} must be an integer")
+    if keep_min_size < 0:
+        raise ValueError("keep_min_size must not be negative")
+    if not -2 ** 31 <= min_points < 2 ** 31:
+        raise ValueError("min_points does not fit an int")
+    n = len(p)
+    out = np.empty((n, 3), np.float32)
+    idx = np.empty(n, np.uint32) if return_map else None
+    label = np.empty(n, np.int32) if return_map else None
+    nbr = np.empty(n, np.uint32) if return_map else None
+    size = np.empty(n, np.uint64) if return_map else None
+    ptr = lambda a, t: None if a is None else a.ctypes.data_as(t)
+    info = _lib.ClusterInfo()
+    _lib.check(_lib.load().fgoicp_cluster_dbscan(_fp(p) if n else None, n, float(eps), int(min_points), int(keep_min_size), int(device), _fp(out), n, ptr(idx, _lib.c_uint32_p),
+                                                 ptr(label, C.POINTER(C.c_int32)), ptr(nbr, _lib.c_uint32_p), ptr(size, C.POINTER(C.c_uint64)), n, C.byref(info)),
+               "fgoicp_cluster_dbscan")
+    m = int(info.kept)
+    out = out[:m].copy()
+    if not return_map:
+        return out
+    d = {name: int(getattr(info, name)) for name, _ in _lib.ClusterInfo._fields_ if name not in ("struct_size", "eps2")}
+    d["eps2"] = np.float32(info.eps2)
+    return out, label, nbr, size[:int(info.clusters)].copy(), idx[:m].copy(), d
+
+
 class Alignment:
     """EXTENSION: the alignment report of fgoicp_alignment / fgoicp_solver_alignment / fgoicp_batch_alignment.  Arrays in the caller's point
     order: indices (ns,) uint32 — nearest target point of every source point; dist2 (ns,) float32 — its squared distance in the frame the

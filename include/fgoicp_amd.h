@@ -613,6 +613,58 @@ typedef struct fgoicp_fps_info_t {
 int fgoicp_farthest_point_sample(const float* xyz, size_t n, size_t m, size_t start_index, int device,
                                  float* out_xyz_m3, uint32_t* sample_index_m, float* pick_dist2_m,
                                  float* min_dist2_n, uint32_t* owner_n, fgoicp_fps_info_t* out);
+/*
+ * EXTENSION — density clustering on the device (no reference counterpart; Open3D: cluster_dbscan(eps, min_points) followed by "keep the
+ * largest label", PCL: EuclideanClusterExtraction, which is the min_points = 1 case).  Removes what the outlier filter cannot: a detached
+ * CLUMP of points — a piece of the fixture, a second object, a blob of ghost returns — whose members are each other's close neighbours.
+ *
+ * Inputs: n points (fp32 xyz triples, caller order), eps finite and > 0, min_points >= 1, keep_min_size.
+ *   d2(i, j)       the scans' fp32 dist_sq(p_i, p_j) = fma(dz, dz, fma(dy, dy, dx * dx)), the differences formed in fp32: symmetric in its
+ *                  arguments and 0 on the diagonal, both to the bit.  eps2 = eps * eps in fp32
+ *   neighbours[i]  #{ j : d2(i, j) <= eps2 }, the point itself counted; the comparison is <= on fp32
+ *   core[i]        neighbours[i] >= min_points
+ *   cluster        a connected component of the graph on the CORE points with an edge wherever d2 <= eps2.  Clusters are numbered
+ *                  0 .. clusters - 1 in ascending order of their lowest caller index among core members
+ *   border point   a point that is not core and has at least one core neighbour: it gets the label of the core neighbour with the smallest key
+ *                  (bits(d2) << 32) | caller index — the total order of fgoicp_target_knn, a tie goes to the lowest index
+ *   noise          every other point: label -1
+ *   cluster_size[c]  the number of points labelled c, core and border together; the LARGEST cluster is the one of greatest size, a tie going
+ *                  to the lowest label
+ *   kept           keep_min_size == 0: the points of the largest cluster; keep_min_size >= 1: the points of every cluster of at least that
+ *                  many points (1: all but noise).  Noise is never kept; no cluster at all keeps nothing (kept = 0, FGOICP_OK)
+ * min_points = 1 makes every point core: plain Euclidean cluster extraction.
+ * DIFFERS from Open3D and scikit-learn in the border points only: they give a border point to whichever cluster reaches it first, which
+ * depends on the order of their scan; here the nearest core neighbour decides, so the result is a function of the input alone and two calls
+ * return the same bytes in every output.  (The components come out of concurrent integer atomics on the device, yet their fixed point —
+ * every component's root is its lowest caller index — does not depend on how those interleave; `rounds` may.)
+ * Outputs, every array pointer may be NULL (all NULL: `out` alone):
+ *   out_xyz / kept_index  the kept points in caller order, bits verbatim, and their caller indices; both hold capacity_points rows
+ *   label_n (n int32)     neighbours_n (n uint32)     cluster_size (capacity_clusters uint64, `clusters` of them written)
+ * If out_xyz or kept_index is given and capacity_points < kept, or cluster_size is given and capacity_clusters < clusters, the call returns
+ * FGOICP_ERR_TOO_LARGE with `out` filled, so a second call can be sized, and writes nothing to any array; n always suffices for either.
+ * Refused with FGOICP_ERR_INVALID_ARG before any device work (one host pass over the cloud): a null xyz or n == 0, n >= 2^31, a non-finite
+ * coordinate (the message names the point), eps not finite or not > 0, min_points < 1, a null `out` or a struct_size that is 0, ends before
+ * `rounds` or is above 4096, a device ordinal out of range.  No usable device: FGOICP_ERR_NO_DEVICE (no CPU fallback); allocation failure:
+ * FGOICP_ERR_OOM.  The call owns its stream and its one device allocation (about 100 bytes per point) and frees both before it returns; it
+ * touches no fgoicp_ctx, no global state and no knob and may be called from several threads.
+ */
+typedef struct fgoicp_cluster_info_t {
+    uint32_t struct_size;        /* IN: sizeof(fgoicp_cluster_info_t) as the CALLER was compiled; no byte beyond it is written, 0 is refused */
+    uint64_t points;             /* n */
+    uint64_t core_points, border_points, noise_points;
+    uint64_t clusters;
+    int64_t  largest_label;      /* -1: no cluster */
+    uint64_t largest_size;
+    uint64_t kept;               /* rows of the output */
+    uint64_t keep_min_size;
+    int      min_points;
+    float    eps2;               /* the fp32 value every d2 was compared with */
+    uint32_t rounds;             /* hook-and-compress rounds of the connected-components pass, the last one (which changed nothing) included */
+} fgoicp_cluster_info_t;
+int fgoicp_cluster_dbscan(const float* xyz, size_t n, float eps, int min_points, size_t keep_min_size, int device,
+                          float* out_xyz, size_t capacity_points, uint32_t* kept_index,
+                          int32_t* label_n, uint32_t* neighbours_n, uint64_t* cluster_size, size_t capacity_clusters,
+                          fgoicp_cluster_info_t* out);
 /* The operator context the solver drives (borrowed; valid until solver_destroy). */
 fgoicp_ctx* fgoicp_solver_ctx(fgoicp_solver* s);
 
