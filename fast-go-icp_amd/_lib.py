@@ -186,6 +186,7 @@ _SIGS = {
     "fgoicp_bounds_submit": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_float_p, c_float_p, c_int_p, c_int_p, c_float_p]),
     "fgoicp_bounds_submit_twins": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_float_p, c_float_p, c_int_p, c_int_p, c_float_p, c_int_p]),
     "fgoicp_bounds_submit_cut": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_float_p, c_float_p, c_int_p, c_int_p, c_float_p, c_int_p, c_float_p]),
+    "fgoicp_bounds_submit_leaf": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_float_p, c_float_p, c_int_p, c_int_p, c_float_p, c_int_p, c_float_p, c_float_p]),
     "fgoicp_ctx_cut_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int]),
     "fgoicp_solver_set_early_exit": (C.c_int, [C.c_void_p, C.c_int]),
     "fgoicp_bounds_collect": (C.c_int, [C.c_void_p, C.c_int, c_float_p, c_float_p]),

@@ -258,10 +258,15 @@ __global__ __launch_bounds__(64) void bounds_item_kernel(const float4* __restric
     // items get here early depends on timing; what is reported does not: bounds_finalize_kernel returns {T, T} for EVERY row whose lower
     // bound is >= T, cut short or not.  The margin keeps the decision on the safe side of the two summation orders (this running
     // sum: finished items in any order; the reported one: the fixed tree).
+    // A TERMINAL row (fgoicp_bounds_submit_leaf: a leaf of the inner BnB, never split, fgoicp.cpp:155) is decided by its UPPER bound instead:
+    // the caller needs neither bound of it once ub >= T.  The terms of the ub sum are >= 0 too, and each is >= the lb term of the same
+    // point (max(d, 0)^2 >= max(d - r, 0)^2), so the running sums of such a row are the ub partials' and reach T much earlier — for a leaf
+    // that survives the lb rule, often the only way they ever do.  Same gate, same thresholds, same margin; bounds_finalize_kernel
+    // applies the row's rule.
     // (the descriptor: a scalar load issued NEXT TO the gate's, not behind it — an item that ends early does not wait for it, and one that
     // goes on would pay a round trip more: +0.4 % on a tick in which no item is skipped, profiles/ab_early_exit_gate.txt)
     const TickSub sb = subs[s];
-    bool cutting = false;
+    bool cutting = false, term0 = false, term1 = false;
     if (!TRIM && cut.acc) {
         // The gate is the only load an item that ends early waits for behind its slot of `sorted`: `done` and the kind of
         // the evaluation (the same address in every lane; an atomic load of workgroup scope, so that it goes through the vector path to
@@ -272,6 +277,8 @@ __global__ __launch_bounds__(64) void bounds_item_kernel(const float4* __restric
         if (__builtin_amdgcn_readfirstlane((int)(unsigned)gw) && !(cut.probe & 4)) return;
         const unsigned flags = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(gw >> 32));
         cutting = (flags & kGateCutting) != 0u;
+        term0 = (flags & kGateTerm0) != 0u;
+        term1 = (flags & kGateTerm1) != 0u;
         if (cutting && !(cut.probe & 1)) {
             // The running sums live at the device's point of coherence (the eight XCDs' L2s are not coherent with each other): reading
             // them costs a trip to memory, ~2 us.  An item that finds its evaluation finished says so in the gate, with a store that
@@ -295,7 +302,7 @@ __global__ __launch_bounds__(64) void bounds_item_kernel(const float4* __restric
     const f2v t_xy = f2v{sb.tx, sb.ty};
     float* row0 = TRIM ? evals + (size_t)sb.out0 * erow : nullptr;
     float* row1 = TRIM ? evals + (size_t)sb.out1 * erow : nullptr;
-    double lb_fix = 0.0, lb_rot = 0.0;  // what this item adds to the evaluation's running sums
+    double lb_fix = 0.0, lb_rot = 0.0;  // what this item adds to the evaluation's running sums (the lower-bound sums; of a terminal row: the upper-bound sums)
     for (int sub = 0; sub < (SPAN ? nsub : 1); ++sub) {
         const int chunk = chunk0 + sub;
         const int base = chunk * chunk_pts;
@@ -306,10 +313,10 @@ __global__ __launch_bounds__(64) void bounds_item_kernel(const float4* __restric
         if (TRIM) continue;
         // the wave tree of block_sum with one wave (same operands, same order), lane 0 writes
         const double r0 = wave_sum(acc[0]), r1 = wave_sum(acc[1]);
-        lb_fix += r1;
+        lb_fix += term0 ? r0 : r1;
         if (sb.dual) {
             const double r2 = wave_sum(acc[2]), r3 = wave_sum(acc[3]);
-            lb_rot += r3;
+            lb_rot += term1 ? r2 : r3;
             if (lane == 0) {
                 partials[(size_t)sb.out0 * nchunk + chunk] = make_double2(r0, r1);
                 partials[(size_t)sb.out1 * nchunk + chunk] = make_double2(r2, r3);

@@ -123,7 +123,7 @@ static int tick_launch_window(fgoicp_ctx* c, fgoicp_ctx::TickSlot& sl) {
     const TickGroup* dev_groups = small ? sl.hd_groups : sl.d_groups;
     const TickSub* dev_subs = small ? sl.hd_subs : sl.d_subs;
     TickCut cut;  // early exit of evaluations that have reached their group's threshold (fgoicp_bounds_submit_cut)
-    if (sl.win_cut) { cut.acc = sl.d_cut_acc; cut.gate = sl.d_cut_gate; cut.row_cut = sl.d_row_cut; cut.stat = c->d_cut_stat; }
+    if (sl.win_cut) { cut.acc = sl.d_cut_acc; cut.gate = sl.d_cut_gate; cut.row_cut = sl.d_row_cut; cut.row_term = sl.d_row_term; cut.stat = c->d_cut_stat; }
     if (tiers && !small) cut.tier_split = sl.d_cursor + kTickTierSplit;
     static const int cut_probe = [] { const char* e = dev_env("FGOICP_CUT_PROBE"); return e ? std::atoi(e) : 0; }();  // measurement of the early exit's own cost (tools/op_bench.py)
     cut.probe = cut_probe;
@@ -189,7 +189,7 @@ static int tick_launch_window(fgoicp_ctx* c, fgoicp_ctx::TickSlot& sl) {
 // Enqueues the window [pos, pos+rows) of a submission on its slot: packs the descriptors (host), then tick_launch_window.
 // Returns the window end.
 static int tick_enqueue_window(fgoicp_ctx* c, fgoicp_ctx::TickSlot& sl, int G, const float* R9, const float* rot_span, const int* fix_rot,
-                               const int* offsets, const float* tn4, const int* twin, const float* cut_above, int pos, int* end_out) {
+                               const int* offsets, const float* tn4, const int* twin, const float* cut_above, const float* ub_below_span, int pos, int* end_out) {
     const double t0 = g_tt.on ? now_s() : 0;
     int g = 0;
     while (g < G && offsets[g + 1] <= pos) ++g;
@@ -213,6 +213,9 @@ static int tick_enqueue_window(fgoicp_ctx* c, fgoicp_ctx::TickSlot& sl, int G, c
     const int rows = end - pos;  // output rows of this window
     *end_out = end;
     if (rows <= 0) return FGOICP_OK;
+    // terminal rows (fgoicp_bounds_submit_leaf): span below the group's ub_below_span, in a group with a threshold
+    static const bool leaf_rule = [] { const char* e = dev_env("FGOICP_CUT_LEAF"); return !e || std::atoi(e) != 0; }();  // development build, A/B: 0 = every row by the lower-bound rule
+    const auto terminal = [&](int sub_group, float span) { return leaf_rule && cut_above && ub_below_span && span < ub_below_span[sub_group]; };
     // evaluations: one per output row, or one per twin pair (both inside this window, same rotation, same translation node,
     // one in a fix_rot group and one not — checked here, the caller's hint is not trusted)
     int neval = 0;
@@ -237,7 +240,9 @@ static int tick_enqueue_window(fgoicp_ctx* c, fgoicp_ctx::TickSlot& sl, int G, c
                 const float ca = cut_above ? cut_above[a.pad_] : kNoCut, cb = cut_above ? cut_above[b.pad_] : kNoCut;  // (pad_: the submission's group index)
                 ts.cut0 = a.fix_rot ? ca : cb;
                 ts.cut1 = a.fix_rot ? cb : ca;
-                ts.pad_[0] = ts.pad_[1] = 0;
+                const unsigned ta = terminal(a.pad_, ts.span) ? 1u : 0u, tb = terminal(b.pad_, ts.span) ? 1u : 0u;
+                ts.term = a.fix_rot ? (ta * kSubTerm0 | tb * kSubTerm1) : (tb * kSubTerm0 | ta * kSubTerm1);
+                ts.pad_ = 0;
                 continue;
             }
         }
@@ -248,7 +253,8 @@ static int tick_enqueue_window(fgoicp_ctx* c, fgoicp_ctx::TickSlot& sl, int G, c
         ts.out1 = r;
         ts.dual = 0;
         ts.cut0 = ts.cut1 = cut_above ? cut_above[sl.h_groups[gi].pad_] : kNoCut;
-        ts.pad_[0] = ts.pad_[1] = 0;
+        ts.term = terminal(sl.h_groups[gi].pad_, ts.span) ? kSubTerm0 : 0u;
+        ts.pad_ = 0;
     }
     sl.win_cut = cut_above != nullptr && !c->inliers;
     for (int k = 0; k < ng; ++k) sl.h_groups[k].pad_ = 0;
@@ -281,7 +287,8 @@ static int tick_wait_window(fgoicp_ctx* c, fgoicp_ctx::TickSlot& sl) {
     }
 #ifdef FGOICP_DEV_KNOBS
     // FGOICP_CUT_VERIFY=1 (development build): every window that carried thresholds is evaluated once more WITHOUT them and each row is checked against
-    // the contract of fgoicp_bounds_submit_cut — at or above its threshold T in the exact evaluation: {T, T} was reported; below: the exact bits.
+    // the contract of fgoicp_bounds_submit_cut — at or above its threshold T in the exact evaluation: {T, T} was reported; below: the exact bits —
+    // a terminal row (fgoicp_bounds_submit_leaf) by its own rule: "at or above" is said of its UPPER bound.
     // The answers handed on are the first run's, so the search goes on as it would; the tally is printed when the context is destroyed.
     const bool cut_verify = [] { const char* e = dev_env("FGOICP_CUT_VERIFY"); return e && std::atoi(e) != 0; }();  // (read per window: a test toggles it)
     if (cut_verify && sl.win_cut) {
@@ -298,7 +305,8 @@ static int tick_wait_window(fgoicp_ctx* c, fgoicp_ctx::TickSlot& sl) {
             for (int v = 0; v < (ts.dual ? 2 : 1); ++v) {
                 const int r = v ? ts.out1 : ts.out0;
                 const float T = v ? ts.cut1 : ts.cut0;
-                const bool above = sl.h_lb[r] >= T;
+                const bool term = (ts.term & (v ? kSubTerm1 : kSubTerm0)) != 0u;
+                const bool above = (term ? sl.h_ub[r] : sl.h_lb[r]) >= T;
                 const bool ok = above ? (lb[(size_t)r] == T && ub[(size_t)r] == T)
                                       : (std::memcmp(&lb[(size_t)r], &sl.h_lb[r], 4) == 0 && std::memcmp(&ub[(size_t)r], &sl.h_ub[r], 4) == 0);
                 c->cut_verify_rows++;
@@ -324,7 +332,7 @@ static int tick_wait_window(fgoicp_ctx* c, fgoicp_ctx::TickSlot& sl) {
 
 // fgoicp_bounds_submit: all windows but the last are completed here, the last one stays in flight.
 int ctx_bounds_submit(fgoicp_ctx* c, int slot, int G, const float* R9, const float* rot_span, const int* fix_rot, const int* offsets,
-                      const float* tn4, const int* twin, const float* cut_above) {
+                      const float* tn4, const int* twin, const float* cut_above, const float* ub_below_span) {
     HIPCHK(hipSetDevice(c->device));
     fgoicp_ctx::TickSlot& sl = c->slots[slot];
     if (sl.inflight) { set_error("fgoicp_bounds_submit: slot still in flight (collect it first)"); return FGOICP_ERR_INVALID_ARG; }
@@ -335,7 +343,7 @@ int ctx_bounds_submit(fgoicp_ctx* c, int slot, int G, const float* R9, const flo
     int pos = 0;
     while (pos < sl.total) {
         int end = pos;
-        int rc = tick_enqueue_window(c, sl, G, R9, rot_span, fix_rot, offsets, tn4, twin, cut_above, pos, &end);
+        int rc = tick_enqueue_window(c, sl, G, R9, rot_span, fix_rot, offsets, tn4, twin, cut_above, ub_below_span, pos, &end);
         if (rc) return rc;
         if (end <= pos) break;
         pos = end;
@@ -1673,7 +1681,8 @@ static int ctx_create_impl(const float* tgt_xyz, size_t nt, const float* src_xyz
             CHK(hipMalloc(&sl.d_partials, sizeof(double2) * max_items));
             CHK(hipMalloc(&sl.d_cut_acc, sizeof(double) * 2 * (size_t)c->max_subcubes));
             CHK(hipMemset(sl.d_cut_acc, 0, sizeof(double) * 2 * (size_t)c->max_subcubes));  // bounds_finalize_kernel re-zeroes what a window used
-            CHK(hipMalloc(&sl.d_row_cut, sizeof(float) * (size_t)c->max_subcubes));
+            CHK(hipMalloc(&sl.d_row_cut, (sizeof(float) + sizeof(unsigned)) * (size_t)c->max_subcubes));
+            sl.d_row_term = reinterpret_cast<unsigned*>(sl.d_row_cut + c->max_subcubes);
             CHK(hipMalloc(&sl.d_cut_gate, sizeof(TickGate) * (size_t)c->max_subcubes));  // written per window, ahead of its bounds kernel
             if (k == 0 && !c->d_cut_stat) {
                 CHK(hipMalloc(&c->d_cut_stat, sizeof(unsigned long long) * kCutStatSlots));
@@ -1895,12 +1904,17 @@ int fgoicp_bounds_submit_twins(fgoicp_ctx* c, int slot, int G, const float* R9, 
 
 int fgoicp_bounds_submit_cut(fgoicp_ctx* c, int slot, int G, const float* R9, const float* rot_span, const int* fix_rot, const int* offsets,
                              const float* tn4, const int* twin, const float* cut_above) {
+    return fgoicp_bounds_submit_leaf(c, slot, G, R9, rot_span, fix_rot, offsets, tn4, twin, cut_above, nullptr);
+}
+
+int fgoicp_bounds_submit_leaf(fgoicp_ctx* c, int slot, int G, const float* R9, const float* rot_span, const int* fix_rot, const int* offsets,
+                              const float* tn4, const int* twin, const float* cut_above, const float* ub_below_span) {
     if (!c || slot < 0 || slot > 1 || G < 0 || (G > 0 && (!R9 || !rot_span || !fix_rot || !offsets || !tn4))) return FGOICP_ERR_INVALID_ARG;
     static const int zero[1] = {0};
     if (G == 0) offsets = zero;
     for (int g = 0; g < G; ++g)
         if (offsets[g + 1] < offsets[g] || offsets[0] != 0) { set_error("fgoicp_bounds_submit: offsets must start at 0 and be non-decreasing"); return FGOICP_ERR_INVALID_ARG; }
-    return ctx_bounds_submit(c, slot, G, R9, rot_span, fix_rot, offsets, tn4, twin, cut_above);
+    return ctx_bounds_submit(c, slot, G, R9, rot_span, fix_rot, offsets, tn4, twin, cut_above, ub_below_span);
 }
 
 int fgoicp_ctx_cut_stats(fgoicp_ctx* c, uint64_t* items_offered, uint64_t* items_cut, int reset) {

@@ -61,6 +61,7 @@ struct fgoicp_ctx {
         double2* d_partials = nullptr;           // [max_subcubes][nchunk1] {sum_ub, sum_lb}
         double* d_cut_acc = nullptr;             // early exit (fgoicp_bounds_submit_cut): 2 running sums per evaluation, zero between windows
         float* d_row_cut = nullptr;              // ... and the threshold of every output row
+        unsigned* d_row_term = nullptr;          // ... and whether the row is terminal (fgoicp_bounds_submit_leaf): the tail of d_row_cut's allocation
         fgoicp::TickGate* d_cut_gate = nullptr;  // ... and what an item waits for first: "finished" and "cutting" per evaluation
         bool win_cut = false;                    // the window in flight carries thresholds
         float *h_lb = nullptr, *h_ub = nullptr, *hd_lb = nullptr, *hd_ub = nullptr;  // pinned results of the window in flight
@@ -185,7 +186,7 @@ int ctx_bounds_multi(fgoicp_ctx* c, int G, const float* R9, const float* rot_spa
                      const float* tn4, float* lb_out, float* ub_out, const float* cut_above = nullptr);
 int ctx_cut_stats(fgoicp_ctx* c, uint64_t* items_offered, uint64_t* items_cut, int reset);
 int ctx_bounds_submit(fgoicp_ctx* c, int slot, int G, const float* R9, const float* rot_span, const int* fix_rot, const int* offsets, const float* tn4,
-                      const int* twin = nullptr, const float* cut_above = nullptr);
+                      const int* twin = nullptr, const float* cut_above = nullptr, const float* ub_below_span = nullptr);
 int ctx_bounds_collect(fgoicp_ctx* c, int slot, float* lb_out, float* ub_out);
 int ctx_set_inliers(fgoicp_ctx* c, size_t k);
 // Trimmed Go-ICP as fgoicp_solver_create and fgoicp_batch set a context up for trim fraction f: the context flags (curve order) and the

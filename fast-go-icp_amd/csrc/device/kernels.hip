@@ -268,9 +268,10 @@ constexpr int kTickXcds = 16;  // the XCC_ID field is 4 bits wide
 __device__ __forceinline__ void cut_prefill(const TickSub& sb, int s, int chunk_first, int chunk_end, int row_chunks, const TickCut& cut, double2* __restrict__ partials) {
     const bool cutting = sb.cut0 < kCutNone && (!sb.dual || sb.cut1 < kCutNone);
     if (chunk_first == 0) {
-        *reinterpret_cast<uint2*>(cut.gate + s) = make_uint2(0u, cutting ? kGateCutting : 0u);
+        *reinterpret_cast<uint2*>(cut.gate + s) = make_uint2(0u, (cutting ? kGateCutting : 0u) | sb.term << 1);
         cut.row_cut[sb.out0] = sb.cut0;
-        if (sb.dual) cut.row_cut[sb.out1] = sb.cut1;
+        cut.row_term[sb.out0] = sb.term & kSubTerm0;
+        if (sb.dual) { cut.row_cut[sb.out1] = sb.cut1; cut.row_term[sb.out1] = sb.term & kSubTerm1; }
     }
     if (!cutting) return;
     for (int chunk = chunk_first; chunk < chunk_end; ++chunk) {
@@ -319,8 +320,11 @@ __global__ __launch_bounds__(64) void tick_keys_kernel(const float4* __restrict_
             const int iy = (int)fminf(fmaxf((ry + sb.ty + g.off_y) * g.scale, 0.0f), (float)(g.dy - 1));
             const int iz = (int)fminf(fmaxf((rz + sb.tz + g.off_z) * g.scale, 0.0f), (float)(g.dz - 1));
             const float d = sqrtf(tier_lut[((size_t)(iz + 1) * g.py + (size_t)(iy + 1)) * g.px + (size_t)(ix + 1)]);
-            const float e_fix = fmaxf(d - kSqrt3 * sb.span, 0.0f);
-            const float e_rot = fmaxf(d - kSqrt3 * sb.span - 2.0f * gr.sin_half * sqrtf(cc.x * cc.x + cc.y * cc.y + cc.z * cc.z), 0.0f);
+            // (a terminal row runs its UPPER-bound sums against T: the same guess from the upper bound's term — no translation radius)
+            const float r_rot = 2.0f * gr.sin_half * sqrtf(cc.x * cc.x + cc.y * cc.y + cc.z * cc.z);
+            const bool term0 = (sb.term & kSubTerm0) != 0u, term1 = (sb.term & kSubTerm1) != 0u;
+            const float e_fix = fmaxf(d - (term0 ? 0.0f : kSqrt3 * sb.span), 0.0f);
+            const float e_rot = fmaxf(d - ((sb.dual ? term1 : term0) ? 0.0f : kSqrt3 * sb.span) - r_rot, 0.0f);
             bool heavy;
             if (sb.dual) heavy = e_fix * e_fix >= tier_level * sb.cut0 && e_rot * e_rot >= tier_level * sb.cut1;
             else heavy = (gr.fix_rot ? e_fix * e_fix : e_rot * e_rot) >= tier_level * sb.cut0;
@@ -976,8 +980,10 @@ __global__ __launch_bounds__(64) void bounds_finalize_kernel(const double2* __re
     if (threadIdx.x == 0) {
         float ubf = (float)u, lbf = (float)l;
         if (cut.row_cut) {  // fgoicp_bounds_submit_cut: a row at or above its threshold T reports {T, T}, whether the bounds kernel cut it short or not
+            // (a terminal row, fgoicp_bounds_submit_leaf: ... whose UPPER bound is at or above T.  ub >= lb sum by sum, so "lbf >= T" adds no
+            // row that was evaluated in full; it is what the "not evaluated" partials of a row that was cut short say — its ub sum is not one)
             const float T = cut.row_cut[s];
-            if (lbf >= T) lbf = ubf = T;
+            if (lbf >= T || (cut.row_term[s] && ubf >= T)) lbf = ubf = T;
         }
         out_ub[s] = ubf;
         out_lb[s] = lbf;

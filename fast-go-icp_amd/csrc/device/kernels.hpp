@@ -50,11 +50,14 @@ struct TickSub {     // one EVALUATION: a translation node + its rotation node, 
                      // submission: one lookup per point, both variants of the bound formulae (registration.cu:39-58)
     float cut0;      // cut_above of out0's group (fgoicp_bounds_submit_cut; +inf = none): once the lower-bound sums of the evaluation's
     float cut1;      // finished items reach it, the remaining items are not evaluated (dual: both variants must have reached theirs)
-    int pad_[2];
+    unsigned term;   // kSubTerm0 / kSubTerm1: the row out0 / out1 is TERMINAL (fgoicp_bounds_submit_leaf): the sums that are run against its
+                     // threshold, and the bound that decides {T, T}, are the UPPER bound's
+    int pad_;
 };
+constexpr unsigned kSubTerm0 = 1u, kSubTerm1 = 2u;
 static_assert(sizeof(TickSub) == 48, "TickSub is copied in 16-byte units");
-// Early exit (fgoicp_bounds_submit_cut): acc = 2 doubles per evaluation (sum of the lower-bound partials of its finished items, per
-// variant; zero on entry, re-zeroed by bounds_finalize_kernel), row_cut = the threshold of every output row (written ahead of the
+// Early exit (fgoicp_bounds_submit_cut): acc = 2 doubles per evaluation (sum of the lower-bound partials of its finished items — of a
+// terminal row: the upper-bound partials — per variant; zero on entry, re-zeroed by bounds_finalize_kernel), row_cut = the threshold of every output row (written ahead of the
 // bounds kernel, applied by bounds_finalize_kernel), stat = {items not evaluated} (optional).  acc == nullptr: off.
 constexpr int kCutStatSlots = 64;  // the counter is spread over this many words (one atomic per output row with skipped items)
 constexpr float kCutNone = 3.0e38f;  // thresholds at or above this (fgoicp_bounds_submit_cut: +inf) switch the early exit off
@@ -63,14 +66,16 @@ constexpr float kCutNone = 3.0e38f;  // thresholds at or above this (fgoicp_boun
 // also leaves the "not evaluated" partials of every chunk (tick_keys_kernel / tick_prefill_kernel).
 struct TickGate {
     unsigned done;      // 1 = the running sums have been seen at their thresholds (set by the bounds kernel; a stale 0 only costs time)
-    unsigned flags;     // kGateCutting
+    unsigned flags;     // kGateCutting, kGateTerm0, kGateTerm1
 };
 static_assert(sizeof(TickGate) == 8, "TickGate is read and written as one 8-byte word");
 constexpr unsigned kGateCutting = 1u;  // every variant of the evaluation has a threshold below kCutNone
+constexpr unsigned kGateTerm0 = 2u, kGateTerm1 = 4u;  // TickSub::term of the evaluation (kSubTerm0, kSubTerm1), one bit up
 struct TickCut {
     double* acc = nullptr;
     TickGate* gate = nullptr;             // per evaluation (see TickGate)
     float* row_cut = nullptr;
+    unsigned* row_term = nullptr;         // per output row: 1 = terminal, the row's rule is "upper bound >= T" (fgoicp_bounds_submit_leaf)
     unsigned long long* stat = nullptr;   // [kCutStatSlots]
     const unsigned* tier_split = nullptr; // items of the first tier of `sorted` (launch_tick_sort with tier_lut): the grid walks them before the others
     int probe = 0;                        // development build, FGOICP_CUT_PROBE: 1 = the running sums are not read (nothing is ever cut), 2 = not added to, 4 = the gate's `done` is not honoured

@@ -5,6 +5,8 @@
 //     int    Ops::bounds_multi(G, R9, rot_span, fix_rot, offsets, tnodes4, lb, ub, cut_above)   (fgoicp_bounds_multi)
 //     int    Ops::bounds_submit(slot, G, ...tnodes4, twin, cut_above) / bounds_collect(slot, lb, ub)  (fgoicp_bounds_submit_cut / _collect)
 //     bool   Ops::async()                                                            two slots available?
+//     int    Ops::bounds_submit_leaf(slot, G, ...tnodes4, twin, cut_above, ub_below_span)     OPTIONAL (fgoicp_bounds_submit_leaf): detected at
+//                                                                                    compile time, an Ops without it gets bounds_submit
 //     bool   Ops::twins()                                                            does bounds_submit evaluate a twin pair once? (then the memo is free)
 //     int    Ops::icp(R0, t0, max_iter, thr, &sse, R9, t3, &iters)                   (fgoicp_icp)
 //
@@ -133,6 +135,10 @@ struct DriverStats {
 enum { kScheduleSerial = 0, kScheduleRound = 1 };
 enum { kDriverOk = 0, kDriverExchangeFailed = 6 };
 
+// A translation node with a span below this is a LEAF of the inner BnB: never split (fgoicp.cpp:155).  One constant for the rule itself
+// (InnerTask::consume) and for what the operator is told about it (InnerTask::leaf_below), so the two cannot drift apart.
+constexpr float kTransLeafSpan = 0.1f;
+
 // ---- one inner (translation) BnB as a resumable task — fgoicp.cpp:102-174 -----------------------
 struct InnerTask {
     bool fix_rot = true;
@@ -182,10 +188,32 @@ struct InnerTask {
     //     the pass with the rotation fixed hands it to the trigger rule `ub < best_sse * 1.8` (:74) — T = 1.8 * start_sse, rounded up.
     // Both are exact whenever the outer loop looks at more than the comparison.  The child nodes (:163-166) inherit exact bounds:
     // they exist only below the threshold.
+    // The pass with the rotation fixed, tighter: T = min(that, best_ub).  A node whose lb is at or above the running best_ub is dropped
+    // (:151: best_ub >= best_error, both are minima over the same ub values and best_error also over start_sse), and a ub at or above
+    // best_ub cannot lower the minimum: a row answered T = best_ub leaves best_ub, best_error and best_t what the exact row leaves
+    // them.  best_ub only falls too.
     float cut_above() const {
         if (!fix_rot) return best_error;
-        return std::nextafter((float)((double)start_sse * 1.8), kHostInf);
+        const float trigger = std::nextafter((float)((double)start_sse * 1.8), kHostInf);
+        return cut_by_best_ub() && best_ub < trigger ? best_ub : trigger;
     }
+    static bool cut_by_best_ub() {  // development build, A/B: FGOICP_CUT_BEST_UB=0 = the trigger level alone
+        static const bool on = [] { const char* e = dev_env("FGOICP_CUT_BEST_UB"); return !e || std::atoi(e) != 0; }();
+        return on;
+    }
+    // Terminal rows (fgoicp_bounds_submit_leaf): a node whose translation span is below the value returned here is never split (:155), and
+    // the caller needs NEITHER bound of it once its UPPER bound is >= T = cut_above(): such a row may come back as {T, T} as well.
+    //   * its lb takes part in no decision: :151 and :155 both `continue` — whatever lb is, the node pushes no children, so nothing
+    //     inherits its bounds either (for a row that is cut, ub >= T also means that lb = T >= best_error sends it through :151);
+    //   * its ub is used in min_element / best_ub / best_error (:139-145) only: best_error and best_t change only for ub < best_error
+    //     (:143) and T >= best_error, so a row answered T changes neither, exactly like its exact ub >= T; best_ub = min of all ub is
+    //     handed on as described above — every consumer compares it against a value <= T, which T and any ub >= T decide alike;
+    //   * first minimum (std::min_element, :139): the index matters only when ub[idx_min] < best_error <= T, strictly below; rows
+    //     answered T are not below T, rows below T come back exact, so the first row that attains a minimum below T is the same row;
+    //   * staleness: best_error only falls while the task runs and start_sse is fixed, so T of the submission is >= every later
+    //     best_error: the argument also holds for a row that is looked up LATER (memo rows, look-ahead rows).
+    // ub >= lb per point and per fixed-order sum, so for a terminal row this rule subsumes the one above: one rule per row.
+    static constexpr float leaf_below() { return kTransLeafSpan; }
     // consumes the operator's {lb, ub} of the current batch (:139-169)
     void consume(const float* lb, const float* ub) {
         const size_t n = batch.size();
@@ -200,7 +228,7 @@ struct InnerTask {
         for (size_t i = 0; i < n; ++i) {
             if (lb[i] >= best_error) continue;  // :151
             const TransCube& tn = batch[i];
-            if (tn.span < 0.1f) continue;       // :155
+            if (tn.span < kTransLeafSpan) continue;  // :155
             const float span = tn.span / 2.0f;
             for (char j = 0; j < 8; ++j)
                 cand.push(TransCube(tn.t.x - span + (j >> 0 & 1) * tn.span, tn.t.y - span + (j >> 1 & 1) * tn.span,
@@ -1042,6 +1070,7 @@ private:
         std::vector<float> R9, spans, tn4, lb, ub;
         std::vector<int> fix, offsets;
         std::vector<float> cut;        // per group: InnerTask::cut_above() of its task
+        std::vector<float> leaf;       // per group: InnerTask::leaf_below() — rows with a smaller span are terminal
         std::vector<int> twin;         // per subcube: the same translation node in the paired task's batch (or -1)
         std::vector<std::vector<std::pair<int, int>>> pair_twins;  // per (UB, LB) pair: {row in the UB group, row in the LB group}
         bool inflight = false;
@@ -1180,6 +1209,7 @@ private:
         const size_t total = (size_t)h.offsets.back();
         h.R9.resize(9 * G); h.spans.resize(G); h.fix.resize(G); h.tn4.resize(4 * total);
         h.cut.resize(G);
+        h.leaf.assign(G, InnerTask::leaf_below());
         const std::function<void(size_t)> pack_fn = [&](size_t a) {  // groups are independent: packed in parallel
             const int i = h.live[a];
             const Task& tk = *tasks[i];
@@ -1238,6 +1268,20 @@ private:
         }
         std::reverse(keep.begin(), keep.end());
         from.members.swap(keep);
+    }
+    // One submission of a half.  An operator that knows terminal rows (bounds_submit_leaf) is told which rows are leaves of the inner BnB;
+    // any other Ops gets the call it has always got.
+    template <class O>
+    static auto submit_leaf(O& ops, int slot, Half& h, int) -> decltype(ops.bounds_submit_leaf(slot, 0, h.R9.data(), h.spans.data(), h.fix.data(), h.offsets.data(), h.tn4.data(), h.twin.data(), h.cut.data(), h.leaf.data())) {
+        return ops.bounds_submit_leaf(slot, (int)h.live.size(), h.R9.data(), h.spans.data(), h.fix.data(), h.offsets.data(), h.tn4.data(), h.twin.data(), h.cut.data(), h.leaf.data());
+    }
+    template <class O>
+    static int submit_leaf(O& ops, int slot, Half& h, long) {
+        return ops.bounds_submit(slot, (int)h.live.size(), h.R9.data(), h.spans.data(), h.fix.data(), h.offsets.data(), h.tn4.data(), h.twin.data(), h.cut.data());
+    }
+    int submit_half(int slot, Half& h) {
+        if (use_cut_) return submit_leaf(ops_, slot, h, 0);
+        return ops_.bounds_submit(slot, (int)h.live.size(), h.R9.data(), h.spans.data(), h.fix.data(), h.offsets.data(), h.tn4.data(), h.twin.data(), nullptr);
     }
     void consume_half(Half& h, std::vector<Task*>& tasks, bool par) {
         const std::function<void(size_t)> push_fn = [&](size_t k) {
@@ -1303,7 +1347,7 @@ private:
                     const bool more = !h[k].members.empty() && prepare_half(h[k], tasks, cubes, par, ops_.twins());
                     if (tick_hook_) tick_hook_();  // (tasks that have just ended are marked done by now)
                     if (more) {
-                        int rc = ops_.bounds_submit(k, (int)h[k].live.size(), h[k].R9.data(), h[k].spans.data(), h[k].fix.data(), h[k].offsets.data(), h[k].tn4.data(), h[k].twin.data(), use_cut_ ? h[k].cut.data() : nullptr);
+                        int rc = submit_half(k, h[k]);
                         if (rc) return rc;
                         h[k].inflight = true;
                     }

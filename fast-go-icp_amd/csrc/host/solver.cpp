@@ -25,6 +25,10 @@ struct HipOps {
                       const int* twin, const float* cut_above) {
         return ctx_bounds_submit(ctx, slot, G, R9, rot_span, fix_rot, offsets, tn4, twin, cut_above);
     }
+    int bounds_submit_leaf(int slot, int G, const float* R9, const float* rot_span, const int* fix_rot, const int* offsets, const float* tn4,
+                           const int* twin, const float* cut_above, const float* ub_below_span) {
+        return ctx_bounds_submit(ctx, slot, G, R9, rot_span, fix_rot, offsets, tn4, twin, cut_above, ub_below_span);
+    }
     int bounds_collect(int slot, float* lb, float* ub) { return ctx_bounds_collect(ctx, slot, lb, ub); }
     bool async() const { return pipeline; }
     bool twins() const { return true; }

@@ -518,9 +518,11 @@ class Registration:
                    "fgoicp_bounds_multi")
         return [(lb[offs[g]:offs[g + 1]], ub[offs[g]:offs[g + 1]]) for g in range(G)]
 
-    def compute_bounds_cut(self, Rs, rot_spans, fix_rots, tnode_groups, cut_above, twin=None, slot=0):
+    def compute_bounds_cut(self, Rs, rot_spans, fix_rots, tnode_groups, cut_above, twin=None, slot=0, ub_below_span=None):
         """fgoicp_bounds_submit_cut + fgoicp_bounds_collect: as compute_bounds_multi, but a subcube of group g whose lower bound is
-        >= cut_above[g] comes back as lb = ub = cut_above[g] (np.inf: exact).  twin: optional array over all subcubes (-1 = none)."""
+        >= cut_above[g] comes back as lb = ub = cut_above[g] (np.inf: exact).  twin: optional array over all subcubes (-1 = none).
+        ub_below_span (fgoicp_bounds_submit_leaf): per group, subcubes with a translation span below it are terminal — such a row comes
+        back as lb = ub = cut_above[g] once its UPPER bound is >= cut_above[g]."""
         G = len(Rs)
         Rg = np.concatenate([to_glm(R) for R in Rs]).astype(np.float32) if G else np.zeros(0, np.float32)
         spans = np.asarray(rot_spans, dtype=np.float32)
@@ -534,9 +536,14 @@ class Registration:
         tw = None if twin is None else np.ascontiguousarray(twin, dtype=np.int32)
         lb = np.empty(len(tn), dtype=np.float32)
         ub = np.empty(len(tn), dtype=np.float32)
-        _lib.check(self._lib.fgoicp_bounds_submit_cut(self._h, int(slot), G, _fp(Rg), _fp(spans), fr.ctypes.data_as(_lib.c_int_p), offs.ctypes.data_as(_lib.c_int_p),
-                                                      _fp(tn), None if tw is None else tw.ctypes.data_as(_lib.c_int_p), None if cut is None else _fp(cut)),
-                   "fgoicp_bounds_submit_cut")
+        args = (self._h, int(slot), G, _fp(Rg), _fp(spans), fr.ctypes.data_as(_lib.c_int_p), offs.ctypes.data_as(_lib.c_int_p),
+                _fp(tn), None if tw is None else tw.ctypes.data_as(_lib.c_int_p), None if cut is None else _fp(cut))
+        if ub_below_span is None:
+            _lib.check(self._lib.fgoicp_bounds_submit_cut(*args), "fgoicp_bounds_submit_cut")
+        else:
+            leaf = np.ascontiguousarray(ub_below_span, dtype=np.float32)
+            assert len(leaf) == G
+            _lib.check(self._lib.fgoicp_bounds_submit_leaf(*args, _fp(leaf)), "fgoicp_bounds_submit_leaf")
         _lib.check(self._lib.fgoicp_bounds_collect(self._h, int(slot), _fp(lb), _fp(ub)), "fgoicp_bounds_collect")
         return [(lb[offs[g]:offs[g + 1]], ub[offs[g]:offs[g + 1]]) for g in range(G)]
 

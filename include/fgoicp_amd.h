@@ -152,6 +152,21 @@ int fgoicp_bounds_submit_twins(fgoicp_ctx* ctx, int slot, int G, const float* R9
  */
 int fgoicp_bounds_submit_cut(fgoicp_ctx* ctx, int slot, int G, const float* R9, const float* rot_span, const int* fix_rot,
                              const int* offsets, const float* tnodes4, const int* twin, const float* cut_above);
+/*
+ * The same with one more hint: ub_below_span[g] = S (one per group; 0, or ub_below_span = NULL: none — the call is then
+ * fgoicp_bounds_submit_cut) says that a subcube of group g whose translation span is below S is TERMINAL for the caller: it is never split,
+ * so its lower bound takes part in no decision of the caller's, and its upper bound only where it is below T = cut_above[g] (a leaf of the
+ * inner branch-and-bound, span < 0.1: fgoicp.cpp:139-145, :151, :155; csrc/host/driver.hpp InnerTask::leaf_below).  For such a row the
+ * exact bounds do not matter once its UPPER bound is >= T: it comes back as lb = ub = T.  Every term of the upper-bound sum is >= 0 and
+ * >= the lower-bound term of the same point, so the kernel stops evaluating a terminal subcube once the UPPER-bound sums of its finished
+ * items have reached T — much earlier than the lower-bound sums would, which for a leaf that survives often never do.
+ * One rule per row, deterministic either way: a terminal row is {T, T} if its upper bound is >= T (which subsumes "lower bound >= T"),
+ * cut short or not; every other row follows fgoicp_bounds_submit_cut; a row that is not answered {T, T} is bit-identical to
+ * fgoicp_bounds_submit_twins.  The two rows of a twin pair are the same node: each follows the rule of its own group.  Without cut_above
+ * the hint has no effect; trimmed contexts ignore it as they ignore cut_above.
+ */
+int fgoicp_bounds_submit_leaf(fgoicp_ctx* ctx, int slot, int G, const float* R9, const float* rot_span, const int* fix_rot,
+                              const int* offsets, const float* tnodes4, const int* twin, const float* cut_above, const float* ub_below_span);
 int fgoicp_bounds_collect(fgoicp_ctx* ctx, int slot, float* lb_out, float* ub_out);
 /* Work items (subcube x chunk of source points) of the submissions that carried thresholds since the last reset, and how many of them
  * the early exit did not evaluate (measurement: bench.py prices the kernel on the items it evaluated).  Call between submissions. */
