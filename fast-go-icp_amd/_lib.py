@@ -150,6 +150,21 @@ class ClusterInfo(C.Structure):
         self.struct_size = C.sizeof(ClusterInfo)  # the library writes no byte beyond it
 
 
+class SegmentModel(C.Structure):
+    _fields_ = [("candidates", C.c_uint64), ("sample", C.c_uint32 * 3), ("hypothesis", C.c_uint32), ("hypothesis_inliers", C.c_uint64), ("inliers", C.c_uint64),
+                ("hypothesis_plane", C.c_double * 4), ("plane", C.c_double * 4), ("pivot", C.c_double * 3), ("sum_u", C.c_double * 3), ("sum_uu", C.c_double * 6)]
+
+
+class SegmentInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("points", C.c_uint64), ("planes", C.c_uint64), ("on_planes", C.c_uint64), ("kept", C.c_uint64), ("iterations", C.c_int),
+                ("max_planes", C.c_int), ("refit", C.c_int), ("keep_planes", C.c_int), ("min_inliers", C.c_uint64), ("seed", C.c_uint64),
+                ("distance_threshold", C.c_double)]
+
+    def __init__(self):
+        super().__init__()
+        self.struct_size = C.sizeof(SegmentInfo)  # the library writes no byte beyond it
+
+
 OUTLIER_STATISTICAL = 0
 OUTLIER_RADIUS = 1
 
@@ -174,6 +189,11 @@ _SIGS = {
                                                C.POINTER(FpsInfo)]),
     "fgoicp_cluster_dbscan": (C.c_int, [c_float_p, C.c_size_t, C.c_float, C.c_int, C.c_size_t, C.c_int, c_float_p, C.c_size_t, c_uint32_p, C.POINTER(C.c_int32), c_uint32_p,
                                         C.POINTER(C.c_uint64), C.c_size_t, C.POINTER(ClusterInfo)]),
+    "fgoicp_segment_planes": (C.c_int, [c_float_p, C.c_size_t, C.c_float, C.c_int, C.c_uint64, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, c_float_p, C.c_size_t,
+                                        c_uint32_p, C.POINTER(C.c_int32), C.POINTER(SegmentModel), C.c_size_t, C.c_size_t, C.POINTER(SegmentInfo)]),
+    "fgoicp_segment_hypotheses": (C.c_int, [c_float_p, C.c_size_t, c_uint32_p, C.c_size_t, C.c_int, C.c_uint64, C.c_int, c_uint32_p, C.POINTER(C.c_double), c_uint8_p]),
+    "fgoicp_segment_fit_from_moments": (C.c_int, [C.c_uint64, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                                  C.POINTER(C.c_double)]),
     "fgoicp_lut_read": (C.c_int, [C.c_void_p, c_float_p, C.c_size_t]),
     "fgoicp_lut_search": (C.c_int, [C.c_void_p, c_float_p, C.c_size_t, c_float_p]),
     "fgoicp_lut_nodes": (C.c_int, [C.c_void_p, c_int_p, C.c_size_t, c_float_p]),

@@ -140,6 +140,14 @@ struct Config {
         float target_cluster_eps = 0.0f, source_cluster_eps = 0.0f;
         int target_cluster_min_points = 10, source_cluster_min_points = 10;
         int target_cluster_min_size = 0, source_cluster_min_size = 0;
+        // EXTENSION: the dominant planes of a cloud removed after the outlier filter and before the clustering (fgoicp_segment_planes: the table
+        // under the object, the floor of the room).  *_plane_distance: the inlier distance in the files' units, absent or <= 0: off;
+        // *_plane_iterations: the hypotheses per plane; *_plane_count: the planes at most; *_plane_min_fraction: a plane needs at least
+        // ceil(fraction x points) inliers.  A value that is not a number is refused.
+        float target_plane_distance = 0.0f, source_plane_distance = 0.0f;
+        int target_plane_iterations = 1000, source_plane_iterations = 1000;
+        int target_plane_count = 1, source_plane_count = 1;
+        double target_plane_min_fraction = 0.1, source_plane_min_fraction = 0.1;
     } params;
 
     explicit Config(const std::string& toml_filepath) {
@@ -235,6 +243,14 @@ struct Config {
             params.source_cluster_min_points = whole("source_cluster_min_points", 10.0);
             params.target_cluster_min_size = count("target_cluster_min_size");
             params.source_cluster_min_size = count("source_cluster_min_size");
+            params.target_plane_distance = (float)strict("target_plane_distance", 0.0);
+            params.source_plane_distance = (float)strict("source_plane_distance", 0.0);
+            params.target_plane_iterations = whole("target_plane_iterations", 1000.0);
+            params.source_plane_iterations = whole("source_plane_iterations", 1000.0);
+            params.target_plane_count = whole("target_plane_count", 1.0);
+            params.source_plane_count = whole("source_plane_count", 1.0);
+            params.target_plane_min_fraction = strict("target_plane_min_fraction", 0.1);
+            params.source_plane_min_fraction = strict("source_plane_min_fraction", 0.1);
             auto clampf = [](float x, float lo, float hi) { return x < hi ? (x > lo ? x : lo) : hi; };
             params.target_subsample = clampf(params.target_subsample, 1e-5f, 1.0f);  // utilities.hpp:101-104
             params.source_subsample = clampf(params.source_subsample, 1e-5f, 1.0f);
@@ -433,7 +449,7 @@ inline void write_result_toml(const std::string& path, const icp::mat3& R, const
 // the column names — then one line per registered source point, in the order the cloud was loaded (after source_subsample): its coordinates
 // as loaded, the index of its nearest target point (into the target as loaded), its distance to it in the files' units
 // (sqrt(dist2) / scaling_factor) and 1 if the optimum counts it as an inlier.  Points and indices refer to the clouds AS REGISTERED: with
-// params.source_voxel / params.target_voxel those are the voxel grids' centroids in their row order, not the points of the files, and with params.*_outlier_knn or params.*_cluster_eps the rows the filter kept, in their order;
+// params.source_voxel / params.target_voxel those are the voxel grids' centroids in their row order, not the points of the files, and with params.*_outlier_knn, params.*_plane_distance or params.*_cluster_eps the rows the filter kept, in their order;
 // with params.source_points / params.target_points the sampled points in pick order.
 inline void write_alignment_txt(const std::string& path, const std::vector<icp::vec3>& src, const uint32_t* idx, const float* dist2, const uint8_t* inlier,
                                 const fgoicp_alignment_summary& s) {

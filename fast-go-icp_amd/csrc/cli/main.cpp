@@ -64,6 +64,44 @@ static void outlier_filter(std::vector<icp::vec3>& pc, int knn, float std_ratio,
     pc.swap(out);
 }
 
+// params.*_plane_distance: the cloud without the points of its dominant planes (fgoicp_segment_planes on device 0, refitted planes, the rest
+// kept) — after the outlier filter and before the clustering, which a support plane would otherwise join into one component.  A plane needs
+// ceil(min_fraction x points) inliers; none of that size leaves the cloud as it is.  A refused call, and a filter that keeps no point, is an
+// error of the configuration: exit code 1.
+static void plane_filter(std::vector<icp::vec3>& pc, float distance, int iterations, int count, double min_fraction, long long seed, const char* which) {
+    if (!(distance > 0.0f)) return;
+    const double want = std::ceil(min_fraction * (double)pc.size());
+    const size_t min_inliers = want > 0.0 ? (want < 9e18 ? (size_t)want : (size_t)9e18) : 0;
+    std::vector<icp::vec3> out(pc.size());
+    std::vector<fgoicp_segment_model_t> models(16);
+    fgoicp_segment_info_t si{};
+    si.struct_size = sizeof(si);
+    const int rc = fgoicp_segment_planes(&pc.data()->x, pc.size(), distance, iterations, (uint64_t)seed, count, min_inliers, 1, 0, 0, &out.data()->x, out.size(), nullptr,
+                                         nullptr, models.data(), models.size(), sizeof(fgoicp_segment_model_t), &si);
+    if (rc != FGOICP_OK) {
+        icp::Logger(icp::LogLevel::Error) << "params." << which << "_plane_distance = " << distance << ": status " << rc << ": " << fgoicp_last_error();
+        std::exit(1);
+    }
+    if (si.kept == 0) {
+        icp::Logger(icp::LogLevel::Error) << "params." << which << "_plane_distance = " << distance << ": the filter keeps no point (" << si.planes << " planes hold all "
+                                          << si.on_planes << " points)";
+        std::exit(1);
+    }
+    icp::Logger log(icp::LogLevel::Info);
+    log << "Plane filter (" << which << "): " << pc.size() << " -> " << si.kept << " points, distance " << distance << ", " << iterations << " hypotheses: ";
+    if (si.planes == 0) {
+        log << "no plane of at least " << (min_inliers > 3 ? min_inliers : (size_t)3) << " points: unchanged";
+        return;
+    }
+    log << si.planes << (si.planes == 1 ? " plane of " : " planes of ");
+    for (uint64_t j = 0; j < si.planes; ++j) log << (j == 0 ? "" : (j + 1 == si.planes ? " and " : ", ")) << models[(size_t)j].inliers;
+    const double* p = models[0].plane;
+    auto tidy = [](double v) { return std::fabs(v) < 5e-7 ? 0.0 : v; };  // (six digits are printed: no "-0" and no 1e-09 beside a 1)
+    log << " points, normal (" << tidy(p[0]) << " " << tidy(p[1]) << " " << tidy(p[2]) << "), offset " << tidy(p[3]);
+    out.resize((size_t)si.kept);
+    pc.swap(out);
+}
+
 // params.*_cluster_eps: the cloud replaced by the points fgoicp_cluster_dbscan keeps (device 0) — its largest cluster, or with
 // params.*_cluster_min_size >= 1 every cluster of at least that many points — after the outlier filter and before the sampling and any solver:
 // everything downstream sees the filtered cloud.  A refused call, and a filter that keeps no point, is an error of the configuration: exit code 1.
@@ -158,6 +196,10 @@ static int run_batch(const std::string& list_file) {
         voxel_thin(pcs[i], c.params.source_voxel, "source");
         outlier_filter(pct[i], c.params.target_outlier_knn, c.params.target_outlier_std, c.params.target_outlier_radius, "target");
         outlier_filter(pcs[i], c.params.source_outlier_knn, c.params.source_outlier_std, c.params.source_outlier_radius, "source");
+        plane_filter(pct[i], c.params.target_plane_distance, c.params.target_plane_iterations, c.params.target_plane_count, c.params.target_plane_min_fraction,
+                     c.params.seed < 0 ? 0 : c.params.seed, "target");
+        plane_filter(pcs[i], c.params.source_plane_distance, c.params.source_plane_iterations, c.params.source_plane_count, c.params.source_plane_min_fraction,
+                     c.params.seed < 0 ? 1 : c.params.seed + 1, "source");
         cluster_filter(pct[i], c.params.target_cluster_eps, c.params.target_cluster_min_points, c.params.target_cluster_min_size, "target");
         cluster_filter(pcs[i], c.params.source_cluster_eps, c.params.source_cluster_min_points, c.params.source_cluster_min_size, "source");
         farthest_sample(pct[i], c.params.target_points, "target");
@@ -272,6 +314,10 @@ int main(int argc, char* argv[]) {
     voxel_thin(pcs, config.params.source_voxel, "source");
     outlier_filter(pct, config.params.target_outlier_knn, config.params.target_outlier_std, config.params.target_outlier_radius, "target");
     outlier_filter(pcs, config.params.source_outlier_knn, config.params.source_outlier_std, config.params.source_outlier_radius, "source");
+    plane_filter(pct, config.params.target_plane_distance, config.params.target_plane_iterations, config.params.target_plane_count,
+                 config.params.target_plane_min_fraction, config.params.seed < 0 ? 0 : config.params.seed, "target");
+    plane_filter(pcs, config.params.source_plane_distance, config.params.source_plane_iterations, config.params.source_plane_count,
+                 config.params.source_plane_min_fraction, config.params.seed < 0 ? 1 : config.params.seed + 1, "source");
     cluster_filter(pct, config.params.target_cluster_eps, config.params.target_cluster_min_points, config.params.target_cluster_min_size, "target");
     cluster_filter(pcs, config.params.source_cluster_eps, config.params.source_cluster_min_points, config.params.source_cluster_min_size, "source");
     farthest_sample(pct, config.params.target_points, "target");

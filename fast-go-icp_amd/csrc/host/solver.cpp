@@ -12,6 +12,7 @@
 #include "../../../include/fgoicp_amd.h"
 #include "../device/ctx.hpp"
 #include "driver.hpp"
+#include "segment.hpp"
 
 namespace fgoicp {
 
@@ -373,6 +374,16 @@ int fgoicp_information_from_moments(uint64_t n, const double* sum_q3, const doub
     if (!(scale > 0.0f) || !std::isfinite(scale)) { set_error("fgoicp_information_from_moments: scale must be a positive finite number"); return FGOICP_ERR_INVALID_ARG; }
     information_from_moments(n, sum_q3, sum_qq6, offset3, scale, info36, sum_q3_out, sum_qq6_out);
     return FGOICP_OK;
+}
+
+int fgoicp_segment_hypotheses(const float* xyz, size_t n, const uint32_t* candidates_or_NULL, size_t m, int iterations, uint64_t seed, int peel, uint32_t* sample_K3,
+                              double* plane_K4, uint8_t* degenerate_K) {
+    return abi_guard("fgoicp_segment_hypotheses",
+                     [&] { return segment_hypotheses_entry(xyz, n, candidates_or_NULL, m, iterations, seed, peel, sample_K3, plane_K4, degenerate_K); });
+}
+
+int fgoicp_segment_fit_from_moments(uint64_t count, const double* pivot3, const double* sum_u3, const double* sum_uu6, const double* toward4_or_NULL, double* plane4) {
+    return segment_fit_entry(count, pivot3, sum_u3, sum_uu6, toward4_or_NULL, plane4);
 }
 
 int fgoicp_solver_preproc(const fgoicp_solver* s, float* offs6, float* scale, float* bounds6) {

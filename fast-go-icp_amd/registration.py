@@ -161,6 +161,90 @@ def cluster_dbscan(points, eps, min_points=10, keep_min_size=0, device=0, return
     return out, label, nbr, size[:int(info.clusters)].copy(), idx[:m].copy(), d
 
 
+SEGMENT_TILE = 1024   # points per block of the scoring kernel (csrc/device/segment_score.hpp kSegTile)
+SEGMENT_CHUNK = 256   # hypotheses the scoring kernel stages per pass over its tile (kSegChunk)
+
+
+def _whole(name, v, lo, hi):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+        raise TypeError(f"{name} must be an integer")
+    if not lo <= v <= hi:
+        raise ValueError(f"{name} must lie in [{lo}, {hi}]")
+    return int(v)
+
+
+def segment_planes(points, distance_threshold, iterations=1000, seed=0, max_planes=1, min_inliers=0, refit=True, keep="rest", device=0, return_map=False):
+    """fgoicp_segment_planes: up to max_planes planes peeled off the cloud by RANSAC — `iterations` three-point hypotheses per peel, drawn
+    from `seed` by a counter-based generator, all scored on the device in one pass in fp64; the winner is refitted to its inliers (refit) and
+    the points within distance_threshold of it get the plane's number.  Returns the points on no plane (keep="rest": the support plane
+    removed) or those on one (keep="planes"), in caller order, as an (m, 3) float32 array.  return_map=True returns (kept, label (n,) int32
+    with -1 = on no plane, kept_index (m,) uint32, models, info) with models a list of dict(candidates, sample (3,), hypothesis,
+    hypothesis_inliers, inliers, hypothesis_plane (4,), plane (4,), pivot (3,), sum_u (3,), sum_uu (6,)) and info = dict(points, planes,
+    on_planes, kept, iterations, max_planes, refit, keep_planes, min_inliers, seed, distance_threshold)."""
+    p = _cloud(points)
+    iterations = _whole("iterations", iterations, -2 ** 31, 2 ** 31 - 1)  # the call judges the ranges of the definition
+    max_planes = _whole("max_planes", max_planes, -2 ** 31, 2 ** 31 - 1)
+    seed = _whole("seed", seed, 0, 2 ** 64 - 1)
+    min_inliers = _whole("min_inliers", min_inliers, 0, 2 ** 63 - 1)
+    if keep not in ("rest", "planes"):
+        raise ValueError('keep must be "rest" or "planes"')
+    n = len(p)
+    cap = min(max(max_planes, 1), 16)
+    out = np.empty((n, 3), np.float32)
+    idx = np.empty(n, np.uint32) if return_map else None
+    label = np.empty(n, np.int32) if return_map else None
+    models = (_lib.SegmentModel * cap)() if return_map else None
+    ptr = lambda a, t: None if a is None else a.ctypes.data_as(t)
+    info = _lib.SegmentInfo()
+    _lib.check(_lib.load().fgoicp_segment_planes(_fp(p) if n else None, n, float(distance_threshold), iterations, seed, max_planes, min_inliers, 1 if refit else 0,
+                                                 1 if keep == "planes" else 0, int(device), _fp(out), n, ptr(idx, _lib.c_uint32_p), ptr(label, C.POINTER(C.c_int32)),
+                                                 models, cap, C.sizeof(_lib.SegmentModel), C.byref(info)), "fgoicp_segment_planes")
+    m = int(info.kept)
+    out = out[:m].copy()
+    if not return_map:
+        return out
+    found = []
+    for j in range(int(info.planes)):
+        mod = models[j]
+        found.append(dict(candidates=int(mod.candidates), sample=np.array(mod.sample, np.uint32), hypothesis=int(mod.hypothesis),
+                          hypothesis_inliers=int(mod.hypothesis_inliers), inliers=int(mod.inliers), hypothesis_plane=np.array(mod.hypothesis_plane, np.float64),
+                          plane=np.array(mod.plane, np.float64), pivot=np.array(mod.pivot, np.float64), sum_u=np.array(mod.sum_u, np.float64),
+                          sum_uu=np.array(mod.sum_uu, np.float64)))
+    d = {name: int(getattr(info, name)) for name, _ in _lib.SegmentInfo._fields_ if name not in ("struct_size", "distance_threshold")}
+    d["distance_threshold"] = float(info.distance_threshold)
+    return out, label, idx[:m].copy(), found, d
+
+
+def segment_hypotheses(points, iterations, seed=0, peel=0, candidates=None):
+    """fgoicp_segment_hypotheses (host only): the table of one peel of segment_planes — (sample (K, 3) uint32 caller indices, plane (K, 4)
+    float64 nx ny nz d, degenerate (K,) bool).  candidates: the ascending caller indices the peel draws from, None = every point."""
+    p = _cloud(points)
+    K = _whole("iterations", iterations, 1, 65536)
+    seed = _whole("seed", seed, 0, 2 ** 64 - 1)
+    peel = _whole("peel", peel, 0, 15)
+    cand = None if candidates is None else np.ascontiguousarray(candidates, dtype=np.uint32).reshape(-1)
+    sample = np.empty((K, 3), np.uint32)
+    plane = np.empty((K, 4), np.float64)
+    deg = np.empty(K, np.uint8)
+    _lib.check(_lib.load().fgoicp_segment_hypotheses(_fp(p) if len(p) else None, len(p), None if cand is None else cand.ctypes.data_as(_lib.c_uint32_p),
+                                                     len(p) if cand is None else len(cand), K, seed, peel, sample.ctypes.data_as(_lib.c_uint32_p),
+                                                     plane.ctypes.data_as(_lib.c_double_p), deg.ctypes.data_as(_lib.c_uint8_p)), "fgoicp_segment_hypotheses")
+    return sample, plane, deg.astype(bool)
+
+
+def segment_fit_from_moments(count, pivot, sum_u, sum_uu, toward=None):
+    """fgoicp_segment_fit_from_moments (host only): the refit of segment_planes — `count` points u = p - pivot with sums sum_u (3,) and sum_uu
+    (6,: xx xy xz yy yz zz) -> the plane (4,) float64 through pivot + mean whose normal is the eigenvector of the smallest eigenvalue of the
+    covariance, flipped towards the normal of `toward` (4,) when given."""
+    count = _whole("count", count, 0, 2 ** 64 - 1)
+    dp = lambda a: a.ctypes.data_as(_lib.c_double_p)
+    a, su, suu = (np.ascontiguousarray(x, dtype=np.float64).reshape(k) for x, k in ((pivot, 3), (sum_u, 3), (sum_uu, 6)))
+    tw = None if toward is None else np.ascontiguousarray(toward, dtype=np.float64).reshape(4)
+    plane = np.empty(4, np.float64)
+    _lib.check(_lib.load().fgoicp_segment_fit_from_moments(count, dp(a), dp(su), dp(suu), None if tw is None else dp(tw), dp(plane)), "fgoicp_segment_fit_from_moments")
+    return plane
+
+
 class Alignment:
     """EXTENSION: the alignment report of fgoicp_alignment / fgoicp_solver_alignment / fgoicp_batch_alignment.  Arrays in the caller's point
     order: indices (ns,) uint32 — nearest target point of every source point; dist2 (ns,) float32 — its squared distance in the frame the

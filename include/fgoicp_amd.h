@@ -680,6 +680,92 @@ int fgoicp_cluster_dbscan(const float* xyz, size_t n, float eps, int min_points,
                           float* out_xyz, size_t capacity_points, uint32_t* kept_index,
                           int32_t* label_n, uint32_t* neighbours_n, uint64_t* cluster_size, size_t capacity_clusters,
                           fgoicp_cluster_info_t* out);
+/*
+ * EXTENSION — plane segmentation on the device by RANSAC (no reference counterpart; Open3D: segment_plane(distance_threshold, ransac_n = 3,
+ * num_iterations), PCL: SACSegmentation with SACMODEL_PLANE).  Removes what makes the cluster filter useless on a real scan: the SUPPORT
+ * PLANE — the table under an object, the floor of a room — which joins everything that stands on it into one connected component.
+ * ("segment": fgoicp_plane_* is the point-to-plane refinement.)
+ *
+ * Inputs: n points (fp32 xyz triples, caller order), distance_threshold finite and > 0, K = iterations in [1, 65536], seed, max_planes in
+ * [1, 16], min_inliers, refit, keep_planes.  ALL arithmetic is IEEE fp64 on the fp32 coordinates converted to double, every operation rounded
+ * on its own in the order written — no contraction, no reciprocal — so numpy's float64 names the same inlier set for every point, those
+ * exactly at the threshold included.  T = (double)distance_threshold.  Every point starts with label -1.
+ *   peel j         j = 0, 1, ... < max_planes works on the candidates R_j: the caller indices whose label is still -1, ascending, m_j of
+ *                  them.  Peeling stops with no plane j when m_j < 3
+ *   hypothesis h   h = 0 .. K - 1 of peel j draws three numbers, s = 0, 1, 2, everything mod 2^64:
+ *                    u_s = mix64(seed + 0x9E3779B97F4A7C15 * ((j * K + h) * 3 + s + 1))
+ *                    mix64(z): z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  z ^= z >> 31
+ *                  (the splitmix64 finaliser) and its sample s is R_j[((u_s >> 32) * m_j) >> 32] (the product is below 2^63: n < 2^31).
+ *                  Counter based: any hypothesis can be formed alone
+ *   plane          a, b, c = the three sample points;  e1 = b - a, e2 = c - a;
+ *                  N = (e1y*e2z - e1z*e2y, e1z*e2x - e1x*e2z, e1x*e2y - e1y*e2x);  L2 = (Nx*Nx + Ny*Ny) + Nz*Nz;
+ *                  (nx, ny, nz) = N / sqrt(L2), three divisions;  d = -((nx*ax + ny*ay) + nz*az).  The sign is the cross product's
+ *   degenerate     two of the three samples are the same index, or L2 is not a positive finite number: the hypothesis counts 0 inliers,
+ *                  never wins, and its plane is reported as four +0.0
+ *   score          r_i = ((nx*x_i + ny*y_i) + nz*z_i) + d;  count_h = #{ i in R_j : |r_i| <= T }, the comparison is <= on fp64.  The winner
+ *                  has the largest count, a tie goes to the lowest h.  Peeling stops with no plane j when the winner's count is below
+ *                  max(min_inliers, 3)
+ *   refit          (refit != 0) pivot = the winner's first sample a; for every inlier of the winner u = p - a; nine sums, sum_u[3] and
+ *                  sum_uu[6] in the order xx xy xz yy yz zz, in the fixed order of the moment kernels: the term of caller index i sits at
+ *                  position i of an n-vector, every other position adds +0.0, blocks of 256 (oracle/np_restatement.py fixed_order_sum).
+ *                  The host forms mean = sum_u / count, C = sum_uu / count - mean mean^T, the unit eigenvector of C's smallest eigenvalue by
+ *                  symmetric Jacobi sweeps in fp64, flipped so that its dot product with the hypothesis normal is >= 0, and
+ *                  d = -((nx*qx + ny*qy) + nz*qz) with q = a + mean (fgoicp_segment_fit_from_moments).  The final inliers of plane j are
+ *                  the i in R_j with |r_i| <= T under the refitted plane.  refit == 0: the hypothesis plane and its inliers are final, the
+ *                  sums are reported as zero
+ *   label          the final inliers of plane j get label j
+ *   rows           keep_planes == 0: the points with label -1 (the rest: what a pipeline wants); keep_planes != 0: those with label >= 0.
+ *                  Caller order, bits verbatim
+ * The counts are integers and the sums have one order, so the outputs are a function of the input and the seed alone: two calls return the
+ * same bytes.  n < 3 is a valid call that finds no plane.
+ * Outputs, every array pointer may be NULL (all NULL: `out` alone):
+ *   out_xyz / kept_index  the rows and their caller indices; both hold capacity_points rows
+ *   label_n (n int32)     models (capacity_models entries of model_size bytes each, `planes` of them written)
+ * model_size = sizeof(fgoicp_segment_model_t) as the CALLER was compiled: entry j starts at byte j * model_size and no byte beyond
+ * min(model_size, the library's size) of it is written.  If out_xyz or kept_index is given and capacity_points < kept, or models is given
+ * and capacity_models < planes, the call returns FGOICP_ERR_TOO_LARGE with `out` filled, so a second call can be sized, and writes nothing to
+ * any array; n points and max_planes models always suffice.
+ * Refused with FGOICP_ERR_INVALID_ARG before any device work (one host pass over the cloud): a null xyz or n == 0, n >= 2^31, a non-finite
+ * coordinate (the message names the point), a threshold that is not finite or not > 0, iterations or max_planes out of range, a null `out`
+ * or a struct_size that is 0, ends before `distance_threshold` ends or is above 4096, models given with model_size 0, a device ordinal out
+ * of range.  No usable device: FGOICP_ERR_NO_DEVICE (no CPU fallback); allocation failure: FGOICP_ERR_OOM.  The call owns its stream and its
+ * one device allocation (about 40 bytes per point and 36 per hypothesis) and frees both before it returns; it touches no fgoicp_ctx, no
+ * global state and no knob and may be called from several threads.
+ */
+typedef struct fgoicp_segment_model_t {
+    uint64_t candidates;                   /* m_j */
+    uint32_t sample[3];                    /* the winner's three caller indices; sample[0] is the refit's pivot */
+    uint32_t hypothesis;                   /* the winning h */
+    uint64_t hypothesis_inliers, inliers;  /* the counts under the hypothesis plane and under the final one */
+    double   hypothesis_plane[4], plane[4]; /* nx ny nz d */
+    double   pivot[3];
+    double   sum_u[3], sum_uu[6];          /* the refit's sums over the hypothesis inliers (refit == 0: zero) */
+} fgoicp_segment_model_t;
+typedef struct fgoicp_segment_info_t {
+    uint32_t struct_size;        /* IN: sizeof(fgoicp_segment_info_t) as the CALLER was compiled; no byte beyond it is written, 0 is refused */
+    uint64_t points;             /* n */
+    uint64_t planes;             /* the planes found */
+    uint64_t on_planes;          /* the points with label >= 0 */
+    uint64_t kept;               /* rows of the output */
+    int      iterations, max_planes, refit, keep_planes;  /* as given; refit and keep_planes as 0 / 1 */
+    uint64_t min_inliers, seed;
+    double   distance_threshold; /* T: the double every |r| was compared with */
+} fgoicp_segment_info_t;
+int fgoicp_segment_planes(const float* xyz, size_t n, float distance_threshold, int iterations, uint64_t seed,
+                          int max_planes, size_t min_inliers, int refit, int keep_planes, int device,
+                          float* out_xyz, size_t capacity_points, uint32_t* kept_index, int32_t* label_n,
+                          fgoicp_segment_model_t* models, size_t capacity_models, size_t model_size,
+                          fgoicp_segment_info_t* out);
+/* The two host halves of the call, no device needed (the call itself runs these).  fgoicp_segment_hypotheses: the table of one peel —
+ * sample_K3 (3 caller indices per hypothesis), plane_K4 (nx ny nz d), degenerate_K (0 / 1) for h = 0 .. iterations - 1; candidates = the m
+ * ascending caller indices of R_peel, NULL = the identity list, m = n; every output may be NULL.  Refuses what the call refuses of the
+ * cloud, an m outside [1, n], iterations outside [1, 65536], a peel outside [0, 16) and candidates that are not ascending indices below n.
+ * fgoicp_segment_fit_from_moments: the refit — count, pivot, sum_u, sum_uu -> plane4, the normal flipped towards toward4's (NULL: as the
+ * iteration leaves it).  Refuses null pointers, count < 3 and moments that are not finite. */
+int fgoicp_segment_hypotheses(const float* xyz, size_t n, const uint32_t* candidates_or_NULL, size_t m, int iterations, uint64_t seed, int peel,
+                              uint32_t* sample_K3, double* plane_K4, uint8_t* degenerate_K);
+int fgoicp_segment_fit_from_moments(uint64_t count, const double* pivot3, const double* sum_u3, const double* sum_uu6, const double* toward4_or_NULL,
+                                    double* plane4);
 /* The operator context the solver drives (borrowed; valid until solver_destroy). */
 fgoicp_ctx* fgoicp_solver_ctx(fgoicp_solver* s);
 

@@ -1,0 +1,21 @@
+// TEST-ONLY: prints the plane-filter keys of a configuration as the CLI's parser (fast-go-icp_amd/csrc/cli/config.hpp) reads them; exit code 2
+// and the message when the parser refuses the file.
+#include <cstdio>
+
+#include "../../fast-go-icp_amd/csrc/cli/config.hpp"
+
+extern "C" const char* fgoicp_last_error(void) { return ""; }  // icp::check_status is never reached here
+
+int main(int argc, char** argv) {
+    if (argc != 2) return 3;
+    try {
+        cli::Config c(argv[1]);
+        std::printf("SEGMENT %.9g %.9g %d %d %d %d %.17g %.17g\n", c.params.target_plane_distance, c.params.source_plane_distance, c.params.target_plane_iterations,
+                    c.params.source_plane_iterations, c.params.target_plane_count, c.params.source_plane_count, c.params.target_plane_min_fraction,
+                    c.params.source_plane_min_fraction);
+        return 0;
+    } catch (const std::exception& e) {
+        std::printf("REFUSED %s\n", e.what());
+        return 2;
+    }
+}
