@@ -147,6 +147,21 @@ hipError_t bvh_upload(const BvhHost& h, BvhDevice* d) {
     return hipMemcpy(d->pts, h.pts.data(), h.pts.size() * sizeof(float4), hipMemcpyHostToDevice);
 }
 
+BvhHost bvh_build_host_xyz(const float* xyz, size_t n) {
+    std::vector<float4> p4(n);
+    for (size_t i = 0; i < n; ++i) p4[i] = make_float4(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], 0.f);
+    return bvh_build_host(p4.data(), n);
+}
+
+hipError_t bvh_upload_async(const BvhHost& h, const BvhDevice& d, hipStream_t stream, BvhView* view) {
+    *view = d.view();
+    hipError_t e = hipMemcpyAsync(d.box, h.box.data(), h.box.size() * sizeof(float4), hipMemcpyHostToDevice, stream);
+    if (e != hipSuccess) return e;
+    e = hipMemcpyAsync(d.pts, h.pts.data(), h.pts.size() * sizeof(float4), hipMemcpyHostToDevice, stream);
+    if (e != hipSuccess || h.slab.empty()) return e;
+    return hipMemcpyAsync(d.slab, h.slab.data(), h.slab.size() * sizeof(float4), hipMemcpyHostToDevice, stream);
+}
+
 void bvh_free(BvhDevice* d) {
     if (d->box) (void)hipFree(d->box);
     if (d->pts) (void)hipFree(d->pts);

@@ -56,4 +56,18 @@ struct BvhDevice {
 hipError_t bvh_upload(const BvhHost& h, BvhDevice* d);
 void bvh_free(BvhDevice* d);
 
+// The tree of a one-shot call (outlier.hip, cluster.hip) over the caller's own cloud, inside the call's arena (one_shot.hpp):
+BvhHost bvh_build_host_xyz(const float* xyz, size_t n);  // the xyz triples staged as float4, then bvh_build_host
+// the three arrays from the arena's planner, in this order (no slab: nullptr); the arena owns them, d is not for bvh_free
+template <class Plan>
+void bvh_take(Plan& plan, const BvhHost& h, BvhDevice* d) {
+    plan.take(d->box, h.box.size());
+    plan.take(d->pts, h.pts.size());
+    plan.take(d->slab, h.slab.size());
+    d->depth = h.depth;
+    d->first_leaf = h.first_leaf;
+}
+// after the allocation: enqueues the copies (none for an empty slab); *view = the tree as the kernels take it
+hipError_t bvh_upload_async(const BvhHost& h, const BvhDevice& d, hipStream_t stream, BvhView* view);
+
 }  // namespace fgoicp

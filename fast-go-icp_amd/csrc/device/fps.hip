@@ -1,5 +1,5 @@
 // Farthest-point sampling (fgoicp_farthest_point_sample; include/fgoicp_amd.h has the definition, DESIGN.md section 16 the launch chain).
-// One call = one stream + one device allocation of its own, both released before it returns; no fgoicp_ctx, no global state, no knobs.
+// A one-shot call: the frame every such call shares — what it owns, the common refusals, the arena — is one_shot.hpp.
 //
 //   host      the refusals (they need no device) and, in the same pass, the 16-byte records {x, y, z, D = +inf}
 //   step t    fps_step_kernel, m launches queued back to back on the call's stream, nothing between them but the kernel boundary:
@@ -23,9 +23,8 @@
 #include <string>
 #include <vector>
 
-#include "../../../include/fgoicp_amd.h"
-#include "../host/abi_guard.hpp"
 #include "dist_sq.hpp"
+#include "one_shot.hpp"
 
 namespace fgoicp {
 namespace {
@@ -125,72 +124,39 @@ __global__ __launch_bounds__(kFpsBlock) void fps_finish_kernel(const float4* __r
     }
 }
 
-struct FpsDevice {  // what the call owns on the device
-    hipStream_t stream = nullptr;
-    void* arena = nullptr;
-    ~FpsDevice() {  // (an early return may leave copies into the caller's arrays in flight)
-        if (stream) (void)hipStreamSynchronize(stream);
-        if (arena) (void)hipFree(arena);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-};
-
-#define FPSCHK(expr)                                                                                             \
-    do {                                                                                                         \
-        hipError_t e_ = (expr);                                                                                  \
-        if (e_ != hipSuccess) {                                                                                  \
-            set_error(std::string("fgoicp_farthest_point_sample: " #expr " failed: ") + hipGetErrorString(e_)); \
-            return e_ == hipErrorOutOfMemory ? FGOICP_ERR_OOM : FGOICP_ERR_HIP;                                   \
-        }                                                                                                        \
-    } while (0)
-
 int farthest_point_sample_impl(const float* xyz, size_t n, size_t m, size_t start_index, int device, float* out_xyz, uint32_t* sample_index, float* pick_dist2,
                                float* min_dist2_n, uint32_t* owner_n, fgoicp_fps_info_t* out) {
-    auto refuse = [](const std::string& what) { set_error("fgoicp_farthest_point_sample: " + what); return (int)FGOICP_ERR_INVALID_ARG; };
-    if (!xyz || n == 0) return refuse("the cloud must not be null or empty");
-    if (n >= ((size_t)1 << 31)) return refuse("more than 2^31 - 1 points");
-    if (m == 0 || m > n) return refuse("the sample count must lie in [1, the number of points]");
-    if (start_index >= n) return refuse("start_index must be below the number of points");
-    if (!out || out->struct_size < offsetof(fgoicp_fps_info_t, cover_dist2) || out->struct_size > 4096)
-        return refuse("out must not be null and out->struct_size = sizeof(fgoicp_fps_info_t)");
+    const char* const call = "fgoicp_farthest_point_sample";
+    if (const int rc = refuse_cloud_head(call, xyz, n)) return rc;
+    if (m == 0 || m > n) return refuse(call, "the sample count must lie in [1, the number of points]");
+    if (start_index >= n) return refuse(call, "start_index must be below the number of points");
+    if (const int rc = refuse_info(call, out, offsetof(fgoicp_fps_info_t, cover_dist2), "fgoicp_fps_info_t")) return rc;
     std::vector<float4> rec(n);
-    for (size_t i = 0; i < n; ++i) {
+    for (size_t i = 0; i < n; ++i) {  // the finite check and the records in one pass
         for (int a = 0; a < 3; ++a)
-            if (!std::isfinite(xyz[3 * i + a])) return refuse("point " + std::to_string(i) + " has a non-finite coordinate");
+            if (!std::isfinite(xyz[3 * i + a])) return refuse_non_finite(call, i);
         rec[i] = make_float4(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], INFINITY);
     }
+    if (const int rc = select_device(call, device)) return rc;
 
-    int ndev = 0;
-    const hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev <= 0) {
-        set_error(std::string("fgoicp_farthest_point_sample: no HIP device available (") + (e != hipSuccess ? hipGetErrorString(e) : "device count 0") +
-                  "); fgoicp_amd has no CPU path");
-        return FGOICP_ERR_NO_DEVICE;
-    }
-    if (device < 0 || device >= ndev) return refuse("device ordinal out of range");
-    FPSCHK(hipSetDevice(device));
-
-    FpsDevice d;
-    FPSCHK(hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking));
+    OneShot d(call);
+    ONECHK(call, hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking));
     const uint32_t n32 = (uint32_t)n, m32 = (uint32_t)m;
     const uint32_t per_point = (uint32_t)((n + kFpsBlock - 1) / kFpsBlock);
     const uint32_t nblocks = per_point < kFpsMaxBlocks ? per_point : kFpsMaxBlocks;  // above 1024 x 256 points a block loops over its slice
-    // the arena: every array starts on a 256-byte boundary
-    size_t total = 0;
-    auto take = [&](size_t bytes) { const size_t at = total; total += (bytes + 255) & ~(size_t)255; return at; };
-    const size_t at_rec = take(16 * n), at_keys = take(2 * 8 * (size_t)kFpsMaxBlocks), at_out = take(12 * m), at_idx = take(4 * m), at_pick = take(4 * m);
-    const size_t at_min = take(min_dist2_n ? 4 * n : 0), at_owner = take(owner_n ? 4 * n : 0), at_info = take(8);
-    FPSCHK(hipMalloc(&d.arena, total));
-    char* base = static_cast<char*>(d.arena);
-    float4* d_rec = reinterpret_cast<float4*>(base + at_rec);
-    long long* d_keys = reinterpret_cast<long long*>(base + at_keys);
-    float *d_out = reinterpret_cast<float*>(base + at_out), *d_pick = reinterpret_cast<float*>(base + at_pick);
-    float* d_min = min_dist2_n ? reinterpret_cast<float*>(base + at_min) : nullptr;
-    uint32_t *d_idx = reinterpret_cast<uint32_t*>(base + at_idx), *d_info = reinterpret_cast<uint32_t*>(base + at_info);
-    uint32_t* d_owner = owner_n ? reinterpret_cast<uint32_t*>(base + at_owner) : nullptr;
+    float4* d_rec;
+    long long* d_keys;
+    float *d_out, *d_pick, *d_min;  // d_min, d_owner: nullptr unless asked for
+    uint32_t *d_idx, *d_owner, *d_info;
+    Arena plan;
+    plan.take(d_rec, n); plan.take(d_keys, 2 * (size_t)kFpsMaxBlocks); plan.take(d_out, 3 * m); plan.take(d_idx, m); plan.take(d_pick, m);
+    plan.take(d_min, min_dist2_n ? n : 0); plan.take(d_owner, owner_n ? n : 0); plan.take(d_info, 2);
+    const size_t total = plan.total();
+    ONECHK(call, hipMalloc(&d.arena, total));
+    plan.place(d.arena);
 
-    FPSCHK(hipMemcpyAsync(d_rec, rec.data(), 16 * n, hipMemcpyHostToDevice, d.stream));
-    if (d_owner) FPSCHK(hipMemsetAsync(d_owner, 0, 4 * n, d.stream));  // (a point at an infinite fp32 distance from every sample is never lowered)
+    ONECHK(call, hipMemcpyAsync(d_rec, rec.data(), 16 * n, hipMemcpyHostToDevice, d.stream));
+    if (d_owner) ONECHK(call, hipMemsetAsync(d_owner, 0, 4 * n, d.stream));  // (a point at an infinite fp32 distance from every sample is never lowered)
     const dim3 block(kFpsBlock), grid(nblocks);
     for (uint32_t t = 0; t < m32; ++t) {  // the chain: step t reads the keys of step t - 1 and leaves its own in the other half
         const long long* prev = d_keys + (size_t)((t + 1u) & 1u) * kFpsMaxBlocks;
@@ -203,14 +169,14 @@ int farthest_point_sample_impl(const float* xyz, size_t n, size_t m, size_t star
     hipLaunchKernelGGL(fps_finish_kernel, dim3(d_min ? per_point : 1u), block, 0, d.stream, d_rec, n32, d_keys + (size_t)((m32 - 1u) & 1u) * kFpsMaxBlocks, nblocks, d_min,
                        d_info);
     uint32_t h_info[2] = {0u, 0u};
-    FPSCHK(hipMemcpyAsync(h_info, d_info, 8, hipMemcpyDeviceToHost, d.stream));
-    if (out_xyz) FPSCHK(hipMemcpyAsync(out_xyz, d_out, 12 * m, hipMemcpyDeviceToHost, d.stream));
-    if (sample_index) FPSCHK(hipMemcpyAsync(sample_index, d_idx, 4 * m, hipMemcpyDeviceToHost, d.stream));
-    if (pick_dist2) FPSCHK(hipMemcpyAsync(pick_dist2, d_pick, 4 * m, hipMemcpyDeviceToHost, d.stream));
-    if (min_dist2_n) FPSCHK(hipMemcpyAsync(min_dist2_n, d_min, 4 * n, hipMemcpyDeviceToHost, d.stream));
-    if (owner_n) FPSCHK(hipMemcpyAsync(owner_n, d_owner, 4 * n, hipMemcpyDeviceToHost, d.stream));
-    FPSCHK(hipStreamSynchronize(d.stream));
-    FPSCHK(hipGetLastError());
+    ONECHK(call, hipMemcpyAsync(h_info, d_info, 8, hipMemcpyDeviceToHost, d.stream));
+    if (out_xyz) ONECHK(call, hipMemcpyAsync(out_xyz, d_out, 12 * m, hipMemcpyDeviceToHost, d.stream));
+    if (sample_index) ONECHK(call, hipMemcpyAsync(sample_index, d_idx, 4 * m, hipMemcpyDeviceToHost, d.stream));
+    if (pick_dist2) ONECHK(call, hipMemcpyAsync(pick_dist2, d_pick, 4 * m, hipMemcpyDeviceToHost, d.stream));
+    if (min_dist2_n) ONECHK(call, hipMemcpyAsync(min_dist2_n, d_min, 4 * n, hipMemcpyDeviceToHost, d.stream));
+    if (owner_n) ONECHK(call, hipMemcpyAsync(owner_n, d_owner, 4 * n, hipMemcpyDeviceToHost, d.stream));
+    ONECHK(call, hipStreamSynchronize(d.stream));
+    ONECHK(call, hipGetLastError());
     if (h_info[0] > n32 || (h_info[0] == n32) != (m == n)) {
         set_error("fgoicp_farthest_point_sample: the device returned an inconsistent next index");
         return FGOICP_ERR_HIP;
@@ -222,8 +188,7 @@ int farthest_point_sample_impl(const float* xyz, size_t n, size_t m, size_t star
     full.start_index = start_index;
     full.next_index = h_info[0];
     std::memcpy(&full.cover_dist2, &h_info[1], 4);
-    full.struct_size = out->struct_size < sizeof(full) ? out->struct_size : (uint32_t)sizeof(full);
-    std::memcpy(out, &full, full.struct_size);
+    write_info(out, full);
     return FGOICP_OK;
 }
 

@@ -1,5 +1,5 @@
 // Voxel-grid downsampling (fgoicp_voxel_downsample; include/fgoicp_amd.h has the definition, DESIGN.md section 13 the pipeline).
-// One call = one stream + one device allocation of its own, both released before it returns; no fgoicp_ctx, no global state, no knobs.
+// A one-shot call: the frame every such call shares — what it owns, the common refusals, the arena — is one_shot.hpp.
 //
 //   host    finite check, origin (given, or the per-axis minimum), every cell in [0, 2^21) — the refusals need no device
 //   key     one thread per point: c = floor(((double)p - o) / v) per axis in IEEE fp64; sort key and caller index
@@ -27,9 +27,8 @@
 #include <cstring>
 #include <string>
 
-#include "../../../include/fgoicp_amd.h"
-#include "../host/abi_guard.hpp"
 #include "fixed_sum.hpp"
+#include "one_shot.hpp"
 
 namespace fgoicp {
 namespace {
@@ -179,38 +178,18 @@ int bit_width(uint32_t x) {
     return b;
 }
 
-struct VoxDevice {  // what the call owns on the device
-    hipStream_t stream = nullptr;
-    void* arena = nullptr;
-    ~VoxDevice() {  // (an early return may leave copies into the caller's arrays in flight)
-        if (stream) (void)hipStreamSynchronize(stream);
-        if (arena) (void)hipFree(arena);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-};
-
-#define VOXCHK(expr)                                                                                        \
-    do {                                                                                                    \
-        hipError_t e_ = (expr);                                                                             \
-        if (e_ != hipSuccess) {                                                                             \
-            set_error(std::string("fgoicp_voxel_downsample: " #expr " failed: ") + hipGetErrorString(e_)); \
-            return e_ == hipErrorOutOfMemory ? FGOICP_ERR_OOM : FGOICP_ERR_HIP;                              \
-        }                                                                                                   \
-    } while (0)
-
 int voxel_downsample_impl(const float* xyz, size_t n, float voxel_size, const float* origin3, int device, float* out_xyz, size_t capacity, uint32_t* voxel_of_point,
                           uint32_t* count_per_voxel, fgoicp_voxel_info_t* out) {
-    auto refuse = [](const std::string& what) { set_error("fgoicp_voxel_downsample: " + what); return (int)FGOICP_ERR_INVALID_ARG; };
-    if (!xyz || n == 0) return refuse("the cloud must not be null or empty");
-    if (n >= ((size_t)1 << 31)) return refuse("more than 2^31 - 1 points");
+    const char* const call = "fgoicp_voxel_downsample";
+    auto refuse = [call](const std::string& what) { return fgoicp::refuse(call, what); };
+    if (const int rc = refuse_cloud_head(call, xyz, n)) return rc;
     if (!(voxel_size > 0.0f) || !std::isfinite(voxel_size)) return refuse("voxel_size must be a positive finite number");
-    if (!out || out->struct_size < offsetof(fgoicp_voxel_info_t, max_points_per_voxel) || out->struct_size > 4096)
-        return refuse("out must not be null and out->struct_size = sizeof(fgoicp_voxel_info_t)");
+    if (const int rc = refuse_info(call, out, offsetof(fgoicp_voxel_info_t, max_points_per_voxel), "fgoicp_voxel_info_t")) return rc;
     float o[3] = {xyz[0], xyz[1], xyz[2]};
-    for (size_t i = 0; i < n; ++i)
+    for (size_t i = 0; i < n; ++i)  // the finite check and the per-axis minimum in one pass
         for (int a = 0; a < 3; ++a) {
             const float c = xyz[3 * i + a];
-            if (!std::isfinite(c)) return refuse("point " + std::to_string(i) + " has a non-finite coordinate");
+            if (!std::isfinite(c)) return refuse_non_finite(call, i);
             if (c < o[a]) o[a] = c;
         }
     if (origin3)
@@ -233,59 +212,47 @@ int voxel_downsample_impl(const float* xyz, size_t n, float voxel_size, const fl
     g.shift_z = g.shift_y + bit_width(cmax[1]);
     const unsigned end_bit = (unsigned)std::max(1, g.shift_z + bit_width(cmax[2]));
 
-    int ndev = 0;
-    const hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev <= 0) {
-        set_error(std::string("fgoicp_voxel_downsample: no HIP device available (") + (e != hipSuccess ? hipGetErrorString(e) : "device count 0") +
-                  "); fgoicp_amd has no CPU path");
-        return FGOICP_ERR_NO_DEVICE;
-    }
-    if (device < 0 || device >= ndev) return refuse("device ordinal out of range");
-    VOXCHK(hipSetDevice(device));
+    if (const int rc = select_device(call, device)) return rc;
 
-    VoxDevice d;
-    VOXCHK(hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking));
+    OneShot d(call);
+    ONECHK(call, hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking));
     const uint32_t n32 = (uint32_t)n;
     const size_t max_tiles = n / (kVoxTile / 2) + 1;  // a row of L > kVoxTile points has ceil(L / kVoxTile) < 2 L / kVoxTile tiles
     size_t sort_bytes = 0, scan_bytes = 0;
-    VOXCHK(rocprim::radix_sort_pairs(nullptr, sort_bytes, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, n, 0u, end_bit, d.stream));
-    VOXCHK(rocprim::inclusive_scan(nullptr, scan_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr, n, rocprim::plus<uint32_t>(), d.stream));
-    // the arena: every array starts on a 256-byte boundary.  After the sort the first key buffer is free: its halves hold the head flags
-    // and their scan; the first index buffer then holds the tile counts.
-    size_t total = 0;
-    auto take = [&](size_t bytes) { const size_t at = total; total += (bytes + 255) & ~(size_t)255; return at; };
-    const size_t at_xyz = take(12 * n), at_keys_a = take(8 * n), at_keys_b = take(8 * n), at_idx_a = take(4 * n), at_idx_b = take(4 * n);
-    const size_t at_start = take(4 * (n + 1)), at_vop = take(4 * n), at_counts = take(4 * n), at_tile_incl = take(4 * n), at_out = take(12 * n);
-    const size_t at_partials = take(sizeof(VoxPartial) * max_tiles), at_max = take(4), at_tmp = take(std::max(sort_bytes, scan_bytes));
-    VOXCHK(hipMalloc(&d.arena, total));
-    char* base = static_cast<char*>(d.arena);
-    float* d_xyz = reinterpret_cast<float*>(base + at_xyz);
-    uint64_t *keys_a = reinterpret_cast<uint64_t*>(base + at_keys_a), *keys_b = reinterpret_cast<uint64_t*>(base + at_keys_b);
-    uint32_t *idx_a = reinterpret_cast<uint32_t*>(base + at_idx_a), *idx_b = reinterpret_cast<uint32_t*>(base + at_idx_b);
+    ONECHK(call, rocprim::radix_sort_pairs(nullptr, sort_bytes, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, n, 0u, end_bit, d.stream));
+    ONECHK(call, rocprim::inclusive_scan(nullptr, scan_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr, n, rocprim::plus<uint32_t>(), d.stream));
+    float *d_xyz, *d_out;
+    uint64_t *keys_a, *keys_b;
+    uint32_t *idx_a, *idx_b, *start, *vop, *counts, *tile_incl, *d_max;
+    VoxPartial* partials;
+    char* tmp;
+    Arena plan;
+    plan.take(d_xyz, 3 * n); plan.take(keys_a, n); plan.take(keys_b, n); plan.take(idx_a, n); plan.take(idx_b, n);
+    plan.take(start, n + 1); plan.take(vop, n); plan.take(counts, n); plan.take(tile_incl, n); plan.take(d_out, 3 * n);
+    plan.take(partials, max_tiles); plan.take(d_max, 1); plan.take(tmp, std::max(sort_bytes, scan_bytes));
+    const size_t total = plan.total();
+    ONECHK(call, hipMalloc(&d.arena, total));
+    plan.place(d.arena);
+    // After the sort the first key buffer is free: its halves hold the head flags and their scan; the first index buffer then holds the
+    // tile counts.
     uint32_t *head = reinterpret_cast<uint32_t*>(keys_a), *row_incl = head + n, *tiles = idx_a;
-    uint32_t *start = reinterpret_cast<uint32_t*>(base + at_start), *vop = reinterpret_cast<uint32_t*>(base + at_vop);
-    uint32_t *counts = reinterpret_cast<uint32_t*>(base + at_counts), *tile_incl = reinterpret_cast<uint32_t*>(base + at_tile_incl);
-    float* d_out = reinterpret_cast<float*>(base + at_out);
-    VoxPartial* partials = reinterpret_cast<VoxPartial*>(base + at_partials);
-    uint32_t* d_max = reinterpret_cast<uint32_t*>(base + at_max);
-    void* tmp = base + at_tmp;
 
     const dim3 block(kVoxBlock), per_point((unsigned)((n + kVoxBlock - 1) / kVoxBlock));
-    VOXCHK(hipMemcpyAsync(d_xyz, xyz, 12 * n, hipMemcpyHostToDevice, d.stream));
-    VOXCHK(hipMemsetAsync(d_max, 0, 4, d.stream));
+    ONECHK(call, hipMemcpyAsync(d_xyz, xyz, 12 * n, hipMemcpyHostToDevice, d.stream));
+    ONECHK(call, hipMemsetAsync(d_max, 0, 4, d.stream));
     hipLaunchKernelGGL(voxel_key_kernel, per_point, block, 0, d.stream, d_xyz, n32, g, keys_a, idx_a);
-    VOXCHK(rocprim::radix_sort_pairs(tmp, sort_bytes, keys_a, keys_b, idx_a, idx_b, n, 0u, end_bit, d.stream));
+    ONECHK(call, rocprim::radix_sort_pairs(tmp, sort_bytes, keys_a, keys_b, idx_a, idx_b, n, 0u, end_bit, d.stream));
     hipLaunchKernelGGL(voxel_heads_kernel, per_point, block, 0, d.stream, keys_b, n32, head);
-    VOXCHK(rocprim::inclusive_scan(tmp, scan_bytes, head, row_incl, n, rocprim::plus<uint32_t>(), d.stream));
+    ONECHK(call, rocprim::inclusive_scan(tmp, scan_bytes, head, row_incl, n, rocprim::plus<uint32_t>(), d.stream));
     hipLaunchKernelGGL(voxel_rows_kernel, per_point, block, 0, d.stream, idx_b, head, row_incl, n32, vop, start);
     hipLaunchKernelGGL(voxel_counts_kernel, per_point, block, 0, d.stream, start, row_incl, n32, counts, tiles, d_max);
-    VOXCHK(rocprim::inclusive_scan(tmp, scan_bytes, tiles, tile_incl, n, rocprim::plus<uint32_t>(), d.stream));
+    ONECHK(call, rocprim::inclusive_scan(tmp, scan_bytes, tiles, tile_incl, n, rocprim::plus<uint32_t>(), d.stream));
     uint32_t h[3] = {0u, 0u, 0u};  // rows, the longest row, tiles of the rows beyond kVoxTile
-    VOXCHK(hipMemcpyAsync(&h[0], row_incl + (n - 1), 4, hipMemcpyDeviceToHost, d.stream));
-    VOXCHK(hipMemcpyAsync(&h[1], d_max, 4, hipMemcpyDeviceToHost, d.stream));
-    VOXCHK(hipMemcpyAsync(&h[2], tile_incl + (n - 1), 4, hipMemcpyDeviceToHost, d.stream));
-    VOXCHK(hipStreamSynchronize(d.stream));
-    VOXCHK(hipGetLastError());
+    ONECHK(call, hipMemcpyAsync(&h[0], row_incl + (n - 1), 4, hipMemcpyDeviceToHost, d.stream));
+    ONECHK(call, hipMemcpyAsync(&h[1], d_max, 4, hipMemcpyDeviceToHost, d.stream));
+    ONECHK(call, hipMemcpyAsync(&h[2], tile_incl + (n - 1), 4, hipMemcpyDeviceToHost, d.stream));
+    ONECHK(call, hipStreamSynchronize(d.stream));
+    ONECHK(call, hipGetLastError());
     const uint32_t voxels = h[0], longest = h[1], total_tiles = h[2];
     if (voxels == 0 || voxels > n32 || longest == 0 || total_tiles > max_tiles) {
         set_error("fgoicp_voxel_downsample: the device returned an inconsistent row count");
@@ -298,8 +265,7 @@ int voxel_downsample_impl(const float* xyz, size_t n, float voxel_size, const fl
     full.max_points_per_voxel = longest;
     for (int a = 0; a < 3; ++a) full.origin[a] = o[a];
     full.voxel_size = voxel_size;
-    full.struct_size = out->struct_size < sizeof(full) ? out->struct_size : (uint32_t)sizeof(full);
-    std::memcpy(out, &full, full.struct_size);
+    write_info(out, full);
     if ((out_xyz || count_per_voxel) && capacity < voxels) {
         set_error("fgoicp_voxel_downsample: " + std::to_string(voxels) + " occupied voxels, capacity_points is " + std::to_string(capacity));
         return FGOICP_ERR_TOO_LARGE;
@@ -314,12 +280,12 @@ int voxel_downsample_impl(const float* xyz, size_t n, float voxel_size, const fl
                                voxels, total_tiles, partials);
             hipLaunchKernelGGL(voxel_centroid_fold_kernel, dim3((total_tiles + kVoxBlock - 1) / kVoxBlock), block, 0, d.stream, partials, start, total_tiles, d_out);
         }
-        VOXCHK(hipMemcpyAsync(out_xyz, d_out, 12 * (size_t)voxels, hipMemcpyDeviceToHost, d.stream));
+        ONECHK(call, hipMemcpyAsync(out_xyz, d_out, 12 * (size_t)voxels, hipMemcpyDeviceToHost, d.stream));
     }
-    if (voxel_of_point) VOXCHK(hipMemcpyAsync(voxel_of_point, vop, 4 * n, hipMemcpyDeviceToHost, d.stream));
-    if (count_per_voxel) VOXCHK(hipMemcpyAsync(count_per_voxel, counts, 4 * (size_t)voxels, hipMemcpyDeviceToHost, d.stream));
-    VOXCHK(hipStreamSynchronize(d.stream));
-    VOXCHK(hipGetLastError());
+    if (voxel_of_point) ONECHK(call, hipMemcpyAsync(voxel_of_point, vop, 4 * n, hipMemcpyDeviceToHost, d.stream));
+    if (count_per_voxel) ONECHK(call, hipMemcpyAsync(count_per_voxel, counts, 4 * (size_t)voxels, hipMemcpyDeviceToHost, d.stream));
+    ONECHK(call, hipStreamSynchronize(d.stream));
+    ONECHK(call, hipGetLastError());
     return FGOICP_OK;
 }
 
