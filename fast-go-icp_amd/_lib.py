@@ -200,6 +200,7 @@ _SIGS = {
     "fgoicp_bounds_point_distances": (C.c_int, [C.c_void_p, c_float_p, C.c_float, c_float_p, C.c_int, c_float_p]),
     "fgoicp_ctx_sort_fallbacks": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "fgoicp_ctx_test_sort_fault": (C.c_int, [C.c_void_p, C.c_int]),
+    "fgoicp_test_live_resources": (C.c_int, [C.POINTER(C.c_uint64)]),
     "fgoicp_bounds_batch": (C.c_int, [C.c_void_p, c_float_p, C.c_float, c_float_p, C.c_int, C.c_int, c_float_p, c_float_p]),
     "fgoicp_bounds_multi": (C.c_int, [C.c_void_p, C.c_int, c_float_p, c_float_p, c_int_p, c_int_p, c_float_p, c_float_p,
                                       c_float_p]),
@@ -324,6 +325,13 @@ def load():
 def dev_knobs():
     """True if the loaded library is the development build (reads the FGOICP_* A/B knobs; csrc/host/knobs.hpp)."""
     return bool(load().fgoicp_dev_knobs())
+
+
+def live_resources():
+    """Test hook: (device allocations, pinned allocations, streams, events) the library's owning handles hold in this process."""
+    out = (C.c_uint64 * 4)()
+    check(load().fgoicp_test_live_resources(out), "fgoicp_test_live_resources")
+    return tuple(int(v) for v in out)
 
 
 def exported_symbols():

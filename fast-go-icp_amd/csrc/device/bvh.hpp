@@ -55,6 +55,13 @@ struct BvhDevice {
 };
 hipError_t bvh_upload(const BvhHost& h, BvhDevice* d);
 void bvh_free(BvhDevice* d);
+// a tree that bvh_upload filled (whole or in part), freed with its owner
+struct BvhOwned : BvhDevice {
+    BvhOwned() = default;
+    BvhOwned(const BvhOwned&) = delete;
+    BvhOwned& operator=(const BvhOwned&) = delete;
+    ~BvhOwned() { bvh_free(this); }
+};
 
 // The tree of a one-shot call (outlier.hip, cluster.hip) over the caller's own cloud, inside the call's arena (one_shot.hpp):
 BvhHost bvh_build_host_xyz(const float* xyz, size_t n);  // the xyz triples staged as float4, then bvh_build_host

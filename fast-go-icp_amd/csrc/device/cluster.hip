@@ -87,7 +87,7 @@ int cluster_dbscan_impl(const float* xyz, size_t n, float eps, int min_points, s
     const BvhHost tree = bvh_build_host_xyz(xyz, n);
 
     OneShot d(call);
-    ONECHK(call, hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking));
+    ONECHK(call, d.stream.create(hipStreamNonBlocking));
     const uint32_t n32 = (uint32_t)n;
     const float eps2 = eps * eps;
     size_t scan_bytes = 0;
@@ -104,7 +104,7 @@ int cluster_dbscan_impl(const float* xyz, size_t n, float eps, int min_points, s
     plan.take(d_parent, n); plan.take(d_flag, n); plan.take(d_row, n); plan.take(d_label, n); plan.take(d_size, n); plan.take(d_out, 3 * n); plan.take(d_idx, n);
     plan.take(d_ctr, 4); plan.take(tmp, scan_bytes);
     const size_t total = plan.total();
-    ONECHK(call, hipMalloc(&d.arena, total));
+    ONECHK(call, d.arena.alloc(total));
     plan.place(d.arena);
     uint32_t* d_changed = reinterpret_cast<uint32_t*>(d_ctr + 3);
 

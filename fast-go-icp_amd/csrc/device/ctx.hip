@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <chrono>
 #include <limits>
+#include <memory>
 #include <cmath>
 #include <cstddef>
 #include <cstdio>
@@ -21,6 +22,7 @@
 #include "../host/knobs.hpp"
 #include "ctx.hpp"
 #include "kernels.hpp"
+#include "arena.hpp"
 #include "morton.hpp"
 
 namespace fgoicp {
@@ -43,11 +45,12 @@ void set_error(const std::string& s) { g_last_error = s; }
 // MEASURED (profiles/r04_ab_spin_sync.txt): nothing — 54.7-55.9 us per ICP iteration blocking against 54.7-60.3 polling, every bench leg within noise: the
 // runtime's own wait is not what an iteration's 18-us host turn-around consists of.  OFF (0) by default; FGOICP_SPIN_SYNC_US=<us> is the development knob.
 static const int g_spin_sync_us = [] { const char* e = dev_env("FGOICP_SPIN_SYNC_US"); return e ? std::atoi(e) : 0; }();
-static hipError_t wait_event(hipEvent_t ev) {
+template <class Query, class Block>
+static hipError_t spin_then_block(Query query, Block block) {
     if (g_spin_sync_us > 0) {
         const auto t0 = std::chrono::steady_clock::now();
         for (unsigned spins = 0;; ++spins) {
-            const hipError_t q = hipEventQuery(ev);
+            const hipError_t q = query();
             if (q != hipErrorNotReady) return q;
 #if defined(__x86_64__)
             __builtin_ia32_pause();
@@ -55,22 +58,10 @@ static hipError_t wait_event(hipEvent_t ev) {
             if ((spins & 15u) == 15u && std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(g_spin_sync_us)) break;
         }
     }
-    return hipEventSynchronize(ev);
+    return block();
 }
-static hipError_t wait_stream(hipStream_t st) {
-    if (g_spin_sync_us > 0) {
-        const auto t0 = std::chrono::steady_clock::now();
-        for (unsigned spins = 0;; ++spins) {
-            const hipError_t q = hipStreamQuery(st);
-            if (q != hipErrorNotReady) return q;
-#if defined(__x86_64__)
-            __builtin_ia32_pause();
-#endif
-            if ((spins & 15u) == 15u && std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(g_spin_sync_us)) break;
-        }
-    }
-    return hipStreamSynchronize(st);
-}
+static hipError_t wait_event(hipEvent_t ev) { return spin_then_block([&] { return hipEventQuery(ev); }, [&] { return hipEventSynchronize(ev); }); }
+static hipError_t wait_stream(hipStream_t st) { return spin_then_block([&] { return hipStreamQuery(st); }, [&] { return hipStreamSynchronize(st); }); }
 
 int ctx_flush_profile(fgoicp_ctx* c) {
     for (int i = 0; i < c->ev_used; ++i) {
@@ -120,20 +111,20 @@ static int tick_launch_window(fgoicp_ctx* c, fgoicp_ctx::TickSlot& sl) {
     const bool tiers = sl.win_cut && c->cut_tier_level > 0.0f;   // ... and its items in two tiers, the heavy ones first (launch_tick_sort)
     const size_t nitems = (size_t)neval * (size_t)per_eval;
     const bool small = nitems <= (size_t)c->small_tick_items;
-    const TickGroup* dev_groups = small ? sl.hd_groups : sl.d_groups;
-    const TickSub* dev_subs = small ? sl.hd_subs : sl.d_subs;
+    const TickGroup* dev_groups = small ? sl.h_groups.dev() : sl.d_groups;
+    const TickSub* dev_subs = small ? sl.h_subs.dev() : sl.d_subs;
     TickCut cut;  // early exit of evaluations that have reached their group's threshold (fgoicp_bounds_submit_cut)
     if (sl.win_cut) { cut.acc = sl.d_cut_acc; cut.gate = sl.d_cut_gate; cut.row_cut = sl.d_row_cut; cut.row_term = sl.d_row_term; cut.stat = c->d_cut_stat; }
     if (tiers && !small) cut.tier_split = sl.d_cursor + kTickTierSplit;
     static const int cut_probe = [] { const char* e = dev_env("FGOICP_CUT_PROBE"); return e ? std::atoi(e) : 0; }();  // measurement of the early exit's own cost (tools/op_bench.py)
     cut.probe = cut_probe;
     *sl.h_sort_err = 0u;
-    unsigned* fused_err = !small && c->sort_check ? sl.hd_sort_err : nullptr;  // the bounds kernel checks the permutation it walks
+    unsigned* fused_err = !small && c->sort_check ? sl.h_sort_err.dev() : nullptr;  // the bounds kernel checks the permutation it walks
     if (!small) {
         // descriptors + locality sort on the slot's side stream (overlaps the other slot's bounds kernel); the main stream joins behind it
         static const int upload_kernel = [] { const char* e = dev_env("FGOICP_UPLOAD_KERNEL"); return e ? std::atoi(e) : 1; }();  // tuning knob: 0 = two hipMemcpyAsync
         if (upload_kernel) {
-            launch_tick_upload(sl.hd_groups, sl.d_groups, ng, sl.hd_subs, sl.d_subs, neval, sl.sort_stream);
+            launch_tick_upload(sl.h_groups.dev(), sl.d_groups, ng, sl.h_subs.dev(), sl.d_subs, neval, sl.sort_stream);
         } else {
             HIPCHK(hipMemcpyAsync(sl.d_groups, sl.h_groups, sizeof(TickGroup) * ng, hipMemcpyHostToDevice, sl.sort_stream));
             HIPCHK(hipMemcpyAsync(sl.d_subs, sl.h_subs, sizeof(TickSub) * neval, hipMemcpyHostToDevice, sl.sort_stream));
@@ -177,10 +168,10 @@ static int tick_launch_window(fgoicp_ctx* c, fgoicp_ctx::TickSlot& sl) {
     if (c->inliers) {  // trimmed: per row one selection of the k smallest e, both sums from it
         const int pi = e0 ? c->ev_used - 1 : -1;
         if (pi >= 0) { HIPCHK(hipEventRecord(c->ev_sel_start[pi], fin)); c->ev_has_sel[pi] = 1; }
-        launch_trim_rows(sl.d_evals, c->erow, (int)c->ns, (int)c->inliers, rows, sl.hd_row_span, sl.hd_ub, sl.hd_lb, fin, c->trim_samp_shift, c->trim_margin, c->d_trim_stat);
+        launch_trim_rows(sl.d_evals, c->erow, (int)c->ns, (int)c->inliers, rows, sl.h_row_span.dev(), sl.h_ub.dev(), sl.h_lb.dev(), fin, c->trim_samp_shift, c->trim_margin, c->d_trim_stat);
         if (pi >= 0) HIPCHK(hipEventRecord(c->ev_sel_stop[pi], fin));
     } else
-        launch_bounds_finalize(sl.d_partials, c->nchunk1, rows, sl.hd_lb, sl.hd_ub, cut_on ? cut : TickCut(), fin);
+        launch_bounds_finalize(sl.d_partials, c->nchunk1, rows, sl.h_lb.dev(), sl.h_ub.dev(), cut_on ? cut : TickCut(), fin);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(sl.done, fin));
     return FGOICP_OK;
@@ -293,7 +284,7 @@ static int tick_wait_window(fgoicp_ctx* c, fgoicp_ctx::TickSlot& sl) {
     const bool cut_verify = [] { const char* e = dev_env("FGOICP_CUT_VERIFY"); return e && std::atoi(e) != 0; }();  // (read per window: a test toggles it)
     if (cut_verify && sl.win_cut) {
         const int rows = sl.win_rows;
-        std::vector<float> lb(sl.h_lb, sl.h_lb + rows), ub(sl.h_ub, sl.h_ub + rows);
+        std::vector<float> lb(sl.h_lb.get(), sl.h_lb + rows), ub(sl.h_ub.get(), sl.h_ub + rows);
         sl.win_cut = false;
         int rc = tick_launch_window(c, sl);
         sl.win_cut = true;
@@ -435,7 +426,7 @@ static bool trim_skips(const fgoicp_ctx* c) { return c->inliers && c->trim_skip;
 // the caller index of every device slot, on the device: allocated by the first call that needs it (trimmed ICP, the alignment report, source normals)
 static int ensure_orig_of_slot(fgoicp_ctx* c) {
     if (c->d_orig_of_slot) return FGOICP_OK;
-    HIPCHK(hipMalloc(&c->d_orig_of_slot, sizeof(uint32_t) * c->ns));
+    HIPCHK(c->d_orig_of_slot.alloc(c->ns));
     HIPCHK(hipMemcpy(c->d_orig_of_slot, c->perm.data(), sizeof(uint32_t) * c->ns, hipMemcpyHostToDevice));
     return FGOICP_OK;
 }
@@ -474,7 +465,7 @@ static int sse_search_enqueue(fgoicp_ctx* c, fgoicp_ctx::IcpLane& L, const float
     const int ns = (int)c->ns;
     if (fused) {  // one launch: the scan leaves the wave-level sums of its minima in pinned memory, sse_result() folds them
         launch_nn_scan(c->d_src, ns, c->bvh_tgt.view(), c->d_lut, c->geom, R9, t3, 1, 0, c->d_tgt, (int)c->nt, seed_idx, nullptr, nullptr, L.d_min_bits, st, nullptr, nullptr, nullptr,
-                       L.hd_wsse);
+                       L.h_wsse.dev());
     } else if (c->brute_force_nn) {
         launch_fill_u32(L.d_min_bits, 0x501502F9u /* bits(1e10f) */, c->ns, st);
         launch_nn_min(c->d_src, ns, c->d_tgt, (int)c->nt, R9, t3, 1, L.d_min_bits, st);
@@ -492,11 +483,11 @@ static int sse_sum_enqueue(fgoicp_ctx* c, fgoicp_ctx::IcpLane& L, const uint32_t
     L.sse_on_host = fused;
     if (fused) {
     } else if (c->inliers) {
-        launch_trim_select(reinterpret_cast<const float*>(mins), ns, (int)c->inliers, L.hd_trim, nullptr, L.d_sel_wide, st);
+        launch_trim_select(reinterpret_cast<const float*>(mins), ns, (int)c->inliers, L.h_trim.dev(), nullptr, L.d_sel_wide, st);
     } else {
         const int nb = reduce_blocks_for(ns);
         launch_sum_f32_as_f64(mins, ns, L.d_bp3, nb, st);
-        launch_sum_partials(L.d_bp3, nb, 1, L.hd_sums + 12, st);
+        launch_sum_partials(L.d_bp3, nb, 1, L.h_sums.dev() + 12, st);
     }
     HIPCHK(hipGetLastError());
     return FGOICP_OK;
@@ -545,23 +536,21 @@ static int alignment_enqueue(fgoicp_ctx* c, const float* R9, const float* t3, bo
     int rc = ensure_orig_of_slot(c);  // untrimmed contexts have had no use for it so far
     if (rc) return rc;
     if (!A.base) {
-        auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
         A.nt16 = (c->nt + 15) & ~(size_t)15;
         const size_t nblk = (c->ns + kBlock - 1) / kBlock;
-        const size_t o_idx = 0, o_corr = o_idx + up(4 * c->ns), o_d2 = o_corr + up(4 * c->ns), o_inl = o_d2 + up(4 * c->ns), o_hit = o_inl + up(c->ns),
-                     o_part = o_hit + up(A.nt16), o_sum = o_part + up(sizeof(uint2) * nblk), o_rows = o_sum + 256, o_info = o_rows + up(sizeof(MomentRow<kAlignInfoTerms>) * nblk),
-                     total = o_info + 256;
-        HIPCHK(hipMalloc(&A.base, total));
-        char* b = static_cast<char*>(A.base);
-        A.d_idx = reinterpret_cast<uint32_t*>(b + o_idx);
-        A.d_corr = reinterpret_cast<uint32_t*>(b + o_corr);
-        A.d_d2 = reinterpret_cast<float*>(b + o_d2);
-        A.d_inl = reinterpret_cast<unsigned char*>(b + o_inl);
-        A.d_hit = reinterpret_cast<unsigned char*>(b + o_hit);
-        A.d_partials = reinterpret_cast<uint2*>(b + o_part);
-        A.d_sum = reinterpret_cast<uint32_t*>(b + o_sum);
-        A.d_info_rows = reinterpret_cast<MomentRow<kAlignInfoTerms>*>(b + o_rows);
-        A.d_info = reinterpret_cast<unsigned long long*>(b + o_info);
+        Arena plan;
+        plan.take(A.d_idx, c->ns);
+        plan.take(A.d_corr, c->ns);
+        plan.take(A.d_d2, c->ns);
+        plan.take(A.d_inl, c->ns);
+        plan.take(A.d_hit, A.nt16);
+        plan.take(A.d_partials, nblk);
+        plan.take(A.d_sum, 3);
+        static_assert(sizeof(MomentRow<kAlignInfoTerms>) == 88 && kAlignInfoTerms == 10 && kBlock == 256, "tests/host_harness/arena_check.cpp restates these");
+        plan.take(A.d_info_rows, nblk);
+        plan.take(A.d_info, 1 + kAlignInfoTerms);
+        HIPCHK(A.base.alloc(plan.total()));
+        plan.place(A.base);
     }
     hipStream_t st = L.stream;
     rc = sse_enqueue(c, L, R9, t3, nullptr, st, false);
@@ -577,7 +566,7 @@ static int alignment_enqueue(fgoicp_ctx* c, const float* R9, const float* t3, bo
     }
     const unsigned char* use = nullptr;
     if (c->inliers) {
-        launch_inlier_mask(reinterpret_cast<const float*>(L.d_min_bits), ns, (int)c->inliers, L.d_sel, L.d_eq, c->d_orig_of_slot, L.d_use, L.d_sel_wide, st);
+        launch_inlier_mask(reinterpret_cast<const float*>(L.d_min_bits.get()), ns, (int)c->inliers, L.d_sel, L.d_eq, c->d_orig_of_slot, L.d_use, L.d_sel_wide, st);
         use = L.d_use;
     }
     HIPCHK(hipMemsetAsync(A.d_hit, 0, A.nt16, st));
@@ -692,7 +681,7 @@ int ctx_set_target_normals(fgoicp_ctx* c, const float* normals, int k) {
         if (c->brute_force_nn) { set_error("fgoicp_ctx_set_target_normals: estimating normals needs the search tree, which a brute-force context does not build: pass normals"); return FGOICP_ERR_INVALID_ARG; }
     }
     HIPCHK(hipSetDevice(c->device));
-    if (!c->d_normals) HIPCHK(hipMalloc(&c->d_normals, sizeof(float4) * nt));
+    HIPCHK(c->d_normals.ensure(nt));
     hipStream_t st = c->lanes[0].stream;
     c->normals_set = false;
     if (normals) {
@@ -715,12 +704,11 @@ int ctx_target_knn(fgoicp_ctx* c, int k, uint32_t* idx, float* d2) {
     if (c->brute_force_nn) { set_error("fgoicp_target_knn: needs the search tree, which a brute-force context does not build"); return FGOICP_ERR_INVALID_ARG; }
     HIPCHK(hipSetDevice(c->device));
     const size_t n = c->nt * (size_t)k;
-    uint32_t* d_idx = nullptr;
-    float* d_d2 = nullptr;
-    auto done = [&](int rc) { (void)hipFree(d_idx); (void)hipFree(d_d2); return rc; };
+    Dev<uint32_t> d_idx;
+    Dev<float> d_d2;
     hipError_t e = hipSuccess;
-    if (idx) e = hipMalloc(&d_idx, sizeof(uint32_t) * n);
-    if (e == hipSuccess && d2) e = hipMalloc(&d_d2, sizeof(float) * n);
+    if (idx) e = d_idx.alloc(n);
+    if (e == hipSuccess && d2) e = d_d2.alloc(n);
     hipStream_t st = c->lanes[0].stream;
     if (e == hipSuccess) {
         launch_target_knn(c->bvh_tgt.view(), c->d_tgt, (int)c->nt, k, d_idx, d_d2, nullptr, st);
@@ -729,8 +717,8 @@ int ctx_target_knn(fgoicp_ctx* c, int k, uint32_t* idx, float* d2) {
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e == hipSuccess && idx) e = hipMemcpy(idx, d_idx, sizeof(uint32_t) * n, hipMemcpyDeviceToHost);
     if (e == hipSuccess && d2) e = hipMemcpy(d2, d_d2, sizeof(float) * n, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) { set_error(std::string("fgoicp_target_knn: ") + hipGetErrorString(e)); return done(e == hipErrorOutOfMemory ? FGOICP_ERR_OOM : FGOICP_ERR_HIP); }
-    return done(FGOICP_OK);
+    if (e != hipSuccess) { set_error(std::string("fgoicp_target_knn: ") + hipGetErrorString(e)); return e == hipErrorOutOfMemory ? FGOICP_ERR_OOM : FGOICP_ERR_HIP; }
+    return FGOICP_OK;
 }
 
 // EXTENSION: the point-to-plane normal equations at (R, t) (fgoicp_plane_moments), enqueued behind the report's device half on lane 0's
@@ -739,11 +727,8 @@ int ctx_target_knn(fgoicp_ctx* c, int k, uint32_t* idx, float* d2) {
 // gicp: the Generalized-ICP normal equations (launch_gicp_moments) in place of the point-to-plane ones; everything else is shared
 static int moments_at(fgoicp_ctx* c, const float* R9, const float* t3, float max_dist2, bool gicp, double epsilon, PlaneMoments* m, float* sse_out) {
     HIPCHK(hipSetDevice(c->device));
-    if (!c->d_plane_rows) {
-        const size_t nblk = (c->ns + kBlock - 1) / kBlock;
-        HIPCHK(hipMalloc(&c->d_plane_rows, sizeof(MomentRow<kPlaneTerms>) * nblk));
-        HIPCHK(hipMalloc(&c->d_plane_out, sizeof(unsigned long long) * (1 + kPlaneTerms)));
-    }
+    HIPCHK(c->d_plane_rows.ensure((c->ns + kBlock - 1) / kBlock));
+    HIPCHK(c->d_plane_out.ensure(1 + kPlaneTerms));
     const int rc = alignment_enqueue(c, R9, t3, true);
     if (rc) return rc;
     fgoicp_ctx::IcpLane& L = c->lanes[0];
@@ -836,7 +821,7 @@ int ctx_set_source_normals(fgoicp_ctx* c, const float* normals, int k) {
         if (c->brute_force_nn) { set_error("fgoicp_ctx_set_source_normals: estimating normals needs the search tree, which a brute-force context does not build: pass normals"); return FGOICP_ERR_INVALID_ARG; }
     }
     HIPCHK(hipSetDevice(c->device));
-    if (!c->d_src_normals) HIPCHK(hipMalloc(&c->d_src_normals, sizeof(float4) * ns));
+    HIPCHK(c->d_src_normals.ensure(ns));
     hipStream_t st = c->lanes[0].stream;
     HIPCHK(hipStreamSynchronize(st));
     if (normals) {
@@ -850,11 +835,10 @@ int ctx_set_source_normals(fgoicp_ctx* c, const float* normals, int k) {
     HIPCHK(hipMemcpy(h.data(), c->d_src, sizeof(float4) * ns, hipMemcpyDeviceToHost));
     std::vector<float4> caller(ns);
     for (size_t i = 0; i < ns; ++i) caller[c->perm[i]] = make_float4(h[i].x, h[i].y, h[i].z, 0.f);
-    BvhDevice tree;
-    float4* d_caller = nullptr;  // the source in caller order, then its normals in caller order behind it
-    auto done = [&](int rc) { bvh_free(&tree); (void)hipFree(d_caller); return rc; };
+    BvhOwned tree;
+    Dev<float4> d_caller;  // the source in caller order, then its normals in caller order behind it
     hipError_t e = bvh_upload(bvh_build_host(caller.data(), ns), &tree);
-    if (e == hipSuccess) e = hipMalloc(&d_caller, sizeof(float4) * 2 * ns);
+    if (e == hipSuccess) e = d_caller.alloc(2 * ns);
     if (e == hipSuccess) e = hipMemcpy(d_caller, caller.data(), sizeof(float4) * ns, hipMemcpyHostToDevice);
     c->src_normals_set = false;
     if (e == hipSuccess) {
@@ -863,9 +847,9 @@ int ctx_set_source_normals(fgoicp_ctx* c, const float* normals, int k) {
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { set_error(std::string("fgoicp_ctx_set_source_normals: ") + hipGetErrorString(e)); return done(e == hipErrorOutOfMemory ? FGOICP_ERR_OOM : FGOICP_ERR_HIP); }
+    if (e != hipSuccess) { set_error(std::string("fgoicp_ctx_set_source_normals: ") + hipGetErrorString(e)); return e == hipErrorOutOfMemory ? FGOICP_ERR_OOM : FGOICP_ERR_HIP; }
     c->src_normals_set = true;
-    return done(FGOICP_OK);
+    return FGOICP_OK;
 }
 int ctx_source_normals(fgoicp_ctx* c, float* out) {
     if (!c->src_normals_set) { set_error("fgoicp_source_normals: the source normals are not set (fgoicp_ctx_set_source_normals)"); return FGOICP_ERR_INVALID_ARG; }
@@ -908,7 +892,7 @@ static int procrustes_sums_enqueue(fgoicp_ctx* c, fgoicp_ctx::IcpLane& L, const 
     const int ns = (int)c->ns, nt = (int)c->nt, nb = reduce_blocks_for(ns);
     L.cov_on_host = fused;
     if (fused) {
-        launch_icp_cov_cen(L.d_work, c->d_tgt, idx, ns, nt, L.d_wsum, nb, (ns + 63) / 64, L.hd_cen, L.hd_covbp, nb, st);
+        launch_icp_cov_cen(L.d_work, c->d_tgt, idx, ns, nt, L.d_wsum, nb, (ns + 63) / 64, L.h_cen.dev(), L.h_covbp.dev(), nb, st);
         L.cov_blocks = nb;
         HIPCHK(hipGetLastError());
         return FGOICP_OK;
@@ -923,9 +907,9 @@ static int procrustes_sums_enqueue(fgoicp_ctx* c, fgoicp_ctx::IcpLane& L, const 
     // (Folding the block partials in the grid's last block instead of a follow-up one-block kernel — the threadfence reduction —
     // was measured and lost, 62 -> 91 us per iteration: an agent-scope fence per block writes back the XCD's L2 on this 8-XCD part.)
     launch_icp_sums(L.d_work, c->d_tgt, idx, ns, nt, use, L.d_bp, nb, st);
-    launch_icp_centroids(L.d_bp, nb, ncount, L.d_cen, L.hd_cen, st);  // icp3d.cu:152-156, no host round trip
+    launch_icp_centroids(L.d_bp, nb, ncount, L.d_cen, L.h_cen.dev(), st);  // icp3d.cu:152-156, no host round trip
     launch_icp_cov(L.d_work, c->d_tgt, idx, ns, nt, L.d_cen, use, L.d_bp2, nb, st);
-    launch_sum_partials(L.d_bp2, nb, 9, L.hd_sums, st);
+    launch_sum_partials(L.d_bp2, nb, 9, L.h_sums.dev(), st);
     HIPCHK(hipGetLastError());
     return FGOICP_OK;
 }
@@ -1116,10 +1100,8 @@ int ctx_icp_coop(fgoicp_ctx* c, int rank, int world, int (*gather)(void* dev_buf
     const int ns = (int)c->ns, nt = (int)c->nt;
     const size_t per = ((((size_t)ns + world - 1) / world) + 255) & ~(size_t)255;  // whole 256-query blocks per rank
     if (c->coop_cap < per * world) {
-        (void)hipFree(c->d_coop);
-        c->d_coop = nullptr;
         c->coop_cap = 0;
-        HIPCHK(hipMalloc(&c->d_coop, sizeof(uint32_t) * 3 * per * world));
+        HIPCHK(c->d_coop.alloc(3 * per * world));
         HIPCHK(hipMemset(c->d_coop, 0, sizeof(uint32_t) * 3 * per * world));
         c->coop_cap = per * world;
     }
@@ -1250,7 +1232,7 @@ static int lane_icp_dual(fgoicp_ctx* c, fgoicp_ctx::IcpLane& L, const float* R0,
             }
             launch_nn_scan_dual(L.d_work, skip ? nullptr : Rn.m, skip ? nullptr : tn3, skip ? 0 : 1, c->d_src, s.R.m, t3, ns, c->bvh_tgt.view(), c->d_lut, c->geom, c->d_tgt, nt, seed,
                                 skip ? qA.lb : nullptr, skip ? qA.sel : nullptr, skip ? qB.lb : nullptr, skip ? qB.sel : nullptr, idx_out, L.d_min_bits, skip ? nullptr : L.d_work,
-                                fused ? L.d_wsum : nullptr, fused ? L.hd_wsse : nullptr, S);
+                                fused ? L.d_wsum : nullptr, fused ? L.h_wsse.dev() : nullptr, S);
             rc = procrustes_sums_enqueue(c, L, idx_out, L.d_sel_wide2, fused, S);  // inlier cut, sums, covariance of pass k+1
             if (rc) return rc;
             rc = sse_sum_enqueue(c, L, L.d_min_bits, fused, S);                    // sum / trimmed selection of the SSE
@@ -1326,35 +1308,27 @@ static int trim_setup(fgoicp_ctx* c, size_t k, bool slot_rows) {
         c->erow = (c->ns + 3) & ~(size_t)3;  // rows start 16-byte aligned
         if (c->trim_samp_shift > 0)  // + the row's sample (trim_store); rows and samples then start on 256-byte boundaries
             c->erow = ((c->ns + 63) & ~(size_t)63) + (((((c->ns + ((size_t)1 << c->trim_samp_shift) - 1) >> c->trim_samp_shift)) + 63) & ~(size_t)63);
-        // every pointer is guarded on its own: a call that failed half-way (out of memory) can be repeated without leaking
+        // every handle allocates only if it is empty (ensure): a call that failed half-way (out of memory) can be repeated without leaking
         if (slot_rows) {
             size_t free_b = 0, total_b = 0;
             HIPCHK(hipMemGetInfo(&free_b, &total_b));
             const size_t budget = trim_rows_budget(free_b);
-            if (!c->d_trim_stat) { HIPCHK(hipMalloc(&c->d_trim_stat, sizeof(unsigned long long) * 4)); HIPCHK(hipMemset(c->d_trim_stat, 0, sizeof(unsigned long long) * 4)); }
+            if (!c->d_trim_stat) { HIPCHK(c->d_trim_stat.alloc(4)); HIPCHK(hipMemset(c->d_trim_stat, 0, sizeof(unsigned long long) * 4)); }
             size_t rows = budget / (sizeof(float) * c->erow);
             rows = std::max<size_t>(1, std::min<size_t>(rows, (size_t)c->max_subcubes));
             c->vals_rows = (int)rows;
-            for (auto& sl : c->slots) if (!sl.d_evals) HIPCHK(hipMalloc(&sl.d_evals, sizeof(float) * c->erow * rows));
+            for (auto& sl : c->slots) HIPCHK(sl.d_evals.ensure(c->erow * rows));
         }
         for (auto& L : c->lanes) {
-            if (!L.d_d2) HIPCHK(hipMalloc(&L.d_d2, sizeof(float) * c->ns));
-            if (!L.d_nn_lb) HIPCHK(hipMalloc(&L.d_nn_lb, sizeof(float) * c->ns));
-            if (!L.d_nn_ub) HIPCHK(hipMalloc(&L.d_nn_ub, sizeof(float) * c->ns));
-            if (!L.d_nn_lb2) HIPCHK(hipMalloc(&L.d_nn_lb2, sizeof(float) * c->ns));
-            if (!L.d_nn_ub2) HIPCHK(hipMalloc(&L.d_nn_ub2, sizeof(float) * c->ns));
-            if (!L.d_sel) HIPCHK(hipMalloc(&L.d_sel, sizeof(uint32_t) * 16));
-            if (!L.d_eq) HIPCHK(hipMalloc(&L.d_eq, sizeof(uint32_t)));
+            for (Dev<float>* d : {&L.d_d2, &L.d_nn_lb, &L.d_nn_ub, &L.d_nn_lb2, &L.d_nn_ub2}) HIPCHK(d->ensure(c->ns));
+            HIPCHK(L.d_sel.ensure(16));
+            HIPCHK(L.d_eq.ensure(1));
             const char* e = dev_env("FGOICP_SELECT_WIDE");  // tuning knob: 0 = always the one-block selection for single rows
             if (!(e && std::atoi(e) == 0)) {
-                if (!L.d_sel_wide) HIPCHK(hipMalloc(&L.d_sel_wide, 65536));
-                if (!L.d_sel_wide2) HIPCHK(hipMalloc(&L.d_sel_wide2, 65536));
+                for (Dev<uint32_t>* d : {&L.d_sel_wide, &L.d_sel_wide2}) HIPCHK(d->ensure(65536 / sizeof(uint32_t)));
             }
-            if (!L.d_use) HIPCHK(hipMalloc(&L.d_use, c->ns));
-            if (!L.h_trim) {
-                HIPCHK(hipHostMalloc((void**)&L.h_trim, sizeof(float) * 4, hipHostMallocMapped));
-                HIPCHK(hipHostGetDevicePointer((void**)&L.hd_trim, L.h_trim, 0));
-            }
+            HIPCHK(L.d_use.ensure(c->ns));
+            HIPCHK(L.h_trim.ensure(4));
         }
         if (int rc = ensure_orig_of_slot(c)) return rc;
         c->trim_ready = slot_rows;  // (a batch context never gets its slot rows: a later call with them allocates only what is missing)
@@ -1371,31 +1345,15 @@ static int trim_setup(fgoicp_ctx* c, size_t k, bool slot_rows) {
 int ctx_set_inliers(fgoicp_ctx* c, size_t k) { return trim_setup(c, k, true); }
 int ctx_set_inliers_batch(fgoicp_ctx* c, size_t k) { return trim_setup(c, k, false); }
 
-}  // namespace fgoicp
+// ---- fgoicp_ctx_create in stages: each returns FGOICP_OK or the status to return, with the message set.  The context under construction
+// is held by ctx_create_impl; a stage that fails just returns, and whatever exists by then goes with the context.
+namespace {
+struct CreateArgs {  // fgoicp_ctx_create's
+    const float* tgt_xyz; size_t nt; const float* src_xyz; size_t ns; const float* bounds6; float lut_resolution; int device; unsigned flags;
+};
 
-using namespace fgoicp;
-
-extern "C" {
-
-const char* fgoicp_last_error(void) { return g_last_error.c_str(); }
-const char* fgoicp_version(void) { return kDevKnobs ? "fgoicp_amd 0.4 (gfx950, development build)" : "fgoicp_amd 0.4 (gfx950)"; }
-int fgoicp_dev_knobs(void) { return kDevKnobs ? 1 : 0; }
-int fgoicp_abi_version(void) { return FGOICP_ABI_VERSION; }
-
-static int ctx_create_impl(const float* tgt_xyz, size_t nt, const float* src_xyz, size_t ns, const float* bounds6, float lut_resolution, int device, unsigned flags,
-                           fgoicp_ctx** out, fgoicp_ctx** partial);
-int fgoicp_ctx_create(const float* tgt_xyz, size_t nt, const float* src_xyz, size_t ns, const float* bounds6, float lut_resolution,
-                      int device, unsigned flags, fgoicp_ctx** out) {
-    if (!out) return FGOICP_ERR_INVALID_ARG;
-    *out = nullptr;
-    fgoicp_ctx* partial = nullptr;  // what an exception (std::bad_alloc in a host-side table, a thread that cannot start) leaves half-built
-    const int rc = fgoicp::abi_guard("fgoicp_ctx_create", [&] { return ctx_create_impl(tgt_xyz, nt, src_xyz, ns, bounds6, lut_resolution, device, flags, out, &partial); });
-    if (rc != FGOICP_OK && partial && !*out) fgoicp_ctx_destroy(partial);
-    return rc;
-}
-static int ctx_create_impl(const float* tgt_xyz, size_t nt, const float* src_xyz, size_t ns, const float* bounds6, float lut_resolution, int device, unsigned flags,
-                           fgoicp_ctx** out, fgoicp_ctx** partial) {
-    if (!tgt_xyz || !src_xyz || !bounds6 || nt == 0 || ns == 0 || !(lut_resolution > 0) || nt > 0x7ffffffeull || ns > 0x7ffffffeull) {
+int create_refuse_args(const CreateArgs& a) {  // no device needed
+    if (!a.tgt_xyz || !a.src_xyz || !a.bounds6 || a.nt == 0 || a.ns == 0 || !(a.lut_resolution > 0) || a.nt > 0x7ffffffeull || a.ns > 0x7ffffffeull) {
         set_error("fgoicp_ctx_create: invalid argument");
         return FGOICP_ERR_INVALID_ARG;
     }
@@ -1405,10 +1363,13 @@ static int ctx_create_impl(const float* tgt_xyz, size_t nt, const float* src_xyz
         for (size_t i = 0; i < 3 * n; ++i) acc += p[i] * 0.0f;  // stays 0 unless some coordinate is NaN or infinite
         return acc == 0.0f;
     };
-    if (!finite_cloud(tgt_xyz, nt) || !finite_cloud(src_xyz, ns) || !finite_cloud(bounds6, 2)) {
+    if (!finite_cloud(a.tgt_xyz, a.nt) || !finite_cloud(a.src_xyz, a.ns) || !finite_cloud(a.bounds6, 2)) {
         set_error("fgoicp_ctx_create: a cloud (or the target bounds) holds a non-finite coordinate");
         return FGOICP_ERR_INVALID_ARG;
     }
+    return FGOICP_OK;
+}
+int create_select_device(int device) {
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e != hipSuccess || ndev <= 0) {
@@ -1421,51 +1382,54 @@ static int ctx_create_impl(const float* tgt_xyz, size_t nt, const float* src_xyz
         return FGOICP_ERR_INVALID_ARG;
     }
     HIPCHK(hipSetDevice(device));
-    fgoicp_ctx* c = new fgoicp_ctx();
-    *partial = c;
-    c->device = device;
-    c->ns = ns;
-    c->nt = nt;
-    c->profile = (flags & FGOICP_FLAG_PROFILE) != 0;
-    c->brute_force_nn = (flags & FGOICP_FLAG_BRUTE_FORCE_NN) != 0;
-    std::memcpy(c->bounds6, bounds6, sizeof(c->bounds6));
+    return FGOICP_OK;
+}
+// what the arguments say about the context, the target's box, the main stream
+int create_head(fgoicp_ctx* c, const CreateArgs& a) {
+    c->device = a.device; c->ns = a.ns; c->nt = a.nt;
+    c->profile = (a.flags & FGOICP_FLAG_PROFILE) != 0;
+    c->brute_force_nn = (a.flags & FGOICP_FLAG_BRUTE_FORCE_NN) != 0;
+    std::memcpy(c->bounds6, a.bounds6, sizeof(c->bounds6));
     // The trimmed search drops queries whose distance to the target's box already exceeds the cut (nn_prep_kernel): that box is taken
     // from the DATA, not from the caller's `bounds6` — the reference's Registration accepts any target_bounds (they only place the
     // LUT, registration.hpp:68), and with cropped bounds "every target point lies inside the box" would be false.
-    for (int a = 0; a < 3; ++a) { c->tgt_box6[2 * a] = tgt_xyz[a]; c->tgt_box6[2 * a + 1] = tgt_xyz[a]; }
-    for (size_t i = 1; i < nt; ++i)
-        for (int a = 0; a < 3; ++a) {
-            const float v = tgt_xyz[3 * i + a];
-            c->tgt_box6[2 * a] = std::min(c->tgt_box6[2 * a], v);
-            c->tgt_box6[2 * a + 1] = std::max(c->tgt_box6[2 * a + 1], v);
+    for (int k = 0; k < 3; ++k) { c->tgt_box6[2 * k] = a.tgt_xyz[k]; c->tgt_box6[2 * k + 1] = a.tgt_xyz[k]; }
+    for (size_t i = 1; i < a.nt; ++i)
+        for (int k = 0; k < 3; ++k) {
+            const float v = a.tgt_xyz[3 * i + k];
+            c->tgt_box6[2 * k] = std::min(c->tgt_box6[2 * k], v);
+            c->tgt_box6[2 * k + 1] = std::max(c->tgt_box6[2 * k + 1], v);
         }
     if (const char* e = dev_env("FGOICP_TRIM_SKIP")) c->trim_skip = std::atoi(e) != 0;        // tuning knob
     if (const char* e = dev_env("FGOICP_SORT_XCD")) c->sort_xcd = std::atoi(e) != 0;          // tuning knob
     if (const char* e = dev_env("FGOICP_SORT_CHECK")) c->sort_check = std::atoi(e) != 0;      // tuning knob: 0 = no permutation check of the tick sort
-    auto fail = [&](int rc) { fgoicp_ctx_destroy(c); *partial = nullptr; return rc; };
-#define CHK(expr) do { hipError_t e2_ = (expr); if (e2_ != hipSuccess) { set_error(std::string(#expr) + " failed: " + hipGetErrorString(e2_)); return fail(e2_ == hipErrorOutOfMemory ? FGOICP_ERR_OOM : FGOICP_ERR_HIP); } } while (0)
-    CHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-
-    // LUT geometry — NearestNeighborLUT ctor, registration.cu:186-204
+    HIPCHK(c->stream.create(hipStreamNonBlocking));
+    return FGOICP_OK;
+}
+// LUT geometry — NearestNeighborLUT ctor, registration.cu:186-204
+int create_lut_geometry(fgoicp_ctx* c, const CreateArgs& a) {
     LutGeom& g = c->geom;
-    g.resolution = lut_resolution;
-    g.dx = (int)std::ceil((bounds6[1] - bounds6[0]) / lut_resolution);
-    g.dy = (int)std::ceil((bounds6[3] - bounds6[2]) / lut_resolution);
-    g.dz = (int)std::ceil((bounds6[5] - bounds6[4]) / lut_resolution);
+    const float* bounds6 = a.bounds6;
+    g.resolution = a.lut_resolution;
+    g.dx = (int)std::ceil((bounds6[1] - bounds6[0]) / a.lut_resolution);
+    g.dy = (int)std::ceil((bounds6[3] - bounds6[2]) / a.lut_resolution);
+    g.dz = (int)std::ceil((bounds6[5] - bounds6[4]) / a.lut_resolution);
     if (g.dx < 1 || g.dy < 1 || g.dz < 1 || g.dx > 4094 || g.dy > 4094 || g.dz > 4094) {
         set_error("fgoicp_ctx_create: LUT dims out of range (" + std::to_string(g.dx) + "," + std::to_string(g.dy) + "," + std::to_string(g.dz) + ")");
-        return fail(FGOICP_ERR_INVALID_ARG);
+        return FGOICP_ERR_INVALID_ARG;
     }
     g.px = g.dx + 2; g.py = g.dy + 2; g.pz = g.dz + 2;
-    g.scale = 1.0f / lut_resolution;
+    g.scale = 1.0f / a.lut_resolution;
     g.off_x = -bounds6[0]; g.off_y = -bounds6[2]; g.off_z = -bounds6[4];
-    g.quantize = (flags & FGOICP_FLAG_NO_WEIGHT_QUANT) ? 0 : 1;
-    g.idx = nullptr;  // set once the index LUT has been built (below)
-
-    // clouds: float4 on the device.  Source: Morton order, w = x*x+y*y+z*z in the device
-    // contraction order (registration.cu:39-41).  Target: caller order (index tie rule), w = 0.
+    g.quantize = (a.flags & FGOICP_FLAG_NO_WEIGHT_QUANT) ? 0 : 1;
+    g.idx = nullptr;  // set once the index LUT has been built (create_target_lut)
+    return FGOICP_OK;
+}
+// The source as float4 on the device, in the chosen order, w = x*x+y*y+z*z in the device contraction order (registration.cu:39-41).
+int create_source(fgoicp_ctx* c, const CreateArgs& a) {
+    const size_t ns = a.ns;
     c->perm.resize(ns);
-    if (flags & FGOICP_FLAG_NO_MORTON) std::iota(c->perm.begin(), c->perm.end(), 0u);
+    if (a.flags & FGOICP_FLAG_NO_MORTON) std::iota(c->perm.begin(), c->perm.end(), 0u);
     else {
         // k-d order with runs of 64 points (a wave of the exact scan; any chunk of 64 << k consecutive points is one k-d cell,
         // morton.hpp) unless the caller asks for the Hilbert curve (FGOICP_FLAG_CURVE_ORDER).  Measured against the curve (round 3,
@@ -1474,269 +1438,301 @@ static int ctx_create_impl(const float* tgt_xyz, size_t nt, const float* src_xyz
         // at 437k points; with 20 % volume outliers (1M trimmed) the cells grow tails along the surface normal and the trimmed ICP is
         // 13 % SLOWER — hence the flag.  FGOICP_POINT_CURVE overrides: 2 = k-d, 1 = Hilbert, 0 = Z-order.
         static const int forced = [] { const char* e = dev_env("FGOICP_POINT_CURVE"); return e ? std::atoi(e) : -1; }();  // tuning knob
-        const int mode = forced >= 0 ? forced : ((flags & FGOICP_FLAG_CURVE_ORDER) ? 1 : 2);
-        c->perm = point_order(src_xyz, ns, 3, 64, mode);
+        const int mode = forced >= 0 ? forced : ((a.flags & FGOICP_FLAG_CURVE_ORDER) ? 1 : 2);
+        c->perm = point_order(a.src_xyz, ns, 3, 64, mode);
         c->source_order = mode;
     }
-    {
-        std::vector<float4> h(ns);
-        for (size_t i = 0; i < ns; ++i) {
+    std::vector<float4> h(ns);
+    for (size_t i = 0; i < ns; ++i) {
+        const float* p = a.src_xyz + 3 * (size_t)c->perm[i];
+        h[i] = make_float4(p[0], p[1], p[2], std::fmaf(p[2], p[2], std::fmaf(p[1], p[1], p[0] * p[0])));
+    }
+    HIPCHK(c->d_src.alloc(ns));
+    HIPCHK(hipMemcpy(c->d_src, h.data(), sizeof(float4) * ns, hipMemcpyHostToDevice));
+    return FGOICP_OK;
+}
+// The target on the device (caller order: the index tie rule; w = 0), its exact-NN tree, and the LUT — buildLUTKernel, registration.cu:258-318
+int create_target_lut(fgoicp_ctx* c, const CreateArgs& a) {
+    const size_t nt = a.nt;
+    LutGeom& g = c->geom;
+    std::vector<float4> h(nt), hs(nt);
+    for (size_t i = 0; i < nt; ++i) {
+        const float* p = a.tgt_xyz + 3 * i;
+        h[i] = make_float4(p[0], p[1], p[2], 0.f);
+        hs[i] = make_float4(p[0] + g.off_x, p[1] + g.off_y, p[2] + g.off_z, 0.f);  // registration.cu:289-296
+    }
+    HIPCHK(c->d_tgt.alloc(nt));
+    HIPCHK(hipMemcpy(c->d_tgt, h.data(), sizeof(float4) * nt, hipMemcpyHostToDevice));
+    const size_t total = (size_t)g.px * g.py * g.pz;
+    HIPCHK(c->d_lut.alloc(total));
+    hipError_t e3 = hipSuccess;
+    if (c->brute_force_nn) {
+        Dev<float4> d_tgt_shift;
+        e3 = d_tgt_shift.alloc(nt);
+        if (e3 == hipSuccess) e3 = hipMemcpy(d_tgt_shift, hs.data(), sizeof(float4) * nt, hipMemcpyHostToDevice);
+        if (e3 == hipSuccess) {
+            launch_lut_build(d_tgt_shift, (int)nt, g, c->d_lut, c->stream);
+            e3 = hipGetLastError();
+            if (e3 == hipSuccess) e3 = hipStreamSynchronize(c->stream);
+        }
+    } else {
+        std::vector<uint32_t> order;  // one sort for both trees
+        c->tree_order = bvh_kd_order() ? 1 : 0;
+        HIPCHK(bvh_upload(bvh_build_host(h.data(), nt, &order), &c->bvh_tgt));
+        BvhOwned shifted;  // the LUT is built from the SHIFTED targets (pc + offset in fp32), its own tree
+        e3 = bvh_upload(bvh_build_host(hs.data(), nt, &order), &shifted);
+        Dev<float> scratch;
+        if (e3 == hipSuccess) e3 = scratch.alloc(total);
+        // the index LUT (4 B per node; an allocation that fails just leaves the feature off).  Built in round 3, bit-identical (146 GPU
+        // tests with it on), measured — and it buys NOTHING (profiles/r03_ab_lut_index.txt: ICP iteration 44.7 -> 46.4 us at 40k points,
+        // 169 -> 170 us at 437k, trimmed 1M ICP 463 -> 465 ms): the triangle bound's slack is not what makes the scans of a far state
+        // expensive — the leaf BOXES a large ball cuts are (tools/kd_sim.py-style count: 5.4 -> 16 leaves per query group 20 degrees
+        // off the optimum even with exact bounds).  OFF by default; FGOICP_LUT_INDEX=1 builds and uses it.
+        static const bool want_idx = [] { const char* e = dev_env("FGOICP_LUT_INDEX"); return e && std::atoi(e) != 0; }();  // tuning knob / A-B
+        if (e3 == hipSuccess && want_idx && c->d_lut_idx.alloc(total) != hipSuccess) (void)hipGetLastError();
+        if (e3 == hipSuccess) {
+            launch_lut_build_scan(shifted.view(), g, scratch, c->d_lut, c->stream, c->d_lut_idx);
+            e3 = hipGetLastError();
+            if (e3 == hipSuccess) e3 = hipStreamSynchronize(c->stream);
+        }
+    }
+    if (e3 != hipSuccess) { set_error(std::string("LUT build failed: ") + hipGetErrorString(e3)); return e3 == hipErrorOutOfMemory ? FGOICP_ERR_OOM : FGOICP_ERR_HIP; }
+    g.idx = c->d_lut_idx;  // from here on the exact scans seed their bounds with it (kernels.hip lut_upper_bound_d2)
+    return FGOICP_OK;
+}
+// Packed copy for the bounds kernel: 1 z-pair (2x bytes, two rows per lookup), 2 yz-quad (4x bytes, one
+// line per lookup).  Measured: the quad wins on sparse clouds (every lane-gather its own line; +8 % at 40k
+// points), loses on dense ones (lanes share lines and the 4x footprint falls out of cache; -5 % at 437k), so it
+// is chosen by the number of source points per voxel of the LUT's projected faces.
+int create_packed_lut(fgoicp_ctx* c) {
+    const LutGeom& g = c->geom;
+    const size_t total = (size_t)g.px * g.py * g.pz;
+    const double face_voxels = (double)g.dx * g.dy + (double)g.dy * g.dz + (double)g.dx * g.dz;
+    int layout = ((double)c->ns / face_voxels < 0.5 && total * sizeof(float4) <= ((size_t)16 << 30)) ? 2 : 1;
+    // sparse clouds, round 3: the apron-bricked quads (kernels.hip apron_index: every lookup inside one line, a line serves a 3 x 2
+    // patch of base voxels; 21.3 instead of 16 B per node) — bounds kernel -1.1 % on the bunny shape, three A/B pairs
+    const size_t lines = (size_t)((g.px + 2) / 3) * ((g.py + 1) / 2) * g.pz, apron_bytes = lines * 8 * sizeof(float4);
+    if (layout == 2 && apron_bytes <= ((size_t)16 << 30)) layout = 4;
+    if (const char* e = dev_env("FGOICP_LUT_ZPAIR")) { const int v = std::atoi(e); if (v == 1 || v == 2 || v == 4) layout = v; }  // tuning knob
+    if (layout == 4 && (g.px > 1023 || g.py > 1023 || g.pz > 1023)) layout = 2;  // the apron copy packs indices in 10 bits
+    c->lut_layout = layout;
+    // (d_lut_zp counts float2: a float4 is two of them)
+    if (layout == 4) {
+        HIPCHK(c->d_lut_zp.alloc(lines * 8 * 2));
+        launch_lut_quad_apron(c->d_lut, g, reinterpret_cast<float4*>(c->d_lut_zp.get()), c->stream);
+    } else if (layout == 2) {
+        HIPCHK(c->d_lut_zp.alloc(total * 2));
+        launch_lut_quad(c->d_lut, g, reinterpret_cast<float4*>(c->d_lut_zp.get()), c->stream);
+    } else {
+        HIPCHK(c->d_lut_zp.alloc(total));
+        launch_lut_zpair(c->d_lut, g, c->d_lut_zp, c->stream);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return FGOICP_OK;
+}
+// Window sizing: pure arithmetic on ns, the geometry and the knobs.
+int create_window_sizes(fgoicp_ctx* c) {
+    const LutGeom& g = c->geom;
+    const size_t ns = c->ns;
+    // points per work item of the sorted path: the patch of 256 Morton-consecutive points of a sparse cloud spans
+    // ~28 voxels; in a dense cloud (>= 1 point per voxel of the LUT's faces) it shrinks to ~6, so the items grow to
+    // 2048 points — 8x fewer items to sort, 8x fewer partials, same locality.  Measured (437k points, density 1.8,
+    // one certify run): 256 / 512 / 1024 / 2048 / 4096 points per item -> 4.68 / 3.34 / 2.70 / 2.48 / 2.60 s;
+    // 40k points, density 0.1: 256 -> 512 points 8 % slower.
+    const double face_voxels = (double)g.dx * g.dy + (double)g.dy * g.dz + (double)g.dx * g.dz;
+    const double density = (double)ns / face_voxels;
+    c->chunk_pts = density >= 1.0 ? 2048 : density >= 0.5 ? 1024 : density >= 0.25 ? 512 : 256;
+    if (const char* e = dev_env("FGOICP_CHUNK_PTS")) {  // tuning knob
+        const int v = std::atoi(e);
+        if (v == 256 || v == 512 || v == 1024 || v == 2048 || v == 4096) c->chunk_pts = v;
+    }
+    // subcubes per window: as many as 4 GiB of per-(subcube, chunk) scratch per slot hold, 4096..131072 (wide rounds submit
+    // tens of thousands per tick; bigger launches sort into longer runs of items per LUT cell and re-use the L2 better)
+    const size_t nchunk1 = (ns + c->chunk_pts - 1) / c->chunk_pts;
+    const size_t fit = ((size_t)4 << 30) / (nchunk1 * (sizeof(double2) + 2 * sizeof(unsigned) + sizeof(unsigned short)));
+    c->max_subcubes = (int)std::max<size_t>(4096, std::min<size_t>(131072, fit));
+    if (const char* e = dev_env("FGOICP_MAX_SUBCUBES")) c->max_subcubes = std::max(kMaxBatch, std::min(1 << 18, std::atoi(e)));  // tuning knob: subcubes per window
+    // one launch = one workgroup per (subcube, chunk) item: keep items x 256 threads inside the 32-bit grid
+    const size_t launch_fit = (((size_t)1 << 24) - 1) / nchunk1;
+    if (launch_fit < (size_t)kMaxBatch) {
+        set_error("fgoicp_ctx_create: source cloud too large for one bounds launch per batch (ns > ~134M)");
+        return FGOICP_ERR_TOO_LARGE;
+    }
+    c->max_subcubes = (int)std::min<size_t>((size_t)c->max_subcubes, launch_fit);
+    c->nchunk1 = (int)nchunk1;
+    c->max_groups = std::max(512, c->max_subcubes / 8);
+    if (const char* e = dev_env("FGOICP_FINALIZE_SIDE")) c->finalize_on_side = std::atoi(e) != 0;  // tuning knob
+    if (const char* e = dev_env("FGOICP_ICP_SEED")) c->icp_seeding = std::atoi(e) != 0;             // tuning knob
+    if (const char* e = dev_env("FGOICP_COOP_SPLIT_MIN")) c->coop_split_min = c->coop_split_trim_min = (size_t)std::max(0L, std::atol(e));  // tuning knob (both thresholds)
+    if (const char* e = dev_env("FGOICP_SMALL_TICK")) c->small_tick_items = std::max(0, std::atoi(e));  // tuning knob: items
+    const int maxd = std::max(g.dx, std::max(g.dy, g.dz));
+    c->cell_shift = 0;
+    while ((maxd >> c->cell_shift) > 32) ++c->cell_shift;  // 5 bits per axis
+    // Windows with thresholds (fgoicp_bounds_submit_cut) on sparse clouds: two chunks per work item.  Half of such a window's items end
+    // after three loads, and what they cost is their workgroup's dispatch (profiles/r04_dispatch_rate.txt); measured on the bunny
+    // shape with the early exit, 256 / 512 / 1024 points per item: 243 / 220 / 245 ms per certify run — while without thresholds
+    // 512 points are 8 % slower than 256 (above).  The sums stay per chunk, so both kinds of window return the same bits.
+    c->cut_span = c->chunk_pts == 256 ? 2 : 1;
+    if (const char* e = dev_env("FGOICP_CUT_TIERS")) c->cut_tier_level = (float)std::atof(e);  // tuning knob: 0 = one tier
+    if (const char* e = dev_env("FGOICP_CUT_SPAN")) { const int v = std::atoi(e); if (v == 1 || v == 2 || v == 4) c->cut_span = v; }  // tuning knob
+    return FGOICP_OK;
+}
+// centres of the runs of `pts` consecutive points (the tick sort's keys), on the device
+int create_run_centres(fgoicp_ctx* c, const float* src_xyz, size_t pts, Dev<float4>& d_cen) {
+    const size_t ns = c->ns, n = (ns + pts - 1) / pts;
+    std::vector<float4> cen(n);
+    for (size_t k = 0; k < n; ++k) {
+        double sx = 0, sy = 0, sz = 0;
+        const size_t a = k * pts, b = std::min(ns, a + pts);
+        for (size_t i = a; i < b; ++i) {
             const float* p = src_xyz + 3 * (size_t)c->perm[i];
-            h[i] = make_float4(p[0], p[1], p[2], std::fmaf(p[2], p[2], std::fmaf(p[1], p[1], p[0] * p[0])));
+            sx += p[0]; sy += p[1]; sz += p[2];
         }
-        CHK(hipMalloc(&c->d_src, sizeof(float4) * ns));
-        CHK(hipMemcpy(c->d_src, h.data(), sizeof(float4) * ns, hipMemcpyHostToDevice));
+        const double inv = 1.0 / (double)(b - a);
+        cen[k] = make_float4((float)(sx * inv), (float)(sy * inv), (float)(sz * inv), 0.f);
     }
-    // target on the device (caller order) + exact-NN tree; LUT build — buildLUTKernel, registration.cu:258-318
-    {
-        std::vector<float4> h(nt), hs(nt);
-        for (size_t i = 0; i < nt; ++i) {
-            const float* p = tgt_xyz + 3 * i;
-            h[i] = make_float4(p[0], p[1], p[2], 0.f);
-            hs[i] = make_float4(p[0] + g.off_x, p[1] + g.off_y, p[2] + g.off_z, 0.f);  // registration.cu:289-296
-        }
-        CHK(hipMalloc(&c->d_tgt, sizeof(float4) * nt));
-        CHK(hipMemcpy(c->d_tgt, h.data(), sizeof(float4) * nt, hipMemcpyHostToDevice));
-        const size_t total = (size_t)g.px * g.py * g.pz;
-        CHK(hipMalloc(&c->d_lut, total * sizeof(float)));
-        hipError_t e3 = hipSuccess;
-        if (c->brute_force_nn) {
-            float4* d_tgt_shift = nullptr;
-            e3 = hipMalloc(&d_tgt_shift, sizeof(float4) * nt);
-            if (e3 == hipSuccess) e3 = hipMemcpy(d_tgt_shift, hs.data(), sizeof(float4) * nt, hipMemcpyHostToDevice);
-            if (e3 == hipSuccess) {
-                launch_lut_build(d_tgt_shift, (int)nt, g, c->d_lut, c->stream);
-                e3 = hipGetLastError();
-                if (e3 == hipSuccess) e3 = hipStreamSynchronize(c->stream);
-            }
-            (void)hipFree(d_tgt_shift);
-        } else {
-            std::vector<uint32_t> order;  // one sort for both trees
-            c->tree_order = bvh_kd_order() ? 1 : 0;
-            CHK(bvh_upload(bvh_build_host(h.data(), nt, &order), &c->bvh_tgt));
-            BvhDevice shifted;  // the LUT is built from the SHIFTED targets (pc + offset in fp32), its own tree
-            e3 = bvh_upload(bvh_build_host(hs.data(), nt, &order), &shifted);
-            float* scratch = nullptr;
-            if (e3 == hipSuccess) e3 = hipMalloc(&scratch, total * sizeof(float));
-            // the index LUT (4 B per node; an allocation that fails just leaves the feature off).  Built in round 3, bit-identical (146 GPU
-            // tests with it on), measured — and it buys NOTHING (profiles/r03_ab_lut_index.txt: ICP iteration 44.7 -> 46.4 us at 40k points,
-            // 169 -> 170 us at 437k, trimmed 1M ICP 463 -> 465 ms): the triangle bound's slack is not what makes the scans of a far state
-            // expensive — the leaf BOXES a large ball cuts are (tools/kd_sim.py-style count: 5.4 -> 16 leaves per query group 20 degrees
-            // off the optimum even with exact bounds).  OFF by default; FGOICP_LUT_INDEX=1 builds and uses it.
-            static const bool want_idx = [] { const char* e = dev_env("FGOICP_LUT_INDEX"); return e && std::atoi(e) != 0; }();  // tuning knob / A-B
-            if (e3 == hipSuccess && want_idx && hipMalloc(&c->d_lut_idx, total * sizeof(uint32_t)) != hipSuccess) { c->d_lut_idx = nullptr; (void)hipGetLastError(); }
-            if (e3 == hipSuccess) {
-                launch_lut_build_scan(shifted.view(), g, scratch, c->d_lut, c->stream, c->d_lut_idx);
-                e3 = hipGetLastError();
-                if (e3 == hipSuccess) e3 = hipStreamSynchronize(c->stream);
-            }
-            (void)hipFree(scratch);
-            bvh_free(&shifted);
-        }
-        if (e3 != hipSuccess) { set_error(std::string("LUT build failed: ") + hipGetErrorString(e3)); return fail(e3 == hipErrorOutOfMemory ? FGOICP_ERR_OOM : FGOICP_ERR_HIP); }
-        g.idx = c->d_lut_idx;  // from here on the exact scans seed their bounds with it (kernels.hip lut_upper_bound_d2)
-        // Packed copy for the bounds kernel: 1 z-pair (2x bytes, two rows per lookup), 2 yz-quad (4x bytes, one
-        // line per lookup).  Measured: the quad wins on sparse clouds (every lane-gather its own line; +8 % at 40k
-        // points), loses on dense ones (lanes share lines and the 4x footprint falls out of cache; -5 % at 437k), so it
-        // is chosen by the number of source points per voxel of the LUT's projected faces.
-        const double face_voxels = (double)g.dx * g.dy + (double)g.dy * g.dz + (double)g.dx * g.dz;
-        int layout = ((double)ns / face_voxels < 0.5 && total * sizeof(float4) <= ((size_t)16 << 30)) ? 2 : 1;
-        // sparse clouds, round 3: the apron-bricked quads (kernels.hip apron_index: every lookup inside one line, a line serves a 3 x 2
-        // patch of base voxels; 21.3 instead of 16 B per node) — bounds kernel -1.1 % on the bunny shape, three A/B pairs
-        const size_t apron_bytes = (size_t)((g.px + 2) / 3) * ((g.py + 1) / 2) * g.pz * 8 * sizeof(float4);
-        if (layout == 2 && apron_bytes <= ((size_t)16 << 30)) layout = 4;
-        if (const char* e = dev_env("FGOICP_LUT_ZPAIR")) { const int v = std::atoi(e); if (v == 1 || v == 2 || v == 4) layout = v; }  // tuning knob
-        if (layout == 4 && (g.px > 1023 || g.py > 1023 || g.pz > 1023)) layout = 2;  // the apron copy packs indices in 10 bits
-        c->lut_layout = layout;
-        if (layout == 4) {
-            const size_t lines = (size_t)((g.px + 2) / 3) * ((g.py + 1) / 2) * g.pz;
-            CHK(hipMalloc(&c->d_lut_zp, lines * 8 * sizeof(float4)));
-            launch_lut_quad_apron(c->d_lut, g, reinterpret_cast<float4*>(c->d_lut_zp), c->stream);
-        } else if (layout == 2) {
-            CHK(hipMalloc(&c->d_lut_zp, total * sizeof(float4)));
-            launch_lut_quad(c->d_lut, g, reinterpret_cast<float4*>(c->d_lut_zp), c->stream);
-        } else {
-            CHK(hipMalloc(&c->d_lut_zp, total * sizeof(float2)));
-            launch_lut_zpair(c->d_lut, g, c->d_lut_zp, c->stream);
-        }
-        CHK(hipGetLastError());
-        CHK(hipStreamSynchronize(c->stream));
+    HIPCHK(d_cen.alloc(n));
+    HIPCHK(hipMemcpy(d_cen, cen.data(), sizeof(float4) * n, hipMemcpyHostToDevice));
+    return FGOICP_OK;
+}
+// one slot of the locality-sorted whole-tick path
+int create_tick_slot(fgoicp_ctx* c, fgoicp_ctx::TickSlot& sl) {
+    const size_t subcubes = (size_t)c->max_subcubes, max_items = subcubes * c->nchunk1;
+    sl.stream.borrow(c->stream);
+    HIPCHK(sl.done.create(hipEventDisableTiming));
+    const char* e = dev_env("FGOICP_SORT_STREAM");  // tuning knob: 0 = sort on the main stream
+    if (e && std::atoi(e) == 0) sl.sort_stream.borrow(c->stream);
+    else {
+        const char* pe = dev_env("FGOICP_SIDE_PRIORITY");  // tuning knob: -1 = the side streams (sort, finalize / selection) above the bounds kernels' stream, 1 = below
+        const int pri = pe ? std::atoi(pe) : 0;
+        int least = 0, greatest = 0;
+        if (pri) HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
+        if (pri) HIPCHK(sl.sort_stream.create(hipStreamNonBlocking, pri < 0 ? greatest : least));
+        else HIPCHK(sl.sort_stream.create(hipStreamNonBlocking));
     }
-    // bounds scratch
-    {
-        // subcubes per window: as many as 4 GiB of per-(subcube, chunk) scratch per slot hold, 4096..131072 (wide rounds submit
-        // tens of thousands per tick; bigger launches sort into longer runs of items per LUT cell and re-use the L2 better)
-        {
-            // points per work item of the sorted path: the patch of 256 Morton-consecutive points of a sparse cloud spans
-            // ~28 voxels; in a dense cloud (>= 1 point per voxel of the LUT's faces) it shrinks to ~6, so the items grow to
-            // 2048 points — 8x fewer items to sort, 8x fewer partials, same locality.  Measured (437k points, density 1.8,
-            // one certify run): 256 / 512 / 1024 / 2048 / 4096 points per item -> 4.68 / 3.34 / 2.70 / 2.48 / 2.60 s;
-            // 40k points, density 0.1: 256 -> 512 points 8 % slower.
-            {
-                const double face_voxels = (double)g.dx * g.dy + (double)g.dy * g.dz + (double)g.dx * g.dz;
-                const double density = (double)ns / face_voxels;
-                c->chunk_pts = density >= 1.0 ? 2048 : density >= 0.5 ? 1024 : density >= 0.25 ? 512 : 256;
-                if (const char* e = dev_env("FGOICP_CHUNK_PTS")) {  // tuning knob
-                    const int v = std::atoi(e);
-                    if (v == 256 || v == 512 || v == 1024 || v == 2048 || v == 4096) c->chunk_pts = v;
-                }
-            }
-            const size_t nchunk1 = (ns + c->chunk_pts - 1) / c->chunk_pts;
-            const size_t fit = ((size_t)4 << 30) / (nchunk1 * (sizeof(double2) + 2 * sizeof(unsigned) + sizeof(unsigned short)));
-            c->max_subcubes = (int)std::max<size_t>(4096, std::min<size_t>(131072, fit));
-            if (const char* e = dev_env("FGOICP_MAX_SUBCUBES")) c->max_subcubes = std::max(kMaxBatch, std::min(1 << 18, std::atoi(e)));  // tuning knob: subcubes per window
-            // one launch = one workgroup per (subcube, chunk) item: keep items x 256 threads inside the 32-bit grid
-            const size_t launch_fit = (((size_t)1 << 24) - 1) / nchunk1;
-            if (launch_fit < (size_t)kMaxBatch) {
-                set_error("fgoicp_ctx_create: source cloud too large for one bounds launch per batch (ns > ~134M)");
-                return fail(FGOICP_ERR_TOO_LARGE);
-            }
-            c->max_subcubes = (int)std::min<size_t>((size_t)c->max_subcubes, launch_fit);
-        }
-    }
-    // locality-sorted whole-tick path
-    {
-        c->nchunk1 = (int)((ns + c->chunk_pts - 1) / c->chunk_pts);
-        c->max_groups = std::max(512, c->max_subcubes / 8);
-        if (const char* e = dev_env("FGOICP_FINALIZE_SIDE")) c->finalize_on_side = std::atoi(e) != 0;  // tuning knob
-        if (const char* e = dev_env("FGOICP_ICP_SEED")) c->icp_seeding = std::atoi(e) != 0;             // tuning knob
-        if (const char* e = dev_env("FGOICP_COOP_SPLIT_MIN")) c->coop_split_min = c->coop_split_trim_min = (size_t)std::max(0L, std::atol(e));  // tuning knob (both thresholds)
-        if (const char* e = dev_env("FGOICP_SMALL_TICK")) c->small_tick_items = std::max(0, std::atoi(e));  // tuning knob: items
-        int maxd = std::max(g.dx, std::max(g.dy, g.dz));
-        c->cell_shift = 0;
-        while ((maxd >> c->cell_shift) > 32) ++c->cell_shift;  // 5 bits per axis
-        // centres of the runs of `pts` consecutive points (the tick sort's keys)
-        const auto run_centres = [&](size_t pts) {
-            const size_t n = (ns + pts - 1) / pts;
-            std::vector<float4> cen(n);
-            for (size_t k = 0; k < n; ++k) {
-                double sx = 0, sy = 0, sz = 0;
-                const size_t a = k * pts, b = std::min(ns, a + pts);
-                for (size_t i = a; i < b; ++i) {
-                    const float* p = src_xyz + 3 * (size_t)c->perm[i];
-                    sx += p[0]; sy += p[1]; sz += p[2];
-                }
-                const double inv = 1.0 / (double)(b - a);
-                cen[k] = make_float4((float)(sx * inv), (float)(sy * inv), (float)(sz * inv), 0.f);
-            }
-            return cen;
-        };
-        {
-            const std::vector<float4> cen = run_centres((size_t)c->chunk_pts);
-            CHK(hipMalloc(&c->d_chunk_cen, sizeof(float4) * cen.size()));
-            CHK(hipMemcpy(c->d_chunk_cen, cen.data(), sizeof(float4) * cen.size(), hipMemcpyHostToDevice));
-        }
-        // Windows with thresholds (fgoicp_bounds_submit_cut) on sparse clouds: two chunks per work item.  Half of such a window's items end
-        // after three loads, and what they cost is their workgroup's dispatch (profiles/r04_dispatch_rate.txt); measured on the bunny
-        // shape with the early exit, 256 / 512 / 1024 points per item: 243 / 220 / 245 ms per certify run — while without thresholds
-        // 512 points are 8 % slower than 256 (above).  The sums stay per chunk, so both kinds of window return the same bits.
-        c->cut_span = c->chunk_pts == 256 ? 2 : 1;
-        if (const char* e = dev_env("FGOICP_CUT_TIERS")) c->cut_tier_level = (float)std::atof(e);  // tuning knob: 0 = one tier
-        if (const char* e = dev_env("FGOICP_CUT_SPAN")) { const int v = std::atoi(e); if (v == 1 || v == 2 || v == 4) c->cut_span = v; }  // tuning knob
-        if (c->cut_span > 1) {
-            const std::vector<float4> cen = run_centres((size_t)c->chunk_pts * c->cut_span);
-            CHK(hipMalloc(&c->d_span_cen, sizeof(float4) * cen.size()));
-            CHK(hipMemcpy(c->d_span_cen, cen.data(), sizeof(float4) * cen.size(), hipMemcpyHostToDevice));
-        }
-        const size_t max_items = (size_t)c->max_subcubes * c->nchunk1;
-        for (int k = 0; k < 2; ++k) {
-            fgoicp_ctx::TickSlot& sl = c->slots[k];
-            sl.stream = c->stream;
-            CHK(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
-            {
-                const char* e = dev_env("FGOICP_SORT_STREAM");  // tuning knob: 0 = sort on the main stream
-                if (e && std::atoi(e) == 0) sl.sort_stream = c->stream;
-                else {
-                    const char* pe = dev_env("FGOICP_SIDE_PRIORITY");  // tuning knob: -1 = the side streams (sort, finalize / selection) above the bounds kernels' stream, 1 = below
-                    const int pri = pe ? std::atoi(pe) : 0;
-                    int least = 0, greatest = 0;
-                    if (pri) CHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
-                    if (pri) CHK(hipStreamCreateWithPriority(&sl.sort_stream, hipStreamNonBlocking, pri < 0 ? greatest : least));
-                    else CHK(hipStreamCreateWithFlags(&sl.sort_stream, hipStreamNonBlocking));
-                }
-            }
-            CHK(hipEventCreateWithFlags(&sl.sorted_ev, hipEventDisableTiming));
-            CHK(hipEventCreateWithFlags(&sl.bounds_ev, hipEventDisableTiming));
-            CHK(hipMalloc(&sl.d_groups, sizeof(TickGroup) * c->max_groups));
-            CHK(hipMalloc(&sl.d_subs, sizeof(TickSub) * c->max_subcubes));
-            CHK(hipHostMalloc((void**)&sl.h_groups, sizeof(TickGroup) * c->max_groups, hipHostMallocMapped));
-            CHK(hipHostMalloc((void**)&sl.h_subs, sizeof(TickSub) * c->max_subcubes, hipHostMallocMapped));
-            CHK(hipHostGetDevicePointer((void**)&sl.hd_groups, sl.h_groups, 0));
-            CHK(hipHostGetDevicePointer((void**)&sl.hd_subs, sl.h_subs, 0));
-            CHK(hipHostMalloc((void**)&sl.h_row_span, sizeof(float) * c->max_subcubes, hipHostMallocMapped));
-            CHK(hipHostGetDevicePointer((void**)&sl.hd_row_span, sl.h_row_span, 0));
-            CHK(hipHostMalloc((void**)&sl.h_sort_err, sizeof(unsigned) * 4, hipHostMallocMapped));
-            CHK(hipHostGetDevicePointer((void**)&sl.hd_sort_err, sl.h_sort_err, 0));
-            *sl.h_sort_err = 0u;
-            CHK(hipMalloc(&sl.d_keys, sizeof(unsigned short) * max_items));
-            CHK(hipMalloc(&sl.d_ranks, sizeof(unsigned) * max_items));
-            CHK(hipMalloc(&sl.d_hist, sizeof(unsigned) * kTickNumKeys));
-            CHK(hipMemset(sl.d_hist, 0, sizeof(unsigned) * kTickNumKeys));  // the scan kernel re-zeroes it after every tick
-            CHK(hipMalloc(&sl.d_block_sums, sizeof(unsigned) * 64));
-            CHK(hipMalloc(&sl.d_hist_xcd, sizeof(unsigned) * 16 * kTickNumKeys));
-            CHK(hipMemset(sl.d_hist_xcd, 0, sizeof(unsigned) * 16 * kTickNumKeys));
-            CHK(hipMalloc(&sl.d_xoff, sizeof(unsigned) * 16 * kTickNumKeys));
-            CHK(hipMalloc(&sl.d_cursor, sizeof(unsigned) * kTickNumKeys));
-            CHK(hipMalloc(&sl.d_sorted, sizeof(unsigned) * max_items));
-            CHK(hipMalloc(&sl.d_partials, sizeof(double2) * max_items));
-            CHK(hipMalloc(&sl.d_cut_acc, sizeof(double) * 2 * (size_t)c->max_subcubes));
-            CHK(hipMemset(sl.d_cut_acc, 0, sizeof(double) * 2 * (size_t)c->max_subcubes));  // bounds_finalize_kernel re-zeroes what a window used
-            CHK(hipMalloc(&sl.d_row_cut, (sizeof(float) + sizeof(unsigned)) * (size_t)c->max_subcubes));
-            sl.d_row_term = reinterpret_cast<unsigned*>(sl.d_row_cut + c->max_subcubes);
-            CHK(hipMalloc(&sl.d_cut_gate, sizeof(TickGate) * (size_t)c->max_subcubes));  // written per window, ahead of its bounds kernel
-            if (k == 0 && !c->d_cut_stat) {
-                CHK(hipMalloc(&c->d_cut_stat, sizeof(unsigned long long) * kCutStatSlots));
-                CHK(hipMemset(c->d_cut_stat, 0, sizeof(unsigned long long) * kCutStatSlots));
-            }
-            CHK(hipHostMalloc((void**)&sl.h_lb, sizeof(float) * c->max_subcubes, hipHostMallocMapped));
-            CHK(hipHostMalloc((void**)&sl.h_ub, sizeof(float) * c->max_subcubes, hipHostMallocMapped));
-            CHK(hipHostGetDevicePointer((void**)&sl.hd_lb, sl.h_lb, 0));
-            CHK(hipHostGetDevicePointer((void**)&sl.hd_ub, sl.h_ub, 0));
-        }
-    }
-    // exact-NN / ICP scratch
-    {
-        int nl = 4;  // concurrent ICP runs (ctx_icp_batch); lane 0 shares the context's main stream
-        if (const char* e = dev_env("FGOICP_ICP_LANES")) nl = std::max(1, std::min(16, std::atoi(e)));  // tuning knob
-        if (const char* e = dev_env("FGOICP_ICP_OVERLAP")) c->icp_overlap = std::atoi(e) != 0;       // tuning knob
-        if (const char* e = dev_env("FGOICP_ICP_DUAL")) c->icp_dual_env = std::atoi(e) != 0 ? 1 : 0; // tuning knob / A-B: 1 = one walk for both scans of an iteration, 0 = two scans on two streams
-        if (const char* e = dev_env("FGOICP_ICP_FUSE")) c->icp_fuse = std::atoi(e) != 0;             // tuning knob / A-B: 0 = separate reduction kernels
-        c->lanes.resize((size_t)nl);
-        for (int l = 0; l < nl; ++l) {
-            fgoicp_ctx::IcpLane& L = c->lanes[(size_t)l];
-            if (l == 0) L.stream = c->stream;
-            else CHK(hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking));
-            CHK(hipMalloc(&L.d_work, sizeof(float4) * ns));
-            CHK(hipMalloc(&L.d_min_bits, sizeof(uint32_t) * ns));
-            if (l == 0) CHK(hipMalloc(&L.d_thr_bits, sizeof(uint32_t) * ns));  // brute-force kernels only, which run on lane 0
-            CHK(hipMalloc(&L.d_first_idx, sizeof(uint32_t) * ns));
-            CHK(hipMalloc(&L.d_first_idx2, sizeof(uint32_t) * ns));
-            CHK(hipMalloc(&L.d_bp, sizeof(double) * 1024 * 16));
-            CHK(hipMalloc(&L.d_bp2, sizeof(double) * 1024 * 16));
-            CHK(hipMalloc(&L.d_bp3, sizeof(double) * 1024 * 16));
-            CHK(hipStreamCreateWithFlags(&L.icp_stream, hipStreamNonBlocking));
-            CHK(hipEventCreateWithFlags(&L.icp_ev_w, hipEventDisableTiming));
-            CHK(hipEventCreateWithFlags(&L.icp_ev_b, hipEventDisableTiming));
-            CHK(hipMalloc(&L.d_cen, sizeof(float) * 8));
-            CHK(hipHostMalloc((void**)&L.h_cen, sizeof(float) * 8, hipHostMallocMapped));
-            CHK(hipHostGetDevicePointer((void**)&L.hd_cen, L.h_cen, 0));
-            CHK(hipHostMalloc((void**)&L.h_sums, sizeof(double) * 16, hipHostMallocMapped));
-            CHK(hipHostGetDevicePointer((void**)&L.hd_sums, L.h_sums, 0));
-            CHK(hipMalloc(&L.d_wsum, sizeof(double) * 4096 * 6));
-            CHK(hipHostMalloc((void**)&L.h_wsse, sizeof(double) * 4096, hipHostMallocMapped));
-            CHK(hipHostGetDevicePointer((void**)&L.hd_wsse, L.h_wsse, 0));
-            CHK(hipHostMalloc((void**)&L.h_covbp, sizeof(double) * 1024 * 9, hipHostMallocMapped));
-            CHK(hipHostGetDevicePointer((void**)&L.hd_covbp, L.h_covbp, 0));
-        }
-    }
-#undef CHK
+    for (Event* ev : {&sl.sorted_ev, &sl.bounds_ev}) HIPCHK(ev->create(hipEventDisableTiming));
+    HIPCHK(sl.d_groups.alloc(c->max_groups));
+    HIPCHK(sl.d_subs.alloc(subcubes));
+    HIPCHK(sl.h_groups.alloc(c->max_groups));
+    HIPCHK(sl.h_subs.alloc(subcubes));
+    HIPCHK(sl.h_row_span.alloc(subcubes));
+    HIPCHK(sl.h_sort_err.alloc(4));
+    *sl.h_sort_err = 0u;
+    HIPCHK(sl.d_keys.alloc(max_items));
+    HIPCHK(sl.d_ranks.alloc(max_items));
+    HIPCHK(sl.d_hist.alloc(kTickNumKeys));
+    HIPCHK(hipMemset(sl.d_hist, 0, sizeof(unsigned) * kTickNumKeys));  // the scan kernel re-zeroes it after every tick
+    HIPCHK(sl.d_block_sums.alloc(64));
+    HIPCHK(sl.d_hist_xcd.alloc(16 * kTickNumKeys));
+    HIPCHK(hipMemset(sl.d_hist_xcd, 0, sizeof(unsigned) * 16 * kTickNumKeys));
+    HIPCHK(sl.d_xoff.alloc(16 * kTickNumKeys));
+    HIPCHK(sl.d_cursor.alloc(kTickNumKeys));
+    HIPCHK(sl.d_sorted.alloc(max_items));
+    HIPCHK(sl.d_partials.alloc(max_items));
+    HIPCHK(sl.d_cut_acc.alloc(2 * subcubes));
+    HIPCHK(hipMemset(sl.d_cut_acc, 0, sizeof(double) * 2 * subcubes));  // bounds_finalize_kernel re-zeroes what a window used
+    static_assert(sizeof(float) == sizeof(unsigned), "d_row_term is the second half of d_row_cut's allocation");
+    HIPCHK(sl.d_row_cut.alloc(2 * subcubes));
+    sl.d_row_term = reinterpret_cast<unsigned*>(sl.d_row_cut + subcubes);
+    HIPCHK(sl.d_cut_gate.alloc(subcubes));  // written per window, ahead of its bounds kernel
+    if (!c->d_cut_stat) { HIPCHK(c->d_cut_stat.alloc(kCutStatSlots)); HIPCHK(hipMemset(c->d_cut_stat, 0, sizeof(unsigned long long) * kCutStatSlots)); }  // (with the first slot)
+    for (Mapped<float>* h : {&sl.h_lb, &sl.h_ub}) HIPCHK(h->alloc(subcubes));
+    return FGOICP_OK;
+}
+// exact-NN / ICP scratch of one lane; the first lane shares the context's main stream
+int create_icp_lane(fgoicp_ctx* c, fgoicp_ctx::IcpLane& L, bool first) {
+    const size_t ns = c->ns;
+    if (first) L.stream.borrow(c->stream);
+    else HIPCHK(L.stream.create(hipStreamNonBlocking));
+    HIPCHK(L.d_work.alloc(ns));
+    HIPCHK(L.d_min_bits.alloc(ns));
+    if (first) HIPCHK(L.d_thr_bits.alloc(ns));  // brute-force kernels only, which run on lane 0
+    for (Dev<uint32_t>* d : {&L.d_first_idx, &L.d_first_idx2}) HIPCHK(d->alloc(ns));
+    for (Dev<double>* d : {&L.d_bp, &L.d_bp2, &L.d_bp3}) HIPCHK(d->alloc(1024 * 16));
+    HIPCHK(L.icp_stream.create(hipStreamNonBlocking));
+    for (Event* e : {&L.icp_ev_w, &L.icp_ev_b}) HIPCHK(e->create(hipEventDisableTiming));
+    HIPCHK(L.d_cen.alloc(8));
+    HIPCHK(L.h_cen.alloc(8));
+    HIPCHK(L.h_sums.alloc(16));
+    HIPCHK(L.d_wsum.alloc(4096 * 6));
+    HIPCHK(L.h_wsse.alloc(4096));
+    HIPCHK(L.h_covbp.alloc(1024 * 9));
+    return FGOICP_OK;
+}
+}  // namespace
+
+// fgoicp_lut_nodes, fgoicp_lut_search: n queries of three T each through `launch`, one float back per query, on the context's stream
+template <class T, class Launch>
+static int lut_query(fgoicp_ctx* c, const T* q, size_t n, float* out, Launch launch) {
+    if (!c || !q || !out) return FGOICP_ERR_INVALID_ARG;
+    if (n == 0) return FGOICP_OK;
+    HIPCHK(hipSetDevice(c->device));
+    Dev<T> dq;
+    Dev<float> dout;
+    HIPCHK(dq.alloc(3 * n));
+    hipError_t e = dout.alloc(n);
+    if (e == hipSuccess) e = hipMemcpyAsync(dq, q, 3 * n * sizeof(T), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) { launch(dq.get(), dout.get()); e = hipGetLastError(); }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, dout, n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    HIPCHK(e);
+    return FGOICP_OK;
+}
+
+}  // namespace fgoicp
+
+using namespace fgoicp;
+
+extern "C" {
+
+const char* fgoicp_last_error(void) { return g_last_error.c_str(); }
+const char* fgoicp_version(void) { return kDevKnobs ? "fgoicp_amd 0.4 (gfx950, development build)" : "fgoicp_amd 0.4 (gfx950)"; }
+int fgoicp_dev_knobs(void) { return kDevKnobs ? 1 : 0; }
+int fgoicp_abi_version(void) { return FGOICP_ABI_VERSION; }
+
+static int ctx_create_impl(const CreateArgs& a, fgoicp_ctx** out) {
+    int rc = create_refuse_args(a);
+    if (!rc) rc = create_select_device(a.device);
+    if (rc) return rc;
+    // what a failed stage or an exception (std::bad_alloc in a host-side table, a thread that cannot start) leaves half-built goes with `c`
+    std::unique_ptr<fgoicp_ctx, void (*)(fgoicp_ctx*)> c(new fgoicp_ctx(), fgoicp_ctx_destroy);
+    if ((rc = create_head(c.get(), a)) || (rc = create_lut_geometry(c.get(), a)) || (rc = create_source(c.get(), a)) || (rc = create_target_lut(c.get(), a)) ||
+        (rc = create_packed_lut(c.get())) || (rc = create_window_sizes(c.get())))
+        return rc;
+    if ((rc = create_run_centres(c.get(), a.src_xyz, (size_t)c->chunk_pts, c->d_chunk_cen)) ||
+        (c->cut_span > 1 && (rc = create_run_centres(c.get(), a.src_xyz, (size_t)c->chunk_pts * c->cut_span, c->d_span_cen))))
+        return rc;
+    for (auto& sl : c->slots)
+        if ((rc = create_tick_slot(c.get(), sl))) return rc;
+    int nl = 4;  // concurrent ICP runs (ctx_icp_batch)
+    if (const char* e = dev_env("FGOICP_ICP_LANES")) nl = std::max(1, std::min(16, std::atoi(e)));  // tuning knob
+    if (const char* e = dev_env("FGOICP_ICP_OVERLAP")) c->icp_overlap = std::atoi(e) != 0;       // tuning knob
+    if (const char* e = dev_env("FGOICP_ICP_DUAL")) c->icp_dual_env = std::atoi(e) != 0 ? 1 : 0; // tuning knob / A-B: 1 = one walk for both scans of an iteration, 0 = two scans on two streams
+    if (const char* e = dev_env("FGOICP_ICP_FUSE")) c->icp_fuse = std::atoi(e) != 0;             // tuning knob / A-B: 0 = separate reduction kernels
+    c->lanes.resize((size_t)nl);
+    for (int l = 0; l < nl; ++l)
+        if ((rc = create_icp_lane(c.get(), c->lanes[(size_t)l], l == 0))) return rc;
     if (c->profile) {
         c->profile = false;
-        int rc = fgoicp_ctx_set_profile(c, 1);
-        if (rc) { fgoicp_ctx_destroy(c); return rc; }
+        if ((rc = fgoicp_ctx_set_profile(c.get(), 1))) return rc;
     }
-    *out = c;
+    *out = c.release();
     return FGOICP_OK;
+}
+int fgoicp_ctx_create(const float* tgt_xyz, size_t nt, const float* src_xyz, size_t ns, const float* bounds6, float lut_resolution,
+                      int device, unsigned flags, fgoicp_ctx** out) {
+    if (!out) return FGOICP_ERR_INVALID_ARG;
+    *out = nullptr;
+    const CreateArgs a{tgt_xyz, nt, src_xyz, ns, bounds6, lut_resolution, device, flags};
+    return fgoicp::abi_guard("fgoicp_ctx_create", [&] { return ctx_create_impl(a, out); });
+}
+
+fgoicp_ctx::~fgoicp_ctx() {
+    (void)hipSetDevice(device);
+    stream.sync();
+    for (auto& L : lanes) { L.stream.sync(); L.icp_stream.sync(); }
+    for (auto& sl : slots) sl.sort_stream.sync();
 }
 
 void fgoicp_ctx_destroy(fgoicp_ctx* c) {
@@ -1749,55 +1745,6 @@ void fgoicp_ctx_destroy(fgoicp_ctx* c) {
                      1e6 * g_tt.pack / g_tt.ticks, 1e6 * g_tt.enqueue / g_tt.ticks, 1e6 * g_tt.wait / g_tt.ticks, 1e6 * g_tt.copyout / g_tt.ticks);
         g_tt = TickTiming{};
     }
-    (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (auto& e : c->ev_start) if (e) (void)hipEventDestroy(e);
-    for (auto& e : c->ev_stop) if (e) (void)hipEventDestroy(e);
-    for (auto& e : c->ev_sel_start) if (e) (void)hipEventDestroy(e);
-    for (auto& e : c->ev_sel_stop) if (e) (void)hipEventDestroy(e);
-    (void)hipFree(c->d_src); (void)hipFree(c->d_tgt); (void)hipFree(c->d_lut); (void)hipFree(c->d_lut_idx); (void)hipFree(c->d_lut_zp);
-    (void)hipFree(c->d_cut_stat);
-    for (auto& L : c->lanes) {
-        if (L.stream && L.stream != c->stream) { (void)hipStreamSynchronize(L.stream); (void)hipStreamDestroy(L.stream); }
-        if (L.icp_stream) { (void)hipStreamSynchronize(L.icp_stream); (void)hipStreamDestroy(L.icp_stream); }
-        if (L.icp_ev_w) (void)hipEventDestroy(L.icp_ev_w);
-        if (L.icp_ev_b) (void)hipEventDestroy(L.icp_ev_b);
-        (void)hipFree(L.d_wsum);
-        if (L.h_wsse) (void)hipHostFree(L.h_wsse);
-        if (L.h_covbp) (void)hipHostFree(L.h_covbp);
-        (void)hipFree(L.d_work); (void)hipFree(L.d_min_bits); (void)hipFree(L.d_thr_bits); (void)hipFree(L.d_first_idx); (void)hipFree(L.d_first_idx2);
-        (void)hipFree(L.d_bp); (void)hipFree(L.d_bp2); (void)hipFree(L.d_bp3); (void)hipFree(L.d_cen);
-        (void)hipFree(L.d_d2); (void)hipFree(L.d_nn_lb); (void)hipFree(L.d_nn_ub); (void)hipFree(L.d_nn_lb2); (void)hipFree(L.d_nn_ub2);
-        (void)hipFree(L.d_sel); (void)hipFree(L.d_eq); (void)hipFree(L.d_use); (void)hipFree(L.d_sel_wide); (void)hipFree(L.d_sel_wide2);
-        if (L.h_cen) (void)hipHostFree(L.h_cen);
-        if (L.h_sums) (void)hipHostFree(L.h_sums);
-        if (L.h_trim) (void)hipHostFree(L.h_trim);
-    }
-    bvh_free(&c->bvh_tgt);
-    (void)hipFree(c->d_chunk_cen);
-    (void)hipFree(c->d_span_cen);
-    (void)hipFree(c->d_orig_of_slot);
-    (void)hipFree(c->align.base);
-    (void)hipFree(c->d_normals); (void)hipFree(c->d_plane_rows); (void)hipFree(c->d_plane_out); (void)hipFree(c->d_src_normals);
-    for (int k = 0; k < 2; ++k) {
-        fgoicp_ctx::TickSlot& sl = c->slots[k];
-        if (sl.done) (void)hipEventDestroy(sl.done);
-        if (sl.sorted_ev) (void)hipEventDestroy(sl.sorted_ev);
-        if (sl.bounds_ev) (void)hipEventDestroy(sl.bounds_ev);
-        if (sl.sort_stream && sl.sort_stream != c->stream) { (void)hipStreamSynchronize(sl.sort_stream); (void)hipStreamDestroy(sl.sort_stream); }
-        (void)hipFree(sl.d_evals);
-        (void)hipFree(c->d_trim_stat); c->d_trim_stat = nullptr;
-        (void)hipFree(c->d_coop); c->d_coop = nullptr; c->coop_cap = 0;
-        if (sl.h_row_span) (void)hipHostFree(sl.h_row_span);
-        if (sl.h_sort_err) (void)hipHostFree(sl.h_sort_err);
-        (void)hipFree(sl.d_groups); (void)hipFree(sl.d_subs); (void)hipFree(sl.d_keys); (void)hipFree(sl.d_ranks); (void)hipFree(sl.d_hist);
-        (void)hipFree(sl.d_cursor); (void)hipFree(sl.d_block_sums); (void)hipFree(sl.d_hist_xcd); (void)hipFree(sl.d_xoff); (void)hipFree(sl.d_sorted); (void)hipFree(sl.d_partials); (void)hipFree(sl.d_cut_acc); (void)hipFree(sl.d_row_cut); (void)hipFree(sl.d_cut_gate);
-        if (sl.h_groups) (void)hipHostFree(sl.h_groups);
-        if (sl.h_subs) (void)hipHostFree(sl.h_subs);
-        if (sl.h_lb) (void)hipHostFree(sl.h_lb);
-        if (sl.h_ub) (void)hipHostFree(sl.h_ub);
-    }
-    if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
 
@@ -1844,47 +1791,19 @@ int fgoicp_lut_read(fgoicp_ctx* c, float* out, size_t capacity) {
     const size_t total = (size_t)c->geom.dx * c->geom.dy * c->geom.dz;
     if (capacity < total) { set_error("fgoicp_lut_read: buffer too small"); return FGOICP_ERR_INVALID_ARG; }
     HIPCHK(hipSetDevice(c->device));
-    float* d = nullptr;
-    HIPCHK(hipMalloc(&d, total * sizeof(float)));
+    Dev<float> d;
+    HIPCHK(d.alloc(total));
     launch_lut_unpad(c->d_lut, c->geom, d, c->stream);
-    hipError_t e = hipMemcpyAsync(out, d, total * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d);
-    HIPCHK(e);
+    HIPCHK(hipMemcpyAsync(out, d, total * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
     return FGOICP_OK;
 }
 
 int fgoicp_lut_nodes(fgoicp_ctx* c, const int* xyz, size_t n, float* out) {
-    if (!c || !xyz || !out) return FGOICP_ERR_INVALID_ARG;
-    if (n == 0) return FGOICP_OK;
-    HIPCHK(hipSetDevice(c->device));
-    int* dq = nullptr;
-    float* dout = nullptr;
-    HIPCHK(hipMalloc(&dq, 3 * n * sizeof(int)));
-    hipError_t e = hipMalloc(&dout, n * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpyAsync(dq, xyz, 3 * n * sizeof(int), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) { launch_lut_nodes(c->d_lut, c->geom, dq, n, dout, c->stream); e = hipGetLastError(); }
-    if (e == hipSuccess) e = hipMemcpyAsync(out, dout, n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(dq); (void)hipFree(dout);
-    HIPCHK(e);
-    return FGOICP_OK;
+    return lut_query(c, xyz, n, out, [&](const int* dq, float* dout) { launch_lut_nodes(c->d_lut, c->geom, dq, n, dout, c->stream); });
 }
-
 int fgoicp_lut_search(fgoicp_ctx* c, const float* q, size_t n, float* out) {
-    if (!c || !q || !out) return FGOICP_ERR_INVALID_ARG;
-    if (n == 0) return FGOICP_OK;
-    HIPCHK(hipSetDevice(c->device));
-    float *dq = nullptr, *dout = nullptr;
-    HIPCHK(hipMalloc(&dq, 3 * n * sizeof(float)));
-    hipError_t e = hipMalloc(&dout, n * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpyAsync(dq, q, 3 * n * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) { launch_lut_search(c->d_lut, c->geom, dq, n, dout, c->stream); e = hipGetLastError(); }
-    if (e == hipSuccess) e = hipMemcpyAsync(out, dout, n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(dq); (void)hipFree(dout);
-    HIPCHK(e);
-    return FGOICP_OK;
+    return lut_query(c, q, n, out, [&](const float* dq, float* dout) { launch_lut_search(c->d_lut, c->geom, dq, n, dout, c->stream); });
 }
 
 int fgoicp_bounds_multi(fgoicp_ctx* c, int G, const float* R9, const float* rot_span, const int* fix_rot, const int* offsets,
@@ -1958,6 +1877,13 @@ int fgoicp_bounds_point_distances(fgoicp_ctx* c, const float* R9, float rot_span
 int fgoicp_ctx_test_sort_fault(fgoicp_ctx* c, int nth_tick) {
     if (!c || nth_tick < 0) return FGOICP_ERR_INVALID_ARG;
     c->sort_fault_tick = nth_tick ? (int)c->sorted_ticks + nth_tick : 0;
+    return FGOICP_OK;
+}
+
+// TEST HOOK (tests/test_gpu_ctx_lifetime.py): the live counts of owned.hpp
+int fgoicp_test_live_resources(uint64_t out4[4]) {
+    if (!out4) return FGOICP_ERR_INVALID_ARG;
+    out4[0] = live::dev; out4[1] = live::pinned; out4[2] = live::streams; out4[3] = live::events;
     return FGOICP_OK;
 }
 
@@ -2122,13 +2048,14 @@ int fgoicp_ctx_set_inliers(fgoicp_ctx* c, size_t k) {
     return ctx_set_inliers(c, k);
 }
 
+static int flush_pending_profile(fgoicp_ctx* c) {  // drains the main stream if events are waiting to be read
+    if (!c->ev_used) return FGOICP_OK;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return ctx_flush_profile(c);
+}
 int fgoicp_ctx_profile(fgoicp_ctx* c, double* kernel_ms, uint64_t* launches, uint64_t* subcubes, int reset) {
     if (!c) return FGOICP_ERR_INVALID_ARG;
-    if (c->ev_used) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        int rc = ctx_flush_profile(c);
-        if (rc) return rc;
-    }
+    if (int rc = flush_pending_profile(c)) return rc;
     if (kernel_ms) *kernel_ms = c->prof_ms;
     if (launches) *launches = c->prof_launches;
     if (subcubes) *subcubes = c->prof_subcubes;
@@ -2138,11 +2065,7 @@ int fgoicp_ctx_profile(fgoicp_ctx* c, double* kernel_ms, uint64_t* launches, uin
 
 int fgoicp_ctx_profile_select_ms(fgoicp_ctx* c, double* select_ms) {
     if (!c || !select_ms) return FGOICP_ERR_INVALID_ARG;
-    if (c->ev_used) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        int rc = ctx_flush_profile(c);
-        if (rc) return rc;
-    }
+    if (int rc = flush_pending_profile(c)) return rc;
     *select_ms = c->prof_sel_ms;
     return FGOICP_OK;
 }
@@ -2180,23 +2103,14 @@ int fgoicp_ctx_set_profile(fgoicp_ctx* c, int enabled) {
     if (!c) return FGOICP_ERR_INVALID_ARG;
     HIPCHK(hipSetDevice(c->device));
     if (enabled && c->ev_start.empty()) {
-        c->ev_start.assign(1024, nullptr);
-        c->ev_stop.assign(1024, nullptr);
-        c->ev_sel_start.assign(1024, nullptr);
-        c->ev_sel_stop.assign(1024, nullptr);
         c->ev_has_sel.assign(1024, 0);
-        for (size_t i = 0; i < c->ev_start.size(); ++i) {
-            HIPCHK(hipEventCreate(&c->ev_start[i]));
-            HIPCHK(hipEventCreate(&c->ev_stop[i]));
-            HIPCHK(hipEventCreate(&c->ev_sel_start[i]));
-            HIPCHK(hipEventCreate(&c->ev_sel_stop[i]));
-        }
+        std::vector<Event>* const evs[4] = {&c->ev_start, &c->ev_stop, &c->ev_sel_start, &c->ev_sel_stop};
+        for (auto* v : evs) *v = std::vector<Event>(1024);
+        for (size_t i = 0; i < 1024; ++i)
+            for (auto* v : evs) HIPCHK((*v)[i].create());  // start, stop, sel_start, sel_stop per index; default flags: they time
     }
-    if (!enabled && c->ev_used) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        int rc = ctx_flush_profile(c);
-        if (rc) return rc;
-    }
+    if (!enabled)
+        if (int rc = flush_pending_profile(c)) return rc;
     c->profile = enabled != 0;
     return FGOICP_OK;
 }

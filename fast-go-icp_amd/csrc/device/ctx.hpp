@@ -19,23 +19,26 @@
 #include "../host/gicp.hpp"
 #include "bvh.hpp"
 #include "kernels.hpp"
+#include "owned.hpp"
 
+// Every buffer, stream and event below is a handle (owned.hpp) and goes with its owner: the context, a tick slot or an ICP lane.
 struct fgoicp_ctx {
+    ~fgoicp_ctx();  // sets the device, drains every stream the context owns, then lets the members go (ctx.hip)
     int device = 0;
-    hipStream_t stream = nullptr;
+    fgoicp::Stream stream;  // declared first, destroyed last: lane 0, both slots and (FGOICP_SORT_STREAM=0) the sort streams borrow it
     size_t ns = 0, nt = 0;
     bool profile = false;
 
     // HBM-resident state
-    float4* d_src = nullptr;     // ns  x {x,y,z,|p|^2}, Morton order (pristine source, registration.hpp:63)
-    float4* d_tgt = nullptr;     // nt  x {x,y,z,0}, caller order (registration.hpp:61)
-    float* d_lut = nullptr;      // (dx+2)(dy+2)(dz+2) floats, x fastest, replicated border
+    fgoicp::Dev<float4> d_src;           // ns  x {x,y,z,|p|^2}, Morton order (pristine source, registration.hpp:63)
+    fgoicp::Dev<float4> d_tgt;           // nt  x {x,y,z,0}, caller order (registration.hpp:61)
+    fgoicp::Dev<float> d_lut;            // (dx+2)(dy+2)(dz+2) floats, x fastest, replicated border
     int lut_layout = 1;          // 1: d_lut_zp is the z-paired copy (float2), 2: the yz-quad copy (float4), 4: the apron-bricked yz-quads (float4)
     int source_order = 0, tree_order = 0;  // what ctx_create chose (fgoicp_ctx_get_info)
-    uint32_t* d_lut_idx = nullptr;  // index LUT (geom.idx): per padded node the caller index of a nearest target point; seeds of the exact scans (FGOICP_LUT_INDEX=0: none)
-    float2* d_lut_zp = nullptr;  // z-paired copy {T[o], T[o + z-slice]} for the bounds kernel (2x the bytes, half the gathers)
+    fgoicp::Dev<uint32_t> d_lut_idx;        // index LUT (geom.idx): per padded node the caller index of a nearest target point; seeds of the exact scans (FGOICP_LUT_INDEX=0: none)
+    fgoicp::Dev<float2> d_lut_zp;        // z-paired copy {T[o], T[o + z-slice]} for the bounds kernel (2x the bytes, half the gathers)
     fgoicp::LutGeom geom{};
-    fgoicp::BvhDevice bvh_tgt;   // exact-NN tree over the target (caller indices in pts[].w)
+    fgoicp::BvhOwned bvh_tgt;    // exact-NN tree over the target (caller indices in pts[].w)
     bool brute_force_nn = false; // FGOICP_FLAG_BRUTE_FORCE_NN: O(ns*nt) kernels instead of the tree
     std::vector<uint32_t> perm;  // device slot i holds caller point perm[i]
 
@@ -46,35 +49,35 @@ struct fgoicp_ctx {
     // Two tick slots: the host prepares / consumes one half of a round's inner BnBs while the device
     // evaluates the other (fgoicp_bounds_submit / _collect).
     struct TickSlot {
-        hipStream_t stream = nullptr;            // both slots queue on the context stream: their kernels run back to back, never
+        fgoicp::Stream stream;                           // both slots queue on the context stream (borrowed): their kernels run back to back, never
                                                  // concurrently (two sorted kernels at once would thrash each other's L2 neighbourhoods)
-        hipEvent_t done = nullptr;               // recorded behind the slot's last kernel; collect waits on it, not on the stream
-        hipStream_t sort_stream = nullptr;       // descriptors upload + locality sort of THIS slot run here, next to the other
-        hipEvent_t bounds_ev = nullptr;          // bounds kernel of this slot finished (the finalize on the side stream waits for it)
-        hipEvent_t sorted_ev = nullptr;          //   slot's bounds kernel on the main stream, which then waits for sorted_ev
-        fgoicp::TickGroup *d_groups = nullptr, *h_groups = nullptr, *hd_groups = nullptr;   // device / pinned staging / its device alias
-        fgoicp::TickSub *d_subs = nullptr, *h_subs = nullptr, *hd_subs = nullptr;
-        unsigned short* d_keys = nullptr;
-        unsigned* d_ranks = nullptr;             // place of every item inside its key's bin (returned by the histogram atomic)
-        unsigned *d_hist = nullptr, *d_block_sums = nullptr, *d_cursor = nullptr, *d_sorted = nullptr;
-        unsigned *d_hist_xcd = nullptr, *d_xoff = nullptr;   // per-XCD histograms of the tick sort and their offsets inside a bin
-        double2* d_partials = nullptr;           // [max_subcubes][nchunk1] {sum_ub, sum_lb}
-        double* d_cut_acc = nullptr;             // early exit (fgoicp_bounds_submit_cut): 2 running sums per evaluation, zero between windows
-        float* d_row_cut = nullptr;              // ... and the threshold of every output row
-        unsigned* d_row_term = nullptr;          // ... and whether the row is terminal (fgoicp_bounds_submit_leaf): the tail of d_row_cut's allocation
-        fgoicp::TickGate* d_cut_gate = nullptr;  // ... and what an item waits for first: "finished" and "cutting" per evaluation
+        fgoicp::Event done;                              // recorded behind the slot's last kernel; collect waits on it, not on the stream
+        fgoicp::Stream sort_stream;                      // descriptors upload + locality sort of THIS slot run here, next to the other
+        fgoicp::Event bounds_ev;                         // bounds kernel of this slot finished (the finalize on the side stream waits for it)
+        fgoicp::Event sorted_ev;                         //   slot's bounds kernel on the main stream, which then waits for sorted_ev
+        fgoicp::Dev<fgoicp::TickGroup> d_groups; fgoicp::Mapped<fgoicp::TickGroup> h_groups;   // device / pinned staging (dev(): its device alias)
+        fgoicp::Dev<fgoicp::TickSub> d_subs; fgoicp::Mapped<fgoicp::TickSub> h_subs;
+        fgoicp::Dev<unsigned short> d_keys;
+        fgoicp::Dev<unsigned> d_ranks;                   // place of every item inside its key's bin (returned by the histogram atomic)
+        fgoicp::Dev<unsigned> d_hist, d_block_sums, d_cursor, d_sorted;
+        fgoicp::Dev<unsigned> d_hist_xcd, d_xoff;        // per-XCD histograms of the tick sort and their offsets inside a bin
+        fgoicp::Dev<double2> d_partials;                 // [max_subcubes][nchunk1] {sum_ub, sum_lb}
+        fgoicp::Dev<double> d_cut_acc;                   // early exit (fgoicp_bounds_submit_cut): 2 running sums per evaluation, zero between windows
+        fgoicp::Dev<float> d_row_cut;                    // ... and the threshold of every output row
+        unsigned* d_row_term = nullptr;          // ... and whether the row is terminal (fgoicp_bounds_submit_leaf): a view of the tail of d_row_cut's allocation
+        fgoicp::Dev<fgoicp::TickGate> d_cut_gate;        // ... and what an item waits for first: "finished" and "cutting" per evaluation
         bool win_cut = false;                    // the window in flight carries thresholds
-        float *h_lb = nullptr, *h_ub = nullptr, *hd_lb = nullptr, *hd_ub = nullptr;  // pinned results of the window in flight
-        float* d_evals = nullptr;                // trimmed mode: per-point e = max(d, 0) of every output row, [vals_rows][erow]
-        float *h_row_span = nullptr, *hd_row_span = nullptr;   // translation span of every output row of the window (pinned)
-        unsigned *h_sort_err = nullptr, *hd_sort_err = nullptr; // pinned: set by the bounds kernel when `sorted` is no permutation
+        fgoicp::Mapped<float> h_lb, h_ub;                // pinned results of the window in flight
+        fgoicp::Dev<float> d_evals;                      // trimmed mode: per-point e = max(d, 0) of every output row, [vals_rows][erow]
+        fgoicp::Mapped<float> h_row_span;                // translation span of every output row of the window (pinned)
+        fgoicp::Mapped<unsigned> h_sort_err;             // pinned: set by the bounds kernel when `sorted` is no permutation
         int win_groups = 0, win_evals = 0;       // the window in flight: groups and evaluations in the staging buffers
         std::vector<float> lb, ub;
         std::vector<int> row_group;              // window-local group of every output row (packing scratch)               // results of the whole submission
         int total = 0, win_pos = 0, win_rows = 0;
         bool inflight = false;
     };
-    unsigned long long* d_cut_stat = nullptr;    // items the early exit did not evaluate, since creation (device counter)
+    fgoicp::Dev<unsigned long long> d_cut_stat;          // items the early exit did not evaluate, since creation (device counter)
     uint64_t cut_items_offered = 0;              // items of the windows submitted with thresholds
     uint64_t cut_verify_windows = 0, cut_verify_rows = 0, cut_verify_above = 0, cut_verify_bad = 0;  // development build, FGOICP_CUT_VERIFY
     uint64_t cut_stat_base = 0;                  // value of *d_cut_stat at the last reset
@@ -91,10 +94,10 @@ struct fgoicp_ctx {
                                              // iteration on top: 25-44 ms of ICP per rank split against 41 ms replicated, 6.2x against 6.4x with the gathers charged
     size_t coop_split_trim_min = 262144;     // ... trimmed contexts split from this size on: a trimmed iteration is long (1.5 ms at 1M points, 85 % of it the walk) and splitting pays — 8-rank replay of the 1M trimmed run 1.84x -> 2.69x (2.45x with the 632 gathers charged)
     bool icp_seeding = true;                 // ICP passes seed their exact NN search with the previous pass's correspondences
-    float4* d_chunk_cen = nullptr;           // centroid of every chunk (source frame)
+    fgoicp::Dev<float4> d_chunk_cen;                 // centroid of every chunk (source frame)
     float cut_tier_level = 0.5f;             // windows with thresholds: items whose per-point term at the patch centre reaches this multiple of T / ns go first (0: one tier)
     int cut_span = 1;                        // chunks per work item in windows with thresholds (2 on sparse clouds: see bounds_item_kernel)
-    float4* d_span_cen = nullptr;            // centroid of every run of cut_span chunks
+    fgoicp::Dev<float4> d_span_cen;                  // centroid of every run of cut_span chunks
     TickSlot slots[2];
 
     // EXTENSION: trimmed Go-ICP (sum of the `inliers` smallest per-point terms; 0 = off)
@@ -104,20 +107,20 @@ struct fgoicp_ctx {
     int trim_samp_shift = 5;                 // trimmed mode: every 2^shift-th point goes into the row's sample (0: none, two-pass selection)
     float trim_margin_sd = 1.0f;             // bracket half-width in standard deviations of a binomial sample rank
     int trim_margin = 0;                     // ... in sample ranks (set with the inlier count)
-    uint32_t* d_coop = nullptr;              // cooperative ICP: {correspondence indices | bits of the minima}, coop_cap entries each (all ranks' shares)
+    fgoicp::Dev<uint32_t> d_coop;                    // cooperative ICP: {correspondence indices | bits of the minima}, coop_cap entries each (all ranks' shares)
     size_t coop_cap = 0;
-    unsigned long long* d_trim_stat = nullptr;        // {rows selected, rows that fell back to two passes, bracket members}
+    fgoicp::Dev<unsigned long long> d_trim_stat;              // {rows selected, rows that fell back to two passes, bracket members}
     uint64_t trim_stat_acc[3] = {0, 0, 0};
     bool trim_ready = false;                 // trimmed-mode buffers allocated
     bool trim_skip = true;                   // exact NN only for queries that can be among the k smallest (nn_prep_kernel)
     float bounds6[6] = {0, 0, 0, 0, 0, 0};   // target_bounds as passed to fgoicp_ctx_create (they place the LUT)
     float tgt_box6[6] = {0, 0, 0, 0, 0, 0};  // the target's bounding box computed from the points (trimmed search: nn_prep_kernel)
-    uint32_t* d_orig_of_slot = nullptr;      // caller index of every device slot (ties at the inlier cut; the alignment report)
+    fgoicp::Dev<uint32_t> d_orig_of_slot;            // caller index of every device slot (ties at the inlier cut; the alignment report)
 
     // the alignment report (ctx_alignment) and the information moments (ctx_information): one allocation on the first call, 13 bytes per source
     // point, one per target point and 88 per block of kBlock source points
     struct AlignScratch {
-        void* base = nullptr;
+        fgoicp::Dev<char> base;                          // the one allocation; every pointer below is a view into it (Arena)
         uint32_t* d_idx = nullptr;               // correspondences, device order
         uint32_t* d_corr = nullptr;              // ... and the report in caller order: correspondences, squared distances, inlier flags
         float* d_d2 = nullptr;
@@ -131,36 +134,36 @@ struct fgoicp_ctx {
 
     // target normals and the point-to-plane normal equations (ctx_set_target_normals, ctx_plane_moments): each allocated by the first call
     // that needs it — 16 bytes per target point, 232 per block of kBlock source points
-    float4* d_normals = nullptr;             // nt x {n.x, n.y, n.z, 0}, caller order; the zero vector: no normal
+    fgoicp::Dev<float4> d_normals;                   // nt x {n.x, n.y, n.z, 0}, caller order; the zero vector: no normal
     bool normals_set = false;
-    fgoicp::MomentRow<fgoicp::kPlaneTerms>* d_plane_rows = nullptr;
-    unsigned long long* d_plane_out = nullptr;   // {count, the bits of 28 sums} (launch_plane_moments)
+    fgoicp::Dev<fgoicp::MomentRow<fgoicp::kPlaneTerms>> d_plane_rows;
+    fgoicp::Dev<unsigned long long> d_plane_out;         // {count, the bits of 28 sums} (launch_plane_moments)
     // source normals of the Generalized-ICP refinement (ctx_set_source_normals): allocated by the first call, 16 bytes per source point
-    float4* d_src_normals = nullptr;         // ns x {n.x, n.y, n.z, 0}, DEVICE SLOT order (perm); the zero vector: no normal
+    fgoicp::Dev<float4> d_src_normals;               // ns x {n.x, n.y, n.z, 0}, DEVICE SLOT order (perm); the zero vector: no normal
     bool src_normals_set = false;
 
     // exact-NN / ICP scratch, one set per lane: ICP runs on different lanes may be in flight together (ctx_icp_batch).  Lane 0 is
     // the lane of fgoicp_sse / fgoicp_icp / fgoicp_procrustes and queues on the context's main stream.
     struct IcpLane {
-        hipStream_t stream = nullptr;            // main stream of the lane (SSE pass, working-cloud transforms)
-        hipStream_t icp_stream = nullptr;        // side stream (correspondence + covariance pass of the NEXT iteration)
-        hipEvent_t icp_ev_w = nullptr, icp_ev_b = nullptr;  // working cloud transformed / side-stream pass finished
-        float4* d_work = nullptr;                // ns x {x,y,z,-}: ICP working copy (icp3d.hpp:24)
-        uint32_t *d_min_bits = nullptr, *d_thr_bits = nullptr, *d_first_idx = nullptr, *d_first_idx2 = nullptr;
-        double *d_bp = nullptr, *d_bp2 = nullptr, *d_bp3 = nullptr;   // per-block partial sums (sums / covariance / SSE)
-        double *h_sums = nullptr, *hd_sums = nullptr;                 // pinned result of the last reduction (<= 16 doubles)
-        float* d_cen = nullptr;                  // centroids {src, corr} on the device
-        float *h_cen = nullptr, *hd_cen = nullptr;  // ... and their pinned host copy
+        fgoicp::Stream stream;                           // main stream of the lane (SSE pass, working-cloud transforms); lane 0 borrows the context's
+        fgoicp::Stream icp_stream;                       // side stream (correspondence + covariance pass of the NEXT iteration)
+        fgoicp::Event icp_ev_w, icp_ev_b;                // working cloud transformed / side-stream pass finished
+        fgoicp::Dev<float4> d_work;                      // ns x {x,y,z,-}: ICP working copy (icp3d.hpp:24)
+        fgoicp::Dev<uint32_t> d_min_bits, d_thr_bits, d_first_idx, d_first_idx2;
+        fgoicp::Dev<double> d_bp, d_bp2, d_bp3;          // per-block partial sums (sums / covariance / SSE)
+        fgoicp::Mapped<double> h_sums;                   // pinned result of the last reduction (<= 16 doubles)
+        fgoicp::Dev<float> d_cen;                        // centroids {src, corr} on the device
+        fgoicp::Mapped<float> h_cen;                     // ... and their pinned host copy
         // trimmed mode
-        float* d_d2 = nullptr;                   // squared correspondence distances
-        float *d_nn_lb = nullptr, *d_nn_ub = nullptr, *d_nn_lb2 = nullptr, *d_nn_ub2 = nullptr;  // LUT brackets of the nearest distance (SSE pass / correspondence pass)
-        uint32_t *d_sel = nullptr, *d_eq = nullptr, *d_sel_wide = nullptr, *d_sel_wide2 = nullptr;
-        unsigned char* d_use = nullptr;          // inlier mask of the current Procrustes step
-        float *h_trim = nullptr, *hd_trim = nullptr;   // pinned trimmed SSE
+        fgoicp::Dev<float> d_d2;                         // squared correspondence distances
+        fgoicp::Dev<float> d_nn_lb, d_nn_ub, d_nn_lb2, d_nn_ub2;  // LUT brackets of the nearest distance (SSE pass / correspondence pass)
+        fgoicp::Dev<uint32_t> d_sel, d_eq, d_sel_wide, d_sel_wide2;
+        fgoicp::Dev<unsigned char> d_use;                // inlier mask of the current Procrustes step
+        fgoicp::Mapped<float> h_trim;                    // pinned trimmed SSE
         // fused reductions of small clouds (ns <= 262144; ctx.hip icp_fused): wave sums from the scans' epilogues, final folds on the host
-        double* d_wsum = nullptr;                // [groups][6] wave-level sums {query xyz, correspondence xyz} of the last correspondence scan
-        double *h_wsse = nullptr, *hd_wsse = nullptr;     // pinned: [groups] wave-level sums of the last SSE scan
-        double *h_covbp = nullptr, *hd_covbp = nullptr;   // pinned: [blocks][9] block partials of the covariance
+        fgoicp::Dev<double> d_wsum;                      // [groups][6] wave-level sums {query xyz, correspondence xyz} of the last correspondence scan
+        fgoicp::Mapped<double> h_wsse;                   // pinned: [groups] wave-level sums of the last SSE scan
+        fgoicp::Mapped<double> h_covbp;                  // pinned: [blocks][9] block partials of the covariance
         bool cov_on_host = false, sse_on_host = false;    // where the result of the last enqueued pass lands
         int cov_blocks = 0;
     };
@@ -170,7 +173,7 @@ struct fgoicp_ctx {
     int icp_dual_env = -1;                   // FGOICP_ICP_DUAL: one walk serves the two scans of an ICP iteration (nn_scan_dual_kernel); -1 = by cloud size
 
     // HIP-event profile of the bounds kernel
-    std::vector<hipEvent_t> ev_start, ev_stop, ev_sel_start, ev_sel_stop;   // bounds kernel / trimmed selection kernel of the same window
+    std::vector<fgoicp::Event> ev_start, ev_stop, ev_sel_start, ev_sel_stop;   // bounds kernel / trimmed selection kernel of the same window
     std::vector<char> ev_has_sel;
     std::vector<int> ev_evals;          // evaluations of the launch an event pair brackets (FGOICP_TICK_LOG)
     double prof_sel_ms = 0.0, prof_sel_ms_last = 0.0;

@@ -140,7 +140,7 @@ int farthest_point_sample_impl(const float* xyz, size_t n, size_t m, size_t star
     if (const int rc = select_device(call, device)) return rc;
 
     OneShot d(call);
-    ONECHK(call, hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking));
+    ONECHK(call, d.stream.create(hipStreamNonBlocking));
     const uint32_t n32 = (uint32_t)n, m32 = (uint32_t)m;
     const uint32_t per_point = (uint32_t)((n + kFpsBlock - 1) / kFpsBlock);
     const uint32_t nblocks = per_point < kFpsMaxBlocks ? per_point : kFpsMaxBlocks;  // above 1024 x 256 points a block loops over its slice
@@ -152,7 +152,7 @@ int farthest_point_sample_impl(const float* xyz, size_t n, size_t m, size_t star
     plan.take(d_rec, n); plan.take(d_keys, 2 * (size_t)kFpsMaxBlocks); plan.take(d_out, 3 * m); plan.take(d_idx, m); plan.take(d_pick, m);
     plan.take(d_min, min_dist2_n ? n : 0); plan.take(d_owner, owner_n ? n : 0); plan.take(d_info, 2);
     const size_t total = plan.total();
-    ONECHK(call, hipMalloc(&d.arena, total));
+    ONECHK(call, d.arena.alloc(total));
     plan.place(d.arena);
 
     ONECHK(call, hipMemcpyAsync(d_rec, rec.data(), 16 * n, hipMemcpyHostToDevice, d.stream));

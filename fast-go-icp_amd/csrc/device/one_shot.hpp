@@ -3,7 +3,7 @@
 //   OneShot, ONECHK      what the call owns on the device; a failed HIP call ends it
 //   refuse_*, select_device    the refusals every call shares (they need no device), then the device
 //   write_info                 an extensible info struct back to the caller
-//   Arena                      every device array of the call in one allocation
+//   Arena (arena.hpp)          every device array of the call in one allocation
 //   scan_flags_async, kept_rows, scatter_rows_async   stable compaction by a flag per point: the kept rows in caller order
 // Everything here has internal linkage: each of the five translation units carries its own copy, the kernel included.
 #pragma once
@@ -20,21 +20,18 @@
 
 #include "../../../include/fgoicp_amd.h"
 #include "../host/abi_guard.hpp"
+#include "arena.hpp"
+#include "owned.hpp"
 
 namespace fgoicp {
 namespace {
 
 struct OneShot {  // what the call owns on the device
     const char* name;  // "fgoicp_...": the head of every message
-    hipStream_t stream = nullptr;
-    void* arena = nullptr;
+    Stream stream;  // declared first, released last: the arena goes while the stream still exists
+    Dev<char> arena;
     explicit OneShot(const char* call) : name(call) {}
-    OneShot(const OneShot&) = delete;
-    ~OneShot() {  // (an early return may leave copies into the caller's arrays in flight)
-        if (stream) (void)hipStreamSynchronize(stream);
-        if (arena) (void)hipFree(arena);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
+    ~OneShot() { stream.sync(); }  // before the arena is freed (an early return may leave copies into the caller's arrays in flight)
 };
 
 #define ONECHK(call, expr)                                                                 \
@@ -87,30 +84,6 @@ void write_info(Info* out, Info& full) {
     full.struct_size = out->struct_size < sizeof(full) ? out->struct_size : (uint32_t)sizeof(full);
     std::memcpy(out, &full, full.struct_size);
 }
-
-// The arena: take() names an array once, in the order of the layout; every array starts on a 256-byte boundary.  place(), after the one
-// hipMalloc of total() bytes, sets the pointers; an array of no elements gets nullptr.
-class Arena {
-    struct Item {
-        void* where;
-        void (*set)(void* where, char* p);
-        size_t at;
-        bool empty;
-    };
-    std::vector<Item> items_;
-    size_t total_ = 0;
-
-  public:
-    template <class T>
-    void take(T*& p, size_t count) {
-        items_.push_back({&p, [](void* where, char* at) { *static_cast<T**>(where) = reinterpret_cast<T*>(at); }, total_, count == 0});
-        total_ += (sizeof(T) * count + 255) & ~(size_t)255;
-    }
-    size_t total() const { return total_; }
-    void place(void* arena) const {
-        for (const Item& it : items_) it.set(it.where, it.empty ? nullptr : static_cast<char*>(arena) + it.at);
-    }
-};
 
 // ---- stable compaction: flag[i] != 0 keeps point i; row[i] = the exclusive scan of the flags, the number of kept points before i.
 // Templates on the flag word (deduced; uint32_t at every call), so that a file that compacts nothing — fps.hip, voxel.hip — carries neither

@@ -85,7 +85,7 @@ int remove_outliers_impl(const float* xyz, size_t n, int mode, int k, float para
     const BvhHost tree = bvh_build_host_xyz(xyz, n);
 
     OneShot d(call);
-    ONECHK(call, hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking));
+    ONECHK(call, d.stream.create(hipStreamNonBlocking));
     const uint32_t n32 = (uint32_t)n;
     const uint32_t nrows = (uint32_t)((n + kOutBlock - 1) / kOutBlock);
     size_t scan_bytes = 0;
@@ -102,7 +102,7 @@ int remove_outliers_impl(const float* xyz, size_t n, int mode, int k, float para
     plan.take(d_keep, n); plan.take(d_flag, n); plan.take(d_row, n); plan.take(d_out, 3 * n); plan.take(d_idx, n);
     plan.take(d_rows, nrows); plan.take(d_sum, 1); plan.take(tmp, scan_bytes);
     const size_t total = plan.total();
-    ONECHK(call, hipMalloc(&d.arena, total));
+    ONECHK(call, d.arena.alloc(total));
     plan.place(d.arena);
 
     const dim3 block(kOutBlock), per_point(nrows);

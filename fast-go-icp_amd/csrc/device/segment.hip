@@ -100,7 +100,7 @@ int segment_planes_impl(const float* xyz, size_t n, float distance_threshold, in
     if (const int rc = select_device(call, device)) return rc;
 
     OneShot d(call);
-    ONECHK(call, hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking));
+    ONECHK(call, d.stream.create(hipStreamNonBlocking));
     const uint32_t n32 = (uint32_t)n, K = (uint32_t)iterations;
     const double T = (double)distance_threshold;
     const bool want_rows = out_xyz || kept_index;
@@ -118,7 +118,7 @@ int segment_planes_impl(const float* xyz, size_t n, float distance_threshold, in
     plan.take(d_xyz, 3 * n); plan.take(d_label, n); plan.take(d_flag, n); plan.take(d_row, n); plan.take(d_out, 3 * n); plan.take(d_idx, n);
     plan.take(d_planes, K); plan.take(d_counts, K); plan.take(d_rows, nrows); plan.take(d_sums, 1 + kSegTerms); plan.take(d_ctr, 1); plan.take(tmp, scan_bytes);
     const size_t total = plan.total();
-    ONECHK(call, hipMalloc(&d.arena, total));
+    ONECHK(call, d.arena.alloc(total));
     plan.place(d.arena);
 
     const dim3 block(kSegBlock), per_point(nrows);

@@ -215,7 +215,7 @@ int voxel_downsample_impl(const float* xyz, size_t n, float voxel_size, const fl
     if (const int rc = select_device(call, device)) return rc;
 
     OneShot d(call);
-    ONECHK(call, hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking));
+    ONECHK(call, d.stream.create(hipStreamNonBlocking));
     const uint32_t n32 = (uint32_t)n;
     const size_t max_tiles = n / (kVoxTile / 2) + 1;  // a row of L > kVoxTile points has ceil(L / kVoxTile) < 2 L / kVoxTile tiles
     size_t sort_bytes = 0, scan_bytes = 0;
@@ -231,7 +231,7 @@ int voxel_downsample_impl(const float* xyz, size_t n, float voxel_size, const fl
     plan.take(start, n + 1); plan.take(vop, n); plan.take(counts, n); plan.take(tile_incl, n); plan.take(d_out, 3 * n);
     plan.take(partials, max_tiles); plan.take(d_max, 1); plan.take(tmp, std::max(sort_bytes, scan_bytes));
     const size_t total = plan.total();
-    ONECHK(call, hipMalloc(&d.arena, total));
+    ONECHK(call, d.arena.alloc(total));
     plan.place(d.arena);
     // After the sort the first key buffer is free: its halves hold the head flags and their scan; the first index buffer then holds the
     // tile counts.

@@ -76,39 +76,24 @@ struct TrimSubTick {
     size_t first_row = 0, rows = 0, floats = 0;
 };
 
-// Grow-only device buffer
-template <class T>
-struct DevBuf {
-    T* p = nullptr;
+// Grow-only buffers on the device / in pinned host memory (hipHostMallocDefault: no device alias): the handle (owned.hpp) and the elements it holds
+template <class T> hipError_t alloc_elems(Dev<T>& p, size_t n) { return p.alloc(n); }
+template <class T> hipError_t alloc_elems(Mapped<T>& p, size_t n) { return p.alloc(n, hipHostMallocDefault); }
+template <class Handle>
+struct GrowBuf {
+    Handle p;
     size_t cap = 0;
     int ensure(size_t n, bool exact = false) {
         if (n <= cap) return FGOICP_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr;
         cap = 0;
         const size_t want = exact ? n : n + n / 2 + 64;
-        BCHK(hipMalloc(&p, sizeof(T) * want));
+        BCHK(alloc_elems(p, want));
         cap = want;
         return FGOICP_OK;
     }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
 };
-template <class T>
-struct PinBuf {
-    T* p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t n) {
-        if (n <= cap) return FGOICP_OK;
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
-        const size_t want = n + n / 2 + 64;
-        BCHK(hipHostMalloc((void**)&p, sizeof(T) * want, hipHostMallocDefault));
-        cap = want;
-        return FGOICP_OK;
-    }
-    void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
-};
+template <class T> using DevBuf = GrowBuf<Dev<T>>;
+template <class T> using PinBuf = GrowBuf<Mapped<T>>;
 
 struct HipBatchBackend {
     std::vector<PairHost>* pairs = nullptr;
@@ -117,7 +102,7 @@ struct HipBatchBackend {
     std::vector<fgoicp_ctx*> ctx;
     bool borrowed = false;  // the test hooks: the contexts are the caller's (not destroyed here)
     std::vector<IcpStepRun> icp_state;
-    hipStream_t stream = nullptr;
+    Stream stream;  // (declared ahead of the buffers: released after them)
     uint64_t bounds_launches = 0, icp_launches = 0, selection_launches = 0;
     size_t last_lut_bytes = 0, last_lanes = 4;
     int next_pair = 0;            // the pair the scheduler admits next (room_for_more)
@@ -144,13 +129,10 @@ struct HipBatchBackend {
     ~HipBatchBackend() {
         if (!borrowed)
             for (fgoicp_ctx*& c : ctx) { fgoicp_ctx_destroy(c); c = nullptr; }
-        h_views.release(); h_evals.release(); h_items.release(); h_out.release(); h_trows.release();
-        d_views.release(); d_evals.release(); d_items.release(); d_partials.release(); d_out.release(); d_arena.release(); d_trows.release();
-        if (stream) (void)hipStreamDestroy(stream);
     }
     int init() {
         if (hipSetDevice(device) != hipSuccess) { set_error("fgoicp_batch_run: no usable HIP device (there is no CPU path)"); return FGOICP_ERR_NO_DEVICE; }
-        BCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        BCHK(stream.create(hipStreamNonBlocking));
         ctx.assign(pairs->size(), nullptr);
         icp_state.assign(pairs->size(), IcpStepRun());
         for (const PairHost& p : *pairs)
@@ -169,7 +151,7 @@ struct HipBatchBackend {
         icp_state.assign((size_t)n, IcpStepRun());
         device = n > 0 ? cs[0]->device : 0;
         BCHK(hipSetDevice(device));
-        BCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        BCHK(stream.create(hipStreamNonBlocking));
         return FGOICP_OK;
     }
 
@@ -270,7 +252,7 @@ struct HipBatchBackend {
             const fgoicp_ctx* c = ctx[(size_t)view_pair[v]];
             FusedPairView& pv = h_views.p[v];
             pv.src = c->d_src;
-            pv.lutp = reinterpret_cast<const char*>(c->d_lut_zp);
+            pv.lutp = reinterpret_cast<const char*>(c->d_lut_zp.get());
             pv.g = c->geom;
             pv.ns = (int)c->ns;
             pv.chunk_pts = c->chunk_pts;

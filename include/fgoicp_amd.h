@@ -368,6 +368,10 @@ int fgoicp_ctx_sort_fallbacks(const fgoicp_ctx* ctx, uint64_t* sorted_ticks, uin
 /* TEST HOOK, not part of the drop-in surface: spoils the nth_tick-th sorted tick from now (0 = off) so that the permutation check
  * above has something to find.  (Round 2 read this from the environment of the shipped library) */
 int fgoicp_ctx_test_sort_fault(fgoicp_ctx* ctx, int nth_tick);
+/* TEST HOOK, not part of the drop-in surface: what the library's owning handles hold in this process right now — out4 = {device
+ * allocations, pinned host allocations, streams, events}.  Contexts, batches and the one-shot calls release through those handles, so the
+ * counts return to where they were once an object is destroyed or a call has returned.  Needs no device. */
+int fgoicp_test_live_resources(uint64_t out4[4]);
 
 /* Accumulated HIP-event timing of the bounds kernel since the last reset (FGOICP_FLAG_PROFILE):
  * kernel_ms = sum of launch durations, launches = kernel launches, subcubes = (rot, trans) pairs. */

@@ -117,6 +117,7 @@ def test_invalid_arguments_are_refused_before_any_device_work(fg):
     assert lib.fgoicp_multi_run(None, None, None) == 1 and lib.fgoicp_multi_world(None) == 0 and not lib.fgoicp_multi_solver(None, 0)
     assert lib.fgoicp_multi_recorded(None, 0, None, None) == 1 and lib.fgoicp_multi_set_record(None, 1) == 1 and lib.fgoicp_multi_replay_rank(None, 0, None) == 1 and lib.fgoicp_multi_seconds(None, 0, None) == 1
     assert lib.fgoicp_rccl_comm_count(None, None) == 1 and lib.fgoicp_multi_test_fault(None, 0, 0) == 1 and lib.fgoicp_ctx_test_sort_fault(None, 0) == 1
+    assert lib.fgoicp_test_live_resources(None) == 1
     # the batch test hooks: null arguments, counts and indices out of range, a null context, bad offsets — all before any device work
     one, zero, minus = (C.c_int * 2)(1, 1), (C.c_int * 2)(0, 0), (C.c_int * 2)(-1, -1)
     offs = (C.c_int * 2)(0, 1)
