@@ -1175,7 +1175,7 @@ __global__ __launch_bounds__(kBlock) void nn_first_index_kernel(const float4* __
 
 // ---------------------------------------------------------------------------------------------
 // Exact nearest neighbour by a three-level box scan over the Morton-sorted targets (bvh.hpp):
-// "leaves" of kBvhLeaf = 32 consecutive points, "super-leaves" of 32 leaves (1024 points) and "top boxes" of 32 super-leaves, each
+// "leaves" of kBvhLeaf = 32 consecutive points, "super-leaves" of 64 leaves (2048 points) and "top boxes" of 64 super-leaves (kSuperShift), each
 // with its bounding box (three levels of the implicit tree).  Every query walks the SAME sequence
 //     for each top box:  box test  ->  for each of its super-leaves:  box test  ->  for each of its leaves:  box test  ->  its 32 points
 // so control flow is wave-uniform (a branch is taken when ANY lane needs it) and every box and point
@@ -2287,11 +2287,11 @@ void launch_nn_scan(const float4* pts, int n, const BvhView& t, const float* lut
     // chip is already full (measured: 437k queries 1 -> 4 waves 1.75x faster, 40k queries 4 -> 8 waves +4 %, 16 waves slower).
     int nparts = 4;
     while (nparts < 8 && groups * nparts < 4096) nparts <<= 1;
-    static const int forced = [] { const char* e = dev_env("FGOICP_NN_PARTS"); const int v = e ? std::atoi(e) : 0; return v; }();  // tuning knob
+    const int forced = [] { const char* e = dev_env("FGOICP_NN_PARTS"); return e ? std::atoi(e) : 0; }();  // tuning knob (read per launch, as the two below: a test sets them case by case)
     if (forced == 1 || forced == 2 || forced == 4 || forced == 8 || forced == 16) nparts = forced;
     // candidate leaves claimed dynamically by the waves of a block while the grid does not fill the device (the scan then lasts as long as its
     // slowest block: 40k points, -3 %), dealt round-robin when it does (437k / 1M points: the LDS claims cost 1-2 % and buy nothing)
-    static const int dyn_env = [] { const char* e = dev_env("FGOICP_NN_CLAIM"); return e ? std::atoi(e) : -1; }();  // tuning knob / A-B: 0 / 1 force
+    const int dyn_env = [] { const char* e = dev_env("FGOICP_NN_CLAIM"); return e ? std::atoi(e) : -1; }();  // tuning knob / A-B: 0 / 1 force
     const int dyn = dyn_env >= 0 ? dyn_env : (groups * nparts <= 8192 ? 1 : 0);
     const int flat = [] { const char* e = dev_env("FGOICP_NN_FLAT"); return e ? std::atoi(e) : 0; }();  // tuning knob / A-B (read per launch): 1 = flat form of the walk for targets of <= 2048 leaves (measured slower: off)
     if (want_index) hipLaunchKernelGGL(nn_scan_kernel<1>, dim3(groups), dim3(64 * nparts), 0, s, pts, n, t, lut, g, make_rt(R9, t3), apply, tgt, nt, seed_idx, skip_lb, skip_u, out, writeback, rt_dev, done, wsum, dyn, flat);
@@ -2304,9 +2304,9 @@ void launch_nn_scan_dual(const float4* ptsA, const float* RA9, const float* tA3,
     const int groups = (n + 63) / 64;
     int nparts = 4;
     while (nparts < 8 && groups * nparts < 4096) nparts <<= 1;
-    static const int forced = [] { const char* e = dev_env("FGOICP_NN_PARTS"); const int v = e ? std::atoi(e) : 0; return v; }();  // tuning knob
+    const int forced = [] { const char* e = dev_env("FGOICP_NN_PARTS"); return e ? std::atoi(e) : 0; }();  // tuning knob (read per launch)
     if (forced == 1 || forced == 2 || forced == 4 || forced == 8 || forced == 16) nparts = forced;
-    static const int dyn_env = [] { const char* e = dev_env("FGOICP_NN_CLAIM"); return e ? std::atoi(e) : -1; }();  // tuning knob / A-B
+    const int dyn_env = [] { const char* e = dev_env("FGOICP_NN_CLAIM"); return e ? std::atoi(e) : -1; }();  // tuning knob / A-B
     const int dyn = dyn_env >= 0 ? dyn_env : (groups * nparts <= 8192 ? 1 : 0);
     hipLaunchKernelGGL(nn_scan_dual_kernel, dim3(groups), dim3(64 * nparts), 0, s, ptsA, make_rt(RA9, tA3), applyA, ptsB, make_rt(RB9, tB3), n, t, lut, g, tgt, nt, seed_idx,
                        skip_lbA, skip_uA, skip_lbB, skip_uB, out_idx, out_min, writeback, wsumA, wsumB, dyn);

@@ -7,6 +7,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests.nn_restatement import brute_force
+
 pytestmark = pytest.mark.gpu
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -17,34 +19,6 @@ f32 = np.float32
 
 def _bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-# the fp32 arithmetic of oracle/np_restatement.py, restated here: fma(a, b, c) = float32(float64(a) * float64(b) + float64(c))
-def _fma(a, b, c):
-    return (np.asarray(a, np.float64) * np.asarray(b, np.float64) + np.asarray(c, np.float64)).astype(np.float32)
-
-
-def _moved(R, t, p):
-    """R*p + t as the scans move their queries: fma(R[r,2], z, fma(R[r,1], y, R[r,0]*x)) + t[r]"""
-    R = np.asarray(R, f32); t = np.asarray(t, f32); p = np.asarray(p, f32)
-    q = np.empty_like(p)
-    for r in range(3):
-        q[:, r] = (_fma(R[r, 2], p[:, 2], _fma(R[r, 1], p[:, 1], (R[r, 0] * p[:, 0]).astype(f32))) + t[r]).astype(f32)
-    return q
-
-
-def brute_force(pct, pcs, R, t, chunk=512):
-    """-> (indices, dist2): per source point the FIRST target index attaining the smallest sqrt(d2) in fp32 (kernFindNearestNeighbor's
-    loop, icp3d.cu:20-25) and the smallest squared distance (registration.cu:162-174)"""
-    q = _moved(R, t, pcs)
-    idx = np.empty(len(q), np.uint32)
-    d2min = np.empty(len(q), np.float32)
-    for a in range(0, len(q), chunk):
-        d = (q[a:a + chunk, None, :] - pct[None, :, :]).astype(f32)
-        d2 = _fma(d[..., 2], d[..., 2], _fma(d[..., 1], d[..., 1], (d[..., 0] * d[..., 0]).astype(f32)))
-        d2min[a:a + chunk] = d2.min(axis=1)
-        idx[a:a + chunk] = np.argmin(np.sqrt(d2), axis=1)  # fp32 sqrt is correctly rounded; argmin returns the first minimum
-    return idx, d2min
 
 
 def expected_inliers(dist2, k):

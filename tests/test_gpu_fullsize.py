@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 from oracle import np_restatement as npr
+from tests.nn_restatement import brute_nodes
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -28,17 +29,6 @@ def ang_deg(R, R_gt):
 
 def tnodes(rng, B, span, lim=0.5):
     return np.concatenate([rng.uniform(-lim, lim, (B, 3)), np.full((B, 1), span)], axis=1).astype(f32)
-
-
-def brute_nodes(tgt, bounds, res, xyz):
-    """buildLUTKernel for single nodes (registration.cu:258-278): min_j |node * res - (tgt_j - min_bound)|^2 in fp32."""
-    pts = (tgt + (-np.asarray(bounds, f32)[:, 0])[None, :]).astype(f32)
-    out = np.empty(len(xyz), f32)
-    step = max(1, (1 << 24) // len(pts))
-    for a in range(0, len(xyz), step):
-        nodes = (xyz[a:a + step].astype(f32) * f32(res)).astype(f32)
-        out[a:a + step] = npr.dist_sq(nodes[:, None, :], pts[None, :, :]).min(axis=1)
-    return out
 
 
 def same_result(a, b, rel=1e-5):

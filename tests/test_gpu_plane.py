@@ -17,7 +17,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32, f64 = np.float32, np.float64
 INVALID_ARG = 1
 BOX = (0.156, 0.152, 0.118)
-SIZES = ((2500, 700), (1100, 300))  # three super-leaves of 1024 points, nt no multiple of the 32-point leaf; and a smaller one
+SIZES = ((2500, 700), (1100, 300))  # two super-leaves of 64 leaves = 2048 points (the second holds 15 leaves and 49 empty ones), nt no multiple of the 32-point leaf; and one super-leaf
 _CACHE = {}
 
 
