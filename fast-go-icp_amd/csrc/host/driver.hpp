@@ -413,20 +413,22 @@ public:
     void set_use_cut(bool on) { use_cut_ = on; }
     const DriverStats& stats() const { return stats_; }
 
-    float best_sse() const { std::lock_guard<std::mutex> g(mu_); return best_sse_; }
-    void best_transform(Mat3f& R, Vec3f& t) const { std::lock_guard<std::mutex> g(mu_); R = best_R_; t = best_t_; }
+    // The best registration found so far: {error, rotation, translation}.
+    struct Incumbent {
+        float sse = kHostInf;
+        Mat3f R = Mat3f::identity();
+        Vec3f t{0.f, 0.f, 0.f};
+    };
+    Incumbent incumbent() const { std::lock_guard<std::mutex> g(mu_); return best_; }
+    float best_sse() const { std::lock_guard<std::mutex> g(mu_); return best_.sse; }
+    void best_transform(Mat3f& R, Vec3f& t) const { std::lock_guard<std::mutex> g(mu_); R = best_.R; t = best_.t; }
     void last_transform(Mat3f& R, Vec3f& t) const { std::lock_guard<std::mutex> g(mu_); R = last_R_; t = last_t_; }
 
     // FastGoICP::run(), fgoicp.cpp:10-30 (without restore_translation: the caller owns the offsets)
     int run() {
         const auto t_start = clock::now();
         stats_ = DriverStats{};
-        {
-            std::lock_guard<std::mutex> g(mu_);
-            best_sse_ = kHostInf;
-            best_R_ = Mat3f::identity();
-            best_t_ = Vec3f{0.f, 0.f, 0.f};
-        }
+        set_incumbent(Incumbent{});
         float sse;
         Mat3f R;
         Vec3f t;
@@ -444,12 +446,7 @@ public:
         best_transform(bR, bt);
         rc = icp(bR, bt, 0.0005f, sse, R, t);  // :22-23
         if (rc) return rc;
-        {
-            std::lock_guard<std::mutex> g(mu_);
-            best_sse_ = sse;
-            best_R_ = R;
-            best_t_ = t;
-        }
+        set_incumbent(Incumbent{sse, R, t});
         stats_.seconds_total = seconds_since(t_start);
         if (timing_)
             std::fprintf(stderr, "[fgoicp timing] run %.3f s: pop+pack %.3f s, operator %.3f s, push %.3f s, icp %.3f s, calls %llu\n", stats_.seconds_total, t_pop_, t_ops_,
@@ -496,14 +493,51 @@ private:
         if (ex_.world <= 1 || ex_.allgather_device == nullptr) return false;
         return coop_icp_ < 0 ? ns_ >= coop_min_points_ : coop_icp_ != 0;
     }
-    void set_best_sse_only(float sse) { std::lock_guard<std::mutex> g(mu_); best_sse_ = sse; }
-    void log_new_best() {
-        if (!log_) return;
-        float e; Mat3f R; Vec3f t;
-        { std::lock_guard<std::mutex> g(mu_); e = best_sse_; R = best_R_; t = best_t_; }
-        log_(kLogNewBest, e, R, t);
+    void set_best_sse_only(float sse) { std::lock_guard<std::mutex> g(mu_); best_.sse = sse; }
+    void set_incumbent(const Incumbent& c) { std::lock_guard<std::mutex> g(mu_); best_ = c; }
+    bool adopt_if_better(const Incumbent& c) {
+        std::lock_guard<std::mutex> g(mu_);
+        if (!(c.sse < best_.sse)) return false;
+        best_ = c;
+        return true;
     }
+    void log_new_best(const Incumbent& c) { if (log_) log_(kLogNewBest, c.sse, c.R, c.t); }
     void set_last(const Mat3f& R, const Vec3f& t) { std::lock_guard<std::mutex> g(mu_); last_R_ = R; last_t_ = t; }
+
+    // The trigger rule of fgoicp.cpp:71-88 for one evaluated child: its rotation and the best translation of its UB pass are recorded as
+    // the last transform (:71-72); if its upper bound is below 1.8 x the running best (:74) an ICP refines it (:75-78), a strictly smaller
+    // error is adopted into `run` (:79-84) and the running best is logged, improved or not (:85-87).  `background`: the ICP runs on the
+    // background lane of the operator, on a thread that is not run()'s — the last transform and the log stay with run()'s thread then.
+    // Returns the ICP's status; *improved (optional) says whether `run` changed.
+    static bool triggers(float best_sse, float ub) { return ub < best_sse * 1.8; }  // :74, double compare
+    int trigger(Incumbent& run, const Mat3f& R0, const Vec3f& bt, float ub, bool background, bool* improved = nullptr) {
+        if (improved) *improved = false;
+        if (!background) set_last(R0, bt);
+        if (!triggers(run.sse, ub)) return kDriverOk;
+        Incumbent c;
+        const int rc = icp(R0, bt, 0.005f, c.sse, c.R, c.t, background);
+        if (rc) return rc;
+        if (c.sse < run.sse) {
+            run = c;
+            if (improved) *improved = true;
+        }
+        if (!background) log_new_best(run);
+        return kDriverOk;
+    }
+
+    // The children of a rotation cube in the reference's j order (fgoicp.cpp:51-66): fn(child, evaluate) for every child that overlaps
+    // the ball; evaluate = false: its centre is no rotation, it is pushed back unevaluated (:62-66).
+    template <class F>
+    static void for_each_child(const RotCube& rnode, F&& fn) {
+        const float span = rnode.span / 2.0f;
+        for (char j = 0; j < 8; ++j) {
+            if (span < 0.05f) continue;  // :53
+            RotCube child(rnode.q.x - span + (j >> 0 & 1) * rnode.span, rnode.q.y - span + (j >> 1 & 1) * rnode.span,
+                          rnode.q.z - span + (j >> 2 & 1) * rnode.span, span, rnode.lb, rnode.ub);
+            if (!child.overlaps_SO3()) continue;
+            fn(child, child.q.in_SO3());
+        }
+    }
 
     // -------------------------------------------------------------------------------------------
     // SERIAL: fgoicp.cpp:32-100 verbatim in behaviour — same pops, same pushes, same counters — but not
@@ -533,27 +567,22 @@ private:
     }
     static void spec_make_kids(const RotCube& rnode, SpecNode& sp) {
         sp = SpecNode();
-        const float span = rnode.span / 2.0f;
-        for (char j = 0; j < 8; ++j) {
-            if (span < 0.05f) continue;  // :53
-            RotCube child(rnode.q.x - span + (j >> 0 & 1) * rnode.span, rnode.q.y - span + (j >> 1 & 1) * rnode.span,
-                          rnode.q.z - span + (j >> 2 & 1) * rnode.span, span, rnode.lb, rnode.ub);
-            if (!child.overlaps_SO3()) continue;
+        for_each_child(rnode, [&](const RotCube& child, bool evaluate) {
             sp.kids.push_back(child);
-            sp.kind.push_back(child.q.in_SO3() ? 1 : 0);
-        }
+            sp.kind.push_back(evaluate ? 1 : 0);
+        });
         sp.tk.assign(2 * sp.kids.size(), Task());
         sp.valid.assign(2 * sp.kids.size(), 0);
     }
 
     int bnb_so3_serial() {
-        static const int mode = [] { const char* e = dev_env("FGOICP_SERIAL_SPECULATE"); return e ? std::atoi(e) : 2; }();
+        static const int mode = dev_int("FGOICP_SERIAL_SPECULATE", 2);
         // width cap: 256 nodes per rank (the evaluations of a speculation are dealt over the ranks: the same tick sizes per rank at any world size)
-        static const int spec_cap_env = [] { const char* e = dev_env("FGOICP_SERIAL_WIDTH"); const int v = e ? std::atoi(e) : 0; return v > 0 ? v : 0; }();  // tuning knob
+        static const int spec_cap_env = dev_int("FGOICP_SERIAL_WIDTH", 0, 1);  // tuning knob
         const int spec_cap = spec_cap_env > 0 ? spec_cap_env : 256 * (serial_sharded() ? ex_.world : 1);
         // how the width grows while the incumbent stands and where it restarts when it improves (tuning knobs; the trajectory does not depend on them)
-        static const int spec_grow = [] { const char* e = dev_env("FGOICP_SERIAL_GROW"); const int v = e ? std::atoi(e) : 0; return v >= 2 && v <= 16 ? v : 2; }();
-        static const int spec_start = [] { const char* e = dev_env("FGOICP_SERIAL_START"); const int v = e ? std::atoi(e) : 0; return v >= 1 && v <= 256 ? v : 1; }();
+        static const int spec_grow = dev_int("FGOICP_SERIAL_GROW", 2, 2, 16, 2);
+        static const int spec_start = dev_int("FGOICP_SERIAL_START", 1, 1, 256, 1);
         std::priority_queue<RotCube> rcand;
         rcand.push(RotCube(0.f, 0.f, 0.f, 1.0f, 0.f, best_sse()));
         std::map<SpecKey, SpecNode> cache;
@@ -632,19 +661,18 @@ private:
                 const float ub = sp.tk[2 * k].best_ub;  // :69
                 const Vec3f bt = sp.tk[2 * k].best_t;
                 set_last(child.q.R, bt);  // :71-72
-                if (ub < best_sse() * 1.8) {  // :74, double compare
-                    float sse; Mat3f R; Vec3f t;
-                    int rc = icp(child.q.R, bt, 0.005f, sse, R, t);
+                if (triggers(best_sse(), ub)) {  // :74
+                    Incumbent c;
+                    int rc = icp(child.q.R, bt, 0.005f, c.sse, c.R, c.t);
                     if (rc) return rc;
-                    if (sse < best_sse()) {
-                        { std::lock_guard<std::mutex> g(mu_); best_sse_ = sse; best_R_ = R; best_t_ = t; }
+                    if (adopt_if_better(c)) {
                         ++epoch;  // every uncommitted result saw a stale best_sse: this node's later tasks ...
                         sp.epoch = epoch;
                         for (size_t t2 = 2 * k + 1; t2 < sp.valid.size(); ++t2) sp.valid[t2] = 0;
                         for (auto it = cache.begin(); it != cache.end();)  // ... and every other cached node
                             it = it->second.epoch != epoch ? cache.erase(it) : std::next(it);
                     }
-                    log_new_best();  // :85-87
+                    log_new_best(incumbent());  // :85-87
                 }
                 if (!sp.valid[2 * k + 1]) { int rc = evaluate({&sp}, {2 * k + 1}); if (rc) return rc; }
                 commit(sp.tk[2 * k + 1]);
@@ -725,340 +753,294 @@ private:
     // ROUND: K parents per round, all children's UB+LB inner BnBs concurrently, children sharded
     // over ranks, one all-reduce(min) + one all-gather per round.
     // -------------------------------------------------------------------------------------------
+    // A round is a sequence of phases: pop the round's children, start my tasks, run them, refine (one of three
+    // flows, chosen once per round), exchange, push the survivors.
     int bnb_so3_round() {
         std::priority_queue<RotCube> rcand;
         rcand.push(RotCube(0.f, 0.f, 0.f, 1.0f, 0.f, best_sse()));
-        const int rank = ex_.rank, world = ex_.world < 1 ? 1 : ex_.world;
-        std::vector<RotCube> children;
-        // LATE-JOINING REFINEMENT (FGOICP_LATE_ICP = 1; built in round 3, measured, OFF by default).  On the 8-rank replay it LOSES —
-        // bunny shape 5.55x -> 4.17x, dragon shape 6.12x -> 3.33x (profiles/r03_scale_replay.jsonl): a certify run has 5-8 rounds, the
-        // first of which finds the incumbent; one round of lag means round 2 prunes and triggers against the initial ICP's error
-        // (+20-25 % subcubes, 4-10x the ICP time: `ub < 1.8 best` holds for almost every child while `best` is stale).  The ICP runs a round triggers (fgoicp.cpp:74-88) fall on
-        // the ranks whose children trigger them — one or two single runs of tens of milliseconds per round, on ONE rank, while the
-        // others wait in the exchange (the named serial term of the 8-rank estimate).  With this on, a round's
-        // triggers run in the background (own host thread, own ICP lane and streams of the context) while the rank goes on to the
-        // exchange and to the NEXT round's bounds work; their result enters the exchange one round late.  Price: one round of weaker
-        // pruning (tasks and pushes of round r+1 see the incumbent without round r's refinements).  The replicated state stays
-        // identical on all ranks — refinements enter it only through exchanges, a last exchange after the loop collects the final
-        // round's — and the result is an epsilon-optimal solution as before, reached through a different sequence of incumbents.
-        struct LateJob {
-            std::thread th;
-            std::vector<std::tuple<Mat3f, Vec3f, float>> cands;  // (rotation, best translation, ub) in child order
-            float sse = 0.f; Mat3f R{}; Vec3f t{0, 0, 0};
-            int rc = kDriverOk;
-            bool active = false;
-            ~LateJob() { if (th.joinable()) th.join(); }
-        } late;
-        // folds a finished background job into (loc_sse, loc_R, loc_t)
-        auto join_late = [&](float& ls, Mat3f& lR, Vec3f& lt) -> int {
-            if (!late.active) return kDriverOk;
-            late.th.join();
-            late.active = false;
-            if (late.rc) return late.rc;
-            if (late.sse < ls) { ls = late.sse; lR = late.R; lt = late.t; }
-            return kDriverOk;
-        };
+        LateJob late;
         // round_width 0 = adaptive: start at 32 cubes per rank, double after every round that leaves the incumbent
         // standing (the search is certifying: every cube below the threshold gap has to be expanded anyway, wide rounds
         // waste nothing and feed the device bigger ticks), fall back to the base width when the incumbent improves.
         const bool adaptive = round_width_ <= 0;
-        const int base_width = adaptive ? 32 * world : round_width_;
+        const int base_width = adaptive ? 32 * world() : round_width_;
         int width = base_width;
         while (!rcand.empty()) {
-            const auto t_iter = clock::now();
-            children.clear();
-            int popped = 0;
-            while (popped < width && !rcand.empty()) {
-                if (best_sse() - rcand.top().lb <= sse_threshold_) break;  // :44 (the top is the global min lb)
-                const RotCube rnode = rcand.top();
-                rcand.pop();
-                ++popped;
-                const float span = rnode.span / 2.0f;
-                for (char j = 0; j < 8; ++j) {
-                    if (span < 0.05f) continue;
-                    RotCube child(rnode.q.x - span + (j >> 0 & 1) * rnode.span, rnode.q.y - span + (j >> 1 & 1) * rnode.span,
-                                  rnode.q.z - span + (j >> 2 & 1) * rnode.span, span, rnode.lb, rnode.ub);
-                    if (!child.overlaps_SO3()) continue;
-                    if (!child.q.in_SO3()) { rcand.push(child); continue; }
-                    children.push_back(child);
-                }
-            }
-            if (popped == 0) break;
+            Round r;
+            if (!pop_children(rcand, width, r)) break;
             stats_.rounds++;
-            const size_t nchild = children.size();
-            // Children are dealt in BLOCKS of deal_block_ consecutive children (siblings: `children` holds a parent's children next to each other):
-            // block b goes to rank b % world.  Block 1 = plain round-robin.  Siblings turn the cloud by nearly the same rotation, so their items
-            // land in the same LUT cells of a tick's locality sort — what the one-GPU run gets for free from having every child in one tick.
-            const size_t B = deal_block_, nblocks = (nchild + B - 1) / B;
-            const size_t slots = ((nblocks + world - 1) / world) * B;  // per-rank child slots
-            auto owner_of = [&](size_t i) { return (int)((i / B) % (size_t)world); };
-            auto slot_of = [&](size_t i) { return (i / (B * (size_t)world)) * B + i % B; };
-            const float snapshot = best_sse();
+            start_my_tasks(r);
+            int rc = run_my_tasks(r);
+            if (rc) return rc;
+            if (coop()) {
+                rc = refine_cooperative(r);  // exchanges the children's bounds first, then every rank refines all children together
+            } else {
+                Incumbent loc = incumbent();
+                rc = late_joining() ? refine_late_joining(r, late, loc) : refine_private(r, loc);
+                if (!rc) rc = exchange_round(r, loc);
+            }
+            if (rc) return rc;
+            const float now = best_sse();
+            if (timing_) print_round_timing(r);
+            if (adaptive) width = now < r.snapshot ? base_width : std::min(width * 2, 1 << 14);
+            push_survivors(r, now, rcand);
+        }
+        return late_joining() ? finish_late_joining(late) : kDriverOk;
+    }
 
-            // my children, in child order (slot_of is increasing along it)
-            std::vector<size_t> mine;
+    int world() const { return ex_.world < 1 ? 1 : ex_.world; }
+
+    // Children are dealt in BLOCKS of deal_block_ consecutive children (siblings: `children` holds a parent's children next to each other):
+    // block b goes to rank b % world.  Block 1 = plain round-robin.  Siblings turn the cloud by nearly the same rotation, so their items
+    // land in the same LUT cells of a tick's locality sort — what the one-GPU run gets for free from having every child in one tick.
+    struct Deal {
+        size_t B = 1, world = 1;
+        size_t slots = 0;          // per-rank child slots of the all-gather
+        std::vector<size_t> mine;  // my children, in child order (slot_of is increasing along it)
+        Deal() = default;
+        Deal(size_t nchild, size_t block, int rank, int world_) : B(block), world((size_t)world_) {
+            const size_t nblocks = (nchild + B - 1) / B;
+            slots = ((nblocks + world - 1) / world) * B;
             for (size_t i = 0; i < nchild; ++i)
                 if (owner_of(i) == rank) mine.push_back(i);
-            std::vector<Task> boxes(2 * mine.size());
-            std::vector<Task*> tasks;
-            std::vector<const RotCube*> cubes;
-            for (size_t k = 0; k < mine.size(); ++k) {
-                boxes[2 * k].batch_cap = boxes[2 * k + 1].batch_cap = round_batch_;
-                boxes[2 * k].start(true, snapshot, children[mine[k]].ub);
-                boxes[2 * k + 1].start(false, snapshot, children[mine[k]].ub);
-                tasks.push_back(&boxes[2 * k]); cubes.push_back(&children[mine[k]]);
-                tasks.push_back(&boxes[2 * k + 1]); cubes.push_back(&children[mine[k]]);
-                stats_.inner_bnb += 2;
-                stats_.rot_cubes++;
-            }
-            const auto t_round = clock::now();
-            const uint64_t calls_before = stats_.bounds_calls, cubes_before = stats_.trans_cubes;
-            const double icp_before = stats_.seconds_icp;
-            // OVERLAPPED REFINEMENTS (round 4).  The triggers of a round (fgoicp.cpp:74-88) read nothing but the UB tasks' results — child by child,
-            // against the running best — and the LB tasks of a ROUND round read nothing of the refinements (they prune against the round-start error,
-            // see above).  So the refinements do not have to wait for the LB tasks, which are five times the work: a second host thread applies the
-            // rule in child order as the UB tasks end and runs each triggered ICP on an ICP lane of its own (own scratch and streams) while this
-            // thread keeps ticking the remaining tasks.  Same rule, same order, same inputs: the bits of the sequential flow; the round ends when both
-            // have ended.  (Not to be confused with round 3's late-joining variant, which let the refinements LAG a round and lost.)
-            // MEASURED (profiles/r04_ab_overlap_icp.txt): bit-identical, and no gain — default-threshold bunny step 15.3 -> 15.1 ms, headline 0.351 -> 0.350 s,
-            // trimmed 1M and dragon within noise.  The timing lines say why: with the tail batches the UB tasks of a small round need as many device round trips as
-            // the LB tasks (8 of the round's 8.5 per half), so the first trigger is known 5.4 ms into a 5.7-ms task phase, and in big rounds the refinements are
-            // 3 % of the time.  OFF by default (development knob FGOICP_OVERLAP_ICP=1).
-            struct Overlapped {
-                std::thread th;
-                std::atomic<size_t> ub_ready{0};   // UB tasks of my children [0, ub_ready) have ended
-                std::atomic<bool> stop{false};
-                float sse = 0.f; Mat3f R{}; Vec3f t{0, 0, 0};
-                int rc = kDriverOk;
-                bool active = false;
-                ~Overlapped() { stop.store(true); if (th.joinable()) th.join(); }
-            } ov;
-            const bool overlapped = overlap_icp_ && !coop() && !(late_icp_ > 0 && (world > 1 || late_icp_ > 1)) && !mine.empty();
-            if (overlapped) {
-                { std::lock_guard<std::mutex> g(mu_); ov.sse = best_sse_; ov.R = best_R_; ov.t = best_t_; }
-                ov.active = true;
-                tick_hook_ = [&] {
-                    size_t k = ov.ub_ready.load(std::memory_order_relaxed);
-                    while (k < mine.size() && boxes[2 * k].done) ++k;
-                    ov.ub_ready.store(k, std::memory_order_release);
-                };
-                ov.th = std::thread([&] {
-                    for (size_t k = 0; k < mine.size(); ++k) {
-                        for (unsigned spins = 0; ov.ub_ready.load(std::memory_order_acquire) <= k; ++spins) {
-                            if (ov.stop.load(std::memory_order_acquire)) return;
-                            if (spins < 64) std::this_thread::yield(); else std::this_thread::sleep_for(std::chrono::microseconds(10));
-                        }
-                        const RotCube& ch = children[mine[k]];
-                        const float ub = boxes[2 * k].best_ub;
-                        const Vec3f bt = boxes[2 * k].best_t;
-                        set_last(ch.q.R, bt);
-                        if (timing_ && mine.size() <= 64) std::fprintf(stderr, "[fgoicp timing] overlapped: UB task of child %zu ended %.3f ms into the round (%llu batches)\n", k, seconds_since(t_round) * 1e3, (unsigned long long)boxes[2 * k].batches);
-                        if (ub < ov.sse * 1.8) {  // fgoicp.cpp:74
-                            float sse; Mat3f R; Vec3f t;
-                            const int r = icp(ch.q.R, bt, 0.005f, sse, R, t, true);
-                            if (r) { ov.rc = r; return; }
-                            if (sse < ov.sse) { ov.sse = sse; ov.R = R; ov.t = t; }
-                            if (log_) log_(kLogNewBest, ov.sse, ov.R, ov.t);  // :85-87, this rank's running best
-                        }
-                    }
-                });
-            }
-            // UB TASKS FIRST in a small round (round 4, FGOICP_UB_FIRST, development knob — see the measurement below): a round of a few cubes is a chain of
-            // device round trips, every UB task needs one per level of its translation tree (5-8), and next to the LB tasks a round trip carries five times the
-            // rows.  Run alone, the UB tasks end in a fraction of the task phase; the triggers are then known and the refinements run on the second thread
-            // (above) next to the LB tasks.  The twin / memo sharing between a cube's two tasks is given up for such a round (a few hundred subcubes).
-            // MEASURED (profiles/r04_ab_ub_first.txt): nothing — default-threshold step 15.3 -> 15.3-15.5 ms, headline and trimmed within noise.  A tick of a few
-            // hundred subcubes is not shorter than one of a thousand: its 245 us are the chain of eight dependent launches (upload, keys, fold, scan, scatter, check,
-            // bounds, finalize), so the UB tasks alone still need their 5-8 round trips of that length and the LB tasks theirs AFTER them.
-            const bool ub_first = overlapped && ub_first_max_ > 0 && mine.size() <= ub_first_max_;
-            int rc = kDriverOk;
-            if (ub_first) {
-                std::vector<Task*> ubt, lbt;
-                std::vector<const RotCube*> ubc, lbc;
-                for (size_t k = 0; k < mine.size(); ++k) {
-                    ubt.push_back(tasks[2 * k]); ubc.push_back(cubes[2 * k]);
-                    lbt.push_back(tasks[2 * k + 1]); lbc.push_back(cubes[2 * k + 1]);
-                }
-                tick_hook_ = nullptr;  // (the hook is keyed to the combined task list)
-                rc = run_task_list(ubt, ubc);
-                ov.ub_ready.store(rc ? 0 : mine.size(), std::memory_order_release);
-                if (!rc) rc = run_task_list(lbt, lbc);
-            } else {
-                rc = run_task_list(tasks, cubes);
-            }
-            if (overlapped) {
-                if (!ub_first) tick_hook_();   // every task has ended
-                tick_hook_ = nullptr;
-                if (rc) ov.stop.store(true);
-                ov.th.join();
-                if (!rc) rc = ov.rc;
-            }
-            if (rc) return rc;
-            const double s_tasks = seconds_since(t_round);
-
-            // ICP triggers in child order against the running local best (fgoicp.cpp:74-88), one run after another: a successful run
-            // tightens the trigger of the next child, and after the first success most children no longer qualify.  (Refining every
-            // child that COULD trigger in one concurrent batch — fgoicp_icp_batch — and replaying the rule over the results was
-            // measured and lost: the default-threshold bunny step 38.1 -> 40.5 ms, ICP 17.5 -> 24.3 ms; the batch runs the
-            // candidates the rule would have skipped, and its length is that of its longest run.)
-            float loc_sse; Mat3f loc_R; Vec3f loc_t;
-            { std::lock_guard<std::mutex> g(mu_); loc_sse = best_sse_; loc_R = best_R_; loc_t = best_t_; }
-            std::vector<float> lbs(nchild), ubs(nchild);
-            if (coop()) {
-                // COOPERATIVE ROUND (round 3): the bounds are exchanged FIRST — {lb, ub, best translation} per child, one all-gather —, then
-                // every rank applies the trigger rule to ALL children in the single-GPU child order against the same running best, and
-                // each triggered refinement is one ICP run that all ranks execute together (ctx_icp_coop: every rank scans 1 / world of
-                // the source, results identical on every rank).  No rank waits for another rank's private ICP (the serial term of the
-                // round-2 flow: one 35-40 ms run on one of eight ranks), no candidate needs to be exchanged, and the sequence of
-                // incumbents is the one-rank run's.
-                const size_t per = 5 * slots;
-                std::vector<float> send(per, 0.f), recv(per * world, 0.f);
-                for (size_t k = 0; k < mine.size(); ++k) {
-                    float* p = &send[5 * slot_of(mine[k])];
-                    p[0] = boxes[2 * k + 1].best_ub;  // LB pass: its best_ub is the cube's lower bound (:90)
-                    p[1] = boxes[2 * k].best_ub;      // UB pass
-                    p[2] = boxes[2 * k].best_t.x; p[3] = boxes[2 * k].best_t.y; p[4] = boxes[2 * k].best_t.z;
-                }
-                if (!ex_.allgather) return kDriverExchangeFailed;
-                if (nchild > 0 && ex_.allgather(send.data(), recv.data(), per, ex_.user)) return kDriverExchangeFailed;  // (a round may consist of cubes pushed unevaluated)
-                for (size_t i = 0; i < nchild; ++i) {
-                    const float* p = &recv[per * (size_t)owner_of(i)] + 5 * slot_of(i);
-                    lbs[i] = p[0];
-                    ubs[i] = p[1];
-                    const Vec3f bt{p[2], p[3], p[4]};
-                    set_last(children[i].q.R, bt);
-                    if (ubs[i] < loc_sse * 1.8) {  // fgoicp.cpp:74
-                        float sse; Mat3f R; Vec3f t;
-                        rc = icp(children[i].q.R, bt, 0.005f, sse, R, t);
-                        if (rc) return rc;
-                        if (sse < loc_sse) { loc_sse = sse; loc_R = R; loc_t = t; }
-                        if (log_) log_(kLogNewBest, loc_sse, loc_R, loc_t);  // :85-87, the running best of the round
-                    }
-                }
-                if (loc_sse < best_sse()) { std::lock_guard<std::mutex> g(mu_); best_sse_ = loc_sse; best_R_ = loc_R; best_t_ = loc_t; }
-            } else {
-            if (late_icp_ > 0 && (world > 1 || late_icp_ > 1)) {
-                rc = join_late(loc_sse, loc_R, loc_t);  // the refinements of the round before: they join THIS exchange
-                if (rc) return rc;
-                late.cands.clear();
-                for (size_t k = 0; k < mine.size(); ++k) {
-                    const RotCube& ch = children[mine[k]];
-                    set_last(ch.q.R, boxes[2 * k].best_t);
-                    if (boxes[2 * k].best_ub < loc_sse * 1.8) late.cands.emplace_back(ch.q.R, boxes[2 * k].best_t, boxes[2 * k].best_ub);  // could trigger at all
-                }
-                if (!late.cands.empty()) {
-                    late.sse = loc_sse; late.R = loc_R; late.t = loc_t; late.rc = kDriverOk;
-                    late.active = true;
-                    late.th = std::thread([this, &late] {  // the rule of fgoicp.cpp:74-88, in child order against the job's running best
-                        for (const auto& c : late.cands) {
-                            if (!(std::get<2>(c) < late.sse * 1.8)) continue;
-                            float sse; Mat3f R; Vec3f t;
-                            const int r = icp(std::get<0>(c), std::get<1>(c), 0.005f, sse, R, t, true);
-                            if (r) { late.rc = r; return; }
-                            if (sse < late.sse) { late.sse = sse; late.R = R; late.t = t; }
-                        }
-                    });
-                }
-            } else if (ov.active) {
-                loc_sse = ov.sse; loc_R = ov.R; loc_t = ov.t;  // the refinements ran next to the tasks (above)
-            } else
-            for (size_t k = 0; k < mine.size(); ++k) {
-                const RotCube& ch = children[mine[k]];
-                const float ub = boxes[2 * k].best_ub;
-                const Vec3f bt = boxes[2 * k].best_t;
-                set_last(ch.q.R, bt);
-                if (ub < loc_sse * 1.8) {
-                    float sse; Mat3f R; Vec3f t;
-                    rc = icp(ch.q.R, bt, 0.005f, sse, R, t);
-                    if (rc) return rc;
-                    if (sse < loc_sse) { loc_sse = sse; loc_R = R; loc_t = t; }
-                    if (log_) log_(kLogNewBest, loc_sse, loc_R, loc_t);  // :85-87, this rank's running best
-                }
-            }
-
-            // exchange: best error (min-all-reduce) + {candidate transform, child bounds} (all-gather)
-            if (world > 1) {
-                float gmin = loc_sse;
-                if (!ex_.allreduce_min || !ex_.allgather) return kDriverExchangeFailed;
-                if (ex_.allreduce_min(&gmin, 1, ex_.user)) return kDriverExchangeFailed;
-                const size_t per = 13 + 2 * slots;
-                std::vector<float> send(per, 0.f), recv(per * world, 0.f);
-                send[0] = loc_sse;
-                std::memcpy(&send[1], loc_R.m, sizeof(float) * 9);
-                send[10] = loc_t.x; send[11] = loc_t.y; send[12] = loc_t.z;
-                for (size_t k = 0; k < mine.size(); ++k) {
-                    send[13 + 2 * slot_of(mine[k])] = boxes[2 * k + 1].best_ub;  // LB pass: its best_ub is the cube's lower bound (:90)
-                    send[13 + 2 * slot_of(mine[k]) + 1] = boxes[2 * k].best_ub;  // UB pass
-                }
-                if (ex_.allgather(send.data(), recv.data(), per, ex_.user)) return kDriverExchangeFailed;
-                for (int r = 0; r < world; ++r) {  // lowest rank holding the global minimum wins
-                    const float* p = &recv[per * r];
-                    if (p[0] == gmin && gmin < best_sse()) {
-                        std::lock_guard<std::mutex> g(mu_);
-                        best_sse_ = gmin;
-                        std::memcpy(best_R_.m, p + 1, sizeof(float) * 9);
-                        best_t_ = Vec3f{p[10], p[11], p[12]};
-                        break;
-                    }
-                }
-                for (size_t i = 0; i < nchild; ++i) {
-                    const float* p = &recv[per * (size_t)owner_of(i)] + 13 + 2 * slot_of(i);
-                    lbs[i] = p[0];
-                    ubs[i] = p[1];
-                }
-            } else {
-                if (loc_sse < best_sse()) { std::lock_guard<std::mutex> g(mu_); best_sse_ = loc_sse; best_R_ = loc_R; best_t_ = loc_t; }
-                for (size_t k = 0; k < mine.size(); ++k) {
-                    lbs[mine[k]] = boxes[2 * k + 1].best_ub;
-                    ubs[mine[k]] = boxes[2 * k].best_ub;
-                }
-            }
-            }  // !coop()
-            const float now = best_sse();
-            if (timing_)
-                std::fprintf(stderr, "[fgoicp timing] round %llu: popped %d, children %zu (mine %zu), submissions %llu, subcubes %llu, tasks %.3f ms, icp %.3f ms, round %.3f ms, setup %.3f ms\n",
-                             (unsigned long long)stats_.rounds, popped, nchild, mine.size(), (unsigned long long)(stats_.bounds_calls - calls_before),
-                             (unsigned long long)(stats_.trans_cubes - cubes_before), s_tasks * 1e3, (stats_.seconds_icp - icp_before) * 1e3, seconds_since(t_round) * 1e3,
-                             std::chrono::duration<double>(t_round - t_iter).count() * 1e3);
-            if (adaptive) width = now < snapshot ? base_width : std::min(width * 2, 1 << 14);
-            for (size_t i = 0; i < nchild; ++i) {
-                if (lbs[i] >= now) continue;  // :92
-                children[i].lb = lbs[i];
-                children[i].ub = ubs[i];
-                rcand.push(children[i]);
-            }
         }
-        if (!coop() && late_icp_ > 0 && (world > 1 || late_icp_ > 1)) {
-            // the last round's refinements: joined and agreed on by one more exchange (every rank gets here after the same round —
-            // the loop's decisions depend on the replicated state only)
-            float loc_sse; Mat3f loc_R; Vec3f loc_t;
-            { std::lock_guard<std::mutex> g(mu_); loc_sse = best_sse_; loc_R = best_R_; loc_t = best_t_; }
-            int rc = join_late(loc_sse, loc_R, loc_t);
+        int owner_of(size_t i) const { return (int)((i / B) % world); }
+        size_t slot_of(size_t i) const { return (i / (B * world)) * B + i % B; }
+    };
+
+    // What the phases of one round hand to each other.
+    struct Round {
+        std::vector<RotCube> children;  // the evaluated children of the popped cubes, a parent's children next to each other
+        int popped = 0;
+        Deal deal;
+        float snapshot = 0.f;           // the incumbent's error when the round started: what its tasks prune against
+        std::vector<Task> boxes;        // per child of mine: its UB task [2k] and its LB task [2k+1]
+        std::vector<Task*> tasks;
+        std::vector<const RotCube*> cubes;
+        std::vector<float> lbs, ubs;    // per child, after the exchange: its bounds (:69, :90)
+        // FGOICP_TIMING
+        clock::time_point t_iter = clock::now(), t_round;
+        uint64_t calls_before = 0, cubes_before = 0;
+        double icp_before = 0, s_tasks = 0;
+        const Task& ub_task(size_t k) const { return boxes[2 * k]; }
+        const Task& lb_task(size_t k) const { return boxes[2 * k + 1]; }  // LB pass: its best_ub is the cube's lower bound (:90)
+    };
+
+    // Pops up to `width` cubes and splits them; false when the search is over.
+    bool pop_children(std::priority_queue<RotCube>& rcand, int width, Round& r) {
+        while (r.popped < width && !rcand.empty()) {
+            if (best_sse() - rcand.top().lb <= sse_threshold_) break;  // :44 (the top is the global min lb)
+            const RotCube rnode = rcand.top();
+            rcand.pop();
+            ++r.popped;
+            for_each_child(rnode, [&](const RotCube& child, bool evaluate) {
+                if (evaluate) r.children.push_back(child);
+                else rcand.push(child);
+            });
+        }
+        return r.popped > 0;
+    }
+
+    void start_my_tasks(Round& r) {
+        r.deal = Deal(r.children.size(), deal_block_, ex_.rank, world());
+        r.snapshot = best_sse();
+        const std::vector<size_t>& mine = r.deal.mine;
+        r.boxes.assign(2 * mine.size(), Task());
+        for (size_t k = 0; k < mine.size(); ++k) {
+            r.boxes[2 * k].batch_cap = r.boxes[2 * k + 1].batch_cap = round_batch_;
+            r.boxes[2 * k].start(true, r.snapshot, r.children[mine[k]].ub);
+            r.boxes[2 * k + 1].start(false, r.snapshot, r.children[mine[k]].ub);
+            r.tasks.push_back(&r.boxes[2 * k]); r.cubes.push_back(&r.children[mine[k]]);
+            r.tasks.push_back(&r.boxes[2 * k + 1]); r.cubes.push_back(&r.children[mine[k]]);
+            stats_.inner_bnb += 2;
+            stats_.rot_cubes++;
+        }
+    }
+
+    int run_my_tasks(Round& r) {
+        r.t_round = clock::now();
+        r.calls_before = stats_.bounds_calls;
+        r.cubes_before = stats_.trans_cubes;
+        r.icp_before = stats_.seconds_icp;
+        const int rc = run_task_list(r.tasks, r.cubes);
+        r.s_tasks = seconds_since(r.t_round);
+        return rc;
+    }
+
+    // PRIVATE REFINEMENTS (the default flow below the cooperative size): ICP triggers of my children in child order against the
+    // running local best (fgoicp.cpp:74-88), one run after another: a successful run
+    // tightens the trigger of the next child, and after the first success most children no longer qualify.  (Refining every
+    // child that COULD trigger in one concurrent batch — fgoicp_icp_batch — and replaying the rule over the results was
+    // measured and lost: the default-threshold bunny step 38.1 -> 40.5 ms, ICP 17.5 -> 24.3 ms; the batch runs the
+    // candidates the rule would have skipped, and its length is that of its longest run.)
+    int refine_private(Round& r, Incumbent& loc) {
+        for (size_t k = 0; k < r.deal.mine.size(); ++k) {
+            const int rc = trigger(loc, r.children[r.deal.mine[k]].q.R, r.ub_task(k).best_t, r.ub_task(k).best_ub, false);  // logs this rank's running best
             if (rc) return rc;
-            if (world > 1) {
-                float gmin = loc_sse;
-                if (ex_.allreduce_min(&gmin, 1, ex_.user)) return kDriverExchangeFailed;
-                std::vector<float> send(13, 0.f), recv((size_t)13 * world, 0.f);
-                send[0] = loc_sse;
-                std::memcpy(&send[1], loc_R.m, sizeof(float) * 9);
-                send[10] = loc_t.x; send[11] = loc_t.y; send[12] = loc_t.z;
-                if (ex_.allgather(send.data(), recv.data(), 13, ex_.user)) return kDriverExchangeFailed;
-                for (int r = 0; r < world; ++r) {
-                    const float* p = &recv[(size_t)13 * r];
-                    if (p[0] == gmin && gmin < best_sse()) {
-                        std::lock_guard<std::mutex> g(mu_);
-                        best_sse_ = gmin;
-                        std::memcpy(best_R_.m, p + 1, sizeof(float) * 9);
-                        best_t_ = Vec3f{p[10], p[11], p[12]};
-                        break;
-                    }
-                }
-            } else if (loc_sse < best_sse()) {
-                std::lock_guard<std::mutex> g(mu_);
-                best_sse_ = loc_sse; best_R_ = loc_R; best_t_ = loc_t;
-            }
         }
         return kDriverOk;
+    }
+
+    // COOPERATIVE ROUND (round 3): the bounds are exchanged FIRST — {lb, ub, best translation} per child, one all-gather —, then
+    // every rank applies the trigger rule to ALL children in the single-GPU child order against the same running best, and
+    // each triggered refinement is one ICP run that all ranks execute together (ctx_icp_coop: every rank scans 1 / world of
+    // the source, results identical on every rank).  No rank waits for another rank's private ICP (the serial term of the
+    // round-2 flow: one 35-40 ms run on one of eight ranks), no candidate needs to be exchanged, and the sequence of
+    // incumbents is the one-rank run's.
+    int refine_cooperative(Round& r) {
+        const Deal& d = r.deal;
+        const size_t nchild = r.children.size(), per = 5 * d.slots;
+        std::vector<float> send(per, 0.f), recv(per * world(), 0.f);
+        for (size_t k = 0; k < d.mine.size(); ++k) {
+            float* p = &send[5 * d.slot_of(d.mine[k])];
+            p[0] = r.lb_task(k).best_ub;
+            p[1] = r.ub_task(k).best_ub;
+            p[2] = r.ub_task(k).best_t.x; p[3] = r.ub_task(k).best_t.y; p[4] = r.ub_task(k).best_t.z;
+        }
+        if (!ex_.allgather) return kDriverExchangeFailed;
+        if (nchild > 0 && ex_.allgather(send.data(), recv.data(), per, ex_.user)) return kDriverExchangeFailed;  // (a round may consist of cubes pushed unevaluated)
+        Incumbent loc = incumbent();
+        r.lbs.resize(nchild); r.ubs.resize(nchild);
+        for (size_t i = 0; i < nchild; ++i) {
+            const float* p = &recv[per * (size_t)d.owner_of(i)] + 5 * d.slot_of(i);
+            r.lbs[i] = p[0];
+            r.ubs[i] = p[1];
+            const int rc = trigger(loc, r.children[i].q.R, Vec3f{p[2], p[3], p[4]}, r.ubs[i], false);  // logs the running best of the round
+            if (rc) return rc;
+        }
+        adopt_if_better(loc);
+        return kDriverOk;
+    }
+
+    // LATE-JOINING REFINEMENT (FGOICP_LATE_ICP = 1; built in round 3, measured, OFF by default).  On the 8-rank replay it LOSES —
+    // bunny shape 5.55x -> 4.17x, dragon shape 6.12x -> 3.33x (profiles/r03_scale_replay.jsonl): a certify run has 5-8 rounds, the
+    // first of which finds the incumbent; one round of lag means round 2 prunes and triggers against the initial ICP's error
+    // (+20-25 % subcubes, 4-10x the ICP time: `ub < 1.8 best` holds for almost every child while `best` is stale).  The ICP runs a round triggers (fgoicp.cpp:74-88) fall on
+    // the ranks whose children trigger them — one or two single runs of tens of milliseconds per round, on ONE rank, while the
+    // others wait in the exchange (the named serial term of the 8-rank estimate).  With this on, a round's
+    // triggers run in the background (own host thread, own ICP lane and streams of the context) while the rank goes on to the
+    // exchange and to the NEXT round's bounds work; their result enters the exchange one round late.  Price: one round of weaker
+    // pruning (tasks and pushes of round r+1 see the incumbent without round r's refinements).  The replicated state stays
+    // identical on all ranks — refinements enter it only through exchanges, a last exchange after the loop collects the final
+    // round's — and the result is an epsilon-optimal solution as before, reached through a different sequence of incumbents.
+    struct LateJob {
+        std::thread th;
+        std::vector<std::tuple<Mat3f, Vec3f, float>> cands;  // (rotation, best translation, ub) in child order
+        Incumbent best;  // the job's running best
+        int rc = kDriverOk;
+        bool active = false;
+        ~LateJob() { if (th.joinable()) th.join(); }
+    };
+    bool late_joining() const { return !coop() && late_icp_ > 0 && (world() > 1 || late_icp_ > 1); }
+    // folds a finished background job into loc
+    static int join_late(LateJob& late, Incumbent& loc) {
+        if (!late.active) return kDriverOk;
+        late.th.join();
+        late.active = false;
+        if (late.rc) return late.rc;
+        if (late.best.sse < loc.sse) loc = late.best;
+        return kDriverOk;
+    }
+    int refine_late_joining(Round& r, LateJob& late, Incumbent& loc) {
+        const int rc = join_late(late, loc);  // the refinements of the round before: they join THIS exchange
+        if (rc) return rc;
+        late.cands.clear();
+        for (size_t k = 0; k < r.deal.mine.size(); ++k) {
+            const RotCube& ch = r.children[r.deal.mine[k]];
+            set_last(ch.q.R, r.ub_task(k).best_t);
+            if (triggers(loc.sse, r.ub_task(k).best_ub)) late.cands.emplace_back(ch.q.R, r.ub_task(k).best_t, r.ub_task(k).best_ub);  // could trigger at all
+        }
+        if (late.cands.empty()) return kDriverOk;
+        late.best = loc;
+        late.rc = kDriverOk;
+        late.active = true;
+        late.th = std::thread([this, &late] {  // the rule of fgoicp.cpp:74-88, in child order against the job's running best
+            for (const auto& c : late.cands) {
+                late.rc = trigger(late.best, std::get<0>(c), std::get<1>(c), std::get<2>(c), true);
+                if (late.rc) return;
+            }
+        });
+        return kDriverOk;
+    }
+    // the last round's refinements: joined and agreed on by one more exchange (every rank gets here after the same round —
+    // the loop's decisions depend on the replicated state only)
+    int finish_late_joining(LateJob& late) {
+        Incumbent loc = incumbent();
+        const int rc = join_late(late, loc);
+        if (rc) return rc;
+        std::vector<float> recv;
+        return exchange_incumbent(loc, {}, recv);
+    }
+
+    // The incumbent hand-over: best error (min-all-reduce) + {candidate transform, the caller's payload} (all-gather of 13 + payload
+    // floats per rank); the lowest rank holding the global minimum wins.  `recv` returns what was gathered, for the caller's payload.
+    // One rank: the local best is adopted, nothing is exchanged.
+    static constexpr size_t kIncumbentFloats = 13;  // {sse, R, t}
+    int exchange_incumbent(const Incumbent& loc, const std::vector<float>& payload, std::vector<float>& recv) {
+        if (world() <= 1) { adopt_if_better(loc); return kDriverOk; }
+        float gmin = loc.sse;
+        if (!ex_.allreduce_min || !ex_.allgather) return kDriverExchangeFailed;
+        if (ex_.allreduce_min(&gmin, 1, ex_.user)) return kDriverExchangeFailed;
+        const size_t per = kIncumbentFloats + payload.size();
+        std::vector<float> send(per, 0.f);
+        send[0] = loc.sse;
+        std::memcpy(&send[1], loc.R.m, sizeof(float) * 9);
+        send[10] = loc.t.x; send[11] = loc.t.y; send[12] = loc.t.z;
+        std::copy(payload.begin(), payload.end(), send.begin() + kIncumbentFloats);
+        recv.assign(per * world(), 0.f);
+        if (ex_.allgather(send.data(), recv.data(), per, ex_.user)) return kDriverExchangeFailed;
+        for (int rk = 0; rk < world(); ++rk) {
+            const float* p = &recv[per * rk];
+            if (p[0] != gmin) continue;
+            adopt_if_better(Incumbent{gmin, Mat3f::from(p + 1), Vec3f{p[10], p[11], p[12]}});
+            break;
+        }
+        return kDriverOk;
+    }
+
+    // The round's exchange: the incumbent, with the bounds of my children as payload ({lb, ub} per child slot).
+    int exchange_round(Round& r, const Incumbent& loc) {
+        const Deal& d = r.deal;
+        const size_t nchild = r.children.size();
+        r.lbs.resize(nchild); r.ubs.resize(nchild);
+        if (world() <= 1) {  // every child is mine
+            adopt_if_better(loc);
+            for (size_t k = 0; k < d.mine.size(); ++k) {
+                r.lbs[d.mine[k]] = r.lb_task(k).best_ub;
+                r.ubs[d.mine[k]] = r.ub_task(k).best_ub;
+            }
+            return kDriverOk;
+        }
+        std::vector<float> bounds(2 * d.slots, 0.f), recv;
+        for (size_t k = 0; k < d.mine.size(); ++k) {
+            bounds[2 * d.slot_of(d.mine[k])] = r.lb_task(k).best_ub;
+            bounds[2 * d.slot_of(d.mine[k]) + 1] = r.ub_task(k).best_ub;
+        }
+        const int rc = exchange_incumbent(loc, bounds, recv);
+        if (rc) return rc;
+        const size_t per = kIncumbentFloats + bounds.size();
+        for (size_t i = 0; i < nchild; ++i) {
+            const float* p = &recv[per * (size_t)d.owner_of(i)] + kIncumbentFloats + 2 * d.slot_of(i);
+            r.lbs[i] = p[0];
+            r.ubs[i] = p[1];
+        }
+        return kDriverOk;
+    }
+
+    void print_round_timing(const Round& r) {
+        std::fprintf(stderr, "[fgoicp timing] round %llu: popped %d, children %zu (mine %zu), submissions %llu, subcubes %llu, tasks %.3f ms, icp %.3f ms, round %.3f ms, setup %.3f ms\n",
+                     (unsigned long long)stats_.rounds, r.popped, r.children.size(), r.deal.mine.size(), (unsigned long long)(stats_.bounds_calls - r.calls_before),
+                     (unsigned long long)(stats_.trans_cubes - r.cubes_before), r.s_tasks * 1e3, (stats_.seconds_icp - r.icp_before) * 1e3, seconds_since(r.t_round) * 1e3,
+                     std::chrono::duration<double>(r.t_round - r.t_iter).count() * 1e3);
+    }
+
+    void push_survivors(Round& r, float now, std::priority_queue<RotCube>& rcand) {
+        for (size_t i = 0; i < r.children.size(); ++i) {
+            if (r.lbs[i] >= now) continue;  // :92
+            r.children[i].lb = r.lbs[i];
+            r.children[i].ub = r.ubs[i];
+            rcand.push(r.children[i]);
+        }
     }
 
     // Advance a set of inner tasks in lock-step: every tick submits the current batch of every live
@@ -1090,78 +1072,8 @@ private:
     bool prepare_half(Half& h, std::vector<Task*>& tasks, const std::vector<const RotCube*>& cubes, bool par, bool twins_honoured) {
         const bool memo_on = use_memo_ && use_twins_ && twins_honoured;  // phantom rows cost nothing only where the twin hint is used
         const auto tp0 = clock::now();
-        // ROUND, tail of a round: a few long-running tasks are left and every tick is a latency-bound device round trip that fills a
-        // fraction of the GPU.  Such a half takes bigger batches (the extra nodes are the next-best of the task's own queue: some
-        // would have been pruned by the results of the batch before — paid with idle capacity — and the round ends in fewer ticks).
-        // the fewer tasks a half holds, the more of a tick is round-trip latency and the bigger the batch may be: 128 nodes from 32 tasks
-        // down, 256 from 16, 512 from 8 (measured: default-threshold bunny step 17.3 -> 15.6 ms, the 16 tasks of its one round; certify runs
-        // unchanged; profiles/r03_ab_tail_batch.txt) — for clouds of up to 200 000 points: on the dragon shape every extra node is 437k
-        // point evaluations on a device that is full anyway (512: +2 % subcubes and time).  FGOICP_TAIL_BATCH fixes the size.
-        size_t tail_cap = 0;
-        if (tail_batch_ && h.members.size() <= tail_tasks_) {
-            tail_cap = tail_batch_;
-            if (!tail_batch_fixed_ && ns_ <= 200000) tail_cap = h.members.size() <= tail_tasks_ / 4 ? 512 : h.members.size() <= tail_tasks_ / 2 ? 256 : tail_batch_;
-        }
-        // the same rule made continuous (FGOICP_TICK_ROWS = R > 0): a half's batches are sized so that a tick carries about R rows — batch =
-        // R / live tasks, between ROUND's 48 and 512 — which also reaches the middle of a round on a rank of many (a few hundred tasks per
-        // half: ticks of 4 000 rows at 275 ns per evaluation where the one-GPU run's big ticks cost 207)
-        if (tick_rows_ > 0 && tail_batch_ && !tail_batch_fixed_ && ns_ <= 200000 && !h.members.empty()) {
-            const size_t b = std::min<size_t>(512, tick_rows_ / h.members.size());
-            tail_cap = b > round_batch_ ? b : 0;
-        }
-        const std::function<void(size_t)> pop_fn = [&](size_t k) {
-            Task& tk = *tasks[h.members[k]];
-            if (tk.batch_cap != 32) tk.batch_cap = tail_cap ? tail_cap : round_batch_;  // SERIAL tasks keep the reference's 32 (fgoicp.cpp:122)
-            tk.has_batch = false;
-            tk.phantom.clear();
-            if (tk.done) return;
-            for (;;) {
-                if (!tk.next_batch(sse_threshold_)) { tk.done = true; return; }
-                tk.batches++;
-                if (overlap_stats_)
-                    for (const TransCube& c : tk.batch) tk.seen.push_back(node_key(c));
-                const size_t n = tk.batch.size();
-                tk.brow.resize(n); tk.blb.resize(n); tk.bub.resize(n);
-                tk.nrows = 0;
-                for (size_t q = 0; q < n; ++q) {
-                    if (!tk.memo.empty()) {
-                        if (const auto* hit = tk.memo.find(node_key(tk.batch[q]))) { tk.blb[q] = hit->first; tk.bub[q] = hit->second; tk.brow[q] = -1; continue; }
-                    }
-                    tk.brow[q] = tk.nrows++;
-                }
-                if (tk.nrows > 0) break;
-                tk.consume(tk.blb.data(), tk.bub.data());  // the whole batch came from the memo
-            }
-            tk.has_batch = true;
-            // SERIAL, tail of an evaluation (round 3): a SERIAL task pops the reference's 32 nodes per operator call (fgoicp.cpp:122) — that is part
-            // of the trajectory — so the tail of an evaluation is a long chain of round trips with a few tasks x 32 nodes each (tick log:
-            // 36 % of the kernel time of a SERIAL certify run sits in ticks of 256-1024 evaluations at 350 instead of 217 ns each).
-            // LOOK-AHEAD: the nodes the task pops NEXT if nothing changes — the tops of a COPY of its queue (the real heap is not touched:
-            // re-seating equal keys would change the pop order) — ride along as phantom rows of its own group; their bounds go into the
-            // task's memo, and a later batch that the memo serves entirely is consumed without a device round trip (the mechanism the LB
-            // tasks use for their twins' nodes).  The task's pops, pushes, counters and bounds are what they were: a node's sums do not
-            // depend on the tick it is evaluated in; look-ahead nodes that are never popped are wasted work, not counted.
-            // Measured (profiles/r03_ab_serial_ahead.txt): bunny-shape certify run 450 -> 377 ms (launches 1298 -> 410, evaluations + 5 %), the same run
-            // on 8 ranks 3.5x -> 4.6x; look-ahead up to 512 live tasks per half (480 / 224 / 96 nodes from a quarter / half / all of that down) —
-            // beyond that the wasted evaluations cost more than the round trips saved (2048 tasks: 414 ms), and on the dragon shape, where a node
-            // is 437k point evaluations on a device that is full anyway, 32 tasks is the limit (1.63 -> 1.59 s; 512: 1.78 s).
-            // (clouds below 16 384 points: off — such runs are bound by the host's queue work, not by device round trips: on the shape of
-            // test/bunny.toml, 3 037 source points, the queue copies and memo look-ups add 15 ms of pops to a 100-ms run and save nothing)
-            const size_t ahead_tasks = serial_ahead_tasks_ ? serial_ahead_tasks_ : (ns_ < 16384 ? 0 : ns_ <= 200000 ? 512 : 32);
-            if (serial_ahead_ > 0 && tk.batch_cap == 32 && h.members.size() <= ahead_tasks && !tk.cand.empty()) {
-                const size_t want = h.members.size() <= ahead_tasks / 4 ? 15 * 32 : h.members.size() <= ahead_tasks / 2 ? 7 * 32 : 3 * 32;
-                std::priority_queue<TransCube> peek = tk.cand;
-                for (size_t got = 0; got < std::min(want, (size_t)serial_ahead_) && !peek.empty();) {
-                    const TransCube tn = peek.top();
-                    peek.pop();
-                    if (tk.best_error - tn.lb < sse_threshold_) break;  // the task would stop here (:120)
-                    if (!(tn.lb < tk.best_error)) continue;             // popped and dropped (:126)
-                    if (tk.memo.find(node_key(tn))) continue;
-                    tk.phantom.push_back(tn);
-                    ++got;
-                }
-            }
-        };
+        const size_t tail_cap = tail_batch_cap(h.members.size());
+        const auto pop_fn = [&](size_t k) { pop_batch(*tasks[h.members[k]], h.members.size(), tail_cap); };
         if (par) pool_->parallel_for(h.members.size(), pop_fn);
         else for (size_t k = 0; k < h.members.size(); ++k) pop_fn(k);
         const auto tp1 = clock::now();
@@ -1175,32 +1087,7 @@ private:
             for (size_t a = 0; a + 1 < G; ++a)
                 if ((h.live[a] ^ 1) == h.live[a + 1] && cubes[h.live[a]] == cubes[h.live[a + 1]] && tasks[h.live[a]]->fix_rot && !tasks[h.live[a + 1]]->fix_rot) pairs.push_back(a);
         h.pair_twins.assign(pairs.size(), {});
-        const std::function<void(size_t)> match_fn = [&](size_t q) {
-            Task &ub = *tasks[h.live[pairs[q]]], &lb = *tasks[h.live[pairs[q] + 1]];
-            auto& tw = h.pair_twins[q];
-            const size_t n0 = ub.batch.size(), n1 = lb.batch.size();
-            if (n0 > 512 || n1 > 512) return;  // batches hold <= 512 nodes (32 in the reference, fgoicp.cpp:122); the table below assumes it
-            int table[1024];
-            for (int& x : table) x = -1;
-            for (size_t j = 0; j < n1; ++j) {
-                if (lb.brow[j] < 0) continue;
-                uint32_t sl = (uint32_t)NodeKeyHash()(node_key(lb.batch[j])) & 1023u;
-                while (table[sl] >= 0) sl = (sl + 1) & 1023u;
-                table[sl] = (int)j;
-            }
-            for (size_t i = 0; i < n0; ++i) {
-                if (ub.brow[i] < 0) continue;  // served from the UB task's own memo (look-ahead): no row of this submission to pair with
-                const NodeKey ki = node_key(ub.batch[i]);
-                int hit = -1;
-                for (uint32_t sl = (uint32_t)NodeKeyHash()(ki) & 1023u; table[sl] >= 0; sl = (sl + 1) & 1023u)
-                    if (node_key(lb.batch[(size_t)table[sl]]) == ki) { hit = table[sl]; break; }
-                if (hit >= 0) tw.push_back({ub.brow[i], lb.brow[(size_t)hit]});
-                else if (memo_on && !lb.memo.find(ki)) {
-                    tw.push_back({ub.brow[i], lb.nrows + (int)lb.phantom.size()});
-                    lb.phantom.push_back(ub.batch[i]);
-                }
-            }
-        };
+        const auto match_fn = [&](size_t q) { match_twins(*tasks[h.live[pairs[q]]], *tasks[h.live[pairs[q] + 1]], h.pair_twins[q], memo_on); };
         if (par && pairs.size() >= 64) pool_->parallel_for(pairs.size(), match_fn);
         else for (size_t q = 0; q < pairs.size(); ++q) match_fn(q);
         const auto tp2 = clock::now();
@@ -1210,23 +1097,7 @@ private:
         h.R9.resize(9 * G); h.spans.resize(G); h.fix.resize(G); h.tn4.resize(4 * total);
         h.cut.resize(G);
         h.leaf.assign(G, InnerTask::leaf_below());
-        const std::function<void(size_t)> pack_fn = [&](size_t a) {  // groups are independent: packed in parallel
-            const int i = h.live[a];
-            const Task& tk = *tasks[i];
-            std::memcpy(&h.R9[9 * a], cubes[i]->q.R.m, 9 * sizeof(float));
-            h.spans[a] = cubes[i]->span;
-            h.fix[a] = tk.fix_rot ? 1 : 0;
-            h.cut[a] = tk.cut_above();
-            float* base = &h.tn4[4 * (size_t)h.offsets[a]];
-            for (size_t q = 0; q < tk.batch.size(); ++q) {
-                if (tk.brow[q] < 0) continue;
-                const TransCube& c = tk.batch[q];
-                float* out = base + 4 * (size_t)tk.brow[q];
-                out[0] = c.t.x; out[1] = c.t.y; out[2] = c.t.z; out[3] = c.span;
-            }
-            float* out = base + 4 * (size_t)tk.nrows;
-            for (const TransCube& c : tk.phantom) { out[0] = c.t.x; out[1] = c.t.y; out[2] = c.t.z; out[3] = c.span; out += 4; }
-        };
+        const auto pack_fn = [&](size_t a) { pack_group(h, a, *tasks[h.live[a]], *cubes[h.live[a]]); };  // groups are independent: packed in parallel
         if (par && G >= 256) pool_->parallel_for(G, pack_fn);
         else for (size_t a = 0; a < G; ++a) pack_fn(a);
         h.lb.resize(total);
@@ -1243,6 +1114,125 @@ private:
             t_prep_[2] += std::chrono::duration<double>(tp3 - tp2).count();
         }
         return !h.live.empty();
+    }
+    // ROUND, tail of a round: a few long-running tasks are left and every tick is a latency-bound device round trip that fills a
+    // fraction of the GPU.  Such a half takes bigger batches (the extra nodes are the next-best of the task's own queue: some
+    // would have been pruned by the results of the batch before — paid with idle capacity — and the round ends in fewer ticks).
+    // the fewer tasks a half holds, the more of a tick is round-trip latency and the bigger the batch may be: 128 nodes from 32 tasks
+    // down, 256 from 16, 512 from 8 (measured: default-threshold bunny step 17.3 -> 15.6 ms, the 16 tasks of its one round; certify runs
+    // unchanged; profiles/r03_ab_tail_batch.txt) — for clouds of up to 200 000 points: on the dragon shape every extra node is 437k
+    // point evaluations on a device that is full anyway (512: +2 % subcubes and time).  FGOICP_TAIL_BATCH fixes the size.
+    // Returns the batch size of a half of `members` tasks, 0 = ROUND's own.
+    size_t tail_batch_cap(size_t members) const {
+        size_t tail_cap = 0;
+        if (tail_batch_ && members <= tail_tasks_) {
+            tail_cap = tail_batch_;
+            if (!tail_batch_fixed_ && ns_ <= 200000) tail_cap = members <= tail_tasks_ / 4 ? 512 : members <= tail_tasks_ / 2 ? 256 : tail_batch_;
+        }
+        // the same rule made continuous (FGOICP_TICK_ROWS = R > 0): a half's batches are sized so that a tick carries about R rows — batch =
+        // R / live tasks, between ROUND's 48 and 512 — which also reaches the middle of a round on a rank of many (a few hundred tasks per
+        // half: ticks of 4 000 rows at 275 ns per evaluation where the one-GPU run's big ticks cost 207)
+        if (tick_rows_ > 0 && tail_batch_ && !tail_batch_fixed_ && ns_ <= 200000 && members > 0) {
+            const size_t b = std::min<size_t>(512, tick_rows_ / members);
+            tail_cap = b > round_batch_ ? b : 0;
+        }
+        return tail_cap;
+    }
+    // Pops the next batch of one task of a half of `members` tasks: nodes the task's memo holds are served from it (a batch served
+    // entirely is consumed on the spot), the others get rows of the submission.
+    void pop_batch(Task& tk, size_t members, size_t tail_cap) const {
+        if (tk.batch_cap != 32) tk.batch_cap = tail_cap ? tail_cap : round_batch_;  // SERIAL tasks keep the reference's 32 (fgoicp.cpp:122)
+        tk.has_batch = false;
+        tk.phantom.clear();
+        if (tk.done) return;
+        for (;;) {
+            if (!tk.next_batch(sse_threshold_)) { tk.done = true; return; }
+            tk.batches++;
+            if (overlap_stats_)
+                for (const TransCube& c : tk.batch) tk.seen.push_back(node_key(c));
+            const size_t n = tk.batch.size();
+            tk.brow.resize(n); tk.blb.resize(n); tk.bub.resize(n);
+            tk.nrows = 0;
+            for (size_t q = 0; q < n; ++q) {
+                if (!tk.memo.empty()) {
+                    if (const auto* hit = tk.memo.find(node_key(tk.batch[q]))) { tk.blb[q] = hit->first; tk.bub[q] = hit->second; tk.brow[q] = -1; continue; }
+                }
+                tk.brow[q] = tk.nrows++;
+            }
+            if (tk.nrows > 0) break;
+            tk.consume(tk.blb.data(), tk.bub.data());  // the whole batch came from the memo
+        }
+        tk.has_batch = true;
+        // SERIAL, tail of an evaluation (round 3): a SERIAL task pops the reference's 32 nodes per operator call (fgoicp.cpp:122) — that is part
+        // of the trajectory — so the tail of an evaluation is a long chain of round trips with a few tasks x 32 nodes each (tick log:
+        // 36 % of the kernel time of a SERIAL certify run sits in ticks of 256-1024 evaluations at 350 instead of 217 ns each).
+        // LOOK-AHEAD: the nodes the task pops NEXT if nothing changes — the tops of a COPY of its queue (the real heap is not touched:
+        // re-seating equal keys would change the pop order) — ride along as phantom rows of its own group; their bounds go into the
+        // task's memo, and a later batch that the memo serves entirely is consumed without a device round trip (the mechanism the LB
+        // tasks use for their twins' nodes).  The task's pops, pushes, counters and bounds are what they were: a node's sums do not
+        // depend on the tick it is evaluated in; look-ahead nodes that are never popped are wasted work, not counted.
+        // Measured (profiles/r03_ab_serial_ahead.txt): bunny-shape certify run 450 -> 377 ms (launches 1298 -> 410, evaluations + 5 %), the same run
+        // on 8 ranks 3.5x -> 4.6x; look-ahead up to 512 live tasks per half (480 / 224 / 96 nodes from a quarter / half / all of that down) —
+        // beyond that the wasted evaluations cost more than the round trips saved (2048 tasks: 414 ms), and on the dragon shape, where a node
+        // is 437k point evaluations on a device that is full anyway, 32 tasks is the limit (1.63 -> 1.59 s; 512: 1.78 s).
+        // (clouds below 16 384 points: off — such runs are bound by the host's queue work, not by device round trips: on the shape of
+        // test/bunny.toml, 3 037 source points, the queue copies and memo look-ups add 15 ms of pops to a 100-ms run and save nothing)
+        const size_t ahead_tasks = serial_ahead_tasks_ ? serial_ahead_tasks_ : (ns_ < 16384 ? 0 : ns_ <= 200000 ? 512 : 32);
+        if (serial_ahead_ > 0 && tk.batch_cap == 32 && members <= ahead_tasks && !tk.cand.empty()) {
+            const size_t want = members <= ahead_tasks / 4 ? 15 * 32 : members <= ahead_tasks / 2 ? 7 * 32 : 3 * 32;
+            std::priority_queue<TransCube> peek = tk.cand;
+            for (size_t got = 0; got < std::min(want, (size_t)serial_ahead_) && !peek.empty();) {
+                const TransCube tn = peek.top();
+                peek.pop();
+                if (tk.best_error - tn.lb < sse_threshold_) break;  // the task would stop here (:120)
+                if (!(tn.lb < tk.best_error)) continue;             // popped and dropped (:126)
+                if (tk.memo.find(node_key(tn))) continue;
+                tk.phantom.push_back(tn);
+                ++got;
+            }
+        }
+    }
+    // The twins of one (UB task, LB task) pair: {row in the UB group, row in the LB group} of every node both hold in this submission,
+    // and (memo on) a phantom row in the LB group for every other node of the UB batch.
+    static void match_twins(Task& ub, Task& lb, std::vector<std::pair<int, int>>& tw, bool memo_on) {
+        const size_t n0 = ub.batch.size(), n1 = lb.batch.size();
+        if (n0 > 512 || n1 > 512) return;  // batches hold <= 512 nodes (32 in the reference, fgoicp.cpp:122); the table below assumes it
+        int table[1024];
+        for (int& x : table) x = -1;
+        for (size_t j = 0; j < n1; ++j) {
+            if (lb.brow[j] < 0) continue;
+            uint32_t sl = (uint32_t)NodeKeyHash()(node_key(lb.batch[j])) & 1023u;
+            while (table[sl] >= 0) sl = (sl + 1) & 1023u;
+            table[sl] = (int)j;
+        }
+        for (size_t i = 0; i < n0; ++i) {
+            if (ub.brow[i] < 0) continue;  // served from the UB task's own memo (look-ahead): no row of this submission to pair with
+            const NodeKey ki = node_key(ub.batch[i]);
+            int hit = -1;
+            for (uint32_t sl = (uint32_t)NodeKeyHash()(ki) & 1023u; table[sl] >= 0; sl = (sl + 1) & 1023u)
+                if (node_key(lb.batch[(size_t)table[sl]]) == ki) { hit = table[sl]; break; }
+            if (hit >= 0) tw.push_back({ub.brow[i], lb.brow[(size_t)hit]});
+            else if (memo_on && !lb.memo.find(ki)) {
+                tw.push_back({ub.brow[i], lb.nrows + (int)lb.phantom.size()});
+                lb.phantom.push_back(ub.batch[i]);
+            }
+        }
+    }
+    // Packs group `a` of the submission: the task's rotation cube, its thresholds, the rows of its batch and its phantom rows.
+    static void pack_group(Half& h, size_t a, const Task& tk, const RotCube& cube) {
+        std::memcpy(&h.R9[9 * a], cube.q.R.m, 9 * sizeof(float));
+        h.spans[a] = cube.span;
+        h.fix[a] = tk.fix_rot ? 1 : 0;
+        h.cut[a] = tk.cut_above();
+        float* base = &h.tn4[4 * (size_t)h.offsets[a]];
+        for (size_t q = 0; q < tk.batch.size(); ++q) {
+            if (tk.brow[q] < 0) continue;
+            const TransCube& c = tk.batch[q];
+            float* out = base + 4 * (size_t)tk.brow[q];
+            out[0] = c.t.x; out[1] = c.t.y; out[2] = c.t.z; out[3] = c.span;
+        }
+        float* out = base + 4 * (size_t)tk.nrows;
+        for (const TransCube& c : tk.phantom) { out[0] = c.t.x; out[1] = c.t.y; out[2] = c.t.z; out[3] = c.span; out += 4; }
     }
     // Tasks finish at very different times (an UB task may need 5 batches, its neighbour 50): when the idle half `from`
     // holds many more unfinished tasks than the other, it hands over the surplus so that both slots stay busy and the
@@ -1345,7 +1335,6 @@ private:
                     const auto tc = clock::now();
                     rebalance(h[k], h[1 - k]);
                     const bool more = !h[k].members.empty() && prepare_half(h[k], tasks, cubes, par, ops_.twins());
-                    if (tick_hook_) tick_hook_();  // (tasks that have just ended are marked done by now)
                     if (more) {
                         int rc = submit_half(k, h[k]);
                         if (rc) return rc;
@@ -1366,7 +1355,6 @@ private:
         for (;;) {
             const auto ta = clock::now();
             const bool more = prepare_half(h, tasks, cubes, par, false);
-            if (tick_hook_) tick_hook_();
             if (!more) return kDriverOk;
             const auto tb = clock::now();
             int rc = ops_.bounds_multi((int)h.live.size(), h.R9.data(), h.spans.data(), h.fix.data(), h.offsets.data(), h.tn4.data(), h.lb.data(), h.ub.data(), use_cut_ ? h.cut.data() : nullptr);
@@ -1388,24 +1376,21 @@ private:
     const bool serial_shard_ = [] { const char* e = dev_env("FGOICP_SERIAL_SHARD"); return !e || std::atoi(e) != 0; }();  // tuning knob / A-B: 0 = SERIAL on N ranks runs replicated
     const int coop_icp_ = [] { const char* e = dev_env("FGOICP_COOP_ICP"); return e ? (std::atoi(e) != 0 ? 1 : 0) : -1; }();  // tuning knob / A-B: 0 = every rank refines its own children alone, 1 = cooperative rounds, unset = by size
     const size_t coop_min_points_ = [] { const char* e = dev_env("FGOICP_COOP_MIN_POINTS"); return e ? (size_t)std::max(0L, std::atol(e)) : (size_t)131072; }();  // tuning knob
-    const int late_icp_ = [] { const char* e = dev_env("FGOICP_LATE_ICP"); return e ? std::atoi(e) : 0; }();  // tuning knob (ROUND): 0 = off (default: measured slower, see above), 1 = with an exchange (world > 1), 2 = always
+    const int late_icp_ = dev_int("FGOICP_LATE_ICP", 0);  // tuning knob (ROUND): 0 = off (default: measured slower, see above), 1 = with an exchange (world > 1), 2 = always
     bool use_cut_ = true;   // hand every task's cut_above() to the operator (set_use_cut: the A/B and the exact-rows mode of the tests)
     bool use_twins_ = [] { const char* e = dev_env("FGOICP_TWINS"); return !e || std::atoi(e) != 0; }();  // tuning knob
-    const size_t round_batch_ = [] { const char* e = dev_env("FGOICP_ROUND_BATCH"); const int v = e ? std::atoi(e) : 48; return (size_t)(v >= 8 && v <= 64 ? v : 48); }();  // tuning knob (ROUND only; SERIAL keeps the reference's 32)
-    const int serial_ahead_ = [] { const char* e = dev_env("FGOICP_SERIAL_AHEAD"); return e ? std::max(0, std::atoi(e)) : 480; }();  // tuning knob: look-ahead nodes of a SERIAL task in the tail of an evaluation (0 = off)
-    const size_t serial_ahead_tasks_ = [] { const char* e = dev_env("FGOICP_SERIAL_AHEAD_TASKS"); const int v = e ? std::atoi(e) : 0; return (size_t)(v > 0 ? v : 0); }();  // ... while its half holds at most this many tasks (0 = by cloud size: 512 / 32)
-    const size_t tick_rows_ = [] { const char* e = dev_env("FGOICP_TICK_ROWS"); const int v = e ? std::atoi(e) : 0; return (size_t)(v > 0 ? v : 0); }();  // tuning knob (ROUND): rows a tick should carry (0 = the stepwise tail rule)
-    const size_t deal_block_ = [] { const char* e = dev_env("FGOICP_DEAL_BLOCK"); const int v = e ? std::atoi(e) : 0; return (size_t)(v >= 1 && v <= 64 ? v : 1); }();  // tuning knob (ROUND on N ranks): consecutive children dealt to one rank
+    const size_t round_batch_ = (size_t)dev_int("FGOICP_ROUND_BATCH", 48, 8, 64, 48);  // tuning knob (ROUND only; SERIAL keeps the reference's 32)
+    const int serial_ahead_ = dev_int("FGOICP_SERIAL_AHEAD", 480, 0);  // tuning knob: look-ahead nodes of a SERIAL task in the tail of an evaluation (0 = off)
+    const size_t serial_ahead_tasks_ = (size_t)dev_int("FGOICP_SERIAL_AHEAD_TASKS", 0, 1);  // ... while its half holds at most this many tasks (0 = by cloud size: 512 / 32)
+    const size_t tick_rows_ = (size_t)dev_int("FGOICP_TICK_ROWS", 0, 1);  // tuning knob (ROUND): rows a tick should carry (0 = the stepwise tail rule)
+    const size_t deal_block_ = (size_t)dev_int("FGOICP_DEAL_BLOCK", 1, 1, 64, 1);  // tuning knob (ROUND on N ranks): consecutive children dealt to one rank
     const bool tail_batch_fixed_ = dev_env("FGOICP_TAIL_BATCH") != nullptr;
-    const size_t tail_batch_ = [] { const char* e = dev_env("FGOICP_TAIL_BATCH"); const int v = e ? std::atoi(e) : 128; return (size_t)(v >= 8 && v <= 512 ? v : 0); }();  // tuning knob (ROUND): batch of a half with few tasks left (0 = off)
-    const size_t tail_tasks_ = [] { const char* e = dev_env("FGOICP_TAIL_TASKS"); const int v = e ? std::atoi(e) : 32; return (size_t)(v >= 0 ? v : 32); }();  // ... "few" = at most this many
+    const size_t tail_batch_ = (size_t)dev_int("FGOICP_TAIL_BATCH", 128, 8, 512, 0);  // tuning knob (ROUND): batch of a half with few tasks left (0 = off)
+    const size_t tail_tasks_ = (size_t)dev_int("FGOICP_TAIL_TASKS", 32, 0, INT_MAX, 32);  // ... "few" = at most this many
     bool use_memo_ = [] { const char* e = dev_env("FGOICP_MEMO"); return !e || std::atoi(e) != 0; }();    // tuning knob: memo of the twin task's evaluations
     const bool overlap_stats_ = dev_env("FGOICP_OVERLAP_STATS") != nullptr;  // diagnostic: how many nodes both tasks of a rotation cube evaluate
     uint64_t ov_ub_ = 0, ov_lb_ = 0, ov_both_ = 0;
     bool account_submissions_ = true;   // false while SERIAL speculates: work is accounted per committed task instead
-    std::function<void()> tick_hook_;   // called by the task loop's thread after every batch preparation (ROUND: the overlapped refinements watch the UB tasks end)
-    const size_t ub_first_max_ = [] { const char* e = dev_env("FGOICP_UB_FIRST"); const int v = e ? std::atoi(e) : 0; return (size_t)(v > 0 ? v : 0); }();  // development knob: rounds of at most this many children run their UB tasks first (needs FGOICP_OVERLAP_ICP=1)
-    const bool overlap_icp_ = [] { const char* e = dev_env("FGOICP_OVERLAP_ICP"); return e && std::atoi(e) != 0; }();  // development knob: 1 = a round's refinements next to its tasks (measured: no gain, see bnb_so3_round)
     std::unique_ptr<WorkerPool> pool_;
     float sse_threshold_;
     size_t ns_;
@@ -1414,9 +1399,9 @@ private:
     std::function<void(int, float, const Mat3f&, const Vec3f&)> log_;
     DriverStats stats_;
     mutable std::mutex mu_;
-    float best_sse_ = kHostInf;
-    Mat3f best_R_ = Mat3f::identity(), last_R_ = Mat3f::identity();
-    Vec3f best_t_{0.f, 0.f, 0.f}, last_t_{0.f, 0.f, 0.f};
+    Incumbent best_;
+    Mat3f last_R_ = Mat3f::identity();
+    Vec3f last_t_{0.f, 0.f, 0.f};
 };
 
 }  // namespace fgoicp

@@ -30,7 +30,13 @@ def launch(tmp_path, case, K, world, late="0", coop="0", extra_env=None):
            "--master-port", str(free_port()), os.path.join(REPO, "tests", "dist_worker.py"), prefix, case, str(K)]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
-    return [np.load(f"{prefix}.rank{r}.npz") for r in range(world)]
+    ranks = [np.load(f"{prefix}.rank{r}.npz") for r in range(world)]
+    # the driver is deterministic on the CPU: every rank's counters, exchanges and result bits are the recorded ones
+    from tests import trajectory_record
+    knobs = "".join(f"/{k}={v}" for k, v in sorted((extra_env or {}).items()) if k.startswith("FGOICP_"))
+    for r, z in enumerate(ranks):
+        trajectory_record.check(f"dist/{case}K{K}/world{world}/late{late}/coop{coop}{knobs}/rank{r}", z, z["R"], z["t"], z["sse"], z["exchange_calls"])
+    return ranks
 
 
 @pytest.mark.parametrize("case,K", [("runsyn_", 1), ("runbun_", 2), ("runsyn_", 0)])

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from tests import host_harness as hh
+from tests import trajectory_record
 
 G = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "goicp_golden.npz"))
 f32 = np.float32
@@ -106,6 +107,7 @@ def test_round_schedule_reaches_the_same_optimum(pre, K, sched):
     assert np.allclose(r["R"], G[pre + "R"], atol=1e-5) and np.allclose(r["t"], G[pre + "t"], atol=1e-5 * max(1.0, float(np.abs(G[pre + "t"]).max())))
     if sched == 1:
         assert r["stats"]["bounds_calls"] < G[pre + "stats"][1]  # batches of many tasks share one submission
+    trajectory_record.check_run(f"round/{pre}K{K}/sched{sched}", r)
 
 
 def test_pipelined_and_synchronous_task_loops_are_equivalent(monkeypatch):
@@ -120,6 +122,8 @@ def test_pipelined_and_synchronous_task_loops_are_equivalent(monkeypatch):
         assert a["stats"][k] == b["stats"][k], k
     # two balanced halves: at most two submissions where the synchronous loop needs one
     assert a["stats"]["bounds_calls"] <= b["stats"]["bounds_calls"] <= 2 * a["stats"]["bounds_calls"]
+    trajectory_record.check_run("loops/runbun_K4/tail0/sched1", a)
+    trajectory_record.check_run("loops/runbun_K4/tail0/sched2", b)
     # With the tail batches ON (ROUND's default) a task's batch size depends on the company it keeps, so the two modes may differ — but
     # only inside the threshold the inner BnB stops on (fgoicp.cpp:120): the same epsilon-optimal answer, not the same bits.
     monkeypatch.delenv("FGOICP_TAIL_BATCH")
@@ -127,6 +131,8 @@ def test_pipelined_and_synchronous_task_loops_are_equivalent(monkeypatch):
     b = hh.HostDriver(G[pre + "tgt"], G[pre + "src"], float(G[pre + "res"]), float(G[pre + "mse"]), schedule=2, round_width=4).run()
     eps = float(G[pre + "mse"]) * len(G[pre + "src"])
     assert abs(float(a["best_sse"]) - float(b["best_sse"])) <= eps + 2e-3 * float(a["best_sse"])
+    trajectory_record.check_run("loops/runbun_K4/tail/sched1", a)
+    trajectory_record.check_run("loops/runbun_K4/tail/sched2", b)
 
 
 def test_twin_task_memo_changes_nothing_a_task_can_see():
