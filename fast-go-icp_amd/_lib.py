@@ -113,6 +113,30 @@ class PlaneResult(C.Structure):
         self.struct_size = C.sizeof(PlaneResult)  # the library writes no byte beyond it
 
 
+class RobustMoments(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("points", C.c_uint64), ("correspondences", C.c_uint64), ("m", C.c_double * 28), ("weight_sum", C.c_double),
+                ("max_dist2", C.c_float), ("loss", C.c_int), ("scale", C.c_double)]
+
+    def __init__(self):
+        super().__init__()
+        self.struct_size = C.sizeof(RobustMoments)  # the library writes no byte beyond it
+
+
+class RobustResult(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("R", C.c_float * 9), ("t", C.c_float * 3), ("iterations", C.c_int), ("rank", C.c_int), ("correspondences", C.c_uint64),
+                ("weight_sum", C.c_double), ("rmse", C.c_double), ("sse", C.c_float), ("scaling_factor", C.c_float), ("loss", C.c_int), ("scale_estimated", C.c_int),
+                ("scale", C.c_double)]
+
+    def __init__(self):
+        super().__init__()
+        self.struct_size = C.sizeof(RobustResult)  # the library writes no byte beyond it
+
+
+LOSS_NONE, LOSS_HUBER, LOSS_CAUCHY, LOSS_GEMAN_MCCLURE, LOSS_TUKEY = range(5)
+LOSSES = {"none": LOSS_NONE, "huber": LOSS_HUBER, "cauchy": LOSS_CAUCHY, "geman_mcclure": LOSS_GEMAN_MCCLURE, "tukey": LOSS_TUKEY}
+MODEL_PLANE, MODEL_GICP = 0, 1
+
+
 class VoxelInfo(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("points", C.c_uint64), ("voxels", C.c_uint64), ("max_points_per_voxel", C.c_uint64), ("origin", C.c_float * 3),
                 ("voxel_size", C.c_float)]
@@ -234,6 +258,13 @@ _SIGS = {
     "fgoicp_icp_gicp": (C.c_int, [C.c_void_p, c_float_p, c_float_p, C.c_size_t, C.c_float, C.c_float, C.c_double, C.POINTER(PlaneResult)]),
     "fgoicp_solver_refine_gicp": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.c_float, C.c_float, C.c_double, C.POINTER(PlaneResult)]),
     "fgoicp_gicp_terms": (C.c_int, [c_float_p, c_float_p, c_float_p, c_float_p, c_float_p, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "fgoicp_robust_weight": (C.c_int, [C.c_int, C.c_double, C.c_double, C.POINTER(C.c_double)]),
+    "fgoicp_robust_moments": (C.c_int, [C.c_void_p, c_float_p, c_float_p, C.c_float, C.c_int, C.c_double, C.c_int, C.c_double, C.POINTER(RobustMoments)]),
+    "fgoicp_robust_residuals": (C.c_int, [C.c_void_p, c_float_p, c_float_p, C.c_float, C.c_int, C.c_double, C.c_int, C.c_double, C.POINTER(C.c_double),
+                                          C.POINTER(C.c_double), c_uint8_p]),
+    "fgoicp_robust_scale": (C.c_int, [C.c_void_p, c_float_p, c_float_p, C.c_float, C.c_int, C.c_double, C.POINTER(C.c_double)]),
+    "fgoicp_icp_robust": (C.c_int, [C.c_void_p, c_float_p, c_float_p, C.c_size_t, C.c_float, C.c_float, C.c_int, C.c_double, C.c_int, C.c_double, C.POINTER(RobustResult)]),
+    "fgoicp_solver_refine_robust": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_float, C.c_float, C.c_double, C.c_int, C.c_double, C.POINTER(RobustResult)]),
     "fgoicp_icp": (C.c_int, [C.c_void_p, c_float_p, c_float_p, C.c_size_t, C.c_float, c_float_p, c_float_p, c_float_p, c_int_p]),
     "fgoicp_icp_batch": (C.c_int, [C.c_void_p, C.c_int, c_float_p, c_float_p, C.c_size_t, C.c_float, c_float_p, c_float_p, c_float_p, c_int_p]),
     "fgoicp_procrustes": (C.c_int, [C.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p, c_int_p]),

@@ -125,6 +125,14 @@ struct Config {
         int refine_max_iter = 30;
         float refine_distance = 0.0f;  // ... distance threshold in the files' units (absent or 0: none)
         double refine_epsilon = 1e-3;  // ... "gicp" only: the smallest eigenvalue of the regularised covariances, in (0, 1]
+        std::string refine_loss = "none";  // EXTENSION: the robust loss of the refinement (fgoicp_solver_refine_robust): "none", "huber", "cauchy", "geman_mcclure", "tukey"; anything else, or a loss without params.refine, is refused
+        double refine_loss_scale = 0.0;    // ... its scale in the files' units; absent or <= 0: estimated at the best transform
+        int refine_loss_code() const {     // FGOICP_LOSS_*
+            static const char* const names[] = {"none", "huber", "cauchy", "geman_mcclure", "tukey"};
+            for (int k = 0; k < 5; ++k)
+                if (refine_loss == names[k]) return k;
+            return -1;
+        }
         float target_voxel = 0.0f, source_voxel = 0.0f;  // EXTENSION: voxel size in the files' units; the cloud is replaced by its voxel grid's centroids (fgoicp_voxel_downsample) after loading; absent or <= 0: off, NaN is refused
         // EXTENSION: outlier removal per cloud after the voxel grid (fgoicp_remove_outliers).  *_outlier_knn: the neighbours, absent or <= 0: off;
         // *_outlier_std: the statistical filter's std ratio; *_outlier_radius (the files' units) > 0: the radius filter in place of the statistical one.
@@ -208,6 +216,12 @@ struct Config {
                 throw std::invalid_argument("params.refine = \"" + params.refine + "\" is not supported: the refinements are \"plane\" and \"gicp\"");
             if (!params.refine.empty() && (params.refine_knn < 4 || params.refine_knn > 32)) throw std::invalid_argument("params.refine_knn must lie in [4, 32]");
             if (params.refine == "gicp" && !(params.refine_epsilon > 0.0 && params.refine_epsilon <= 1.0)) throw std::invalid_argument("params.refine_epsilon must lie in (0, 1]");
+            params.refine_loss = str("params", "refine_loss", "none");
+            params.refine_loss_scale = num("params", "refine_loss_scale", 0.0);
+            if (!(params.refine_loss_scale > 0.0) || !std::isfinite(params.refine_loss_scale)) params.refine_loss_scale = 0.0;
+            if (params.refine_loss_code() < 0)
+                throw std::invalid_argument("params.refine_loss = \"" + params.refine_loss + "\" is not supported: the losses are \"none\", \"huber\", \"cauchy\", \"geman_mcclure\" and \"tukey\"");
+            if (params.refine_loss_code() > 0 && params.refine.empty()) throw std::invalid_argument("params.refine_loss needs params.refine (\"plane\" or \"gicp\")");
             params.target_voxel = (float)num("params", "target_voxel", 0.0);
             params.source_voxel = (float)num("params", "source_voxel", 0.0);
             if (std::isnan(params.target_voxel) || std::isnan(params.source_voxel)) throw std::invalid_argument("params.target_voxel and params.source_voxel must not be NaN");
@@ -423,9 +437,11 @@ inline size_t load_cloud(const std::string& filepath, float subsample, std::vect
 
 // io.output / io.visualization (declared by test/bunny.toml:10-11, unimplemented upstream)
 // refined (optional, EXTENSION: params.refine): a [refined] table behind the existing keys, which stay as they are; rmse_key names its
-// residual — plane_rmse for "plane", gicp_rmse for "gicp"
+// residual — plane_rmse for "plane", gicp_rmse for "gicp".  robust (optional, EXTENSION: params.refine_loss): loss, loss_scale (the files'
+// units) and weight_sum behind the table's keys
 inline void write_result_toml(const std::string& path, const icp::mat3& R, const icp::vec3& t, float sse, size_t ns, double seconds,
-                              const fgoicp_run_stats& st, const fgoicp_plane_result_t* refined = nullptr, const char* rmse_key = "plane_rmse") {
+                              const fgoicp_run_stats& st, const fgoicp_plane_result_t* refined = nullptr, const char* rmse_key = "plane_rmse",
+                              const fgoicp_robust_result_t* robust = nullptr, const char* loss_name = "") {
     std::ofstream f(path);
     if (!f) throw std::runtime_error("Unable to write " + path);
     f.precision(9);
@@ -443,6 +459,8 @@ inline void write_result_toml(const std::string& path, const icp::mat3& R, const
     f << "]\ntranslation = [" << refined->t[0] << ", " << refined->t[1] << ", " << refined->t[2] << "]\n";
     f << rmse_key << " = " << refined->plane_rmse / (double)refined->scaling_factor << "\niterations = " << refined->iterations << "\nrank = " << refined->rank
       << "\ncorrespondences = " << refined->correspondences << "\n";
+    if (!robust) return;
+    f << "loss = \"" << loss_name << "\"\nloss_scale = " << robust->scale / (double)robust->scaling_factor << "\nweight_sum = " << robust->weight_sum << "\n";
 }
 
 // io.alignment (EXTENSION): the alignment report of the run (fgoicp_solver_alignment / fgoicp_batch_alignment).  Two '#' lines — the summary,

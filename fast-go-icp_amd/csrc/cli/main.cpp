@@ -7,6 +7,7 @@
 #include <cstring>
 #include <filesystem>
 #include <fstream>
+#include <sstream>
 #include <string>
 #include <vector>
 
@@ -353,10 +354,38 @@ int main(int argc, char* argv[]) {
     fgoicp_plane_result_t refined{};
     bool have_refined = false;
     const bool gicp = config.params.refine == "gicp";
+    // params.refine_loss: the same refinement under a robust loss (fgoicp_solver_refine_robust); its pose and counts go into `refined`
+    fgoicp_robust_result_t robust{};
+    const int loss = config.params.refine_loss_code();
+    bool have_robust = false;
     auto refine = [&](fgoicp_solver* s) {
         if (config.params.refine != "plane" && !gicp) return;
         refined.struct_size = sizeof(refined);
         const float d = config.params.refine_distance;
+        if (loss > 0) {
+            robust.struct_size = sizeof(robust);
+            icp::check_status(fgoicp_solver_refine_robust(s, gicp ? FGOICP_MODEL_GICP : FGOICP_MODEL_PLANE, config.params.refine_knn, (size_t)config.params.refine_max_iter,
+                                                          1e-6f, d > 0.0f ? d : INFINITY, config.params.refine_epsilon, loss, config.params.refine_loss_scale, &robust),
+                              "fgoicp_solver_refine_robust");
+            std::memcpy(refined.R, robust.R, sizeof(refined.R));
+            std::memcpy(refined.t, robust.t, sizeof(refined.t));
+            refined.iterations = robust.iterations; refined.rank = robust.rank; refined.correspondences = robust.correspondences;
+            refined.plane_rmse = robust.rmse; refined.sse = robust.sse; refined.scaling_factor = robust.scaling_factor;
+            have_refined = have_robust = true;
+            icp::mat3 Rr;
+            std::memcpy(Rr.data(), refined.R, sizeof(refined.R));
+            std::ostringstream head;
+            if (gicp)
+                head << "Generalized-ICP refinement: " << refined.iterations << " iterations, rank " << refined.rank << ", " << refined.correspondences
+                     << " correspondences, epsilon " << config.params.refine_epsilon << ", plane-to-plane RMSE " << refined.plane_rmse / (double)refined.scaling_factor;
+            else
+                head << "Point-to-plane refinement: " << refined.iterations << " iterations, rank " << refined.rank << ", " << refined.correspondences
+                     << " correspondences, plane RMSE " << refined.plane_rmse / (double)refined.scaling_factor;
+            icp::Logger(icp::LogLevel::Info) << head.str() << ", " << config.params.refine_loss << " loss, scale " << robust.scale / (double)robust.scaling_factor
+                                             << (robust.scale_estimated ? " (estimated)" : " (given)") << ", weight " << robust.weight_sum << " of " << robust.correspondences
+                                             << "\n\tRotation:\n" << Rr << "\n\tTranslation: " << icp::vec3{refined.t[0], refined.t[1], refined.t[2]};
+            return;
+        }
         if (gicp) {
             icp::check_status(fgoicp_solver_refine_gicp(s, config.params.refine_knn, (size_t)config.params.refine_max_iter, 1e-6f, d > 0.0f ? d : INFINITY,
                                                         config.params.refine_epsilon, &refined), "fgoicp_solver_refine_gicp");
@@ -454,7 +483,8 @@ int main(int argc, char* argv[]) {
     }
     icp::Logger(icp::LogLevel::Debug) << "Subcubes: " << st.trans_cubes << ", rotation cubes: " << st.rot_cubes << ", ICP runs: " << st.icp_runs;
     icp::Logger(icp::LogLevel::Info) << "Fast Go-ICP finished, time elapsed: " << std::fixed << std::setprecision(3) << elapsed_seconds.count() << " seconds";
-    if (!config.io.output.empty()) cli::write_result_toml(config.io.output, R, t, best_error, pcs_in.size(), elapsed_seconds.count(), st, have_refined ? &refined : nullptr, gicp ? "gicp_rmse" : "plane_rmse");
+    if (!config.io.output.empty()) cli::write_result_toml(config.io.output, R, t, best_error, pcs_in.size(), elapsed_seconds.count(), st, have_refined ? &refined : nullptr, gicp ? "gicp_rmse" : "plane_rmse",
+                                                              have_robust ? &robust : nullptr, config.params.refine_loss.c_str());
     if (!config.io.visualization.empty()) cli::write_visualization_ply(config.io.visualization, pct_in, pcs_in, R, t);
     return 0;
 }

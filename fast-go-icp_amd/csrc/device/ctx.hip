@@ -804,6 +804,109 @@ int ctx_icp_gicp(fgoicp_ctx* c, const float* R0, const float* t0, size_t max_ite
                         R0, t0, max_iter, thr, full);
 }
 
+// EXTENSION: robust losses (fgoicp_robust_*, fgoicp_icp_robust).  moments_at with launch_robust_moments in place of
+// the plain launch, over rows and an output of its own; the per-point outputs are stored by the kernel only when a caller asks.
+int robust_refusals(const fgoicp_ctx* c, const RobustSpec& r, bool need_scale, const char* where) {
+    const std::string w(where);
+    if (!(r.max_dist2 >= 0.0f)) { set_error(w + ": max_dist2 must be >= 0 (+inf: no threshold)"); return FGOICP_ERR_INVALID_ARG; }
+    if (!robust_model_ok(r.model)) { set_error(w + ": unknown model " + std::to_string(r.model) + " (0: point-to-plane, 1: Generalized ICP)"); return FGOICP_ERR_INVALID_ARG; }
+    if (!robust_loss_ok(r.loss)) { set_error(w + ": unknown loss " + std::to_string(r.loss)); return FGOICP_ERR_INVALID_ARG; }
+    if (r.model == FGOICP_MODEL_GICP && !gicp_epsilon_ok(r.epsilon)) { set_error(w + ": epsilon must be finite and lie in (0, 1]"); return FGOICP_ERR_INVALID_ARG; }
+    if (need_scale && r.loss != FGOICP_LOSS_NONE && !robust_scale_ok(r.scale)) { set_error(w + ": the scale must be finite and > 0"); return FGOICP_ERR_INVALID_ARG; }
+    if (!c->normals_set) { set_error(w + ": the target normals are not set: call fgoicp_ctx_set_target_normals first"); return FGOICP_ERR_INVALID_ARG; }
+    if (r.model == FGOICP_MODEL_GICP && !c->src_normals_set) { set_error(w + ": the source normals are not set: call fgoicp_ctx_set_source_normals first"); return FGOICP_ERR_INVALID_ARG; }
+    return FGOICP_OK;
+}
+int ctx_robust_moments(fgoicp_ctx* c, const float* R9, const float* t3, const RobustSpec& r, RobustMoments* m, float* sse_out, double* residual, double* weight,
+                       unsigned char* counted) {
+    const bool per_point = residual || weight || counted;
+    const size_t ns = c->ns;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(c->d_robust_rows.ensure((ns + kBlock - 1) / kBlock));
+    HIPCHK(c->d_robust_out.ensure(1 + kRobustTerms));
+    if (per_point) {
+        HIPCHK(c->d_robust_point.ensure(2 * ns));
+        HIPCHK(c->d_robust_counted.ensure(ns));
+    }
+    const int rc = alignment_enqueue(c, R9, t3, true);
+    if (rc) return rc;
+    fgoicp_ctx::IcpLane& L = c->lanes[0];
+    fgoicp_ctx::AlignScratch& A = c->align;
+    double* const d_res = per_point ? (double*)c->d_robust_point : nullptr;
+    launch_robust_moments(r.model == FGOICP_MODEL_GICP, L.d_work, c->d_orig_of_slot, A.d_inl, A.d_d2, A.d_corr, c->d_tgt, c->d_normals, c->d_src_normals, R9, r.epsilon, r.loss,
+                          r.loss == FGOICP_LOSS_NONE ? 1.0 : r.scale, (int)ns, (int)c->nt, r.max_dist2, c->d_robust_rows, c->d_robust_out, d_res, per_point ? d_res + ns : nullptr,
+                          per_point ? (unsigned char*)c->d_robust_counted : nullptr, L.stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(L.stream));
+    unsigned long long h[1 + kRobustTerms];
+    HIPCHK(hipMemcpy(h, c->d_robust_out, sizeof(h), hipMemcpyDeviceToHost));
+    static_assert(kRobustTerms == kRobustMoments && kRobustTerms == kPlaneMoments + 1, "the device's row and the host's moments are the same 29 terms");
+    m->n = h[0];
+    std::memcpy(m->m, h + 1, sizeof(m->m));
+    if (residual) HIPCHK(hipMemcpy(residual, d_res, sizeof(double) * ns, hipMemcpyDeviceToHost));
+    if (weight) HIPCHK(hipMemcpy(weight, d_res + ns, sizeof(double) * ns, hipMemcpyDeviceToHost));
+    if (counted) HIPCHK(hipMemcpy(counted, c->d_robust_counted, ns, hipMemcpyDeviceToHost));
+    if (sse_out) *sse_out = sse_result(c, L);
+    return FGOICP_OK;
+}
+int ctx_robust_scale(fgoicp_ctx* c, const float* R9, const float* t3, const RobustSpec& r, double* scale, const char* where) {
+    RobustSpec plain = r;
+    plain.loss = FGOICP_LOSS_NONE;
+    std::vector<double> res(c->ns);
+    std::vector<unsigned char> cnt(c->ns);
+    RobustMoments m;
+    const int rc = ctx_robust_moments(c, R9, t3, plain, &m, nullptr, res.data(), nullptr, cnt.data());
+    if (rc) return rc;
+    double s = 0.0;
+    if (!robust_mad_scale(res.data(), cnt.data(), c->ns, &s)) { set_error(std::string(where) + ": nothing is counted at this pose, there is no scale to estimate: pass a scale"); return FGOICP_ERR_INVALID_ARG; }
+    if (!robust_scale_ok(s)) { set_error(std::string(where) + ": the median residual is 0, there is no scale to estimate: pass a scale"); return FGOICP_ERR_INVALID_ARG; }
+    *scale = s;
+    return FGOICP_OK;
+}
+// moments_loop, term for term, over ctx_robust_moments: a weight sum of 0 ends it like a count of 0
+int ctx_icp_robust(fgoicp_ctx* c, const float* R0, const float* t0, size_t max_iter, float thr, RobustSpec r, fgoicp_robust_result_t* full, const char* where) {
+    int estimated = 0;
+    if (r.loss != FGOICP_LOSS_NONE && !(r.scale > 0.0)) {
+        const int rc = ctx_robust_scale(c, R0, t0, r, &r.scale, where);
+        if (rc) return rc;
+        estimated = 1;
+    }
+    Mat3f R = Mat3f::from(R0);
+    Vec3f t{t0[0], t0[1], t0[2]};
+    RobustMoments m;
+    float sse = 0.f;
+    int iters = 0, rank = 0;
+    bool stop = false;
+    for (;;) {
+        const float t3[3] = {t.x, t.y, t.z};
+        const int rc = ctx_robust_moments(c, R.m, t3, r, &m, &sse);
+        if (rc) return rc;
+        if (stop || (size_t)iters >= max_iter || m.n == 0 || m.m[28] == 0.0) break;
+        if (!plane_moments_finite(m.m) || !std::isfinite(m.m[28])) { set_error(std::string(where) + ": the normal equations are not finite"); return FGOICP_ERR_INVALID_ARG; }
+        double xi[6];
+        plane_step(m.m, xi, &rank);
+        plane_apply_step(R, t, xi, R, t);
+        ++iters;
+        const double step = std::sqrt(xi[0] * xi[0] + xi[1] * xi[1] + xi[2] * xi[2]) + std::sqrt(xi[3] * xi[3] + xi[4] * xi[4] + xi[5] * xi[5]);
+        stop = step < (double)thr || (iters == 1 && rank < 6);  // one more evaluation, at the pose returned, then out
+    }
+    std::memset(full, 0, sizeof(*full));  // the padding too: two results of the same inputs are the same bytes
+    full->struct_size = (uint32_t)sizeof(*full);
+    std::memcpy(full->R, R.m, sizeof(R.m));
+    full->t[0] = t.x; full->t[1] = t.y; full->t[2] = t.z;
+    full->iterations = iters;
+    full->rank = rank;
+    full->correspondences = m.n;
+    full->weight_sum = m.m[28];
+    full->rmse = m.m[28] > 0.0 ? std::sqrt(m.m[27] / m.m[28]) : 0.0;
+    full->sse = sse;
+    full->scaling_factor = 1.0f;
+    full->loss = r.loss;
+    full->scale_estimated = estimated;
+    full->scale = r.loss == FGOICP_LOSS_NONE ? 0.0 : r.scale;
+    return FGOICP_OK;
+}
+
 // EXTENSION: source normals (fgoicp_ctx_set_source_normals), kept in device slot order for gicp_moments_kernel.  Given: checked and
 // normalised on the host (fp64) as the target's, permuted, uploaded.  Estimated: the rule of the target's normals over the source itself —
 // a caller-order float4 copy of the source as the context holds it, a throw-away tree over it (bvh_build_host), one launch of
@@ -2040,6 +2143,72 @@ int fgoicp_icp_gicp(fgoicp_ctx* c, const float* R0_9, const float* t0_3, size_t 
         fgoicp_plane_result_t full;
         rc = ctx_icp_gicp(c, R0_9, t0_3, max_iter, conv_thr, max_dist2, epsilon, &full);
         return rc ? rc : plane_out(full, out, "fgoicp_icp_gicp", "fgoicp_plane_result_t");
+    });
+}
+
+// a robust call's arguments as one value; a scale that does not matter (FGOICP_LOSS_NONE) is carried as given
+static RobustSpec robust_spec(float max_dist2, int model, double epsilon, int loss, double scale) {
+    RobustSpec r;
+    r.model = model; r.epsilon = epsilon; r.loss = loss; r.scale = scale; r.max_dist2 = max_dist2;
+    return r;
+}
+int fgoicp_robust_moments(fgoicp_ctx* c, const float* R9, const float* t3, float max_dist2, int model, double epsilon, int loss, double scale,
+                          fgoicp_robust_moments_t* out) {
+    if (!c || !R9 || !t3) { set_error("fgoicp_robust_moments: the context, R and t must not be null"); return FGOICP_ERR_INVALID_ARG; }
+    if (!plane_size_ok(out)) { set_error("fgoicp_robust_moments: out must not be null and out->struct_size = sizeof(fgoicp_robust_moments_t)"); return FGOICP_ERR_INVALID_ARG; }
+    return fgoicp::abi_guard("fgoicp_robust_moments", [&] {
+        const RobustSpec r = robust_spec(max_dist2, model, epsilon, loss, scale);
+        int rc = robust_refusals(c, r, true, "fgoicp_robust_moments");
+        if (rc) return rc;
+        RobustMoments m;
+        rc = ctx_robust_moments(c, R9, t3, r, &m);
+        if (rc) return rc;
+        fgoicp_robust_moments_t full;
+        std::memset(&full, 0, sizeof(full));  // the padding too: two results of the same inputs are the same bytes
+        full.struct_size = (uint32_t)sizeof(full);
+        full.points = c->ns;
+        full.correspondences = m.n;
+        std::memcpy(full.m, m.m, sizeof(full.m));
+        full.weight_sum = m.m[28];
+        full.max_dist2 = max_dist2;
+        full.loss = loss;
+        full.scale = scale;
+        return plane_out(full, out, "fgoicp_robust_moments", "fgoicp_robust_moments_t");
+    });
+}
+int fgoicp_robust_residuals(fgoicp_ctx* c, const float* R9, const float* t3, float max_dist2, int model, double epsilon, int loss, double scale,
+                            double* residual_ns, double* weight_ns, unsigned char* counted_ns) {
+    if (!c || !R9 || !t3) { set_error("fgoicp_robust_residuals: the context, R and t must not be null"); return FGOICP_ERR_INVALID_ARG; }
+    return fgoicp::abi_guard("fgoicp_robust_residuals", [&] {
+        const RobustSpec r = robust_spec(max_dist2, model, epsilon, loss, scale);
+        const int rc = robust_refusals(c, r, true, "fgoicp_robust_residuals");
+        if (rc) return rc;
+        RobustMoments m;
+        std::vector<unsigned char> cnt;  // the kernel stores all three or none
+        if (!residual_ns && !weight_ns && !counted_ns) cnt.resize(c->ns);
+        return ctx_robust_moments(c, R9, t3, r, &m, nullptr, residual_ns, weight_ns, cnt.empty() ? counted_ns : cnt.data());
+    });
+}
+int fgoicp_robust_scale(fgoicp_ctx* c, const float* R9, const float* t3, float max_dist2, int model, double epsilon, double* scale) {
+    if (!c || !R9 || !t3 || !scale) { set_error("fgoicp_robust_scale: the context, R, t and scale must not be null"); return FGOICP_ERR_INVALID_ARG; }
+    return fgoicp::abi_guard("fgoicp_robust_scale", [&] {
+        const RobustSpec r = robust_spec(max_dist2, model, epsilon, FGOICP_LOSS_NONE, 0.0);
+        const int rc = robust_refusals(c, r, false, "fgoicp_robust_scale");
+        return rc ? rc : ctx_robust_scale(c, R9, t3, r, scale, "fgoicp_robust_scale");
+    });
+}
+int fgoicp_icp_robust(fgoicp_ctx* c, const float* R0_9, const float* t0_3, size_t max_iter, float conv_thr, float max_dist2, int model, double epsilon, int loss,
+                      double scale, fgoicp_robust_result_t* out) {
+    if (!c || !R0_9 || !t0_3) { set_error("fgoicp_icp_robust: the context, R0 and t0 must not be null"); return FGOICP_ERR_INVALID_ARG; }
+    if (!plane_size_ok(out)) { set_error("fgoicp_icp_robust: out must not be null and out->struct_size = sizeof(fgoicp_robust_result_t)"); return FGOICP_ERR_INVALID_ARG; }
+    return fgoicp::abi_guard("fgoicp_icp_robust", [&] {
+        const RobustSpec r = robust_spec(max_dist2, model, epsilon, loss, scale);
+        if (scale != scale || std::isinf(scale)) { set_error("fgoicp_icp_robust: the scale must be finite (<= 0: estimated)"); return (int)FGOICP_ERR_INVALID_ARG; }
+        int rc = robust_refusals(c, r, false, "fgoicp_icp_robust");
+        if (rc) return rc;
+        fgoicp_robust_result_t full;
+        rc = ctx_icp_robust(c, R0_9, t0_3, max_iter, conv_thr, r, &full, "fgoicp_icp_robust");
+        return rc ? rc : plane_out(full, out, "fgoicp_icp_robust", "fgoicp_robust_result_t");
     });
 }
 

@@ -17,6 +17,7 @@
 #include "../host/information.hpp"
 #include "../host/plane.hpp"
 #include "../host/gicp.hpp"
+#include "../host/robust.hpp"
 #include "bvh.hpp"
 #include "kernels.hpp"
 #include "owned.hpp"
@@ -141,6 +142,12 @@ struct fgoicp_ctx {
     // source normals of the Generalized-ICP refinement (ctx_set_source_normals): allocated by the first call, 16 bytes per source point
     fgoicp::Dev<float4> d_src_normals;               // ns x {n.x, n.y, n.z, 0}, DEVICE SLOT order (perm); the zero vector: no normal
     bool src_normals_set = false;
+    // the robustly weighted normal equations (ctx_robust_moments): rows and output of their own, allocated by the first call — 240 bytes per
+    // block of kBlock source points; the per-point outputs (fgoicp_robust_residuals, the scale) by the first call that asks: 17 bytes per source point
+    fgoicp::Dev<fgoicp::MomentRow<fgoicp::kRobustTerms>> d_robust_rows;
+    fgoicp::Dev<unsigned long long> d_robust_out;        // {count, the bits of 29 sums} (launch_robust_moments)
+    fgoicp::Dev<double> d_robust_point;                  // ns residuals, then ns weights, caller order
+    fgoicp::Dev<unsigned char> d_robust_counted;         // ns flags, caller order
 
     // exact-NN / ICP scratch, one set per lane: ICP runs on different lanes may be in flight together (ctx_icp_batch).  Lane 0 is
     // the lane of fgoicp_sse / fgoicp_icp / fgoicp_procrustes and queues on the context's main stream.
@@ -232,6 +239,24 @@ int ctx_source_normals(fgoicp_ctx* c, float* out_ns3);
 int ctx_gicp_moments(fgoicp_ctx* c, const float* R9, const float* t3, float max_dist2, double epsilon, PlaneMoments* m, float* sse_out = nullptr);
 // fgoicp_icp_gicp: ctx_icp_plane's loop over ctx_gicp_moments; full->plane_rmse = sqrt(sum d^T M d / N)
 int ctx_icp_gicp(fgoicp_ctx* c, const float* R0, const float* t0, size_t max_iter, float thr, float max_dist2, double epsilon, fgoicp_plane_result_t* full);
+// EXTENSION: robust losses over either model (include/fgoicp_amd.h).  What one evaluation takes: checked by robust_refusals first.
+struct RobustSpec {
+    int model = FGOICP_MODEL_PLANE;
+    double epsilon = 1e-3;  // FGOICP_MODEL_GICP only
+    int loss = FGOICP_LOSS_NONE;
+    double scale = 0.0;
+    float max_dist2 = 0.f;
+};
+// what every robust call refuses before any device work: max_dist2, the model, its normals, epsilon (GICP), the loss and, need_scale, the scale
+int robust_refusals(const fgoicp_ctx* c, const RobustSpec& r, bool need_scale, const char* where);
+// one evaluation on lane 0, as ctx_plane_moments / ctx_gicp_moments.  residual / weight / counted (each optional, ns entries, caller
+// order): the per-point outputs, read back behind the evaluation.
+int ctx_robust_moments(fgoicp_ctx* c, const float* R9, const float* t3, const RobustSpec& r, RobustMoments* m, float* sse_out = nullptr, double* residual = nullptr,
+                       double* weight = nullptr, unsigned char* counted = nullptr);
+// fgoicp_robust_scale: one evaluation with the per-point outputs, the median on the host
+int ctx_robust_scale(fgoicp_ctx* c, const float* R9, const float* t3, const RobustSpec& r, double* scale, const char* where);
+// fgoicp_icp_robust; r.scale <= 0: estimated at (R0, t0).  `full` is filled whole (scaling_factor = 1)
+int ctx_icp_robust(fgoicp_ctx* c, const float* R0, const float* t0, size_t max_iter, float thr, RobustSpec r, fgoicp_robust_result_t* full, const char* where);
 // a summary handed to a caller: no byte beyond the struct_size the caller set is written (0, or less than the size field itself: refused)
 inline int alignment_summary_out(const fgoicp_alignment_summary& full, fgoicp_alignment_summary* out, const char* where) {
     if (!out) return FGOICP_OK;

@@ -20,6 +20,7 @@
 #include "bvh.hpp"
 #include "../host/math3.hpp"
 #include "../host/gicp.hpp"
+#include "../host/robust.hpp"
 
 namespace fgoicp {
 namespace {
@@ -2901,6 +2902,85 @@ void launch_gicp_moments(const float4* moved, const uint32_t* orig_of_slot, cons
     hipLaunchKernelGGL(gicp_moments_kernel, dim3(nb), dim3(kBlock), 0, s, moved, orig_of_slot, inlier, d2, corr, tgt, normals, src_normals, make_rt(R9, nullptr), eps, n, nt,
                        max_d2, rows);
     hipLaunchKernelGGL(moment_fold_kernel<kPlaneTerms>, dim3(1), dim3(1024), 0, s, rows, nb, out29);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The robustly weighted normal equations (fgoicp_robust_moments, fgoicp_robust_residuals).  One thread per device
+// slot i over the arrays of the two kernels above.  GICP = false: plane_moments_kernel's counted set and its 28 terms, operation for
+// operation, s = r.  GICP = true: gicp_moments_kernel's counted set, gicp_pair_terms, s = sqrt(max(d^T M d, 0)).  Then w = robust_weight(loss,
+// s, c) (host/robust.hpp, the text fgoicp_robust_weight runs on the host; the switch on `loss` is wave-uniform), each of the 28 terms
+// times w once, and w as the 29th.  With loss = none w is exactly 1 and the 28 sums have the bits of the plain kernels': the reduction is
+// theirs, block_moment_row and moment_fold_kernel at K = 29, where every term's additions are its own.  No atomics.
+// PER_POINT: additionally residual / weight / counted at the caller index o = orig_of_slot[i] (a permutation: every row is written once),
+// 0 / 0 / 0 for an uncounted point.  The loop's launches are the instantiation without these stores.
+// `moved`, `orig_of_slot` and `src_normals` are coalesced reads; the target point and its normal are the only gathers (behind the
+// caller-order report entries of o, as in the plain kernels).
+// ---------------------------------------------------------------------------------------------
+template <bool GICP, bool PER_POINT>
+__global__ __launch_bounds__(kBlock) void robust_moments_kernel(const float4* __restrict__ moved, const uint32_t* __restrict__ orig_of_slot,
+                                                                const unsigned char* __restrict__ inlier, const float* __restrict__ d2,
+                                                                const uint32_t* __restrict__ corr, const float4* __restrict__ tgt,
+                                                                const float4* __restrict__ normals, const float4* __restrict__ src_normals, Rt rt, double eps,
+                                                                int loss, double scale, int n, int nt, float max_d2, MomentRow<kRobustTerms>* __restrict__ rows,
+                                                                double* __restrict__ residual, double* __restrict__ weight, unsigned char* __restrict__ counted) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    double v[kRobustTerms];
+#pragma unroll
+    for (int k = 0; k < kRobustTerms; ++k) v[k] = 0.0;
+    unsigned cnt = 0u;
+    if (i < n) {
+        const uint32_t o = orig_of_slot[i];
+        const float4 x = moved[i];
+        float4 np = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (GICP) np = src_normals[i];
+        float4 nn, q;
+        double s = 0.0, w = 0.0;
+        if ((!GICP || nonzero3(np)) && counted_pair(o, inlier, d2, corr, tgt, normals, n, nt, max_d2, nn, q)) {
+            const double X[3] = {(double)x.x, (double)x.y, (double)x.z}, N[3] = {(double)nn.x, (double)nn.y, (double)nn.z};
+            double u[kPlaneTerms];  // the pair's unweighted terms, an array of their own: handed to gicp_pair_terms by pointer and then scaled in place, the accumulators went to scratch memory (240 bytes per lane)
+            if (GICP) {
+                const double Q[3] = {(double)q.x, (double)q.y, (double)q.z}, NP[3] = {(double)np.x, (double)np.y, (double)np.z};
+                gicp_pair_terms(X, Q, N, NP, rt.R, eps, nullptr, u);
+                s = sqrt(u[27] > 0.0 ? u[27] : 0.0);
+            } else {
+                const double r = N[0] * (X[0] - (double)q.x) + N[1] * (X[1] - (double)q.y) + N[2] * (X[2] - (double)q.z);
+                const double J[6] = {X[1] * N[2] - X[2] * N[1], X[2] * N[0] - X[0] * N[2], X[0] * N[1] - X[1] * N[0], N[0], N[1], N[2]};
+                int m = 0;
+#pragma unroll
+                for (int a = 0; a < 6; ++a)
+#pragma unroll
+                    for (int b = a; b < 6; ++b) u[m++] = J[a] * J[b];
+#pragma unroll
+                for (int a = 0; a < 6; ++a) u[21 + a] = J[a] * r;
+                u[27] = r * r;
+                s = r;
+            }
+            w = robust_weight(loss, s, scale);
+#pragma unroll
+            for (int k = 0; k < kPlaneTerms; ++k) v[k] = u[k] * w;
+            v[kPlaneTerms] = w;
+            cnt = 1u;
+        }
+        if (PER_POINT && o < (uint32_t)n) {
+            residual[o] = s;
+            weight[o] = w;
+            counted[o] = (unsigned char)cnt;
+        }
+    }
+    block_moment_row<kBlock / 64>(v, cnt, &rows[blockIdx.x]);
+}
+
+void launch_robust_moments(bool gicp, const float4* moved, const uint32_t* orig_of_slot, const unsigned char* inlier, const float* d2, const uint32_t* corr,
+                           const float4* tgt, const float4* normals, const float4* src_normals, const float* R9, double eps, int loss, double scale, int n, int nt,
+                           float max_d2, MomentRow<kRobustTerms>* rows, unsigned long long* out30, double* residual, double* weight, unsigned char* counted,
+                           hipStream_t s) {
+    const int nb = (n + kBlock - 1) / kBlock;
+    const bool per_point = residual && weight && counted;
+    auto* const kernel = gicp ? (per_point ? robust_moments_kernel<true, true> : robust_moments_kernel<true, false>)
+                              : (per_point ? robust_moments_kernel<false, true> : robust_moments_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, dim3(nb), dim3(kBlock), 0, s, moved, orig_of_slot, inlier, d2, corr, tgt, normals, src_normals, make_rt(R9, nullptr), eps, loss, scale, n, nt,
+                       max_d2, rows, residual, weight, counted);
+    hipLaunchKernelGGL(moment_fold_kernel<kRobustTerms>, dim3(1), dim3(1024), 0, s, rows, nb, out30);
 }
 
 // out[i] = in[orig_of_slot[i]]: per-point data from caller order into device slot order (the source normals: target_knn_kernel writes them

@@ -171,6 +171,16 @@ void launch_plane_moments(const float4* moved, const uint32_t* orig_of_slot, con
 void launch_gicp_moments(const float4* moved, const uint32_t* orig_of_slot, const unsigned char* inlier, const float* d2, const uint32_t* corr, const float4* tgt,
                          const float4* normals, const float4* src_normals, const float* R9, double eps, int n, int nt, float max_d2, MomentRow<kPlaneTerms>* rows,
                          unsigned long long* out29, hipStream_t s);
+// The robustly weighted normal equations of either model (fgoicp_robust_moments; kernels.hip robust_moments_kernel, then moment_fold_kernel
+// at K = 29): the counted set and the 28 terms of launch_plane_moments (gicp = false; src_normals, R9 and eps unused) or launch_gicp_moments
+// (gicp = true), each term times w(s) (host/robust.hpp robust_weight; loss and scale c as fgoicp_robust_weight takes them), and w as the
+// 29th term.  out30 = {count, the bits of 29 doubles}.  residual / weight / counted (all three or none): per-point outputs at the CALLER
+// index, n entries each, 0 / 0 / 0 for an uncounted point; with nullptr the launch is the kernel without those stores.
+constexpr int kRobustTerms = 29;
+void launch_robust_moments(bool gicp, const float4* moved, const uint32_t* orig_of_slot, const unsigned char* inlier, const float* d2, const uint32_t* corr,
+                           const float4* tgt, const float4* normals, const float4* src_normals, const float* R9, double eps, int loss, double scale, int n, int nt,
+                           float max_d2, MomentRow<kRobustTerms>* rows, unsigned long long* out30, double* residual, double* weight, unsigned char* counted,
+                           hipStream_t s);
 // out[i] = in[orig_of_slot[i]], i < n: caller order -> device slot order
 void launch_slot_order(const float4* in, const uint32_t* orig_of_slot, int n, float4* out, hipStream_t s);
 // The bounds of many registrations in one launch (fgoicp_batch, bounds_fused.hpp): a view per pair of the batch, an evaluation per output

@@ -344,6 +344,47 @@ int fgoicp_solver_refine_gicp(fgoicp_solver* s, int k, size_t max_iter, float co
     });
 }
 
+int fgoicp_solver_refine_robust(fgoicp_solver* s, int model, int k, size_t max_iter, float conv_thr, float max_distance, double epsilon, int loss, double loss_scale,
+                                fgoicp_robust_result_t* out) {
+    if (!s) { set_error("fgoicp_solver_refine_robust: the solver must not be null"); return FGOICP_ERR_INVALID_ARG; }
+    if (!s->ran) { set_error("fgoicp_solver_refine_robust: fgoicp_solver_run has not succeeded yet: there is no best transform"); return FGOICP_ERR_INVALID_ARG; }
+    if (!plane_size_ok(out)) { set_error("fgoicp_solver_refine_robust: out must not be null and out->struct_size = sizeof(fgoicp_robust_result_t)"); return FGOICP_ERR_INVALID_ARG; }
+    if (!(max_distance >= 0.0f)) { set_error("fgoicp_solver_refine_robust: max_distance must be >= 0 (+inf: no threshold)"); return FGOICP_ERR_INVALID_ARG; }
+    if (!robust_model_ok(model)) { set_error("fgoicp_solver_refine_robust: unknown model " + std::to_string(model) + " (0: point-to-plane, 1: Generalized ICP)"); return FGOICP_ERR_INVALID_ARG; }
+    if (!robust_loss_ok(loss)) { set_error("fgoicp_solver_refine_robust: unknown loss " + std::to_string(loss)); return FGOICP_ERR_INVALID_ARG; }
+    if (model == FGOICP_MODEL_GICP && !gicp_epsilon_ok(epsilon)) { set_error("fgoicp_solver_refine_robust: epsilon must be finite and lie in (0, 1]"); return FGOICP_ERR_INVALID_ARG; }
+    if (!std::isfinite(loss_scale)) { set_error("fgoicp_solver_refine_robust: loss_scale must be finite (<= 0: estimated)"); return FGOICP_ERR_INVALID_ARG; }
+    return fgoicp::abi_guard("fgoicp_solver_refine_robust", [&] {
+        if (!s->ctx->normals_set) {  // normals are invariant under the solver's centring and uniform scale
+            const int rc = ctx_set_target_normals(s->ctx, nullptr, k);
+            if (rc) return rc;
+        }
+        if (model == FGOICP_MODEL_GICP && !s->ctx->src_normals_set) {
+            const int rc = ctx_set_source_normals(s->ctx, nullptr, k);
+            if (rc) return rc;
+        }
+        Mat3f R;
+        Vec3f t;
+        s->driver->best_transform(R, t);  // the normalised frame the search ran in, as fgoicp_solver_refine_plane
+        const float t3[3] = {t.x, t.y, t.z};
+        RobustSpec r;
+        r.model = model; r.epsilon = epsilon; r.loss = loss;
+        r.scale = loss_scale > 0.0 ? loss_scale * (double)s->scaling_factor : 0.0;  // a residual of either model scales with the frame
+        r.max_dist2 = information_max_dist2(max_distance, s->scaling_factor);
+        fgoicp_robust_result_t full;
+        const int rc = ctx_icp_robust(s->ctx, R.m, t3, max_iter, conv_thr, r, &full, "fgoicp_solver_refine_robust");
+        if (rc) return rc;
+        const Mat3f Rr = Mat3f::from(full.R);
+        const Vec3f ts{full.t[0], full.t[1], full.t[2]};
+        const Vec3f tr = ts / s->scaling_factor + Rr * s->offset_pcs - s->offset_pct;  // restore_translation, fgoicp.hpp:87-90
+        full.t[0] = tr.x; full.t[1] = tr.y; full.t[2] = tr.z;
+        full.scaling_factor = s->scaling_factor;
+        return plane_out(full, out, "fgoicp_solver_refine_robust", "fgoicp_robust_result_t");
+    });
+}
+
+int fgoicp_robust_weight(int loss, double s, double scale, double* w) { return robust_weight_entry(loss, s, scale, w); }
+
 int fgoicp_gicp_terms(const float* x3, const float* q3, const float* nq3, const float* np3, const float* R9, double epsilon, double* M6_or_NULL, double* v28_or_NULL) {
     return gicp_terms_entry(x3, q3, nq3, np3, R9, epsilon, M6_or_NULL, v28_or_NULL);
 }

@@ -6,7 +6,7 @@ import numpy as np
 
 from . import _lib
 from .nodes import from_glm
-from .registration import GicpRefinement, PlaneRefinement, Registration, _alignment, _cloud, _fp, _information
+from .registration import GicpRefinement, PlaneRefinement, Registration, RobustRefinement, _alignment, _cloud, _fp, _information, _loss_code
 
 
 class FastGoICP:
@@ -65,19 +65,32 @@ class FastGoICP:
         d = float("inf") if max_distance is None else float(max_distance)
         return _information(lambda out: self._lib.fgoicp_solver_information(self._h, d, out), "fgoicp_solver_information")
 
-    def refine_plane(self, k=16, max_iter=30, conv_thr=1e-6, max_distance=None):
+    def _refine_robust(self, model, k, max_iter, conv_thr, max_distance, epsilon, loss, loss_scale):
+        d = float("inf") if max_distance is None else float(max_distance)
+        raw = _lib.RobustResult()
+        _lib.check(self._lib.fgoicp_solver_refine_robust(self._h, model, int(k), int(max_iter), float(conv_thr), d, float(epsilon), _loss_code(loss),
+                                                         0.0 if loss_scale is None else float(loss_scale), C.byref(raw)), "fgoicp_solver_refine_robust")
+        return RobustRefinement(raw, model)
+
+    def refine_plane(self, k=16, max_iter=30, conv_thr=1e-6, max_distance=None, loss=None, loss_scale=None):
         """EXTENSION (fgoicp_solver_refine_plane): point-to-plane ICP from the best transform, after run() -> PlaneRefinement with R and t
         in the callers' frame.  The target's normals are estimated from k neighbours unless the registration already has some;
-        max_distance: callers' units (None: no threshold), as information() takes it.  run() and the best transform are untouched."""
+        max_distance: callers' units (None: no threshold), as information() takes it.  run() and the best transform are untouched.
+        loss "huber" / "cauchy" / "geman_mcclure" / "tukey" (fgoicp_solver_refine_robust): the robustly weighted loop -> RobustRefinement;
+        loss_scale in the callers' units, None: estimated at the best transform."""
+        if loss is not None:
+            return self._refine_robust(_lib.MODEL_PLANE, k, max_iter, conv_thr, max_distance, 1e-3, loss, loss_scale)
         d = float("inf") if max_distance is None else float(max_distance)
         raw = _lib.PlaneResult()
         _lib.check(self._lib.fgoicp_solver_refine_plane(self._h, int(k), int(max_iter), float(conv_thr), d, C.byref(raw)), "fgoicp_solver_refine_plane")
         return PlaneRefinement(raw)
 
-    def refine_gicp(self, k=16, max_iter=30, conv_thr=1e-6, max_distance=None, epsilon=1e-3):
+    def refine_gicp(self, k=16, max_iter=30, conv_thr=1e-6, max_distance=None, epsilon=1e-3, loss=None, loss_scale=None):
         """EXTENSION (fgoicp_solver_refine_gicp): Generalized ICP from the best transform, after run() -> GicpRefinement (a
         PlaneRefinement) with R and t in the callers' frame.  Whichever normal set the registration lacks is estimated from k neighbours;
-        max_distance as refine_plane takes it.  run() and the best transform are untouched."""
+        max_distance as refine_plane takes it.  run() and the best transform are untouched.  loss and loss_scale as refine_plane's."""
+        if loss is not None:
+            return self._refine_robust(_lib.MODEL_GICP, k, max_iter, conv_thr, max_distance, epsilon, loss, loss_scale)
         d = float("inf") if max_distance is None else float(max_distance)
         raw = _lib.PlaneResult()
         _lib.check(self._lib.fgoicp_solver_refine_gicp(self._h, int(k), int(max_iter), float(conv_thr), d, float(epsilon), C.byref(raw)), "fgoicp_solver_refine_gicp")

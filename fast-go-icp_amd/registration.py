@@ -384,6 +384,64 @@ class GicpRefinement(PlaneRefinement):
         self.gicp_rmse_scaled, self.gicp_rmse = self.plane_rmse_scaled, self.plane_rmse
 
 
+def _loss_code(loss):
+    """None / a name of _lib.LOSSES / its code -> the code"""
+    if loss is None:
+        return _lib.LOSS_NONE
+    if isinstance(loss, str):
+        if loss not in _lib.LOSSES:
+            raise ValueError(f"loss must be None or one of {sorted(_lib.LOSSES)}, not {loss!r}")
+        return _lib.LOSSES[loss]
+    return int(loss)
+
+
+def _model_code(model):
+    return {"plane": _lib.MODEL_PLANE, "gicp": _lib.MODEL_GICP}.get(model, model)
+
+
+LOSS_NAMES = {v: k for k, v in _lib.LOSSES.items()}
+
+
+def robust_weight(loss, s, scale):
+    """fgoicp_robust_weight (host only): the IRLS weight w(s) of the loss ("huber", "cauchy", "geman_mcclure", "tukey", "none" or a
+    code) at the scale -> float (fp64; the arithmetic the device kernel runs)."""
+    w = C.c_double()
+    _lib.check(_lib.load().fgoicp_robust_weight(_loss_code(loss), float(s), float(scale), C.byref(w)), "fgoicp_robust_weight")
+    return w.value
+
+
+class RobustMomentsResult(PlaneMomentsResult):
+    """EXTENSION (fgoicp_robust_moments): a PlaneMomentsResult whose every term carries its pair's weight, plus weight_sum, loss (name)
+    and scale."""
+
+    def __init__(self, raw):
+        super().__init__(raw)
+        self.weight_sum, self.loss, self.scale = float(raw.weight_sum), LOSS_NAMES.get(int(raw.loss), int(raw.loss)), float(raw.scale)
+
+
+class RobustRefinement(PlaneRefinement):
+    """EXTENSION (fgoicp_icp_robust / fgoicp_solver_refine_robust): a PlaneRefinement (model "plane") or GicpRefinement ("gicp") of the
+    robustly weighted loop.  plane_rmse / gicp_rmse hold sqrt(sum w s^2 / sum w) at the returned pose; weight_sum = sum w there; loss (name);
+    loss_scale — the scale the loop ran with, in the callers' units; scale_estimated — whether the library estimated it."""
+
+    def __init__(self, raw, model):
+        self.R, self.t = from_glm(np.array(raw.R, np.float32)), np.array(raw.t, np.float32)
+        self.iterations, self.rank, self.correspondences = int(raw.iterations), int(raw.rank), int(raw.correspondences)
+        self.scaling_factor = np.float32(raw.scaling_factor)
+        self.plane_rmse_scaled = float(raw.rmse)
+        self.plane_rmse = float(raw.rmse / np.float64(raw.scaling_factor))
+        if model == _lib.MODEL_GICP:
+            self.gicp_rmse_scaled, self.gicp_rmse = self.plane_rmse_scaled, self.plane_rmse
+        self.sse = np.float32(raw.sse)
+        self.weight_sum = float(raw.weight_sum)
+        self.loss = LOSS_NAMES.get(int(raw.loss), int(raw.loss))
+        self.loss_scale_scaled = float(raw.scale)
+        self.loss_scale = float(raw.scale / np.float64(raw.scaling_factor))
+        self.scale_estimated = bool(raw.scale_estimated)
+        self.model = "gicp" if model == _lib.MODEL_GICP else "plane"
+        self.raw = bytes(raw)
+
+
 def gicp_terms(x, q, nq, np_, R, epsilon=1e-3):
     """fgoicp_gicp_terms (host only): one pair -> (M (3, 3) float64, v (28,) float64) — M = (C_q + R C_p R^T)^-1 of the regularised
     covariances, v the pair's terms of J^T M J (upper triangle row by row), J^T M d and d^T M d."""
@@ -533,8 +591,49 @@ class Registration:
         _lib.check(self._lib.fgoicp_plane_moments(self._h, _fp(Rg), _fp(tt), float(max_dist2), C.byref(raw)), "fgoicp_plane_moments")
         return PlaneMomentsResult(raw)
 
-    def icp_plane(self, R, t, max_iter=30, conv_thr=1e-6, max_dist2=np.inf):
-        """EXTENSION (fgoicp_icp_plane): point-to-plane ICP from (R, t) -> PlaneRefinement.  max_iter = 0 evaluates the start."""
+    def robust_moments(self, R, t, model="plane", loss=None, scale=0.0, max_dist2=np.inf, epsilon=1e-3):
+        """EXTENSION (fgoicp_robust_moments): plane_moments (model "plane") or gicp_moments ("gicp") with every pair's terms times its
+        weight w(s) -> RobustMomentsResult.  loss None / "none": the plain sums, bit for bit."""
+        Rg = to_glm(R)
+        tt = np.ascontiguousarray(t, dtype=np.float32).reshape(3)
+        raw = _lib.RobustMoments()
+        _lib.check(self._lib.fgoicp_robust_moments(self._h, _fp(Rg), _fp(tt), float(max_dist2), _model_code(model), float(epsilon), _loss_code(loss), float(scale),
+                                                   C.byref(raw)), "fgoicp_robust_moments")
+        return RobustMomentsResult(raw)
+
+    def robust_residuals(self, R, t, model="plane", loss=None, scale=0.0, max_dist2=np.inf, epsilon=1e-3):
+        """EXTENSION (fgoicp_robust_residuals): per source point in the caller's order -> (residual (ns,) float64, weight (ns,) float64,
+        counted (ns,) bool); an uncounted point has 0, 0, False."""
+        Rg = to_glm(R)
+        tt = np.ascontiguousarray(t, dtype=np.float32).reshape(3)
+        res = np.empty(self.ns, np.float64); w = np.empty(self.ns, np.float64); cnt = np.empty(self.ns, np.uint8)
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        _lib.check(self._lib.fgoicp_robust_residuals(self._h, _fp(Rg), _fp(tt), float(max_dist2), _model_code(model), float(epsilon), _loss_code(loss), float(scale),
+                                                     dp(res), dp(w), cnt.ctypes.data_as(_lib.c_uint8_p)), "fgoicp_robust_residuals")
+        return res, w, cnt.astype(bool)
+
+    def robust_scale(self, R, t, model="plane", max_dist2=np.inf, epsilon=1e-3):
+        """EXTENSION (fgoicp_robust_scale): 1.4826 x the lower median of |residual| over the counted -> float."""
+        Rg = to_glm(R)
+        tt = np.ascontiguousarray(t, dtype=np.float32).reshape(3)
+        s = C.c_double()
+        _lib.check(self._lib.fgoicp_robust_scale(self._h, _fp(Rg), _fp(tt), float(max_dist2), _model_code(model), float(epsilon), C.byref(s)), "fgoicp_robust_scale")
+        return s.value
+
+    def _icp_robust(self, model, R, t, max_iter, conv_thr, max_dist2, epsilon, loss, loss_scale):
+        Rg = to_glm(R)
+        tt = np.ascontiguousarray(t, dtype=np.float32).reshape(3)
+        raw = _lib.RobustResult()
+        _lib.check(self._lib.fgoicp_icp_robust(self._h, _fp(Rg), _fp(tt), int(max_iter), float(conv_thr), float(max_dist2), model, float(epsilon), _loss_code(loss),
+                                               0.0 if loss_scale is None else float(loss_scale), C.byref(raw)), "fgoicp_icp_robust")
+        return RobustRefinement(raw, model)
+
+    def icp_plane(self, R, t, max_iter=30, conv_thr=1e-6, max_dist2=np.inf, loss=None, loss_scale=None):
+        """EXTENSION (fgoicp_icp_plane): point-to-plane ICP from (R, t) -> PlaneRefinement.  max_iter = 0 evaluates the start.
+        loss "huber" / "cauchy" / "geman_mcclure" / "tukey" (fgoicp_icp_robust): the robustly weighted loop -> RobustRefinement;
+        loss_scale None: estimated at (R, t)."""
+        if loss is not None:
+            return self._icp_robust(_lib.MODEL_PLANE, R, t, max_iter, conv_thr, max_dist2, 1e-3, loss, loss_scale)
         Rg = to_glm(R)
         tt = np.ascontiguousarray(t, dtype=np.float32).reshape(3)
         raw = _lib.PlaneResult()
@@ -567,8 +666,11 @@ class Registration:
         _lib.check(self._lib.fgoicp_gicp_moments(self._h, _fp(Rg), _fp(tt), float(max_dist2), float(epsilon), C.byref(raw)), "fgoicp_gicp_moments")
         return PlaneMomentsResult(raw)
 
-    def icp_gicp(self, R, t, max_iter=30, conv_thr=1e-6, max_dist2=np.inf, epsilon=1e-3):
-        """EXTENSION (fgoicp_icp_gicp): Generalized ICP from (R, t) -> GicpRefinement.  max_iter = 0 evaluates the start."""
+    def icp_gicp(self, R, t, max_iter=30, conv_thr=1e-6, max_dist2=np.inf, epsilon=1e-3, loss=None, loss_scale=None):
+        """EXTENSION (fgoicp_icp_gicp): Generalized ICP from (R, t) -> GicpRefinement.  max_iter = 0 evaluates the start.  loss and
+        loss_scale as icp_plane's."""
+        if loss is not None:
+            return self._icp_robust(_lib.MODEL_GICP, R, t, max_iter, conv_thr, max_dist2, epsilon, loss, loss_scale)
         Rg = to_glm(R)
         tt = np.ascontiguousarray(t, dtype=np.float32).reshape(3)
         raw = _lib.PlaneResult()

@@ -75,6 +75,15 @@ public:
         check_status(fgoicp_solver_refine_gicp(s_, k, max_iter, conv_thr, max_distance, epsilon, &p.result), "fgoicp_solver_refine_gicp");
         return p;
     }
+    // EXTENSION: either refinement under a robust loss (fgoicp_solver_refine_robust): model FGOICP_MODEL_PLANE / FGOICP_MODEL_GICP, loss
+    // FGOICP_LOSS_*, loss_scale in the callers' units (<= 0: estimated at the best transform); the rest as refine_plane / refine_gicp.
+    RobustRefinement refine_robust(int model, int loss, double loss_scale = 0.0, int k = 16, size_t max_iter = 30, float conv_thr = 1e-6f, float max_distance = INFINITY,
+                                   double epsilon = 1e-3) const {
+        RobustRefinement p;
+        p.result.struct_size = sizeof(p.result);
+        check_status(fgoicp_solver_refine_robust(s_, model, k, max_iter, conv_thr, max_distance, epsilon, loss, loss_scale, &p.result), "fgoicp_solver_refine_robust");
+        return p;
+    }
     fgoicp_run_stats stats() const { fgoicp_run_stats st{}; check_status(fgoicp_solver_stats(s_, &st), "fgoicp_solver_stats"); return st; }
     fgoicp_solver* handle() const { return s_; }
     // the reference's own lines while the search runs (fgoicp.cpp:15-17 Info, :85-87 Debug), from the driver's log events

@@ -72,6 +72,17 @@ struct PlaneRefinement {
     vec3 t() const { return vec3{result.t[0], result.t[1], result.t[2]}; }
     double plane_rmse() const { return result.plane_rmse / (double)result.scaling_factor; }  // callers' units
 };
+// EXTENSION (ours): the robustly weighted loop of either refinement (fgoicp_icp_robust, fgoicp_solver_refine_robust): the pose as
+// PlaneRefinement's, rmse() = sqrt(sum w s^2 / sum w) and loss_scale() in the callers' units.
+struct RobustRefinement {
+    fgoicp_robust_result_t result{};
+    mat3 R() const { mat3 m; for (int k = 0; k < 9; ++k) m.data()[k] = result.R[k]; return m; }
+    vec3 t() const { return vec3{result.t[0], result.t[1], result.t[2]}; }
+    double rmse() const { return result.rmse / (double)result.scaling_factor; }
+    double loss_scale() const { return result.scale / (double)result.scaling_factor; }
+    double weight_sum() const { return result.weight_sum; }
+    bool scale_estimated() const { return result.scale_estimated != 0; }
+};
 struct TargetKnn {
     std::vector<uint32_t> indices;  // nt rows of k: every target point's k nearest target points, itself included, sorted by (distance, index)
     std::vector<float> dist2;
@@ -177,6 +188,27 @@ public:
         PlaneRefinement p;
         p.result.struct_size = sizeof(p.result);
         check_status(fgoicp_icp_gicp(ctx_, R.data(), &t.x, max_iter, conv_thr, max_dist2, epsilon, &p.result), "fgoicp_icp_gicp");
+        return p;
+    }
+    // EXTENSION: robust losses over either refinement (model FGOICP_MODEL_PLANE / FGOICP_MODEL_GICP, loss FGOICP_LOSS_*): the weighted
+    // normal equations at a pose (fgoicp_robust_moments), the automatic scale there (fgoicp_robust_scale) and the loop
+    // (fgoicp_icp_robust; scale <= 0: estimated at (R, t))
+    fgoicp_robust_moments_t robust_moments(mat3 R, vec3 t, int model, int loss, double scale, float max_dist2 = INFINITY, double epsilon = 1e-3) const {
+        fgoicp_robust_moments_t m{};
+        m.struct_size = sizeof(m);
+        check_status(fgoicp_robust_moments(ctx_, R.data(), &t.x, max_dist2, model, epsilon, loss, scale, &m), "fgoicp_robust_moments");
+        return m;
+    }
+    double robust_scale(mat3 R, vec3 t, int model, float max_dist2 = INFINITY, double epsilon = 1e-3) const {
+        double s = 0.0;
+        check_status(fgoicp_robust_scale(ctx_, R.data(), &t.x, max_dist2, model, epsilon, &s), "fgoicp_robust_scale");
+        return s;
+    }
+    RobustRefinement icp_robust(mat3 R, vec3 t, int model, int loss, double scale = 0.0, size_t max_iter = 30, float conv_thr = 1e-6f, float max_dist2 = INFINITY,
+                                double epsilon = 1e-3) const {
+        RobustRefinement p;
+        p.result.struct_size = sizeof(p.result);
+        check_status(fgoicp_icp_robust(ctx_, R.data(), &t.x, max_iter, conv_thr, max_dist2, model, epsilon, loss, scale, &p.result), "fgoicp_icp_robust");
         return p;
     }
 

@@ -332,6 +332,67 @@ int fgoicp_icp_gicp(fgoicp_ctx* ctx, const float* R0_9, const float* t0_3, size_
  * (optional): the pair's 28 terms.  Refuses null inputs and an epsilon outside (0, 1]. */
 int fgoicp_gicp_terms(const float* x3, const float* q3, const float* nq3, const float* np3, const float* R9, double epsilon, double* M6_or_NULL, double* v28_or_NULL);
 
+/*
+ * EXTENSION — robust losses for the two refinements (no reference counterpart; Open3D: registration.HuberLoss, CauchyLoss, GMLoss,
+ * TukeyLoss): iteratively reweighted least squares.  Every term a counted correspondence contributes to the normal equations is multiplied
+ * by w(s), s the correspondence's residual: s = r = n.(x - q) for FGOICP_MODEL_PLANE, s = sqrt(max(d^T M d, 0)) for FGOICP_MODEL_GICP.  The
+ * scale c > 0 is fixed for a whole loop.  All arithmetic is fp64 with one rounding per operation, a = |s|:
+ *   FGOICP_LOSS_NONE           w = 1
+ *   FGOICP_LOSS_HUBER          w = a <= c ? 1 : c / a
+ *   FGOICP_LOSS_CAUCHY         u = s / c;  w = 1 / (1 + u * u)
+ *   FGOICP_LOSS_GEMAN_MCCLURE  c2 = c * c;  g = c2 / (c2 + s * s);  w = g * g
+ *   FGOICP_LOSS_TUKEY          w = a <= c ? (v = 1 - (s / c) * (s / c), v * v) : 0
+ * Only + - * / and one sqrt: the host function, the kernel and a float64 restatement agree in every bit.  The rho values are not computed.
+ * The counted set, the 28 unweighted terms and the order of every addition are those of fgoicp_plane_moments / fgoicp_gicp_moments; with
+ * FGOICP_LOSS_NONE m[28] has the bits of the plain call and weight_sum == correspondences.  Context frame.
+ */
+enum { FGOICP_LOSS_NONE = 0, FGOICP_LOSS_HUBER = 1, FGOICP_LOSS_CAUCHY = 2, FGOICP_LOSS_GEMAN_MCCLURE = 3, FGOICP_LOSS_TUKEY = 4 };
+enum { FGOICP_MODEL_PLANE = 0, FGOICP_MODEL_GICP = 1 };
+typedef struct fgoicp_robust_moments_t {
+    uint32_t struct_size;             /* IN: sizeof(fgoicp_robust_moments_t) as the CALLER was compiled; no byte beyond it is written, 0 is refused */
+    uint64_t points, correspondences; /* ns; the counted correspondences N (a zero weight still counts) */
+    double   m[28];                   /* the layout of fgoicp_plane_moments_t, every term times its pair's w */
+    double   weight_sum;              /* sum w over the counted */
+    float    max_dist2;               /* the threshold the device compared with */
+    int      loss;
+    double   scale;                   /* as given */
+} fgoicp_robust_moments_t;
+typedef struct fgoicp_robust_result_t {
+    uint32_t struct_size;             /* IN: sizeof(fgoicp_robust_result_t) as the CALLER was compiled; no byte beyond it is written, 0 is refused */
+    float    R[9], t[3];              /* the refined pose (fgoicp_solver_refine_robust: t restored to the callers' frame) */
+    int      iterations;              /* steps taken */
+    int      rank;                    /* of the last solve (0 when max_iter = 0, nothing was counted or every weight was zero) */
+    uint64_t correspondences;         /* counted at the returned pose */
+    double   weight_sum;              /* sum w at the returned pose */
+    double   rmse;                    /* sqrt(sum w s^2 / sum w) at the returned pose, context frame (0 when the weight sum is 0) */
+    float    sse;                     /* == fgoicp_sse(ctx, R, t) at the returned pose, bit for bit (context frame) */
+    float    scaling_factor;          /* 1 for a bare context; the solver's scale otherwise */
+    int      loss;
+    int      scale_estimated;         /* 1: the scale was estimated at the start pose (fgoicp_robust_scale), 0: it was given */
+    double   scale;                   /* the scale the loop ran with, context frame (/ scaling_factor: callers' units) */
+} fgoicp_robust_result_t;
+/* Host only, no device: *w = w(s).  Refuses a null w, an unknown loss, a non-finite s and, except for FGOICP_LOSS_NONE, a scale that is
+ * not finite and positive; a refusal leaves *w untouched. */
+int fgoicp_robust_weight(int loss, double s, double scale, double* w);
+/* One evaluation at a fixed pose, as fgoicp_plane_moments (model 0) / fgoicp_gicp_moments (model 1; epsilon is ignored by model 0).
+ * Refuses what those refuse and an unknown loss or model and a bad scale (FGOICP_LOSS_NONE ignores the scale), all before any device
+ * work.  Leaves the context as it found it.  Two calls return the same bytes. */
+int fgoicp_robust_moments(fgoicp_ctx* ctx, const float* R9, const float* t3, float max_dist2, int model, double epsilon, int loss, double scale,
+                          fgoicp_robust_moments_t* out);
+/* The same evaluation per point, caller order, ns entries each: residual s, weight w(s), counted 0 / 1; an uncounted point gets 0, 0, 0.
+ * Any of the arrays may be NULL. */
+int fgoicp_robust_residuals(fgoicp_ctx* ctx, const float* R9, const float* t3, float max_dist2, int model, double epsilon, int loss, double scale,
+                            double* residual_ns, double* weight_ns, unsigned char* counted_ns);
+/* The automatic scale at (R, t): 1.4826 * sorted(|s| over the N counted)[(N - 1) / 2] — the lower median, one fp64 product.  Refused
+ * (FGOICP_ERR_INVALID_ARG, the message says to pass a scale) when nothing is counted or that median is 0. */
+int fgoicp_robust_scale(fgoicp_ctx* ctx, const float* R9, const float* t3, float max_dist2, int model, double epsilon, double* scale);
+/* fgoicp_icp_plane's / fgoicp_icp_gicp's loop, term for term, over fgoicp_robust_moments: the stop band, the rank-deficient first
+ * step, the evaluation at the returned pose.  scale <= 0: estimated once at (R0, t0).  It also ends when the weight sum is 0 (every
+ * counted pair beyond a Tukey scale): the pose is then the one that evaluation was made at.  With FGOICP_LOSS_NONE R, t, iterations, rank
+ * and sse are the plain loop's.  Leaves the context as it found it. */
+int fgoicp_icp_robust(fgoicp_ctx* ctx, const float* R0_9, const float* t0_3, size_t max_iter, float conv_thr, float max_dist2, int model, double epsilon,
+                      int loss, double scale, fgoicp_robust_result_t* out);
+
 /* Replaces IterativeClosestPoint3D(reg, pct, pcs, max_iter, thr, R, t) + run()
  * (fgoicp/icp3d.hpp:30-35, icp3d.cu:55-108).  Returns the reference's Result_t {sse, R, t}
  * plus the number of loop iterations executed. */
@@ -508,6 +569,12 @@ int fgoicp_solver_refine_plane(fgoicp_solver* s, int k, size_t max_iter, float c
  * the solver's centring and uniform scale).  max_distance, R, t and scaling_factor as fgoicp_solver_refine_plane; plane_rmse holds
  * sqrt(sum d^T M d / N) in the solver's frame.  The solver's own result is untouched. */
 int fgoicp_solver_refine_gicp(fgoicp_solver* s, int k, size_t max_iter, float conv_thr, float max_distance, double epsilon, fgoicp_plane_result_t* out);
+/* EXTENSION: fgoicp_icp_robust from the best transform, as the two calls above (model FGOICP_MODEL_PLANE / FGOICP_MODEL_GICP; normals
+ * estimated with k where they are not set).  max_distance and loss_scale are in the CALLERS' units (x scaling_factor inwards;
+ * loss_scale <= 0: estimated); t is restored to the callers' frame; rmse, sse and scale stay in the solver's frame (scaling_factor
+ * converts).  The solver's best transform is left alone. */
+int fgoicp_solver_refine_robust(fgoicp_solver* s, int model, int k, size_t max_iter, float conv_thr, float max_distance, double epsilon, int loss, double loss_scale,
+                                fgoicp_robust_result_t* out);
 /* Pre-processing results (tests): offs6 = {offset_pcs, offset_pct}, bounds6 as in ctx_create. */
 int fgoicp_solver_preproc(const fgoicp_solver* s, float* offs6, float* scale, float* bounds6);
 /* Statistics of a raw cloud, host side, no device needed (TODO.md:7 of the reference: "compute point clouds' stats"): what the

@@ -1,0 +1,20 @@
+// TEST-ONLY: prints the robust-loss keys of a configuration as the CLI's parser (fast-go-icp_amd/csrc/cli/config.hpp) reads them; exit code 2
+// and the message when the parser refuses the file.
+#include <cstdio>
+
+#include "../../fast-go-icp_amd/csrc/cli/config.hpp"
+
+extern "C" const char* fgoicp_last_error(void) { return ""; }  // icp::check_status is never reached here
+
+int main(int argc, char** argv) {
+    if (argc != 2) return 3;
+    try {
+        cli::Config c(argv[1]);
+        std::printf("ROBUST %s %s %d %.17g\n", c.params.refine.empty() ? "-" : c.params.refine.c_str(), c.params.refine_loss.c_str(), c.params.refine_loss_code(),
+                    c.params.refine_loss_scale);
+        return 0;
+    } catch (const std::exception& e) {
+        std::printf("REFUSED %s\n", e.what());
+        return 2;
+    }
+}
