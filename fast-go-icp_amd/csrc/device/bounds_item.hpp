@@ -38,6 +38,7 @@ struct ItemGeom {
     int px;
     int c0;                  // (py + 1) * px + 1: what the "+ 1" of the three padded indices adds to the offset
     unsigned nbx3, nby2;     // apron layout
+    unsigned nby3;           // z-pair apron layout
 };
 __device__ __forceinline__ ItemGeom item_geom(const LutGeom& g) {
     ItemGeom G;
@@ -51,6 +52,7 @@ __device__ __forceinline__ ItemGeom item_geom(const LutGeom& g) {
     G.c0 = (g.py + 1) * g.px + 1;
     G.nbx3 = (unsigned)(g.px + 2) / 3u;
     G.nby2 = (unsigned)(g.py + 1) >> 1;
+    G.nby3 = (unsigned)(g.py + 2) / 3u;
     return G;
 }
 
@@ -113,7 +115,8 @@ __device__ __forceinline__ float item_blend(const ItemTex& t, f2v lo_y0, f2v hi_
 }
 
 // MODE: 0 = fix_rot item, 1 = rotation-uncertainty item, 2 = dual (both variants from one lookup: acc[0..1] fix_rot = 1, acc[2..3] fix_rot = 0)
-// LAYOUT: 1 = z-pair copy (float2 {T[o], T[o + slice]}), 3 = yz-quad runs, 5 = apron-bricked yz-quads (both fetched by lane pairs)
+// LAYOUT: 1 = z-pair copy (float2 {T[o], T[o + slice]}), 3 = yz-quad runs, 5 = apron-bricked yz-quads, 6 = z-pair apron bricks (the three
+// fetched by lane pairs)
 template <int LAYOUT, int TRIM, bool WIDE, bool QUANT, int MODE, bool FULL>
 __device__ __forceinline__ void item_pass(const float4* __restrict__ src, int ns, const char* __restrict__ lutp, const ItemGeom& G, const float (&R)[9], f2v t_xy, float t_z,
                                           float sin_half, float trans_radius, int first, int odd, double (&acc)[4], float* __restrict__ row0, float* __restrict__ row1,
@@ -137,22 +140,35 @@ __device__ __forceinline__ void item_pass(const float4* __restrict__ src, int ns
             ga[k] = *reinterpret_cast<const float4u*>(item_address<WIDE, 3>(lutp, idx));
             gb[k] = *reinterpret_cast<const float4u*>(item_address<WIDE, 3>(row1, idx));
         }
-    } else {            // yz-quads (at most 2^30 of them), the two 16-byte halves of a lookup fetched by a pair of neighbouring lanes (swap_lane_pair above)
+    } else {            // the two 16-byte pieces of a lookup fetched by a pair of neighbouring lanes (swap_lane_pair above): load 1 brings the even lane's
+                        // lookup (even lane: first piece, odd lane: second), load 2 the odd lane's.  yz-quads (at most 2^30 of them): the quads of x0 and
+                        // x0 + 1, one slot apart; z-pair apron bricks (fewer than 2^31 slots): rows y0 and y0 + 1, four slots apart, 8-byte aligned
+        constexpr int kStep = LAYOUT == 6 ? 4 : 1;
         QuadPairLoads qp[P];
 #pragma unroll
         for (int k = 0; k < P; ++k) {
-            const int own = LAYOUT == 5 ? (int)apron_index(item_packed_index(tx[k]), G.nbx3, G.nby2) : (int)item_index<WIDE>(G, tx[k]);
+            const int own = LAYOUT == 6   ? (int)zpair_apron_index(item_packed_index(tx[k]), G.nbx3, G.nby3)
+                            : LAYOUT == 5 ? (int)apron_index(item_packed_index(tx[k]), G.nbx3, G.nby2)
+                                          : (int)item_index<WIDE>(G, tx[k]);
             const int other = swap_lane_pair(own);
             const int o_even = odd ? other : own, o_odd = odd ? own : other;
-            qp[k].r1 = *reinterpret_cast<const float4a*>(item_address<WIDE, 4>(lutp, (size_t)(unsigned)(o_even + odd)));
-            qp[k].r2 = *reinterpret_cast<const float4a*>(item_address<WIDE, 4>(lutp, (size_t)(unsigned)(o_odd + odd)));
+            if (LAYOUT == 6) {
+                const f4v r1 = *reinterpret_cast<const float4u*>(item_address<WIDE, 3>(lutp, (size_t)(unsigned)(o_even + kStep * odd)));
+                const f4v r2 = *reinterpret_cast<const float4u*>(item_address<WIDE, 3>(lutp, (size_t)(unsigned)(o_odd + kStep * odd)));
+                qp[k].r1 = float4a{r1.x, r1.y, r1.z, r1.w};
+                qp[k].r2 = float4a{r2.x, r2.y, r2.z, r2.w};
+            } else {
+                qp[k].r1 = *reinterpret_cast<const float4a*>(item_address<WIDE, 4>(lutp, (size_t)(unsigned)(o_even + kStep * odd)));
+                qp[k].r2 = *reinterpret_cast<const float4a*>(item_address<WIDE, 4>(lutp, (size_t)(unsigned)(o_odd + kStep * odd)));
+            }
         }
 #pragma unroll
         for (int k = 0; k < P; ++k) {
             const float4a send = odd ? qp[k].r1 : qp[k].r2;
             float4a recv;
             recv.x = swap_lane_pair(send.x); recv.y = swap_lane_pair(send.y); recv.z = swap_lane_pair(send.z); recv.w = swap_lane_pair(send.w);
-            const float4a a = odd ? recv : qp[k].r1, b = odd ? qp[k].r2 : recv;  // quad of x0, quad of x1: {y0z0, y0z1, y1z0, y1z1}
+            // quads: quad of x0, quad of x1, each {y0z0, y0z1, y1z0, y1z1}; z-pair bricks: row y0, row y0 + 1, each {x0z0, x0z1, x1z0, x1z1}
+            const float4a a = odd ? recv : qp[k].r1, b = odd ? qp[k].r2 : recv;
             ga[k] = f4v{a.x, a.y, a.z, a.w};
             gb[k] = f4v{b.x, b.y, b.z, b.w};
         }
@@ -161,7 +177,7 @@ __device__ __forceinline__ void item_pass(const float4* __restrict__ src, int ns
 #pragma unroll
     for (int k = 0; k < P; ++k) {
         float dsq;
-        if (LAYOUT == 1) dsq = item_blend(tx[k], f2v{ga[k].x, ga[k].y}, f2v{ga[k].z, ga[k].w}, f2v{gb[k].x, gb[k].y}, f2v{gb[k].z, gb[k].w});   // :46
+        if (LAYOUT == 1 || LAYOUT == 6) dsq = item_blend(tx[k], f2v{ga[k].x, ga[k].y}, f2v{ga[k].z, ga[k].w}, f2v{gb[k].x, gb[k].y}, f2v{gb[k].z, gb[k].w});   // :46
         else dsq = item_blend(tx[k], f2v{ga[k].x, ga[k].y}, f2v{gb[k].x, gb[k].y}, f2v{ga[k].z, ga[k].w}, f2v{gb[k].z, gb[k].w});
         const float d1 = sqrtf(dsq);                                              // :48
         const float d0 = d1 - 2.0f * p[k].w * sin_half;                           // :39-43, :49-52 (fix_rot = 0)

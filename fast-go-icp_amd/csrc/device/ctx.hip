@@ -1614,14 +1614,21 @@ int create_packed_lut(fgoicp_ctx* c) {
     int layout = ((double)c->ns / face_voxels < 0.5 && total * sizeof(float4) <= ((size_t)16 << 30)) ? 2 : 1;
     // sparse clouds, round 3: the apron-bricked quads (kernels.hip apron_index: every lookup inside one line, a line serves a 3 x 2
     // patch of base voxels; 21.3 instead of 16 B per node) — bounds kernel -1.1 % on the bunny shape, three A/B pairs
-    const size_t lines = (size_t)((g.px + 2) / 3) * ((g.py + 1) / 2) * g.pz, apron_bytes = lines * 8 * sizeof(float4);
+    const size_t apron_bytes = packed_lut_bytes(g, 4);
     if (layout == 2 && apron_bytes <= ((size_t)16 << 30)) layout = 4;
-    if (const char* e = dev_env("FGOICP_LUT_ZPAIR")) { const int v = std::atoi(e); if (v == 1 || v == 2 || v == 4) layout = v; }  // tuning knob
-    if (layout == 4 && (g.px > 1023 || g.py > 1023 || g.pz > 1023)) layout = 2;  // the apron copy packs indices in 10 bits
+    // ... and once that copy no longer fits the 256 MiB Infinity Cache, where every byte of a gathered line comes from memory: the z-pair
+    // apron bricks (kernels.hip zpair_apron_index: still one line per lookup, a line serves a 3 x 3 patch; 14.2 B per node) —
+    // profiles/ab_zpair_apron.txt.  Below it the copy is served on die and the quads' single 32-byte piece per lookup stays.
+    if (layout == 4 && apron_bytes > ((size_t)256 << 20)) layout = 6;
+    if (const char* e = dev_env("FGOICP_LUT_ZPAIR")) { const int v = std::atoi(e); if (v == 1 || v == 2 || v == 4 || v == 6) layout = v; }  // tuning knob
+    if ((layout == 4 || layout == 6) && (g.px > 1023 || g.py > 1023 || g.pz > 1023)) layout = 2;  // the apron copies pack indices in 10 bits
     c->lut_layout = layout;
     // (d_lut_zp counts float2: a float4 is two of them)
-    if (layout == 4) {
-        HIPCHK(c->d_lut_zp.alloc(lines * 8 * 2));
+    if (layout == 6) {
+        HIPCHK(c->d_lut_zp.alloc(packed_lut_bytes(g, 6) / sizeof(float2)));
+        launch_lut_zpair_apron(c->d_lut, g, c->d_lut_zp, c->stream);
+    } else if (layout == 4) {
+        HIPCHK(c->d_lut_zp.alloc(apron_bytes / sizeof(float2)));
         launch_lut_quad_apron(c->d_lut, g, reinterpret_cast<float4*>(c->d_lut_zp.get()), c->stream);
     } else if (layout == 2) {
         HIPCHK(c->d_lut_zp.alloc(total * 2));
@@ -1871,11 +1878,7 @@ int fgoicp_ctx_get_info(const fgoicp_ctx* c, fgoicp_ctx_info* out) {
     out->lut_layout = c->d_lut_zp ? c->lut_layout : 0;
     out->lut_nodes = (uint64_t)g.dx * g.dy * g.dz;
     const uint64_t padded = (uint64_t)g.px * g.py * g.pz;
-    size_t packed = 0;
-    if (c->d_lut_zp) {
-        if (c->lut_layout == 4) packed = (size_t)((c->geom.px + 2) / 3) * ((c->geom.py + 1) / 2) * c->geom.pz * 8 * sizeof(float4);
-        else packed = padded * (c->lut_layout == 2 ? sizeof(float4) : sizeof(float2));
-    }
+    const size_t packed = c->d_lut_zp ? packed_lut_bytes(g, c->lut_layout) : 0;
     out->lut_bytes = padded * sizeof(float) + packed + (c->d_lut_idx ? padded * sizeof(uint32_t) : 0);  // + the index LUT of the exact scans
     out->source_points_per_face_voxel = (double)c->ns / ((double)g.dx * g.dy + (double)g.dy * g.dz + (double)g.dx * g.dz);
     out->points_per_item = c->chunk_pts;

@@ -34,7 +34,7 @@ struct fgoicp_ctx {
     fgoicp::Dev<float4> d_src;           // ns  x {x,y,z,|p|^2}, Morton order (pristine source, registration.hpp:63)
     fgoicp::Dev<float4> d_tgt;           // nt  x {x,y,z,0}, caller order (registration.hpp:61)
     fgoicp::Dev<float> d_lut;            // (dx+2)(dy+2)(dz+2) floats, x fastest, replicated border
-    int lut_layout = 1;          // 1: d_lut_zp is the z-paired copy (float2), 2: the yz-quad copy (float4), 4: the apron-bricked yz-quads (float4)
+    int lut_layout = 1;          // 1: d_lut_zp is the z-paired copy (float2), 2: the yz-quad copy (float4), 4: the apron-bricked yz-quads (float4), 6: the z-pair apron bricks (float2)
     int source_order = 0, tree_order = 0;  // what ctx_create chose (fgoicp_ctx_get_info)
     fgoicp::Dev<uint32_t> d_lut_idx;        // index LUT (geom.idx): per padded node the caller index of a nearest target point; seeds of the exact scans (FGOICP_LUT_INDEX=0: none)
     fgoicp::Dev<float2> d_lut_zp;        // z-paired copy {T[o], T[o + z-slice]} for the bounds kernel (2x the bytes, half the gathers)

@@ -184,6 +184,34 @@ __global__ __launch_bounds__(kBlock) void lut_quad_apron_kernel(const float* __r
     }
 }
 
+// Z-pair apron copy (FGOICP_LUT_ZPAIR=6): the z-pairs {T[x, y, z], T[x, y, z + 1]} in bricks of 4 x 4 (x, y) at one z, one 128-byte line
+// each, consecutive bricks OVERLAPPING by one x and one y: line (xb, yb, z) = slots x in [3 xb, 3 xb + 3], y in [3 yb, 3 yb + 3], row-major,
+// 4 slots (32 B) per y-row.  A lookup with base voxel (x0, y0, z0) needs the slots of x0, x0 + 1 of rows y0 and y0 + 1: 16 bytes at slot
+// s = (y0 % 3) * 4 + x0 % 3 of line (x0 / 3, y0 / 3, z0) and 16 bytes at s + 4 — ALWAYS one line, which serves a 3 x 3 patch of base
+// voxels: 32 / 9 texels = 14.2 B per node, a third fewer than the apron-bricked quads and fewer than the quad runs.  The two pieces are
+// the z-pair copy's operands {x0z0, x0z1, x1z0, x1z1} of rows y0 and y0 + 1: same texels, same blend, bit-identical values.
+__device__ __forceinline__ unsigned zpair_apron_index(unsigned pk /* x | y << 10 | z << 20 */, unsigned nbx3, unsigned nby3) {  // in float2 slots
+    const unsigned x = pk & 1023u, y = (pk >> 10) & 1023u, z = pk >> 20;
+    const unsigned qx = (x * 43691u) >> 17, qy = (y * 43691u) >> 17;  // x / 3, y / 3 (< 1024)
+    return ((z * nby3 + qy) * nbx3 + qx) * 16u + ((y - 3u * qy) << 2) + (x - 3u * qx);
+}
+__global__ __launch_bounds__(kBlock) void lut_zpair_apron_kernel(const float* __restrict__ lut, LutGeom g, float2* __restrict__ zp) {
+    const unsigned nbx3 = (unsigned)(g.px + 2) / 3u, nby3 = (unsigned)(g.py + 2) / 3u;
+    const size_t slots = (size_t)nbx3 * nby3 * g.pz * 16, total = (size_t)g.px * g.py * g.pz, sz = (size_t)g.px * g.py;
+    for (size_t e = (size_t)blockIdx.x * kBlock + threadIdx.x; e < slots; e += (size_t)gridDim.x * kBlock) {
+        const unsigned s = (unsigned)(e & 15u);
+        const size_t line = e >> 4;
+        const unsigned xb = (unsigned)(line % nbx3), yb = (unsigned)((line / nbx3) % nby3), z = (unsigned)(line / ((size_t)nbx3 * nby3));
+        const unsigned x = 3u * xb + (s & 3u), y = 3u * yb + (s >> 2);
+        float2 v = make_float2(0.f, 0.f);
+        if (x < (unsigned)g.px && y < (unsigned)g.py) {
+            const size_t n = ((size_t)z * g.py + y) * g.px + x;
+            v = make_float2(lut[n], n + sz < total ? lut[n + sz] : lut[n]);  // the last padded slice is never a z0
+        }
+        zp[e] = v;
+    }
+}
+
 __global__ __launch_bounds__(kBlock) void lut_quad_kernel(const float* __restrict__ lut, LutGeom g, float4* __restrict__ qd) {
     const size_t total = (size_t)g.px * g.py * g.pz, sy = (size_t)g.px, sz = (size_t)g.px * g.py;
     for (size_t n = (size_t)blockIdx.x * kBlock + threadIdx.x; n < total; n += (size_t)gridDim.x * kBlock) {
@@ -2147,11 +2175,13 @@ bool launch_bounds_sorted(const float4* src, int ns, const float2* packed, int l
     if (evals) {
         if (layout == 1) launch_item<1, 1>(src, ns, lutp, g, wide, groups, subs, sorted, nchunk, chunk_pts, partials, evals, erow, samp_shift, nitems, sort_err, cut, span, s);
         else if (layout == 2) launch_item<3, 1>(src, ns, lutp, g, wide, groups, subs, sorted, nchunk, chunk_pts, partials, evals, erow, samp_shift, nitems, sort_err, cut, span, s);
-        else launch_item<5, 1>(src, ns, lutp, g, wide, groups, subs, sorted, nchunk, chunk_pts, partials, evals, erow, samp_shift, nitems, sort_err, cut, span, s);
+        else if (layout == 4) launch_item<5, 1>(src, ns, lutp, g, wide, groups, subs, sorted, nchunk, chunk_pts, partials, evals, erow, samp_shift, nitems, sort_err, cut, span, s);
+        else launch_item<6, 1>(src, ns, lutp, g, wide, groups, subs, sorted, nchunk, chunk_pts, partials, evals, erow, samp_shift, nitems, sort_err, cut, span, s);
     } else {
         if (layout == 1) launch_item<1, 0>(src, ns, lutp, g, wide, groups, subs, sorted, nchunk, chunk_pts, partials, evals, erow, samp_shift, nitems, sort_err, cut, span, s);
         else if (layout == 2) launch_item<3, 0>(src, ns, lutp, g, wide, groups, subs, sorted, nchunk, chunk_pts, partials, evals, erow, samp_shift, nitems, sort_err, cut, span, s);
-        else launch_item<5, 0>(src, ns, lutp, g, wide, groups, subs, sorted, nchunk, chunk_pts, partials, evals, erow, samp_shift, nitems, sort_err, cut, span, s);
+        else if (layout == 4) launch_item<5, 0>(src, ns, lutp, g, wide, groups, subs, sorted, nchunk, chunk_pts, partials, evals, erow, samp_shift, nitems, sort_err, cut, span, s);
+        else launch_item<6, 0>(src, ns, lutp, g, wide, groups, subs, sorted, nchunk, chunk_pts, partials, evals, erow, samp_shift, nitems, sort_err, cut, span, s);
     }
     if (ev_stop) (void)hipEventRecord(ev_stop, s);
     return cut.acc && !evals;  // the early exit was in force (trimmed windows carry no thresholds: exact rows)
@@ -2160,9 +2190,15 @@ bool launch_bounds_sorted(const float4* src, int ns, const float2* packed, int l
 // 32-bit texel addressing unless the row number (z * py + y) does not fit the signed 24-bit multiply or the byte offsets of the packed
 // copy do not fit 32 bits (launch_bounds_sorted and the fused kernel of fgoicp_batch)
 bool bounds_lut_wide(const LutGeom& g, int layout) {
-    const size_t nodes = (size_t)g.px * g.py * g.pz;
-    const size_t bytes = layout == 4 ? (size_t)((g.px + 2) / 3) * ((g.py + 1) / 2) * g.pz * 8 * sizeof(float4) : nodes * (layout == 2 ? sizeof(float4) : sizeof(float2));
-    return (size_t)g.py * g.pz > ((size_t)1 << 23) || bytes + 64 > ((size_t)1 << 32);
+    return (size_t)g.py * g.pz > ((size_t)1 << 23) || packed_lut_bytes(g, layout) + 64 > ((size_t)1 << 32);
+}
+
+// bytes of the packed copy of a layout (fgoicp_ctx::lut_layout): whole 128-byte lines for the two apron copies
+size_t packed_lut_bytes(const LutGeom& g, int layout) {
+    const size_t bx = (size_t)(g.px + 2) / 3;
+    if (layout == 4) return bx * (size_t)((g.py + 1) / 2) * g.pz * 128;
+    if (layout == 6) return bx * (size_t)((g.py + 2) / 3) * g.pz * 128;
+    return (size_t)g.px * g.py * g.pz * (layout == 2 ? sizeof(float4) : sizeof(float2));
 }
 
 void launch_fused_bounds(int layout, bool wide, bool quant, const FusedPairView* pairs, const FusedEval* evals, const uint2* items, unsigned nitems, double2* partials,
@@ -2174,7 +2210,8 @@ void launch_fused_bounds(int layout, bool wide, bool quant, const FusedPairView*
                                 else { if (quant) FGOICP_FUSED(L, false, true); else FGOICP_FUSED(L, false, false); } } while (0)
     if (layout == 1) FGOICP_FUSED_WQ(1);
     else if (layout == 2) FGOICP_FUSED_WQ(3);
-    else FGOICP_FUSED_WQ(5);
+    else if (layout == 4) FGOICP_FUSED_WQ(5);
+    else FGOICP_FUSED_WQ(6);
 #undef FGOICP_FUSED_WQ
 #undef FGOICP_FUSED
 }
@@ -2188,7 +2225,8 @@ void launch_fused_trim_bounds(int layout, bool wide, bool quant, const FusedPair
                                 else { if (quant) FGOICP_FUSED(L, false, true); else FGOICP_FUSED(L, false, false); } } while (0)
     if (layout == 1) FGOICP_FUSED_WQ(1);
     else if (layout == 2) FGOICP_FUSED_WQ(3);
-    else FGOICP_FUSED_WQ(5);
+    else if (layout == 4) FGOICP_FUSED_WQ(5);
+    else FGOICP_FUSED_WQ(6);
 #undef FGOICP_FUSED_WQ
 #undef FGOICP_FUSED
 }
@@ -2229,6 +2267,9 @@ void launch_lut_build(const float4* tgt_shifted, int nt, const LutGeom& g, float
 
 void launch_lut_quad_apron(const float* lut_padded, const LutGeom& g, float4* qd, hipStream_t s) {
     hipLaunchKernelGGL(lut_quad_apron_kernel, dim3(4096), dim3(kBlock), 0, s, lut_padded, g, qd);
+}
+void launch_lut_zpair_apron(const float* lut_padded, const LutGeom& g, float2* zp, hipStream_t s) {
+    hipLaunchKernelGGL(lut_zpair_apron_kernel, dim3(4096), dim3(kBlock), 0, s, lut_padded, g, zp);
 }
 void launch_lut_quad(const float* lut_padded, const LutGeom& g, float4* qd, hipStream_t s) {
     hipLaunchKernelGGL(lut_quad_kernel, dim3(8192), dim3(kBlock), 0, s, lut_padded, g, qd);

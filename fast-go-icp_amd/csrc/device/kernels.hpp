@@ -99,7 +99,7 @@ void launch_tick_prefill(const TickSub* subs, int nsub, int nchunk, const TickCu
 void launch_tick_upload(const TickGroup* hd_groups, TickGroup* d_groups, int ngroups, const TickSub* hd_subs, TickSub* d_subs, int nsubs, hipStream_t s);
 // Returns true if the early exit was in force: the window carried thresholds and is untrimmed (trimmed windows carry none, so trimmed
 // contexts are the only case where fgoicp_bounds_submit_cut returns exact rows above the threshold).
-bool launch_bounds_sorted(const float4* src, int ns, const float2* packed, int layout /* 1 z-pair, 2 yz-quad, 4 apron-bricked yz-quad */, const LutGeom& g,
+bool launch_bounds_sorted(const float4* src, int ns, const float2* packed, int layout /* 1 z-pair, 2 yz-quad, 4 apron-bricked yz-quad, 6 z-pair apron */, const LutGeom& g,
                           int nchunk, int chunk_pts /* 256 .. 2048 points per item */, const TickGroup* groups, const TickSub* subs, int nsub, const unsigned* sorted,
                           double2* partials, float* evals_or_null /* trimmed mode: row r = the per-point e = max(d, 0) of output row r */, size_t erow /* floats per row, multiple of 4 */,
                           int samp_shift /* trimmed mode: > 0 = every 2^samp_shift-th point once more in the sample behind the row (offset: ns rounded up to 64 floats) */,
@@ -215,7 +215,8 @@ struct FusedTrimRow {
     int out;
 };
 bool bounds_lut_wide(const LutGeom& g, int layout);
-// layout: fgoicp_ctx::lut_layout (1, 2, 4) of EVERY pair the items belong to; wide = bounds_lut_wide, quant = g.quantize, alike for all of them
+size_t packed_lut_bytes(const LutGeom& g, int layout);  // of the packed copy alone
+// layout: fgoicp_ctx::lut_layout (1, 2, 4, 6) of EVERY pair the items belong to; wide = bounds_lut_wide, quant = g.quantize, alike for all of them
 void launch_fused_bounds(int layout, bool wide, bool quant, const FusedPairView* pairs, const FusedEval* evals, const uint2* items, unsigned nitems, double2* partials,
                          hipStream_t s);
 void launch_fused_finalize(const FusedEval* evals, int nevals, const double2* partials, float* out_lb, float* out_ub, hipStream_t s);
@@ -232,6 +233,7 @@ void launch_lut_build(const float4* tgt_shifted, int nt, const LutGeom& g, float
 void launch_lut_zpair(const float* lut_padded, const LutGeom& g, float2* zp, hipStream_t s);
 void launch_lut_quad(const float* lut_padded, const LutGeom& g, float4* qd, hipStream_t s);
 void launch_lut_quad_apron(const float* lut_padded, const LutGeom& g, float4* qd /* ceil(px/3)*ceil(py/2)*pz*8 quads */, hipStream_t s);
+void launch_lut_zpair_apron(const float* lut_padded, const LutGeom& g, float2* zp /* ceil(px/3)*ceil(py/3)*pz*16 z-pairs */, hipStream_t s);
 void launch_lut_unpad(const float* lut_padded, const LutGeom& g, float* out, hipStream_t s);
 void launch_lut_search(const float* lut, const LutGeom& g, const float* q_xyz, size_t n, float* out, hipStream_t s);
 void launch_lut_nodes(const float* lut_padded, const LutGeom& g, const int* xyz /* device, n node indices (clamped into the grid) */, size_t n, float* out, hipStream_t s);

@@ -503,7 +503,7 @@ class Registration:
 
     def info(self):
         """fgoicp_ctx_get_info: LUT size and layout, source density per LUT face voxel, points per work item (what the context
-        derived from the clouds' statistics)."""
+        derived from the clouds' statistics).  lut_layout: 1 z-pairs, 2 yz-quad runs, 4 apron-bricked yz-quads, 6 z-pair apron bricks."""
         i = _lib.CtxInfo()
         i.struct_size = C.sizeof(_lib.CtxInfo)
         _lib.check(self._lib.fgoicp_ctx_get_info(self._h, C.byref(i)), "fgoicp_ctx_get_info")

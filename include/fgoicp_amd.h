@@ -86,7 +86,8 @@ typedef struct fgoicp_ctx_info {
     size_t struct_size;          /* IN: sizeof(fgoicp_ctx_info) as the CALLER was compiled (ABI 2).  fgoicp_ctx_get_info writes no byte beyond it, so a caller
                                     built against an older, shorter struct is not overrun when members are appended; 0 is refused */
     int lut_dims[3];
-    int lut_layout;              /* next to the plain fp32 LUT: 1 = z-pair copy (8 B per node), 2 = yz-quad copy (16 B per node), 4 = apron-bricked yz-quad copy (21.3 B per node) */
+    int lut_layout;              /* next to the plain fp32 LUT: 1 = z-pair copy (8 B per node), 2 = yz-quad copy (16 B per node), 4 = apron-bricked yz-quad copy (21.3 B per node),
+                                    6 = z-pair apron bricks (14.2 B per node; sparse clouds whose quad copy would exceed 256 MiB) */
     uint64_t lut_nodes;
     uint64_t lut_bytes;          /* plain LUT (padded) + packed copy, device memory */
     double source_points_per_face_voxel;
