@@ -361,51 +361,36 @@ int main(int argc, char* argv[]) {
     auto refine = [&](fgoicp_solver* s) {
         if (config.params.refine != "plane" && !gicp) return;
         refined.struct_size = sizeof(refined);
-        const float d = config.params.refine_distance;
+        const float d = config.params.refine_distance > 0.0f ? config.params.refine_distance : INFINITY;
+        const int knn = config.params.refine_knn;
+        const size_t max_iter = (size_t)config.params.refine_max_iter;
         if (loss > 0) {
             robust.struct_size = sizeof(robust);
-            icp::check_status(fgoicp_solver_refine_robust(s, gicp ? FGOICP_MODEL_GICP : FGOICP_MODEL_PLANE, config.params.refine_knn, (size_t)config.params.refine_max_iter,
-                                                          1e-6f, d > 0.0f ? d : INFINITY, config.params.refine_epsilon, loss, config.params.refine_loss_scale, &robust),
-                              "fgoicp_solver_refine_robust");
+            icp::check_status(fgoicp_solver_refine_robust(s, gicp ? FGOICP_MODEL_GICP : FGOICP_MODEL_PLANE, knn, max_iter, 1e-6f, d, config.params.refine_epsilon, loss,
+                                                          config.params.refine_loss_scale, &robust), "fgoicp_solver_refine_robust");
             std::memcpy(refined.R, robust.R, sizeof(refined.R));
             std::memcpy(refined.t, robust.t, sizeof(refined.t));
             refined.iterations = robust.iterations; refined.rank = robust.rank; refined.correspondences = robust.correspondences;
             refined.plane_rmse = robust.rmse; refined.sse = robust.sse; refined.scaling_factor = robust.scaling_factor;
-            have_refined = have_robust = true;
-            icp::mat3 Rr;
-            std::memcpy(Rr.data(), refined.R, sizeof(refined.R));
-            std::ostringstream head;
-            if (gicp)
-                head << "Generalized-ICP refinement: " << refined.iterations << " iterations, rank " << refined.rank << ", " << refined.correspondences
-                     << " correspondences, epsilon " << config.params.refine_epsilon << ", plane-to-plane RMSE " << refined.plane_rmse / (double)refined.scaling_factor;
-            else
-                head << "Point-to-plane refinement: " << refined.iterations << " iterations, rank " << refined.rank << ", " << refined.correspondences
-                     << " correspondences, plane RMSE " << refined.plane_rmse / (double)refined.scaling_factor;
-            icp::Logger(icp::LogLevel::Info) << head.str() << ", " << config.params.refine_loss << " loss, scale " << robust.scale / (double)robust.scaling_factor
-                                             << (robust.scale_estimated ? " (estimated)" : " (given)") << ", weight " << robust.weight_sum << " of " << robust.correspondences
-                                             << "\n\tRotation:\n" << Rr << "\n\tTranslation: " << icp::vec3{refined.t[0], refined.t[1], refined.t[2]};
-            return;
+            have_robust = true;
+        } else if (gicp) {
+            icp::check_status(fgoicp_solver_refine_gicp(s, knn, max_iter, 1e-6f, d, config.params.refine_epsilon, &refined), "fgoicp_solver_refine_gicp");
+        } else {
+            icp::check_status(fgoicp_solver_refine_plane(s, knn, max_iter, 1e-6f, d, &refined), "fgoicp_solver_refine_plane");
         }
-        if (gicp) {
-            icp::check_status(fgoicp_solver_refine_gicp(s, config.params.refine_knn, (size_t)config.params.refine_max_iter, 1e-6f, d > 0.0f ? d : INFINITY,
-                                                        config.params.refine_epsilon, &refined), "fgoicp_solver_refine_gicp");
-            have_refined = true;
-            icp::mat3 Rr;
-            std::memcpy(Rr.data(), refined.R, sizeof(refined.R));
-            icp::Logger(icp::LogLevel::Info) << "Generalized-ICP refinement: " << refined.iterations << " iterations, rank " << refined.rank << ", " << refined.correspondences
-                                             << " correspondences, epsilon " << config.params.refine_epsilon << ", plane-to-plane RMSE "
-                                             << refined.plane_rmse / (double)refined.scaling_factor << "\n\tRotation:\n" << Rr
-                                             << "\n\tTranslation: " << icp::vec3{refined.t[0], refined.t[1], refined.t[2]};
-            return;
-        }
-        icp::check_status(fgoicp_solver_refine_plane(s, config.params.refine_knn, (size_t)config.params.refine_max_iter, 1e-6f, d > 0.0f ? d : INFINITY, &refined),
-                          "fgoicp_solver_refine_plane");
         have_refined = true;
         icp::mat3 Rr;
         std::memcpy(Rr.data(), refined.R, sizeof(refined.R));
-        icp::Logger(icp::LogLevel::Info) << "Point-to-plane refinement: " << refined.iterations << " iterations, rank " << refined.rank << ", " << refined.correspondences
-                                         << " correspondences, plane RMSE " << refined.plane_rmse / (double)refined.scaling_factor << "\n\tRotation:\n" << Rr
-                                         << "\n\tTranslation: " << icp::vec3{refined.t[0], refined.t[1], refined.t[2]};
+        icp::Logger log(icp::LogLevel::Info);
+        log << (gicp ? "Generalized-ICP" : "Point-to-plane") << " refinement: " << refined.iterations << " iterations, rank " << refined.rank << ", "
+            << refined.correspondences << " correspondences, ";
+        if (gicp) log << "epsilon " << config.params.refine_epsilon << ", plane-to-plane RMSE ";
+        else log << "plane RMSE ";
+        log << refined.plane_rmse / (double)refined.scaling_factor;
+        if (have_robust)
+            log << ", " << config.params.refine_loss << " loss, scale " << robust.scale / (double)robust.scaling_factor << (robust.scale_estimated ? " (estimated)" : " (given)")
+                << ", weight " << robust.weight_sum << " of " << robust.correspondences;
+        log << "\n\tRotation:\n" << Rr << "\n\tTranslation: " << icp::vec3{refined.t[0], refined.t[1], refined.t[2]};
     };
     // io.information: the information matrix in the files' frame — at the best transform, or at the refined pose when there is one: then
     // from the context at that pose in the solver's frame (the restored translation taken back, t_s = (t - R offset_pcs + offset_pct) * scale)

@@ -721,109 +721,32 @@ int ctx_target_knn(fgoicp_ctx* c, int k, uint32_t* idx, float* d2) {
     return FGOICP_OK;
 }
 
-// EXTENSION: the point-to-plane normal equations at (R, t) (fgoicp_plane_moments), enqueued behind the report's device half on lane 0's
-// stream like the information moments: reads the report's arrays, the moved queries the index scan left in d_work, the target and its
-// normals; writes its own rows only.
-// gicp: the Generalized-ICP normal equations (launch_gicp_moments) in place of the point-to-plane ones; everything else is shared
-static int moments_at(fgoicp_ctx* c, const float* R9, const float* t3, float max_dist2, bool gicp, double epsilon, PlaneMoments* m, float* sse_out) {
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(c->d_plane_rows.ensure((c->ns + kBlock - 1) / kBlock));
-    HIPCHK(c->d_plane_out.ensure(1 + kPlaneTerms));
-    const int rc = alignment_enqueue(c, R9, t3, true);
-    if (rc) return rc;
-    fgoicp_ctx::IcpLane& L = c->lanes[0];
-    fgoicp_ctx::AlignScratch& A = c->align;
-    if (gicp)
-        launch_gicp_moments(L.d_work, c->d_orig_of_slot, A.d_inl, A.d_d2, A.d_corr, c->d_tgt, c->d_normals, c->d_src_normals, R9, epsilon, (int)c->ns, (int)c->nt, max_dist2,
-                            c->d_plane_rows, c->d_plane_out, L.stream);
-    else
-        launch_plane_moments(L.d_work, c->d_orig_of_slot, A.d_inl, A.d_d2, A.d_corr, c->d_tgt, c->d_normals, (int)c->ns, (int)c->nt, max_dist2, c->d_plane_rows, c->d_plane_out,
-                             L.stream);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(L.stream));
-    unsigned long long h[1 + kPlaneTerms];
-    HIPCHK(hipMemcpy(h, c->d_plane_out, sizeof(h), hipMemcpyDeviceToHost));
-    static_assert(kPlaneTerms == kPlaneMoments, "the device's row and the host's moments are the same 28 terms");
-    m->n = h[0];
-    std::memcpy(m->m, h + 1, sizeof(m->m));
-    if (sse_out) *sse_out = sse_result(c, L);
-    return FGOICP_OK;
-}
-int ctx_plane_moments(fgoicp_ctx* c, const float* R9, const float* t3, float max_dist2, PlaneMoments* m, float* sse_out) {
-    if (!c->normals_set) { set_error("the target normals are not set: call fgoicp_ctx_set_target_normals first"); return FGOICP_ERR_INVALID_ARG; }
-    return moments_at(c, R9, t3, max_dist2, false, 0.0, m, sse_out);
-}
-int ctx_gicp_moments(fgoicp_ctx* c, const float* R9, const float* t3, float max_dist2, double epsilon, PlaneMoments* m, float* sse_out) {
-    if (!c->normals_set) { set_error("the target normals are not set: call fgoicp_ctx_set_target_normals first"); return FGOICP_ERR_INVALID_ARG; }
-    if (!c->src_normals_set) { set_error("the source normals are not set: call fgoicp_ctx_set_source_normals first"); return FGOICP_ERR_INVALID_ARG; }
-    if (!gicp_epsilon_ok(epsilon)) { set_error("epsilon must be finite and lie in (0, 1]"); return FGOICP_ERR_INVALID_ARG; }
-    return moments_at(c, R9, t3, max_dist2, true, epsilon, m, sse_out);
-}
-
-// fgoicp_icp_plane, fgoicp_icp_gicp: evaluate, solve, update (plane.hpp), until the step is short, the first solve is rank-deficient,
-// nothing is counted or max_iter steps are done; the result's count, rmse and sse are those of one more evaluation at the pose returned.
-template <class Eval>
-static int moments_loop(const char* where, Eval eval, const float* R0, const float* t0, size_t max_iter, float thr, fgoicp_plane_result_t* full) {
-    Mat3f R = Mat3f::from(R0);
-    Vec3f t{t0[0], t0[1], t0[2]};
-    PlaneMoments m;
-    float sse = 0.f;
-    int iters = 0, rank = 0;
-    bool stop = false;
-    for (;;) {
-        const float t3[3] = {t.x, t.y, t.z};
-        const int rc = eval(R.m, t3, &m, &sse);
-        if (rc) return rc;
-        if (stop || (size_t)iters >= max_iter || m.n == 0) break;
-        if (!plane_moments_finite(m.m)) { set_error(std::string(where) + ": the normal equations are not finite"); return FGOICP_ERR_INVALID_ARG; }
-        double xi[6];
-        plane_step(m.m, xi, &rank);
-        plane_apply_step(R, t, xi, R, t);
-        ++iters;
-        const double step = std::sqrt(xi[0] * xi[0] + xi[1] * xi[1] + xi[2] * xi[2]) + std::sqrt(xi[3] * xi[3] + xi[4] * xi[4] + xi[5] * xi[5]);
-        stop = step < (double)thr || (iters == 1 && rank < 6);  // one more evaluation, at the pose returned, then out
-    }
-    std::memset(full, 0, sizeof(*full));  // the padding too: two results of the same inputs are the same bytes
-    full->struct_size = (uint32_t)sizeof(*full);
-    std::memcpy(full->R, R.m, sizeof(R.m));
-    full->t[0] = t.x; full->t[1] = t.y; full->t[2] = t.z;
-    full->iterations = iters;
-    full->rank = rank;
-    full->correspondences = m.n;
-    full->plane_rmse = m.n ? std::sqrt(m.m[27] / (double)m.n) : 0.0;
-    full->sse = sse;
-    full->scaling_factor = 1.0f;
-    return FGOICP_OK;
-}
-int ctx_icp_plane(fgoicp_ctx* c, const float* R0, const float* t0, size_t max_iter, float thr, float max_dist2, fgoicp_plane_result_t* full) {
-    return moments_loop("fgoicp_icp_plane", [&](const float* R9, const float* t3, PlaneMoments* m, float* sse) { return ctx_plane_moments(c, R9, t3, max_dist2, m, sse); }, R0, t0,
-                        max_iter, thr, full);
-}
-int ctx_icp_gicp(fgoicp_ctx* c, const float* R0, const float* t0, size_t max_iter, float thr, float max_dist2, double epsilon, fgoicp_plane_result_t* full) {
-    return moments_loop("fgoicp_icp_gicp", [&](const float* R9, const float* t3, PlaneMoments* m, float* sse) { return ctx_gicp_moments(c, R9, t3, max_dist2, epsilon, m, sse); },
-                        R0, t0, max_iter, thr, full);
-}
-
-// EXTENSION: robust losses (fgoicp_robust_*, fgoicp_icp_robust).  moments_at with launch_robust_moments in place of
-// the plain launch, over rows and an output of its own; the per-point outputs are stored by the kernel only when a caller asks.
-int robust_refusals(const fgoicp_ctx* c, const RobustSpec& r, bool need_scale, const char* where) {
+// EXTENSION: the refinements (fgoicp_plane_moments, fgoicp_gicp_moments, fgoicp_robust_*, the three loops; DESIGN.md sections 12, 15, 19).
+// What every one of their context entry points refuses before any device work, in this order (each only where it applies):
+//   the scale is not finite (ScaleCheck::or_estimated); max_dist2; the model; the loss; epsilon (Generalized ICP); the scale is not finite
+//   and > 0 (ScaleCheck::given, a loss other than none); the target normals; the source normals (Generalized ICP)
+int refine_refusals(const fgoicp_ctx* c, const RefineSpec& r, ScaleCheck scale, const char* where) {
     const std::string w(where);
+    if (scale == ScaleCheck::or_estimated && !std::isfinite(r.scale)) { set_error(w + ": the scale must be finite (<= 0: estimated)"); return FGOICP_ERR_INVALID_ARG; }
     if (!(r.max_dist2 >= 0.0f)) { set_error(w + ": max_dist2 must be >= 0 (+inf: no threshold)"); return FGOICP_ERR_INVALID_ARG; }
     if (!robust_model_ok(r.model)) { set_error(w + ": unknown model " + std::to_string(r.model) + " (0: point-to-plane, 1: Generalized ICP)"); return FGOICP_ERR_INVALID_ARG; }
     if (!robust_loss_ok(r.loss)) { set_error(w + ": unknown loss " + std::to_string(r.loss)); return FGOICP_ERR_INVALID_ARG; }
     if (r.model == FGOICP_MODEL_GICP && !gicp_epsilon_ok(r.epsilon)) { set_error(w + ": epsilon must be finite and lie in (0, 1]"); return FGOICP_ERR_INVALID_ARG; }
-    if (need_scale && r.loss != FGOICP_LOSS_NONE && !robust_scale_ok(r.scale)) { set_error(w + ": the scale must be finite and > 0"); return FGOICP_ERR_INVALID_ARG; }
+    if (scale == ScaleCheck::given && r.loss != FGOICP_LOSS_NONE && !robust_scale_ok(r.scale)) { set_error(w + ": the scale must be finite and > 0"); return FGOICP_ERR_INVALID_ARG; }
     if (!c->normals_set) { set_error(w + ": the target normals are not set: call fgoicp_ctx_set_target_normals first"); return FGOICP_ERR_INVALID_ARG; }
     if (r.model == FGOICP_MODEL_GICP && !c->src_normals_set) { set_error(w + ": the source normals are not set: call fgoicp_ctx_set_source_normals first"); return FGOICP_ERR_INVALID_ARG; }
     return FGOICP_OK;
 }
-int ctx_robust_moments(fgoicp_ctx* c, const float* R9, const float* t3, const RobustSpec& r, RobustMoments* m, float* sse_out, double* residual, double* weight,
-                       unsigned char* counted) {
+// One evaluation at (R, t), enqueued behind the report's device half on lane 0's stream like the information moments: reads the report's
+// arrays, the moved queries the index scan left in d_work, the target and the normals; writes its own rows only.  The per-point outputs
+// are stored by the kernel only when a caller asks.
+int refine_evaluate(fgoicp_ctx* c, const float* R9, const float* t3, const RefineSpec& r, RefineMoments* m, float* sse_out, double* residual, double* weight,
+                    unsigned char* counted) {
     const bool per_point = residual || weight || counted;
-    const size_t ns = c->ns;
+    const size_t ns = c->ns, nb = (ns + kBlock - 1) / kBlock;
     HIPCHK(hipSetDevice(c->device));
-    HIPCHK(c->d_robust_rows.ensure((ns + kBlock - 1) / kBlock));
-    HIPCHK(c->d_robust_out.ensure(1 + kRobustTerms));
+    HIPCHK(r.weighted ? c->d_robust_rows.ensure(nb) : c->d_plane_rows.ensure(nb));
+    HIPCHK(c->d_refine_out.ensure(1 + kRobustTerms));
     if (per_point) {
         HIPCHK(c->d_robust_point.ensure(2 * ns));
         HIPCHK(c->d_robust_counted.ensure(ns));
@@ -832,30 +755,37 @@ int ctx_robust_moments(fgoicp_ctx* c, const float* R9, const float* t3, const Ro
     if (rc) return rc;
     fgoicp_ctx::IcpLane& L = c->lanes[0];
     fgoicp_ctx::AlignScratch& A = c->align;
+    const RefineInputs in{L.d_work, c->d_orig_of_slot, A.d_inl, A.d_d2, A.d_corr, c->d_tgt, c->d_normals, c->d_src_normals, (int)ns, (int)c->nt, r.max_dist2};
+    const bool gicp = r.model == FGOICP_MODEL_GICP;
     double* const d_res = per_point ? (double*)c->d_robust_point : nullptr;
-    launch_robust_moments(r.model == FGOICP_MODEL_GICP, L.d_work, c->d_orig_of_slot, A.d_inl, A.d_d2, A.d_corr, c->d_tgt, c->d_normals, c->d_src_normals, R9, r.epsilon, r.loss,
-                          r.loss == FGOICP_LOSS_NONE ? 1.0 : r.scale, (int)ns, (int)c->nt, r.max_dist2, c->d_robust_rows, c->d_robust_out, d_res, per_point ? d_res + ns : nullptr,
-                          per_point ? (unsigned char*)c->d_robust_counted : nullptr, L.stream);
+    if (r.weighted)
+        launch_refine_moments<kRobustTerms>(in, gicp, R9, r.epsilon, r.loss, r.loss == FGOICP_LOSS_NONE ? 1.0 : r.scale, c->d_robust_rows, c->d_refine_out, d_res,
+                                            per_point ? d_res + ns : nullptr, per_point ? (unsigned char*)c->d_robust_counted : nullptr, L.stream);
+    else
+        launch_refine_moments<kPlaneTerms>(in, gicp, R9, r.epsilon, FGOICP_LOSS_NONE, 1.0, c->d_plane_rows, c->d_refine_out, nullptr, nullptr, nullptr, L.stream);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(L.stream));
+    static_assert(kRobustTerms == kRobustMoments && kPlaneTerms == kPlaneMoments && kRobustTerms == kPlaneTerms + 1, "the device's rows and the host's moments are the same terms");
+    const size_t K = r.weighted ? kRobustTerms : kPlaneTerms;
     unsigned long long h[1 + kRobustTerms];
-    HIPCHK(hipMemcpy(h, c->d_robust_out, sizeof(h), hipMemcpyDeviceToHost));
-    static_assert(kRobustTerms == kRobustMoments && kRobustTerms == kPlaneMoments + 1, "the device's row and the host's moments are the same 29 terms");
+    HIPCHK(hipMemcpy(h, c->d_refine_out, sizeof(h[0]) * (1 + K), hipMemcpyDeviceToHost));
     m->n = h[0];
-    std::memcpy(m->m, h + 1, sizeof(m->m));
+    std::memcpy(m->m, h + 1, sizeof(double) * K);
+    if (!r.weighted) m->m[kPlaneMoments] = (double)m->n;  // every counted pair weighs 1
     if (residual) HIPCHK(hipMemcpy(residual, d_res, sizeof(double) * ns, hipMemcpyDeviceToHost));
     if (weight) HIPCHK(hipMemcpy(weight, d_res + ns, sizeof(double) * ns, hipMemcpyDeviceToHost));
     if (counted) HIPCHK(hipMemcpy(counted, c->d_robust_counted, ns, hipMemcpyDeviceToHost));
     if (sse_out) *sse_out = sse_result(c, L);
     return FGOICP_OK;
 }
-int ctx_robust_scale(fgoicp_ctx* c, const float* R9, const float* t3, const RobustSpec& r, double* scale, const char* where) {
-    RobustSpec plain = r;
+int ctx_robust_scale(fgoicp_ctx* c, const float* R9, const float* t3, const RefineSpec& r, double* scale, const char* where) {
+    RefineSpec plain = r;
+    plain.weighted = true;  // the kernel with the per-point stores
     plain.loss = FGOICP_LOSS_NONE;
     std::vector<double> res(c->ns);
     std::vector<unsigned char> cnt(c->ns);
-    RobustMoments m;
-    const int rc = ctx_robust_moments(c, R9, t3, plain, &m, nullptr, res.data(), nullptr, cnt.data());
+    RefineMoments m;
+    const int rc = refine_evaluate(c, R9, t3, plain, &m, nullptr, res.data(), nullptr, cnt.data());
     if (rc) return rc;
     double s = 0.0;
     if (!robust_mad_scale(res.data(), cnt.data(), c->ns, &s)) { set_error(std::string(where) + ": nothing is counted at this pose, there is no scale to estimate: pass a scale"); return FGOICP_ERR_INVALID_ARG; }
@@ -863,51 +793,64 @@ int ctx_robust_scale(fgoicp_ctx* c, const float* R9, const float* t3, const Robu
     *scale = s;
     return FGOICP_OK;
 }
-// moments_loop, term for term, over ctx_robust_moments: a weight sum of 0 ends it like a count of 0
-int ctx_icp_robust(fgoicp_ctx* c, const float* R0, const float* t0, size_t max_iter, float thr, RobustSpec r, fgoicp_robust_result_t* full, const char* where) {
-    int estimated = 0;
-    if (r.loss != FGOICP_LOSS_NONE && !(r.scale > 0.0)) {
-        const int rc = ctx_robust_scale(c, R0, t0, r, &r.scale, where);
+
+// fgoicp_icp_plane, fgoicp_icp_gicp, fgoicp_icp_robust: evaluate, solve, update (plane.hpp), until the step is short, the first solve is
+// rank-deficient, nothing is counted, the weights sum to 0 or max_iter steps are done; the end's moments and sse are those of one more
+// evaluation at the pose returned.  A weighted loss without a scale > 0: estimated at (R0, t0) first.
+int refine_loop(fgoicp_ctx* c, const float* R0, const float* t0, size_t max_iter, float thr, const RefineSpec& spec, const char* where, RefineEnd* end) {
+    RefineEnd e;
+    e.spec = spec;
+    if (spec.weighted && spec.loss != FGOICP_LOSS_NONE && !(spec.scale > 0.0)) {
+        const int rc = ctx_robust_scale(c, R0, t0, spec, &e.spec.scale, where);
         if (rc) return rc;
-        estimated = 1;
+        e.scale_estimated = 1;
     }
-    Mat3f R = Mat3f::from(R0);
-    Vec3f t{t0[0], t0[1], t0[2]};
-    RobustMoments m;
-    float sse = 0.f;
-    int iters = 0, rank = 0;
+    e.R = Mat3f::from(R0);
+    e.t = Vec3f{t0[0], t0[1], t0[2]};
     bool stop = false;
     for (;;) {
-        const float t3[3] = {t.x, t.y, t.z};
-        const int rc = ctx_robust_moments(c, R.m, t3, r, &m, &sse);
+        const float t3[3] = {e.t.x, e.t.y, e.t.z};
+        const int rc = refine_evaluate(c, e.R.m, t3, e.spec, &e.m, &e.sse);
         if (rc) return rc;
-        if (stop || (size_t)iters >= max_iter || m.n == 0 || m.m[28] == 0.0) break;
-        if (!plane_moments_finite(m.m) || !std::isfinite(m.m[28])) { set_error(std::string(where) + ": the normal equations are not finite"); return FGOICP_ERR_INVALID_ARG; }
+        if (stop || (size_t)e.iterations >= max_iter || e.m.n == 0 || e.m.m[28] == 0.0) break;
+        if (!plane_moments_finite(e.m.m) || !std::isfinite(e.m.m[28])) { set_error(std::string(where) + ": the normal equations are not finite"); return FGOICP_ERR_INVALID_ARG; }
         double xi[6];
-        plane_step(m.m, xi, &rank);
-        plane_apply_step(R, t, xi, R, t);
-        ++iters;
+        plane_step(e.m.m, xi, &e.rank);
+        plane_apply_step(e.R, e.t, xi, e.R, e.t);
+        ++e.iterations;
         const double step = std::sqrt(xi[0] * xi[0] + xi[1] * xi[1] + xi[2] * xi[2]) + std::sqrt(xi[3] * xi[3] + xi[4] * xi[4] + xi[5] * xi[5]);
-        stop = step < (double)thr || (iters == 1 && rank < 6);  // one more evaluation, at the pose returned, then out
+        stop = step < (double)thr || (e.iterations == 1 && e.rank < 6);  // one more evaluation, at the pose returned, then out
     }
-    std::memset(full, 0, sizeof(*full));  // the padding too: two results of the same inputs are the same bytes
-    full->struct_size = (uint32_t)sizeof(*full);
-    std::memcpy(full->R, R.m, sizeof(R.m));
-    full->t[0] = t.x; full->t[1] = t.y; full->t[2] = t.z;
-    full->iterations = iters;
-    full->rank = rank;
-    full->correspondences = m.n;
-    full->weight_sum = m.m[28];
-    full->rmse = m.m[28] > 0.0 ? std::sqrt(m.m[27] / m.m[28]) : 0.0;
-    full->sse = sse;
-    full->scaling_factor = 1.0f;
-    full->loss = r.loss;
-    full->scale_estimated = estimated;
-    full->scale = r.loss == FGOICP_LOSS_NONE ? 0.0 : r.scale;
+    *end = e;
     return FGOICP_OK;
 }
+// what fgoicp_plane_result_t and fgoicp_robust_result_t share
+template <class Result>
+static void refine_result_head(const RefineEnd& e, Result* full) {
+    std::memset(full, 0, sizeof(*full));  // the padding too: two results of the same inputs are the same bytes
+    full->struct_size = (uint32_t)sizeof(*full);
+    std::memcpy(full->R, e.R.m, sizeof(e.R.m));
+    full->t[0] = e.t.x; full->t[1] = e.t.y; full->t[2] = e.t.z;
+    full->iterations = e.iterations;
+    full->rank = e.rank;
+    full->correspondences = e.m.n;
+    full->sse = e.sse;
+    full->scaling_factor = 1.0f;
+}
+void refine_result(const RefineEnd& e, fgoicp_plane_result_t* full) {
+    refine_result_head(e, full);
+    full->plane_rmse = e.m.n ? std::sqrt(e.m.m[27] / (double)e.m.n) : 0.0;
+}
+void refine_result(const RefineEnd& e, fgoicp_robust_result_t* full) {
+    refine_result_head(e, full);
+    full->weight_sum = e.m.m[28];
+    full->rmse = e.m.m[28] > 0.0 ? std::sqrt(e.m.m[27] / e.m.m[28]) : 0.0;
+    full->loss = e.spec.loss;
+    full->scale_estimated = e.scale_estimated;
+    full->scale = e.spec.loss == FGOICP_LOSS_NONE ? 0.0 : e.spec.scale;
+}
 
-// EXTENSION: source normals (fgoicp_ctx_set_source_normals), kept in device slot order for gicp_moments_kernel.  Given: checked and
+// EXTENSION: source normals (fgoicp_ctx_set_source_normals), kept in device slot order for refine_moments_kernel.  Given: checked and
 // normalised on the host (fp64) as the target's, permuted, uploaded.  Estimated: the rule of the target's normals over the source itself —
 // a caller-order float4 copy of the source as the context holds it, a throw-away tree over it (bvh_build_host), one launch of
 // target_knn_kernel, the result moved from caller order into slot order; tree, copy and caller-order normals are freed before the call returns.
@@ -1794,6 +1737,64 @@ static int lut_query(fgoicp_ctx* c, const T* q, size_t n, float* out, Launch lau
 
 using namespace fgoicp;
 
+// The refinements' entry points on the context.  Each refuses, before any device work: a null context, R or t (fgoicp_robust_scale: or
+// scale), a bad out->struct_size, then refine_refusals' list, of which
+//   fgoicp_plane_moments, fgoicp_icp_plane          max_dist2, the target normals
+//   fgoicp_gicp_moments, fgoicp_icp_gicp            max_dist2, epsilon, the target normals, the source normals
+//   fgoicp_robust_moments, fgoicp_robust_residuals  max_dist2, the model, the loss, epsilon (Generalized ICP), the scale (finite and > 0,
+//                                                   a loss other than none), the target normals, the source normals (Generalized ICP)
+//   fgoicp_robust_scale                             the same without the loss and the scale
+//   fgoicp_icp_robust                               the scale (finite) first, then fgoicp_robust_moments' list without its scale
+// apply (the plain calls' model and loss are always good ones).  fgoicp_robust_residuals has no out struct.
+static RefineSpec refine_spec(bool weighted, float max_dist2, int model, double epsilon, int loss, double scale) {
+    RefineSpec r;
+    r.weighted = weighted; r.model = model; r.epsilon = epsilon; r.loss = loss; r.scale = scale; r.max_dist2 = max_dist2;  // a scale that does not matter is carried as given
+    return r;
+}
+// fgoicp_plane_moments_t, or the fields fgoicp_robust_moments_t shares with it
+template <class Moments>
+static int refine_moments_call(fgoicp_ctx* c, const float* R9, const float* t3, const RefineSpec& r, const char* where, RefineMoments* m, Moments* full) {
+    int rc = refine_refusals(c, r, ScaleCheck::given, where);
+    if (rc) return rc;
+    rc = refine_evaluate(c, R9, t3, r, m);
+    if (rc) return rc;
+    std::memset(full, 0, sizeof(*full));  // the padding too: two results of the same inputs are the same bytes
+    full->struct_size = (uint32_t)sizeof(*full);
+    full->points = c->ns;
+    full->correspondences = m->n;
+    std::memcpy(full->m, m->m, sizeof(full->m));
+    full->max_dist2 = r.max_dist2;
+    return FGOICP_OK;
+}
+static int plain_moments_call(fgoicp_ctx* c, const float* R9, const float* t3, const RefineSpec& r, const char* where, fgoicp_plane_moments_t* out) {
+    const std::string w(where);
+    if (!c || !R9 || !t3) { set_error(w + ": the context, R and t must not be null"); return FGOICP_ERR_INVALID_ARG; }
+    if (!plane_size_ok(out)) { set_error(w + ": out must not be null and out->struct_size = sizeof(fgoicp_plane_moments_t)"); return FGOICP_ERR_INVALID_ARG; }
+    return fgoicp::abi_guard(where, [&] {
+        RefineMoments m;
+        fgoicp_plane_moments_t full;
+        const int rc = refine_moments_call(c, R9, t3, r, where, &m, &full);
+        return rc ? rc : plane_out(full, out, where, "fgoicp_plane_moments_t");
+    });
+}
+template <class Result>
+static int refine_loop_call(fgoicp_ctx* c, const float* R0, const float* t0, size_t max_iter, float conv_thr, const RefineSpec& r, const char* where, const char* type,
+                            Result* out) {
+    const std::string w(where);
+    if (!c || !R0 || !t0) { set_error(w + ": the context, R0 and t0 must not be null"); return FGOICP_ERR_INVALID_ARG; }
+    if (!plane_size_ok(out)) { set_error(w + ": out must not be null and out->struct_size = sizeof(" + type + ")"); return FGOICP_ERR_INVALID_ARG; }
+    return fgoicp::abi_guard(where, [&] {
+        int rc = refine_refusals(c, r, r.weighted ? ScaleCheck::or_estimated : ScaleCheck::none, where);
+        if (rc) return rc;
+        RefineEnd end;
+        rc = refine_loop(c, R0, t0, max_iter, conv_thr, r, where, &end);
+        if (rc) return rc;
+        Result full;
+        refine_result(end, &full);
+        return plane_out(full, out, where, type);
+    });
+}
+
 extern "C" {
 
 const char* fgoicp_last_error(void) { return g_last_error.c_str(); }
@@ -2075,32 +2076,6 @@ int fgoicp_target_knn(fgoicp_ctx* c, int k, uint32_t* idx_ntk, float* d2_ntk) {
     if (!c) { set_error("fgoicp_target_knn: the context must not be null"); return FGOICP_ERR_INVALID_ARG; }
     return ctx_target_knn(c, k, idx_ntk, d2_ntk);
 }
-int fgoicp_plane_moments(fgoicp_ctx* c, const float* R9, const float* t3, float max_dist2, fgoicp_plane_moments_t* out) {
-    if (!c || !R9 || !t3) { set_error("fgoicp_plane_moments: the context, R and t must not be null"); return FGOICP_ERR_INVALID_ARG; }
-    if (!plane_size_ok(out)) { set_error("fgoicp_plane_moments: out must not be null and out->struct_size = sizeof(fgoicp_plane_moments_t)"); return FGOICP_ERR_INVALID_ARG; }
-    if (!(max_dist2 >= 0.0f)) { set_error("fgoicp_plane_moments: max_dist2 must be >= 0 (+inf: no threshold)"); return FGOICP_ERR_INVALID_ARG; }
-    if (!c->normals_set) { set_error("fgoicp_plane_moments: the target normals are not set: call fgoicp_ctx_set_target_normals first"); return FGOICP_ERR_INVALID_ARG; }
-    PlaneMoments m;
-    const int rc = ctx_plane_moments(c, R9, t3, max_dist2, &m);
-    if (rc) return rc;
-    fgoicp_plane_moments_t full;
-    std::memset(&full, 0, sizeof(full));
-    full.struct_size = (uint32_t)sizeof(full);
-    full.points = c->ns;
-    full.correspondences = m.n;
-    std::memcpy(full.m, m.m, sizeof(full.m));
-    full.max_dist2 = max_dist2;
-    return plane_out(full, out, "fgoicp_plane_moments", "fgoicp_plane_moments_t");
-}
-int fgoicp_icp_plane(fgoicp_ctx* c, const float* R0_9, const float* t0_3, size_t max_iter, float conv_thr, float max_dist2, fgoicp_plane_result_t* out) {
-    if (!c || !R0_9 || !t0_3) { set_error("fgoicp_icp_plane: the context, R0 and t0 must not be null"); return FGOICP_ERR_INVALID_ARG; }
-    if (!plane_size_ok(out)) { set_error("fgoicp_icp_plane: out must not be null and out->struct_size = sizeof(fgoicp_plane_result_t)"); return FGOICP_ERR_INVALID_ARG; }
-    if (!(max_dist2 >= 0.0f)) { set_error("fgoicp_icp_plane: max_dist2 must be >= 0 (+inf: no threshold)"); return FGOICP_ERR_INVALID_ARG; }
-    if (!c->normals_set) { set_error("fgoicp_icp_plane: the target normals are not set: call fgoicp_ctx_set_target_normals first"); return FGOICP_ERR_INVALID_ARG; }
-    fgoicp_plane_result_t full;
-    const int rc = ctx_icp_plane(c, R0_9, t0_3, max_iter, conv_thr, max_dist2, &full);
-    return rc ? rc : plane_out(full, out, "fgoicp_icp_plane", "fgoicp_plane_result_t");
-}
 int fgoicp_ctx_set_source_normals(fgoicp_ctx* c, const float* normals_ns3_or_NULL, int k) {
     if (!c) { set_error("fgoicp_ctx_set_source_normals: the context must not be null"); return FGOICP_ERR_INVALID_ARG; }
     return fgoicp::abi_guard("fgoicp_ctx_set_source_normals", [&] { return ctx_set_source_normals(c, normals_ns3_or_NULL, k); });
@@ -2109,71 +2084,30 @@ int fgoicp_source_normals(fgoicp_ctx* c, float* out_ns3) {
     if (!c || !out_ns3) { set_error("fgoicp_source_normals: the context and the output must not be null"); return FGOICP_ERR_INVALID_ARG; }
     return fgoicp::abi_guard("fgoicp_source_normals", [&] { return ctx_source_normals(c, out_ns3); });
 }
-// what fgoicp_gicp_moments and fgoicp_icp_gicp refuse before any device work, behind the null and struct_size checks
-static int gicp_refusals(const fgoicp_ctx* c, float max_dist2, double epsilon, const char* where) {
-    const std::string w(where);
-    if (!(max_dist2 >= 0.0f)) { set_error(w + ": max_dist2 must be >= 0 (+inf: no threshold)"); return FGOICP_ERR_INVALID_ARG; }
-    if (!gicp_epsilon_ok(epsilon)) { set_error(w + ": epsilon must be finite and lie in (0, 1]"); return FGOICP_ERR_INVALID_ARG; }
-    if (!c->normals_set) { set_error(w + ": the target normals are not set: call fgoicp_ctx_set_target_normals first"); return FGOICP_ERR_INVALID_ARG; }
-    if (!c->src_normals_set) { set_error(w + ": the source normals are not set: call fgoicp_ctx_set_source_normals first"); return FGOICP_ERR_INVALID_ARG; }
-    return FGOICP_OK;
+int fgoicp_plane_moments(fgoicp_ctx* c, const float* R9, const float* t3, float max_dist2, fgoicp_plane_moments_t* out) {
+    return plain_moments_call(c, R9, t3, refine_spec(false, max_dist2, FGOICP_MODEL_PLANE, 0.0, FGOICP_LOSS_NONE, 0.0), "fgoicp_plane_moments", out);
+}
+int fgoicp_icp_plane(fgoicp_ctx* c, const float* R0_9, const float* t0_3, size_t max_iter, float conv_thr, float max_dist2, fgoicp_plane_result_t* out) {
+    return refine_loop_call(c, R0_9, t0_3, max_iter, conv_thr, refine_spec(false, max_dist2, FGOICP_MODEL_PLANE, 0.0, FGOICP_LOSS_NONE, 0.0), "fgoicp_icp_plane",
+                            "fgoicp_plane_result_t", out);
 }
 int fgoicp_gicp_moments(fgoicp_ctx* c, const float* R9, const float* t3, float max_dist2, double epsilon, fgoicp_plane_moments_t* out) {
-    if (!c || !R9 || !t3) { set_error("fgoicp_gicp_moments: the context, R and t must not be null"); return FGOICP_ERR_INVALID_ARG; }
-    if (!plane_size_ok(out)) { set_error("fgoicp_gicp_moments: out must not be null and out->struct_size = sizeof(fgoicp_plane_moments_t)"); return FGOICP_ERR_INVALID_ARG; }
-    return fgoicp::abi_guard("fgoicp_gicp_moments", [&] {
-        int rc = gicp_refusals(c, max_dist2, epsilon, "fgoicp_gicp_moments");
-        if (rc) return rc;
-        PlaneMoments m;
-        rc = ctx_gicp_moments(c, R9, t3, max_dist2, epsilon, &m);
-        if (rc) return rc;
-        fgoicp_plane_moments_t full;
-        std::memset(&full, 0, sizeof(full));  // the padding too: two results of the same inputs are the same bytes
-        full.struct_size = (uint32_t)sizeof(full);
-        full.points = c->ns;
-        full.correspondences = m.n;
-        std::memcpy(full.m, m.m, sizeof(full.m));
-        full.max_dist2 = max_dist2;
-        return plane_out(full, out, "fgoicp_gicp_moments", "fgoicp_plane_moments_t");
-    });
+    return plain_moments_call(c, R9, t3, refine_spec(false, max_dist2, FGOICP_MODEL_GICP, epsilon, FGOICP_LOSS_NONE, 0.0), "fgoicp_gicp_moments", out);
 }
 int fgoicp_icp_gicp(fgoicp_ctx* c, const float* R0_9, const float* t0_3, size_t max_iter, float conv_thr, float max_dist2, double epsilon, fgoicp_plane_result_t* out) {
-    if (!c || !R0_9 || !t0_3) { set_error("fgoicp_icp_gicp: the context, R0 and t0 must not be null"); return FGOICP_ERR_INVALID_ARG; }
-    if (!plane_size_ok(out)) { set_error("fgoicp_icp_gicp: out must not be null and out->struct_size = sizeof(fgoicp_plane_result_t)"); return FGOICP_ERR_INVALID_ARG; }
-    return fgoicp::abi_guard("fgoicp_icp_gicp", [&] {
-        int rc = gicp_refusals(c, max_dist2, epsilon, "fgoicp_icp_gicp");
-        if (rc) return rc;
-        fgoicp_plane_result_t full;
-        rc = ctx_icp_gicp(c, R0_9, t0_3, max_iter, conv_thr, max_dist2, epsilon, &full);
-        return rc ? rc : plane_out(full, out, "fgoicp_icp_gicp", "fgoicp_plane_result_t");
-    });
-}
-
-// a robust call's arguments as one value; a scale that does not matter (FGOICP_LOSS_NONE) is carried as given
-static RobustSpec robust_spec(float max_dist2, int model, double epsilon, int loss, double scale) {
-    RobustSpec r;
-    r.model = model; r.epsilon = epsilon; r.loss = loss; r.scale = scale; r.max_dist2 = max_dist2;
-    return r;
+    return refine_loop_call(c, R0_9, t0_3, max_iter, conv_thr, refine_spec(false, max_dist2, FGOICP_MODEL_GICP, epsilon, FGOICP_LOSS_NONE, 0.0), "fgoicp_icp_gicp",
+                            "fgoicp_plane_result_t", out);
 }
 int fgoicp_robust_moments(fgoicp_ctx* c, const float* R9, const float* t3, float max_dist2, int model, double epsilon, int loss, double scale,
                           fgoicp_robust_moments_t* out) {
     if (!c || !R9 || !t3) { set_error("fgoicp_robust_moments: the context, R and t must not be null"); return FGOICP_ERR_INVALID_ARG; }
     if (!plane_size_ok(out)) { set_error("fgoicp_robust_moments: out must not be null and out->struct_size = sizeof(fgoicp_robust_moments_t)"); return FGOICP_ERR_INVALID_ARG; }
     return fgoicp::abi_guard("fgoicp_robust_moments", [&] {
-        const RobustSpec r = robust_spec(max_dist2, model, epsilon, loss, scale);
-        int rc = robust_refusals(c, r, true, "fgoicp_robust_moments");
-        if (rc) return rc;
-        RobustMoments m;
-        rc = ctx_robust_moments(c, R9, t3, r, &m);
-        if (rc) return rc;
+        RefineMoments m;
         fgoicp_robust_moments_t full;
-        std::memset(&full, 0, sizeof(full));  // the padding too: two results of the same inputs are the same bytes
-        full.struct_size = (uint32_t)sizeof(full);
-        full.points = c->ns;
-        full.correspondences = m.n;
-        std::memcpy(full.m, m.m, sizeof(full.m));
+        const int rc = refine_moments_call(c, R9, t3, refine_spec(true, max_dist2, model, epsilon, loss, scale), "fgoicp_robust_moments", &m, &full);
+        if (rc) return rc;
         full.weight_sum = m.m[28];
-        full.max_dist2 = max_dist2;
         full.loss = loss;
         full.scale = scale;
         return plane_out(full, out, "fgoicp_robust_moments", "fgoicp_robust_moments_t");
@@ -2183,36 +2117,26 @@ int fgoicp_robust_residuals(fgoicp_ctx* c, const float* R9, const float* t3, flo
                             double* residual_ns, double* weight_ns, unsigned char* counted_ns) {
     if (!c || !R9 || !t3) { set_error("fgoicp_robust_residuals: the context, R and t must not be null"); return FGOICP_ERR_INVALID_ARG; }
     return fgoicp::abi_guard("fgoicp_robust_residuals", [&] {
-        const RobustSpec r = robust_spec(max_dist2, model, epsilon, loss, scale);
-        const int rc = robust_refusals(c, r, true, "fgoicp_robust_residuals");
+        const RefineSpec r = refine_spec(true, max_dist2, model, epsilon, loss, scale);
+        const int rc = refine_refusals(c, r, ScaleCheck::given, "fgoicp_robust_residuals");
         if (rc) return rc;
-        RobustMoments m;
+        RefineMoments m;
         std::vector<unsigned char> cnt;  // the kernel stores all three or none
         if (!residual_ns && !weight_ns && !counted_ns) cnt.resize(c->ns);
-        return ctx_robust_moments(c, R9, t3, r, &m, nullptr, residual_ns, weight_ns, cnt.empty() ? counted_ns : cnt.data());
+        return refine_evaluate(c, R9, t3, r, &m, nullptr, residual_ns, weight_ns, cnt.empty() ? counted_ns : cnt.data());
     });
 }
 int fgoicp_robust_scale(fgoicp_ctx* c, const float* R9, const float* t3, float max_dist2, int model, double epsilon, double* scale) {
     if (!c || !R9 || !t3 || !scale) { set_error("fgoicp_robust_scale: the context, R, t and scale must not be null"); return FGOICP_ERR_INVALID_ARG; }
     return fgoicp::abi_guard("fgoicp_robust_scale", [&] {
-        const RobustSpec r = robust_spec(max_dist2, model, epsilon, FGOICP_LOSS_NONE, 0.0);
-        const int rc = robust_refusals(c, r, false, "fgoicp_robust_scale");
+        const RefineSpec r = refine_spec(true, max_dist2, model, epsilon, FGOICP_LOSS_NONE, 0.0);
+        const int rc = refine_refusals(c, r, ScaleCheck::none, "fgoicp_robust_scale");
         return rc ? rc : ctx_robust_scale(c, R9, t3, r, scale, "fgoicp_robust_scale");
     });
 }
 int fgoicp_icp_robust(fgoicp_ctx* c, const float* R0_9, const float* t0_3, size_t max_iter, float conv_thr, float max_dist2, int model, double epsilon, int loss,
                       double scale, fgoicp_robust_result_t* out) {
-    if (!c || !R0_9 || !t0_3) { set_error("fgoicp_icp_robust: the context, R0 and t0 must not be null"); return FGOICP_ERR_INVALID_ARG; }
-    if (!plane_size_ok(out)) { set_error("fgoicp_icp_robust: out must not be null and out->struct_size = sizeof(fgoicp_robust_result_t)"); return FGOICP_ERR_INVALID_ARG; }
-    return fgoicp::abi_guard("fgoicp_icp_robust", [&] {
-        const RobustSpec r = robust_spec(max_dist2, model, epsilon, loss, scale);
-        if (scale != scale || std::isinf(scale)) { set_error("fgoicp_icp_robust: the scale must be finite (<= 0: estimated)"); return (int)FGOICP_ERR_INVALID_ARG; }
-        int rc = robust_refusals(c, r, false, "fgoicp_icp_robust");
-        if (rc) return rc;
-        fgoicp_robust_result_t full;
-        rc = ctx_icp_robust(c, R0_9, t0_3, max_iter, conv_thr, r, &full, "fgoicp_icp_robust");
-        return rc ? rc : plane_out(full, out, "fgoicp_icp_robust", "fgoicp_robust_result_t");
-    });
+    return refine_loop_call(c, R0_9, t0_3, max_iter, conv_thr, refine_spec(true, max_dist2, model, epsilon, loss, scale), "fgoicp_icp_robust", "fgoicp_robust_result_t", out);
 }
 
 int fgoicp_ctx_set_inliers(fgoicp_ctx* c, size_t k) {

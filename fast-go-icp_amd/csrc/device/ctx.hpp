@@ -133,19 +133,18 @@ struct fgoicp_ctx {
         unsigned long long* d_info = nullptr;    // {count, the bits of ten sums} (launch_align_info)
     } align;
 
-    // target normals and the point-to-plane normal equations (ctx_set_target_normals, ctx_plane_moments): each allocated by the first call
-    // that needs it — 16 bytes per target point, 232 per block of kBlock source points
+    // target normals (ctx_set_target_normals): allocated by the first call, 16 bytes per target point
     fgoicp::Dev<float4> d_normals;                   // nt x {n.x, n.y, n.z, 0}, caller order; the zero vector: no normal
     bool normals_set = false;
-    fgoicp::Dev<fgoicp::MomentRow<fgoicp::kPlaneTerms>> d_plane_rows;
-    fgoicp::Dev<unsigned long long> d_plane_out;         // {count, the bits of 28 sums} (launch_plane_moments)
     // source normals of the Generalized-ICP refinement (ctx_set_source_normals): allocated by the first call, 16 bytes per source point
     fgoicp::Dev<float4> d_src_normals;               // ns x {n.x, n.y, n.z, 0}, DEVICE SLOT order (perm); the zero vector: no normal
     bool src_normals_set = false;
-    // the robustly weighted normal equations (ctx_robust_moments): rows and output of their own, allocated by the first call — 240 bytes per
-    // block of kBlock source points; the per-point outputs (fgoicp_robust_residuals, the scale) by the first call that asks: 17 bytes per source point
+    // the refinements' normal equations (refine_evaluate), each allocated by the first call that needs it.  One output; two sets of rows,
+    // 232 and 240 bytes per block of kBlock source points: the unweighted and the weighted kernel reduce rows of 28 and of 29 terms, and
+    // one allocation behind both types would take a cast.  The per-point outputs (fgoicp_robust_residuals, the scale): 17 bytes per source point
+    fgoicp::Dev<fgoicp::MomentRow<fgoicp::kPlaneTerms>> d_plane_rows;
     fgoicp::Dev<fgoicp::MomentRow<fgoicp::kRobustTerms>> d_robust_rows;
-    fgoicp::Dev<unsigned long long> d_robust_out;        // {count, the bits of 29 sums} (launch_robust_moments)
+    fgoicp::Dev<unsigned long long> d_refine_out;        // {count, the bits of 28 or 29 sums} (launch_refine_moments)
     fgoicp::Dev<double> d_robust_point;                  // ns residuals, then ns weights, caller order
     fgoicp::Dev<unsigned char> d_robust_counted;         // ns flags, caller order
 
@@ -226,37 +225,46 @@ int ctx_alignment_information(fgoicp_ctx* c, const float* R9, const float* t3, u
 int ctx_set_target_normals(fgoicp_ctx* c, const float* normals, int k);
 int ctx_target_normals(fgoicp_ctx* c, float* out_nt3);
 int ctx_target_knn(fgoicp_ctx* c, int k, uint32_t* idx, float* d2);
-// one evaluation on lane 0: the report's device half (its index scan keeps the moved queries), then launch_plane_moments.  max_dist2 must
-// have been checked (not NaN, >= 0) and the normals set.  sse_out (optional): the report's sse, the bits of fgoicp_sse.
-int ctx_plane_moments(fgoicp_ctx* c, const float* R9, const float* t3, float max_dist2, PlaneMoments* m, float* sse_out = nullptr);
-// fgoicp_icp_plane; `full` is filled whole (scaling_factor = 1)
-int ctx_icp_plane(fgoicp_ctx* c, const float* R0, const float* t0, size_t max_iter, float thr, float max_dist2, fgoicp_plane_result_t* full);
 // EXTENSION: source normals and the Generalized-ICP refinement (include/fgoicp_amd.h).  normals = nullptr: estimated from the k nearest
 // SOURCE points through a throw-away tree over the source.
 int ctx_set_source_normals(fgoicp_ctx* c, const float* normals, int k);
 int ctx_source_normals(fgoicp_ctx* c, float* out_ns3);
-// ctx_plane_moments with launch_gicp_moments in place of launch_plane_moments; epsilon checked (gicp_epsilon_ok), both normal sets set
-int ctx_gicp_moments(fgoicp_ctx* c, const float* R9, const float* t3, float max_dist2, double epsilon, PlaneMoments* m, float* sse_out = nullptr);
-// fgoicp_icp_gicp: ctx_icp_plane's loop over ctx_gicp_moments; full->plane_rmse = sqrt(sum d^T M d / N)
-int ctx_icp_gicp(fgoicp_ctx* c, const float* R0, const float* t0, size_t max_iter, float thr, float max_dist2, double epsilon, fgoicp_plane_result_t* full);
-// EXTENSION: robust losses over either model (include/fgoicp_amd.h).  What one evaluation takes: checked by robust_refusals first.
-struct RobustSpec {
+// EXTENSION: the point-to-plane and Generalized-ICP refinements and their robust losses (include/fgoicp_amd.h).  What one evaluation
+// takes; checked by refine_refusals first.
+struct RefineSpec {
     int model = FGOICP_MODEL_PLANE;
     double epsilon = 1e-3;  // FGOICP_MODEL_GICP only
+    bool weighted = false;  // false, the plain calls: the unweighted kernel and its 28 sums; loss and scale are not read
     int loss = FGOICP_LOSS_NONE;
     double scale = 0.0;
     float max_dist2 = 0.f;
 };
-// what every robust call refuses before any device work: max_dist2, the model, its normals, epsilon (GICP), the loss and, need_scale, the scale
-int robust_refusals(const fgoicp_ctx* c, const RobustSpec& r, bool need_scale, const char* where);
-// one evaluation on lane 0, as ctx_plane_moments / ctx_gicp_moments.  residual / weight / counted (each optional, ns entries, caller
-// order): the per-point outputs, read back behind the evaluation.
-int ctx_robust_moments(fgoicp_ctx* c, const float* R9, const float* t3, const RobustSpec& r, RobustMoments* m, float* sse_out = nullptr, double* residual = nullptr,
-                       double* weight = nullptr, unsigned char* counted = nullptr);
+// how a call takes its scale: not at all, as given (finite and > 0 unless the loss is none), or given or estimated (finite)
+enum class ScaleCheck { none, given, or_estimated };
+// what every refinement call on the context refuses before any device work (the list and its order: ctx.hip)
+int refine_refusals(const fgoicp_ctx* c, const RefineSpec& r, ScaleCheck scale, const char* where);
+// one evaluation on lane 0: the report's device half (its index scan keeps the moved queries), then launch_refine_moments.  Unweighted,
+// m->m[28] is the count.  sse_out (optional): the report's sse, the bits of fgoicp_sse.  residual / weight / counted (each optional, ns
+// entries, caller order; weighted specs only): the per-point outputs, read back behind the evaluation.
+int refine_evaluate(fgoicp_ctx* c, const float* R9, const float* t3, const RefineSpec& r, RefineMoments* m, float* sse_out = nullptr, double* residual = nullptr,
+                    double* weight = nullptr, unsigned char* counted = nullptr);
 // fgoicp_robust_scale: one evaluation with the per-point outputs, the median on the host
-int ctx_robust_scale(fgoicp_ctx* c, const float* R9, const float* t3, const RobustSpec& r, double* scale, const char* where);
-// fgoicp_icp_robust; r.scale <= 0: estimated at (R0, t0).  `full` is filled whole (scaling_factor = 1)
-int ctx_icp_robust(fgoicp_ctx* c, const float* R0, const float* t0, size_t max_iter, float thr, RobustSpec r, fgoicp_robust_result_t* full, const char* where);
+int ctx_robust_scale(fgoicp_ctx* c, const float* R9, const float* t3, const RefineSpec& r, double* scale, const char* where);
+// where a loop ended: the pose, the last evaluation there, and the spec it ran with (its scale: given or estimated)
+struct RefineEnd {
+    Mat3f R;
+    Vec3f t;
+    RefineMoments m;
+    float sse = 0.f;
+    int iterations = 0, rank = 0;
+    RefineSpec spec;
+    int scale_estimated = 0;
+};
+// fgoicp_icp_plane, fgoicp_icp_gicp, fgoicp_icp_robust (weighted; spec.scale <= 0: estimated at (R0, t0))
+int refine_loop(fgoicp_ctx* c, const float* R0, const float* t0, size_t max_iter, float thr, const RefineSpec& spec, const char* where, RefineEnd* end);
+// `full` is filled whole (scaling_factor = 1): plane_rmse = sqrt(m[27] / N), rmse = sqrt(m[27] / sum w)
+void refine_result(const RefineEnd& e, fgoicp_plane_result_t* full);
+void refine_result(const RefineEnd& e, fgoicp_robust_result_t* full);
 // a summary handed to a caller: no byte beyond the struct_size the caller set is written (0, or less than the size field itself: refused)
 inline int alignment_summary_out(const fgoicp_alignment_summary& full, fgoicp_alignment_summary* out, const char* where) {
     if (!out) return FGOICP_OK;

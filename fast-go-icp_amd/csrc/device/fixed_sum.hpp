@@ -76,7 +76,7 @@ __device__ __forceinline__ Count wave_sums(double (&v)[K], Count count, WaveSums
 }
 
 // *row = the sums of a block of W waves over its threads' terms[K] and count (0 or 1); every thread of the block calls this.  The terms
-// are copied first: the caller's array stays its own (gicp_moments_kernel hands it to gicp_pair_terms by pointer, and with the butterfly
+// are copied first: the caller's array stays its own (refine_moments_kernel hands it to gicp_pair_terms by pointer, and with the butterfly
 // written into that same array the compiler kept all 28 doubles in scratch memory).
 template <int W, int K>
 __device__ __forceinline__ void block_moment_row(const double (&terms)[K], unsigned count, MomentRow<K>* __restrict__ row) {

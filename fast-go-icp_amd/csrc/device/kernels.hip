@@ -2845,164 +2845,91 @@ void launch_cluster_border(const BvhView& t, int nt, float eps2, const uint32_t*
 }
 
 // ---------------------------------------------------------------------------------------------
-// The point-to-plane normal equations (fgoicp_plane_moments) over the report's arrays.  One thread per device slot i: the moved query
-// x = R p + t as the report's index scan wrote it back (fp32, the scans' fma convention), the slot's caller index o, and the report's
-// entries of o.  COUNTED are the o with inlier[o] != 0, d2[o] <= max_d2, corr[o] < nt and a non-zero normal at corr[o].  With q the target
-// point corr[o], n its normal: r = n.(x - q), J = [ (x cross n)^T, n^T ] (twist order wx wy wz vx vy vz); every term is formed in fp64
-// from the fp32 inputs.  Reduced: the upper triangle of sum J^T J row by row (21), sum J^T r (6), sum r^2 (1), and the count — in
-// the fixed order of fixed_sum.hpp (block_moment_row, then moment_fold_kernel).  No atomics: the same arrays give the same bytes.  Every
-// term is even in n: the sign of a normal does not matter.
+// The normal equations of the refinements (fgoicp_plane_moments, fgoicp_gicp_moments, fgoicp_robust_moments, fgoicp_robust_residuals and
+// the loops over them; DESIGN.md sections 12, 15 and 19) over the report's arrays: ONE kernel text with a model switch, a weight switch and
+// a per-point switch.  One thread per device slot i: the moved query x = R p + t as the report's index scan wrote it back (fp32, the scans'
+// fma convention), the slot's caller index o, the report's entries of o and, GICP, the slot's source normal (`moved`, `orig_of_slot` and
+// `src_normals` are coalesced reads; the target point and its normal are the only gathers).  COUNTED are the o with inlier[o] != 0,
+// d2[o] <= max_d2, corr[o] < nt and a non-zero normal at corr[o]; GICP: whose own source normal is non-zero too.
+//   GICP = false  with q the target point corr[o], n its normal: r = n.(x - q), J = [ (x cross n)^T, n^T ] (twist order wx wy wz vx vy
+//                 vz); the upper triangle of J^T J row by row (21), J^T r (6), r^2 (1); the residual s = r (plane_pair_terms)
+//   GICP = true   m = R n_p, S = 2 I - (1 - eps)(n_q n_q^T + m m^T), M = adj(S) / det(S), the 28 terms of J^T M J, J^T M d, d^T M d with
+//                 J = [ -[x]x | I ] — gicp_pair_terms (host/gicp.hpp), the text fgoicp_gicp_terms runs on the host; s = sqrt(max(d^T M d, 0))
+// Every term is formed in fp64 from the fp32 inputs and is even in each normal: the sign of a normal does not matter.
+//   WEIGHTED      w = robust_weight(loss, s, c) (host/robust.hpp, the text fgoicp_robust_weight runs on the host; the switch on `loss` is
+//                 wave-uniform), each of the 28 terms times w once, and w as the 29th.  With loss = none w is exactly 1 and the 28 sums
+//                 have the bits of the unweighted instantiation's: at K = 29 every term's additions are still its own.
+//   PER_POINT     additionally residual / weight / counted at the caller index o (a permutation: every row is written once), 0 / 0 / 0
+//                 for an uncounted point.  The loops' launches are the instantiations without these stores.
+// Reduced in the fixed order of fixed_sum.hpp (block_moment_row, then moment_fold_kernel), K = 28 or 29.  No atomics: the same arrays
+// give the same bytes.
 // ---------------------------------------------------------------------------------------------
-// The counted-set gate of plane_moments_kernel and gicp_moments_kernel for the caller index o of a device slot, and the gathers behind it:
-// true with nn = the target normal and q = the target point at corr[o]
 __device__ __forceinline__ bool nonzero3(const float4& a) { return a.x != 0.0f || a.y != 0.0f || a.z != 0.0f; }
-__device__ __forceinline__ bool counted_pair(uint32_t o, const unsigned char* __restrict__ inlier, const float* __restrict__ d2, const uint32_t* __restrict__ corr,
-                                             const float4* __restrict__ tgt, const float4* __restrict__ normals, int n, int nt, float max_d2, float4& nn, float4& q) {
-    if (!(o < (uint32_t)n)) return false;
-    const uint32_t j = corr[o];
-    if (!(inlier[o] != 0 && d2[o] <= max_d2 && j < (uint32_t)nt)) return false;
-    nn = normals[j];
+// the counted-set gate for the caller index o of a device slot, and the gathers behind it: true with nn = the target normal and q = the
+// target point at corr[o]
+__device__ __forceinline__ bool counted_pair(uint32_t o, const RefineInputs& in, float4& nn, float4& q) {
+    if (!(o < (uint32_t)in.n)) return false;
+    const uint32_t j = in.corr[o];
+    if (!(in.inlier[o] != 0 && in.d2[o] <= in.max_d2 && j < (uint32_t)in.nt)) return false;
+    nn = in.normals[j];
     if (!nonzero3(nn)) return false;
-    q = tgt[j];
+    q = in.tgt[j];
     return true;
 }
-__global__ __launch_bounds__(kBlock) void plane_moments_kernel(const float4* __restrict__ moved, const uint32_t* __restrict__ orig_of_slot,
-                                                               const unsigned char* __restrict__ inlier, const float* __restrict__ d2,
-                                                               const uint32_t* __restrict__ corr, const float4* __restrict__ tgt,
-                                                               const float4* __restrict__ normals, int n, int nt, float max_d2,
-                                                               MomentRow<kPlaneTerms>* __restrict__ rows) {
-    const int i = blockIdx.x * kBlock + threadIdx.x;
-    double v[kPlaneTerms];
+// u = the 28 point-to-plane terms of one pair; returns the residual r
+__device__ __forceinline__ double plane_pair_terms(const double X[3], const float4& q, const double N[3], double* u) {
+    const double r = N[0] * (X[0] - (double)q.x) + N[1] * (X[1] - (double)q.y) + N[2] * (X[2] - (double)q.z);
+    const double J[6] = {X[1] * N[2] - X[2] * N[1], X[2] * N[0] - X[0] * N[2], X[0] * N[1] - X[1] * N[0], N[0], N[1], N[2]};
+    int m = 0;
 #pragma unroll
-    for (int k = 0; k < kPlaneTerms; ++k) v[k] = 0.0;
-    unsigned cnt = 0u;
-    float4 nn, q;
-    if (i < n && counted_pair(orig_of_slot[i], inlier, d2, corr, tgt, normals, n, nt, max_d2, nn, q)) {
-        const float4 x = moved[i];
-        const double X[3] = {(double)x.x, (double)x.y, (double)x.z}, N[3] = {(double)nn.x, (double)nn.y, (double)nn.z};
-        const double r = N[0] * (X[0] - (double)q.x) + N[1] * (X[1] - (double)q.y) + N[2] * (X[2] - (double)q.z);
-        const double J[6] = {X[1] * N[2] - X[2] * N[1], X[2] * N[0] - X[0] * N[2], X[0] * N[1] - X[1] * N[0], N[0], N[1], N[2]};
-        int m = 0;
+    for (int a = 0; a < 6; ++a)
 #pragma unroll
-        for (int a = 0; a < 6; ++a)
+        for (int b = a; b < 6; ++b) u[m++] = J[a] * J[b];
 #pragma unroll
-            for (int b = a; b < 6; ++b) v[m++] = J[a] * J[b];
-#pragma unroll
-        for (int a = 0; a < 6; ++a) v[21 + a] = J[a] * r;
-        v[27] = r * r;
-        cnt = 1u;
-    }
-    block_moment_row<kBlock / 64>(v, cnt, &rows[blockIdx.x]);
+    for (int a = 0; a < 6; ++a) u[21 + a] = J[a] * r;
+    u[27] = r * r;
+    return r;
 }
-
-void launch_plane_moments(const float4* moved, const uint32_t* orig_of_slot, const unsigned char* inlier, const float* d2, const uint32_t* corr, const float4* tgt,
-                          const float4* normals, int n, int nt, float max_d2, MomentRow<kPlaneTerms>* rows, unsigned long long* out29, hipStream_t s) {
-    const int nb = (n + kBlock - 1) / kBlock;
-    hipLaunchKernelGGL(plane_moments_kernel, dim3(nb), dim3(kBlock), 0, s, moved, orig_of_slot, inlier, d2, corr, tgt, normals, n, nt, max_d2, rows);
-    hipLaunchKernelGGL(moment_fold_kernel<kPlaneTerms>, dim3(1), dim3(1024), 0, s, rows, nb, out29);
-}
-
-
-// ---------------------------------------------------------------------------------------------
-// The Generalized-ICP normal equations (fgoicp_gicp_moments) over the same arrays as plane_moments_kernel, plus the
-// SOURCE normals in device slot order (a coalesced read like `moved`).  One thread per device slot i; COUNTED are plane_moments_kernel's
-// caller indices whose own source normal is non-zero too.  The per-pair arithmetic — m = R n_p, S = 2 I - (1 - eps)(n_q n_q^T + m m^T),
-// M = adj(S) / det(S), the 28 terms of J^T M J, J^T M d, d^T M d with J = [ -[x]x | I ] — is gicp_pair_terms (host/gicp.hpp), the text
-// fgoicp_gicp_terms runs on the host.  The reduction is plane_moments_kernel's: block_moment_row, then
-// moment_fold_kernel.  No atomics.  Every term is even in n_q and in n_p.
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kBlock) void gicp_moments_kernel(const float4* __restrict__ moved, const uint32_t* __restrict__ orig_of_slot,
-                                                              const unsigned char* __restrict__ inlier, const float* __restrict__ d2,
-                                                              const uint32_t* __restrict__ corr, const float4* __restrict__ tgt,
-                                                              const float4* __restrict__ normals, const float4* __restrict__ src_normals, Rt rt, double eps, int n,
-                                                              int nt, float max_d2, MomentRow<kPlaneTerms>* __restrict__ rows) {
-    const int i = blockIdx.x * kBlock + threadIdx.x;
-    double v[kPlaneTerms];
-#pragma unroll
-    for (int k = 0; k < kPlaneTerms; ++k) v[k] = 0.0;
-    unsigned cnt = 0u;
-    if (i < n) {
-        const uint32_t o = orig_of_slot[i];
-        const float4 x = moved[i], np = src_normals[i];
-        float4 nn, q;
-        if (nonzero3(np) && counted_pair(o, inlier, d2, corr, tgt, normals, n, nt, max_d2, nn, q)) {
-            const double X[3] = {(double)x.x, (double)x.y, (double)x.z}, Q[3] = {(double)q.x, (double)q.y, (double)q.z};
-            const double NQ[3] = {(double)nn.x, (double)nn.y, (double)nn.z}, NP[3] = {(double)np.x, (double)np.y, (double)np.z};
-            gicp_pair_terms(X, Q, NQ, NP, rt.R, eps, nullptr, v);
-            cnt = 1u;
-        }
-    }
-    block_moment_row<kBlock / 64>(v, cnt, &rows[blockIdx.x]);
-}
-
-
-void launch_gicp_moments(const float4* moved, const uint32_t* orig_of_slot, const unsigned char* inlier, const float* d2, const uint32_t* corr, const float4* tgt,
-                         const float4* normals, const float4* src_normals, const float* R9, double eps, int n, int nt, float max_d2, MomentRow<kPlaneTerms>* rows,
-                         unsigned long long* out29, hipStream_t s) {
-    const int nb = (n + kBlock - 1) / kBlock;
-    hipLaunchKernelGGL(gicp_moments_kernel, dim3(nb), dim3(kBlock), 0, s, moved, orig_of_slot, inlier, d2, corr, tgt, normals, src_normals, make_rt(R9, nullptr), eps, n, nt,
-                       max_d2, rows);
-    hipLaunchKernelGGL(moment_fold_kernel<kPlaneTerms>, dim3(1), dim3(1024), 0, s, rows, nb, out29);
-}
-
-// ---------------------------------------------------------------------------------------------
-// The robustly weighted normal equations (fgoicp_robust_moments, fgoicp_robust_residuals).  One thread per device
-// slot i over the arrays of the two kernels above.  GICP = false: plane_moments_kernel's counted set and its 28 terms, operation for
-// operation, s = r.  GICP = true: gicp_moments_kernel's counted set, gicp_pair_terms, s = sqrt(max(d^T M d, 0)).  Then w = robust_weight(loss,
-// s, c) (host/robust.hpp, the text fgoicp_robust_weight runs on the host; the switch on `loss` is wave-uniform), each of the 28 terms
-// times w once, and w as the 29th.  With loss = none w is exactly 1 and the 28 sums have the bits of the plain kernels': the reduction is
-// theirs, block_moment_row and moment_fold_kernel at K = 29, where every term's additions are its own.  No atomics.
-// PER_POINT: additionally residual / weight / counted at the caller index o = orig_of_slot[i] (a permutation: every row is written once),
-// 0 / 0 / 0 for an uncounted point.  The loop's launches are the instantiation without these stores.
-// `moved`, `orig_of_slot` and `src_normals` are coalesced reads; the target point and its normal are the only gathers (behind the
-// caller-order report entries of o, as in the plain kernels).
-// ---------------------------------------------------------------------------------------------
-template <bool GICP, bool PER_POINT>
-__global__ __launch_bounds__(kBlock) void robust_moments_kernel(const float4* __restrict__ moved, const uint32_t* __restrict__ orig_of_slot,
-                                                                const unsigned char* __restrict__ inlier, const float* __restrict__ d2,
-                                                                const uint32_t* __restrict__ corr, const float4* __restrict__ tgt,
-                                                                const float4* __restrict__ normals, const float4* __restrict__ src_normals, Rt rt, double eps,
-                                                                int loss, double scale, int n, int nt, float max_d2, MomentRow<kRobustTerms>* __restrict__ rows,
+template <bool GICP, bool WEIGHTED, bool PER_POINT>
+__global__ __launch_bounds__(kBlock) void refine_moments_kernel(RefineInputs in, Rt rt, double eps, int loss, double scale,
+                                                                MomentRow<WEIGHTED ? kRobustTerms : kPlaneTerms>* __restrict__ rows,
                                                                 double* __restrict__ residual, double* __restrict__ weight, unsigned char* __restrict__ counted) {
+    static_assert(WEIGHTED || !PER_POINT, "the per-point outputs are the weighted kernel's");
+    constexpr int K = WEIGHTED ? kRobustTerms : kPlaneTerms;
     const int i = blockIdx.x * kBlock + threadIdx.x;
-    double v[kRobustTerms];
+    double v[K];
 #pragma unroll
-    for (int k = 0; k < kRobustTerms; ++k) v[k] = 0.0;
+    for (int k = 0; k < K; ++k) v[k] = 0.0;
     unsigned cnt = 0u;
-    if (i < n) {
-        const uint32_t o = orig_of_slot[i];
-        const float4 x = moved[i];
+    if (i < in.n) {
+        const uint32_t o = in.orig_of_slot[i];
+        const float4 x = in.moved[i];
         float4 np = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (GICP) np = src_normals[i];
+        if (GICP) np = in.src_normals[i];
         float4 nn, q;
         double s = 0.0, w = 0.0;
-        if ((!GICP || nonzero3(np)) && counted_pair(o, inlier, d2, corr, tgt, normals, n, nt, max_d2, nn, q)) {
+        if ((!GICP || nonzero3(np)) && counted_pair(o, in, nn, q)) {
             const double X[3] = {(double)x.x, (double)x.y, (double)x.z}, N[3] = {(double)nn.x, (double)nn.y, (double)nn.z};
-            double u[kPlaneTerms];  // the pair's unweighted terms, an array of their own: handed to gicp_pair_terms by pointer and then scaled in place, the accumulators went to scratch memory (240 bytes per lane)
+            // the pair's unweighted terms: straight into the accumulators, or (WEIGHTED) an array of their own — handed to gicp_pair_terms
+            // by pointer and then scaled in place, the accumulators went to scratch memory (240 bytes per lane)
+            double own[WEIGHTED ? kPlaneTerms : 1];
+            double* const u = WEIGHTED ? own : v;
             if (GICP) {
                 const double Q[3] = {(double)q.x, (double)q.y, (double)q.z}, NP[3] = {(double)np.x, (double)np.y, (double)np.z};
                 gicp_pair_terms(X, Q, N, NP, rt.R, eps, nullptr, u);
                 s = sqrt(u[27] > 0.0 ? u[27] : 0.0);
             } else {
-                const double r = N[0] * (X[0] - (double)q.x) + N[1] * (X[1] - (double)q.y) + N[2] * (X[2] - (double)q.z);
-                const double J[6] = {X[1] * N[2] - X[2] * N[1], X[2] * N[0] - X[0] * N[2], X[0] * N[1] - X[1] * N[0], N[0], N[1], N[2]};
-                int m = 0;
-#pragma unroll
-                for (int a = 0; a < 6; ++a)
-#pragma unroll
-                    for (int b = a; b < 6; ++b) u[m++] = J[a] * J[b];
-#pragma unroll
-                for (int a = 0; a < 6; ++a) u[21 + a] = J[a] * r;
-                u[27] = r * r;
-                s = r;
+                s = plane_pair_terms(X, q, N, u);
             }
-            w = robust_weight(loss, s, scale);
+            if (WEIGHTED) {
+                w = robust_weight(loss, s, scale);
 #pragma unroll
-            for (int k = 0; k < kPlaneTerms; ++k) v[k] = u[k] * w;
-            v[kPlaneTerms] = w;
+                for (int k = 0; k < kPlaneTerms; ++k) v[k] = u[k] * w;
+                v[K - 1] = w;
+            }
             cnt = 1u;
         }
-        if (PER_POINT && o < (uint32_t)n) {
+        if (PER_POINT && o < (uint32_t)in.n) {
             residual[o] = s;
             weight[o] = w;
             counted[o] = (unsigned char)cnt;
@@ -3011,18 +2938,22 @@ __global__ __launch_bounds__(kBlock) void robust_moments_kernel(const float4* __
     block_moment_row<kBlock / 64>(v, cnt, &rows[blockIdx.x]);
 }
 
-void launch_robust_moments(bool gicp, const float4* moved, const uint32_t* orig_of_slot, const unsigned char* inlier, const float* d2, const uint32_t* corr,
-                           const float4* tgt, const float4* normals, const float4* src_normals, const float* R9, double eps, int loss, double scale, int n, int nt,
-                           float max_d2, MomentRow<kRobustTerms>* rows, unsigned long long* out30, double* residual, double* weight, unsigned char* counted,
-                           hipStream_t s) {
-    const int nb = (n + kBlock - 1) / kBlock;
-    const bool per_point = residual && weight && counted;
-    auto* const kernel = gicp ? (per_point ? robust_moments_kernel<true, true> : robust_moments_kernel<true, false>)
-                              : (per_point ? robust_moments_kernel<false, true> : robust_moments_kernel<false, false>);
-    hipLaunchKernelGGL(kernel, dim3(nb), dim3(kBlock), 0, s, moved, orig_of_slot, inlier, d2, corr, tgt, normals, src_normals, make_rt(R9, nullptr), eps, loss, scale, n, nt,
-                       max_d2, rows, residual, weight, counted);
-    hipLaunchKernelGGL(moment_fold_kernel<kRobustTerms>, dim3(1), dim3(1024), 0, s, rows, nb, out30);
+// K = kPlaneTerms: the unweighted kernel (loss, scale and the per-point outputs unused); K = kRobustTerms: the weighted one
+template <int K>
+void launch_refine_moments(const RefineInputs& in, bool gicp, const float* R9, double eps, int loss, double scale, MomentRow<K>* rows, unsigned long long* out,
+                           double* residual, double* weight, unsigned char* counted, hipStream_t s) {
+    constexpr bool W = K == kRobustTerms;
+    const int nb = (in.n + kBlock - 1) / kBlock;
+    const bool per_point = W && residual && weight && counted;
+    auto* const kernel = gicp ? (per_point ? refine_moments_kernel<true, W, W> : refine_moments_kernel<true, W, false>)
+                              : (per_point ? refine_moments_kernel<false, W, W> : refine_moments_kernel<false, W, false>);
+    hipLaunchKernelGGL(kernel, dim3(nb), dim3(kBlock), 0, s, in, make_rt(R9, nullptr), eps, loss, scale, rows, residual, weight, counted);
+    hipLaunchKernelGGL(moment_fold_kernel<K>, dim3(1), dim3(1024), 0, s, rows, nb, out);
 }
+template void launch_refine_moments<kPlaneTerms>(const RefineInputs&, bool, const float*, double, int, double, MomentRow<kPlaneTerms>*, unsigned long long*, double*, double*,
+                                                 unsigned char*, hipStream_t);
+template void launch_refine_moments<kRobustTerms>(const RefineInputs&, bool, const float*, double, int, double, MomentRow<kRobustTerms>*, unsigned long long*, double*, double*,
+                                                  unsigned char*, hipStream_t);
 
 // out[i] = in[orig_of_slot[i]]: per-point data from caller order into device slot order (the source normals: target_knn_kernel writes them
 // at the caller index)

@@ -157,30 +157,33 @@ void launch_cluster_round(const BvhView& t, int nt, float eps2, const uint32_t* 
 // label[i] = rank[parent[i]] for a core point; for another point the same of its core neighbour with the smallest key (bits(d2) << 32) | index,
 // -1 if it has none.  rank: the dense number of every root (the exclusive scan of the root flags over caller index).
 void launch_cluster_border(const BvhView& t, int nt, float eps2, const uint32_t* core, const uint32_t* parent, const uint32_t* rank, int32_t* label, hipStream_t s);
-// The point-to-plane normal equations (fgoicp_plane_moments; kernels.hip plane_moments_kernel, fixed_sum.hpp moment_fold_kernel) over the report's
-// arrays (caller order) and the moved queries of its index scan (device order, `moved`): counted are the caller indices with inlier != 0,
-// d2 <= max_d2, corr < nt and a non-zero normal at corr.  rows: ceil(n / kBlock) entries; out29 = {count, the bits of 28 doubles: the
-// upper triangle of sum J^T J row by row (21), sum J^T r (6), sum r^2}.  Fixed order of every addition.
-constexpr int kPlaneTerms = 28;
-void launch_plane_moments(const float4* moved, const uint32_t* orig_of_slot, const unsigned char* inlier, const float* d2, const uint32_t* corr, const float4* tgt,
-                          const float4* normals, int n, int nt, float max_d2, MomentRow<kPlaneTerms>* rows, unsigned long long* out29, hipStream_t s);
-// The Generalized-ICP normal equations (fgoicp_gicp_moments; kernels.hip gicp_moments_kernel, then moment_fold_kernel): as
-// launch_plane_moments, with src_normals = the source normals in DEVICE SLOT order (n x {n.x, n.y, n.z, 0}; a zero vector takes its point
-// out of the counted set), R9 the rotation of the pose `moved` was formed with (glm order) and eps in (0, 1].  out29 = {count, the bits of
-// 28 doubles: the upper triangle of sum J^T M J row by row (21), sum J^T M d (6), sum d^T M d} (host/gicp.hpp).  Fixed order of every addition.
-void launch_gicp_moments(const float4* moved, const uint32_t* orig_of_slot, const unsigned char* inlier, const float* d2, const uint32_t* corr, const float4* tgt,
-                         const float4* normals, const float4* src_normals, const float* R9, double eps, int n, int nt, float max_d2, MomentRow<kPlaneTerms>* rows,
-                         unsigned long long* out29, hipStream_t s);
-// The robustly weighted normal equations of either model (fgoicp_robust_moments; kernels.hip robust_moments_kernel, then moment_fold_kernel
-// at K = 29): the counted set and the 28 terms of launch_plane_moments (gicp = false; src_normals, R9 and eps unused) or launch_gicp_moments
-// (gicp = true), each term times w(s) (host/robust.hpp robust_weight; loss and scale c as fgoicp_robust_weight takes them), and w as the
-// 29th term.  out30 = {count, the bits of 29 doubles}.  residual / weight / counted (all three or none): per-point outputs at the CALLER
-// index, n entries each, 0 / 0 / 0 for an uncounted point; with nullptr the launch is the kernel without those stores.
-constexpr int kRobustTerms = 29;
-void launch_robust_moments(bool gicp, const float4* moved, const uint32_t* orig_of_slot, const unsigned char* inlier, const float* d2, const uint32_t* corr,
-                           const float4* tgt, const float4* normals, const float4* src_normals, const float* R9, double eps, int loss, double scale, int n, int nt,
-                           float max_d2, MomentRow<kRobustTerms>* rows, unsigned long long* out30, double* residual, double* weight, unsigned char* counted,
-                           hipStream_t s);
+// The normal equations of the refinements (kernels.hip refine_moments_kernel, then fixed_sum.hpp moment_fold_kernel) over the report's arrays
+// (caller order) and the moved queries of its index scan (device order, `moved`): counted are the caller indices with inlier != 0,
+// d2 <= max_d2, corr < nt and a non-zero normal at corr; gicp: whose own source normal is non-zero too.  src_normals: the source normals in
+// DEVICE SLOT order (n x {n.x, n.y, n.z, 0}), read only with gicp.
+struct RefineInputs {
+    const float4* moved;
+    const uint32_t* orig_of_slot;
+    const unsigned char* inlier;
+    const float* d2;
+    const uint32_t* corr;
+    const float4 *tgt, *normals, *src_normals;
+    int n, nt;
+    float max_d2;
+};
+// K = kPlaneTerms, the unweighted sums: out = {count, the bits of 28 doubles} — gicp = false (fgoicp_plane_moments): the upper triangle of
+// sum J^T J row by row (21), sum J^T r (6), sum r^2; gicp = true (fgoicp_gicp_moments; host/gicp.hpp): the same of J^T M J, J^T M d,
+// d^T M d, with R9 the rotation of the pose `moved` was formed with (glm order) and eps in (0, 1].  loss, scale and the per-point outputs
+// are not read.
+// K = kRobustTerms, the weighted sums (fgoicp_robust_moments): each of those terms times w(s) (host/robust.hpp robust_weight; loss and scale
+// c as fgoicp_robust_weight takes them), and w as the 29th: out = {count, the bits of 29 doubles}.  residual / weight / counted (all three
+// or none): per-point outputs at the CALLER index, n entries each, 0 / 0 / 0 for an uncounted point; with nullptr the launch is the kernel
+// without those stores.
+// rows: ceil(n / kBlock) entries.  Fixed order of every addition.
+constexpr int kPlaneTerms = 28, kRobustTerms = 29;
+template <int K>
+void launch_refine_moments(const RefineInputs& in, bool gicp, const float* R9, double eps, int loss, double scale, MomentRow<K>* rows, unsigned long long* out,
+                           double* residual, double* weight, unsigned char* counted, hipStream_t s);
 // out[i] = in[orig_of_slot[i]], i < n: caller order -> device slot order
 void launch_slot_order(const float4* in, const uint32_t* orig_of_slot, int n, float4* out, hipStream_t s);
 // The bounds of many registrations in one launch (fgoicp_batch, bounds_fused.hpp): a view per pair of the batch, an evaluation per output

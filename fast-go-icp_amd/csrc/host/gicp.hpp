@@ -1,5 +1,5 @@
 // The per-pair arithmetic of the Generalized-ICP refinement (fgoicp_gicp_terms, fgoicp_gicp_moments, fgoicp_icp_gicp):
-// ONE text for gicp_moments_kernel (kernels.hip) and the host entry point.  No device, no HIP headers: under hipcc the function is
+// ONE text for refine_moments_kernel (kernels.hip) and the host entry point.  No device, no HIP headers: under hipcc the function is
 // __host__ __device__, under a plain C++ compiler it is a host function.
 #pragma once
 #include <cmath>

@@ -13,13 +13,9 @@
 namespace fgoicp {
 void set_error(const std::string& s);
 
-// what the device leaves (launch_plane_moments): the counted correspondences and the 28 sums — the upper triangle of sum J^T J row by
-// row (21), sum J^T r (6), sum r^2 — with J = [ (x cross n)^T, n^T ], r = n.(x - q), twist order (wx, wy, wz, vx, vy, vz)
+// what the device leaves (launch_refine_moments): the 28 sums — the upper triangle of sum J^T J row by row (21), sum J^T r (6),
+// sum r^2 — with J = [ (x cross n)^T, n^T ], r = n.(x - q), twist order (wx, wy, wz, vx, vy, vz)
 constexpr int kPlaneMoments = 28;
-struct PlaneMoments {
-    uint64_t n = 0;
-    double m[kPlaneMoments] = {};
-};
 
 // Eigen-decomposition of a symmetric 6 x 6 matrix by cyclic Jacobi sweeps: A = V diag(w) V^T, the columns of V the eigenvectors.  The
 // sweeps end when the off-diagonal part is below 1e-30 of the whole in squared Frobenius norm (quadratic convergence: 6-8 sweeps).

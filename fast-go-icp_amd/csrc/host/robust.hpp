@@ -1,5 +1,5 @@
 // The robust losses of the point-to-plane and Generalized-ICP refinements (fgoicp_robust_weight, fgoicp_robust_moments,
-// fgoicp_robust_residuals, fgoicp_robust_scale, fgoicp_icp_robust): ONE text of the weight for robust_moments_kernel
+// fgoicp_robust_residuals, fgoicp_robust_scale, fgoicp_icp_robust): ONE text of the weight for refine_moments_kernel
 // (kernels.hip) and the host entry point, and the host half of the scale.  No device, no HIP headers: under hipcc the weight is
 // __host__ __device__, under a plain C++ compiler it is a host function.
 #pragma once
@@ -58,9 +58,9 @@ inline int robust_weight_entry(int loss, double s, double scale, double* w) {
     return FGOICP_OK;
 }
 
-// what the device leaves (launch_robust_moments): the counted correspondences, the 28 weighted sums in PlaneMoments' layout, the sum of the weights
+// what the device leaves (launch_refine_moments): the counted correspondences, the 28 sums of plane.hpp (weighted or not), the sum of the weights
 constexpr int kRobustMoments = 29;
-struct RobustMoments {
+struct RefineMoments {
     uint64_t n = 0;
     double m[kRobustMoments] = {};  // m[28]: sum w
 };

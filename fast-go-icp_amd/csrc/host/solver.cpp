@@ -102,6 +102,41 @@ struct fgoicp_solver {
     }
 };
 
+// The refinements from the best transform, behind each entry point's own refusals.  spec.scale and max_distance are in the caller's
+// units: a residual of either model and a distance scale with the frame.  Missing normals are estimated from k neighbours (they are
+// invariant under the solver's centring and uniform scale).  Result: fgoicp_plane_result_t or fgoicp_robust_result_t (refine_result).
+// The plain loops report a failure of the loop itself under the context entry point's name, as they always have.
+template <class Result>
+static int solver_refine(fgoicp_solver* s, const char* where, RefineSpec spec, float max_distance, int k, size_t max_iter, float conv_thr, const char* type, Result* out) {
+    return fgoicp::abi_guard(where, [&] {
+        if (!s->ctx->normals_set) {
+            const int rc = ctx_set_target_normals(s->ctx, nullptr, k);
+            if (rc) return rc;
+        }
+        if (spec.model == FGOICP_MODEL_GICP && !s->ctx->src_normals_set) {
+            const int rc = ctx_set_source_normals(s->ctx, nullptr, k);
+            if (rc) return rc;
+        }
+        Mat3f R;
+        Vec3f t;
+        s->driver->best_transform(R, t);  // the normalised frame the search ran in, as fgoicp_solver_information
+        const float t3[3] = {t.x, t.y, t.z};
+        spec.scale = spec.scale > 0.0 ? spec.scale * (double)s->scaling_factor : 0.0;
+        spec.max_dist2 = information_max_dist2(max_distance, s->scaling_factor);
+        RefineEnd end;
+        const int rc = refine_loop(s->ctx, R.m, t3, max_iter, conv_thr, spec, spec.weighted ? where : spec.model == FGOICP_MODEL_GICP ? "fgoicp_icp_gicp" : "fgoicp_icp_plane", &end);
+        if (rc) return rc;
+        Result full;
+        refine_result(end, &full);
+        const Mat3f Rr = Mat3f::from(full.R);
+        const Vec3f ts{full.t[0], full.t[1], full.t[2]};
+        const Vec3f tr = ts / s->scaling_factor + Rr * s->offset_pcs - s->offset_pct;  // restore_translation, fgoicp.hpp:87-90
+        full.t[0] = tr.x; full.t[1] = tr.y; full.t[2] = tr.z;
+        full.scaling_factor = s->scaling_factor;
+        return plane_out(full, out, where, type);
+    });
+}
+
 extern "C" {
 
 static int solver_create_impl(const float* tgt_xyz, size_t nt, const float* src_xyz, size_t ns, float lut_resolution, float mse_threshold, const fgoicp_solver_opts* opts,
@@ -292,25 +327,7 @@ int fgoicp_solver_refine_plane(fgoicp_solver* s, int k, size_t max_iter, float c
     if (!s->ran) { set_error("fgoicp_solver_refine_plane: fgoicp_solver_run has not succeeded yet: there is no best transform"); return FGOICP_ERR_INVALID_ARG; }
     if (!plane_size_ok(out)) { set_error("fgoicp_solver_refine_plane: out must not be null and out->struct_size = sizeof(fgoicp_plane_result_t)"); return FGOICP_ERR_INVALID_ARG; }
     if (!(max_distance >= 0.0f)) { set_error("fgoicp_solver_refine_plane: max_distance must be >= 0 (+inf: no threshold)"); return FGOICP_ERR_INVALID_ARG; }
-    return fgoicp::abi_guard("fgoicp_solver_refine_plane", [&] {
-        if (!s->ctx->normals_set) {  // normals are invariant under the solver's centring and uniform scale
-            const int rc = ctx_set_target_normals(s->ctx, nullptr, k);
-            if (rc) return rc;
-        }
-        Mat3f R;
-        Vec3f t;
-        s->driver->best_transform(R, t);  // the normalised frame the search ran in, as fgoicp_solver_information
-        const float t3[3] = {t.x, t.y, t.z};
-        fgoicp_plane_result_t full;
-        const int rc = ctx_icp_plane(s->ctx, R.m, t3, max_iter, conv_thr, information_max_dist2(max_distance, s->scaling_factor), &full);
-        if (rc) return rc;
-        const Mat3f Rr = Mat3f::from(full.R);
-        const Vec3f ts{full.t[0], full.t[1], full.t[2]};
-        const Vec3f tr = ts / s->scaling_factor + Rr * s->offset_pcs - s->offset_pct;  // restore_translation, fgoicp.hpp:87-90
-        full.t[0] = tr.x; full.t[1] = tr.y; full.t[2] = tr.z;
-        full.scaling_factor = s->scaling_factor;
-        return plane_out(full, out, "fgoicp_solver_refine_plane", "fgoicp_plane_result_t");
-    });
+    return solver_refine(s, "fgoicp_solver_refine_plane", RefineSpec{}, max_distance, k, max_iter, conv_thr, "fgoicp_plane_result_t", out);
 }
 
 int fgoicp_solver_refine_gicp(fgoicp_solver* s, int k, size_t max_iter, float conv_thr, float max_distance, double epsilon, fgoicp_plane_result_t* out) {
@@ -319,29 +336,9 @@ int fgoicp_solver_refine_gicp(fgoicp_solver* s, int k, size_t max_iter, float co
     if (!plane_size_ok(out)) { set_error("fgoicp_solver_refine_gicp: out must not be null and out->struct_size = sizeof(fgoicp_plane_result_t)"); return FGOICP_ERR_INVALID_ARG; }
     if (!(max_distance >= 0.0f)) { set_error("fgoicp_solver_refine_gicp: max_distance must be >= 0 (+inf: no threshold)"); return FGOICP_ERR_INVALID_ARG; }
     if (!gicp_epsilon_ok(epsilon)) { set_error("fgoicp_solver_refine_gicp: epsilon must be finite and lie in (0, 1]"); return FGOICP_ERR_INVALID_ARG; }
-    return fgoicp::abi_guard("fgoicp_solver_refine_gicp", [&] {
-        if (!s->ctx->normals_set) {  // normals are invariant under the solver's centring and uniform scale
-            const int rc = ctx_set_target_normals(s->ctx, nullptr, k);
-            if (rc) return rc;
-        }
-        if (!s->ctx->src_normals_set) {
-            const int rc = ctx_set_source_normals(s->ctx, nullptr, k);
-            if (rc) return rc;
-        }
-        Mat3f R;
-        Vec3f t;
-        s->driver->best_transform(R, t);  // the normalised frame the search ran in, as fgoicp_solver_refine_plane
-        const float t3[3] = {t.x, t.y, t.z};
-        fgoicp_plane_result_t full;
-        const int rc = ctx_icp_gicp(s->ctx, R.m, t3, max_iter, conv_thr, information_max_dist2(max_distance, s->scaling_factor), epsilon, &full);
-        if (rc) return rc;
-        const Mat3f Rr = Mat3f::from(full.R);
-        const Vec3f ts{full.t[0], full.t[1], full.t[2]};
-        const Vec3f tr = ts / s->scaling_factor + Rr * s->offset_pcs - s->offset_pct;  // restore_translation, fgoicp.hpp:87-90
-        full.t[0] = tr.x; full.t[1] = tr.y; full.t[2] = tr.z;
-        full.scaling_factor = s->scaling_factor;
-        return plane_out(full, out, "fgoicp_solver_refine_gicp", "fgoicp_plane_result_t");
-    });
+    RefineSpec spec;
+    spec.model = FGOICP_MODEL_GICP; spec.epsilon = epsilon;
+    return solver_refine(s, "fgoicp_solver_refine_gicp", spec, max_distance, k, max_iter, conv_thr, "fgoicp_plane_result_t", out);
 }
 
 int fgoicp_solver_refine_robust(fgoicp_solver* s, int model, int k, size_t max_iter, float conv_thr, float max_distance, double epsilon, int loss, double loss_scale,
@@ -354,33 +351,9 @@ int fgoicp_solver_refine_robust(fgoicp_solver* s, int model, int k, size_t max_i
     if (!robust_loss_ok(loss)) { set_error("fgoicp_solver_refine_robust: unknown loss " + std::to_string(loss)); return FGOICP_ERR_INVALID_ARG; }
     if (model == FGOICP_MODEL_GICP && !gicp_epsilon_ok(epsilon)) { set_error("fgoicp_solver_refine_robust: epsilon must be finite and lie in (0, 1]"); return FGOICP_ERR_INVALID_ARG; }
     if (!std::isfinite(loss_scale)) { set_error("fgoicp_solver_refine_robust: loss_scale must be finite (<= 0: estimated)"); return FGOICP_ERR_INVALID_ARG; }
-    return fgoicp::abi_guard("fgoicp_solver_refine_robust", [&] {
-        if (!s->ctx->normals_set) {  // normals are invariant under the solver's centring and uniform scale
-            const int rc = ctx_set_target_normals(s->ctx, nullptr, k);
-            if (rc) return rc;
-        }
-        if (model == FGOICP_MODEL_GICP && !s->ctx->src_normals_set) {
-            const int rc = ctx_set_source_normals(s->ctx, nullptr, k);
-            if (rc) return rc;
-        }
-        Mat3f R;
-        Vec3f t;
-        s->driver->best_transform(R, t);  // the normalised frame the search ran in, as fgoicp_solver_refine_plane
-        const float t3[3] = {t.x, t.y, t.z};
-        RobustSpec r;
-        r.model = model; r.epsilon = epsilon; r.loss = loss;
-        r.scale = loss_scale > 0.0 ? loss_scale * (double)s->scaling_factor : 0.0;  // a residual of either model scales with the frame
-        r.max_dist2 = information_max_dist2(max_distance, s->scaling_factor);
-        fgoicp_robust_result_t full;
-        const int rc = ctx_icp_robust(s->ctx, R.m, t3, max_iter, conv_thr, r, &full, "fgoicp_solver_refine_robust");
-        if (rc) return rc;
-        const Mat3f Rr = Mat3f::from(full.R);
-        const Vec3f ts{full.t[0], full.t[1], full.t[2]};
-        const Vec3f tr = ts / s->scaling_factor + Rr * s->offset_pcs - s->offset_pct;  // restore_translation, fgoicp.hpp:87-90
-        full.t[0] = tr.x; full.t[1] = tr.y; full.t[2] = tr.z;
-        full.scaling_factor = s->scaling_factor;
-        return plane_out(full, out, "fgoicp_solver_refine_robust", "fgoicp_robust_result_t");
-    });
+    RefineSpec spec;
+    spec.model = model; spec.epsilon = epsilon; spec.weighted = true; spec.loss = loss; spec.scale = loss_scale;
+    return solver_refine(s, "fgoicp_solver_refine_robust", spec, max_distance, k, max_iter, conv_thr, "fgoicp_robust_result_t", out);
 }
 
 int fgoicp_robust_weight(int loss, double s, double scale, double* w) { return robust_weight_entry(loss, s, scale, w); }

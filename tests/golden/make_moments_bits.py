@@ -1,9 +1,10 @@
 """Records tests/golden/moments_bits.npz: the bytes that fgoicp_plane_moments and fgoicp_gicp_moments return.
 
-The moved queries of plane_moments_kernel and gicp_moments_kernel never leave the device, so their fixed-order fp64 sums cannot be
-restated from the caller's side the way oracle/np_restatement.py::fixed_order_sum restates fgoicp_information's.  The tolerance of
-tests/test_gpu_plane.py and tests/test_gpu_gicp.py (16 x 2^-24 x sum |term|) would not notice a changed order of additions either.  This
-fixture pins the bytes instead: tests/test_gpu_moments_bits.py asks the current build for the same structs.
+The moved queries of plane_moments_kernel and gicp_moments_kernel (today the unweighted instantiations of refine_moments_kernel) never
+leave the device, so their fixed-order fp64 sums cannot be restated from the caller's side the way oracle/np_restatement.py::fixed_order_sum
+restates fgoicp_information's.  The tolerance of tests/test_gpu_plane.py and tests/test_gpu_gicp.py (16 x 2^-24 x sum |term|) would not
+notice a changed order of additions either.  This fixture pins the bytes instead: tests/test_gpu_moments_bits.py asks the current build
+for the same structs.
 
 Cases: the plane tests' two sizes, (nt, ns) = (2500, 700) and (1100, 300); untrimmed, and trimmed at 0.8 ns (with FGOICP_FLAG_CURVE_ORDER,
 as those tests run it); at the true pose and at the tests' 5 degrees off pose; max_dist2 = inf and the median dist2 of the report; normals

@@ -1,5 +1,5 @@
 """GPU: Generalized-ICP refinement with device-estimated source normals — the source normals (target_knn_kernel over a throw-away tree of
-the source) against numpy.linalg.eigh of brute-force neighbourhoods, the normal equations (gicp_moments_kernel, moment_fold_kernel)
+the source) against numpy.linalg.eigh of brute-force neighbourhoods, the normal equations (refine_moments_kernel, moment_fold_kernel)
 against an fp64 numpy sum over the alignment report, the loop against a numpy restatement of it, the solver entry point and the CLI."""
 import ctypes as C
 import os

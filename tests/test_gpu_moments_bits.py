@@ -1,6 +1,6 @@
 """GPU: fgoicp_plane_moments and fgoicp_gicp_moments return the bytes recorded in tests/golden/moments_bits.npz (recorded by
 tests/golden/make_moments_bits.py before the three moment kernels came to share csrc/device/fixed_sum.hpp).  The moved queries of
-plane_moments_kernel and gicp_moments_kernel stay on the device, so the fixed order of their fp64 additions is pinned by recorded bytes
+the two kernels (today the unweighted instantiations of refine_moments_kernel) stay on the device, so the fixed order of their fp64 additions is pinned by recorded bytes
 rather than by oracle/np_restatement.py fixed_order_sum; the fixture holds every input, and nothing here is computed from the clouds'
 generator."""
 import os

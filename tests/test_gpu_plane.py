@@ -1,5 +1,5 @@
 """GPU: point-to-plane refinement with device-estimated target normals — the exact k-nearest-neighbour sets of the target's own tree
-(target_knn_kernel) against a numpy brute force, the normals against numpy.linalg.eigh, the normal equations (plane_moments_kernel,
+(target_knn_kernel) against a numpy brute force, the normals against numpy.linalg.eigh, the normal equations (refine_moments_kernel,
 moment_fold_kernel of csrc/device/fixed_sum.hpp) against an fp64 numpy sum over the alignment report, the loop against a numpy restatement of it, the solver
 entry point and the CLI."""
 import ctypes as C

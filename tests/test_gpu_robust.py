@@ -1,5 +1,5 @@
 """GPU: robust losses for the point-to-plane and Generalized-ICP refinements — the per-point residuals, weights and
-counted set of robust_moments_kernel against numpy on the alignment report, the weighted normal equations against fp64 sums of the device's
+counted set of refine_moments_kernel (weighted) against numpy on the alignment report, the weighted normal equations against fp64 sums of the device's
 own weights times numpy's terms, the automatic scale, the edges (every weight zero, one point, one slot into a new block, a trimmed
 context), the loop against the plain loop and a numpy restatement on a source with 20 % stray points, the solver entry point and the CLI."""
 import ctypes as C
