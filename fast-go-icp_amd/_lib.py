@@ -78,6 +78,17 @@ class BatchOptsInformation(BatchOpts):
                 ("information_max_distance", C.c_float)]  # callers' units; <= 0: no threshold
 
 
+class BatchRefine(C.Structure):
+    """fgoicp_batch_refine_t: how one pair of a batch is refined after its search; model = -1: not at all."""
+    _fields_ = [("struct_size", C.c_uint32), ("model", C.c_int), ("k", C.c_int), ("max_iter", C.c_size_t), ("conv_thr", C.c_float), ("max_distance", C.c_float),
+                ("epsilon", C.c_double), ("loss", C.c_int), ("loss_scale", C.c_double)]
+
+
+class BatchOptsRefine(BatchOptsInformation):
+    """fgoicp_batch_opts_refine: fgoicp_batch_opts (56 bytes, as published) followed by the refine table (n entries or NULL)."""
+    _fields_ = [("refine", C.POINTER(BatchRefine))]
+
+
 class AlignmentSummary(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("points", C.c_uint64), ("inliers", C.c_uint64), ("targets_hit", C.c_uint64), ("sse", C.c_float),
                 ("max_inlier_dist2", C.c_float), ("scaling_factor", C.c_float)]
@@ -316,6 +327,12 @@ _SIGS = {
     "fgoicp_batch_best_error": (C.c_int, [C.c_void_p, C.c_int, c_float_p]),
     "fgoicp_batch_stats": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RunStats)]),
     "fgoicp_batch_launches": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "fgoicp_batch_refined_plane": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(PlaneResult)]),
+    "fgoicp_batch_refined_robust": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RobustResult)]),
+    "fgoicp_batch_refined_information": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Information)]),
+    "fgoicp_batch_refine_launches": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "fgoicp_batch_test_refine": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(BatchRefine), c_int_p, c_float_p, c_float_p, C.POINTER(RobustResult), c_int_p,
+                                           C.c_char_p, C.POINTER(C.c_uint64)]),
     "fgoicp_batch_destroy": (None, [C.c_void_p]),
     "fgoicp_batch_test_bounds": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, c_int_p, c_int_p, c_float_p, c_float_p, c_int_p, c_int_p, c_float_p,
                                            c_float_p, c_float_p, C.POINTER(C.c_uint64)]),

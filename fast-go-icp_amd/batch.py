@@ -6,16 +6,55 @@ import numpy as np
 
 from . import _lib
 from .nodes import from_glm
-from .registration import _alignment, _cloud, _fp, _information
+from .registration import GicpRefinement, PlaneRefinement, RobustRefinement, _alignment, _cloud, _fp, _information, _loss_code, _model_code
+
+_REFINE_DEFAULTS = {"model": "plane", "k": 16, "max_iter": 30, "conv_thr": 1e-6, "max_distance": None, "epsilon": 1e-3, "loss": None, "loss_scale": None}
+
+
+def _refine_entries(refine, n):
+    """refine= of FastGoICPBatch -> None, or a list of n entries (None, or a dict with every key of _REFINE_DEFAULTS)."""
+    if refine is None:
+        return None
+    specs = [refine] * n if isinstance(refine, dict) else list(refine)
+    if len(specs) != n:
+        raise ValueError(f"refine: {len(specs)} entries for {n} pairs (one dict for all, or a list with one dict or None per pair)")
+    out = []
+    for i, r in enumerate(specs):
+        if r is None:
+            out.append(None)
+            continue
+        unknown = set(r) - set(_REFINE_DEFAULTS)
+        if unknown:
+            raise ValueError(f"refine[{i}]: unknown keys {sorted(unknown)} (the keys are {sorted(_REFINE_DEFAULTS)})")
+        out.append({**_REFINE_DEFAULTS, **r})
+    return out
+
+
+def _refine_array(entries):
+    arr = (_lib.BatchRefine * max(1, len(entries)))()
+    for i, r in enumerate(entries):
+        arr[i].struct_size = C.sizeof(_lib.BatchRefine)
+        if r is None:
+            arr[i].model = -1
+            continue
+        arr[i].model = _model_code(r["model"])
+        arr[i].k, arr[i].max_iter, arr[i].conv_thr = int(r["k"]), int(r["max_iter"]), float(r["conv_thr"])
+        arr[i].max_distance = float("inf") if r["max_distance"] is None else float(r["max_distance"])
+        arr[i].epsilon = float(r["epsilon"])
+        arr[i].loss = _lib.LOSS_NONE if r["loss"] is None else _loss_code(r["loss"])
+        arr[i].loss_scale = 0.0 if r["loss_scale"] is None else float(r["loss_scale"])
+    return arr
 
 
 class FastGoICPBatch:
     """pairs: iterable of (pct, pcs), (pct, pcs, lut_resolution, mse_threshold) or (pct, pcs, lut_resolution, mse_threshold, trim_fraction);
     the defaults below apply to what a pair leaves out.  trim_fraction: as FastGoICP's, per pair (0 = untrimmed).  information: False, True
-    (every pair's Information without a distance threshold) or a distance in the callers' units."""
+    (every pair's Information without a distance threshold) or a distance in the callers' units.  refine: None, one dict for every pair, or
+    a list with one dict or None per pair; the keys are model ("plane" / "gicp") and the arguments of FastGoICP.refine_plane / refine_gicp
+    with their defaults: k, max_iter, conv_thr, max_distance, epsilon, loss, loss_scale (loss None or "none": the plain refinement)."""
 
     def __init__(self, pairs, lut_resolution=0.005, mse_threshold=1e-3, schedule=_lib.SCHEDULE_SERIAL, round_width=1, device=0, flags=0,
-                 max_live=0, trim_fraction=0.0, alignment=False, information=False):
+                 max_live=0, trim_fraction=0.0, alignment=False, information=False, refine=None):
         self._lib = _lib.load()
         self._clouds = []
         self._sizes = []
@@ -29,9 +68,13 @@ class FastGoICPBatch:
             self._sizes.append((len(pcs), len(pct)))
             arr[i] = _lib.BatchPair(_fp(pct), len(pct), _fp(pcs), len(pcs), float(lr), float(mt))
         self.n = len(pairs)
-        opts = _lib.BatchOptsInformation(C.sizeof(_lib.BatchOptsInformation), _lib.SolverOpts(int(schedule), int(round_width), int(flags), int(device), 0.0), int(max_live),
+        self._refine = _refine_entries(refine, self.n)
+        rarr = None if self._refine is None else _refine_array(self._refine)
+        opts = _lib.BatchOptsRefine(C.sizeof(_lib.BatchOptsRefine), _lib.SolverOpts(int(schedule), int(round_width), int(flags), int(device), 0.0), int(max_live),
                               _fp(trim), int(bool(alignment)), int(information is not False and information is not None),
                               0.0 if isinstance(information, bool) or information is None else float(information))
+        if rarr is not None:
+            opts.refine = rarr
         self._h = C.c_void_p()
         _lib.check(self._lib.fgoicp_batch_create(arr, self.n, C.byref(opts), C.byref(self._h)), "fgoicp_batch_create")
         self._clouds = None
@@ -79,6 +122,30 @@ class FastGoICPBatch:
         """EXTENSION (fgoicp_batch_information; needs information=True or a distance): pair i's Information at its best transform, what
         FastGoICP.information(distance) returns for that pair alone."""
         return _information(lambda out: self._lib.fgoicp_batch_information(self._h, int(i), out), "fgoicp_batch_information")
+
+    def refined(self, i):
+        """EXTENSION (fgoicp_batch_refined_plane / _robust; needs refine=): pair i's refinement from its best transform, the object
+        FastGoICP.refine_plane / refine_gicp returns for that pair alone with the same arguments."""
+        r = self._refine[i] if self._refine is not None else None
+        model = _lib.MODEL_PLANE if r is None else _model_code(r["model"])
+        if r is not None and r["loss"] is not None and _loss_code(r["loss"]) != _lib.LOSS_NONE:
+            raw = _lib.RobustResult()
+            _lib.check(self._lib.fgoicp_batch_refined_robust(self._h, int(i), C.byref(raw)), "fgoicp_batch_refined_robust")
+            return RobustRefinement(raw, model)
+        raw = _lib.PlaneResult()
+        _lib.check(self._lib.fgoicp_batch_refined_plane(self._h, int(i), C.byref(raw)), "fgoicp_batch_refined_plane")
+        return GicpRefinement(raw) if model == _lib.MODEL_GICP else PlaneRefinement(raw)
+
+    def refined_information(self, i):
+        """EXTENSION (fgoicp_batch_refined_information; needs information= and refine=): pair i's Information at its REFINED pose;
+        information(i) stays the search's."""
+        return _information(lambda out: self._lib.fgoicp_batch_refined_information(self._h, int(i), out), "fgoicp_batch_refined_information")
+
+    def refine_launches(self):
+        """-> (fused refinement moment launches, refinement evaluations) of the last run."""
+        b = C.c_uint64(); c = C.c_uint64()
+        _lib.check(self._lib.fgoicp_batch_refine_launches(self._h, C.byref(b), C.byref(c)), "fgoicp_batch_refine_launches")
+        return int(b.value), int(c.value)
 
     def launches(self):
         """-> (fused bounds launches, lock-step ICP iterations) of the last run."""

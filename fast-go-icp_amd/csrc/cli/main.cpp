@@ -13,6 +13,7 @@
 
 #include "../../../include/fgoicp/fgoicp.hpp"
 #include "config.hpp"
+#include "../host/refined_pose.hpp"
 
 static std::string usage(const std::string& exe) {
     return "Fast Go-ICP: an MI355X (HIP) implementation of Go-ICP\nUsage: " + exe + " [OPTIONS]\n\nOptions:\n"
@@ -156,9 +157,34 @@ static void farthest_sample(std::vector<icp::vec3>& pc, int points, const char* 
     pc.swap(out);
 }
 
+// a robust result as the [refined] table and the log line take it: the fields fgoicp_plane_result_t shares
+static void plane_from_robust(const fgoicp_robust_result_t& robust, fgoicp_plane_result_t& refined) {
+    std::memcpy(refined.R, robust.R, sizeof(refined.R));
+    std::memcpy(refined.t, robust.t, sizeof(refined.t));
+    refined.iterations = robust.iterations; refined.rank = robust.rank; refined.correspondences = robust.correspondences;
+    refined.plane_rmse = robust.rmse; refined.sse = robust.sse; refined.scaling_factor = robust.scaling_factor;
+}
+// the refinement's log line (a lone run's, or with a batch's "Pair i: " in front)
+static void log_refinement(const std::string& prefix, const cli::Config& config, const fgoicp_plane_result_t& refined, const fgoicp_robust_result_t* robust) {
+    const bool gicp = config.params.refine == "gicp";
+    icp::mat3 Rr;
+    std::memcpy(Rr.data(), refined.R, sizeof(refined.R));
+    icp::Logger log(icp::LogLevel::Info);
+    log << prefix << (gicp ? "Generalized-ICP" : "Point-to-plane") << " refinement: " << refined.iterations << " iterations, rank " << refined.rank << ", "
+        << refined.correspondences << " correspondences, ";
+    if (gicp) log << "epsilon " << config.params.refine_epsilon << ", plane-to-plane RMSE ";
+    else log << "plane RMSE ";
+    log << refined.plane_rmse / (double)refined.scaling_factor;
+    if (robust)
+        log << ", " << config.params.refine_loss << " loss, scale " << robust->scale / (double)robust->scaling_factor << (robust->scale_estimated ? " (estimated)" : " (given)")
+            << ", weight " << robust->weight_sum << " of " << robust->correspondences;
+    log << "\n\tRotation:\n" << Rr << "\n\tTranslation: " << icp::vec3{refined.t[0], refined.t[1], refined.t[2]};
+}
+
 // --batch LIST: every config of the list registered in one fgoicp_batch run; each config's io.output / io.visualization as a lone -c run
 // of it writes them (the seconds written are the batch's).  The configs must agree on the schedule and round width; each is trimmed with
-// its own params.trim_fraction.
+// its own params.trim_fraction and refined with its own params.refine* (fgoicp_batch_opts_refine.refine): the refinement's log line, the
+// [refined] table and io.information at the refined pose as a lone run of it.
 static int run_batch(const std::string& list_file) {
     std::ifstream lf(list_file);
     if (!lf) { icp::Logger(icp::LogLevel::Error) << "Unable to read " << list_file; return 1; }
@@ -174,7 +200,6 @@ static int run_batch(const std::string& list_file) {
             icp::Logger(icp::LogLevel::Error) << e.what();
             return 1;
         }
-        if (!configs.back().params.refine.empty()) { icp::Logger(icp::LogLevel::Error) << "--batch: params.refine is not supported in a batch"; return 1; }
     }
     if (configs.empty()) { icp::Logger(icp::LogLevel::Error) << "--batch: " << list_file << " lists no config"; return 1; }
     const cli::Config& c0 = configs[0];
@@ -210,8 +235,9 @@ static int run_batch(const std::string& list_file) {
         trim[i] = c.params.trim_fraction;
     }
     const int schedule = c0.params.schedule == "round" ? FGOICP_SCHEDULE_ROUND : FGOICP_SCHEDULE_SERIAL;
-    fgoicp_batch_opts o{};
-    o.struct_size = sizeof(o);
+    fgoicp_batch_opts_refine with_refine{};
+    fgoicp_batch_opts& o = with_refine.opts;
+    o.struct_size = sizeof(with_refine);
     o.solver = fgoicp_solver_opts{schedule, c0.params.round_width, 0u, 0, 0.0f};
     o.trim_fractions = trim.data();
     for (const cli::Config& c : configs) o.alignment |= c.io.alignment.empty() ? 0 : 1;  // the reports are kept only if a config asks for one
@@ -224,6 +250,24 @@ static int run_batch(const std::string& list_file) {
         o.information = 1;
         o.information_max_distance = c.params.information_distance;
     }
+    std::vector<fgoicp_batch_refine_t> refine(n);
+    bool any_refine = false;
+    for (size_t i = 0; i < n; ++i) {
+        const cli::Config& c = configs[i];
+        fgoicp_batch_refine_t& r = refine[i];
+        r.struct_size = sizeof(r);
+        r.model = c.params.refine == "gicp" ? FGOICP_MODEL_GICP : c.params.refine == "plane" ? FGOICP_MODEL_PLANE : -1;
+        if (r.model < 0) continue;
+        any_refine = true;
+        r.k = c.params.refine_knn;
+        r.max_iter = (size_t)c.params.refine_max_iter;
+        r.conv_thr = 1e-6f;
+        r.max_distance = c.params.refine_distance > 0.0f ? c.params.refine_distance : INFINITY;
+        r.epsilon = c.params.refine_epsilon;
+        r.loss = c.params.refine_loss_code();
+        r.loss_scale = c.params.refine_loss_scale;
+    }
+    if (any_refine) with_refine.refine = refine.data();
     fgoicp_batch* b = nullptr;
     icp::check_status(fgoicp_batch_create(pairs.data(), (int)n, &o, &b), "fgoicp_batch_create");
     std::vector<float> R9(9 * n), t3(3 * n);
@@ -244,7 +288,21 @@ static int run_batch(const std::string& list_file) {
         icp::check_status(fgoicp_batch_stats(b, (int)i, &st), "fgoicp_batch_stats");
         icp::Logger(icp::LogLevel::Info) << "Pair " << i << ": Best Error: " << best_error << "\n\tRotation:\n" << R << "\n\tTranslation: " << t;
         const cli::Config& c = configs[i];
-        if (!c.io.output.empty()) cli::write_result_toml(c.io.output, R, t, best_error, pcs[i].size(), elapsed.count(), st);
+        fgoicp_plane_result_t refined{};
+        fgoicp_robust_result_t robust{};
+        const bool have_refined = refine[i].model >= 0, have_robust = have_refined && refine[i].loss != FGOICP_LOSS_NONE;
+        if (have_robust) {
+            robust.struct_size = sizeof(robust);
+            icp::check_status(fgoicp_batch_refined_robust(b, (int)i, &robust), "fgoicp_batch_refined_robust");
+            plane_from_robust(robust, refined);
+        } else if (have_refined) {
+            refined.struct_size = sizeof(refined);
+            icp::check_status(fgoicp_batch_refined_plane(b, (int)i, &refined), "fgoicp_batch_refined_plane");
+        }
+        if (have_refined) log_refinement("Pair " + std::to_string(i) + ": ", c, refined, have_robust ? &robust : nullptr);
+        if (!c.io.output.empty())
+            cli::write_result_toml(c.io.output, R, t, best_error, pcs[i].size(), elapsed.count(), st, have_refined ? &refined : nullptr, c.params.refine == "gicp" ? "gicp_rmse" : "plane_rmse",
+                                   have_robust ? &robust : nullptr, c.params.refine_loss.c_str());
         if (!c.io.visualization.empty()) cli::write_visualization_ply(c.io.visualization, pct[i], pcs[i], R, t);
         if (!c.io.alignment.empty()) {
             std::vector<uint32_t> idx(pcs[i].size());
@@ -258,7 +316,8 @@ static int run_batch(const std::string& list_file) {
         if (!c.io.information.empty()) {
             fgoicp_information_t inf{};
             inf.struct_size = sizeof(inf);
-            icp::check_status(fgoicp_batch_information(b, (int)i, &inf), "fgoicp_batch_information");
+            if (have_refined) icp::check_status(fgoicp_batch_refined_information(b, (int)i, &inf), "fgoicp_batch_refined_information");  // as a lone run: at the refined pose
+            else icp::check_status(fgoicp_batch_information(b, (int)i, &inf), "fgoicp_batch_information");
             cli::write_information_txt(c.io.information, inf, c.params.information_distance);
         }
     }
@@ -368,10 +427,7 @@ int main(int argc, char* argv[]) {
             robust.struct_size = sizeof(robust);
             icp::check_status(fgoicp_solver_refine_robust(s, gicp ? FGOICP_MODEL_GICP : FGOICP_MODEL_PLANE, knn, max_iter, 1e-6f, d, config.params.refine_epsilon, loss,
                                                           config.params.refine_loss_scale, &robust), "fgoicp_solver_refine_robust");
-            std::memcpy(refined.R, robust.R, sizeof(refined.R));
-            std::memcpy(refined.t, robust.t, sizeof(refined.t));
-            refined.iterations = robust.iterations; refined.rank = robust.rank; refined.correspondences = robust.correspondences;
-            refined.plane_rmse = robust.rmse; refined.sse = robust.sse; refined.scaling_factor = robust.scaling_factor;
+            plane_from_robust(robust, refined);
             have_robust = true;
         } else if (gicp) {
             icp::check_status(fgoicp_solver_refine_gicp(s, knn, max_iter, 1e-6f, d, config.params.refine_epsilon, &refined), "fgoicp_solver_refine_gicp");
@@ -379,22 +435,11 @@ int main(int argc, char* argv[]) {
             icp::check_status(fgoicp_solver_refine_plane(s, knn, max_iter, 1e-6f, d, &refined), "fgoicp_solver_refine_plane");
         }
         have_refined = true;
-        icp::mat3 Rr;
-        std::memcpy(Rr.data(), refined.R, sizeof(refined.R));
-        icp::Logger log(icp::LogLevel::Info);
-        log << (gicp ? "Generalized-ICP" : "Point-to-plane") << " refinement: " << refined.iterations << " iterations, rank " << refined.rank << ", "
-            << refined.correspondences << " correspondences, ";
-        if (gicp) log << "epsilon " << config.params.refine_epsilon << ", plane-to-plane RMSE ";
-        else log << "plane RMSE ";
-        log << refined.plane_rmse / (double)refined.scaling_factor;
-        if (have_robust)
-            log << ", " << config.params.refine_loss << " loss, scale " << robust.scale / (double)robust.scaling_factor << (robust.scale_estimated ? " (estimated)" : " (given)")
-                << ", weight " << robust.weight_sum << " of " << robust.correspondences;
-        log << "\n\tRotation:\n" << Rr << "\n\tTranslation: " << icp::vec3{refined.t[0], refined.t[1], refined.t[2]};
+        log_refinement("", config, refined, have_robust ? &robust : nullptr);
     };
     // io.information: the information matrix in the files' frame — at the best transform, or at the refined pose when there is one: then
     // from the context at that pose in the solver's frame (the restored translation taken back, t_s = (t - R offset_pcs + offset_pct) * scale)
-    // and converted as fgoicp_solver_information converts (fgoicp_information_from_moments)
+    // and converted as fgoicp_solver_information converts (fgoicp_information_from_moments): refined_pose.hpp, the text a batch runs too
     auto write_information = [&](fgoicp_solver* s) {
         if (config.io.information.empty()) return;
         fgoicp_information_t inf{};
@@ -405,14 +450,7 @@ int main(int argc, char* argv[]) {
         } else {
             float offs[6], scale = 1.0f;
             icp::check_status(fgoicp_solver_preproc(s, offs, &scale, nullptr), "fgoicp_solver_preproc");
-            const float* Q = refined.R;
-            float ts[3];
-            for (int r = 0; r < 3; ++r) ts[r] = (refined.t[r] - (Q[r] * offs[0] + Q[3 + r] * offs[1] + Q[6 + r] * offs[2]) + offs[3 + r]) * scale;
-            const float ds = d * scale;
-            icp::check_status(fgoicp_information(fgoicp_solver_ctx(s), refined.R, ts, d > 0.0f ? ds * ds : INFINITY, &inf), "fgoicp_information");
-            const float c3[3] = {-offs[3], -offs[4], -offs[5]};
-            icp::check_status(fgoicp_information_from_moments(inf.correspondences, inf.sum_q, inf.sum_qq, c3, scale, inf.info, inf.sum_q, inf.sum_qq), "fgoicp_information_from_moments");
-            inf.scaling_factor = scale;
+            icp::check_status(fgoicp::refined_information(fgoicp_solver_ctx(s), refined.R, refined.t, offs, scale, d, &inf), "fgoicp_information at the refined pose");
         }
         cli::write_information_txt(config.io.information, inf, d);
     };

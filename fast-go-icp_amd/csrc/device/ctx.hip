@@ -737,25 +737,47 @@ int refine_refusals(const fgoicp_ctx* c, const RefineSpec& r, ScaleCheck scale, 
     if (r.model == FGOICP_MODEL_GICP && !c->src_normals_set) { set_error(w + ": the source normals are not set: call fgoicp_ctx_set_source_normals first"); return FGOICP_ERR_INVALID_ARG; }
     return FGOICP_OK;
 }
-// One evaluation at (R, t), enqueued behind the report's device half on lane 0's stream like the information moments: reads the report's
-// arrays, the moved queries the index scan left in d_work, the target and the normals; writes its own rows only.  The per-point outputs
-// are stored by the kernel only when a caller asks.
+// One evaluation at (R, t) in two halves.  The enqueue half: the pair's rows, then the report's device half on lane 0's stream (its index
+// scan keeps the moved queries) — nothing is waited for, on trimmed and brute-force contexts too.  What reduces the moments behind it is the
+// caller's: the context's own launch (refine_evaluate) or a batch's fused one over refine_inputs (ctx_refine_step_enqueue).
+static int refine_enqueue(fgoicp_ctx* c, const float* R9, const float* t3, const RefineSpec& r) {
+    const size_t nb = (c->ns + kBlock - 1) / kBlock;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(r.weighted ? c->d_robust_rows.ensure(nb) : c->d_plane_rows.ensure(nb));
+    return alignment_enqueue(c, R9, t3, true);
+}
+// what the moments kernel reads: the report's arrays, the moved queries the index scan left in d_work, the target and the normals
+static RefineInputs refine_inputs(const fgoicp_ctx* c, const RefineSpec& r) {
+    const fgoicp_ctx::IcpLane& L = c->lanes[0];
+    const fgoicp_ctx::AlignScratch& A = c->align;
+    return RefineInputs{L.d_work, c->d_orig_of_slot, A.d_inl, A.d_d2, A.d_corr, c->d_tgt, c->d_normals, c->d_src_normals, (int)c->ns, (int)c->nt, r.max_dist2};
+}
+// The collect half, behind a wait that covers lane 0's stream: h = {n, the bits of the 28 or 29 sums} as the fold left them; unweighted,
+// m->m[28] is the count.  sse_out (optional): the report's sse.
+static void refine_collect(const fgoicp_ctx* c, const RefineSpec& r, const unsigned long long* h, RefineMoments* m, float* sse_out) {
+    static_assert(kRobustTerms == kRobustMoments && kPlaneTerms == kPlaneMoments && kRobustTerms == kPlaneTerms + 1, "the device's rows and the host's moments are the same terms");
+    const size_t K = r.weighted ? kRobustTerms : kPlaneTerms;
+    m->n = h[0];
+    std::memcpy(m->m, h + 1, sizeof(double) * K);
+    if (!r.weighted) m->m[kPlaneMoments] = (double)m->n;  // every counted pair weighs 1
+    if (sse_out) *sse_out = sse_result(c, c->lanes[0]);
+}
+// One evaluation on the context alone: the two halves around its own launch, one wait.  The per-point outputs are stored by the kernel
+// only when a caller asks.
 int refine_evaluate(fgoicp_ctx* c, const float* R9, const float* t3, const RefineSpec& r, RefineMoments* m, float* sse_out, double* residual, double* weight,
                     unsigned char* counted) {
     const bool per_point = residual || weight || counted;
-    const size_t ns = c->ns, nb = (ns + kBlock - 1) / kBlock;
+    const size_t ns = c->ns;
     HIPCHK(hipSetDevice(c->device));
-    HIPCHK(r.weighted ? c->d_robust_rows.ensure(nb) : c->d_plane_rows.ensure(nb));
     HIPCHK(c->d_refine_out.ensure(1 + kRobustTerms));
     if (per_point) {
         HIPCHK(c->d_robust_point.ensure(2 * ns));
         HIPCHK(c->d_robust_counted.ensure(ns));
     }
-    const int rc = alignment_enqueue(c, R9, t3, true);
+    const int rc = refine_enqueue(c, R9, t3, r);
     if (rc) return rc;
     fgoicp_ctx::IcpLane& L = c->lanes[0];
-    fgoicp_ctx::AlignScratch& A = c->align;
-    const RefineInputs in{L.d_work, c->d_orig_of_slot, A.d_inl, A.d_d2, A.d_corr, c->d_tgt, c->d_normals, c->d_src_normals, (int)ns, (int)c->nt, r.max_dist2};
+    const RefineInputs in = refine_inputs(c, r);
     const bool gicp = r.model == FGOICP_MODEL_GICP;
     double* const d_res = per_point ? (double*)c->d_robust_point : nullptr;
     if (r.weighted)
@@ -765,17 +787,13 @@ int refine_evaluate(fgoicp_ctx* c, const float* R9, const float* t3, const Refin
         launch_refine_moments<kPlaneTerms>(in, gicp, R9, r.epsilon, FGOICP_LOSS_NONE, 1.0, c->d_plane_rows, c->d_refine_out, nullptr, nullptr, nullptr, L.stream);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(L.stream));
-    static_assert(kRobustTerms == kRobustMoments && kPlaneTerms == kPlaneMoments && kRobustTerms == kPlaneTerms + 1, "the device's rows and the host's moments are the same terms");
     const size_t K = r.weighted ? kRobustTerms : kPlaneTerms;
     unsigned long long h[1 + kRobustTerms];
     HIPCHK(hipMemcpy(h, c->d_refine_out, sizeof(h[0]) * (1 + K), hipMemcpyDeviceToHost));
-    m->n = h[0];
-    std::memcpy(m->m, h + 1, sizeof(double) * K);
-    if (!r.weighted) m->m[kPlaneMoments] = (double)m->n;  // every counted pair weighs 1
+    refine_collect(c, r, h, m, sse_out);
     if (residual) HIPCHK(hipMemcpy(residual, d_res, sizeof(double) * ns, hipMemcpyDeviceToHost));
     if (weight) HIPCHK(hipMemcpy(weight, d_res + ns, sizeof(double) * ns, hipMemcpyDeviceToHost));
     if (counted) HIPCHK(hipMemcpy(counted, c->d_robust_counted, ns, hipMemcpyDeviceToHost));
-    if (sse_out) *sse_out = sse_result(c, L);
     return FGOICP_OK;
 }
 int ctx_robust_scale(fgoicp_ctx* c, const float* R9, const float* t3, const RefineSpec& r, double* scale, const char* where) {
@@ -797,8 +815,13 @@ int ctx_robust_scale(fgoicp_ctx* c, const float* R9, const float* t3, const Refi
 // fgoicp_icp_plane, fgoicp_icp_gicp, fgoicp_icp_robust: evaluate, solve, update (plane.hpp), until the step is short, the first solve is
 // rank-deficient, nothing is counted, the weights sum to 0 or max_iter steps are done; the end's moments and sse are those of one more
 // evaluation at the pose returned.  A weighted loss without a scale > 0: estimated at (R0, t0) first.
-int refine_loop(fgoicp_ctx* c, const float* R0, const float* t0, size_t max_iter, float thr, const RefineSpec& spec, const char* where, RefineEnd* end) {
-    RefineEnd e;
+// The loop's state before its first evaluation (the scale estimate is one evaluation of its own, ctx_robust_scale, whole).
+static int refine_run_begin(fgoicp_ctx* c, RefineStepRun& s, const float* R0, const float* t0, size_t max_iter, float thr, const RefineSpec& spec, const char* where) {
+    s = RefineStepRun();
+    s.max_iter = max_iter;
+    s.thr = thr;
+    s.where = where;
+    RefineEnd& e = s.end;
     e.spec = spec;
     if (spec.weighted && spec.loss != FGOICP_LOSS_NONE && !(spec.scale > 0.0)) {
         const int rc = ctx_robust_scale(c, R0, t0, spec, &e.spec.scale, where);
@@ -807,22 +830,74 @@ int refine_loop(fgoicp_ctx* c, const float* R0, const float* t0, size_t max_iter
     }
     e.R = Mat3f::from(R0);
     e.t = Vec3f{t0[0], t0[1], t0[2]};
-    bool stop = false;
-    for (;;) {
-        const float t3[3] = {e.t.x, e.t.y, e.t.z};
-        const int rc = refine_evaluate(c, e.R.m, t3, e.spec, &e.m, &e.sse);
-        if (rc) return rc;
-        if (stop || (size_t)e.iterations >= max_iter || e.m.n == 0 || e.m.m[28] == 0.0) break;
-        if (!plane_moments_finite(e.m.m) || !std::isfinite(e.m.m[28])) { set_error(std::string(where) + ": the normal equations are not finite"); return FGOICP_ERR_INVALID_ARG; }
-        double xi[6];
-        plane_step(e.m.m, xi, &e.rank);
-        plane_apply_step(e.R, e.t, xi, e.R, e.t);
-        ++e.iterations;
-        const double step = std::sqrt(xi[0] * xi[0] + xi[1] * xi[1] + xi[2] * xi[2]) + std::sqrt(xi[3] * xi[3] + xi[4] * xi[4] + xi[5] * xi[5]);
-        stop = step < (double)thr || (e.iterations == 1 && e.rank < 6);  // one more evaluation, at the pose returned, then out
-    }
-    *end = e;
     return FGOICP_OK;
+}
+// The host arithmetic between two evaluations, for the context's own loop and for the stepped one: s.end.m / s.end.sse hold the evaluation
+// at (s.end.R, s.end.t).  Leaves s.done set, or the next pose to evaluate.
+static int refine_run_advance(RefineStepRun& s) {
+    RefineEnd& e = s.end;
+    ++s.evaluations;
+    if (s.stop || (size_t)e.iterations >= s.max_iter || e.m.n == 0 || e.m.m[28] == 0.0) { s.done = true; return FGOICP_OK; }
+    if (!plane_moments_finite(e.m.m) || !std::isfinite(e.m.m[28])) { set_error(s.where + ": the normal equations are not finite"); return FGOICP_ERR_INVALID_ARG; }
+    double xi[6];
+    plane_step(e.m.m, xi, &e.rank);
+    plane_apply_step(e.R, e.t, xi, e.R, e.t);
+    ++e.iterations;
+    const double step = std::sqrt(xi[0] * xi[0] + xi[1] * xi[1] + xi[2] * xi[2]) + std::sqrt(xi[3] * xi[3] + xi[4] * xi[4] + xi[5] * xi[5]);
+    s.stop = step < (double)s.thr || (e.iterations == 1 && e.rank < 6);  // one more evaluation, at the pose returned, then out
+    return FGOICP_OK;
+}
+int refine_loop(fgoicp_ctx* c, const float* R0, const float* t0, size_t max_iter, float thr, const RefineSpec& spec, const char* where, RefineEnd* end) {
+    RefineStepRun s;
+    int rc = refine_run_begin(c, s, R0, t0, max_iter, thr, spec, where);
+    while (!rc && !s.done) {
+        RefineEnd& e = s.end;
+        const float t3[3] = {e.t.x, e.t.y, e.t.z};
+        rc = refine_evaluate(c, e.R.m, t3, e.spec, &e.m, &e.sse);
+        if (!rc) rc = refine_run_advance(s);
+    }
+    if (rc) return rc;
+    *end = s.end;
+    return FGOICP_OK;
+}
+// The same loop cut at its host wait (fgoicp_batch): begin, then per tick ctx_refine_step_enqueue, the batch's fused reduction of
+// *view, a wait that covers s.ready, and ctx_refine_step with the fold's output — until s.done.
+int ctx_refine_step_begin(fgoicp_ctx* c, RefineStepRun& s, const float* R0, const float* t0, size_t max_iter, float thr, const RefineSpec& spec, const char* where,
+                          int estimate_k) {
+    s = RefineStepRun();
+    if (estimate_k > 0 && !c->normals_set) {
+        const int rc = ctx_set_target_normals(c, nullptr, estimate_k);
+        if (rc) return rc;
+    }
+    if (estimate_k > 0 && spec.model == FGOICP_MODEL_GICP && !c->src_normals_set) {
+        const int rc = ctx_set_source_normals(c, nullptr, estimate_k);
+        if (rc) return rc;
+    }
+    int rc = refine_refusals(c, spec, spec.weighted ? ScaleCheck::or_estimated : ScaleCheck::none, where);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    if (!c->refine_ready) HIPCHK(c->refine_ready.create(hipEventDisableTiming));
+    return refine_run_begin(c, s, R0, t0, max_iter, thr, spec, where);
+}
+int ctx_refine_step_enqueue(fgoicp_ctx* c, const RefineStepRun& s, FusedRefineView* view) {
+    const RefineEnd& e = s.end;
+    const float t3[3] = {e.t.x, e.t.y, e.t.z};
+    const int rc = refine_enqueue(c, e.R.m, t3, e.spec);
+    if (rc) return rc;
+    HIPCHK(hipEventRecord(c->refine_ready, c->lanes[0].stream));
+    view->in = refine_inputs(c, e.spec);
+    std::memcpy(view->R, e.R.m, sizeof(view->R));
+    view->eps = e.spec.epsilon;
+    view->loss = e.spec.weighted ? e.spec.loss : FGOICP_LOSS_NONE;  // as refine_evaluate hands them to its own launch
+    view->scale = e.spec.weighted && e.spec.loss != FGOICP_LOSS_NONE ? e.spec.scale : 1.0;
+    view->rows = e.spec.weighted ? (void*)c->d_robust_rows.get() : (void*)c->d_plane_rows.get();
+    view->first_block = 0;
+    view->nblocks = (int)((c->ns + kBlock - 1) / kBlock);
+    return FGOICP_OK;
+}
+int ctx_refine_step(fgoicp_ctx* c, RefineStepRun& s, const unsigned long long* out) {
+    refine_collect(c, s.end.spec, out, &s.end.m, &s.end.sse);
+    return refine_run_advance(s);
 }
 // what fgoicp_plane_result_t and fgoicp_robust_result_t share
 template <class Result>

@@ -147,6 +147,7 @@ struct fgoicp_ctx {
     fgoicp::Dev<unsigned long long> d_refine_out;        // {count, the bits of 28 or 29 sums} (launch_refine_moments)
     fgoicp::Dev<double> d_robust_point;                  // ns residuals, then ns weights, caller order
     fgoicp::Dev<unsigned char> d_robust_counted;         // ns flags, caller order
+    fgoicp::Event refine_ready;                          // stepped refinement (ctx_refine_step_begin creates it): recorded on lane 0's stream behind an evaluation's device half
 
     // exact-NN / ICP scratch, one set per lane: ICP runs on different lanes may be in flight together (ctx_icp_batch).  Lane 0 is
     // the lane of fgoicp_sse / fgoicp_icp / fgoicp_procrustes and queues on the context's main stream.
@@ -262,6 +263,27 @@ struct RefineEnd {
 };
 // fgoicp_icp_plane, fgoicp_icp_gicp, fgoicp_icp_robust (weighted; spec.scale <= 0: estimated at (R0, t0))
 int refine_loop(fgoicp_ctx* c, const float* R0, const float* t0, size_t max_iter, float thr, const RefineSpec& spec, const char* where, RefineEnd* end);
+// One refine_loop run cut at its host wait (fgoicp_batch): refine_loop itself runs on this state, so there is one
+// loop logic.  After ctx_refine_step_begin, per tick and until `done`:
+//   ctx_refine_step_enqueue   the evaluation's device half at the run's pose on lane 0's stream, c->refine_ready recorded behind it;
+//                             *view = what the batch's fused launch reduces (first_block is the batch's to set)
+//   (the batch: its stream waits for refine_ready, launch_fused_refine_moments, one copy of the outputs, one wait)
+//   ctx_refine_step           out = the pair's {count, sums}; the sse is read here, behind that wait; then the loop's host arithmetic
+// end holds refine_loop's result, bit for bit.
+struct RefineStepRun {
+    RefineEnd end;
+    size_t max_iter = 0;
+    float thr = 0.f;
+    std::string where;
+    bool stop = false, done = false;
+    int evaluations = 0;
+};
+// begin: estimate_k > 0 estimates the normals the spec needs and the context lacks from estimate_k neighbours (as fgoicp_solver_refine_*);
+// then refine_refusals, then the scale estimate where the spec asks for one (ctx_robust_scale, whole).  Enqueues no evaluation.
+int ctx_refine_step_begin(fgoicp_ctx* c, RefineStepRun& s, const float* R0, const float* t0, size_t max_iter, float thr, const RefineSpec& spec, const char* where,
+                          int estimate_k);
+int ctx_refine_step_enqueue(fgoicp_ctx* c, const RefineStepRun& s, FusedRefineView* view);
+int ctx_refine_step(fgoicp_ctx* c, RefineStepRun& s, const unsigned long long* out);
 // `full` is filled whole (scaling_factor = 1): plane_rmse = sqrt(m[27] / N), rmse = sqrt(m[27] / sum w)
 void refine_result(const RefineEnd& e, fgoicp_plane_result_t* full);
 void refine_result(const RefineEnd& e, fgoicp_robust_result_t* full);

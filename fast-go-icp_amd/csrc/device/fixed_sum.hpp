@@ -92,9 +92,10 @@ __device__ __forceinline__ void block_moment_row(const double (&terms)[K], unsig
     }
 }
 
-// One block of 1024 threads, any number of rows: out = {the count (one 64-bit integer), the bits of the K sums}.
+// One block of 1024 threads, any number of rows: out = {the count (one 64-bit integer), the bits of the K sums}.  Every thread of the
+// block calls this (moment_fold_kernel; fused_moment_fold_kernel, one block per pair of a batch tick).
 template <int K>
-__global__ __launch_bounds__(1024) void moment_fold_kernel(const MomentRow<K>* __restrict__ rows, int nrows, unsigned long long* __restrict__ out) {
+__device__ __forceinline__ void moment_fold_block(const MomentRow<K>* __restrict__ rows, int nrows, unsigned long long* __restrict__ out) {
     __shared__ WaveSums<K, 16, unsigned long long> s;
     double v[K];
 #pragma unroll
@@ -108,6 +109,10 @@ __global__ __launch_bounds__(1024) void moment_fold_kernel(const MomentRow<K>* _
     count = wave_sums(v, count, s);
     if (threadIdx.x < K) out[1 + threadIdx.x] = (unsigned long long)__double_as_longlong(waves_in_order<16>(&s.v[0][threadIdx.x], K));
     if (threadIdx.x == 0) out[0] = count + waves_in_order<15>(s.count + 1);
+}
+template <int K>
+__global__ __launch_bounds__(1024) void moment_fold_kernel(const MomentRow<K>* __restrict__ rows, int nrows, unsigned long long* __restrict__ out) {
+    moment_fold_block<K>(rows, nrows, out);
 }
 
 }  // namespace fgoicp

@@ -2864,78 +2864,46 @@ void launch_cluster_border(const BvhView& t, int nt, float eps2, const uint32_t*
 // Reduced in the fixed order of fixed_sum.hpp (block_moment_row, then moment_fold_kernel), K = 28 or 29.  No atomics: the same arrays
 // give the same bytes.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool nonzero3(const float4& a) { return a.x != 0.0f || a.y != 0.0f || a.z != 0.0f; }
-// the counted-set gate for the caller index o of a device slot, and the gathers behind it: true with nn = the target normal and q = the
-// target point at corr[o]
-__device__ __forceinline__ bool counted_pair(uint32_t o, const RefineInputs& in, float4& nn, float4& q) {
-    if (!(o < (uint32_t)in.n)) return false;
-    const uint32_t j = in.corr[o];
-    if (!(in.inlier[o] != 0 && in.d2[o] <= in.max_d2 && j < (uint32_t)in.nt)) return false;
-    nn = in.normals[j];
-    if (!nonzero3(nn)) return false;
-    q = in.tgt[j];
-    return true;
-}
-// u = the 28 point-to-plane terms of one pair; returns the residual r
-__device__ __forceinline__ double plane_pair_terms(const double X[3], const float4& q, const double N[3], double* u) {
-    const double r = N[0] * (X[0] - (double)q.x) + N[1] * (X[1] - (double)q.y) + N[2] * (X[2] - (double)q.z);
-    const double J[6] = {X[1] * N[2] - X[2] * N[1], X[2] * N[0] - X[0] * N[2], X[0] * N[1] - X[1] * N[0], N[0], N[1], N[2]};
-    int m = 0;
-#pragma unroll
-    for (int a = 0; a < 6; ++a)
-#pragma unroll
-        for (int b = a; b < 6; ++b) u[m++] = J[a] * J[b];
-#pragma unroll
-    for (int a = 0; a < 6; ++a) u[21 + a] = J[a] * r;
-    u[27] = r * r;
-    return r;
-}
+#include "refine_item.hpp"  // nonzero3, counted_pair, plane_pair_terms, refine_slot_terms: the per-thread text, shared with the fused launch below
 template <bool GICP, bool WEIGHTED, bool PER_POINT>
 __global__ __launch_bounds__(kBlock) void refine_moments_kernel(RefineInputs in, Rt rt, double eps, int loss, double scale,
                                                                 MomentRow<WEIGHTED ? kRobustTerms : kPlaneTerms>* __restrict__ rows,
                                                                 double* __restrict__ residual, double* __restrict__ weight, unsigned char* __restrict__ counted) {
     static_assert(WEIGHTED || !PER_POINT, "the per-point outputs are the weighted kernel's");
     constexpr int K = WEIGHTED ? kRobustTerms : kPlaneTerms;
-    const int i = blockIdx.x * kBlock + threadIdx.x;
     double v[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) v[k] = 0.0;
-    unsigned cnt = 0u;
-    if (i < in.n) {
-        const uint32_t o = in.orig_of_slot[i];
-        const float4 x = in.moved[i];
-        float4 np = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (GICP) np = in.src_normals[i];
-        float4 nn, q;
-        double s = 0.0, w = 0.0;
-        if ((!GICP || nonzero3(np)) && counted_pair(o, in, nn, q)) {
-            const double X[3] = {(double)x.x, (double)x.y, (double)x.z}, N[3] = {(double)nn.x, (double)nn.y, (double)nn.z};
-            // the pair's unweighted terms: straight into the accumulators, or (WEIGHTED) an array of their own — handed to gicp_pair_terms
-            // by pointer and then scaled in place, the accumulators went to scratch memory (240 bytes per lane)
-            double own[WEIGHTED ? kPlaneTerms : 1];
-            double* const u = WEIGHTED ? own : v;
-            if (GICP) {
-                const double Q[3] = {(double)q.x, (double)q.y, (double)q.z}, NP[3] = {(double)np.x, (double)np.y, (double)np.z};
-                gicp_pair_terms(X, Q, N, NP, rt.R, eps, nullptr, u);
-                s = sqrt(u[27] > 0.0 ? u[27] : 0.0);
-            } else {
-                s = plane_pair_terms(X, q, N, u);
-            }
-            if (WEIGHTED) {
-                w = robust_weight(loss, s, scale);
-#pragma unroll
-                for (int k = 0; k < kPlaneTerms; ++k) v[k] = u[k] * w;
-                v[K - 1] = w;
-            }
-            cnt = 1u;
-        }
-        if (PER_POINT && o < (uint32_t)in.n) {
-            residual[o] = s;
-            weight[o] = w;
-            counted[o] = (unsigned char)cnt;
-        }
-    }
+    const unsigned cnt = refine_slot_terms<GICP, WEIGHTED, PER_POINT>(blockIdx.x * kBlock + threadIdx.x, in, rt.R, eps, loss, scale, v, residual, weight, counted);
     block_moment_row<kBlock / 64>(v, cnt, &rows[blockIdx.x]);
+}
+
+// fgoicp_batch: the refining pairs of one class in one launch (kernels.hpp FusedRefineView).  A block finds its pair from blockIdx.x and the
+// views' first blocks (block-uniform: scalar loads), then is the solo kernel's block blockIdx.x - first_block of that pair.  All of a block
+// belongs to one pair: the switch on `loss` stays wave-uniform and no butterfly mixes two pairs.  No per-point stores, no atomics.
+template <bool GICP, bool WEIGHTED>
+__global__ __launch_bounds__(kBlock) void fused_refine_moments_kernel(const FusedRefineView* __restrict__ views, int nviews) {
+    constexpr int K = WEIGHTED ? kRobustTerms : kPlaneTerms;
+    int p = 0;
+    for (int k = 1; k < nviews; ++k)
+        if ((int)blockIdx.x >= views[k].first_block) p = k;
+    const FusedRefineView& pv = views[p];
+    const int local = (int)blockIdx.x - pv.first_block;
+    if (local >= pv.nblocks) return;  // (the whole block: no barrier is skipped by part of one)
+    double v[K];
+    const unsigned cnt = refine_slot_terms<GICP, WEIGHTED, false>(local * kBlock + threadIdx.x, pv.in, pv.R, pv.eps, pv.loss, pv.scale, v, nullptr, nullptr, nullptr);
+    block_moment_row<kBlock / 64>(v, cnt, static_cast<MomentRow<K>*>(pv.rows) + local);
+}
+// one 1024-thread block per view: moment_fold_kernel<K> over that pair's rows, into its own kFusedRefineOut words of `out`
+template <int K>
+__global__ __launch_bounds__(1024) void fused_moment_fold_kernel(const FusedRefineView* __restrict__ views, unsigned long long* __restrict__ out) {
+    const FusedRefineView& pv = views[blockIdx.x];
+    moment_fold_block<K>(static_cast<const MomentRow<K>*>(pv.rows), pv.nblocks, out + (size_t)kFusedRefineOut * blockIdx.x);
+}
+void launch_fused_refine_moments(bool gicp, bool weighted, const FusedRefineView* views, int n, int total_blocks, unsigned long long* out, hipStream_t s) {
+    auto* const kernel = gicp ? (weighted ? fused_refine_moments_kernel<true, true> : fused_refine_moments_kernel<true, false>)
+                              : (weighted ? fused_refine_moments_kernel<false, true> : fused_refine_moments_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, dim3(total_blocks), dim3(kBlock), 0, s, views, n);
+    if (weighted) hipLaunchKernelGGL(fused_moment_fold_kernel<kRobustTerms>, dim3(n), dim3(1024), 0, s, views, out);
+    else hipLaunchKernelGGL(fused_moment_fold_kernel<kPlaneTerms>, dim3(n), dim3(1024), 0, s, views, out);
 }
 
 // K = kPlaneTerms: the unweighted kernel (loss, scale and the per-point outputs unused); K = kRobustTerms: the weighted one

@@ -184,6 +184,24 @@ constexpr int kPlaneTerms = 28, kRobustTerms = 29;
 template <int K>
 void launch_refine_moments(const RefineInputs& in, bool gicp, const float* R9, double eps, int loss, double scale, MomentRow<K>* rows, unsigned long long* out,
                            double* residual, double* weight, unsigned char* counted, hipStream_t s);
+// The same reduction for the refining pairs of a batch tick in one launch per class (fgoicp_batch; kernels.hip fused_refine_moments_kernel,
+// fused_moment_fold_kernel).  A class is gicp x weighted; its views lie next to each other in the table.  View p owns the blocks
+// [first_block, first_block + ceil(in.n / kBlock)) of the launch — block b of them is the solo launch's block b - first_block: the same slots,
+// the same per-thread text (refine_item.hpp), the same row of the pair's OWN rows — and one fold block, which leaves {count, the bits of the
+// K sums} at out + kFusedRefineOut * p.  No block, wave or addition is shared between two pairs: every pair's bytes are its solo launch's.
+constexpr int kFusedRefineMax = 16;  // views per launch: the batch's limit on live pairs (kBatchAutoLive)
+constexpr int kFusedRefineOut = 1 + kRobustTerms;
+struct FusedRefineView {
+    RefineInputs in;
+    float R[9];        // the rotation of the pose in.moved was formed with
+    int loss;
+    double eps, scale;
+    void* rows;        // MomentRow<kPlaneTerms>* (unweighted) or MomentRow<kRobustTerms>* (weighted): the context's own
+    int first_block;   // of this view inside its class's launch
+    int nblocks;
+};
+// views: the n (1 .. kFusedRefineMax) views of one class, device memory; total_blocks = the sum of their nblocks
+void launch_fused_refine_moments(bool gicp, bool weighted, const FusedRefineView* views, int n, int total_blocks, unsigned long long* out, hipStream_t s);
 // out[i] = in[orig_of_slot[i]], i < n: caller order -> device slot order
 void launch_slot_order(const float4* in, const uint32_t* orig_of_slot, int n, float4* out, hipStream_t s);
 // The bounds of many registrations in one launch (fgoicp_batch, bounds_fused.hpp): a view per pair of the batch, an evaluation per output

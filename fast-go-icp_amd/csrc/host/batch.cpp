@@ -15,6 +15,7 @@
 #include "../../../include/fgoicp_amd.h"
 #include "../device/ctx.hpp"
 #include "batch.hpp"
+#include "refined_pose.hpp"
 
 namespace fgoicp {
 namespace {
@@ -60,6 +61,45 @@ struct PairInfo {
     bool have = false;
 };
 
+// how a pair is refined after its search (fgoicp_batch_refine_t, checked by fgoicp_batch_create); model < 0: not at all
+struct PairRefineSpec {
+    int model = -1, k = 16;
+    size_t max_iter = 0;
+    float conv_thr = 0.f, max_distance = 0.f;
+    double epsilon = 1e-3;
+    int loss = FGOICP_LOSS_NONE;
+    double loss_scale = 0.0;
+    bool weighted() const { return loss != FGOICP_LOSS_NONE; }
+};
+// a pair's refinement, kept on the host: the result as fgoicp_solver_refine_* fills it (one of the two), or the refinement's own status
+// and message; the information matrix at the refined pose (fgoicp_batch_opts.information)
+struct PairRefined {
+    fgoicp_plane_result_t plane{};
+    fgoicp_robust_result_t robust{};
+    int rc = FGOICP_OK;
+    std::string err;
+    bool have = false;
+    fgoicp_information_t info{};
+    int info_rc = FGOICP_OK;
+    std::string info_err;
+    bool have_info = false;
+};
+// the spec of one evaluation in the context's frame, as solver_refine (solver.cpp) forms it
+inline RefineSpec refine_ctx_spec(const PairRefineSpec& r, float scaling_factor) {
+    RefineSpec spec;
+    spec.model = r.model;
+    spec.epsilon = r.epsilon;
+    spec.weighted = r.weighted();
+    spec.loss = r.loss;
+    spec.scale = r.loss_scale > 0.0 ? r.loss_scale * (double)scaling_factor : 0.0;
+    spec.max_dist2 = information_max_dist2(r.max_distance, scaling_factor);
+    return spec;
+}
+// the name a refinement's messages carry: the robust loop's caller, the plain loops' context entry points (as solver_refine)
+inline const char* refine_where(const RefineSpec& spec, const char* robust_caller) {
+    return spec.weighted ? robust_caller : spec.model == FGOICP_MODEL_GICP ? "fgoicp_icp_gicp" : "fgoicp_icp_plane";
+}
+
 // work items per fused launch (one 64-thread block each): a class with more is split, so that blocks x threads stay inside the 32-bit
 // grid size of a dispatch, with the margin the solo path keeps (ctx.hip, launch_fit)
 constexpr size_t kFusedLaunchItems = (size_t)1 << 24;
@@ -102,8 +142,19 @@ struct HipBatchBackend {
     std::vector<fgoicp_ctx*> ctx;
     bool borrowed = false;  // the test hooks: the contexts are the caller's (not destroyed here)
     std::vector<IcpStepRun> icp_state;
+    std::vector<RefineStepRun> refine_state;   // one per pair: the refinement loop cut at its host wait (ctx.hpp)
     Stream stream;  // (declared ahead of the buffers: released after them)
     uint64_t bounds_launches = 0, icp_launches = 0, selection_launches = 0;
+    uint64_t refine_launches = 0, refine_evaluations = 0;   // fused moment launches (one per class per tick) / evaluations (one per active loop per tick)
+    const std::vector<PairRefineSpec>* rspec = nullptr;  // fgoicp_batch_opts_refine.refine (nullptr: no pair is refined)
+    std::vector<PairRefined>* refined = nullptr;          // ... and where every refined pair's result is left
+    bool want_refined_info = false;                       // fgoicp_batch_opts.information: the matrix at the refined pose too
+    float refined_info_distance = 0.f;                    // callers' units, <= 0: no threshold (as the command-line tool takes it)
+    // refinement tick staging: the views of every class next to each other, {count, sums} per view
+    PinBuf<FusedRefineView> h_rviews;
+    DevBuf<FusedRefineView> d_rviews;
+    PinBuf<unsigned long long> h_rout;
+    DevBuf<unsigned long long> d_rout;
     size_t last_lut_bytes = 0, last_lanes = 4;
     int next_pair = 0;            // the pair the scheduler admits next (room_for_more)
     std::vector<PairAlign>* align = nullptr;   // fgoicp_batch_opts.alignment: where finished() leaves every pair's report (nullptr: off)
@@ -135,6 +186,7 @@ struct HipBatchBackend {
         BCHK(stream.create(hipStreamNonBlocking));
         ctx.assign(pairs->size(), nullptr);
         icp_state.assign(pairs->size(), IcpStepRun());
+        refine_state.assign(pairs->size(), RefineStepRun());
         for (const PairHost& p : *pairs)
             if (p.inliers) {  // the arena's budget is set aside before any pair enters (room_for_more)
                 size_t free_b = 0, total_b = 0;
@@ -149,6 +201,7 @@ struct HipBatchBackend {
         borrowed = true;
         ctx.assign(cs, cs + n);
         icp_state.assign((size_t)n, IcpStepRun());
+        refine_state.assign((size_t)n, RefineStepRun());
         device = n > 0 ? cs[0]->device : 0;
         BCHK(hipSetDevice(device));
         BCHK(stream.create(hipStreamNonBlocking));
@@ -404,6 +457,121 @@ struct HipBatchBackend {
         ++icp_launches;
         return FGOICP_OK;
     }
+
+    // One refinement tick over the runs `idx` (indices into ctx / refine_state), each advanced by ONE evaluation:
+    //   1. every run's device half on its own context's stream, an event behind it;  2. the batch stream waits for the events;
+    //   3. one fused moments launch (and its folds) per class present, at most kFusedRefineMax views each;  4. one copy of all outputs to
+    //   pinned memory;  5. one wait;  6. every run's host step.
+    // done[k]: run k's loop has ended; run_rc[k] != 0: it failed in its host step (the normal equations are not finite), with run_err[k].
+    // The return value is a device failure: the tick's, not one run's.
+    int refine_tick(const std::vector<int>& idx, std::vector<char>& done, std::vector<int>& run_rc, std::vector<std::string>& run_err) {
+        const size_t n = idx.size();
+        done.assign(n, 0);
+        run_rc.assign(n, FGOICP_OK);
+        run_err.assign(n, std::string());
+        if (n == 0) return FGOICP_OK;
+        BCHK(hipSetDevice(device));
+        int rc;
+        if ((rc = h_rviews.ensure(n)) || (rc = d_rviews.ensure(n)) || (rc = h_rout.ensure(kFusedRefineOut * n)) || (rc = d_rout.ensure(kFusedRefineOut * n))) return rc;
+        std::vector<FusedRefineView> views(n);
+        for (size_t k = 0; k < n; ++k)
+            if ((rc = ctx_refine_step_enqueue(ctx[(size_t)idx[k]], refine_state[(size_t)idx[k]], &views[k]))) return rc;
+        for (size_t k = 0; k < n; ++k) BCHK(hipStreamWaitEvent(stream, ctx[(size_t)idx[k]]->refine_ready, 0));
+        // the table: class after class (model x weighted), the runs of a class in the order given; a launch takes up to kFusedRefineMax of them
+        std::vector<size_t> slot_of(n);
+        struct Launch { bool gicp, weighted; size_t first, count; int blocks; };
+        std::vector<Launch> launches;
+        size_t pos = 0;
+        for (int cls = 0; cls < 4; ++cls) {
+            const bool gicp = (cls & 1) != 0, weighted = (cls & 2) != 0;
+            for (size_t k = 0; k < n; ++k) {
+                const RefineSpec& sp = refine_state[(size_t)idx[k]].end.spec;
+                if ((sp.model == FGOICP_MODEL_GICP) != gicp || sp.weighted != weighted) continue;
+                if (launches.empty() || launches.back().gicp != gicp || launches.back().weighted != weighted || launches.back().count == (size_t)kFusedRefineMax)
+                    launches.push_back(Launch{gicp, weighted, pos, 0, 0});
+                Launch& l = launches.back();
+                views[k].first_block = l.blocks;
+                l.blocks += views[k].nblocks;
+                ++l.count;
+                h_rviews.p[pos] = views[k];
+                slot_of[k] = pos++;
+            }
+        }
+        BCHK(hipMemcpyAsync(d_rviews.p, h_rviews.p, sizeof(FusedRefineView) * n, hipMemcpyHostToDevice, stream));
+        for (const Launch& l : launches) {
+            launch_fused_refine_moments(l.gicp, l.weighted, d_rviews.p + l.first, (int)l.count, l.blocks, d_rout.p + (size_t)kFusedRefineOut * l.first, stream);
+            ++refine_launches;
+        }
+        BCHK(hipGetLastError());
+        BCHK(hipMemcpyAsync(h_rout.p, d_rout.p, sizeof(unsigned long long) * kFusedRefineOut * n, hipMemcpyDeviceToHost, stream));
+        BCHK(hipStreamSynchronize(stream));  // covers every run's own stream up to its event: the report's sse is in pinned memory
+        for (size_t k = 0; k < n; ++k) {
+            RefineStepRun& s = refine_state[(size_t)idx[k]];
+            run_rc[k] = ctx_refine_step(ctx[(size_t)idx[k]], s, h_rout.p + (size_t)kFusedRefineOut * slot_of[k]);
+            if (run_rc[k]) run_err[k] = fgoicp_last_error();
+            done[k] = run_rc[k] || s.done;
+            ++refine_evaluations;
+        }
+        return FGOICP_OK;
+    }
+
+    // BatchScheduler's optional refinement hooks (BackendHasRefine)
+    bool refines(int i) const { return rspec && (*rspec)[(size_t)i].model >= 0; }
+    // the refinement itself was refused or failed: kept for the pair's getter; the pair's search result and status stay as they are
+    void refine_failed(int i, int rc, const std::string& err) {
+        PairRefined& o = (*refined)[(size_t)i];
+        o.rc = rc;
+        o.err = err;
+        o.have = false;
+    }
+    int refine_start(int i, const BatchPairResult& r, bool* done) {
+        const PairHost& p = (*pairs)[(size_t)i];
+        const PairRefineSpec& q = (*rspec)[(size_t)i];
+        const RefineSpec spec = refine_ctx_spec(q, p.scaling_factor);
+        const float t3[3] = {r.t.x, r.t.y, r.t.z};  // the normalised frame the search ran in
+        const int rc = ctx_refine_step_begin(ctx[(size_t)i], refine_state[(size_t)i], r.R.m, t3, q.max_iter, q.conv_thr, spec, refine_where(spec, "fgoicp_solver_refine_robust"), q.k);
+        *done = rc != 0;
+        if (rc == FGOICP_ERR_HIP) return rc;
+        if (rc) refine_failed(i, rc, fgoicp_last_error());
+        return FGOICP_OK;
+    }
+    // the loop has ended: the result as solver_refine (solver.cpp) hands it out, then the information matrix at that pose
+    template <class Result>
+    void refine_restore(const PairHost& p, const RefineEnd& end, Result* full) {
+        refine_result(end, full);
+        const Mat3f Rr = Mat3f::from(full->R);
+        const Vec3f ts{full->t[0], full->t[1], full->t[2]};
+        const Vec3f tr = ts / p.scaling_factor + Rr * p.offset_pcs - p.offset_pct;  // restore_translation, fgoicp.hpp:87-90
+        full->t[0] = tr.x; full->t[1] = tr.y; full->t[2] = tr.z;
+        full->scaling_factor = p.scaling_factor;
+    }
+    void refine_finish(int i) {
+        const PairHost& p = (*pairs)[(size_t)i];
+        const RefineEnd& end = refine_state[(size_t)i].end;
+        PairRefined& o = (*refined)[(size_t)i];
+        const float *R9, *t3;
+        if (end.spec.weighted) { refine_restore(p, end, &o.robust); R9 = o.robust.R; t3 = o.robust.t; }
+        else { refine_restore(p, end, &o.plane); R9 = o.plane.R; t3 = o.plane.t; }
+        o.have = true;
+        if (!want_refined_info) return;
+        const float offs[6] = {p.offset_pcs.x, p.offset_pcs.y, p.offset_pcs.z, p.offset_pct.x, p.offset_pct.y, p.offset_pct.z};
+        std::memset(&o.info, 0, sizeof(o.info));
+        o.info.struct_size = (uint32_t)sizeof(o.info);
+        o.info_rc = refined_information(ctx[(size_t)i], R9, t3, offs, p.scaling_factor, refined_info_distance, &o.info);
+        o.have_info = o.info_rc == FGOICP_OK;
+        if (o.info_rc) o.info_err = fgoicp_last_error();
+    }
+    int refine_step(const std::vector<int>& active, std::vector<char>& done) {
+        std::vector<int> run_rc;
+        std::vector<std::string> run_err;
+        const int rc = refine_tick(active, done, run_rc, run_err);
+        if (rc) return rc;
+        for (size_t k = 0; k < active.size(); ++k) {
+            if (run_rc[k]) refine_failed(active[k], run_rc[k], run_err[k]);
+            else if (done[k]) refine_finish(active[k]);
+        }
+        return FGOICP_OK;
+    }
 };
 
 }  // namespace
@@ -420,7 +588,25 @@ struct fgoicp_batch {
     bool ran = false;
     std::vector<PairAlign> align;  // opts.alignment: one per pair
     std::vector<PairInfo> info;    // opts.information: one per pair
+    std::vector<PairRefineSpec> rspec;   // opts.refine: one per pair (empty: none)
+    std::vector<PairRefined> refined;    // ... and what the last run left
+    uint64_t refine_launches = 0, refine_evaluations = 0;
 };
+
+// one fgoicp_batch_refine_t entry, refused as the solo entry points refuse their arguments; `who` names the pair
+static int refine_entry_check(const fgoicp_batch_refine_t& q, const std::string& who, PairRefineSpec* out) {
+    if (q.struct_size < sizeof(fgoicp_batch_refine_t) || q.struct_size > 4096) { set_error(who + ": set struct_size = sizeof(fgoicp_batch_refine_t)"); return FGOICP_ERR_INVALID_ARG; }
+    if (q.model == -1) { *out = PairRefineSpec(); return FGOICP_OK; }
+    if (!robust_model_ok(q.model)) { set_error(who + ": unknown model " + std::to_string(q.model) + " (-1: not refined, 0: point-to-plane, 1: Generalized ICP)"); return FGOICP_ERR_INVALID_ARG; }
+    if (q.k < kKnnMin || q.k > kKnnMax) { set_error(who + ": k must lie in [4, 32]"); return FGOICP_ERR_INVALID_ARG; }
+    if (!(q.max_distance >= 0.0f)) { set_error(who + ": max_distance must be >= 0 (+inf: no threshold)"); return FGOICP_ERR_INVALID_ARG; }
+    if (!robust_loss_ok(q.loss)) { set_error(who + ": unknown loss " + std::to_string(q.loss)); return FGOICP_ERR_INVALID_ARG; }
+    if (q.model == FGOICP_MODEL_GICP && !gicp_epsilon_ok(q.epsilon)) { set_error(who + ": epsilon must be finite and lie in (0, 1]"); return FGOICP_ERR_INVALID_ARG; }
+    if (!std::isfinite(q.loss_scale)) { set_error(who + ": loss_scale must be finite (<= 0: estimated)"); return FGOICP_ERR_INVALID_ARG; }
+    out->model = q.model; out->k = q.k; out->max_iter = q.max_iter; out->conv_thr = q.conv_thr; out->max_distance = q.max_distance;
+    out->epsilon = q.epsilon; out->loss = q.loss; out->loss_scale = q.loss_scale;
+    return FGOICP_OK;
+}
 
 extern "C" {
 
@@ -432,7 +618,10 @@ static int batch_create_impl(const fgoicp_batch_pair* pairs, int n, const fgoicp
         return FGOICP_ERR_INVALID_ARG;
     }
     auto b = std::make_unique<fgoicp_batch>();
-    std::memcpy(&b->opts, opts, sz < sizeof(b->opts) ? sz : sizeof(b->opts));  // members beyond the caller's struct stay 0
+    static_assert(offsetof(fgoicp_batch_opts_refine, refine) == sizeof(fgoicp_batch_opts), "the refine table lies right behind the options as published");
+    fgoicp_batch_opts_refine full{};
+    std::memcpy(&full, opts, sz < sizeof(full) ? sz : sizeof(full));  // members beyond the caller's struct stay 0
+    b->opts = full.opts;
     b->opts.struct_size = sizeof(b->opts);
     if (b->opts.solver.trim_fraction != 0.0f) {
         set_error("fgoicp_batch_create: solver.trim_fraction must be 0 (trimming is per pair: fgoicp_batch_opts.trim_fractions)");
@@ -445,6 +634,12 @@ static int batch_create_impl(const fgoicp_batch_pair* pairs, int n, const fgoicp
     }
     const float* trim = b->opts.trim_fractions;
     b->opts.trim_fractions = nullptr;  // read here only
+    const fgoicp_batch_refine_t* refine = full.refine;  // read here only
+    if (refine) {
+        b->rspec.resize((size_t)n);
+        for (int i = 0; i < n; ++i)
+            if (int rc = refine_entry_check(refine[i], "fgoicp_batch_create: refine[" + std::to_string(i) + "] (pair " + std::to_string(i) + ")", &b->rspec[(size_t)i])) return rc;
+    }
     for (int i = 0; trim && i < n; ++i)
         if (!(trim[i] >= 0.0f && trim[i] < 1.0f)) { set_error("fgoicp_batch_create: trim_fractions[" + std::to_string(i) + "] is not in [0, 1)"); return FGOICP_ERR_INVALID_ARG; }
     b->pairs.resize((size_t)n);
@@ -499,6 +694,13 @@ static int batch_run_impl(fgoicp_batch* b, float* R_out9n, float* t_out3n, int* 
         be.info = &b->info;
         be.info_max_distance = b->opts.information_max_distance > 0.0f ? b->opts.information_max_distance : std::numeric_limits<float>::infinity();
     }
+    if (!b->rspec.empty()) {
+        b->refined.assign((size_t)n, PairRefined());
+        be.rspec = &b->rspec;
+        be.refined = &b->refined;
+        be.want_refined_info = b->opts.information != 0;
+        be.refined_info_distance = b->opts.information_max_distance;
+    }
     int rc = be.init();
     if (rc) return rc;
     std::vector<BatchPairSpec> specs((size_t)n);
@@ -518,6 +720,8 @@ static int batch_run_impl(fgoicp_batch* b, float* R_out9n, float* t_out3n, int* 
     }
     b->bounds_launches = be.bounds_launches;
     b->icp_launches = be.icp_launches;
+    b->refine_launches = be.refine_launches;
+    b->refine_evaluations = be.refine_evaluations;
     b->ran = true;
     for (int i = 0; i < n; ++i) {
         const BatchPairResult& r = b->results[(size_t)i];
@@ -589,6 +793,53 @@ int fgoicp_batch_launches(const fgoicp_batch* b, uint64_t* bounds_launches, uint
     if (!b) return FGOICP_ERR_INVALID_ARG;
     if (bounds_launches) *bounds_launches = b->bounds_launches;
     if (icp_launches) *icp_launches = b->icp_launches;
+    return FGOICP_OK;
+}
+
+// what the refinement getters share: the refusals, then the pair's record.  weighted: the kind of result the getter serves
+static int batch_refined_pair(const fgoicp_batch* b, int i, const char* where, int weighted, const PairRefined** out) {
+    if (!b) { set_error(std::string(where) + ": the batch must not be null"); return FGOICP_ERR_INVALID_ARG; }
+    if (i < 0 || i >= (int)b->pairs.size()) { set_error(std::string(where) + ": pair index out of range"); return FGOICP_ERR_INVALID_ARG; }
+    if (b->rspec.empty() || b->rspec[(size_t)i].model < 0) { set_error(std::string(where) + ": pair " + std::to_string(i) + " has no refinement (fgoicp_batch_opts_refine.refine)"); return FGOICP_ERR_INVALID_ARG; }
+    if (weighted >= 0 && (int)b->rspec[(size_t)i].weighted() != weighted) {
+        set_error(std::string(where) + ": pair " + std::to_string(i) + (weighted ? " is refined without a loss: fgoicp_batch_refined_plane serves it" : " is refined under a loss: fgoicp_batch_refined_robust serves it"));
+        return FGOICP_ERR_INVALID_ARG;
+    }
+    if (!b->ran) { set_error(std::string(where) + ": fgoicp_batch_run has not run yet"); return FGOICP_ERR_INVALID_ARG; }
+    if (b->status[(size_t)i]) { set_error(std::string(where) + ": pair " + std::to_string(i) + " failed (status " + std::to_string(b->status[(size_t)i]) + ")"); return FGOICP_ERR_INVALID_ARG; }
+    const PairRefined& r = b->refined[(size_t)i];
+    if (!r.have) { set_error(std::string(where) + ": pair " + std::to_string(i) + ": " + (r.err.empty() ? "no refinement was run" : r.err)); return r.rc ? r.rc : FGOICP_ERR_INVALID_ARG; }
+    *out = &r;
+    return FGOICP_OK;
+}
+int fgoicp_batch_refined_plane(const fgoicp_batch* b, int i, fgoicp_plane_result_t* out) {
+    const char* where = "fgoicp_batch_refined_plane";
+    if (!plane_size_ok(out)) { set_error(std::string(where) + ": out must not be null and out->struct_size = sizeof(fgoicp_plane_result_t)"); return FGOICP_ERR_INVALID_ARG; }
+    const PairRefined* r = nullptr;
+    const int rc = batch_refined_pair(b, i, where, 0, &r);
+    return rc ? rc : plane_out(r->plane, out, where, "fgoicp_plane_result_t");
+}
+int fgoicp_batch_refined_robust(const fgoicp_batch* b, int i, fgoicp_robust_result_t* out) {
+    const char* where = "fgoicp_batch_refined_robust";
+    if (!plane_size_ok(out)) { set_error(std::string(where) + ": out must not be null and out->struct_size = sizeof(fgoicp_robust_result_t)"); return FGOICP_ERR_INVALID_ARG; }
+    const PairRefined* r = nullptr;
+    const int rc = batch_refined_pair(b, i, where, 1, &r);
+    return rc ? rc : plane_out(r->robust, out, where, "fgoicp_robust_result_t");
+}
+int fgoicp_batch_refined_information(const fgoicp_batch* b, int i, fgoicp_information_t* out) {
+    const char* where = "fgoicp_batch_refined_information";
+    if (b && !b->opts.information) { set_error(std::string(where) + ": the batch was created with fgoicp_batch_opts.information = 0"); return FGOICP_ERR_INVALID_ARG; }
+    if (!information_size_ok(out)) { set_error(std::string(where) + ": out must not be null and out->struct_size = sizeof(fgoicp_information_t)"); return FGOICP_ERR_INVALID_ARG; }
+    const PairRefined* r = nullptr;
+    const int rc = batch_refined_pair(b, i, where, -1, &r);
+    if (rc) return rc;
+    if (!r->have_info) { set_error(std::string(where) + ": pair " + std::to_string(i) + ": " + (r->info_err.empty() ? "no moments were taken" : r->info_err)); return r->info_rc ? r->info_rc : FGOICP_ERR_INVALID_ARG; }
+    return information_out(r->info, out, where);
+}
+int fgoicp_batch_refine_launches(const fgoicp_batch* b, uint64_t* fused_launches, uint64_t* evaluations) {
+    if (!b) return FGOICP_ERR_INVALID_ARG;
+    if (fused_launches) *fused_launches = b->refine_launches;
+    if (evaluations) *evaluations = b->refine_evaluations;
     return FGOICP_OK;
 }
 
@@ -742,6 +993,88 @@ int fgoicp_batch_test_icp(fgoicp_ctx* const* ctxs, int n, const int* start_pass,
                           const float* thr, float* sse_out, float* R_out9, float* t_out3, int* iters_out) {
     return fgoicp::abi_guard("fgoicp_batch_test_icp", [&] {
         return batch_test_icp_impl(ctxs, n, start_pass, R0s_9, t0s_3, max_iter, thr, sse_out, R_out9, t_out3, iters_out);
+    });
+}
+
+static int batch_test_refine_impl(fgoicp_ctx* const* ctxs, int n, const fgoicp_batch_refine_t* specs, const int* start_pass, const float* R0s_9, const float* t0s_3,
+                                  fgoicp_robust_result_t* out_n, int* status_n, char* messages, uint64_t* fused_launches_out) {
+    const char* where = "fgoicp_batch_test_refine";
+    if (n < 0 || (n > 0 && (!ctxs || !specs || !start_pass || !R0s_9 || !t0s_3 || !out_n || !status_n))) { set_error(std::string(where) + ": invalid argument"); return FGOICP_ERR_INVALID_ARG; }
+    if (fused_launches_out) *fused_launches_out = 0;
+    if (n == 0) return FGOICP_OK;
+    int rc = borrowed_ctx_check(ctxs, n, where);
+    if (rc) return rc;
+    for (int i = 0; i < n; ++i) {
+        if (start_pass[i] < 0) { set_error(std::string(where) + ": start_pass < 0"); return FGOICP_ERR_INVALID_ARG; }
+        for (int j = 0; j < i; ++j)
+            if (ctxs[j] == ctxs[i]) { set_error(std::string(where) + ": a context may run one refinement at a time"); return FGOICP_ERR_INVALID_ARG; }
+        if (specs[i].struct_size < sizeof(fgoicp_batch_refine_t)) { set_error(std::string(where) + ": set specs[i].struct_size"); return FGOICP_ERR_INVALID_ARG; }
+    }
+    HipBatchBackend be;
+    if ((rc = be.init_borrowed(ctxs, n))) return rc;
+    std::memset(out_n, 0, sizeof(fgoicp_robust_result_t) * (size_t)n);
+    auto fail = [&](int i, int status) {
+        status_n[i] = status;
+        if (messages) { std::strncpy(messages + 256 * (size_t)i, fgoicp_last_error(), 255); messages[256 * (size_t)i + 255] = 0; }
+    };
+    auto finish = [&](int i) {
+        const RefineEnd& end = be.refine_state[(size_t)i].end;
+        if (end.spec.weighted) {
+            refine_result(end, &out_n[i]);
+        } else {
+            fgoicp_plane_result_t full;
+            refine_result(end, &full);
+            static_assert(sizeof(fgoicp_plane_result_t) <= sizeof(fgoicp_robust_result_t), "a plain result fits the run's slot");
+            std::memcpy(&out_n[i], &full, sizeof(full));
+        }
+    };
+    std::vector<char> started((size_t)n, 0), ended((size_t)n, 0);
+    std::vector<int> active;
+    for (int i = 0; i < n; ++i) { status_n[i] = FGOICP_OK; if (messages) messages[256 * (size_t)i] = 0; }
+    int left = n;
+    for (int pass = 0; left > 0; ++pass) {
+        if (active.empty()) {  // nothing to step: on to the next pass that starts a run
+            int next = -1;
+            for (int i = 0; i < n; ++i)
+                if (!started[(size_t)i] && (next < 0 || start_pass[i] < next)) next = start_pass[i];
+            if (next > pass) pass = next;
+        }
+        for (int i = 0; i < n; ++i) {
+            if (started[(size_t)i] || start_pass[i] != pass) continue;
+            started[(size_t)i] = 1;
+            RefineSpec spec;  // the context frame: max_dist2 and the scale as given
+            spec.model = specs[i].model; spec.epsilon = specs[i].epsilon; spec.weighted = specs[i].loss != FGOICP_LOSS_NONE; spec.loss = specs[i].loss;
+            spec.scale = specs[i].loss_scale; spec.max_dist2 = specs[i].max_distance;
+            const int r1 = ctx_refine_step_begin(ctxs[i], be.refine_state[(size_t)i], R0s_9 + 9 * (size_t)i, t0s_3 + 3 * (size_t)i, specs[i].max_iter, specs[i].conv_thr, spec,
+                                                 refine_where(spec, "fgoicp_icp_robust"), 0);
+            if (r1 == FGOICP_ERR_HIP) return r1;
+            if (r1) { fail(i, r1); ended[(size_t)i] = 1; continue; }
+            active.push_back(i);
+        }
+        if (!active.empty()) {
+            std::vector<char> done;
+            std::vector<int> run_rc;
+            std::vector<std::string> run_err;
+            if ((rc = be.refine_tick(active, done, run_rc, run_err))) return rc;
+            std::vector<int> still;
+            for (size_t k = 0; k < active.size(); ++k) {
+                const int i = active[k];
+                if (run_rc[k]) { set_error(run_err[k]); fail(i, run_rc[k]); ended[(size_t)i] = 1; }
+                else if (done[k]) { finish(i); ended[(size_t)i] = 1; }
+                else still.push_back(i);
+            }
+            active.swap(still);
+        }
+        left = 0;
+        for (int i = 0; i < n; ++i) left += ended[(size_t)i] ? 0 : 1;
+    }
+    if (fused_launches_out) *fused_launches_out = be.refine_launches;
+    return FGOICP_OK;
+}
+int fgoicp_batch_test_refine(fgoicp_ctx* const* ctxs, int n, const fgoicp_batch_refine_t* specs, const int* start_pass, const float* R0s_9, const float* t0s_3,
+                             fgoicp_robust_result_t* out_n, int* status_n, char* messages_n256, uint64_t* fused_launches_out) {
+    return fgoicp::abi_guard("fgoicp_batch_test_refine", [&] {
+        return batch_test_refine_impl(ctxs, n, specs, start_pass, R0s_9, t0s_3, out_n, status_n, messages_n256, fused_launches_out);
     });
 }
 

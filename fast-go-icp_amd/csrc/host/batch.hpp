@@ -17,6 +17,9 @@
 //     int  Backend::icp_start(BatchIcpReq&)             a run of fgoicp_icp; may complete it at once (req.done)
 //     int  Backend::icp_step(std::vector<BatchIcpReq*>&)    one iteration of every active run; completes those whose loop ended
 //     void Backend::finished(int pair, const BatchPairResult&)   optional (BackendHasFinished): before release, the driver has ended
+//     bool Backend::refines(int pair)                   optional, with the two below (BackendHasRefine): the pair is refined after its search
+//     int  Backend::refine_start(int pair, const BatchPairResult&, bool* done)   a refinement loop from the search's pose; may end it at once
+//     int  Backend::refine_step(const std::vector<int>& pairs, std::vector<char>& done)   one evaluation of every active loop
 //
 // A request's results depend on its pair and its inputs only, never on which other requests share the launch, so every pair gets the
 // bits of its own solo run whatever the grouping (tests/test_batch_host.py varies it at random).
@@ -85,6 +88,19 @@ template <class Backend, class = void>
 struct BackendHasFinished : std::false_type {};
 template <class Backend>
 struct BackendHasFinished<Backend, std::void_t<decltype(std::declval<Backend&>().finished(0, std::declval<const BatchPairResult&>()))>> : std::true_type {};
+
+// Optional backend hooks (all three or none): a pair whose driver has ended with status 0 and for which refines(pair) holds is not released
+// but REFINING — still live for the window, its device state kept.  Every launcher pass starts the new refinements and advances every
+// active one by one evaluation, next to the bounds tick and the ICP step; finished(pair) and release(pair) follow the pass in which the
+// pair's loop ended.  A refinement that is refused or fails is the backend's to record (done, status 0): only a device failure returns
+// non-zero, and that ends the batch like a failed bounds tick.
+template <class Backend, class = void>
+struct BackendHasRefine : std::false_type {};
+template <class Backend>
+struct BackendHasRefine<Backend, std::void_t<decltype(std::declval<Backend&>().refines(0)),
+                                             decltype(std::declval<Backend&>().refine_start(0, std::declval<const BatchPairResult&>(), (bool*)nullptr)),
+                                             decltype(std::declval<Backend&>().refine_step(std::declval<const std::vector<int>&>(), std::declval<std::vector<char>&>()))>>
+    : std::true_type {};
 
 // The operator interface of driver.hpp as seen by one driver of a batch.
 template <class Backend>
@@ -156,8 +172,14 @@ public:
                 if (p.thread.joinable() && p.finished) {
                     lk.unlock();
                     p.thread.join();
-                    if constexpr (BackendHasFinished<Backend>::value) be_.finished(i, p.result);  // the driver thread has ended: its result is final
-                    be_.release(i);
+                    bool refine = false;
+                    if constexpr (BackendHasRefine<Backend>::value) refine = p.result.status == 0 && be_.refines(i);
+                    if (refine) {  // the search is over, the refinement is not: the pair stays live, its device state stays
+                        refine_new_.push_back(i);
+                        lk.lock();
+                        continue;
+                    }
+                    retire(i);
                     lk.lock();
                     p.released = true;
                     --live;
@@ -165,6 +187,7 @@ public:
                     reaped = true;
                 }
             }
+            std::vector<int> rstarts = refine_new_;
             std::vector<BatchBoundsReq*> breqs;
             std::vector<BatchIcpReq*> starts;
             for (auto& pp : pairs_) {
@@ -182,8 +205,14 @@ public:
                 };
                 thin(breqs);
                 thin(starts);
+                if (rstarts.size() >= 2) {
+                    std::vector<int> keep;
+                    for (int i : rstarts) if (rng() & 1) keep.push_back(i);
+                    if (keep.empty()) keep.push_back(rstarts[rng() % rstarts.size()]);
+                    rstarts.swap(keep);
+                }
             }
-            if (breqs.empty() && starts.empty() && active_icp_.empty()) {
+            if (breqs.empty() && starts.empty() && active_icp_.empty() && rstarts.empty() && refine_active_.empty()) {
                 if (reaped) continue;
                 // nothing to serve and nobody running: every live driver would wait for ever (cannot happen: a blocked driver has a request)
                 fgoicp::set_error("fgoicp_batch_run: the launcher found no request while drivers waited");
@@ -202,7 +231,33 @@ public:
                 std::vector<BatchIcpReq*> step = active_icp_;
                 rc = be_.icp_step(step);
             }
+            std::vector<int> refined;  // pairs whose refinement ended in this pass
+            if constexpr (BackendHasRefine<Backend>::value) {
+                for (int i : rstarts) {
+                    if (rc) break;
+                    bool done = false;
+                    rc = be_.refine_start(i, pairs_[(size_t)i]->result, &done);
+                    for (size_t k = 0; k < refine_new_.size(); ++k)
+                        if (refine_new_[k] == i) { refine_new_.erase(refine_new_.begin() + (std::ptrdiff_t)k); break; }
+                    if (!rc) (done ? refined : refine_active_).push_back(i);
+                }
+                if (!rc && !refine_active_.empty()) {
+                    std::vector<char> done(refine_active_.size(), 0);
+                    rc = be_.refine_step(refine_active_, done);
+                    if (!rc) {
+                        std::vector<int> still;
+                        for (size_t k = 0; k < refine_active_.size(); ++k) (done[k] ? refined : still).push_back(refine_active_[k]);
+                        refine_active_.swap(still);
+                    }
+                }
+                for (int i : refined) retire(i);
+            }
             lk.lock();
+            for (int i : refined) {
+                pairs_[(size_t)i]->released = true;
+                --live;
+                no_room = false;
+            }
             if (rc) {
                 rc_all = rc;
                 for (BatchBoundsReq* r : breqs) { r->rc = rc; r->done = true; }
@@ -342,6 +397,11 @@ private:
         p.finished = true;
         if (--running_ == 0) cv_launcher_.notify_one();
     }
+    // launcher, mu_ not held: the pair's driver thread has been joined (and its refinement, if any, has ended): its result is final
+    void retire(int i) {
+        if constexpr (BackendHasFinished<Backend>::value) be_.finished(i, pairs_[(size_t)i]->result);
+        be_.release(i);
+    }
     void join_all() {
         for (auto& p : pairs_)
             if (p && p->thread.joinable()) p->thread.join();
@@ -352,6 +412,7 @@ private:
     int schedule_, round_width_, max_live_;
     std::vector<std::unique_ptr<PairState>> pairs_;
     std::vector<BatchIcpReq*> active_icp_;   // launcher only
+    std::vector<int> refine_new_, refine_active_;  // launcher only: refining pairs that have not started yet / whose loops are running
     std::mutex mu_;
     std::condition_variable cv_launcher_, cv_drivers_;
     int running_ = 0;                        // live drivers that are neither blocked nor finished

@@ -925,6 +925,20 @@ typedef struct fgoicp_batch_pair {
     const float* tgt_xyz; size_t nt; const float* src_xyz; size_t ns;
     float lut_resolution; float mse_threshold;           /* per pair, as fgoicp_solver_create takes them */
 } fgoicp_batch_pair;
+/* EXTENSION: how one pair of a batch is refined after its search (fgoicp_batch_opts_refine.refine) — the arguments of fgoicp_solver_refine_plane /
+ * _gicp / _robust, in the callers' units.  model = -1: this pair is not refined.  loss = FGOICP_LOSS_NONE: the plain (unweighted)
+ * refinement, served by fgoicp_batch_refined_plane; any other loss: fgoicp_solver_refine_robust's, served by fgoicp_batch_refined_robust. */
+typedef struct fgoicp_batch_refine_t {
+    uint32_t struct_size;        /* sizeof(fgoicp_batch_refine_t) as the caller was compiled */
+    int      model;              /* -1, FGOICP_MODEL_PLANE or FGOICP_MODEL_GICP */
+    int      k;                  /* neighbours per normal, 4 .. 32 */
+    size_t   max_iter;
+    float    conv_thr;
+    float    max_distance;       /* >= 0, +inf: no threshold */
+    double   epsilon;            /* FGOICP_MODEL_GICP: in (0, 1] */
+    int      loss;               /* FGOICP_LOSS_* */
+    double   loss_scale;         /* finite; <= 0: estimated at the search's pose */
+} fgoicp_batch_refine_t;
 typedef struct fgoicp_batch_opts {
     size_t struct_size;          /* sizeof(fgoicp_batch_opts) as the caller was compiled (ABI 2): members beyond it are taken as 0 */
     fgoicp_solver_opts solver;   /* schedule, round_width, ctx_flags, device; trim_fraction must be 0 (trimming is per pair: trim_fractions) */
@@ -939,9 +953,19 @@ typedef struct fgoicp_batch_opts {
                                     revision 2: 0 for a caller built with a shorter struct (struct_size) */
     float information_max_distance; /* its distance threshold in the callers' units, as fgoicp_solver_information takes it; <= 0: none.  NaN is refused */
 } fgoicp_batch_opts;
+/* EXTENSION: the options of a batch that refines.  fgoicp_batch_create reads its options as struct_size bytes, so what is appended to them
+ * lies behind fgoicp_batch_opts, whose own 56 bytes stay as published (callers and bindings hold that size): fill this struct, set
+ * opts.struct_size = sizeof(fgoicp_batch_opts_refine) and pass &opts. */
+typedef struct fgoicp_batch_opts_refine {
+    fgoicp_batch_opts opts;      /* every member as above; struct_size covers this whole struct */
+    const fgoicp_batch_refine_t* refine; /* n entries, pair i refined after its search as entry i says; NULL, or a struct_size that ends before this member: no
+                                    pair is refined and the run takes no new path.  Appended within revision 2.  Read by fgoicp_batch_create only */
+} fgoicp_batch_opts_refine;
 /* Copies the clouds and pre-processes every pair on the host (centre, scale, bounds, inlier count, as fgoicp_solver_create); creates no
  * device state.  Refuses n <= 0, a null or empty cloud, solver.trim_fraction != 0, a trim_fractions entry that is NaN, negative or >= 1,
- * and a struct_size shorter than the solver options. */
+ * and a struct_size shorter than the solver options.  Every refine entry is refused as the solo entry points refuse their arguments, the message
+ * naming the pair: a bad struct_size, an unknown model or loss, k outside 4 .. 32, a negative or NaN max_distance, an epsilon outside (0, 1]
+ * for FGOICP_MODEL_GICP, a loss_scale that is not finite. */
 int fgoicp_batch_create(const fgoicp_batch_pair* pairs, int n, const fgoicp_batch_opts* opts, fgoicp_batch** out);
 /* Runs every pair: pairs enter a window of at most max_live live pairs in index order; a pair's context is created when it enters
  * and destroyed when it finishes.  Returns FGOICP_OK when the batch ran; status_n[i] is pair i's own status (a pair that cannot be
@@ -963,6 +987,23 @@ int fgoicp_batch_information(const fgoicp_batch* b, int i, fgoicp_information_t*
  * arena fill for trimmed pairs; neither the finalize nor the trimmed selection counted) and lock-step ICP iterations (one host
  * turn-around each, shared by every active ICP run). */
 int fgoicp_batch_launches(const fgoicp_batch* b, uint64_t* bounds_launches, uint64_t* icp_launches);
+/* EXTENSION: refinement inside a batch (fgoicp_batch_opts_refine.refine).  A pair with a refine entry is refined from its
+ * search's pose before its context is released, and returns, byte for byte, what fgoicp_solver_refine_plane / _gicp (loss none) or
+ * fgoicp_solver_refine_robust returns for that pair alone with the same arguments — t restored, scaling_factor the pair's — whatever the
+ * other pairs, their order, their entries, the window or the grouping into launches: the loops of all refining pairs advance one
+ * evaluation per tick, their moments reduced by one fused launch per class (model x weighted) over per-pair blocks, rows and folds, the
+ * host turn-around shared.  What the batch returns otherwise (R, t, errors, counters, fgoicp_batch_alignment, fgoicp_batch_information at
+ * the SEARCH's pose) is unchanged, bit for bit.  Both getters refuse (FGOICP_ERR_INVALID_ARG) the other kind, a pair without an entry, a
+ * call before fgoicp_batch_run and a pair whose search failed; a refinement that was itself refused (no scale to estimate: "pass a scale")
+ * or failed left the pair's search result and status alone, and the getter returns that refinement's own status and message. */
+int fgoicp_batch_refined_plane(const fgoicp_batch* b, int i, fgoicp_plane_result_t* out);
+int fgoicp_batch_refined_robust(const fgoicp_batch* b, int i, fgoicp_robust_result_t* out);
+/* The information matrix at pair i's REFINED pose (needs fgoicp_batch_opts.information and a refined pair): the restored translation taken
+ * back into the solver's frame, fgoicp_information there, fgoicp_information_from_moments — the bytes the command-line tool writes for that
+ * pair alone (one text of that arithmetic serves both: csrc/host/refined_pose.hpp). */
+int fgoicp_batch_refined_information(const fgoicp_batch* b, int i, fgoicp_information_t* out);
+/* Of the last run: fused moment launches (one per class present in a tick) and evaluations (one per refining pair per tick). */
+int fgoicp_batch_refine_launches(const fgoicp_batch* b, uint64_t* fused_launches, uint64_t* evaluations);
 void fgoicp_batch_destroy(fgoicp_batch* b);
 /* TEST HOOK, not part of the drop-in surface: one tick of the batch's bounds path over contexts the caller made (fgoicp_ctx_create;
  * borrowed, not destroyed).  Request q goes to ctxs[req_ctx[q]] (a context may be named by several requests) with req_G[q] groups; R9,
@@ -987,6 +1028,15 @@ int fgoicp_batch_test_trim_bounds(fgoicp_ctx* const* ctxs, int nctx, int nreq, c
  * run after the other (9 / 3 floats per run). */
 int fgoicp_batch_test_icp(fgoicp_ctx* const* ctxs, int n, const int* start_pass, const float* R0s_9, const float* t0s_3, const size_t* max_iter,
                           const float* thr, float* sse_out, float* R_out9, float* t_out3, int* iters_out);
+/* TEST HOOK, not part of the drop-in surface: n refinement loops stepped as a batch steps them, run i on ctxs[i] (borrowed; each context
+ * once, all on one device; the normals must be set).  specs[i] in the CONTEXT frame: max_distance holds max_dist2, loss_scale the scale,
+ * k is not read; loss none runs fgoicp_icp_plane's / fgoicp_icp_gicp's loop, another loss fgoicp_icp_robust's.  Pass p starts the runs whose
+ * start_pass is p, then advances every active run by one evaluation in the fused launches of a batch tick.  out_n[i]: run i's
+ * fgoicp_robust_result_t, or (loss none) an fgoicp_plane_result_t in the slot's first bytes, the rest zero — the bytes of the solo call.
+ * status_n[i] / messages_n256 (optional, 256 chars per run): a run's own refusal or failure, with the solo call's message; the other
+ * runs go on.  fused_launches_out (optional): fused moment launches made. */
+int fgoicp_batch_test_refine(fgoicp_ctx* const* ctxs, int n, const fgoicp_batch_refine_t* specs, const int* start_pass, const float* R0s_9, const float* t0s_3,
+                             fgoicp_robust_result_t* out_n, int* status_n, char* messages_n256, uint64_t* fused_launches_out);
 
 #ifdef __cplusplus
 }

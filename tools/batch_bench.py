@@ -3,6 +3,9 @@
     python tools/batch_bench.py --workload a      # 64 pairs of ~1k source / 2k target points, lut_resolution 0.01, mse_threshold 1e-3
     python tools/batch_bench.py --workload b      # 16 pairs of the size of the reference's test/bunny.toml (~3k / 18k points)
     python tools/batch_bench.py --trim 0.2        # every pair trimmed (trim_fraction 0.2; a tenth of each source replaced by outliers)
+    python tools/batch_bench.py --refine gicp:tukey --pairs 16 --rounds 2
+                                                  # every pair refined (MODEL[:LOSS]): a batch with refine= against a loop of solo solvers that
+                                                  # run and refine, the two sides alternating, --rounds runs each; its own JSON line
 
 Prints one JSON line: wall time of the batch and of the loop (the loop split into context creation = LUT builds, and runs), the
 ratio, whether every pair of the batch is bit-equal to its solo run (R, t, best error, counters), and the fused bounds launches of
@@ -31,6 +34,35 @@ def make_pairs(w, seed, trim=0.0):
     return pairs
 
 
+def refine_bench(a, w, pairs, kw):
+    """--refine: a batch with refine= against a loop of solo solvers that run and refine, alternating; every pair's refinement compared byte
+    for byte."""
+    model, _, loss = a.refine.partition(":")
+    spec = {"model": model, "loss": loss or None}
+    loop_s, batch_s, equal, launches = [], [], [], (0, 0)
+    for _ in range(a.rounds):
+        t0 = time.perf_counter()
+        solo = []
+        for p in pairs:
+            s = fg.FastGoICP(*p, **kw)
+            s.run()
+            solo.append((s.refine_gicp if model == "gicp" else s.refine_plane)(loss=spec["loss"]).raw)
+            s.close()
+        loop_s.append(time.perf_counter() - t0)
+        b = fg.FastGoICPBatch(pairs, max_live=a.max_live, refine=spec, **kw)
+        t0 = time.perf_counter()
+        out = b.run()
+        batch_s.append(time.perf_counter() - t0)
+        equal = [out[i] is not None and b.refined(i).raw == solo[i] for i in range(len(pairs))]
+        launches = b.refine_launches()
+        b.close()
+    print(json.dumps({
+        "workload": a.workload, "pairs": len(pairs), "ns": w["ns"], "nt": w["nt"], "lut_resolution": w["lut"], "mse_threshold": w["mse"], "schedule": a.schedule,
+        "refine": a.refine, "rounds": a.rounds, "batch_s": [round(t, 4) for t in batch_s], "loop_run_and_refine_s": [round(t, 4) for t in loop_s],
+        "speedup_vs_loop": round(min(loop_s) / min(batch_s), 3), "refined_byte_equal": all(equal),
+        "fused_refine_launches": launches[0], "refine_evaluations": launches[1]}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="a")
@@ -40,8 +72,13 @@ def main():
     ap.add_argument("--trim", type=float, default=0.0, help="trim_fraction of every pair (0: untrimmed)")
     ap.add_argument("--alignment", action="store_true", help="the batch keeps every pair's alignment report (fgoicp_batch_opts.alignment)")
     ap.add_argument("--information", action="store_true", help="the batch keeps every pair's information matrix (fgoicp_batch_opts.information)")
+    ap.add_argument("--refine", default="", help="MODEL[:LOSS], e.g. plane or gicp:tukey: every pair refined after its search; times the batch against a loop that runs and refines")
+    ap.add_argument("--pairs", type=int, default=0, help="pairs of the workload (0: its own count)")
+    ap.add_argument("--rounds", type=int, default=2, help="--refine: runs of each side, alternating")
     a = ap.parse_args()
-    w = WORKLOADS[a.workload]
+    w = dict(WORKLOADS[a.workload])
+    if a.pairs > 0:
+        w["n"] = a.pairs
     sched = fg.SCHEDULE_ROUND if a.schedule == "round" else fg.SCHEDULE_SERIAL
     rw = 0 if sched == fg.SCHEDULE_ROUND else 1
     pairs = make_pairs(w, a.seed, a.trim)
@@ -53,6 +90,8 @@ def main():
     s = fg.FastGoICP(*pairs[0], **kw)
     s.run()
     s.close()
+    if a.refine:
+        return refine_bench(a, w, pairs, kw)
 
     solo, t_create, t_run = [], 0.0, 0.0
     for p in pairs:
