@@ -10,7 +10,7 @@ from ._lib import (FLAG_BRUTE_FORCE_NN, FLAG_CURVE_ORDER, FLAG_NO_MORTON, FLAG_N
                    TRANSPORT_RCCL, FgoicpError, dev_knobs, live_resources)
 from .registration import (Alignment, GicpRefinement, Information, IterativeClosestPoint3D, PlaneMomentsResult, PlaneRefinement, Registration, RobustMomentsResult, RobustRefinement, StreamPool, cloud_stats, cluster_dbscan, icp_batch,  # noqa: F401
                            farthest_point_sample, gicp_terms, information_from_moments, plane_apply_step, plane_step_from_moments, remove_radius_outliers, remove_statistical_outliers, robust_weight, segment_fit_from_moments,
-                           segment_hypotheses, segment_planes, voxel_downsample, SEGMENT_CHUNK, SEGMENT_TILE)
+                           sample_mesh, sample_mesh_even, segment_hypotheses, segment_planes, voxel_downsample, SEGMENT_CHUNK, SEGMENT_TILE)
 from .nodes import Rotation, RotNode, TransNode, from_glm, to_glm  # noqa: F401
 
 try:  # the driver mirror needs nothing beyond the C ABI, but keep import errors local to it

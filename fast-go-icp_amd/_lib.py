@@ -200,6 +200,15 @@ class SegmentInfo(C.Structure):
         self.struct_size = C.sizeof(SegmentInfo)  # the library writes no byte beyond it
 
 
+class MeshInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("vertices", C.c_uint64), ("triangles", C.c_uint64), ("samples", C.c_uint64), ("zero_area", C.c_uint64),
+                ("unweighted", C.c_uint64), ("weight_total", C.c_uint64), ("max_area", C.c_double), ("area", C.c_double)]
+
+    def __init__(self):
+        super().__init__()
+        self.struct_size = C.sizeof(MeshInfo)  # the library writes no byte beyond it
+
+
 OUTLIER_STATISTICAL = 0
 OUTLIER_RADIUS = 1
 
@@ -229,6 +238,10 @@ _SIGS = {
     "fgoicp_segment_hypotheses": (C.c_int, [c_float_p, C.c_size_t, c_uint32_p, C.c_size_t, C.c_int, C.c_uint64, C.c_int, c_uint32_p, C.POINTER(C.c_double), c_uint8_p]),
     "fgoicp_segment_fit_from_moments": (C.c_int, [C.c_uint64, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                                   C.POINTER(C.c_double)]),
+    "fgoicp_mesh_sample": (C.c_int, [c_float_p, C.c_size_t, c_uint32_p, C.c_size_t, C.c_size_t, C.c_uint64, C.c_int, c_float_p, c_float_p, c_uint32_p, c_double_p, c_double_p,
+                                     C.POINTER(MeshInfo)]),
+    "fgoicp_solver_set_target_normals": (C.c_int, [C.c_void_p, c_float_p]),
+    "fgoicp_solver_set_source_normals": (C.c_int, [C.c_void_p, c_float_p]),
     "fgoicp_lut_read": (C.c_int, [C.c_void_p, c_float_p, C.c_size_t]),
     "fgoicp_lut_search": (C.c_int, [C.c_void_p, c_float_p, C.c_size_t, c_float_p]),
     "fgoicp_lut_nodes": (C.c_int, [C.c_void_p, c_int_p, C.c_size_t, c_float_p]),

@@ -26,6 +26,7 @@ SOURCES = [
     os.path.join(CSRC, "device", "fps.hip"),
     os.path.join(CSRC, "device", "cluster.hip"),
     os.path.join(CSRC, "device", "segment.hip"),
+    os.path.join(CSRC, "device", "mesh.hip"),
     os.path.join(CSRC, "host", "solver.cpp"),
     os.path.join(CSRC, "host", "multi.cpp"),
     os.path.join(CSRC, "host", "batch.cpp"),

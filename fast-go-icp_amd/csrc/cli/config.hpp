@@ -1,7 +1,8 @@
 // CLI-side configuration and cloud loaders — the caller side of the drop-in (reference
 // src/utilities.hpp:18-260, test/bunny.toml).  Own minimal parsers: a TOML subset (tables, string /
 // bool / integer / float values, comments) and PLY (ascii, binary little/big endian; any scalar
-// property types; list properties and foreign elements are skipped) — the reference vendors toml++,
+// property types; list properties and foreign elements are skipped, but for the faces' vertex list when
+// a mesh is asked for: load_mesh_ply) — the reference vendors toml++,
 // CLI11 and tinyply for these, none of which are copied here.
 #pragma once
 #include <algorithm>
@@ -156,6 +157,10 @@ struct Config {
         int target_plane_iterations = 1000, source_plane_iterations = 1000;
         int target_plane_count = 1, source_plane_count = 1;
         double target_plane_min_fraction = 0.1, source_plane_min_fraction = 0.1;
+        // EXTENSION: mesh input (fgoicp_mesh_sample).  *_mesh_points: the cloud becomes that many samples of the SURFACE of the file's triangle
+        // mesh (a PLY with faces) in place of its vertices, before everything that sees the loaded cloud, *_subsample included; absent or <= 0:
+        // off.  A value that is not an integer is refused.
+        int target_mesh_points = 0, source_mesh_points = 0;
     } params;
 
     explicit Config(const std::string& toml_filepath) {
@@ -246,6 +251,8 @@ struct Config {
             };
             params.target_points = count("target_points");
             params.source_points = count("source_points");
+            params.target_mesh_points = count("target_mesh_points");
+            params.source_mesh_points = count("source_mesh_points");
             params.target_cluster_eps = (float)strict("target_cluster_eps", 0.0);
             params.source_cluster_eps = (float)strict("source_cluster_eps", 0.0);
             auto whole = [&](const char* key, double def) {  // as strict, and the number must be an integer; the call judges its range
@@ -347,40 +354,47 @@ inline double read_scalar(std::istream& f, const std::string& t, bool swap) {
     if (t == "float" || t == "float32") { float v; std::memcpy(&v, b, 4); return v; }
     double v; std::memcpy(&v, b, 8); return v;
 }
+// the header of an opened file, up to and including end_header: the elements in file order and how the data behind them is written
+struct Header { std::vector<Element> elements; bool ascii = false, swap = false; };
+inline Header read_header(std::ifstream& f, const std::string& path) {
+    if (!f) throw std::runtime_error("Unable to open file: " + path);
+    std::string line;
+    std::getline(f, line);
+    if (trim(line) != "ply") throw std::runtime_error("not a PLY file");
+    std::string format;
+    Header h;
+    while (std::getline(f, line)) {
+        std::istringstream ls(trim(line));
+        std::string tok;
+        ls >> tok;
+        if (tok == "format") ls >> format;
+        else if (tok == "element") { Element e; ls >> e.name >> e.count; h.elements.push_back(e); }
+        else if (tok == "property") {
+            if (h.elements.empty()) throw std::runtime_error("property before element");
+            Property p;
+            std::string t;
+            ls >> t;
+            if (t == "list") { p.is_list = true; ls >> p.count_type >> p.type >> p.name; }
+            else { p.type = t; ls >> p.name; }
+            h.elements.back().props.push_back(p);
+        } else if (tok == "end_header") break;
+    }
+    h.ascii = format == "ascii";
+    const bool big = format == "binary_big_endian";
+    if (!h.ascii && !big && format != "binary_little_endian") throw std::runtime_error("unsupported PLY format '" + format + "'");
+    const uint16_t probe = 1;
+    const bool host_little = *reinterpret_cast<const uint8_t*>(&probe) == 1;
+    h.swap = !h.ascii && (big == host_little);
+    return h;
+}
 }  // namespace ply
 
 inline size_t load_cloud_ply(const std::string& path, float subsample, std::vector<icp::vec3>& cloud, long long seed) {
     try {
         std::ifstream f(path, std::ios::binary);
-        if (!f) throw std::runtime_error("Unable to open file: " + path);
-        std::string line;
-        std::getline(f, line);
-        if (trim(line) != "ply") throw std::runtime_error("not a PLY file");
-        std::string format;
-        std::vector<ply::Element> elements;
-        while (std::getline(f, line)) {
-            std::istringstream ls(trim(line));
-            std::string tok;
-            ls >> tok;
-            if (tok == "format") ls >> format;
-            else if (tok == "element") { ply::Element e; ls >> e.name >> e.count; elements.push_back(e); }
-            else if (tok == "property") {
-                if (elements.empty()) throw std::runtime_error("property before element");
-                ply::Property p;
-                std::string t;
-                ls >> t;
-                if (t == "list") { p.is_list = true; ls >> p.count_type >> p.type >> p.name; }
-                else { p.type = t; ls >> p.name; }
-                elements.back().props.push_back(p);
-            } else if (tok == "end_header") break;
-        }
-        const bool ascii = format == "ascii";
-        const bool big = format == "binary_big_endian";
-        if (!ascii && !big && format != "binary_little_endian") throw std::runtime_error("unsupported PLY format '" + format + "'");
-        const uint16_t probe = 1;
-        const bool host_little = *reinterpret_cast<const uint8_t*>(&probe) == 1;
-        const bool swap = !ascii && (big == host_little);
-        for (const ply::Element& e : elements) {
+        const ply::Header header = ply::read_header(f, path);
+        const bool ascii = header.ascii, swap = header.swap;
+        for (const ply::Element& e : header.elements) {
             const bool is_vertex = e.name == "vertex";
             int ix = -1, iy = -1, iz = -1;
             for (size_t k = 0; k < e.props.size(); ++k) {
@@ -423,6 +437,87 @@ inline size_t load_cloud_ply(const std::string& path, float subsample, std::vect
     } catch (const std::exception& err) {
         throw std::runtime_error(std::string("Error reading PLY file: ") + err.what());
     }
+}
+
+// EXTENSION (params.*_mesh_points): the PLY as a triangle mesh — every vertex (no subsampling here) and the faces of `element face`, read
+// from its list property vertex_indices or vertex_index, any integer count and index type, in the three formats.  A polygon of k > 3
+// vertices is fan-triangulated as (i0, ij, ij+1); a face of fewer than 3 is dropped and counted in *short_faces.  Every other list, element
+// and property is passed over as load_cloud_ply passes over it.  A file without faces returns no triangles: the caller judges that.
+inline void load_mesh_ply(const std::string& path, std::vector<icp::vec3>& vertices, std::vector<uint32_t>& triangles, size_t* short_faces = nullptr) {
+    try {
+        std::ifstream f(path, std::ios::binary);
+        const ply::Header header = ply::read_header(f, path);
+        const bool ascii = header.ascii, swap = header.swap;
+        auto scalar = [&](const std::string& type) {
+            double v;
+            if (ascii) { if (!(f >> v)) throw std::runtime_error("unexpected end of PLY data"); }
+            else v = ply::read_scalar(f, type, swap);
+            return v;
+        };
+        size_t dropped = 0;
+        bool have_vertices = false;
+        std::vector<uint32_t> poly;
+        for (const ply::Element& e : header.elements) {
+            const bool is_vertex = e.name == "vertex", is_face = e.name == "face";
+            int ix = -1, iy = -1, iz = -1;
+            for (size_t k = 0; k < e.props.size(); ++k) {
+                if (e.props[k].name == "x") ix = (int)k;
+                if (e.props[k].name == "y") iy = (int)k;
+                if (e.props[k].name == "z") iz = (int)k;
+            }
+            if (is_vertex && (ix < 0 || iy < 0 || iz < 0)) throw std::runtime_error("PLY file missing 'x', 'y', or 'z' vertex properties.");
+            if (is_vertex && e.count == 0) throw std::runtime_error("No vertices found in the PLY file.");
+            if (is_vertex) { vertices.reserve(e.count); have_vertices = true; }
+            std::vector<double> vals(e.props.size());
+            for (size_t i = 0; i < e.count; ++i) {
+                for (size_t k = 0; k < e.props.size(); ++k) {
+                    const ply::Property& p = e.props[k];
+                    if (!p.is_list) { vals[k] = scalar(p.type); continue; }
+                    const bool corners = is_face && (p.name == "vertex_indices" || p.name == "vertex_index");
+                    const long long n = (long long)scalar(p.count_type);
+                    poly.clear();
+                    for (long long j = 0; j < n; ++j) {
+                        const double v = scalar(p.type);
+                        if (!corners) continue;
+                        if (!(v >= 0.0 && v <= 4294967295.0)) throw std::runtime_error("face " + std::to_string(i) + " has a vertex index outside [0, 2^32)");
+                        poly.push_back((uint32_t)v);
+                    }
+                    if (!corners) continue;
+                    if (poly.size() < 3) { ++dropped; continue; }
+                    for (size_t j = 1; j + 1 < poly.size(); ++j) {
+                        triangles.push_back(poly[0]); triangles.push_back(poly[j]); triangles.push_back(poly[j + 1]);
+                    }
+                }
+                if (is_vertex) vertices.emplace_back((float)vals[ix], (float)vals[iy], (float)vals[iz]);
+            }
+        }
+        if (!have_vertices) throw std::runtime_error("No vertices found in the PLY file.");
+        if (short_faces) *short_faces = dropped;
+    } catch (const std::exception& err) {
+        throw std::runtime_error(std::string("Error reading PLY file: ") + err.what());
+    }
+}
+
+// params.*_subsample over a cloud that was not thinned while it was read (a sampled mesh): load_cloud_txt's rule — the RNG is drawn for
+// every point, a point is kept with probability `subsample` until floor(total * subsample) are kept
+inline void subsample_cloud(std::vector<icp::vec3>& cloud, float subsample, long long seed) {
+    Subsampler ss(cloud.size(), subsample, seed);
+    std::vector<icp::vec3> out;
+    out.reserve(ss.budget);
+    for (const icp::vec3& p : cloud)
+        if (ss.keep() && ss.kept < ss.budget) {
+            out.push_back(p);
+            ++ss.kept;
+        }
+    cloud.swap(out);
+}
+
+inline bool is_ply(const std::string& filepath) {
+    const auto dot = filepath.find_last_of('.');
+    if (dot == std::string::npos) return false;
+    std::string ext = filepath.substr(dot + 1);
+    std::transform(ext.begin(), ext.end(), ext.begin(), ::tolower);
+    return ext == "ply";
 }
 
 inline size_t load_cloud(const std::string& filepath, float subsample, std::vector<icp::vec3>& cloud, long long seed = -1) {

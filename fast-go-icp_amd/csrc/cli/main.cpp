@@ -24,6 +24,38 @@ static std::string usage(const std::string& exe) {
            "  -b,--batch LIST             Run every config listed in LIST (one path per line, relative to LIST) as one batch on one GPU\n\nExample Usage:\n  " + exe + " -c config.toml --verbose\n  " + exe + " --config=config.toml\n";
 }
 
+// One cloud of a run.  params.*_mesh_points off: cli::load_cloud, as ever.  On: the file is read as a triangle mesh (cli::load_mesh_ply) and
+// the cloud is that many samples of its surface (fgoicp_mesh_sample on device 0; the seed is params.seed if >= 0, else 0), then thinned by
+// *_subsample as a loaded cloud is: everything downstream sees the samples.  A TXT file, a PLY without faces and a mesh without area are
+// errors of the configuration: exit code 1.  The face normals are not carried through the filters: params.refine keeps estimating its own.
+static void load_input(const std::string& path, float subsample, int mesh_points, long long load_seed, long long params_seed, std::vector<icp::vec3>& pc, const char* which) {
+    if (mesh_points <= 0) {
+        cli::load_cloud(path, subsample, pc, load_seed);
+        return;
+    }
+    auto fail = [&](const std::string& why) {
+        icp::Logger(icp::LogLevel::Error) << "params." << which << "_mesh_points = " << mesh_points << ": " << why;
+        std::exit(1);
+    };
+    if (!cli::is_ply(path)) fail(path + " is not a PLY file: only a PLY holds a mesh");
+    std::vector<icp::vec3> vertices;
+    std::vector<uint32_t> triangles;
+    size_t short_faces = 0;
+    cli::load_mesh_ply(path, vertices, triangles, &short_faces);
+    if (triangles.empty()) fail(path + " has no faces (element face with a vertex_indices list)");
+    pc.assign((size_t)mesh_points, icp::vec3{});
+    fgoicp_mesh_info_t mi{};
+    mi.struct_size = sizeof(mi);
+    const int rc = fgoicp_mesh_sample(&vertices.data()->x, vertices.size(), triangles.data(), triangles.size() / 3, pc.size(), (uint64_t)(params_seed < 0 ? 0 : params_seed), 0,
+                                      &pc.data()->x, nullptr, nullptr, nullptr, nullptr, &mi);
+    if (rc != FGOICP_OK) fail("status " + std::to_string(rc) + ": " + fgoicp_last_error());
+    icp::Logger log(icp::LogLevel::Info);
+    log << "Mesh sampling (" << which << "): " << mi.vertices << " vertices, " << mi.triangles << " triangles (" << mi.zero_area << " zero-area, " << mi.unweighted
+        << " unweighted), area " << mi.area << " -> " << pc.size() << " points";
+    if (short_faces) log << "; " << short_faces << " faces of fewer than 3 vertices dropped";
+    cli::subsample_cloud(pc, subsample, load_seed);
+}
+
 // params.target_voxel / params.source_voxel: the loaded cloud replaced by the centroids of its voxel grid (fgoicp_voxel_downsample on device 0,
 // the origin is the cloud's own minimum), once, before any solver exists: everything downstream sees the thinned cloud.  A refused size
 // (too small for the cloud's extent, not finite) is an error of the configuration: reported, exit code 1.
@@ -216,8 +248,8 @@ static int run_batch(const std::string& list_file) {
     std::vector<float> trim(n);
     for (size_t i = 0; i < n; ++i) {
         const cli::Config& c = configs[i];
-        cli::load_cloud(c.io.target, c.params.target_subsample, pct[i], c.params.seed);
-        cli::load_cloud(c.io.source, c.params.source_subsample, pcs[i], c.params.seed < 0 ? -1 : c.params.seed + 1);
+        load_input(c.io.target, c.params.target_subsample, c.params.target_mesh_points, c.params.seed, c.params.seed, pct[i], "target");
+        load_input(c.io.source, c.params.source_subsample, c.params.source_mesh_points, c.params.seed < 0 ? -1 : c.params.seed + 1, c.params.seed, pcs[i], "source");
         voxel_thin(pct[i], c.params.target_voxel, "target");
         voxel_thin(pcs[i], c.params.source_voxel, "source");
         outlier_filter(pct[i], c.params.target_outlier_knn, c.params.target_outlier_std, c.params.target_outlier_radius, "target");
@@ -366,9 +398,10 @@ int main(int argc, char* argv[]) {
         }
     }();
     std::vector<icp::vec3> pct, pcs;
-    cli::load_cloud(config.io.target, config.params.target_subsample, pct, config.params.seed);
+    load_input(config.io.target, config.params.target_subsample, config.params.target_mesh_points, config.params.seed, config.params.seed, pct, "target");
     icp::Logger(icp::LogLevel::Info) << "Target point cloud (" << pct.size() << ") loaded from " << config.io.target;
-    cli::load_cloud(config.io.source, config.params.source_subsample, pcs, config.params.seed < 0 ? -1 : config.params.seed + 1);
+    load_input(config.io.source, config.params.source_subsample, config.params.source_mesh_points, config.params.seed < 0 ? -1 : config.params.seed + 1, config.params.seed, pcs,
+               "source");
     icp::Logger(icp::LogLevel::Info) << "Source point cloud (" << pcs.size() << ") loaded from " << config.io.source;
     voxel_thin(pct, config.params.target_voxel, "target");
     voxel_thin(pcs, config.params.source_voxel, "source");

@@ -15,7 +15,10 @@ void set_error(const std::string& s);
 
 constexpr int kSegMaxIterations = 65536, kSegMaxPlanes = 16;
 
-// the splitmix64 finaliser
+// the splitmix64 finaliser; also the hash of fgoicp_mesh_sample's draws, which run on the device (mesh.hip)
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
 inline uint64_t seg_mix64(uint64_t z) {
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;

@@ -322,6 +322,19 @@ int fgoicp_solver_information(fgoicp_solver* s, float max_distance, fgoicp_infor
     return information_out(full, out, "fgoicp_solver_information");
 }
 
+// Given normals: the context call with the pointer (normals do not change under the solver's centring and uniform scale); solver_refine
+// then estimates only the set that is still missing.
+int fgoicp_solver_set_target_normals(fgoicp_solver* s, const float* normals_nt3) {
+    if (!s) { set_error("fgoicp_solver_set_target_normals: the solver must not be null"); return FGOICP_ERR_INVALID_ARG; }
+    if (!normals_nt3) { set_error("fgoicp_solver_set_target_normals: the normals must not be null"); return FGOICP_ERR_INVALID_ARG; }
+    return fgoicp::abi_guard("fgoicp_solver_set_target_normals", [&] { return ctx_set_target_normals(s->ctx, normals_nt3, 0); });
+}
+int fgoicp_solver_set_source_normals(fgoicp_solver* s, const float* normals_ns3) {
+    if (!s) { set_error("fgoicp_solver_set_source_normals: the solver must not be null"); return FGOICP_ERR_INVALID_ARG; }
+    if (!normals_ns3) { set_error("fgoicp_solver_set_source_normals: the normals must not be null"); return FGOICP_ERR_INVALID_ARG; }
+    return fgoicp::abi_guard("fgoicp_solver_set_source_normals", [&] { return ctx_set_source_normals(s->ctx, normals_ns3, 0); });
+}
+
 int fgoicp_solver_refine_plane(fgoicp_solver* s, int k, size_t max_iter, float conv_thr, float max_distance, fgoicp_plane_result_t* out) {
     if (!s) { set_error("fgoicp_solver_refine_plane: the solver must not be null"); return FGOICP_ERR_INVALID_ARG; }
     if (!s->ran) { set_error("fgoicp_solver_refine_plane: fgoicp_solver_run has not succeeded yet: there is no best transform"); return FGOICP_ERR_INVALID_ARG; }

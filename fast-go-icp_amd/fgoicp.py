@@ -65,6 +65,22 @@ class FastGoICP:
         d = float("inf") if max_distance is None else float(max_distance)
         return _information(lambda out: self._lib.fgoicp_solver_information(self._h, d, out), "fgoicp_solver_information")
 
+    def _set_normals(self, normals, n, call, name):
+        a = _cloud(normals)
+        if len(a) != n:
+            raise ValueError(f"normals must be ({n}, 3): one per point of the cloud as passed in")
+        _lib.check(call(self._h, _fp(a)), name)
+
+    def set_target_normals(self, normals):
+        """EXTENSION (fgoicp_solver_set_target_normals): the target's normals (nt, 3), given — those of a mesh's faces (sample_mesh), for
+        instance — in the order of the target as passed in; normalised on upload.  refine_plane / refine_gicp then use them and estimate
+        only what is not set (k is ignored for a set that is given)."""
+        self._set_normals(normals, self.nt, self._lib.fgoicp_solver_set_target_normals, "fgoicp_solver_set_target_normals")
+
+    def set_source_normals(self, normals):
+        """EXTENSION (fgoicp_solver_set_source_normals): the source's normals (ns, 3), as set_target_normals; used by refine_gicp."""
+        self._set_normals(normals, self.ns, self._lib.fgoicp_solver_set_source_normals, "fgoicp_solver_set_source_normals")
+
     def _refine_robust(self, model, k, max_iter, conv_thr, max_distance, epsilon, loss, loss_scale):
         d = float("inf") if max_distance is None else float(max_distance)
         raw = _lib.RobustResult()

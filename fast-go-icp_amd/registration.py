@@ -126,6 +126,62 @@ def farthest_point_sample(points, m, start_index=0, device=0, return_map=False):
                                              cover_dist2=np.float32(info.cover_dist2))
 
 
+def _mesh(vertices, triangles):
+    v = _cloud(vertices)
+    t = np.asarray(triangles)
+    if t.ndim != 2 or t.shape[1] != 3 or t.dtype.kind not in "iu":
+        raise ValueError("triangles must be an (nf, 3) array of integers")
+    if t.size and (int(t.min()) < 0 or int(t.max()) > 0xFFFFFFFF):
+        raise ValueError("a triangle index must lie in [0, 2^32)")
+    return v, np.ascontiguousarray(t, dtype=np.uint32)
+
+
+def sample_mesh(vertices, triangles, m, seed=0, device=0, return_map=False):
+    """fgoicp_mesh_sample: m points on the surface of the triangle mesh (vertices (nv, 3) float32, triangles (nf, 3) vertex indices), spread
+    over the faces in proportion to their area, as an (m, 3) float32 array.  Sample k is a function of (mesh, seed, k): two calls return the
+    same bytes and every prefix is the sampling of that size.  return_map=True returns (points, normals (m, 3) float32 — the unit normal of
+    each sample's face, along the winding —, face (m,) uint32, uv (m, 2) float64, face_area (nf,) float64, info) with
+    info = dict(vertices, triangles, samples, zero_area, unweighted, weight_total, max_area, area)."""
+    v, t = _mesh(vertices, triangles)
+    for name, x in (("m", m), ("seed", seed)):
+        if isinstance(x, bool) or not isinstance(x, (int, np.integer)):
+            raise TypeError(f"{name} must be an integer")
+    if m < 1:
+        raise ValueError("m must be at least 1")
+    m, nv, nf = int(m), len(v), len(t)
+    out = np.empty((m, 3), np.float32)
+    nrm = np.empty((m, 3), np.float32) if return_map else None
+    face = np.empty(m, np.uint32) if return_map else None
+    uv = np.empty((m, 2), np.float64) if return_map else None
+    area = np.empty(nf, np.float64) if return_map else None
+    ptr = lambda a, ty: None if a is None else a.ctypes.data_as(ty)
+    info = _lib.MeshInfo()
+    _lib.check(_lib.load().fgoicp_mesh_sample(_fp(v) if nv else None, nv, ptr(t, _lib.c_uint32_p) if nf else None, nf, m, int(seed) & 0xFFFFFFFFFFFFFFFF, int(device), _fp(out),
+                                              ptr(nrm, _lib.c_float_p), ptr(face, _lib.c_uint32_p), ptr(uv, _lib.c_double_p), ptr(area, _lib.c_double_p), C.byref(info)),
+               "fgoicp_mesh_sample")
+    if not return_map:
+        return out
+    return out, nrm, face, uv, area, dict(vertices=int(info.vertices), triangles=int(info.triangles), samples=int(info.samples), zero_area=int(info.zero_area),
+                                          unweighted=int(info.unweighted), weight_total=int(info.weight_total), max_area=float(info.max_area), area=float(info.area))
+
+
+def sample_mesh_even(vertices, triangles, m, init_factor=5, seed=0, device=0, return_map=False):
+    """The Poisson-disk recipe: sample_mesh draws init_factor * m surface samples and farthest_point_sample (start_index 0) thins them to
+    exactly m, evenly spread, in pick order.  return_map=True returns (points, normals (m, 3), face (m,), sample_index (m,) uint32 — the row
+    of the underlying init_factor * m samples each point is —, info of sample_mesh), normals and faces carried along through sample_index."""
+    for name, x in (("m", m), ("init_factor", init_factor)):
+        if isinstance(x, bool) or not isinstance(x, (int, np.integer)):
+            raise TypeError(f"{name} must be an integer")
+    if m < 1 or init_factor < 1:
+        raise ValueError("m and init_factor must be at least 1")
+    m = int(m)
+    if not return_map:
+        return farthest_point_sample(sample_mesh(vertices, triangles, m * int(init_factor), seed=seed, device=device), m, device=device)
+    pts, nrm, face, _, _, info = sample_mesh(vertices, triangles, m * int(init_factor), seed=seed, device=device, return_map=True)
+    out, idx = farthest_point_sample(pts, m, device=device, return_map=True)[:2]
+    return out, nrm[idx], face[idx], idx, info
+
+
 def cluster_dbscan(points, eps, min_points=10, keep_min_size=0, device=0, return_map=False):
     """fgoicp_cluster_dbscan: density clustering of the cloud (a point is core when at least min_points points, itself included, lie within
     eps; clusters are the connected components of the core points, numbered by their lowest index; a border point joins its nearest core

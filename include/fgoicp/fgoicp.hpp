@@ -58,6 +58,16 @@ public:
         check_status(fgoicp_solver_information(s_, max_distance, &f.result), "fgoicp_solver_information");
         return f;
     }
+    // EXTENSION: given normals (fgoicp_solver_set_target_normals / _source_normals), one per point of the cloud as passed in — a mesh knows
+    // them exactly (fgoicp_mesh_sample); the refinements below then estimate only the set that is not given
+    void set_target_normals(const std::vector<vec3>& normals) {
+        if (normals.size() != nt_) throw std::invalid_argument("FastGoICP::set_target_normals: one normal per target point");
+        check_status(fgoicp_solver_set_target_normals(s_, &normals.data()->x), "fgoicp_solver_set_target_normals");
+    }
+    void set_source_normals(const std::vector<vec3>& normals) {
+        if (normals.size() != ns_) throw std::invalid_argument("FastGoICP::set_source_normals: one normal per source point");
+        check_status(fgoicp_solver_set_source_normals(s_, &normals.data()->x), "fgoicp_solver_set_source_normals");
+    }
     // EXTENSION: point-to-plane refinement from the best transform, after run() (fgoicp_solver_refine_plane): R and t in the callers'
     // frame; normals estimated from k neighbours unless the context has some; max_distance in the callers' units, INFINITY: no threshold.
     // run() and the best transform are untouched.

@@ -838,6 +838,53 @@ int fgoicp_segment_hypotheses(const float* xyz, size_t n, const uint32_t* candid
                               uint32_t* sample_K3, double* plane_K4, uint8_t* degenerate_K);
 int fgoicp_segment_fit_from_moments(uint64_t count, const double* pivot3, const double* sum_u3, const double* sum_uu6, const double* toward4_or_NULL,
                                     double* plane4);
+/*
+ * EXTENSION — surface sampling of a triangle mesh on the device (no reference counterpart: its loaders keep a mesh's vertices only; Open3D:
+ * sample_points_uniformly, and with fgoicp_farthest_point_sample behind it sample_points_poisson_disk).  Turns a CAD or reconstructed model
+ * into the point cloud the rest of the pipeline takes: points spread over the FACES in proportion to their area, each with the exact normal
+ * of its face.
+ *
+ * Inputs: nv vertices (fp32 xyz triples), nf triangles (three uint32 vertex indices each), m samples, a seed.  ALL arithmetic is IEEE fp64 on
+ * the fp32 coordinates converted to double, every operation rounded on its own in the order written — no contraction, no reciprocal.
+ *   face f         a, b, c = its vertices;  e1 = b - a, e2 = c - a;
+ *                  n = (e1y*e2z - e1z*e2y, e1z*e2x - e1x*e2z, e1x*e2y - e1y*e2x);  n2 = (nx*nx + ny*ny) + nz*nz;  area_f = 0.5 * sqrt(n2)
+ *   weight         A_max = the largest area;  q_f = (uint64) floor(area_f / A_max * 4294967296.0);  Q = the inclusive 64-bit integer scan of q in
+ *                  face order, weight_total = Q[nf - 1].  Integer weights: the scan is exact however it is associated.  A face more than 2^32
+ *                  times smaller than the largest has weight 0 and is never sampled (counted in `unweighted`, as the faces of area 0 are)
+ *   draws          h(k, s) = mix64(seed + 0x9E3779B97F4A7C15 * (3k + s + 1)) mod 2^64, s = 0, 1, 2, mix64 the splitmix64 finaliser of
+ *                  fgoicp_segment_planes.  Counter based: any sample can be formed alone
+ *   sample k       r = the high 64 bits of h(k, 0) * weight_total;  face_k = the first f with Q[f] > r;
+ *                  u = (h(k, 1) >> 11) * 2^-53, v = (h(k, 2) >> 11) * 2^-53;  if u + v > 1.0 then u = 1 - u, v = 1 - v (no square root);
+ *                  point_k = (a + u*e1) + v*e2 per axis, rounded to fp32 once;  normal_k = n / sqrt(n2), three divisions, rounded to fp32:
+ *                  its direction follows the winding;  uv_k = (u, v)
+ * Sample k depends on (mesh, seed, k) alone: two calls return the same bytes, and every prefix of a result is the sampling of that size.
+ * Outputs: points_m3 is required; normals_m3, face_m (uint32), uv_m2 (doubles) per sample and face_area_nf (doubles) per face may be NULL.
+ * Refused with FGOICP_ERR_INVALID_ARG before any device work (one host pass over the mesh): null or empty vertices or triangles, a null
+ * points_m3, nv, nf or m at or above 2^31, m == 0, a non-finite vertex coordinate (the message names the vertex), a triangle index >= nv
+ * (the message names the face and the index), a null `info` or a struct_size that is 0, ends before `area` ends or is above 4096, a device
+ * ordinal out of range; and once the areas are known: A_max == 0, "the mesh has no area".  No usable device: FGOICP_ERR_NO_DEVICE (no CPU
+ * fallback); allocation failure: FGOICP_ERR_OOM.  The call owns its stream and its one device allocation (12 bytes per vertex, 36 per face
+ * and 12 to 44 per sample) and frees both before it returns; it touches no fgoicp_ctx, no global state and no knob and may be called from
+ * several threads.
+ */
+typedef struct fgoicp_mesh_info_t {
+    uint32_t struct_size;        /* IN: sizeof(fgoicp_mesh_info_t) as the CALLER was compiled; no byte beyond it is written, 0 is refused */
+    uint64_t vertices, triangles, samples;  /* nv, nf, m */
+    uint64_t zero_area;          /* faces with area == 0 */
+    uint64_t unweighted;         /* faces with weight 0, the zero_area ones included */
+    uint64_t weight_total;
+    double   max_area;
+    double   area;               /* = max_area * (double)weight_total / 2^32: the area the samples are spread over */
+} fgoicp_mesh_info_t;
+int fgoicp_mesh_sample(const float* vertices_nv3, size_t nv, const uint32_t* triangles_nf3, size_t nf, size_t m, uint64_t seed, int device,
+                       float* points_m3, float* normals_m3_or_NULL, uint32_t* face_m_or_NULL, double* uv_m2_or_NULL,
+                       double* face_area_nf_or_NULL, fgoicp_mesh_info_t* info);
+/* EXTENSION: given normals at solver level — fgoicp_ctx_set_target_normals / fgoicp_ctx_set_source_normals with the pointer, on the solver's
+ * context (nt / ns triples in the order the clouds were passed to fgoicp_solver_create, normalised on upload; normals are invariant under
+ * the solver's centring and uniform scale).  A mesh knows its normals exactly (fgoicp_mesh_sample).  fgoicp_solver_refine_plane / _gicp /
+ * _robust estimate only what is not set: with both sets given they ignore k.  Refusals carry the context call's message. */
+int fgoicp_solver_set_target_normals(fgoicp_solver* s, const float* normals_nt3);
+int fgoicp_solver_set_source_normals(fgoicp_solver* s, const float* normals_ns3);
 /* The operator context the solver drives (borrowed; valid until solver_destroy). */
 fgoicp_ctx* fgoicp_solver_ctx(fgoicp_solver* s);
 
