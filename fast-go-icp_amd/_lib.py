@@ -209,6 +209,17 @@ class MeshInfo(C.Structure):
         self.struct_size = C.sizeof(MeshInfo)  # the library writes no byte beyond it
 
 
+class MeshDistanceInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("vertices", C.c_uint64), ("triangles", C.c_uint64), ("queries", C.c_uint64), ("faces", C.c_uint64),
+                ("zero_area", C.c_uint64), ("tree_depth", C.c_uint32), ("leaf_faces", C.c_uint32), ("max_dist2_index", C.c_uint64), ("max_dist2", C.c_double)]
+
+    def __init__(self):
+        super().__init__()
+        self.struct_size = C.sizeof(MeshDistanceInfo)  # the library writes no byte beyond it
+
+
+MESH_DISTANCE_BRUTE = 1
+
 OUTLIER_STATISTICAL = 0
 OUTLIER_RADIUS = 1
 
@@ -240,6 +251,9 @@ _SIGS = {
                                                   C.POINTER(C.c_double)]),
     "fgoicp_mesh_sample": (C.c_int, [c_float_p, C.c_size_t, c_uint32_p, C.c_size_t, C.c_size_t, C.c_uint64, C.c_int, c_float_p, c_float_p, c_uint32_p, c_double_p, c_double_p,
                                      C.POINTER(MeshInfo)]),
+    "fgoicp_mesh_distance": (C.c_int, [c_float_p, C.c_size_t, c_uint32_p, C.c_size_t, c_float_p, C.c_size_t, C.c_uint32, C.c_int, c_uint32_p, c_float_p, c_double_p, c_uint8_p,
+                                       C.POINTER(C.c_int8), C.POINTER(MeshDistanceInfo)]),
+    "fgoicp_point_triangle": (C.c_int, [c_float_p, c_float_p, c_float_p, c_float_p, c_float_p, C.POINTER(C.c_double), c_int_p, c_int_p]),
     "fgoicp_solver_set_target_normals": (C.c_int, [C.c_void_p, c_float_p]),
     "fgoicp_solver_set_source_normals": (C.c_int, [C.c_void_p, c_float_p]),
     "fgoicp_lut_read": (C.c_int, [C.c_void_p, c_float_p, C.c_size_t]),

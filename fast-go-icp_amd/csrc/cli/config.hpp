@@ -111,7 +111,7 @@ inline TomlTable parse_toml(const std::string& path) {
 // Config — src/utilities.hpp:18-107 (same keys, defaults and clamps; `seed` is an addition)
 // ------------------------------------------------------------------------------------------
 struct Config {
-    struct IO { std::string target, source, output, visualization, alignment, information; } io;  // alignment, information: EXTENSION, optional (write_alignment_txt, write_information_txt)
+    struct IO { std::string target, source, output, visualization, alignment, information, deviation; } io;  // alignment, information, deviation: EXTENSION, optional (write_alignment_txt, write_information_txt, write_deviation_txt)
     struct Params {
         bool trim = false;
         float target_subsample = 1.0f, source_subsample = 1.0f, lut_resolution = 0.005f, mse_threshold = 1e-3f;
@@ -197,6 +197,7 @@ struct Config {
         io.visualization = str("io", "visualization", "");  // declared in test/bunny.toml:11, unparsed upstream
         io.alignment = str("io", "alignment", "");          // EXTENSION: where the alignment report goes ("" = none; not part of the printed summary)
         io.information = str("io", "information", "");      // EXTENSION: where the information matrix goes ("" = none; not part of the printed summary)
+        io.deviation = str("io", "deviation", "");          // EXTENSION: where the deviation map against the target's mesh goes ("" = none; not part of the printed summary)
         auto clampf0 = [](float x) { return x < 0.0f ? 0.0f : (x > 0.9f ? 0.9f : x); };
         if (tbl.count("params")) {
             params.trim = boolean("params", "trim", false);
@@ -592,6 +593,42 @@ inline void write_information_txt(const std::string& path, const fgoicp_informat
     f.precision(17);
     for (int r = 0; r < 6; ++r)
         for (int k = 0; k < 6; ++k) f << s.info[6 * r + k] << (k == 5 ? "\n" : " ");
+}
+
+// io.deviation (EXTENSION): the distance of every registered source point, moved by the run's final pose, from the SURFACE of the target
+// file's mesh (fgoicp_mesh_distance).  Two '#' lines — the summary, the column names — then one line per source point in the rows of
+// io.alignment: its coordinates as loaded, the nearest face (an index into the file's triangles after fan triangulation), its distance in
+// the files' units, the side of that face's plane (-1, 0, 1) and the region of the closest point (0 interior, 1 - 3 edge, 4 - 6 vertex).
+// The sums are plain fp64 loops in row order.
+struct DeviationSummary {
+    uint64_t points = 0, triangles = 0, zero_area = 0, negative = 0, on_plane = 0, positive = 0;
+    double mean = 0.0, rms = 0.0, max = 0.0;
+};
+inline DeviationSummary summarize_deviation(const fgoicp_mesh_distance_info_t& mi, const double* dist2, const int8_t* side) {
+    DeviationSummary s;
+    s.points = mi.queries; s.triangles = mi.triangles; s.zero_area = mi.zero_area;
+    double sum = 0.0, sum2 = 0.0;
+    for (uint64_t i = 0; i < s.points; ++i) {
+        const double d = std::sqrt(dist2[i]);
+        sum += d;
+        sum2 += dist2[i];
+        if (d > s.max) s.max = d;
+        (side[i] < 0 ? s.negative : side[i] > 0 ? s.positive : s.on_plane) += 1;
+    }
+    s.mean = s.points ? sum / (double)s.points : 0.0;
+    s.rms = s.points ? std::sqrt(sum2 / (double)s.points) : 0.0;
+    return s;
+}
+inline void write_deviation_txt(const std::string& path, const std::vector<icp::vec3>& src, const uint32_t* face, const double* dist2, const int8_t* side, const uint8_t* region,
+                                const DeviationSummary& s) {
+    std::ofstream f(path);
+    if (!f) throw std::runtime_error("Unable to write " + path);
+    f.precision(9);
+    f << "# deviation: points = " << s.points << ", triangles = " << s.triangles << ", zero_area = " << s.zero_area << ", mean = " << s.mean << ", rms = " << s.rms
+      << ", max = " << s.max << ", negative = " << s.negative << ", on_plane = " << s.on_plane << ", positive = " << s.positive << "\n";
+    f << "# x y z face distance side region\n";
+    for (size_t i = 0; i < src.size(); ++i)
+        f << src[i].x << " " << src[i].y << " " << src[i].z << " " << face[i] << " " << std::sqrt(dist2[i]) << " " << (int)side[i] << " " << (int)region[i] << "\n";
 }
 
 inline void write_visualization_ply(const std::string& path, const std::vector<icp::vec3>& tgt, const std::vector<icp::vec3>& src,

@@ -56,6 +56,53 @@ static void load_input(const std::string& path, float subsample, int mesh_points
     cli::subsample_cloud(pc, subsample, load_seed);
 }
 
+// io.deviation: the target FILE's mesh — every vertex and face (cli::load_mesh_ply), whether or not params.target_mesh_points sampled it for the
+// registration — read before anything runs, so that a TXT target and a PLY without faces end the run at once: exit code 1, the key named.
+struct DeviationMesh {
+    std::vector<icp::vec3> vertices;
+    std::vector<uint32_t> triangles;
+};
+static void load_deviation_mesh(const cli::Config& c, DeviationMesh& m) {
+    if (c.io.deviation.empty()) return;
+    auto fail = [&](const std::string& why) {
+        icp::Logger(icp::LogLevel::Error) << "io.deviation = \"" << c.io.deviation << "\": " << why;
+        std::exit(1);
+    };
+    if (!cli::is_ply(c.io.target)) fail("the target " + c.io.target + " is not a PLY file: only a PLY holds a mesh");
+    cli::load_mesh_ply(c.io.target, m.vertices, m.triangles);
+    if (m.triangles.empty()) fail("the target " + c.io.target + " has no faces (element face with a vertex_indices list)");
+}
+// ... and after the run: the source points the registration saw (the rows of io.alignment), moved by the final pose — the refined one when
+// params.refine is set, else the best transform; R9 in glm order, R9[col * 3 + row] — as write_visualization_ply moves them, formed in fp64
+// per axis, (R[a][0] x + R[a][1] y) + R[a][2] z + t[a], and rounded to fp32 once; fgoicp_mesh_distance on device 0.  A mesh without area
+// is refused by the call: exit code 1, the key named.
+static void write_deviation(const cli::Config& c, const DeviationMesh& m, const std::vector<icp::vec3>& src, const float* R9, const float* t3, const std::string& prefix) {
+    if (c.io.deviation.empty()) return;
+    std::vector<icp::vec3> moved(src.size());
+    for (size_t i = 0; i < src.size(); ++i) {
+        const double x = src[i].x, y = src[i].y, z = src[i].z;
+        float q[3];
+        for (int a = 0; a < 3; ++a) q[a] = (float)((((double)R9[a] * x + (double)R9[3 + a] * y) + (double)R9[6 + a] * z) + (double)t3[a]);
+        moved[i] = icp::vec3{q[0], q[1], q[2]};
+    }
+    std::vector<uint32_t> face(src.size());
+    std::vector<double> dist2(src.size());
+    std::vector<uint8_t> region(src.size());
+    std::vector<int8_t> side(src.size());
+    fgoicp_mesh_distance_info_t mi{};
+    mi.struct_size = sizeof(mi);
+    const int rc = fgoicp_mesh_distance(&m.vertices.data()->x, m.vertices.size(), m.triangles.data(), m.triangles.size() / 3, &moved.data()->x, moved.size(), 0u, 0, face.data(),
+                                        nullptr, dist2.data(), region.data(), side.data(), &mi);
+    if (rc != FGOICP_OK) {
+        icp::Logger(icp::LogLevel::Error) << "io.deviation = \"" << c.io.deviation << "\": status " << rc << ": " << fgoicp_last_error();
+        std::exit(1);
+    }
+    const cli::DeviationSummary s = cli::summarize_deviation(mi, dist2.data(), side.data());
+    cli::write_deviation_txt(c.io.deviation, src, face.data(), dist2.data(), side.data(), region.data(), s);
+    icp::Logger(icp::LogLevel::Info) << prefix << "Deviation (source -> target mesh): " << s.points << " points, " << s.triangles << " triangles (" << s.zero_area
+                                     << " zero-area), rms " << s.rms << ", max " << s.max;
+}
+
 // params.target_voxel / params.source_voxel: the loaded cloud replaced by the centroids of its voxel grid (fgoicp_voxel_downsample on device 0,
 // the origin is the cloud's own minimum), once, before any solver exists: everything downstream sees the thinned cloud.  A refused size
 // (too small for the cloud's extent, not finite) is an error of the configuration: reported, exit code 1.
@@ -244,6 +291,8 @@ static int run_batch(const std::string& list_file) {
     }
     const size_t n = configs.size();
     std::vector<std::vector<icp::vec3>> pct(n), pcs(n);
+    std::vector<DeviationMesh> meshes(n);
+    for (size_t i = 0; i < n; ++i) load_deviation_mesh(configs[i], meshes[i]);
     std::vector<fgoicp_batch_pair> pairs(n);
     std::vector<float> trim(n);
     for (size_t i = 0; i < n; ++i) {
@@ -352,6 +401,7 @@ static int run_batch(const std::string& list_file) {
             else icp::check_status(fgoicp_batch_information(b, (int)i, &inf), "fgoicp_batch_information");
             cli::write_information_txt(c.io.information, inf, c.params.information_distance);
         }
+        write_deviation(c, meshes[i], pcs[i], have_refined ? refined.R : &R9[9 * i], have_refined ? refined.t : &t3[3 * i], "Pair " + std::to_string(i) + ": ");
     }
     fgoicp_batch_destroy(b);
     return rc;
@@ -397,6 +447,8 @@ int main(int argc, char* argv[]) {
             std::exit(1);
         }
     }();
+    DeviationMesh deviation_mesh;
+    load_deviation_mesh(config, deviation_mesh);
     std::vector<icp::vec3> pct, pcs;
     load_input(config.io.target, config.params.target_subsample, config.params.target_mesh_points, config.params.seed, config.params.seed, pct, "target");
     icp::Logger(icp::LogLevel::Info) << "Target point cloud (" << pct.size() << ") loaded from " << config.io.target;
@@ -542,5 +594,6 @@ int main(int argc, char* argv[]) {
     if (!config.io.output.empty()) cli::write_result_toml(config.io.output, R, t, best_error, pcs_in.size(), elapsed_seconds.count(), st, have_refined ? &refined : nullptr, gicp ? "gicp_rmse" : "plane_rmse",
                                                               have_robust ? &robust : nullptr, config.params.refine_loss.c_str());
     if (!config.io.visualization.empty()) cli::write_visualization_ply(config.io.visualization, pct_in, pcs_in, R, t);
+    write_deviation(config, deviation_mesh, pcs_in, have_refined ? refined.R : R.data(), have_refined ? refined.t : &t.x, "");  // once, on the host thread (rank 0's pose is every rank's)
     return 0;
 }

@@ -1,11 +1,11 @@
-// The frame of a one-shot call (voxel.hip, outlier.hip, fps.hip, cluster.hip, segment.hip, mesh.hip; DESIGN.md section 13, "The one-shot pattern").
+// The frame of a one-shot call (voxel.hip, outlier.hip, fps.hip, cluster.hip, segment.hip, mesh.hip, mesh_distance.hip; DESIGN.md section 13, "The one-shot pattern").
 // One call = one stream + one device allocation of its own, both released before it returns; no fgoicp_ctx, no global state, no knobs.
 //   OneShot, ONECHK      what the call owns on the device; a failed HIP call ends it
 //   refuse_*, select_device    the refusals every call shares (they need no device), then the device
 //   write_info                 an extensible info struct back to the caller
 //   Arena (arena.hpp)          every device array of the call in one allocation
 //   scan_flags_async, kept_rows, scatter_rows_async   stable compaction by a flag per point: the kept rows in caller order
-// Everything here has internal linkage: each of the six translation units carries its own copy, the kernel included.
+// Everything here has internal linkage: each of the seven translation units carries its own copy, the kernel included.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -86,7 +86,7 @@ void write_info(Info* out, Info& full) {
 }
 
 // ---- stable compaction: flag[i] != 0 keeps point i; row[i] = the exclusive scan of the flags, the number of kept points before i.
-// Templates on the flag word (deduced; uint32_t at every call), so that a file that compacts nothing — fps.hip, voxel.hip, mesh.hip — carries neither
+// Templates on the flag word (deduced; uint32_t at every call), so that a file that compacts nothing — fps.hip, voxel.hip, mesh.hip, mesh_distance.hip — carries neither
 // the scatter kernel nor rocPRIM's scan kernels.
 constexpr int kRowsBlock = 256;
 

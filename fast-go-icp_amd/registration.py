@@ -182,6 +182,54 @@ def sample_mesh_even(vertices, triangles, m, init_factor=5, seed=0, device=0, re
     return out, nrm[idx], face[idx], idx, info
 
 
+def mesh_distance(vertices, triangles, points, device=0, return_map=False, brute=False):
+    """fgoicp_mesh_distance: the distance from every point to the SURFACE of the triangle mesh (vertices (nv, 3) float32, triangles (nf, 3)
+    vertex indices) as an (nq,) float64 array, sqrt(dist2).  return_map=True returns (dist, face (nq,) uint32 — the nearest face, the lowest
+    index among equally near ones —, closest (nq, 3) float32, region (nq,) uint8 — 0 interior, 1 / 2 / 3 edge ab / bc / ca, 4 / 5 / 6 vertex
+    a / b / c —, side (nq,) int8 — the side of the winning face's plane, weak where region != 0 —, info) with info = dict(flags, vertices,
+    triangles, queries, faces, zero_area, tree_depth, leaf_faces, max_dist2, max_dist2_index, dist2 (nq,) float64).  brute=True tests every
+    face for every point without the tree and returns the same bytes."""
+    v, t = _mesh(vertices, triangles)
+    q = _cloud(points)
+    nv, nf, nq = len(v), len(t), len(q)
+    dist2 = np.empty(nq, np.float64)
+    face = np.empty(nq, np.uint32) if return_map else None
+    closest = np.empty((nq, 3), np.float32) if return_map else None
+    region = np.empty(nq, np.uint8) if return_map else None
+    side = np.empty(nq, np.int8) if return_map else None
+    ptr = lambda a, ty: None if a is None else a.ctypes.data_as(ty)
+    info = _lib.MeshDistanceInfo()
+    _lib.check(_lib.load().fgoicp_mesh_distance(_fp(v) if nv else None, nv, ptr(t, _lib.c_uint32_p) if nf else None, nf, _fp(q) if nq else None, nq,
+                                                _lib.MESH_DISTANCE_BRUTE if brute else 0, int(device), ptr(face, _lib.c_uint32_p), ptr(closest, _lib.c_float_p),
+                                                ptr(dist2, _lib.c_double_p), ptr(region, _lib.c_uint8_p), ptr(side, C.POINTER(C.c_int8)), C.byref(info)), "fgoicp_mesh_distance")
+    dist = np.sqrt(dist2)
+    if not return_map:
+        return dist
+    return dist, face, closest, region, side, dict(flags=int(info.flags), vertices=int(info.vertices), triangles=int(info.triangles), queries=int(info.queries),
+                                                   faces=int(info.faces), zero_area=int(info.zero_area), tree_depth=int(info.tree_depth), leaf_faces=int(info.leaf_faces),
+                                                   max_dist2=float(info.max_dist2), max_dist2_index=int(info.max_dist2_index), dist2=dist2)
+
+
+def mesh_deviation(vertices, triangles, source, R, t, device=0, return_map=False, brute=False):
+    """mesh_distance of R p + t for every source point p: the deviation of a registered scan from the model's surface — what follows
+    FastGoICP.run() or refine_plane() against a mesh's samples.  The moved points are formed in fp64 on the host, per axis
+    (R[a, 0]*x + R[a, 1]*y) + R[a, 2]*z + t[a], and rounded to fp32 once."""
+    p = _cloud(source).astype(np.float64)
+    Rm, tv = np.asarray(R, np.float64).reshape(3, 3), np.asarray(t, np.float64).reshape(3)
+    moved = np.stack([((Rm[a, 0] * p[:, 0] + Rm[a, 1] * p[:, 1]) + Rm[a, 2] * p[:, 2]) + tv[a] for a in range(3)], 1).astype(np.float32)
+    return mesh_distance(vertices, triangles, moved, device=device, return_map=return_map, brute=brute)
+
+
+def point_triangle(p, a, b, c):
+    """fgoicp_point_triangle (host only): the closest point of the triangle (a, b, c) to p in the arithmetic the kernel runs —
+    (closest (3,) float32, dist2 float64, region int, side int)."""
+    x = [np.ascontiguousarray(v, dtype=np.float32).reshape(3) for v in (p, a, b, c)]
+    closest = np.empty(3, np.float32)
+    d2, region, side = C.c_double(), C.c_int(), C.c_int()
+    _lib.check(_lib.load().fgoicp_point_triangle(_fp(x[0]), _fp(x[1]), _fp(x[2]), _fp(x[3]), _fp(closest), C.byref(d2), C.byref(region), C.byref(side)), "fgoicp_point_triangle")
+    return closest, np.float64(d2.value), int(region.value), int(side.value)
+
+
 def cluster_dbscan(points, eps, min_points=10, keep_min_size=0, device=0, return_map=False):
     """fgoicp_cluster_dbscan: density clustering of the cloud (a point is core when at least min_points points, itself included, lie within
     eps; clusters are the connected components of the core points, numbered by their lowest index; a border point joins its nearest core

@@ -879,6 +879,65 @@ typedef struct fgoicp_mesh_info_t {
 int fgoicp_mesh_sample(const float* vertices_nv3, size_t nv, const uint32_t* triangles_nf3, size_t nf, size_t m, uint64_t seed, int device,
                        float* points_m3, float* normals_m3_or_NULL, uint32_t* face_m_or_NULL, double* uv_m2_or_NULL,
                        double* face_area_nf_or_NULL, fgoicp_mesh_info_t* info);
+/*
+ * EXTENSION — the distance from points to a triangle mesh on the device (no reference counterpart; Open3D: RaycastingScene
+ * compute_closest_points / compute_distance, CloudCompare: cloud-to-mesh distance).  After a registration against a model's samples this
+ * is the deviation of every scan point from the model's SURFACE, not from its nearest sample.
+ *
+ * Inputs: nv vertices (fp32 xyz), nf triangles (uint32 triples), nq query points (fp32 xyz).  ALL arithmetic is IEEE fp64 on the fp32 values
+ * converted to double, every operation rounded once in the order written, nothing contracted, divisions are divisions.
+ * dot(x, y) = (x0*y0 + x1*y1) + x2*y2.
+ *   closest point of (a, b, c) to p — the seven regions of Ericson (Real-Time Collision Detection 5.1.5), in his order:
+ *     1  ab = b - a, ac = c - a, ap = p - a, d1 = dot(ab, ap), d2 = dot(ac, ap);  d1 <= 0 && d2 <= 0: vertex a
+ *     2  bp = p - b, d3 = dot(ab, bp), d4 = dot(ac, bp);  d3 >= 0 && d4 <= d3: vertex b
+ *     3  vc = d1*d4 - d3*d2;  vc <= 0 && d1 >= 0 && d3 <= 0: edge ab at a + (d1 / (d1 - d3)) * ab
+ *     4  cp = p - c, d5 = dot(ab, cp), d6 = dot(ac, cp);  d6 >= 0 && d5 <= d6: vertex c
+ *     5  vb = d5*d2 - d1*d6;  vb <= 0 && d2 >= 0 && d6 <= 0: edge ac at a + (d2 / (d2 - d6)) * ac
+ *     6  va = d3*d6 - d5*d4;  va <= 0 && d4 - d3 >= 0 && d5 - d6 >= 0: edge bc at b + ((d4 - d3) / ((d4 - d3) + (d5 - d6))) * (c - b)
+ *     7  s = (va + vb) + vc, v = vb / s, w = vc / s;  s > 0 && v >= 0 && w >= 0 && v + w <= 1: the interior at (a + v*ab) + w*ac
+ *     A quotient of steps 3, 5, 6 whose denominator is 0 is taken as 0 (the edge's first vertex).  When step 7's condition fails — a
+ *     sliver whose va, vb, vc are rounding noise: s <= 0, a quotient that is not finite or weights outside the triangle — the answer is
+ *     the nearest of the three edges taken as segments x -> y, in the order ab, bc, ca: e = y - x, num = dot(e, p - x), den = dot(e, e);
+ *     not (num > 0): vertex x; not (num < den): vertex y; otherwise x + (num / den) * e on the edge; the smallest dist2 wins, a tie goes to
+ *     the lowest region code.  Every branch returns a point whose computed weights lie inside the triangle.
+ *   region   0 interior, 1 / 2 / 3 edge ab / bc / ca, 4 / 5 / 6 vertex a / b / c
+ *   dist2    (dx*dx + dy*dy) + dz*dz of p - closest, with the fp64 closest point;  closest is returned rounded to fp32 once per axis
+ *   side     the sign (-1, 0, +1) of dot(n, p - closest), n = ab x ac as fgoicp_mesh_sample forms it.  This is the side of the WINNING
+ *            FACE'S PLANE, not an inside / outside test of the mesh: where region != 0 (the closest point lies on an edge or a vertex) the
+ *            face's plane says little about the surface around it and the sign is weak
+ *   faces left out   a face whose n2 is 0 under fgoicp_mesh_sample's formula takes no part (counted in zero_area); a mesh without any
+ *            other face is refused, "the mesh has no area"
+ *   winner   per query the smallest (dist2, face index) over the participating faces: among equal dist2 — a query on a shared edge or
+ *            vertex, or midway between two faces — the lowest face index.  A total order: the result is a function of the inputs alone,
+ *            two calls return the same bytes, and FGOICP_MESH_DISTANCE_BRUTE (every query against every face, no tree) returns them too
+ * Outputs per query, every array may be NULL: face_nq, closest_nq3, dist2_nq, region_nq, side_nq.  info->max_dist2 is the largest dist2
+ * and max_dist2_index the lowest query index that attains it.
+ * Refused with FGOICP_ERR_INVALID_ARG before any device work (one host pass over the inputs): null or empty vertices, triangles or
+ * queries, nv, nf or nq at or above 2^31, a null `info` or a struct_size that is 0, ends before `max_dist2` ends or is above 4096, an
+ * unknown flag bit, a non-finite vertex or query coordinate (the message names it), a triangle index >= nv (the message names the face
+ * and the index), a device ordinal out of range; and once the device is chosen: "the mesh has no area".  No usable device:
+ * FGOICP_ERR_NO_DEVICE (no CPU fallback); allocation failure: FGOICP_ERR_OOM.  The call owns its stream and its one device allocation (40
+ * bytes per participating face, 6 to 12 per face for the tree's boxes, 36 to 54 per query plus the sort's storage; no vertex array) and frees both before it returns; it touches no
+ * fgoicp_ctx, no global state and no knob and may be called from several threads.
+ */
+enum { FGOICP_MESH_DISTANCE_BRUTE = 1 };  /* flags bit 0: no tree — the on-device checker of the walk and the baseline of its timings */
+typedef struct fgoicp_mesh_distance_info_t {
+    uint32_t struct_size;        /* IN: sizeof(fgoicp_mesh_distance_info_t) as the CALLER was compiled; no byte beyond it is written, 0 is refused */
+    uint32_t flags;              /* as given */
+    uint64_t vertices, triangles, queries;  /* nv, nf, nq */
+    uint64_t faces;              /* the faces that take part: triangles - zero_area */
+    uint64_t zero_area;          /* faces with n2 == 0 */
+    uint32_t tree_depth;         /* levels below the root: 2^tree_depth >= the number of leaves */
+    uint32_t leaf_faces;         /* faces per leaf */
+    uint64_t max_dist2_index;
+    double   max_dist2;
+} fgoicp_mesh_distance_info_t;
+int fgoicp_mesh_distance(const float* vertices_nv3, size_t nv, const uint32_t* triangles_nf3, size_t nf, const float* queries_nq3, size_t nq,
+                         uint32_t flags, int device, uint32_t* face_nq, float* closest_nq3, double* dist2_nq, uint8_t* region_nq, int8_t* side_nq,
+                         fgoicp_mesh_distance_info_t* info);
+/* The arithmetic the kernel runs on one (point, triangle) pair, on the host (no device needed; csrc/device/point_triangle.hpp is the one
+ * text of both).  Every output may be NULL.  Refuses null inputs and a coordinate that is not finite. */
+int fgoicp_point_triangle(const float* p3, const float* a3, const float* b3, const float* c3, float* closest3, double* dist2, int* region, int* side);
 /* EXTENSION: given normals at solver level — fgoicp_ctx_set_target_normals / fgoicp_ctx_set_source_normals with the pointer, on the solver's
  * context (nt / ns triples in the order the clouds were passed to fgoicp_solver_create, normalised on upload; normals are invariant under
  * the solver's centring and uniform scale).  A mesh knows its normals exactly (fgoicp_mesh_sample).  fgoicp_solver_refine_plane / _gicp /
