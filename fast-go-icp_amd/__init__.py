@@ -9,7 +9,7 @@ from . import _lib, build, nodes, synth  # noqa: F401
 from ._lib import (FLAG_BRUTE_FORCE_NN, FLAG_CURVE_ORDER, FLAG_NO_MORTON, FLAG_NO_WEIGHT_QUANT, FLAG_PROFILE, SCHEDULE_ROUND, SCHEDULE_SERIAL, TRANSPORT_IN_PROCESS,  # noqa: F401
                    TRANSPORT_RCCL, FgoicpError, dev_knobs, live_resources)
 from .registration import (Alignment, GicpRefinement, Information, IterativeClosestPoint3D, PlaneMomentsResult, PlaneRefinement, Registration, RobustMomentsResult, RobustRefinement, StreamPool, cloud_stats, cluster_dbscan, icp_batch,  # noqa: F401
-                           farthest_point_sample, gicp_terms, information_from_moments, mesh_deviation, mesh_distance, plane_apply_step, plane_step_from_moments, point_triangle, remove_radius_outliers, remove_statistical_outliers, robust_weight, segment_fit_from_moments,
+                           farthest_point_sample, gicp_terms, information_from_moments, mesh_deviation, mesh_distance, mesh_moments, mesh_pair_terms, refine_to_mesh, MeshMomentsResult, MeshRefinement, plane_apply_step, plane_step_from_moments, point_triangle, remove_radius_outliers, remove_statistical_outliers, robust_weight, segment_fit_from_moments,
                            sample_mesh, sample_mesh_even, segment_hypotheses, segment_planes, voxel_downsample, SEGMENT_CHUNK, SEGMENT_TILE)
 from .nodes import Rotation, RotNode, TransNode, from_glm, to_glm  # noqa: F401
 

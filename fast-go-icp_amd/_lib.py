@@ -218,6 +218,26 @@ class MeshDistanceInfo(C.Structure):
         self.struct_size = C.sizeof(MeshDistanceInfo)  # the library writes no byte beyond it
 
 
+class MeshMoments(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("points", C.c_uint64), ("correspondences", C.c_uint64), ("m", C.c_double * 28), ("weight_sum", C.c_double),
+                ("sum_dist2", C.c_double), ("max_dist2", C.c_double), ("loss", C.c_int), ("scale", C.c_double), ("vertices", C.c_uint64), ("triangles", C.c_uint64),
+                ("faces", C.c_uint64), ("zero_area", C.c_uint64), ("tree_depth", C.c_uint32), ("leaf_faces", C.c_uint32)]
+
+    def __init__(self):
+        super().__init__()
+        self.struct_size = C.sizeof(MeshMoments)  # the library writes no byte beyond it
+
+
+class MeshRefineResult(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("R", C.c_float * 9), ("t", C.c_float * 3), ("iterations", C.c_int), ("rank", C.c_int), ("points", C.c_uint64),
+                ("correspondences", C.c_uint64), ("weight_sum", C.c_double), ("mesh_rmse", C.c_double), ("rms_distance", C.c_double), ("loss", C.c_int),
+                ("scale_estimated", C.c_int), ("loss_scale", C.c_double), ("triangles", C.c_uint64), ("faces", C.c_uint64), ("zero_area", C.c_uint64)]
+
+    def __init__(self):
+        super().__init__()
+        self.struct_size = C.sizeof(MeshRefineResult)  # the library writes no byte beyond it
+
+
 MESH_DISTANCE_BRUTE = 1
 
 OUTLIER_STATISTICAL = 0
@@ -254,6 +274,12 @@ _SIGS = {
     "fgoicp_mesh_distance": (C.c_int, [c_float_p, C.c_size_t, c_uint32_p, C.c_size_t, c_float_p, C.c_size_t, C.c_uint32, C.c_int, c_uint32_p, c_float_p, c_double_p, c_uint8_p,
                                        C.POINTER(C.c_int8), C.POINTER(MeshDistanceInfo)]),
     "fgoicp_point_triangle": (C.c_int, [c_float_p, c_float_p, c_float_p, c_float_p, c_float_p, C.POINTER(C.c_double), c_int_p, c_int_p]),
+    "fgoicp_mesh_pair_terms": (C.c_int, [c_float_p, c_float_p, c_float_p, c_float_p, C.c_int, C.c_double, c_double_p, c_double_p, c_int_p, c_double_p, c_double_p, c_double_p,
+                                         c_double_p]),
+    "fgoicp_mesh_moments": (C.c_int, [c_float_p, C.c_size_t, c_uint32_p, C.c_size_t, c_float_p, C.c_size_t, c_float_p, c_float_p, C.c_float, C.c_int, C.c_double, C.c_uint32,
+                                      C.c_int, c_uint32_p, c_float_p, c_double_p, c_uint8_p, c_double_p, c_double_p, c_double_p, c_uint8_p, c_uint32_p, C.POINTER(MeshMoments)]),
+    "fgoicp_mesh_refine": (C.c_int, [c_float_p, C.c_size_t, c_uint32_p, C.c_size_t, c_float_p, C.c_size_t, c_float_p, c_float_p, C.c_size_t, C.c_float, C.c_float, C.c_int,
+                                     C.c_double, C.c_uint32, C.c_int, C.POINTER(MeshRefineResult)]),
     "fgoicp_solver_set_target_normals": (C.c_int, [C.c_void_p, c_float_p]),
     "fgoicp_solver_set_source_normals": (C.c_int, [C.c_void_p, c_float_p]),
     "fgoicp_lut_read": (C.c_int, [C.c_void_p, c_float_p, C.c_size_t]),

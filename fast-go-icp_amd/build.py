@@ -28,6 +28,7 @@ SOURCES = [
     os.path.join(CSRC, "device", "segment.hip"),
     os.path.join(CSRC, "device", "mesh.hip"),
     os.path.join(CSRC, "device", "mesh_distance.hip"),
+    os.path.join(CSRC, "device", "mesh_refine.hip"),
     os.path.join(CSRC, "host", "solver.cpp"),
     os.path.join(CSRC, "host", "multi.cpp"),
     os.path.join(CSRC, "host", "batch.cpp"),

@@ -121,7 +121,7 @@ struct Config {
         float trim_fraction = 0.0f;  // EXTENSION: > 0 enables trimmed Go-ICP; `trim` itself stays parsed-and-ignored as upstream
         int gpus = 1;                // EXTENSION: > 1 shards the outer BnB over that many GPUs of this node (one host thread each, RCCL)
         float information_distance = 0.0f;  // EXTENSION: distance threshold of io.information in the files' units (absent or 0: none)
-        std::string refine;          // EXTENSION: "plane" = point-to-plane refinement after the search (fgoicp_solver_refine_plane), "gicp" = Generalized ICP (fgoicp_solver_refine_gicp); absent or "": none; anything else is refused
+        std::string refine;          // EXTENSION: "plane" = point-to-plane refinement after the search (fgoicp_solver_refine_plane), "gicp" = Generalized ICP (fgoicp_solver_refine_gicp), "mesh" = point-to-mesh refinement against the target FILE's triangles (fgoicp_mesh_refine; refine_knn and refine_epsilon are ignored); absent or "": none; anything else is refused
         int refine_knn = 16;         // ... neighbours per target point for its normal (4 .. 32)
         int refine_max_iter = 30;
         float refine_distance = 0.0f;  // ... distance threshold in the files' units (absent or 0: none)
@@ -218,16 +218,16 @@ struct Config {
             params.refine_distance = (float)num("params", "refine_distance", 0.0);
             if (!(params.refine_distance > 0.0f)) params.refine_distance = 0.0f;
             params.refine_epsilon = num("params", "refine_epsilon", 1e-3);
-            if (!params.refine.empty() && params.refine != "plane" && params.refine != "gicp")  // (thrown, not exit(1): the callers report it; a typo must not silently skip the refinement)
-                throw std::invalid_argument("params.refine = \"" + params.refine + "\" is not supported: the refinements are \"plane\" and \"gicp\"");
-            if (!params.refine.empty() && (params.refine_knn < 4 || params.refine_knn > 32)) throw std::invalid_argument("params.refine_knn must lie in [4, 32]");
+            if (!params.refine.empty() && params.refine != "plane" && params.refine != "gicp" && params.refine != "mesh")  // (thrown, not exit(1): the callers report it; a typo must not silently skip the refinement)
+                throw std::invalid_argument("params.refine = \"" + params.refine + "\" is not supported: the refinements are \"plane\", \"gicp\" and \"mesh\"");
+            if (!params.refine.empty() && params.refine != "mesh" && (params.refine_knn < 4 || params.refine_knn > 32)) throw std::invalid_argument("params.refine_knn must lie in [4, 32]");
             if (params.refine == "gicp" && !(params.refine_epsilon > 0.0 && params.refine_epsilon <= 1.0)) throw std::invalid_argument("params.refine_epsilon must lie in (0, 1]");
             params.refine_loss = str("params", "refine_loss", "none");
             params.refine_loss_scale = num("params", "refine_loss_scale", 0.0);
             if (!(params.refine_loss_scale > 0.0) || !std::isfinite(params.refine_loss_scale)) params.refine_loss_scale = 0.0;
             if (params.refine_loss_code() < 0)
                 throw std::invalid_argument("params.refine_loss = \"" + params.refine_loss + "\" is not supported: the losses are \"none\", \"huber\", \"cauchy\", \"geman_mcclure\" and \"tukey\"");
-            if (params.refine_loss_code() > 0 && params.refine.empty()) throw std::invalid_argument("params.refine_loss needs params.refine (\"plane\" or \"gicp\")");
+            if (params.refine_loss_code() > 0 && params.refine.empty()) throw std::invalid_argument("params.refine_loss needs params.refine (\"plane\", \"gicp\" or \"mesh\")");
             params.target_voxel = (float)num("params", "target_voxel", 0.0);
             params.source_voxel = (float)num("params", "source_voxel", 0.0);
             if (std::isnan(params.target_voxel) || std::isnan(params.source_voxel)) throw std::invalid_argument("params.target_voxel and params.source_voxel must not be NaN");
@@ -534,10 +534,11 @@ inline size_t load_cloud(const std::string& filepath, float subsample, std::vect
 // io.output / io.visualization (declared by test/bunny.toml:10-11, unimplemented upstream)
 // refined (optional, EXTENSION: params.refine): a [refined] table behind the existing keys, which stay as they are; rmse_key names its
 // residual — plane_rmse for "plane", gicp_rmse for "gicp".  robust (optional, EXTENSION: params.refine_loss): loss, loss_scale (the files'
-// units) and weight_sum behind the table's keys
+// units) and weight_sum behind the table's keys.  rms_distance (optional, EXTENSION: params.refine = "mesh"): the rms of the deviation map at
+// the refined pose, behind the residual (whose key is then mesh_rmse)
 inline void write_result_toml(const std::string& path, const icp::mat3& R, const icp::vec3& t, float sse, size_t ns, double seconds,
                               const fgoicp_run_stats& st, const fgoicp_plane_result_t* refined = nullptr, const char* rmse_key = "plane_rmse",
-                              const fgoicp_robust_result_t* robust = nullptr, const char* loss_name = "") {
+                              const fgoicp_robust_result_t* robust = nullptr, const char* loss_name = "", const double* rms_distance = nullptr) {
     std::ofstream f(path);
     if (!f) throw std::runtime_error("Unable to write " + path);
     f.precision(9);
@@ -553,7 +554,9 @@ inline void write_result_toml(const std::string& path, const icp::mat3& R, const
     f << "\n[refined]\nrotation = [\n";
     for (int r = 0; r < 3; ++r) f << "  [" << Q[r] << ", " << Q[3 + r] << ", " << Q[6 + r] << "],\n";
     f << "]\ntranslation = [" << refined->t[0] << ", " << refined->t[1] << ", " << refined->t[2] << "]\n";
-    f << rmse_key << " = " << refined->plane_rmse / (double)refined->scaling_factor << "\niterations = " << refined->iterations << "\nrank = " << refined->rank
+    f << rmse_key << " = " << refined->plane_rmse / (double)refined->scaling_factor;
+    if (rms_distance) f << "\nrms_distance = " << *rms_distance;
+    f << "\niterations = " << refined->iterations << "\nrank = " << refined->rank
       << "\ncorrespondences = " << refined->correspondences << "\n";
     if (!robust) return;
     f << "loss = \"" << loss_name << "\"\nloss_scale = " << robust->scale / (double)robust->scaling_factor << "\nweight_sum = " << robust->weight_sum << "\n";

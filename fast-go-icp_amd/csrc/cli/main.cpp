@@ -27,7 +27,8 @@ static std::string usage(const std::string& exe) {
 // One cloud of a run.  params.*_mesh_points off: cli::load_cloud, as ever.  On: the file is read as a triangle mesh (cli::load_mesh_ply) and
 // the cloud is that many samples of its surface (fgoicp_mesh_sample on device 0; the seed is params.seed if >= 0, else 0), then thinned by
 // *_subsample as a loaded cloud is: everything downstream sees the samples.  A TXT file, a PLY without faces and a mesh without area are
-// errors of the configuration: exit code 1.  The face normals are not carried through the filters: params.refine keeps estimating its own.
+// errors of the configuration: exit code 1.  The face normals are not carried through the filters: params.refine = "plane" / "gicp" keep estimating
+// their own ("mesh" refines against the file's triangles themselves, refine_to_mesh below).
 static void load_input(const std::string& path, float subsample, int mesh_points, long long load_seed, long long params_seed, std::vector<icp::vec3>& pc, const char* which) {
     if (mesh_points <= 0) {
         cli::load_cloud(path, subsample, pc, load_seed);
@@ -62,10 +63,12 @@ struct DeviationMesh {
     std::vector<icp::vec3> vertices;
     std::vector<uint32_t> triangles;
 };
+// params.refine = "mesh" needs the same mesh, read by the same loader at the same moment: without io.deviation the errors name that key.
+static std::string mesh_key(const cli::Config& c) { return c.io.deviation.empty() ? "params.refine = \"mesh\"" : "io.deviation = \"" + c.io.deviation + "\""; }
 static void load_deviation_mesh(const cli::Config& c, DeviationMesh& m) {
-    if (c.io.deviation.empty()) return;
+    if (c.io.deviation.empty() && c.params.refine != "mesh") return;
     auto fail = [&](const std::string& why) {
-        icp::Logger(icp::LogLevel::Error) << "io.deviation = \"" << c.io.deviation << "\": " << why;
+        icp::Logger(icp::LogLevel::Error) << mesh_key(c) << ": " << why;
         std::exit(1);
     };
     if (!cli::is_ply(c.io.target)) fail("the target " + c.io.target + " is not a PLY file: only a PLY holds a mesh");
@@ -244,20 +247,53 @@ static void plane_from_robust(const fgoicp_robust_result_t& robust, fgoicp_plane
     refined.plane_rmse = robust.rmse; refined.sse = robust.sse; refined.scaling_factor = robust.scaling_factor;
 }
 // the refinement's log line (a lone run's, or with a batch's "Pair i: " in front)
-static void log_refinement(const std::string& prefix, const cli::Config& config, const fgoicp_plane_result_t& refined, const fgoicp_robust_result_t* robust) {
+// rms_distance: params.refine = "mesh" (the rms of the deviation map at the refined pose; refined.plane_rmse then holds mesh_rmse)
+static void log_refinement(const std::string& prefix, const cli::Config& config, const fgoicp_plane_result_t& refined, const fgoicp_robust_result_t* robust,
+                           const double* rms_distance = nullptr) {
     const bool gicp = config.params.refine == "gicp";
     icp::mat3 Rr;
     std::memcpy(Rr.data(), refined.R, sizeof(refined.R));
     icp::Logger log(icp::LogLevel::Info);
-    log << prefix << (gicp ? "Generalized-ICP" : "Point-to-plane") << " refinement: " << refined.iterations << " iterations, rank " << refined.rank << ", "
-        << refined.correspondences << " correspondences, ";
-    if (gicp) log << "epsilon " << config.params.refine_epsilon << ", plane-to-plane RMSE ";
+    log << prefix << (rms_distance ? "Point-to-mesh" : gicp ? "Generalized-ICP" : "Point-to-plane") << " refinement: " << refined.iterations << " iterations, rank " << refined.rank
+        << ", " << refined.correspondences << " correspondences, ";
+    if (rms_distance) log << "rms distance " << *rms_distance << ", mesh RMSE ";
+    else if (gicp) log << "epsilon " << config.params.refine_epsilon << ", plane-to-plane RMSE ";
     else log << "plane RMSE ";
     log << refined.plane_rmse / (double)refined.scaling_factor;
     if (robust)
         log << ", " << config.params.refine_loss << " loss, scale " << robust->scale / (double)robust->scaling_factor << (robust->scale_estimated ? " (estimated)" : " (given)")
             << ", weight " << robust->weight_sum << " of " << robust->correspondences;
     log << "\n\tRotation:\n" << Rr << "\n\tTranslation: " << icp::vec3{refined.t[0], refined.t[1], refined.t[2]};
+}
+
+// params.refine = "mesh": the pose near (R9, t3) — the best transform, in the files' frame, which is the mesh's — that minimises the distances
+// from the source points the registration saw to the target FILE's triangles (fgoicp_mesh_refine on device 0; params.refine_max_iter,
+// refine_distance, refine_loss and refine_loss_scale apply, refine_knn and refine_epsilon do not).  The result as the [refined] table and
+// the log line take it: `refined` (plane_rmse holds mesh_rmse; the files' frame is the call's, so the scaling factor is 1) and, with a loss,
+// `robust`.  A refusal — a mesh without area among them — ends the run: exit code 1, the key named.
+static void refine_to_mesh(const cli::Config& c, const DeviationMesh& m, const std::vector<icp::vec3>& src, const float* R9, const float* t3, const std::string& prefix,
+                           fgoicp_plane_result_t& refined, fgoicp_robust_result_t& robust, double& rms_distance) {
+    fgoicp_mesh_refine_result_t r{};
+    r.struct_size = sizeof(r);
+    const int loss = c.params.refine_loss_code();
+    const int rc = fgoicp_mesh_refine(&m.vertices.data()->x, m.vertices.size(), m.triangles.data(), m.triangles.size() / 3, &src.data()->x, src.size(), R9, t3,
+                                      (size_t)c.params.refine_max_iter, 1e-6f, c.params.refine_distance, loss, c.params.refine_loss_scale, 0u, 0, &r);
+    if (rc != FGOICP_OK) {
+        icp::Logger(icp::LogLevel::Error) << "params.refine = \"mesh\": status " << rc << ": " << fgoicp_last_error();
+        std::exit(1);
+    }
+    refined = fgoicp_plane_result_t{};
+    refined.struct_size = sizeof(refined);
+    std::memcpy(refined.R, r.R, sizeof(refined.R));
+    std::memcpy(refined.t, r.t, sizeof(refined.t));
+    refined.iterations = r.iterations; refined.rank = r.rank; refined.correspondences = r.correspondences;
+    refined.plane_rmse = r.mesh_rmse; refined.scaling_factor = 1.0f;
+    robust = fgoicp_robust_result_t{};
+    robust.struct_size = sizeof(robust);
+    robust.correspondences = r.correspondences; robust.weight_sum = r.weight_sum; robust.scaling_factor = 1.0f;
+    robust.loss = r.loss; robust.scale_estimated = r.scale_estimated; robust.scale = r.loss_scale;
+    rms_distance = r.rms_distance;
+    log_refinement(prefix, c, refined, loss > 0 ? &robust : nullptr, &rms_distance);
 }
 
 // --batch LIST: every config of the list registered in one fgoicp_batch run; each config's io.output / io.visualization as a lone -c run
@@ -371,8 +407,14 @@ static int run_batch(const std::string& list_file) {
         const cli::Config& c = configs[i];
         fgoicp_plane_result_t refined{};
         fgoicp_robust_result_t robust{};
-        const bool have_refined = refine[i].model >= 0, have_robust = have_refined && refine[i].loss != FGOICP_LOSS_NONE;
-        if (have_robust) {
+        // params.refine = "mesh": not one of the batch's own refinements (its specs stay plane / gicp) — the one-shot call, here, as
+        // write_deviation below; io.information of such a config stays at the best transform (a batch keeps no context to ask at another pose)
+        const bool to_mesh = c.params.refine == "mesh", in_batch = refine[i].model >= 0;
+        const bool have_refined = in_batch || to_mesh, have_robust = have_refined && c.params.refine_loss_code() > 0;
+        double rms_distance = 0.0;
+        if (to_mesh) {
+            refine_to_mesh(c, meshes[i], pcs[i], &R9[9 * i], &t3[3 * i], "Pair " + std::to_string(i) + ": ", refined, robust, rms_distance);
+        } else if (have_robust) {
             robust.struct_size = sizeof(robust);
             icp::check_status(fgoicp_batch_refined_robust(b, (int)i, &robust), "fgoicp_batch_refined_robust");
             plane_from_robust(robust, refined);
@@ -380,10 +422,11 @@ static int run_batch(const std::string& list_file) {
             refined.struct_size = sizeof(refined);
             icp::check_status(fgoicp_batch_refined_plane(b, (int)i, &refined), "fgoicp_batch_refined_plane");
         }
-        if (have_refined) log_refinement("Pair " + std::to_string(i) + ": ", c, refined, have_robust ? &robust : nullptr);
+        if (in_batch) log_refinement("Pair " + std::to_string(i) + ": ", c, refined, have_robust ? &robust : nullptr);
         if (!c.io.output.empty())
-            cli::write_result_toml(c.io.output, R, t, best_error, pcs[i].size(), elapsed.count(), st, have_refined ? &refined : nullptr, c.params.refine == "gicp" ? "gicp_rmse" : "plane_rmse",
-                                   have_robust ? &robust : nullptr, c.params.refine_loss.c_str());
+            cli::write_result_toml(c.io.output, R, t, best_error, pcs[i].size(), elapsed.count(), st, have_refined ? &refined : nullptr,
+                                   to_mesh ? "mesh_rmse" : c.params.refine == "gicp" ? "gicp_rmse" : "plane_rmse", have_robust ? &robust : nullptr, c.params.refine_loss.c_str(),
+                                   to_mesh ? &rms_distance : nullptr);
         if (!c.io.visualization.empty()) cli::write_visualization_ply(c.io.visualization, pct[i], pcs[i], R, t);
         if (!c.io.alignment.empty()) {
             std::vector<uint32_t> idx(pcs[i].size());
@@ -397,7 +440,7 @@ static int run_batch(const std::string& list_file) {
         if (!c.io.information.empty()) {
             fgoicp_information_t inf{};
             inf.struct_size = sizeof(inf);
-            if (have_refined) icp::check_status(fgoicp_batch_refined_information(b, (int)i, &inf), "fgoicp_batch_refined_information");  // as a lone run: at the refined pose
+            if (in_batch) icp::check_status(fgoicp_batch_refined_information(b, (int)i, &inf), "fgoicp_batch_refined_information");  // as a lone run: at the refined pose
             else icp::check_status(fgoicp_batch_information(b, (int)i, &inf), "fgoicp_batch_information");
             cli::write_information_txt(c.io.information, inf, c.params.information_distance);
         }
@@ -502,7 +545,16 @@ int main(int argc, char* argv[]) {
     fgoicp_robust_result_t robust{};
     const int loss = config.params.refine_loss_code();
     bool have_robust = false;
+    // params.refine = "mesh": from the best transform too, against the target FILE's triangles; once, on the host thread
+    const bool to_mesh = config.params.refine == "mesh";
+    double rms_distance = 0.0;
     auto refine = [&](fgoicp_solver* s) {
+        if (to_mesh) {
+            refine_to_mesh(config, deviation_mesh, pcs_in, R.data(), &t.x, "", refined, robust, rms_distance);
+            have_refined = true;
+            have_robust = loss > 0;
+            return;
+        }
         if (config.params.refine != "plane" && !gicp) return;
         refined.struct_size = sizeof(refined);
         const float d = config.params.refine_distance > 0.0f ? config.params.refine_distance : INFINITY;
@@ -591,8 +643,8 @@ int main(int argc, char* argv[]) {
     }
     icp::Logger(icp::LogLevel::Debug) << "Subcubes: " << st.trans_cubes << ", rotation cubes: " << st.rot_cubes << ", ICP runs: " << st.icp_runs;
     icp::Logger(icp::LogLevel::Info) << "Fast Go-ICP finished, time elapsed: " << std::fixed << std::setprecision(3) << elapsed_seconds.count() << " seconds";
-    if (!config.io.output.empty()) cli::write_result_toml(config.io.output, R, t, best_error, pcs_in.size(), elapsed_seconds.count(), st, have_refined ? &refined : nullptr, gicp ? "gicp_rmse" : "plane_rmse",
-                                                              have_robust ? &robust : nullptr, config.params.refine_loss.c_str());
+    if (!config.io.output.empty()) cli::write_result_toml(config.io.output, R, t, best_error, pcs_in.size(), elapsed_seconds.count(), st, have_refined ? &refined : nullptr, to_mesh ? "mesh_rmse" : gicp ? "gicp_rmse" : "plane_rmse",
+                                                              have_robust ? &robust : nullptr, config.params.refine_loss.c_str(), to_mesh ? &rms_distance : nullptr);
     if (!config.io.visualization.empty()) cli::write_visualization_ply(config.io.visualization, pct_in, pcs_in, R, t);
     write_deviation(config, deviation_mesh, pcs_in, have_refined ? refined.R : R.data(), have_refined ? refined.t : &t.x, "");  // once, on the host thread (rank 0's pose is every rank's)
     return 0;

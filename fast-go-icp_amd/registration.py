@@ -230,6 +230,115 @@ def point_triangle(p, a, b, c):
     return closest, np.float64(d2.value), int(region.value), int(side.value)
 
 
+def _loss_args(loss, scale):
+    """(code, scale as a float; None -> 0)"""
+    return _loss_code(loss), 0.0 if scale is None else float(scale)
+
+
+def mesh_pair_terms(x, a, b, c, loss=None, scale=None):
+    """fgoicp_mesh_pair_terms (host only): what the moved point x contributes against the triangle (a, b, c) in the arithmetic the kernel
+    runs — dict(closest (3,) float64, dist2, region, g (3,) float64 — the direction —, s — the residual —, w — its weight —, v (28,)
+    float64 — the terms, times w when a loss is set)."""
+    p = [np.ascontiguousarray(v, dtype=np.float32).reshape(3) for v in (x, a, b, c)]
+    code, sc = _loss_args(loss, scale)
+    closest, g, v = np.empty(3, np.float64), np.empty(3, np.float64), np.empty(28, np.float64)
+    d2, s, w, region = C.c_double(), C.c_double(), C.c_double(), C.c_int()
+    dp = lambda arr: arr.ctypes.data_as(_lib.c_double_p)
+    _lib.check(_lib.load().fgoicp_mesh_pair_terms(_fp(p[0]), _fp(p[1]), _fp(p[2]), _fp(p[3]), code, sc, dp(closest), C.byref(d2), C.byref(region), dp(g), C.byref(s), C.byref(w),
+                                                  dp(v)), "fgoicp_mesh_pair_terms")
+    return dict(closest=closest, dist2=np.float64(d2.value), region=int(region.value), g=g, s=np.float64(s.value), w=np.float64(w.value), v=v)
+
+
+class MeshMomentsResult:
+    """EXTENSION (fgoicp_mesh_moments): m (28,) float64 in the layout of PlaneMomentsResult (JtJ, Jtr, sum_r2), points, correspondences,
+    weight_sum, sum_dist2, max_dist2 (the fp64 threshold compared with; inf: none), loss (name), scale, flags, vertices, triangles, faces,
+    zero_area, tree_depth, leaf_faces; rms_distance = sqrt(sum_dist2 / correspondences).  With return_map=True also, per source point in
+    caller order: face, closest (float32), dist2, region, direction, residual, weight, counted (bool), and order — slot k of the sums holds
+    the caller's point order[k]."""
+
+    def __init__(self, raw, per_point=None):
+        self.m = np.array(raw.m, np.float64)
+        self.points, self.correspondences = int(raw.points), int(raw.correspondences)
+        self.JtJ = np.zeros((6, 6))
+        self.JtJ[np.triu_indices(6)] = self.m[:21]
+        self.JtJ = self.JtJ + np.triu(self.JtJ, 1).T
+        self.Jtr, self.sum_r2 = self.m[21:27].copy(), float(self.m[27])
+        self.weight_sum, self.sum_dist2, self.max_dist2 = float(raw.weight_sum), float(raw.sum_dist2), float(raw.max_dist2)
+        self.rms_distance = float(np.sqrt(np.float64(raw.sum_dist2) / np.float64(self.correspondences))) if self.correspondences else 0.0
+        self.loss, self.scale, self.flags = LOSS_NAMES.get(int(raw.loss), int(raw.loss)), float(raw.scale), int(raw.flags)
+        self.vertices, self.triangles, self.faces, self.zero_area = int(raw.vertices), int(raw.triangles), int(raw.faces), int(raw.zero_area)
+        self.tree_depth, self.leaf_faces = int(raw.tree_depth), int(raw.leaf_faces)
+        self.raw = bytes(raw)  # the struct as the library filled it (two results of the same inputs are the same bytes)
+        for key, value in (per_point or {}).items():
+            setattr(self, key, value)
+
+
+def mesh_moments(vertices, triangles, source, R, t, max_distance=None, loss=None, loss_scale=None, device=0, return_map=False, brute=False):
+    """fgoicp_mesh_moments: ONE evaluation of the point-to-mesh normal equations at the pose (R (3, 3), t (3,)) in the mesh's frame — every
+    source point moved, its nearest triangle found (the search of mesh_distance), residual and direction taken from the exact closest
+    point — as a MeshMomentsResult.  max_distance (None or <= 0: none) leaves out the points farther from the surface; loss / loss_scale as
+    robust_weight.  plane_step_from_moments(r.correspondences, r.m) and plane_apply_step give the step and the pose it leads to."""
+    v, tr = _mesh(vertices, triangles)
+    p = _cloud(source)
+    nv, nf, ns = len(v), len(tr), len(p)
+    Rg, tt = to_glm(R), np.ascontiguousarray(t, np.float32).reshape(3)
+    code, sc = _loss_args(loss, loss_scale)
+    per = None
+    if return_map:
+        per = dict(face=np.empty(ns, np.uint32), closest=np.empty((ns, 3), np.float32), dist2=np.empty(ns, np.float64), region=np.empty(ns, np.uint8),
+                   direction=np.empty((ns, 3), np.float64), residual=np.empty(ns, np.float64), weight=np.empty(ns, np.float64), counted=np.empty(ns, np.uint8),
+                   order=np.empty(ns, np.uint32))
+    ptr = lambda key, ty: None if per is None else per[key].ctypes.data_as(ty)
+    raw = _lib.MeshMoments()
+    _lib.check(_lib.load().fgoicp_mesh_moments(_fp(v) if nv else None, nv, tr.ctypes.data_as(_lib.c_uint32_p) if nf else None, nf, _fp(p) if ns else None, ns, _fp(Rg), _fp(tt),
+                                               0.0 if max_distance is None else float(max_distance), code, sc, _lib.MESH_DISTANCE_BRUTE if brute else 0, int(device),
+                                               ptr("face", _lib.c_uint32_p), ptr("closest", _lib.c_float_p), ptr("dist2", _lib.c_double_p), ptr("region", _lib.c_uint8_p),
+                                               ptr("direction", _lib.c_double_p), ptr("residual", _lib.c_double_p), ptr("weight", _lib.c_double_p),
+                                               ptr("counted", _lib.c_uint8_p), ptr("order", _lib.c_uint32_p), C.byref(raw)), "fgoicp_mesh_moments")
+    if per is not None:
+        per["counted"] = per["counted"].astype(bool)
+    return MeshMomentsResult(raw, per)
+
+
+class MeshRefinement:
+    """EXTENSION (fgoicp_mesh_refine): R (3, 3), t (3,) — the refined pose in the mesh's frame; iterations; rank of the last solve (6: well
+    posed); points; correspondences counted at the returned pose; mesh_rmse = sqrt(sum w s^2 / sum w) there; rms_distance =
+    sqrt(sum dist2 / correspondences) there — the rms of mesh_deviation at (R, t) when no max_distance is set; weight_sum; loss (name);
+    loss_scale — the scale the loop ran with; scale_estimated; triangles, faces, zero_area of the mesh."""
+
+    def __init__(self, raw):
+        self.R, self.t = from_glm(np.array(raw.R, np.float32)), np.array(raw.t, np.float32)
+        self.iterations, self.rank, self.points, self.correspondences = int(raw.iterations), int(raw.rank), int(raw.points), int(raw.correspondences)
+        self.weight_sum, self.mesh_rmse, self.rms_distance = float(raw.weight_sum), float(raw.mesh_rmse), float(raw.rms_distance)
+        self.loss, self.loss_scale, self.scale_estimated = LOSS_NAMES.get(int(raw.loss), int(raw.loss)), float(raw.loss_scale), bool(raw.scale_estimated)
+        self.triangles, self.faces, self.zero_area = int(raw.triangles), int(raw.faces), int(raw.zero_area)
+        self.raw = bytes(raw)
+
+
+def refine_to_mesh(vertices, triangles, source, R, t, max_iter=30, conv_thr=1e-6, max_distance=None, loss=None, loss_scale=None, device=0, brute=False):
+    """fgoicp_mesh_refine: the pose near (R, t) that minimises the deviation map — the squared distances from the moved source points to the
+    SURFACE of the mesh — by Gauss-Newton steps over mesh_moments, as a MeshRefinement.  The tree is built and the points are sorted once;
+    an iteration is one kernel launch.  loss_scale None or <= 0 with a loss: estimated at the start pose.
+
+    After a registration against a mesh's samples the caller writes (poses in the frame of the files, which is the mesh's):
+
+        R, t = solver.run()                    # or fine = solver.refine_plane(); R, t = fine.R, fine.t
+        fine = fg.refine_to_mesh(V, T, source, R, t)
+        dist = fg.mesh_deviation(V, T, source, fine.R, fine.t)   # its rms is fine.rms_distance"""
+    v, tr = _mesh(vertices, triangles)
+    p = _cloud(source)
+    nv, nf, ns = len(v), len(tr), len(p)
+    if isinstance(max_iter, bool) or not isinstance(max_iter, (int, np.integer)) or max_iter < 0:
+        raise ValueError("max_iter must be a non-negative integer")
+    Rg, tt = to_glm(R), np.ascontiguousarray(t, np.float32).reshape(3)
+    code, sc = _loss_args(loss, loss_scale)
+    raw = _lib.MeshRefineResult()
+    _lib.check(_lib.load().fgoicp_mesh_refine(_fp(v) if nv else None, nv, tr.ctypes.data_as(_lib.c_uint32_p) if nf else None, nf, _fp(p) if ns else None, ns, _fp(Rg), _fp(tt),
+                                              int(max_iter), float(conv_thr), 0.0 if max_distance is None else float(max_distance), code, sc,
+                                              _lib.MESH_DISTANCE_BRUTE if brute else 0, int(device), C.byref(raw)), "fgoicp_mesh_refine")
+    return MeshRefinement(raw)
+
+
 def cluster_dbscan(points, eps, min_points=10, keep_min_size=0, device=0, return_map=False):
     """fgoicp_cluster_dbscan: density clustering of the cloud (a point is core when at least min_points points, itself included, lie within
     eps; clusters are the connected components of the core points, numbered by their lowest index; a border point joins its nearest core

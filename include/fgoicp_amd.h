@@ -938,6 +938,85 @@ int fgoicp_mesh_distance(const float* vertices_nv3, size_t nv, const uint32_t* t
 /* The arithmetic the kernel runs on one (point, triangle) pair, on the host (no device needed; csrc/device/point_triangle.hpp is the one
  * text of both).  Every output may be NULL.  Refuses null inputs and a coordinate that is not finite. */
 int fgoicp_point_triangle(const float* p3, const float* a3, const float* b3, const float* c3, float* closest3, double* dist2, int* region, int* side);
+/*
+ * EXTENSION — point-to-mesh refinement on the device (no reference counterpart; CloudCompare: fine registration of a cloud against a
+ * mesh): the pose that minimises the deviation map of fgoicp_mesh_distance itself.  The refinements above minimise residuals against the
+ * nearest SAMPLE of a model, with normals estimated from samples; this one takes the exact closest point of the nearest triangle and the
+ * exact direction of the distance field there, so the number minimised is the number the deviation map reports.
+ *
+ * Everything is IEEE fp64 on the fp32 inputs converted to double, every operation rounded once in the order written, nothing contracted;
+ * dot is fgoicp_mesh_distance's.  For a source point p and a pose (R9 in glm order, R[a][b] = R9[3 b + a]; t3), both in the mesh's frame:
+ *   moved point   x[a] = (float)((((double)R[a][0] px + (double)R[a][1] py) + (double)R[a][2] pz) + (double)t[a]) — rounded to fp32 once, so
+ *                 face, closest, dist2 and region of the point are, byte for byte, what fgoicp_mesh_distance returns for the query x
+ *   winner        fgoicp_mesh_distance's smallest (dist2, face index) over the faces with area; c = its fp64 closest point, d = x - c
+ *   direction g   region != 0 and dist2 > 0 (off an edge or a vertex): g = d / sqrt(dist2) per axis, the gradient of the distance field;
+ *                 otherwise g = n / sqrt(n2) per axis, n = ab x ac and n2 = (nx nx + ny ny) + nz nz as fgoicp_mesh_sample forms them: the
+ *                 face's unit normal
+ *   residual      s = dot(g, d); for an interior closest point s = +- sqrt(dist2) up to rounding
+ *   counted       max_distance <= 0: every point; otherwise the points with dist2 <= (double)max_distance * (double)max_distance.  No
+ *                 trimming, no context
+ *   weight        w = the w(s) of fgoicp_robust_weight at (loss, scale); with FGOICP_LOSS_NONE w = 1 and nothing is multiplied by it
+ *   terms         J = [ (x cross g)^T, g^T ] with the fp64 value of the fp32 x; the 28 terms in the layout and order of
+ *                 fgoicp_plane_moments_t::m — the upper triangle of J^T J row by row (21), J^T s (6), s s (1) — each times w when weighted;
+ *                 so fgoicp_plane_step_from_moments and fgoicp_plane_apply_step serve unchanged
+ *   sums          the 28 terms, weight_sum = sum w and sum_dist2 = sum dist2 over the counted points, each added in a fixed order: the
+ *                 points sorted once by (a 30-bit Z-order code of the SOURCE point inside the source's box, caller index) — the stable sort
+ *                 of fgoicp_mesh_distance, a function of the source alone — then the order of fgoicp_plane_moments over those slots.  Two
+ *                 calls return the same bytes, and FGOICP_MESH_DISTANCE_BRUTE (flags bit 0: no tree) returns them too.
+ */
+/* Host only, no device: the arithmetic of ONE (moved point, triangle) pair, the text the kernel runs.  x3: the moved point; every output may
+ * be NULL: closest3 (fp64), dist2, region, g3, s, w, v28 (the 28 terms, times w unless the loss is FGOICP_LOSS_NONE).  Refuses null inputs, a
+ * coordinate that is not finite, an unknown loss, a scale that is not finite and > 0 (FGOICP_LOSS_NONE ignores the scale) and a triangle
+ * without area (n2 == 0: it takes no part in a mesh). */
+int fgoicp_mesh_pair_terms(const float* x3, const float* a3, const float* b3, const float* c3, int loss, double scale, double* closest3, double* dist2, int* region,
+                           double* g3, double* s, double* w, double* v28);
+typedef struct fgoicp_mesh_moments_t {
+    uint32_t struct_size;             /* IN: sizeof(fgoicp_mesh_moments_t) as the CALLER was compiled; no byte beyond it is written, 0 is refused */
+    uint32_t flags;                   /* as given */
+    uint64_t points, correspondences; /* ns; the counted points N (a zero weight still counts) */
+    double   m[28];                   /* the layout of fgoicp_plane_moments_t */
+    double   weight_sum;              /* sum w over the counted (FGOICP_LOSS_NONE: == correspondences) */
+    double   sum_dist2;               /* sum dist2 over the counted */
+    double   max_dist2;               /* the fp64 threshold the device compared dist2 with; +inf: none */
+    int      loss;
+    double   scale;                   /* as given */
+    uint64_t vertices, triangles;     /* nv, nf */
+    uint64_t faces, zero_area;        /* as fgoicp_mesh_distance_info_t */
+    uint32_t tree_depth, leaf_faces;
+} fgoicp_mesh_moments_t;
+/* One evaluation at (R9, t3).  Optional per-point outputs in caller order, ns entries each, any may be NULL: face, closest (fp32, 3 per
+ * point), dist2, region, direction (3 doubles per point), residual, weight, counted (0 / 1); order_ns: the sorted order — slot k of the
+ * sums holds the caller's point order_ns[k].  An uncounted point gets residual, weight and counted 0; its other outputs are still its own.
+ * Refuses what fgoicp_mesh_distance refuses (the source points are its queries) and a non-finite pose, max_distance or scale, an unknown
+ * loss, a loss with a scale that is not finite and > 0 — all before any device work.  One-shot as fgoicp_mesh_distance: its own stream and
+ * one device allocation (that call's for the mesh; 28 bytes per point, 248 per 256 points, 66 more per point when a per-point output is asked
+ * for; the sort's storage), nothing left behind. */
+int fgoicp_mesh_moments(const float* vertices_nv3, size_t nv, const uint32_t* triangles_nf3, size_t nf, const float* points_ns3, size_t ns, const float* R9, const float* t3,
+                        float max_distance, int loss, double scale, uint32_t flags, int device, uint32_t* face_ns, float* closest_ns3, double* dist2_ns, uint8_t* region_ns,
+                        double* direction_ns3, double* residual_ns, double* weight_ns, unsigned char* counted_ns, uint32_t* order_ns, fgoicp_mesh_moments_t* out);
+typedef struct fgoicp_mesh_refine_result_t {
+    uint32_t struct_size;             /* IN: sizeof(fgoicp_mesh_refine_result_t) as the CALLER was compiled; no byte beyond it is written, 0 is refused */
+    float    R[9], t[3];              /* the refined pose, in the mesh's frame */
+    int      iterations;              /* steps taken */
+    int      rank;                    /* of the last solve (0 when max_iter = 0, nothing was counted or every weight was zero) */
+    uint64_t points, correspondences; /* ns; counted at the returned pose */
+    double   weight_sum;              /* sum w at the returned pose */
+    double   mesh_rmse;               /* sqrt(sum w s^2 / sum w) at the returned pose (0 when the weight sum is 0) */
+    double   rms_distance;            /* sqrt(sum_dist2 / correspondences) there (0 when nothing is counted): the rms of the deviation map */
+    int      loss;
+    int      scale_estimated;         /* 1: the scale was estimated at the start pose, 0: it was given (or there is no loss) */
+    double   loss_scale;              /* the scale the loop ran with (0 without a loss) */
+    uint64_t triangles, faces, zero_area;
+} fgoicp_mesh_refine_result_t;
+/* The loop of fgoicp_icp_plane / fgoicp_icp_robust, term for term, over these moments: evaluate, fgoicp_plane_step_from_moments,
+ * fgoicp_plane_apply_step; it ends after a step with |w| + |v| < conv_thr, after the first step when that solve had rank < 6, when nothing
+ * is counted or the weights sum to 0, or after max_iter steps; the result's sums are those of one more evaluation at the pose returned.
+ * The tree is built, the points are uploaded and sorted ONCE per call; an iteration is one kernel, one fold and one 248-byte copy.
+ * loss_scale <= 0 with a loss: estimated once at the start pose, 1.4826 * the lower median of |s| over the counted points (as
+ * fgoicp_robust_scale); refused, the message saying to pass a scale, when nothing is counted or that median is 0.  Refuses what
+ * fgoicp_mesh_moments refuses (a scale <= 0 asks for the estimate) and a non-finite conv_thr. */
+int fgoicp_mesh_refine(const float* vertices_nv3, size_t nv, const uint32_t* triangles_nf3, size_t nf, const float* points_ns3, size_t ns, const float* R0_9, const float* t0_3,
+                       size_t max_iter, float conv_thr, float max_distance, int loss, double loss_scale, uint32_t flags, int device, fgoicp_mesh_refine_result_t* out);
 /* EXTENSION: given normals at solver level — fgoicp_ctx_set_target_normals / fgoicp_ctx_set_source_normals with the pointer, on the solver's
  * context (nt / ns triples in the order the clouds were passed to fgoicp_solver_create, normalised on upload; normals are invariant under
  * the solver's centring and uniform scale).  A mesh knows its normals exactly (fgoicp_mesh_sample).  fgoicp_solver_refine_plane / _gicp /
