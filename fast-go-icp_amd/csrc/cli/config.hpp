@@ -114,7 +114,7 @@ struct Config {
     struct IO { std::string target, source, output, visualization, alignment, information, deviation; } io;  // alignment, information, deviation: EXTENSION, optional (write_alignment_txt, write_information_txt, write_deviation_txt)
     struct Params {
         bool trim = false;
-        float target_subsample = 1.0f, source_subsample = 1.0f, lut_resolution = 0.005f, mse_threshold = 1e-3f;
+        float lut_resolution = 0.005f, mse_threshold = 1e-3f;
         long long seed = -1;       // < 0: std::random_device, as the reference (utilities.hpp:149-150)
         std::string schedule = "serial";
         int round_width = 1;
@@ -134,33 +134,36 @@ struct Config {
                 if (refine_loss == names[k]) return k;
             return -1;
         }
-        float target_voxel = 0.0f, source_voxel = 0.0f;  // EXTENSION: voxel size in the files' units; the cloud is replaced by its voxel grid's centroids (fgoicp_voxel_downsample) after loading; absent or <= 0: off, NaN is refused
-        // EXTENSION: outlier removal per cloud after the voxel grid (fgoicp_remove_outliers).  *_outlier_knn: the neighbours, absent or <= 0: off;
-        // *_outlier_std: the statistical filter's std ratio; *_outlier_radius (the files' units) > 0: the radius filter in place of the statistical one.
-        // A value that is not a number is refused.
-        int target_outlier_knn = 0, source_outlier_knn = 0;
-        float target_outlier_std = 2.0f, source_outlier_std = 2.0f, target_outlier_radius = 0.0f, source_outlier_radius = 0.0f;
-        // EXTENSION: farthest-point sampling per cloud after the outlier filter (fgoicp_farthest_point_sample, start_index 0): the number of points the
-        // cloud is brought down to; absent or <= 0: off; a cloud that has no more points stays as it is.  A value that is not an integer is refused.
-        int target_points = 0, source_points = 0;
-        // EXTENSION: density clustering per cloud after the outlier filter and before the sampling (fgoicp_cluster_dbscan).  *_cluster_eps: the
-        // radius in the files' units, absent or <= 0: off; *_cluster_min_points: the neighbours (the point included) that make a point core;
-        // *_cluster_min_size: 0 keeps the largest cluster, >= 1 every cluster of at least that many points.  A value that is not a number is refused.
-        float target_cluster_eps = 0.0f, source_cluster_eps = 0.0f;
-        int target_cluster_min_points = 10, source_cluster_min_points = 10;
-        int target_cluster_min_size = 0, source_cluster_min_size = 0;
-        // EXTENSION: the dominant planes of a cloud removed after the outlier filter and before the clustering (fgoicp_segment_planes: the table
-        // under the object, the floor of the room).  *_plane_distance: the inlier distance in the files' units, absent or <= 0: off;
-        // *_plane_iterations: the hypotheses per plane; *_plane_count: the planes at most; *_plane_min_fraction: a plane needs at least
-        // ceil(fraction x points) inliers.  A value that is not a number is refused.
-        float target_plane_distance = 0.0f, source_plane_distance = 0.0f;
-        int target_plane_iterations = 1000, source_plane_iterations = 1000;
-        int target_plane_count = 1, source_plane_count = 1;
-        double target_plane_min_fraction = 0.1, source_plane_min_fraction = 0.1;
-        // EXTENSION: mesh input (fgoicp_mesh_sample).  *_mesh_points: the cloud becomes that many samples of the SURFACE of the file's triangle
-        // mesh (a PLY with faces) in place of its vertices, before everything that sees the loaded cloud, *_subsample included; absent or <= 0:
-        // off.  A value that is not an integer is refused.
-        int target_mesh_points = 0, source_mesh_points = 0;
+        // The keys a cloud has of its own: params.target_<field> and params.source_<field>, read by the same rules (cloud_keys in the
+        // constructor) and applied in the stage order of csrc/cli/prepare.hpp.
+        struct Cloud {
+            float subsample = 1.0f;  // utilities.hpp:101-104: clamped to [1e-5, 1], the source's to [1e-5, 0.5]
+            // EXTENSION: mesh input (fgoicp_mesh_sample).  *_mesh_points: the cloud becomes that many samples of the SURFACE of the file's triangle
+            // mesh (a PLY with faces) in place of its vertices, before everything that sees the loaded cloud, *_subsample included; absent or <= 0:
+            // off.  A value that is not an integer is refused.
+            int mesh_points = 0;
+            float voxel = 0.0f;  // EXTENSION: voxel size in the files' units; the cloud is replaced by its voxel grid's centroids (fgoicp_voxel_downsample) after loading; absent or <= 0: off, NaN is refused
+            // EXTENSION: outlier removal per cloud after the voxel grid (fgoicp_remove_outliers).  *_outlier_knn: the neighbours, absent or <= 0: off;
+            // *_outlier_std: the statistical filter's std ratio; *_outlier_radius (the files' units) > 0: the radius filter in place of the statistical one.
+            // A value that is not a number is refused.
+            int outlier_knn = 0;
+            float outlier_std = 2.0f, outlier_radius = 0.0f;
+            // EXTENSION: the dominant planes of a cloud removed after the outlier filter and before the clustering (fgoicp_segment_planes: the table
+            // under the object, the floor of the room).  *_plane_distance: the inlier distance in the files' units, absent or <= 0: off;
+            // *_plane_iterations: the hypotheses per plane; *_plane_count: the planes at most; *_plane_min_fraction: a plane needs at least
+            // ceil(fraction x points) inliers.  A value that is not a number is refused.
+            float plane_distance = 0.0f;
+            int plane_iterations = 1000, plane_count = 1;
+            double plane_min_fraction = 0.1;
+            // EXTENSION: density clustering per cloud after the outlier filter and before the sampling (fgoicp_cluster_dbscan).  *_cluster_eps: the
+            // radius in the files' units, absent or <= 0: off; *_cluster_min_points: the neighbours (the point included) that make a point core;
+            // *_cluster_min_size: 0 keeps the largest cluster, >= 1 every cluster of at least that many points.  A value that is not a number is refused.
+            float cluster_eps = 0.0f;
+            int cluster_min_points = 10, cluster_min_size = 0;
+            // EXTENSION: farthest-point sampling per cloud after the outlier filter (fgoicp_farthest_point_sample, start_index 0): the number of points the
+            // cloud is brought down to; absent or <= 0: off; a cloud that has no more points stays as it is.  A value that is not an integer is refused.
+            int points = 0;
+        } target, source;
     } params;
 
     explicit Config(const std::string& toml_filepath) {
@@ -201,8 +204,6 @@ struct Config {
         auto clampf0 = [](float x) { return x < 0.0f ? 0.0f : (x > 0.9f ? 0.9f : x); };
         if (tbl.count("params")) {
             params.trim = boolean("params", "trim", false);
-            params.target_subsample = (float)num("params", "target_subsample", 1.0);
-            params.source_subsample = (float)num("params", "source_subsample", 1.0);
             params.lut_resolution = (float)num("params", "lut_resolution", 0.005);
             params.mse_threshold = (float)num("params", "mse_threshold", 1e-3);
             params.seed = (long long)num("params", "seed", -1);
@@ -228,55 +229,47 @@ struct Config {
             if (params.refine_loss_code() < 0)
                 throw std::invalid_argument("params.refine_loss = \"" + params.refine_loss + "\" is not supported: the losses are \"none\", \"huber\", \"cauchy\", \"geman_mcclure\" and \"tukey\"");
             if (params.refine_loss_code() > 0 && params.refine.empty()) throw std::invalid_argument("params.refine_loss needs params.refine (\"plane\", \"gicp\" or \"mesh\")");
-            params.target_voxel = (float)num("params", "target_voxel", 0.0);
-            params.source_voxel = (float)num("params", "source_voxel", 0.0);
-            if (std::isnan(params.target_voxel) || std::isnan(params.source_voxel)) throw std::invalid_argument("params.target_voxel and params.source_voxel must not be NaN");
-            auto strict = [&](const char* key, double def) {  // as num, but a key that is present and not a number is an error of the configuration
+            auto strict = [&](const std::string& key, double def) {  // as num, but a key that is present and not a number is an error of the configuration
                 auto k = tbl["params"].find(key);
-                if (k != tbl["params"].end() && k->second.kind != TomlValue::Number) throw std::invalid_argument(std::string("params.") + key + " must be a number");
-                const double v = num("params", key, def);
-                if (std::isnan(v)) throw std::invalid_argument(std::string("params.") + key + " must not be NaN");
+                if (k != tbl["params"].end() && k->second.kind != TomlValue::Number) throw std::invalid_argument("params." + key + " must be a number");
+                const double v = num("params", key.c_str(), def);
+                if (std::isnan(v)) throw std::invalid_argument("params." + key + " must not be NaN");
                 return v;
             };
             auto knn = [](double v) { return v >= 1.0 ? (v > 1e6 ? 1000000 : (int)v) : 0; };
-            params.target_outlier_knn = knn(strict("target_outlier_knn", 0.0));
-            params.source_outlier_knn = knn(strict("source_outlier_knn", 0.0));
-            params.target_outlier_std = (float)strict("target_outlier_std", 2.0);
-            params.source_outlier_std = (float)strict("source_outlier_std", 2.0);
-            params.target_outlier_radius = (float)strict("target_outlier_radius", 0.0);
-            params.source_outlier_radius = (float)strict("source_outlier_radius", 0.0);
-            auto count = [&](const char* key) {  // as strict, and the number must be an integer; <= 0: off
+            auto count = [&](const std::string& key) {  // as strict, and the number must be an integer; <= 0: off
                 const double v = strict(key, 0.0);
-                if (v != std::floor(v)) throw std::invalid_argument(std::string("params.") + key + " must be an integer");
+                if (v != std::floor(v)) throw std::invalid_argument("params." + key + " must be an integer");
                 return v >= 1.0 ? (v > 2147483647.0 ? 2147483647 : (int)v) : 0;
             };
-            params.target_points = count("target_points");
-            params.source_points = count("source_points");
-            params.target_mesh_points = count("target_mesh_points");
-            params.source_mesh_points = count("source_mesh_points");
-            params.target_cluster_eps = (float)strict("target_cluster_eps", 0.0);
-            params.source_cluster_eps = (float)strict("source_cluster_eps", 0.0);
-            auto whole = [&](const char* key, double def) {  // as strict, and the number must be an integer; the call judges its range
+            auto whole = [&](const std::string& key, double def) {  // as strict, and the number must be an integer; the call judges its range
                 const double v = strict(key, def);
-                if (v != std::floor(v)) throw std::invalid_argument(std::string("params.") + key + " must be an integer");
+                if (v != std::floor(v)) throw std::invalid_argument("params." + key + " must be an integer");
                 return v > 2147483647.0 ? 2147483647 : (v < -2147483647.0 ? -2147483647 : (int)v);
             };
-            params.target_cluster_min_points = whole("target_cluster_min_points", 10.0);
-            params.source_cluster_min_points = whole("source_cluster_min_points", 10.0);
-            params.target_cluster_min_size = count("target_cluster_min_size");
-            params.source_cluster_min_size = count("source_cluster_min_size");
-            params.target_plane_distance = (float)strict("target_plane_distance", 0.0);
-            params.source_plane_distance = (float)strict("source_plane_distance", 0.0);
-            params.target_plane_iterations = whole("target_plane_iterations", 1000.0);
-            params.source_plane_iterations = whole("source_plane_iterations", 1000.0);
-            params.target_plane_count = whole("target_plane_count", 1.0);
-            params.source_plane_count = whole("source_plane_count", 1.0);
-            params.target_plane_min_fraction = strict("target_plane_min_fraction", 0.1);
-            params.source_plane_min_fraction = strict("source_plane_min_fraction", 0.1);
+            auto cloud_keys = [&](const std::string& side, Params::Cloud& c) {  // side: "target_" / "source_"
+                c.subsample = (float)num("params", (side + "subsample").c_str(), 1.0);
+                c.voxel = (float)num("params", (side + "voxel").c_str(), 0.0);
+                c.outlier_knn = knn(strict(side + "outlier_knn", 0.0));
+                c.outlier_std = (float)strict(side + "outlier_std", 2.0);
+                c.outlier_radius = (float)strict(side + "outlier_radius", 0.0);
+                c.points = count(side + "points");
+                c.mesh_points = count(side + "mesh_points");
+                c.cluster_eps = (float)strict(side + "cluster_eps", 0.0);
+                c.cluster_min_points = whole(side + "cluster_min_points", 10.0);
+                c.cluster_min_size = count(side + "cluster_min_size");
+                c.plane_distance = (float)strict(side + "plane_distance", 0.0);
+                c.plane_iterations = whole(side + "plane_iterations", 1000.0);
+                c.plane_count = whole(side + "plane_count", 1.0);
+                c.plane_min_fraction = strict(side + "plane_min_fraction", 0.1);
+            };
+            cloud_keys("target_", params.target);
+            cloud_keys("source_", params.source);
+            if (std::isnan(params.target.voxel) || std::isnan(params.source.voxel)) throw std::invalid_argument("params.target_voxel and params.source_voxel must not be NaN");
             auto clampf = [](float x, float lo, float hi) { return x < hi ? (x > lo ? x : lo) : hi; };
-            params.target_subsample = clampf(params.target_subsample, 1e-5f, 1.0f);  // utilities.hpp:101-104
-            params.source_subsample = clampf(params.source_subsample, 1e-5f, 1.0f);
-            params.source_subsample = clampf(params.source_subsample, 1e-5f, 0.5f);
+            params.target.subsample = clampf(params.target.subsample, 1e-5f, 1.0f);  // utilities.hpp:101-104
+            params.source.subsample = clampf(params.source.subsample, 1e-5f, 1.0f);
+            params.source.subsample = clampf(params.source.subsample, 1e-5f, 0.5f);
             params.mse_threshold = clampf(params.mse_threshold, 1e-12f, INFINITY);
         }
         icp::Logger(icp::LogLevel::Info) << *this;
@@ -289,8 +282,8 @@ struct Config {
            << "\t\tSource: " << c.io.source << "\n"
            << "\tParameters:\n"
            << "\t\tTrim: " << (c.params.trim ? "true" : "false") << "\n"
-           << "\t\tTarget Subsample: " << c.params.target_subsample << "\n"
-           << "\t\tSource Subsample: " << c.params.source_subsample << "\n"
+           << "\t\tTarget Subsample: " << c.params.target.subsample << "\n"
+           << "\t\tSource Subsample: " << c.params.source.subsample << "\n"
            << "\t\tLUT Resolution: " << c.params.lut_resolution << "\n"
            << "\t\tMSE Threshold: " << c.params.mse_threshold;
         return os;

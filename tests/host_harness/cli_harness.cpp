@@ -25,8 +25,8 @@ int cli_parse_config(const char* path, CliConfigOut* out) {
         std::snprintf(out->visualization, sizeof(out->visualization), "%s", c.io.visualization.c_str());
         std::snprintf(out->schedule, sizeof(out->schedule), "%s", c.params.schedule.c_str());
         out->trim = c.params.trim;
-        out->target_subsample = c.params.target_subsample;
-        out->source_subsample = c.params.source_subsample;
+        out->target_subsample = c.params.target.subsample;
+        out->source_subsample = c.params.source.subsample;
         out->lut_resolution = c.params.lut_resolution;
         out->mse_threshold = c.params.mse_threshold;
         out->seed = c.params.seed;

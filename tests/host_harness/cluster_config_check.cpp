@@ -10,8 +10,8 @@ int main(int argc, char** argv) {
     if (argc != 2) return 3;
     try {
         cli::Config c(argv[1]);
-        std::printf("CLUSTER %.9g %.9g %d %d %d %d\n", c.params.target_cluster_eps, c.params.source_cluster_eps, c.params.target_cluster_min_points,
-                    c.params.source_cluster_min_points, c.params.target_cluster_min_size, c.params.source_cluster_min_size);
+        std::printf("CLUSTER %.9g %.9g %d %d %d %d\n", c.params.target.cluster_eps, c.params.source.cluster_eps, c.params.target.cluster_min_points,
+                    c.params.source.cluster_min_points, c.params.target.cluster_min_size, c.params.source.cluster_min_size);
         return 0;
     } catch (const std::exception& e) {
         std::printf("REFUSED %s\n", e.what());

@@ -10,7 +10,7 @@ int main(int argc, char** argv) {
     if (argc != 2) return 3;
     try {
         cli::Config c(argv[1]);
-        std::printf("POINTS %d %d\n", c.params.target_points, c.params.source_points);
+        std::printf("POINTS %d %d\n", c.params.target.points, c.params.source.points);
         return 0;
     } catch (const std::exception& e) {
         std::printf("REFUSED %s\n", e.what());

@@ -15,7 +15,7 @@ int main(int argc, char** argv) {
     try {
         if (!std::strcmp(argv[1], "config")) {
             cli::Config c(argv[2]);
-            std::printf("MESH_POINTS %d %d\n", c.params.target_mesh_points, c.params.source_mesh_points);
+            std::printf("MESH_POINTS %d %d\n", c.params.target.mesh_points, c.params.source.mesh_points);
             return 0;
         }
         std::vector<icp::vec3> v;

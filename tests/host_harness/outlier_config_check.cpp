@@ -10,8 +10,8 @@ int main(int argc, char** argv) {
     if (argc != 2) return 3;
     try {
         cli::Config c(argv[1]);
-        std::printf("OUTLIER %d %d %.9g %.9g %.9g %.9g\n", c.params.target_outlier_knn, c.params.source_outlier_knn, c.params.target_outlier_std, c.params.source_outlier_std,
-                    c.params.target_outlier_radius, c.params.source_outlier_radius);
+        std::printf("OUTLIER %d %d %.9g %.9g %.9g %.9g\n", c.params.target.outlier_knn, c.params.source.outlier_knn, c.params.target.outlier_std, c.params.source.outlier_std,
+                    c.params.target.outlier_radius, c.params.source.outlier_radius);
         return 0;
     } catch (const std::exception& e) {
         std::printf("REFUSED %s\n", e.what());

@@ -10,9 +10,9 @@ int main(int argc, char** argv) {
     if (argc != 2) return 3;
     try {
         cli::Config c(argv[1]);
-        std::printf("SEGMENT %.9g %.9g %d %d %d %d %.17g %.17g\n", c.params.target_plane_distance, c.params.source_plane_distance, c.params.target_plane_iterations,
-                    c.params.source_plane_iterations, c.params.target_plane_count, c.params.source_plane_count, c.params.target_plane_min_fraction,
-                    c.params.source_plane_min_fraction);
+        std::printf("SEGMENT %.9g %.9g %d %d %d %d %.17g %.17g\n", c.params.target.plane_distance, c.params.source.plane_distance, c.params.target.plane_iterations,
+                    c.params.source.plane_iterations, c.params.target.plane_count, c.params.source.plane_count, c.params.target.plane_min_fraction,
+                    c.params.source.plane_min_fraction);
         return 0;
     } catch (const std::exception& e) {
         std::printf("REFUSED %s\n", e.what());
